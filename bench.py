@@ -1,12 +1,23 @@
 #!/usr/bin/env python
 """bench.py -- particle-updates/s of the PIPs inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3] [--no-extras] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--dump-outputs DIR]
+                    [--full [--no-extras] [--no-cpu-baseline] [--no-stage-profile]]
 
 One "step" = one whole ``Pips.forward`` (encoder + 6 update iterations) over one batch of
 synthetic clips already resident in HBM.  Workload = BASELINE.json configs[1]:
 B=1 clip per GPU, S=8 frames, 368x496, N=256 particles, I=6 iterations, fp32, stride 8,
 seeded random-init weights (the reference checkpoint is not obtainable offline).
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line.  Everything
+else listed below (split-bf16 figures, stage profile, roofline, the other configs, the PyTorch-ROCm
+and CPU baselines, the multi-rank collective and config3 legs) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, the arrays the timed path returned in its last step are
+written as DIR/<name>.npy (float32); inputs and weights are seeded, so two builds compare output
+for output.  Config 2/3: coord_predictions [I,B,S,N,2], coord_predictions2 [I+4,B,S,N,2], vis_e
+[B,S,N] (+ trajs_e_gathered / vis_e_gathered, the all-gathered result, with --gpus N > 1; rank 0
+writes).  Config 4: trajs_e [B,S,N,2], vis_e [B,S,N].
 
 --gpus N > 1: one process per GPU, clips sharded on the batch axis (weak scaling), one RCCL
 all-gather of the final [x,y,vis] per step.  Launched by ``python -m torch.distributed.run``
@@ -16,6 +27,7 @@ itself under torch.distributed.run with N ranks.  WORLD_SIZE != N is an error.
 Prints ONE JSON line (rank 0): the driver contract plus
   "ms_per_step_median"  -- median of the per-step durations between HIP events recorded around every timed step (the
                            contract's ms_per_step / value stay the wall-clock bracket over all K steps);
+and with --full:
   "roofline"            -- dominant kernel (fp32-MFMA GEMM of the mixer) vs the 157.3 TF fp32 peak,
                            timed live with HIP events on the launch stream (any number of ranks: measured on rank 0);
   "config3"             -- BASELINE configs[2] (bf16 operands): "weak" = B=8 clips per GPU, "strong" = B=64 clips in total
@@ -68,6 +80,26 @@ def make_inputs(rank, device, b, h=H, w=W, n=NPTS):
     rgbs = torch.randint(0, 256, (b, S, 3, h, w), generator=g).float()
     xys = torch.rand(b, n, 2, generator=g) * torch.tensor([w - 1.0, h - 1.0])
     return xys.to(device), rgbs.to(device)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: one step's outputs as float32 DIR/<name>.npy; a list of per-iteration tensors is stacked on a new
+    leading axis.  Every workload's outputs are a few MB at most: past the limit this fails instead of truncating."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, v in outputs.items():
+        t = torch.stack(list(v)) if isinstance(v, (list, tuple)) else v
+        arrays[name] = t.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def ev_time_ms(fn, reps):
@@ -573,9 +605,14 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stage-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config 3/4/5 legs and the torch-ROCm baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: split-bf16, stage profile and roofline, the config 3/4/5 "
+                         "legs, the torch-ROCm and CPU baselines (multi-rank: roofline, collective, config3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-stage-profile", action="store_true", help="with --full: skip split-bf16, stage profile and roofline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the config 3/4/5 legs and the torch-ROCm baseline")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4),
                     help="2 (default, the headline: B=1/GPU fp32), 3 (B=8/GPU, bf16 MFMA operands) or 4 (BASELINE configs[3]: "
                          "B=4 720x1280 N=4096 fp32 -- with --gpus N the PARTICLES are sharded over the ranks on replicated maps, "
@@ -668,30 +705,38 @@ def main(argv=None):
     enc4 = args.encode if (world > 1 and S % world == 0 and not fake) else "replicate"       # (the CPU stand-in has no pyramid to exchange)
 
     def step():
+        """One step; returns what a caller of the timed path receives, by name (--dump-outputs)."""
         if args.config == 4:          # particles sharded over the ranks on replicated maps + one gather on the particle axis
-            return pdist.track_sharded_particles(model, xys, rgbs, iters=ITERS, encode=enc4)
-        preds, _, vis, _ = model(xys, rgbs, iters=ITERS)
+            trajs, vis = pdist.track_sharded_particles(model, xys, rgbs, iters=ITERS, encode=enc4)
+            return {"trajs_e": trajs, "vis_e": vis}
+        preds, preds2, vis, _ = model(xys, rgbs, iters=ITERS)
+        out = {"coord_predictions": preds, "coord_predictions2": preds2, "vis_e": vis}
         if world > 1:
-            pdist.all_gather_result(preds[-1], vis)
-        return preds
+            out["trajs_e_gathered"], out["vis_e_gathered"] = pdist.all_gather_result(preds[-1], vis)
+        return out
 
     on_dev = backend == "nccl" and not fake
 
     def timed_steps(nsteps):
         """The contract's bracket (barrier + synchronize, wall clock over exactly nsteps steps, max over ranks) and, beside
-        it, one HIP event per step boundary on the launch stream -> per-step durations (median reported)."""
+        it, one HIP event per step boundary on the launch stream -> per-step durations (median reported).  Also returns
+        the last step's outputs (only that one is held, so earlier steps free theirs as before)."""
         if world > 1:
             dist.barrier()
         sync()
         evs = [] if fake else [torch.cuda.Event(enable_timing=True) for _ in range(nsteps + 1)]
         marks = []
+        last = None
         t0 = time.perf_counter()
         for i in range(nsteps):
             if fake:
                 marks.append(time.perf_counter())
             else:
                 evs[i].record()
-            step()
+            if i + 1 < nsteps:
+                step()
+            else:
+                last = step()
         if fake:
             marks.append(time.perf_counter())
         else:
@@ -702,11 +747,16 @@ def main(argv=None):
         dt = _max_over_ranks(time.perf_counter() - t0, world, device, on_dev)
         per = ([(b - a) * 1e3 for a, b in zip(marks[:-1], marks[1:])] if fake else
                [evs[i].elapsed_time(evs[i + 1]) for i in range(nsteps)])
-        return dt, per
+        return dt, per, last
 
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     for _ in range(args.warmup):
         step()
-    dt, per_step = timed_steps(args.steps)
+    dt, per_step, last_out = timed_steps(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out)
+    del last_out
 
     npts = 16 if fake else NPTS
     updates = world * b_per_gpu * S * npts * ITERS * args.steps
@@ -752,13 +802,13 @@ def main(argv=None):
         res["data"] = "PIPS_BENCH_FAKE=1: CPU stand-in model, launcher/collective self-test only -- not a measurement"
     main_cfg = args.config == 2 and args.matmul == "exact"
     headline = rank == 0 and world == 1 and main_cfg and not fake
-    if headline and not args.no_stage_profile:
+    if headline and args.full and not args.no_stage_profile:
         # the same workload on the fp32-grade split-bf16 matrix path (Pips.matmul = "split"; passes the
         # same fp32 parity gates, tests/test_forward_gpu.py) -- reported beside the exact-fp32 headline
         model.matmul = "split"
         for _ in range(args.warmup):
             step()
-        dts, per_s = timed_steps(args.steps)
+        dts, per_s, _ = timed_steps(args.steps)
         model.matmul = "exact"
         res["split_bf16"] = {"value": updates / dts, "unit": "particle-updates/s", "ms_per_step": dts / args.steps * 1e3,
                              "ms_per_step_median": statistics.median(per_s),
@@ -771,7 +821,7 @@ def main(argv=None):
         res["stages_ms"] = stages
         flop_per_update = 72.2e6
         res["forward_mfma_frac"] = res["value"] / world * flop_per_update / (PEAK_F32_MFMA_TF * 1e12)
-    if world > 1 and main_cfg and not args.no_extras:
+    if world > 1 and main_cfg and args.full and not args.no_extras:
         # A multi-rank line still describes the workload it scales: the dominant kernel's roofline (rank 0, in situ), the
         # exchange alone, and BASELINE configs[2] -- the multi-GPU config -- weak (8 clips per GPU) and strong (64 clips).
         if not fake and rank == 0:
@@ -782,7 +832,7 @@ def main(argv=None):
             res["config3"] = config3_leg(device, world, rank, fake, on_dev)
         except Exception as e:                                       # (every rank raises alike: shapes and code are identical)
             res["config3"] = {"error": f"{type(e).__name__}: {e}"}
-    if headline and not args.no_extras:
+    if headline and args.full and not args.no_extras:
         for name, leg in (("config3", config3_leg), ("config4", config4_leg), ("config5", config5_leg),
                           ("torch_rocm_baseline", torch_rocm_baseline)):
             try:
@@ -791,7 +841,7 @@ def main(argv=None):
             except Exception as e:                                   # a leg must not take the headline down
                 res[name] = {"error": f"{type(e).__name__}: {e}"}
         torch.cuda.empty_cache()
-    if headline and not args.no_cpu_baseline:
+    if headline and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(res), flush=True)

@@ -90,3 +90,19 @@ def make_chain_inputs(case: dict = CHAIN_CASE, seed: int = 11):
     video = torch.cat([(base * (1 - 0.04 * t) + 9.0 * t).clamp(0, 255).round() for t in range(T)], dim=1)
     xy0 = torch.rand(1, N, 2, generator=g) * torch.tensor([W - 17.0, H - 17.0]) + 8.0
     return video, xy0
+
+
+# a fresh seed beside CASES (tests/test_oracle_golden.py::test_oracle_equals_live_reference): raw weights, two iterations
+FRESH_CASE = dict(B=1, N=9, H=128, W=160, stride=8, iters=2, tamed=False)
+FRESH_SEED = 7
+
+
+def make_score_map_inputs(seed: int = 4):
+    """(fcps (B,S,I,N,H8,W8) heat maps, trajs_g in map pixels -- some outside the map --, vis_g, valids) for
+    score_map_loss (nets/pips.py:58-92)."""
+    g = torch.Generator().manual_seed(seed)
+    fcps = torch.randn(2, 8, 3, 5, 12, 16, generator=g) * 3
+    tg = torch.rand(2, 8, 5, 2, generator=g) * torch.tensor([18.0, 14.0]) - 1.0
+    vg = (torch.rand(2, 8, 5, generator=g) > 0.3).float()
+    va = (torch.rand(2, 8, 5, generator=g) > 0.1).float()
+    return fcps, tg, vg, va

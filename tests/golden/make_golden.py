@@ -1,6 +1,6 @@
 """Generate the golden vectors by running the UNMODIFIED reference (build container only).
 
-    python tests/golden/make_golden.py              (--windows: only the Pips(S != 8) cases)
+    python tests/golden/make_golden.py              (--windows: only the Pips(S != 8) cases; --fresh: main_fresh)
 
 For every case of cases.py: load seeded weights into /root/reference/nets/pips.py's Pips,
 run forward on the seeded inputs, store coord_predictions / vis_e / ffeat as float32 in
@@ -96,7 +96,28 @@ def main_losses(name="s8_raw_i3"):
     print(name, "losses: seq", float(seq), "vis", float(vis), "ce", float(ce))
 
 
+def main_fresh():
+    """The reference on cases.FRESH_CASE (outputs -> fresh_s7_raw_i2.npz) and its score_map_loss on
+    cases.make_score_map_inputs() (-> score_map_loss_s4.npz): the stored side of the two oracle tests that compared
+    with the reference live."""
+    assert R.available(), "reference not mounted"
+    case = G.FRESH_CASE
+    sd = init_state_dict(0, tamed=case["tamed"])
+    xys, rgbs, _, _ = G.make_inputs(case, seed=G.FRESH_SEED)
+    ref = R.load_reference_pips(sd, stride=case["stride"])
+    with torch.no_grad():
+        p, p2, vis, ff, _ = ref(xys, rgbs, iters=case["iters"], return_feat=True)
+    np.savez_compressed(os.path.join(HERE, "fresh_s7_raw_i2.npz"), trajs=torch.stack(p).numpy(), trajs2=torch.stack(p2).numpy(),
+                        vis=vis.numpy(), ffeat=ff.numpy())
+    loss = R.reference_module().score_map_loss(*G.make_score_map_inputs())
+    np.savez_compressed(os.path.join(HERE, "score_map_loss_s4.npz"), loss=np.float32(loss))
+    print("fresh_s7_raw_i2 trajs", tuple(torch.stack(p).shape), "score_map_loss", float(loss))
+
+
 if __name__ == "__main__":
+    if "--fresh" in sys.argv:                # only the fresh-seed forward and the score_map_loss value
+        main_fresh()
+        sys.exit(0)
     if "--demo-full" in sys.argv:            # only BASELINE configs[0] at its own size
         assert R.available(), "reference not mounted at /root/reference"
         make_demo_frames()

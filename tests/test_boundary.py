@@ -83,45 +83,59 @@ def test_reference_import_path_resolves_to_the_hip_model():
     assert nets.pips.Pips is pips_amd.Pips
 
 
-def test_nets_is_a_namespace_package_merged_with_the_reference():
+def test_nets_is_a_namespace_package_merged_with_the_reference(tmp_path):
     """``nets`` ships no __init__.py: with this repository ahead of the reference checkout on sys.path the reference's
     sibling modules stay importable (``from nets.raftnet import Raftnet`` is line 5 of test_on_flt.py / test_on_crohd.py
-    / test_on_badja.py, ahead of ``from nets.pips import Pips``) while nets.pips resolves to the HIP model."""
+    / test_on_badja.py, ahead of ``from nets.pips import Pips``) while nets.pips resolves to the HIP model.  The checkout
+    is stood in for by a tree of the same shape: ``nets/`` without __init__.py, a sibling ``raftnet.py`` and a
+    ``pips.py`` of its own that must lose to this repository's."""
     import subprocess, sys
     assert not os.path.exists(os.path.join(ROOT, "nets", "__init__.py"))
-    ref_root = "/root/reference"
-    have_ref = os.path.isfile(os.path.join(ref_root, "nets", "raftnet.py"))
+    ref_root = str(tmp_path / "checkout")
+    os.makedirs(os.path.join(ref_root, "nets"))
+    with open(os.path.join(ref_root, "nets", "raftnet.py"), "w") as f:
+        f.write("class Raftnet:\n    pass\n")
+    with open(os.path.join(ref_root, "nets", "pips.py"), "w") as f:
+        f.write("raise ImportError('the checkout nets.pips shadowed the HIP model')\n")
     code = ("import sys, importlib.util\n"
             f"sys.path[:0] = [{ROOT!r}, {ref_root!r}]\n"
             "import nets.pips, pips_amd\n"
             "assert nets.pips.Pips is pips_amd.Pips\n"
             "assert nets.pips.__file__.startswith(%r)\n" % ROOT +
-            (f"spec = importlib.util.find_spec('nets.raftnet')\nassert spec is not None and spec.origin.startswith({ref_root!r}), spec\n"
-             if have_ref else "") + "print('ok')\n")
+            f"spec = importlib.util.find_spec('nets.raftnet')\nassert spec is not None and spec.origin.startswith({ref_root!r}), spec\n"
+            "from nets.raftnet import Raftnet\n"
+            "print('ok')\n")
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd="/")
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr
 
 
 def test_reference_saverloader_round_trip(tmp_path, weights_tamed):
-    """The reference's own saverloader.save / saverloader.load (saverloader.py:5-69), unmodified, on pips_amd.Pips
-    (build container only: needs /root/reference)."""
-    ref_root = "/root/reference"
-    if not os.path.isfile(os.path.join(ref_root, "saverloader.py")):
-        pytest.skip("reference checkout not mounted")
-    import importlib.util
-    import sys
-    sys.dont_write_bytecode = True
-    spec = importlib.util.spec_from_file_location("_reference_saverloader", os.path.join(ref_root, "saverloader.py"))
-    saverloader = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(saverloader)
+    """Checkpoints of pips_amd.Pips in the layout the reference's saverloader.save / saverloader.load (saverloader.py:5-69)
+    use, recorded from those functions on this model in tests/golden/saverloader_layout.json (make_saverloader_golden.py):
+    ``<ckpt_dir>/model-%09d.pth`` per global step, a dict of optimizer_state_dict + model_state_dict; load takes the
+    highest step and does ``load_state_dict(ckpt['model_state_dict'], strict=False)``."""
+    with open(os.path.join(ROOT, "tests", "golden", "saverloader_layout.json")) as f:
+        layout = json.load(f)
     from nets.pips import Pips
     src = Pips(stride=8)
     src.load_state_dict(weights_tamed)
     opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=0.1)
-    ckpt_dir = str(tmp_path / "ckpt")
-    saverloader.save(ckpt_dir, opt, src, global_step=7)
+    ckpt_dir = tmp_path / "ckpt"
+    ckpt_dir.mkdir()
+    for step in layout["saved_steps"]:
+        parts = {"optimizer_state_dict": opt.state_dict(), "model_state_dict": src.state_dict()}
+        torch.save({k: parts[k] for k in layout["checkpoint_keys"]}, ckpt_dir / ("model-%09d.pth" % step))
+    names = sorted(os.listdir(ckpt_dir))
+    assert names == layout["files"]
+    step = max(int(n.split("-")[1].split(".")[0]) for n in names)
+    assert step == layout["load_returned_step"] == 7
+    ck = torch.load(ckpt_dir / ("model-%09d.pth" % step))
+    assert list(ck.keys()) == layout["checkpoint_keys"]
+    assert type(ck["model_state_dict"]).__name__ == layout["model_state_dict_type"]
+    assert layout["model_state_dict_keys_match"] and list(ck["model_state_dict"].keys()) == list(src.state_dict().keys())
     dst = Pips(stride=8)                                        # seeded init != tamed weights
-    assert saverloader.load(ckpt_dir, dst) == 7
+    res = dst.load_state_dict(ck["model_state_dict"], strict=False)
+    assert not res.missing_keys and not res.unexpected_keys
     for (ka, a), (kb, b) in zip(src.state_dict().items(), dst.state_dict().items()):
         assert ka == kb and torch.equal(a, b)
 

@@ -145,7 +145,7 @@ def test_shard_range():
 
 
 def test_bench_spawns_its_own_ranks():
-    """`python bench.py --gpus 2` with WORLD_SIZE unset re-executes itself under torch.distributed.run with two
+    """`python bench.py --gpus 2 --full` with WORLD_SIZE unset re-executes itself under torch.distributed.run with two
     ranks and reports n_gpus = 2 (CPU stand-in model + gloo: the launcher, barrier, max-over-ranks and all-gather
     plumbing of the real run)."""
     import json
@@ -154,7 +154,7 @@ def test_bench_spawns_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PIPS_BENCH_FAKE="1", PIPS_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -195,3 +195,33 @@ def test_bench_rejects_world_size_mismatch():
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                          env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode != 0 and "WORLD_SIZE=1" in (out.stderr + out.stdout)
+
+
+def test_bench_plain_line_is_lean_and_dumps_outputs(tmp_path):
+    """A plain two-rank `python bench.py` (no --full) prints the headline only -- none of the legs that --full adds --
+    and --dump-outputs writes the last timed step's outputs as float32 .npy, the same from run to run (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(PIPS_BENCH_FAKE="1", PIPS_BENCH_BACKEND="gloo")
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / f"out{run}")
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", d], env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert res["n_gpus"] == 2 and res["steps"] == 3 and res["value"] > 0 and res["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in res, k
+        for k in ("collective_ms", "config3", "roofline", "split_bf16", "cpu_baseline"):
+            assert k not in res, k
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["coord_predictions", "coord_predictions2", "trajs_e_gathered", "vis_e", "vis_e_gathered"]
+    assert a["coord_predictions"].shape == (6, 1, 8, 16, 2) and a["trajs_e_gathered"].shape == (2, 8, 16, 2)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k

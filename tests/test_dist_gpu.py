@@ -117,12 +117,12 @@ def test_rccl_track_sharded_matches_single_rank():
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs (RCCL); the gpurun box has one")
 def test_rccl_bench_line_two_ranks():
-    """`python bench.py --gpus 2` as the driver launches it: the line must say the exchange went over RCCL."""
+    """`python bench.py --gpus 2 --full` under torch.distributed.run: the line must say the exchange went over RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.pop("PIPS_BENCH_BACKEND", None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                          "--steps", "3", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=900)
+                          "--steps", "3", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 2 and res["scaling"] == "weak" and res["value"] > 0

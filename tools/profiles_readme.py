@@ -98,7 +98,7 @@ def section(r):
     ks, k3, k4 = _stats(t + "_kernel_stats.txt"), _stats(t + "_config3_kernel_stats.txt"), _stats(t + "_config4_kernel_stats.txt")
     pm, pm3 = _json(t + "_pmc_traffic.json"), _json(t + "_pmc_traffic_config3.json")
     L = []
-    L.append("## Round %d (`sh tools/r%d_final.sh` = `pytest -m gpu; python bench.py; sh tools/profile_round.sh r%d; sh tools/profile_mfma.sh r%d; "
+    L.append("## Round %d (`sh tools/r%d_final.sh` = `pytest -m gpu; python bench.py --full; sh tools/profile_round.sh r%d; sh tools/profile_mfma.sh r%d; "
              "sh tools/gather_pmc.sh … fp32 / bf16`; the `r%d_probe_*` files come from the `tools/history/r%d_call*.sh` scripts; THIS TABLE IS "
              "GENERATED from the files by `python tools/profiles_readme.py`)" % (r, r, r, r, r, r))
     L.append("")
@@ -112,7 +112,7 @@ def section(r):
                  "`split_bf16` %.2f ms; `config3` weak %.2f ms = %.2f M updates/s per GPU (strong, 64 clips: %.1f ms), %.3f of the bf16 roof; `config4` %.1f ms "
                  "(split %.1f ms, **bf16 mode %.1f ms = %.2f M updates/s**), `gather_tiled_kernel` %.1f µs = %.3f of 8 TB/s (path bin + embed + gather %.1f µs = %.3f; "
                  "`ceiling_frac` %.2f), `gather_mfma_kernel` %.1f µs = %.3f (path %.1f µs = %.3f; `ceiling_frac` %.2f); `config5` %.3f s per video; "
-                 "stock PyTorch-ROCm ops %.1f ms; CPU port %.0f updates/s on %d cores | `python bench.py` |" % (
+                 "stock PyTorch-ROCm ops %.1f ms; CPU port %.0f updates/s on %d cores | `python bench.py --full` |" % (
                      t, b["ms_per_step"], b["value"] / 1e6, b.get("ms_per_step_median", 0.0), ro["frac"], ro.get("kernel", "?").split("(")[0],
                      ro["launch_ms"] * 1e3, ro.get("kernel_body_ms", 0.0) * 1e3,
                      ("%.3f" % ro["frac_rocprof"]) if ro.get("frac_rocprof") else "n/a", ro.get("rocprof_source", "n/a"),

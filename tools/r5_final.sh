@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -q > $O/r5_pytest_gpu.log 2>&1
 echo "tests rc=$?"; tail -3 $O/r5_pytest_gpu.log
-timeout 900 python bench.py > $O/r5_bench.json 2> $O/r5_bench.err
+timeout 900 python bench.py --full > $O/r5_bench.json 2> $O/r5_bench.err
 echo "bench rc=$?"; tail -c 600 $O/r5_bench.json
 timeout 1500 sh tools/profile_round.sh r5 > $O/r5_profile.log 2>&1
 echo "profile rc=$?"

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
 timeout 1200 python -m pytest tests -m gpu -q > $O/r6_pytest_gpu.log 2>&1
 echo "tests rc=$?"; tail -3 $O/r6_pytest_gpu.log
-timeout 1200 python bench.py > $O/r6_bench.json 2> $O/r6_bench.err
+timeout 1200 python bench.py --full > $O/r6_bench.json 2> $O/r6_bench.err
 echo "bench rc=$?"; tail -c 400 $O/r6_bench.json
 timeout 2400 sh tools/profile_round.sh r6 > $O/r6_profile.log 2>&1
 echo "profile rc=$?"
