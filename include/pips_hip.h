@@ -93,7 +93,9 @@ const char* pips_last_error(void);
  * 1 -> 2: the pyramid buffer of EVERY encoder mode is pips_pyramid_floats() long (the bf16 encoder writes
  * a bf16 mirror of the four levels behind them, at pips_pyramid_mirror_offset -- a buffer sized from the level offsets alone
  * is too short); the PIPS_PACK_FFN arena section and pips_mixer_fwd_bf16_fused (round 3's fused FeedForward, measured slower than
- * the two GEMMs again in round 4 -- tools/experiments/) are gone. */
+ * the two GEMMs again in round 4 -- tools/experiments/) are gone.
+ * Still 3 after additions that change no existing entry point: pips_track_win and pips_mixer_input_build_win (per-particle
+ * time direction win_dir). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -169,6 +171,11 @@ int    pips_forward(const void* arena, const float* rgbs, const float* xys,
  *              F = B*T; per-frame InstanceNorm makes a frame's maps independent of its clip)
  *   win_start  (B*N) int32 first frame of each particle's 8-frame window, or NULL (= 0);
  *              frames past T-1 repeat frame T-1 (chain_demo.py:50-52)
+ *   win_dir    (pips_track_win only) (B*N) int32 time direction of each particle's window, or NULL (= all forward);
+ *              only the sign is used: < 0 = backward.  Row s of a backward window reads frame
+ *              clamp(win_start - s, 0, T-1): frames before 0 repeat frame 0, which is chain_demo.py's loop run on the
+ *              time-reversed video.  The time embedding is still s and row 0 (the query frame) still locks the start.
+ *              Needs win_start; windowed particles always take the direct gather.
  * All other arguments as pips_forward.  T = 8 and win_start = NULL is exactly the forward. */
 size_t pips_track_workspace_bytes(int B, int N);
 int    pips_track(const void* arena, const float* pyramid, int B, int T, int H8, int W8,
@@ -176,6 +183,12 @@ int    pips_track(const void* arena, const float* pyramid, int B, int T, int H8,
                   const int* win_start, const float* times, int N, int stride, int iters, int flags,
                   void* workspace, size_t workspace_bytes,
                   float* out_trajs, float* out_vis, float* out_ffeat0, void* stream);
+/* pips_track_s plus win_dir (see above), without the score-map terms; win_dir = NULL is exactly pips_track_s */
+int    pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8, int W8,
+                      const float* xys, const float* coords_init, const float* feat_init,
+                      const int* win_start, const int* win_dir, const float* times, int N, int stride, int iters,
+                      int flags, int S, void* workspace, size_t workspace_bytes,
+                      float* out_trajs, float* out_vis, float* out_ffeat0, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 
@@ -219,6 +232,11 @@ int    pips_mixer_input_build(const float* pyramid, int B, int S, int H8, int W8
 /* the same with per-particle window starts (pips_track's win_start, may be NULL) and flags = 0 | PIPS_FLAG_BF16_MAPS */
 int    pips_mixer_input_build_ex(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats, const float* coords,
                                  const float* times, int N, const int* win_start, int flags, float* X, void* stream);
+/* pips_mixer_input_build_ex plus pips_track_win's win_dir and the window length S (1..PIPS_S_MAX; rows of ffeats / coords / X
+ * are B*N*S); T = frames per clip in the pyramid */
+int    pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, int W8, const float* ffeats, const float* coords,
+                                  const float* times, int N, const int* win_start, const int* win_dir, int flags, int S,
+                                  float* X, void* stream);
 
 /* Same result as pips_mixer_input_build through the LDS-tiled kernels meant for dense query sets
  * (BASELINE configs[3], test_on_davis.py:103-130): particles binned by 16x16 map tile, the tile's

@@ -691,7 +691,8 @@ static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const
                        const float* times, int N, const int* win_start, float* X, hipStream_t st,
                        void* scratch = nullptr, size_t scratch_bytes = 0, int force_tiled = -1, hipEvent_t* ev = nullptr,
                        int Sw = PIPS_S,         // S: frames per clip in the pyramid; Sw: window length = mixer rows per particle
-                       bool bf16_maps = false) {   // the direct gather reads the bf16 mirror behind the fp32 levels
+                       bool bf16_maps = false,     // the direct gather reads the bf16 mirror behind the fp32 levels
+                       const int* win_dir = nullptr) {   // per-particle time direction (sign), read with win_start only
     size_t off[PIPS_LEVELS];
     int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
     lh[0] = H8; lw[0] = W8;
@@ -702,7 +703,7 @@ static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const
         o += ((size_t)B * S * lh[l] * lw[l] * PIPS_C + 63) / 64 * 64;
     }
     PIPS_CHECK_ARG(lh[PIPS_LEVELS - 1] >= 1 && lw[PIPS_LEVELS - 1] >= 1, "mixer_input: map too small");
-    const bool can_tile = scratch != nullptr && win_start == nullptr && S == PIPS_S && Sw == PIPS_S &&
+    const bool can_tile = scratch != nullptr && win_start == nullptr && win_dir == nullptr && S == PIPS_S && Sw == PIPS_S &&
                           scratch_bytes >= tiled_gather_scratch_bytes(B, N, H8, W8);
     const bool tiled = force_tiled >= 0 ? (force_tiled != 0) : tiled_gather_wanted(B, N, H8, W8, bf16_maps);
     if (tiled && can_tile)      // (bf16 mode: the same work items on the matrix cores, reading the bf16 mirror behind the fp32 levels)
@@ -710,8 +711,10 @@ static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const
                                         bf16_maps ? reinterpret_cast<const unsigned short*>(pyramid + o) : nullptr);
     PIPS_CHECK_ARG(force_tiled != 1, "tiled gather needs scratch of %zu bytes, no win_start and 8 frames per clip",
                    tiled_gather_scratch_bytes(B, N, H8, W8));
-    if (bf16_maps) return launch_mixer_input_bf16maps(pyramid + o, off, lh, lw, B, S, ffeats, coords, times, N, win_start, X, st, Sw);
-    return launch_mixer_input(pyramid, off, lh, lw, B, S, ffeats, coords, times, N, win_start, X, st, Sw);
+    PIPS_CHECK_ARG(win_dir == nullptr || win_start != nullptr, "mixer_input: win_dir needs win_start");
+    if (bf16_maps)
+        return launch_mixer_input_bf16maps(pyramid + o, off, lh, lw, B, S, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
+    return launch_mixer_input(pyramid, off, lh, lw, B, S, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
 }
 
 int pips_mixer_input_build(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
@@ -727,6 +730,16 @@ int pips_mixer_input_build_ex(const float* pyramid, int B, int S, int H8, int W8
     PIPS_CHECK_ARG(S >= 1 && B > 0 && N > 0, "mixer_input: empty problem");
     return mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
                        PIPS_S, (flags & PIPS_FLAG_BF16_MAPS) != 0);
+}
+
+int pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, int W8, const float* ffeats, const float* coords,
+                               const float* times, int N, const int* win_start, const int* win_dir, int flags, int S, float* X,
+                               void* stream) {
+    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X, "mixer_input: null pointer");
+    PIPS_CHECK_ARG(T >= 1 && B > 0 && N > 0, "mixer_input: empty problem");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", S, PIPS_S_MAX);
+    return mixer_input(pyramid, B, T, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
+                       S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir);
 }
 
 size_t pips_gather_scratch_bytes(int B, int N, int H8, int W8) {
@@ -1138,8 +1151,8 @@ int pips_score_map_terms(const float* U, int B, int S, int H8, int W8, const flo
 
 // S = window length (tokens per particle) the arena was packed for; S == PIPS_S runs the specialised kernels
 static int track_impl(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
-                      const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
-                      int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
+                      const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                      const float* times, int N, int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                       float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                       size_t ce_ws_bytes, void* stream);
 
@@ -1149,7 +1162,7 @@ int pips_track(const void* arena, const float* pyramid, int B, int T, int H8, in
                const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
                int stride, int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs,
                float* out_vis, float* out_ffeat0, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
                       flags, PIPS_S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
                       stream);
 }
@@ -1159,7 +1172,7 @@ int pips_track_s(const void* arena, const float* pyramid, int B, int T, int H8, 
                  int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                  float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                  size_t ce_ws_bytes, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
                       flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes,
                       stream);
 }
@@ -1169,22 +1182,32 @@ int pips_track_ce(const void* arena, const float* pyramid, int B, int T, int H8,
                   int stride, int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs,
                   float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                   size_t ce_ws_bytes, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
                       flags, PIPS_S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws,
                       ce_ws_bytes, stream);
+}
+
+int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
+                   const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                   const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
+                   size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
+    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
+                      flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
+                      stream);
 }
 
 }  // extern "C"
 
 static int track_impl(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
-                      const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
-                      int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
+                      const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                      const float* times, int N, int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                       float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                       size_t ce_ws_bytes, void* stream) {
     PIPS_CHECK_ARG(arena && pyramid && xys && times && workspace && out_trajs && out_vis, "track: null pointer");
     PIPS_CHECK_ARG(B > 0 && N > 0 && T >= 1 && iters >= 0 && stride >= 1, "track: need B,N,T,stride >= 1 and iters >= 0");
     PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "track: window length S=%d outside 1..%d", S, PIPS_S_MAX);
     PIPS_CHECK_ARG(H8 >= 8 && W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", H8, W8);
+    PIPS_CHECK_ARG(win_dir == nullptr || win_start != nullptr, "track: win_dir needs win_start");
     const TrackPlan P = plan_track(B, N, S);
     if (workspace_bytes < P.total * sizeof(float)) {
         set_error("track: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
@@ -1220,7 +1243,7 @@ static int track_impl(const void* arena, const float* pyramid, int B, int T, int
             RUN(launch_score_terms((const float*)ce_ws, B, S, H8, W8, ffeats, N, ce_tgt, ce_terms + (size_t)it * M * 2, st));
         // the mixer workspace is idle while the gather runs: it doubles as the binning scratch
         RUN(mixer_input(pyramid, B, T, H8, W8, ffeats, coords, times, N, win_start, ws + P.X, st, ws + P.mixer,
-                        pips_mixer_workspace_bytes_s(M, S), -1, nullptr, S, (flags & PIPS_FLAG_BF16_MAPS) != 0));
+                        pips_mixer_workspace_bytes_s(M, S), -1, nullptr, S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir));
         RUN(mixer_impl(arena, ws + P.X, M, ws + P.delta, ws + P.mixer, pips_mixer_workspace_bytes_s(M, S), stream, nullptr,
                        mixer_mode(flags), S));
         RUN(launch_state_update((const float*)arena, ws + P.delta, ffeats, coords, coords0, B, N, (float)stride,
@@ -1273,7 +1296,7 @@ int pips_forward_ce(const void* arena, const float* rgbs, const float* xys, cons
         (flags & (PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_BF16_MIXER)) == (PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_BF16_MIXER) &&
         PIPS_TUNE("PIPS_BF16_MAPS", 1))
         flags |= PIPS_FLAG_BF16_MAPS;
-    return track_impl(arena, pyramid, B, S, H / stride, W / stride, xys, coords_init, feat_init, nullptr, times, N,
+    return track_impl(arena, pyramid, B, S, H / stride, W / stride, xys, coords_init, feat_init, nullptr, nullptr, times, N,
                       stride, iters, flags, S, ws + P.track, plan_track(B, N, S).total * sizeof(float), out_trajs, out_vis,
                       out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes, stream);
 }

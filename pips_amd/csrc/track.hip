@@ -126,6 +126,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
                                                           const float* __restrict__ coords,
                                                           const float* __restrict__ times, int N,
                                                           const int* __restrict__ win_start,
+                                                          const int* __restrict__ win_dir,
                                                           float* __restrict__ X) {
     __shared__ float Dw[PIPS_LEVELS][64];
     const int S = SCT ? SCT : Srt;                       // (shadows the file-scope constant)
@@ -135,8 +136,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     // The map buffer holds S_ frames per clip.  S_ = 8 with win_start == null is the plain
     // forward; a longer cache + per-particle window start gives chained tracking, where frames
     // past the end repeat the last one (chain_demo.py:50-52) = a clamp of the frame index.
-    const int fstart = win_start != nullptr ? win_start[pn] : 0;
-    const int frame = b * S_ + min(max(fstart + s, 0), S_ - 1);
+    // win_dir (sign per particle, null = forward): a backward window reads fstart, fstart-1, ...
+    // and repeats frame 0 past the start -- the same loop on the time-reversed video.
+    int fstart = 0, dir = 1;
+    if (win_start != nullptr) {
+        fstart = win_start[pn];
+        if (win_dir != nullptr) dir = win_dir[pn] < 0 ? -1 : 1;
+    }
+    const int frame = b * S_ + min(max(fstart + dir * s, 0), S_ - 1);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lvl = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float cxm = coords[(size_t)m * 2 + 0], cym = coords[(size_t)m * 2 + 1];
@@ -250,14 +257,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 template <int SCT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void mixer_input_bf16maps_kernel(
     const unsigned short* __restrict__ mirror, LevelTable lv, int S_, int Srt, const float* __restrict__ ffeats,
-    const float* __restrict__ coords, const float* __restrict__ times, int N, const int* __restrict__ win_start, float* __restrict__ X) {
+    const float* __restrict__ coords, const float* __restrict__ times, int N, const int* __restrict__ win_start,
+    const int* __restrict__ win_dir, float* __restrict__ X) {
     __shared__ float Dw[PIPS_LEVELS][64];
     const int S = SCT ? SCT : Srt;
     const int m = blockIdx.x;
     const int s = m % S, pn = m / S;
     const int b = pn / N;
-    const int fstart = win_start != nullptr ? win_start[pn] : 0;
-    const int frame = b * S_ + min(max(fstart + s, 0), S_ - 1);
+    int fstart = 0, dir = 1;                            // (window frames as in mixer_input_kernel)
+    if (win_start != nullptr) {
+        fstart = win_start[pn];
+        if (win_dir != nullptr) dir = win_dir[pn] < 0 ? -1 : 1;
+    }
+    const int frame = b * S_ + min(max(fstart + dir * s, 0), S_ - 1);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lvl = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float cxm = coords[(size_t)m * 2 + 0], cym = coords[(size_t)m * 2 + 1];
@@ -362,16 +374,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 
 int launch_mixer_input_bf16maps(const void* mirror, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B, int S_,
                                 const float* ffeats, const float* coords, const float* times, int N, const int* win_start,
-                                float* X, hipStream_t st, int Sw) {
+                                const int* win_dir, float* X, hipStream_t st, int Sw) {
     LevelTable lv;
     for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
     const unsigned short* mp = reinterpret_cast<const unsigned short*>(mirror);
     if (Sw == PIPS_S)
         hipLaunchKernelGGL(mixer_input_bf16maps_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, mp, lv, S_, Sw, ffeats,
-                           coords, times, N, win_start, X);
+                           coords, times, N, win_start, win_dir, X);
     else
         hipLaunchKernelGGL(mixer_input_bf16maps_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, mp, lv, S_, Sw, ffeats,
-                           coords, times, N, win_start, X);
+                           coords, times, N, win_start, win_dir, X);
     PIPS_CHECK_LAUNCH("mixer_input_bf16maps_kernel");
     return PIPS_OK;
 }
@@ -394,15 +406,15 @@ int launch_pyramid_mirror(const float* pyramid, size_t floats, void* mirror, hip
 
 int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
                        int B, int S_, const float* ffeats, const float* coords, const float* times,
-                       int N, const int* win_start, float* X, hipStream_t st, int Sw) {
+                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
     LevelTable lv;
     for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
     if (Sw == PIPS_S)
         hipLaunchKernelGGL(mixer_input_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, pyramid, lv, S_, Sw, ffeats,
-                           coords, times, N, win_start, X);
+                           coords, times, N, win_start, win_dir, X);
     else
         hipLaunchKernelGGL(mixer_input_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, pyramid, lv, S_, Sw, ffeats,
-                           coords, times, N, win_start, X);
+                           coords, times, N, win_start, win_dir, X);
     PIPS_CHECK_LAUNCH("mixer_input_kernel");
     return PIPS_OK;
 }

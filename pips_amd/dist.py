@@ -7,7 +7,7 @@ train.py:254).  Two axes shard without any exchange inside the forward:
   InstanceNorm is per frame, correlation and mixer are per (clip, particle) -- so each rank runs
   whole clips and the only exchange is one all-gather of the final ``[x, y, vis_logit]`` per
   (clip, frame, particle): 196 KB per rank at B/G=8, N=256.
-* **particles** (secondary, for B < G: ``track_sharded_particles``, ``track_chained_sharded``):
+* **particles** (secondary, for B < G: ``track_sharded_particles``, ``track_chained_sharded``, ``track_queries_sharded``):
   given the feature maps, particles are independent (the reference's own callers loop over them:
   chain_demo.py:40, test_on_davis.py:116-118).  Every rank holds the maps of the whole clip --
   encoded redundantly (``encode="replicate"``: 2.8 ms at BASELINE configs[1], no exchange) or each rank
@@ -161,3 +161,17 @@ def track_chained_sharded(model, rgbs, xy0, iters=6, group=None):
     if not _live(group):
         return mine
     return _all_gather_cat(mine, 2, group)[:, :, :n].contiguous()
+
+
+def track_queries_sharded(model, rgbs, queries, iters=6, group=None):
+    """``drivers.track_queries`` with the queries split over the ranks -- every query's two chains are independent of the
+    other queries', so, as in ``track_chained_sharded``, every rank encodes the video, tracks N/G queries (padded to the world
+    size by repeating the last one) and one all-gather of the packed ``[x, y, vis_logit]`` on the particle axis collects
+    ``trajs_e (1,T,N,2)`` and ``vis_e (1,T,N)``."""
+    from . import drivers
+    rank, world = _world(group)
+    qp, n = pad_to_world(queries, world, dim=1)
+    lo, hi = shard_range(qp.shape[1], rank, world)
+    trajs, vis = drivers.track_queries(model, rgbs, qp[:, lo:hi], iters=iters)
+    trajs, vis = all_gather_result(trajs, vis, group=group, dim=2)
+    return trajs[:, :, :n].contiguous(), vis[:, :, :n].contiguous()

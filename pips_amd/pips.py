@@ -286,10 +286,13 @@ class Pips(nn.Module):
 
     @torch.no_grad()
     def track(self, cache: FeatureCache, xys, coords_init=None, feat_init=None, iters=3, win_start=None,
-              return_feat=False):
+              return_feat=False, win_dir=None):
         """The update loop of ``forward`` (nets/pips.py:450-563) on cached maps.  ``win_start``
         ``(B,N)`` int = first frame of each particle's 8-frame window inside the ``T`` cached
         frames (default 0); frames past the end repeat the last one (chain_demo.py:50-52).
+        ``win_dir`` ``(B,N)`` int, its sign = the time direction of each particle's window (default: all
+        forward): row ``s`` of a backward window reads frame ``win_start - s``, frames before 0 repeat
+        frame 0 -- the same loop on the time-reversed video.
         Returns the same tuple as ``forward`` (losses = None)."""
         lib = _lib.load()
         B, N, D = xys.shape
@@ -300,10 +303,13 @@ class Pips(nn.Module):
         ci = None if coords_init is None else coords_init.to(dev).contiguous().to(f32)
         fi = None if feat_init is None else feat_init.to(dev).contiguous().to(f32)
         ws_i = None if win_start is None else win_start.to(dev).contiguous().to(torch.int32)
+        wd_i = None if win_dir is None else win_dir.to(dev).contiguous().to(torch.int32)
         if ws_i is not None:
             assert tuple(ws_i.shape) == (B, N)
-        elif cache.T != S:
+        elif cache.T != S or wd_i is not None:
             ws_i = torch.zeros(B, N, dtype=torch.int32, device=dev)
+        if wd_i is not None:
+            assert tuple(wd_i.shape) == (B, N)
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
             fl = self._flags()
@@ -320,11 +326,11 @@ class Pips(nn.Module):
             trajs = torch.empty(iters + 1, B, S, N, 2, dtype=f32, device=dev)
             vis_e = torch.empty(B, S, N, dtype=f32, device=dev)
             ffeat = torch.empty(B, N, self.latent_dim, dtype=f32, device=dev)
-            rc = lib.pips_track_s(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, H8, W8, _lib.ptr(xys_c), _lib.ptr(ci),
-                                  _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(times), N, int(cache.stride), int(iters),
-                                  fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs), _lib.ptr(vis_e),
-                                  _lib.ptr(ffeat), None, None, None, 0, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "pips_track_s")
+            rc = lib.pips_track_win(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, H8, W8, _lib.ptr(xys_c), _lib.ptr(ci),
+                                    _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(times), N, int(cache.stride), int(iters),
+                                    fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs), _lib.ptr(vis_e),
+                                    _lib.ptr(ffeat), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.check(rc, "pips_track_win")
         preds = [trajs[i + 1] for i in range(iters)]
         preds2 = [trajs[0], trajs[0]] + preds + [trajs[iters], trajs[iters]]
         if return_feat:
