@@ -95,7 +95,8 @@ const char* pips_last_error(void);
  * is too short); the PIPS_PACK_FFN arena section and pips_mixer_fwd_bf16_fused (round 3's fused FeedForward, measured slower than
  * the two GEMMs again in round 4 -- tools/experiments/) are gone.
  * Still 3 after additions that change no existing entry point: pips_track_win and pips_mixer_input_build_win (per-particle
- * time direction win_dir). */
+ * time direction win_dir); pips_track_ring, pips_mixer_input_build_ring and pips_pyramid_append (a ring of R frame slots
+ * for streamed video). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -189,6 +190,16 @@ int    pips_track_win(const void* arena, const float* pyramid, int B, int T, int
                       const int* win_start, const int* win_dir, const float* times, int N, int stride, int iters,
                       int flags, int S, void* workspace, size_t workspace_bytes,
                       float* out_trajs, float* out_vis, float* out_ffeat0, void* stream);
+/* pips_track_win on a ring of R frame slots per clip (streamed video, pips_pyramid_append): the pyramid is laid out for R
+ * frames (pips_pyramid_floats(B*R, ...)), T is the number of logical frames appended so far and only the clamp bound, and
+ * logical frame f lives in slot f mod R.  Row s of a window reads slot clamp(win_start + dir*s, 0, T-1) mod R; the point
+ * sample of feat_init = NULL reads slot clamp(win_start, 0, T-1) mod R.  R = T is exactly pips_track_win.  The caller
+ * keeps every frame a window can read in the ring: with T frames appended, frames T-R .. T-1. */
+int    pips_track_ring(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8,
+                       const float* xys, const float* coords_init, const float* feat_init,
+                       const int* win_start, const int* win_dir, const float* times, int N, int stride, int iters,
+                       int flags, int S, void* workspace, size_t workspace_bytes,
+                       float* out_trajs, float* out_vis, float* out_ffeat0, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 
@@ -201,6 +212,11 @@ size_t pips_pyramid_offset(int F, int H, int W, int stride, int level);   /* in 
 /* pips_pyramid_floats = the four fp32 levels + their bf16 mirror (same element offsets, half the bytes) behind them */
 size_t pips_pyramid_mirror_offset(int F, int H, int W, int stride);       /* in floats: where the mirror starts = size of the fp32 levels */
 int    pips_pyramid_mirror(float* pyramid, int F, int H, int W, int stride, void* stream);   /* (re)write the mirror from the fp32 levels */
+/* Streamed video: copy the levels of k frames just encoded (src: a pips_encoder_fwd* pyramid of F = k frames) into slots
+ * (T0 + i) mod R, i < k, of a ring pyramid of R frame slots (pips_pyramid_floats(R, ...)), wrapping past slot R-1, and write
+ * the bf16 mirror of those slots from the fp32 levels in the same pass (pips_pyramid_mirror's rounding).  One launch.
+ * Needs R >= 1, T0 >= 0 and 1 <= k <= R. */
+int    pips_pyramid_append(const float* src, int k, float* ring, int R, int T0, int H, int W, int stride, void* stream);
 int    pips_encoder_fwd(const void* arena, const float* rgbs, int F, int H, int W, int stride,
                         float* pyramid, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -237,6 +253,10 @@ int    pips_mixer_input_build_ex(const float* pyramid, int B, int S, int H8, int
 int    pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, int W8, const float* ffeats, const float* coords,
                                   const float* times, int N, const int* win_start, const int* win_dir, int flags, int S,
                                   float* X, void* stream);
+/* pips_mixer_input_build_win on a ring of R frame slots per clip holding T logical frames (pips_track_ring) */
+int    pips_mixer_input_build_ring(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
+                                   const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
+                                   int flags, int S, float* X, void* stream);
 
 /* Same result as pips_mixer_input_build through the LDS-tiled kernels meant for dense query sets
  * (BASELINE configs[3], test_on_davis.py:103-130): particles binned by 16x16 map tile, the tile's

@@ -592,6 +592,24 @@ size_t pips_pyramid_offset(int F, int H, int W, int stride, int level) {
     return n;
 }
 
+int pips_pyramid_append(const float* src, int k, float* ring, int R, int T0, int H, int W, int stride, void* stream) {
+    PIPS_CHECK_ARG(src != nullptr && ring != nullptr, "pyramid_append: null pointer");
+    PIPS_CHECK_ARG(R >= 1 && T0 >= 0 && k >= 1 && k <= R, "pyramid_append: need R >= 1, T0 >= 0 and 1 <= k <= R (k=%d, R=%d, T0=%d)",
+                   k, R, T0);
+    PIPS_CHECK_ARG(H > 0 && W > 0 && stride >= 1, "pyramid_append: bad geometry");
+    int lh[PIPS_LEVELS], lw[PIPS_LEVELS], pf8[PIPS_LEVELS];
+    pyramid_dims(H, W, stride, lh, lw);
+    PIPS_CHECK_ARG(lh[PIPS_LEVELS - 1] >= 1 && lw[PIPS_LEVELS - 1] >= 1, "pyramid_append: map too small");
+    size_t so[PIPS_LEVELS], dof[PIPS_LEVELS];
+    for (int l = 0; l < PIPS_LEVELS; ++l) {
+        so[l] = pips_pyramid_offset(k, H, W, stride, l);
+        dof[l] = pips_pyramid_offset(R, H, W, stride, l);
+        pf8[l] = lh[l] * lw[l] * PIPS_C / 8;
+    }
+    return launch_pyramid_append(src, so, k, ring, dof, ring + pips_pyramid_mirror_offset(R, H, W, stride), pf8, R, T0,
+                                 (hipStream_t)stream);
+}
+
 static int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int W, int stride, float* pyramid,
                         void* workspace, size_t workspace_bytes, void* stream, int mode);
 
@@ -692,7 +710,9 @@ static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const
                        void* scratch = nullptr, size_t scratch_bytes = 0, int force_tiled = -1, hipEvent_t* ev = nullptr,
                        int Sw = PIPS_S,         // S: frames per clip in the pyramid; Sw: window length = mixer rows per particle
                        bool bf16_maps = false,     // the direct gather reads the bf16 mirror behind the fp32 levels
-                       const int* win_dir = nullptr) {   // per-particle time direction (sign), read with win_start only
+                       const int* win_dir = nullptr,     // per-particle time direction (sign), read with win_start only
+                       int T = 0) {             // logical frames (the clamp bound), 0 = S; frame f lies in slot f mod S
+    if (T == 0) T = S;
     size_t off[PIPS_LEVELS];
     int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
     lh[0] = H8; lw[0] = W8;
@@ -703,7 +723,7 @@ static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const
         o += ((size_t)B * S * lh[l] * lw[l] * PIPS_C + 63) / 64 * 64;
     }
     PIPS_CHECK_ARG(lh[PIPS_LEVELS - 1] >= 1 && lw[PIPS_LEVELS - 1] >= 1, "mixer_input: map too small");
-    const bool can_tile = scratch != nullptr && win_start == nullptr && win_dir == nullptr && S == PIPS_S && Sw == PIPS_S &&
+    const bool can_tile = scratch != nullptr && win_start == nullptr && win_dir == nullptr && S == PIPS_S && T == S && Sw == PIPS_S &&
                           scratch_bytes >= tiled_gather_scratch_bytes(B, N, H8, W8);
     const bool tiled = force_tiled >= 0 ? (force_tiled != 0) : tiled_gather_wanted(B, N, H8, W8, bf16_maps);
     if (tiled && can_tile)      // (bf16 mode: the same work items on the matrix cores, reading the bf16 mirror behind the fp32 levels)
@@ -713,8 +733,9 @@ static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const
                    tiled_gather_scratch_bytes(B, N, H8, W8));
     PIPS_CHECK_ARG(win_dir == nullptr || win_start != nullptr, "mixer_input: win_dir needs win_start");
     if (bf16_maps)
-        return launch_mixer_input_bf16maps(pyramid + o, off, lh, lw, B, S, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
-    return launch_mixer_input(pyramid, off, lh, lw, B, S, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
+        return launch_mixer_input_bf16maps(pyramid + o, off, lh, lw, B, S, T, ffeats, coords, times, N, win_start, win_dir, X, st,
+                                           Sw);
+    return launch_mixer_input(pyramid, off, lh, lw, B, S, T, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
 }
 
 int pips_mixer_input_build(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
@@ -740,6 +761,16 @@ int pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, int W
     PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", S, PIPS_S_MAX);
     return mixer_input(pyramid, B, T, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
                        S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir);
+}
+
+int pips_mixer_input_build_ring(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
+                                const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
+                                int flags, int S, float* X, void* stream) {
+    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X, "mixer_input: null pointer");
+    PIPS_CHECK_ARG(T >= 1 && R >= 1 && B > 0 && N > 0, "mixer_input: need T, R, B, N >= 1");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", S, PIPS_S_MAX);
+    return mixer_input(pyramid, B, R, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
+                       S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir, T);
 }
 
 size_t pips_gather_scratch_bytes(int B, int N, int H8, int W8) {
@@ -1150,7 +1181,7 @@ int pips_score_map_terms(const float* U, int B, int S, int H8, int W8, const flo
 }  // extern "C"
 
 // S = window length (tokens per particle) the arena was packed for; S == PIPS_S runs the specialised kernels
-static int track_impl(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
+static int track_impl(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
                       const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
                       const float* times, int N, int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                       float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
@@ -1162,7 +1193,7 @@ int pips_track(const void* arena, const float* pyramid, int B, int T, int H8, in
                const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
                int stride, int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs,
                float* out_vis, float* out_ffeat0, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
                       flags, PIPS_S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
                       stream);
 }
@@ -1172,7 +1203,7 @@ int pips_track_s(const void* arena, const float* pyramid, int B, int T, int H8, 
                  int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                  float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                  size_t ce_ws_bytes, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
                       flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes,
                       stream);
 }
@@ -1182,7 +1213,7 @@ int pips_track_ce(const void* arena, const float* pyramid, int B, int T, int H8,
                   int stride, int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs,
                   float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                   size_t ce_ws_bytes, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
                       flags, PIPS_S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws,
                       ce_ws_bytes, stream);
 }
@@ -1191,20 +1222,30 @@ int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8
                    const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
                    const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
                    size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
-    return track_impl(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
+    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
+                      flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
+                      stream);
+}
+
+int pips_track_ring(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
+                    const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                    const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
+                    size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
+    return track_impl(arena, pyramid, B, T, R, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
                       flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
                       stream);
 }
 
 }  // extern "C"
 
-static int track_impl(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
+static int track_impl(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
                       const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
                       const float* times, int N, int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                       float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                       size_t ce_ws_bytes, void* stream) {
     PIPS_CHECK_ARG(arena && pyramid && xys && times && workspace && out_trajs && out_vis, "track: null pointer");
-    PIPS_CHECK_ARG(B > 0 && N > 0 && T >= 1 && iters >= 0 && stride >= 1, "track: need B,N,T,stride >= 1 and iters >= 0");
+    PIPS_CHECK_ARG(B > 0 && N > 0 && T >= 1 && R >= 1 && iters >= 0 && stride >= 1,
+                   "track: need B,N,T,R,stride >= 1 and iters >= 0");
     PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "track: window length S=%d outside 1..%d", S, PIPS_S_MAX);
     PIPS_CHECK_ARG(H8 >= 8 && W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", H8, W8);
     PIPS_CHECK_ARG(win_dir == nullptr || win_start != nullptr, "track: win_dir needs win_start");
@@ -1224,11 +1265,11 @@ static int track_impl(const void* arena, const float* pyramid, int B, int T, int
         if (feat_init != ffeat0)
             (void)hipMemcpyAsync(ffeat0, feat_init, (size_t)B * N * PIPS_C * sizeof(float), hipMemcpyDeviceToDevice, st);
     } else {
-        RUN(launch_point_sample_strided(pyramid, B, T, H8, W8, coords, S * 2, N, win_start, ffeat0, st));   // :463
+        RUN(launch_point_sample_strided(pyramid, B, R, T, H8, W8, coords, S * 2, N, win_start, ffeat0, st));   // :463
     }
     RUN(launch_init_ffeats(ffeat0, B * N, ffeats, st, S));                                                    // :466
     if (ce_tgt != nullptr) {            // score-map loss terms of every iteration (:501-511, 58-92): evaluation only
-        PIPS_CHECK_ARG(ce_terms && ce_ws && win_start == nullptr && T == S,
+        PIPS_CHECK_ARG(ce_terms && ce_ws && win_start == nullptr && T == S && R == T,
                        "track: score-map terms need their output and workspace, S frames per clip and no windows");
         if (ce_ws_bytes < pips_score_map_workspace_bytes(B, T, H8, W8)) {
             set_error("track: score-map workspace %zu < %zu bytes", ce_ws_bytes, pips_score_map_workspace_bytes(B, T, H8, W8));
@@ -1242,8 +1283,8 @@ static int track_impl(const void* arena, const float* pyramid, int B, int T, int
         if (ce_tgt != nullptr)           // fcorr_fn.corr(ffeats) of this iteration (:501), before the update
             RUN(launch_score_terms((const float*)ce_ws, B, S, H8, W8, ffeats, N, ce_tgt, ce_terms + (size_t)it * M * 2, st));
         // the mixer workspace is idle while the gather runs: it doubles as the binning scratch
-        RUN(mixer_input(pyramid, B, T, H8, W8, ffeats, coords, times, N, win_start, ws + P.X, st, ws + P.mixer,
-                        pips_mixer_workspace_bytes_s(M, S), -1, nullptr, S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir));
+        RUN(mixer_input(pyramid, B, R, H8, W8, ffeats, coords, times, N, win_start, ws + P.X, st, ws + P.mixer,
+                        pips_mixer_workspace_bytes_s(M, S), -1, nullptr, S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir, T));
         RUN(mixer_impl(arena, ws + P.X, M, ws + P.delta, ws + P.mixer, pips_mixer_workspace_bytes_s(M, S), stream, nullptr,
                        mixer_mode(flags), S));
         RUN(launch_state_update((const float*)arena, ws + P.delta, ffeats, coords, coords0, B, N, (float)stride,
@@ -1296,7 +1337,7 @@ int pips_forward_ce(const void* arena, const float* rgbs, const float* xys, cons
         (flags & (PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_BF16_MIXER)) == (PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_BF16_MIXER) &&
         PIPS_TUNE("PIPS_BF16_MAPS", 1))
         flags |= PIPS_FLAG_BF16_MAPS;
-    return track_impl(arena, pyramid, B, S, H / stride, W / stride, xys, coords_init, feat_init, nullptr, nullptr, times, N,
+    return track_impl(arena, pyramid, B, S, S, H / stride, W / stride, xys, coords_init, feat_init, nullptr, nullptr, times, N,
                       stride, iters, flags, S, ws + P.track, plan_track(B, N, S).total * sizeof(float), out_trajs, out_vis,
                       out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes, stream);
 }

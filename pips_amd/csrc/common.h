@@ -135,6 +135,8 @@ __device__ __forceinline__ void store_c_tile_bf16(const float (&v)[16], int l31,
 }
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// slot of logical frame f >= 0 in a ring of R frame slots (a linear cache, R = frames, never wraps)
+__device__ __forceinline__ int ring_slot(int f, int R) { return f < R ? f : f % R; }
 
 // InstanceNorm partials of a convolution tile, one per WAVE ROW (m tile, wm) and channel, about a PIVOT -- the value of
 // the wave's first output row in that channel: {sum(x-p), sum((x-p)^2), p, n}.  E[x^2] - mean^2 of raw fp32 sums loses
@@ -375,21 +377,27 @@ int launch_resize_into_bf16(const void* src, int F, int Hs, int Ws, int C, void*
 // ---------------------------------------------------------------- tracker pieces (track.hip)
 int launch_point_sample(const float* level0, int B, int S, int H8, int W8, const float* xy, int N,
                         float* out, hipStream_t st);
-int launch_point_sample_strided(const float* level0, int B, int S, int H8, int W8, const float* xy,
+// S: frame slots per clip in the buffer; T: logical frames (window starts are clamped to T - 1, then taken mod S)
+int launch_point_sample_strided(const float* level0, int B, int S, int T, int H8, int W8, const float* xy,
                                 int xy_stride, int N, const int* win_start, float* out, hipStream_t st);
 // Sw (last argument of the tracker launchers): the window length = mixer rows per particle; PIPS_S runs the specialised kernels
 int launch_init_coords(const float* xys, const float* coords_init, int B, int N, float stride,
                        float* coords, float* coords0, float* out_traj0, hipStream_t st, int Sw = PIPS_S);
 int launch_init_ffeats(const float* ffeat0, int BN, float* ffeats, hipStream_t st, int Sw = PIPS_S);
+// S: frame slots per clip in the pyramid, T: logical frames (the clamp bound; frame f is read from slot f mod S)
 int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
-                       int B, int S, const float* ffeats, const float* coords, const float* times,
+                       int B, int S, int T, const float* ffeats, const float* coords, const float* times,
                        int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S);
 // win_dir (B*N, sign = time direction of each particle's window, null = forward) is read only with win_start
 // the direct gather on the bf16 mirror of the pyramid (PIPS_FLAG_BF16_MAPS), and the pass that writes the mirror
 int launch_mixer_input_bf16maps(const void* mirror, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B, int S,
-                                const float* ffeats, const float* coords, const float* times, int N, const int* win_start,
-                                const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S);
+                                int T, const float* ffeats, const float* coords, const float* times, int N,
+                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S);
 int launch_pyramid_mirror(const float* pyramid, size_t floats, void* mirror, hipStream_t st);
+// k encoded frames (levels at src_off, pf8[l] = 8-float groups per frame of level l) -> ring slots (T0 + i) mod R of a pyramid
+// with levels at dst_off and its bf16 mirror at dst_mirror (same element offsets as the fp32 levels), in one pass
+int launch_pyramid_append(const float* src, const size_t* src_off, int k, float* dst, const size_t* dst_off, void* dst_mirror,
+                          const int* pf8, int R, int T0, hipStream_t st);
 // LDS-tiled gather for dense query sets (gather_tiled.hip)
 size_t tiled_gather_scratch_bytes(int B, int N, int H8, int W8);
 bool tiled_gather_wanted(int B, int N, int H8, int W8, bool bf16_maps = false);

@@ -15,7 +15,9 @@ constexpr int C = PIPS_C;
 // utils.samp.bilinear_sample2d (utils/samp.py:5-78) on frame 0 of each clip: neighbour
 // indices clamped to the border, weights unclamped, products and sums rounded one by one
 // in the reference's order (samp.py:59-65).  128 threads = 128 channels of one point.
-__global__ __launch_bounds__(128) void point_sample_kernel(const float* __restrict__ level0, int S_,
+// The map buffer holds R frame slots per clip; T_ logical frames: window start f reads slot
+// clamp(f, 0, T_-1) mod R (ring_slot).  A linear cache is R = T_.
+__global__ __launch_bounds__(128) void point_sample_kernel(const float* __restrict__ level0, int S_, int T_,
                                                            int H, int W, const float* __restrict__ xy,
                                                            int xy_stride, int N,
                                                            const int* __restrict__ win_start,
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(128) void point_sample_kernel(const float* __restri
     const int y0 = min(max((int)y0f, 0), H - 1), y1 = min(max((int)y0f + 1, 0), H - 1);
     const float w00 = __fmul_rn(x1f - x, y1f - y), w01 = __fmul_rn(x - x0f, y1f - y);
     const float w10 = __fmul_rn(x1f - x, y - y0f), w11 = __fmul_rn(x - x0f, y - y0f);
-    const int f_first = win_start != nullptr ? min(max(win_start[pn], 0), S_ - 1) : 0;
+    const int f_first = win_start != nullptr ? ring_slot(min(max(win_start[pn], 0), T_ - 1), S_) : 0;
     const float* f0 = level0 + ((size_t)b * S_ + f_first) * H * W * C;   // first frame of the window
     const int c = threadIdx.x;
     const float v00 = f0[((size_t)y0 * W + x0) * C + c], v01 = f0[((size_t)y0 * W + x1) * C + c];
@@ -40,9 +42,9 @@ __global__ __launch_bounds__(128) void point_sample_kernel(const float* __restri
     out[(size_t)pn * C + c] = o;
 }
 
-int launch_point_sample_strided(const float* level0, int B, int S_, int H8, int W8, const float* xy,
+int launch_point_sample_strided(const float* level0, int B, int S_, int T_, int H8, int W8, const float* xy,
                                 int xy_stride, int N, const int* win_start, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(point_sample_kernel, dim3(B * N), dim3(128), 0, st, level0, S_, H8, W8, xy,
+    hipLaunchKernelGGL(point_sample_kernel, dim3(B * N), dim3(128), 0, st, level0, S_, T_, H8, W8, xy,
                        xy_stride, N, win_start, out);
     PIPS_CHECK_LAUNCH("point_sample_kernel");
     return PIPS_OK;
@@ -50,7 +52,7 @@ int launch_point_sample_strided(const float* level0, int B, int S_, int H8, int 
 
 int launch_point_sample(const float* level0, int B, int S_, int H8, int W8, const float* xy, int N,
                         float* out, hipStream_t st) {
-    return launch_point_sample_strided(level0, B, S_, H8, W8, xy, 2, N, nullptr, out, st);
+    return launch_point_sample_strided(level0, B, S_, S_, H8, W8, xy, 2, N, nullptr, out, st);
 }
 
 // ------------------------------------------------------------------------ state init
@@ -121,7 +123,7 @@ struct LevelTable {
 // SCT: window length (mixer rows per particle) as a compile-time constant, 0 = the run-time argument Srt (Pips(S != 8))
 template <int SCT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void mixer_input_kernel(const float* __restrict__ pyramid,
-                                                          LevelTable lv, int S_, int Srt,
+                                                          LevelTable lv, int S_, int T_, int Srt,
                                                           const float* __restrict__ ffeats,
                                                           const float* __restrict__ coords,
                                                           const float* __restrict__ times, int N,
@@ -133,9 +135,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     const int m = blockIdx.x;
     const int s = m % S, pn = m / S;
     const int b = pn / N;
-    // The map buffer holds S_ frames per clip.  S_ = 8 with win_start == null is the plain
-    // forward; a longer cache + per-particle window start gives chained tracking, where frames
-    // past the end repeat the last one (chain_demo.py:50-52) = a clamp of the frame index.
+    // The map buffer holds S_ frame slots per clip and T_ logical frames.  S_ = T_ = 8 with
+    // win_start == null is the plain forward; a longer cache + per-particle window start gives
+    // chained tracking, where frames past the end repeat the last one (chain_demo.py:50-52) = a
+    // clamp of the frame index to T_ - 1.  Logical frame f lives in slot f mod S_ (a ring of
+    // S_ < T_ slots for streamed video; the identity for a linear cache, S_ = T_).
     // win_dir (sign per particle, null = forward): a backward window reads fstart, fstart-1, ...
     // and repeats frame 0 past the start -- the same loop on the time-reversed video.
     int fstart = 0, dir = 1;
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         fstart = win_start[pn];
         if (win_dir != nullptr) dir = win_dir[pn] < 0 ? -1 : 1;
     }
-    const int frame = b * S_ + min(max(fstart + dir * s, 0), S_ - 1);
+    const int frame = b * S_ + ring_slot(min(max(fstart + dir * s, 0), T_ - 1), S_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lvl = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float cxm = coords[(size_t)m * 2 + 0], cym = coords[(size_t)m * 2 + 1];
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 // lanes of a pixel group: lane r of group g ends with window row r >> 1, column 4 * (r & 1) + g.
 template <int SCT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void mixer_input_bf16maps_kernel(
-    const unsigned short* __restrict__ mirror, LevelTable lv, int S_, int Srt, const float* __restrict__ ffeats,
+    const unsigned short* __restrict__ mirror, LevelTable lv, int S_, int T_, int Srt, const float* __restrict__ ffeats,
     const float* __restrict__ coords, const float* __restrict__ times, int N, const int* __restrict__ win_start,
     const int* __restrict__ win_dir, float* __restrict__ X) {
     __shared__ float Dw[PIPS_LEVELS][64];
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         fstart = win_start[pn];
         if (win_dir != nullptr) dir = win_dir[pn] < 0 ? -1 : 1;
     }
-    const int frame = b * S_ + min(max(fstart + dir * s, 0), S_ - 1);
+    const int frame = b * S_ + ring_slot(min(max(fstart + dir * s, 0), T_ - 1), S_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lvl = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float cxm = coords[(size_t)m * 2 + 0], cym = coords[(size_t)m * 2 + 1];
@@ -373,16 +377,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 }
 
 int launch_mixer_input_bf16maps(const void* mirror, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B, int S_,
-                                const float* ffeats, const float* coords, const float* times, int N, const int* win_start,
-                                const int* win_dir, float* X, hipStream_t st, int Sw) {
+                                int T_, const float* ffeats, const float* coords, const float* times, int N,
+                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
     LevelTable lv;
     for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
     const unsigned short* mp = reinterpret_cast<const unsigned short*>(mirror);
     if (Sw == PIPS_S)
-        hipLaunchKernelGGL(mixer_input_bf16maps_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, mp, lv, S_, Sw, ffeats,
+        hipLaunchKernelGGL(mixer_input_bf16maps_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, mp, lv, S_, T_, Sw, ffeats,
                            coords, times, N, win_start, win_dir, X);
     else
-        hipLaunchKernelGGL(mixer_input_bf16maps_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, mp, lv, S_, Sw, ffeats,
+        hipLaunchKernelGGL(mixer_input_bf16maps_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, mp, lv, S_, T_, Sw, ffeats,
                            coords, times, N, win_start, win_dir, X);
     PIPS_CHECK_LAUNCH("mixer_input_bf16maps_kernel");
     return PIPS_OK;
@@ -404,16 +408,68 @@ int launch_pyramid_mirror(const float* pyramid, size_t floats, void* mirror, hip
     return PIPS_OK;
 }
 
+// ------------------------------------------------------------------ ring append
+// The levels of k freshly encoded frames -> slots (T0 + i) mod R of a ring pyramid, fp32 levels and bf16 mirror in one
+// pass (pyramid_mirror_kernel's rounding).  One thread = 8 channels of one pixel: two 16-byte loads, three 16-byte stores.
+// Threads are laid out level-major, each level k frames deep; `first` holds the first group of every level.
+struct AppendTable {
+    size_t src_off[PIPS_LEVELS], dst_off[PIPS_LEVELS];
+    unsigned pf8[PIPS_LEVELS];               // 8-float groups per frame of the level
+    unsigned first[PIPS_LEVELS + 1];
+};
+
+__global__ __launch_bounds__(256) void pyramid_append_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                             uint4* __restrict__ mirror, AppendTable t, int R, int s0) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= t.first[PIPS_LEVELS]) return;
+    // level of this thread by selects on the (uniform) table, never a dynamic index into the kernel arguments
+    size_t so = t.src_off[0], dof = t.dst_off[0];
+    unsigned pf = t.pf8[0], f0 = t.first[0];
+#pragma unroll
+    for (int l = 1; l < PIPS_LEVELS; ++l)
+        if (i >= t.first[l]) { so = t.src_off[l]; dof = t.dst_off[l]; pf = t.pf8[l]; f0 = t.first[l]; }
+    const unsigned r = i - f0;
+    const unsigned f = r / pf, e = r - f * pf;
+    int slot = s0 + (int)f;                  // s0 = T0 mod R and f < k <= R: at most one wrap
+    if (slot >= R) slot -= R;
+    const float4* sp = reinterpret_cast<const float4*>(src + so + ((size_t)f * pf + e) * 8);
+    const size_t d = dof + ((size_t)slot * pf + e) * 8;
+    const float4 a = sp[0], b = sp[1];
+    float4* dp = reinterpret_cast<float4*>(dst + d);
+    dp[0] = a;
+    dp[1] = b;
+    mirror[d / 8] = make_uint4(pack2_bf16(a.x, a.y), pack2_bf16(a.z, a.w), pack2_bf16(b.x, b.y), pack2_bf16(b.z, b.w));
+}
+
+int launch_pyramid_append(const float* src, const size_t* src_off, int k, float* dst, const size_t* dst_off, void* dst_mirror,
+                          const int* pf8, int R, int T0, hipStream_t st) {
+    AppendTable t;
+    size_t n = 0;
+    for (int l = 0; l < PIPS_LEVELS; ++l) {
+        t.src_off[l] = src_off[l];
+        t.dst_off[l] = dst_off[l];
+        t.pf8[l] = (unsigned)pf8[l];
+        t.first[l] = (unsigned)n;
+        n += (size_t)k * pf8[l];
+    }
+    PIPS_CHECK_ARG(n < (1u << 31), "pyramid_append: %zu pixel groups in one launch", n);
+    t.first[PIPS_LEVELS] = (unsigned)n;
+    hipLaunchKernelGGL(pyramid_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst,
+                       reinterpret_cast<uint4*>(dst_mirror), t, R, T0 % R);
+    PIPS_CHECK_LAUNCH("pyramid_append_kernel");
+    return PIPS_OK;
+}
+
 int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
-                       int B, int S_, const float* ffeats, const float* coords, const float* times,
+                       int B, int S_, int T_, const float* ffeats, const float* coords, const float* times,
                        int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
     LevelTable lv;
     for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
     if (Sw == PIPS_S)
-        hipLaunchKernelGGL(mixer_input_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, pyramid, lv, S_, Sw, ffeats,
+        hipLaunchKernelGGL(mixer_input_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, pyramid, lv, S_, T_, Sw, ffeats,
                            coords, times, N, win_start, win_dir, X);
     else
-        hipLaunchKernelGGL(mixer_input_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, pyramid, lv, S_, Sw, ffeats,
+        hipLaunchKernelGGL(mixer_input_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, pyramid, lv, S_, T_, Sw, ffeats,
                            coords, times, N, win_start, win_dir, X);
     PIPS_CHECK_LAUNCH("mixer_input_kernel");
     return PIPS_OK;

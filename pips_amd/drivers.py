@@ -9,6 +9,9 @@
 * ``track_queries`` -- the same chaining from a query frame ``t`` per point, forwards to the end and
   backwards to frame 0 (the reference's loop on ``rgbs[:, t:]`` and on ``rgbs[:, :t+1].flip(1)``):
   one encoder pass, both directions in the same hop launches (per-particle ``win_dir``).
+* ``StreamTracker`` / ``track_stream`` -- ``track_queries``' forward chains on a video fed in chunks: frames are
+  encoded into a ring of ``slots`` frames (``Pips.ring_cache``) and trajectories come back as frames become final,
+  so device memory does not grow with the length of the video.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -56,6 +59,33 @@ def skip_scan(vis):
     return last + 2
 
 
+def _hop(model, cache, trajs, vis_p, base, cur, active, feat, d=None, iters=6):
+    """One window of chain_demo.py:40-83 for each particle in ``active``: its start position is its trajectory at its window
+    start ``cur[active]`` (logical frames), its rows are written back and ``skip_scan`` gives the step.  trajs (L,n,2) and
+    vis_p (L,n) (or None) hold frame f in row (f + base) mod L.  feat: (n,128) features carried from the first window, or
+    None (the track call samples them); d: the active particles' directions (+1 / -1) or None (all forward).
+    -> (the new window starts of ``active``, their steps si, the features of this call (n_active,128))."""
+    S = 8
+    L = trajs.shape[0]
+    c = cur[active]
+    start_xy = trajs[(c + base) % L, active].unsqueeze(0)                        # traj_e[:,cur_frame]
+    fi = None if feat is None else feat[active].unsqueeze(0)
+    rows = torch.arange(S, device=c.device).unsqueeze(1)                         # (S,1)
+    kw = {}
+    if d is not None:
+        kw["win_dir"] = d.to(torch.int32).unsqueeze(0)
+        rows = rows * d.unsqueeze(0)                                              # row s of a window is frame c + d * s
+    preds, _, vis, ffeat, _ = model.track(cache, start_xy, iters=iters, feat_init=fi,
+                                          win_start=c.to(torch.int32).unsqueeze(0), return_feat=True, **kw)
+    rows = (c.unsqueeze(0) + rows + base) % L                                     # (S,n)
+    cols = active.unsqueeze(0).expand(S, -1)
+    trajs[rows, cols] = preds[-1][0]                                              # traj_e[cur:cur+8] = xys[:S_local]
+    if vis_p is not None:
+        vis_p[rows, cols] = vis[0]
+    si = skip_scan(torch.sigmoid(vis[0]))
+    return c + (si if d is None else si * d), si, ffeat[0]
+
+
 def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
     """The hop loop of chain_demo.py:40-83 for all particles at once.  xy (n,2) px at frames f0 (n,) int64; dirs (n,) +1 / -1
     per particle or None (all forward).  A backward particle runs the loop on the time-reversed video: its window rows
@@ -63,44 +93,26 @@ def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
     -> trajs (T,n,2), vis (T,n) logits (None without ``with_vis``) -- each frame from the last window that wrote it -- and
     the hop log [(active, si)]."""
     dev = xy.device
-    S = 8
-    pad = S - 1
+    pad = 7
     n = xy.shape[0]
     # S - 1 frames of padding on both sides of the video: a window that runs past either end is written whole and cut off
     # on return (no per-row masks, no host round trips inside a hop)
-    trajs = torch.zeros(1, T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
-    vis_p = torch.zeros(1, T + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
+    trajs = torch.zeros(T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
+    vis_p = torch.zeros(T + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
     active = torch.arange(n, device=dev)
-    cur = f0 + pad                                                                 # window starts in padded frames
-    trajs[0, cur, active] = xy.to(torch.float32)
-    offs = torch.arange(S, device=dev).unsqueeze(1)                                # (S,1)
+    cur = f0.clone()                                                               # window starts
+    trajs[cur + pad, active] = xy.to(torch.float32)
     feat = None
     log = []
     while active.numel() > 0:
-        c = cur[active]
-        start_xy = trajs[0, c, active].unsqueeze(0)                               # traj_e[:,cur_frame]
-        fi = None if feat is None else feat[active].unsqueeze(0)
-        kw, rows = {}, offs
-        if dirs is not None:
-            d = dirs[active]
-            kw["win_dir"] = d.to(torch.int32).unsqueeze(0)
-            rows = offs * d.unsqueeze(0)                                          # row s of a window is frame c + d * s
-        preds, _, vis, ffeat, _ = model.track(cache, start_xy, iters=iters, feat_init=fi,
-                                              win_start=(c - pad).to(torch.int32).unsqueeze(0), return_feat=True, **kw)
+        c, si, ffeat = _hop(model, cache, trajs, vis_p, pad, cur, active, feat, None if dirs is None else dirs[active], iters)
         if feat is None:
-            feat = ffeat[0].clone()                                              # carried forever (:57)
-        rows = c.unsqueeze(0) + rows                                              # (S,n)
-        cols = active.unsqueeze(0).expand(S, -1)
-        trajs[0, rows, cols] = preds[-1][0]                                       # traj_e[cur:cur+8] = xys[:S_local]
-        if vis_p is not None:
-            vis_p[0, rows, cols] = vis[0]
-        si = skip_scan(torch.sigmoid(vis[0]))
-        c = c + (si if dirs is None else si * d)
+            feat = ffeat.clone()                                                   # carried forever (:57)
         cur[active] = c
         log.append((active, si))
-        live = c < T + pad if dirs is None else (c < T + pad) & (c >= pad)
+        live = c < T if dirs is None else (c < T) & (c >= 0)
         active = active[live]                                                     # (one host sync per hop: the live count)
-    return trajs[0, pad:pad + T], None if vis_p is None else vis_p[0, pad:pad + T], log
+    return trajs[pad:pad + T], None if vis_p is None else vis_p[pad:pad + T], log
 
 
 def _hops(log, n):
@@ -129,6 +141,19 @@ def track_chained(model, rgbs, xy0, iters=6, return_hops=False):
     return out, _hops(log, N)
 
 
+def _query_frames(queries, T=None):
+    """queries (1,N,3) = (t, x, y) -> t as int64 on the host; ValueError unless every t is an integer in [0, T-1] (T = None:
+    no upper bound)."""
+    if queries.dim() != 3 or queries.shape[0] != 1 or queries.shape[2] != 3:
+        raise ValueError(f"queries must be (1,N,3) = (t, x, y), not {tuple(queries.shape)}")
+    t = queries[0, :, 0].detach().to("cpu", torch.float64)
+    hi = float("inf") if T is None else T - 1
+    if not bool(torch.isfinite(t).all()) or not torch.equal(t, t.round()) or bool(((t < 0) | (t > hi)).any()):
+        raise ValueError("query frames must be non-negative integers" if T is None else
+                         f"query frames must be integers in [0, {T - 1}]")
+    return t.to(torch.int64)
+
+
 @torch.no_grad()
 def track_queries(model, rgbs, queries, iters=6, return_hops=False):
     """Track query points from any frame over the whole video, forwards and backwards in time.
@@ -146,12 +171,7 @@ def track_queries(model, rgbs, queries, iters=6, return_hops=False):
     assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
     dev = rgbs.device
     T, N = rgbs.shape[1], queries.shape[1]
-    if queries.dim() != 3 or queries.shape[2] != 3:
-        raise ValueError(f"queries must be (1,N,3) = (t, x, y), not {tuple(queries.shape)}")
-    t = queries[0, :, 0].detach().to("cpu", torch.float64)
-    if not bool(torch.isfinite(t).all()) or not torch.equal(t, t.round()) or bool(((t < 0) | (t > T - 1)).any()):
-        raise ValueError(f"query frames must be integers in [0, {T - 1}]")
-    tq = t.to(torch.int64)
+    tq = _query_frames(queries, T)
     back = torch.nonzero(tq > 0).squeeze(1)
     nb = back.numel()
     xy = queries[0, :, 1:3].to(dev, torch.float32)
@@ -172,3 +192,150 @@ def track_queries(model, rgbs, queries, iters=6, return_hops=False):
     for j, q in enumerate(back.tolist()):
         bwd[q] = hops[N + j]
     return trajs, vis, (hops[:N], bwd)
+
+
+class StreamTracker:
+    """``track_queries``' forward chains on a video that arrives in chunks, in bounded device memory.
+
+    queries (1,N,3) = (t, x, y) as for ``track_queries``; ``t`` may lie beyond the frames pushed so far.  ``push(frames)`` takes
+    the next ``(1,k,3,H,W)`` frames (host or device, uint8 or float, 0..255) and returns ``(f0, trajs (1,m,N,2), vis (1,m,N))``
+    for the frames ``[f0, f0+m)`` that became final (``m`` may be 0); ``finish()`` ends the video and returns the rest.
+    Frame ``t >= t_q`` of a query is the reference's chaining loop (chain_demo.py:40-83) on ``rgbs[:, t_q:]`` -- the forward
+    frames of ``track_queries`` -- and frames before ``t_q`` are NaN (no backward tracking).
+
+    Frames are encoded once into a ring of ``slots`` frames (``Pips.ring_cache``).  A window runs once its 8 frames have
+    arrived (at ``finish()``, past the last frame it repeats it, chain_demo.py:50-52); each round is one ``model.track``
+    call over every ready particle, new ones joining with their first-window features (the same point sample as
+    ``feat_init=None``).  A frame is final when it lies below every unfinished particle's window start.  ``push`` splits
+    a chunk so that no slot is overwritten while a pending window can still read it: ``slots >= 9`` keeps the 8 frames of
+    a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query."""
+
+    S = 8
+
+    def __init__(self, model, queries, iters=6, slots=24, record_hops=False):
+        assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
+        if int(slots) < self.S + 1:
+            raise ValueError(f"slots must be at least {self.S + 1} (one window and a new frame), not {slots}")
+        self.model, self.iters, self.slots = model, iters, int(slots)
+        self.tq_host = _query_frames(queries)
+        self.xy_in = queries[0, :, 1:3]
+        self.N = self.tq_host.numel()
+        self.cache = None
+        self.finished = False
+        self.hops = [[] for _ in range(self.N)] if record_hops else None       # frame steps per query (grows with T)
+
+    def _start(self, frames):
+        self.size = tuple(frames.shape[3:])
+        self.cache = c = self.model.ring_cache(*self.size, self.slots)
+        dev = c.device
+        L = self.slots + self.S                                                   # output rows: frames f live in row f % L
+        self.L = L
+        self.trajs = torch.full((L, self.N, 2), float("nan"), dtype=torch.float32, device=dev)
+        self.vis = torch.full((L, self.N), float("nan"), dtype=torch.float32, device=dev)
+        self.tq = self.tq_host.to(dev)
+        self.xy = self.xy_in.to(dev, torch.float32)
+        self.cur = self.tq.clone()                                                # window start (= t_q until it joins)
+        self.joined = torch.zeros(self.N, dtype=torch.bool, device=dev)
+        self.done = torch.zeros(self.N, dtype=torch.bool, device=dev)
+        self.feat = None                                                          # (N,128) features of the first windows
+        self.emitted = 0                                                          # frames [0, emitted) returned
+
+    def _pending(self):
+        """lowest window start of the unfinished particles (None when all are finished)"""
+        live = self.cur[~self.done]
+        return None if live.numel() == 0 else int(live.min())
+
+    @torch.no_grad()
+    def push(self, frames):
+        if self.finished:
+            raise ValueError("push() after finish()")
+        if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[2] != 3:
+            raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(frames.shape)}")
+        if self.cache is None:
+            self._start(frames)
+        elif tuple(frames.shape[3:]) != self.size:
+            raise ValueError(f"frames of {tuple(frames.shape[3:])} pushed to a stream of {self.size}")
+        f0, outs = self.emitted, []
+        k, i = frames.shape[1], 0
+        while i < k:
+            low = self._pending()
+            # the slot of frame T + j holds frame T + j - slots until then: no pending window may still read that one
+            room = self.slots if low is None else min(self.slots, low + self.slots - self.cache.T)
+            n = min(k - i, room)
+            self.model.encode(frames[:, i:i + n], into=self.cache)
+            i += n
+            self._rounds(final=False)
+            outs.append(self._emit())
+        return self._cat(f0, outs)
+
+    @torch.no_grad()
+    def finish(self):
+        if self.finished:
+            raise ValueError("finish() called twice")
+        T = 0 if self.cache is None else self.cache.T
+        if bool((self.tq_host > T - 1).any()):
+            raise ValueError(f"a query frame lies beyond the last frame of the video ({T - 1})")
+        self.finished = True
+        f0 = self.emitted
+        self._rounds(final=True)
+        return self._cat(f0, [self._emit()])
+
+    def _rounds(self, final):
+        """hop rounds until no particle is ready: one whose 8 window frames have all arrived (final: every unfinished one)"""
+        T = self.cache.T
+        while True:
+            ready = ~self.done & ((self.cur < T) if final else (self.cur + self.S <= T))
+            active = torch.nonzero(ready).squeeze(1)
+            if active.numel() == 0:
+                return
+            new = active[~self.joined[active]]
+            if new.numel() > 0:
+                # first window: the start is the query and the features are its point sample at t_q (feat_init=None)
+                self.trajs[self.tq[new] % self.L, new] = self.xy[new]
+                ff = self.model.track(self.cache, self.xy[new].unsqueeze(0), iters=0, return_feat=True,
+                                      win_start=self.tq[new].to(torch.int32).unsqueeze(0))[3]
+                if self.feat is None:
+                    self.feat = ff.new_zeros(self.N, ff.shape[-1])
+                self.feat[new] = ff[0]
+                self.joined[new] = True
+            c, si, _ = _hop(self.model, self.cache, self.trajs, self.vis, 0, self.cur, active, self.feat, None, self.iters)
+            self.cur[active] = c
+            if final:
+                self.done[active] = c >= T
+            if self.hops is not None:
+                for q, h in zip(active.tolist(), si.tolist()):
+                    self.hops[q].append(h)
+
+    def _emit(self):
+        """the rows of the frames that became final, moved out of the ring (their rows are reset to NaN for reuse)"""
+        low = self._pending()
+        end = self.cache.T if low is None else min(low, self.cache.T)
+        if end <= self.emitted:
+            return None
+        rows = torch.arange(self.emitted, end, device=self.trajs.device) % self.L
+        out = (self.trajs[rows], self.vis[rows])
+        self.trajs[rows] = float("nan")
+        self.vis[rows] = float("nan")
+        self.emitted = end
+        return out
+
+    def _cat(self, f0, outs):
+        outs = [o for o in outs if o is not None]
+        if not outs:
+            dev = self.cache.device if self.cache is not None else self.xy_in.device
+            return f0, torch.empty(1, 0, self.N, 2, device=dev), torch.empty(1, 0, self.N, device=dev)
+        return f0, torch.cat([o[0] for o in outs]).unsqueeze(0), torch.cat([o[1] for o in outs]).unsqueeze(0)
+
+
+@torch.no_grad()
+def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False):
+    """``StreamTracker`` over an iterable of ``(1,k,3,H,W)`` chunks -> trajs_e (1,T,N,2) px and vis_e (1,T,N) logits, NaN
+    before each query's frame.  ``return_hops=True``: also, per query, the frame steps of its windows."""
+    st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=return_hops)
+    parts = [st.push(c) for c in chunks]
+    parts.append(st.finish())
+    trajs = torch.cat([p[1] for p in parts], dim=1)
+    vis = torch.cat([p[2] for p in parts], dim=1)
+    if not return_hops:
+        return trajs, vis
+    return trajs, vis, st.hops

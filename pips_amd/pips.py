@@ -37,15 +37,25 @@ class FeatureCache:
     """Encoder output kept on the device for re-use: the packed 4-level channel-last pyramid of
     ``B`` clips x ``T`` frames (``T`` need not be 8).  Produced by ``Pips.encode``, consumed by
     ``Pips.track``.  Per-frame InstanceNorm (nets/pips.py:153-157) makes a frame's maps
-    independent of which clip/window it sits in, so the cache is exact for any window."""
+    independent of which clip/window it sits in, so the cache is exact for any window.
 
-    def __init__(self, pyr, B, T, H, W, stride, bf16_maps=False):
+    ``slots``: frame slots the buffer is laid out for (default ``T``: a linear cache).  A ring cache
+    (``Pips.ring_cache``) has a fixed number of slots and grows ``T`` as frames are appended
+    (``Pips.encode(..., into=cache)``); logical frame ``f`` lives in slot ``f % slots``, so only the
+    last ``slots`` frames are held."""
+
+    def __init__(self, pyr, B, T, H, W, stride, bf16_maps=False, slots=None):
         self.pyr, self.B, self.T, self.H, self.W, self.stride = pyr, B, T, H, W, stride
         self.bf16_maps = bf16_maps          # the buffer's bf16 mirror is valid (written by the bf16 encoder): PIPS_FLAG_BF16_MAPS
+        self.slots = T if slots is None else int(slots)
 
     @property
     def map_size(self):
         return self.H // self.stride, self.W // self.stride
+
+    @property
+    def device(self):
+        return self.pyr.device
 
 
 class _Node(nn.Module):
@@ -251,11 +261,33 @@ class Pips(nn.Module):
 
     # ------------------------------------------------------------------ encoder / tracker split
     @torch.no_grad()
-    def encode(self, rgbs, frames_per_pass: int = 16) -> FeatureCache:
+    def ring_cache(self, H: int, W: int, slots: int, device=None) -> FeatureCache:
+        """An empty ring ``FeatureCache`` of ``slots`` frame slots for one video of ``H x W`` frames (B = 1, T = 0) on
+        ``device`` (default: the module's).  Fill it with ``encode(rgbs, into=cache)``; device memory is
+        ``pips_pyramid_floats(slots, H, W, stride)`` floats whatever the length of the video."""
+        if int(slots) < 1:
+            raise ValueError("a ring cache needs at least one frame slot")
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.PipsHipError("pips_amd.Pips needs CUDA/HIP tensors; there is no CPU fallback")
+        lib = _lib.load()
+        st = int(self.stride)
+        pyr = torch.zeros(lib.pips_pyramid_floats(int(slots), H, W, st), dtype=torch.float32, device=dev)
+        return FeatureCache(pyr, 1, 0, H, W, st, slots=int(slots))
+
+    @torch.no_grad()
+    def encode(self, rgbs, frames_per_pass: int = 16, into: FeatureCache = None) -> FeatureCache:
         """BasicEncoder + pyramid of every frame of ``rgbs (B,T,3,H,W)`` (0..255), once.
         Replaces the per-chunk / per-hop encoder re-runs of test_on_davis.py:116-118 and
         chain_demo.py:54.  Frames are encoded ``frames_per_pass`` at a time to bound the
-        activation workspace for long videos."""
+        activation workspace for long videos.
+
+        ``into``: a ring cache (``ring_cache``) the frames are appended to instead, B = 1: each pass of at most
+        ``frames_per_pass`` (and ``into.slots``) frames is copied into the next slots, wrapping, with its bf16 mirror
+        (``pips_pyramid_append``), and ``into.T`` grows by the number of frames.  ``rgbs`` may then be a host tensor, uint8
+        or float.  Returns ``into``."""
+        if into is not None:
+            return self._append(rgbs, frames_per_pass, into)
         if not rgbs.is_cuda:
             raise _lib.PipsHipError("pips_amd.Pips needs CUDA/HIP tensors; there is no CPU fallback")
         lib = _lib.load()
@@ -284,6 +316,28 @@ class Pips(nn.Module):
                                "pips_pyramid_mirror")
         return FeatureCache(pyr, B, T, H, W, st, bf16_maps=eb and not sp)
 
+    def _append(self, rgbs, frames_per_pass, cache):
+        lib = _lib.load()
+        B, T, C3, H, W = rgbs.shape
+        if B != 1 or cache.B != 1 or C3 != 3 or (H, W) != (cache.H, cache.W) or int(self.stride) != cache.stride:
+            raise ValueError(f"frames {tuple(rgbs.shape)} do not fit a ring cache of 1 x {cache.H} x {cache.W}, stride {cache.stride}")
+        dev, st = cache.device, cache.stride
+        step = max(1, min(int(frames_per_pass), cache.slots))
+        with torch.cuda.device(dev):
+            arena = self._aux(dev)[0]
+            eb = bool(self._flags() & 4)
+            sp = bool(self._flags() & 16)
+            for f0 in range(0, T, step):
+                f1 = min(T, f0 + step)
+                part = rgbs[0, f0:f1].to(dev)
+                part = part if part.dtype == torch.uint8 else part.to(torch.float32)
+                pyr = ops.encoder_fwd(arena, part, st, bf16=eb, split=sp)
+                _lib.check(lib.pips_pyramid_append(_lib.ptr(pyr), f1 - f0, _lib.ptr(cache.pyr), cache.slots, cache.T, H, W, st,
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pips_pyramid_append")
+                cache.T += f1 - f0
+        cache.bf16_maps = eb and not sp          # as for a cache encode() returns: the gather may read the mirror
+        return cache
+
     @torch.no_grad()
     def track(self, cache: FeatureCache, xys, coords_init=None, feat_init=None, iters=3, win_start=None,
               return_feat=False, win_dir=None):
@@ -292,7 +346,8 @@ class Pips(nn.Module):
         frames (default 0); frames past the end repeat the last one (chain_demo.py:50-52).
         ``win_dir`` ``(B,N)`` int, its sign = the time direction of each particle's window (default: all
         forward): row ``s`` of a backward window reads frame ``win_start - s``, frames before 0 repeat
-        frame 0 -- the same loop on the time-reversed video.
+        frame 0 -- the same loop on the time-reversed video.  On a ring cache (``cache.slots != cache.T``)
+        frame ``f`` is read from slot ``f % cache.slots``: every frame a window reads must still be held.
         Returns the same tuple as ``forward`` (losses = None)."""
         lib = _lib.load()
         B, N, D = xys.shape
@@ -306,7 +361,7 @@ class Pips(nn.Module):
         wd_i = None if win_dir is None else win_dir.to(dev).contiguous().to(torch.int32)
         if ws_i is not None:
             assert tuple(ws_i.shape) == (B, N)
-        elif cache.T != S or wd_i is not None:
+        elif cache.T != S or cache.slots != cache.T or wd_i is not None:
             ws_i = torch.zeros(B, N, dtype=torch.int32, device=dev)
         if wd_i is not None:
             assert tuple(wd_i.shape) == (B, N)
@@ -326,11 +381,11 @@ class Pips(nn.Module):
             trajs = torch.empty(iters + 1, B, S, N, 2, dtype=f32, device=dev)
             vis_e = torch.empty(B, S, N, dtype=f32, device=dev)
             ffeat = torch.empty(B, N, self.latent_dim, dtype=f32, device=dev)
-            rc = lib.pips_track_win(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, H8, W8, _lib.ptr(xys_c), _lib.ptr(ci),
-                                    _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(times), N, int(cache.stride), int(iters),
-                                    fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs), _lib.ptr(vis_e),
-                                    _lib.ptr(ffeat), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "pips_track_win")
+            rc = lib.pips_track_ring(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
+                                     _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(times), N,
+                                     int(cache.stride), int(iters), fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs),
+                                     _lib.ptr(vis_e), _lib.ptr(ffeat), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.check(rc, "pips_track_ring")
         preds = [trajs[i + 1] for i in range(iters)]
         preds2 = [trajs[0], trajs[0]] + preds + [trajs[iters], trajs[iters]]
         if return_feat:

@@ -1,0 +1,120 @@
+"""Streamed tracking at the BASELINE configs[4] geometry: drivers.track_stream against track_queries and track_chained.
+
+360x640 frames, stride 4, 256 query points (a 16 x 16 grid) split over frames 0/33/66/99, seeded synthetic uint8 frames made
+on the host, chunks of 16 frames, a ring of 24 slots.  Prints one JSON line:
+  * wall time of each driver at T = 100 (median of --reps calls after a warm-up; the linear drivers get the video on the
+    device, the stream gets host chunks);
+  * peak torch.cuda.max_memory_allocated above the pre-call allocation at T = 100 and T = --long (1000), the device video of
+    the linear drivers included;
+  * the bytes pips_pyramid_append moves per frame (fp32 read + fp32 write + bf16 mirror write), for the kernel-trace run.
+The append kernel's time comes from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only stream``."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from pips_amd import Pips, _lib, drivers  # noqa: E402
+from pips_amd.weights import init_state_dict  # noqa: E402
+
+H, W, STRIDE, N, CHUNK, SLOTS = 360, 640, 4, 256, 16, 24
+
+
+def frames(t0, k, seed=5):
+    """frames t0 .. t0+k-1 of a seeded synthetic video (a textured image drifting by one pixel per frame + noise), uint8"""
+    g = torch.Generator().manual_seed(seed)
+    base = torch.randint(0, 256, (3, H // 8, W // 8), generator=g).float()
+    base = torch.nn.functional.interpolate(base[None], size=(H, W), mode="bilinear", align_corners=False)[0]
+    out = []
+    for t in range(t0, t0 + k):
+        gt = torch.Generator().manual_seed(seed * 100003 + t)
+        f = torch.roll(base, shifts=(t // 3, t), dims=(1, 2)) + torch.randint(0, 12, (3, H, W), generator=gt).float()
+        out.append(f.clamp(0, 255).to(torch.uint8))
+    return torch.stack(out).unsqueeze(0)
+
+
+def chunks(host):
+    for t0 in range(0, host.shape[1], CHUNK):
+        yield host[:, t0:t0 + CHUNK]
+
+
+def queries(dev):
+    gy, gx = torch.meshgrid(torch.linspace(16, H - 17, 16), torch.linspace(16, W - 17, 16), indexing="ij")
+    t = torch.tensor([(0, 33, 66, 99)[n % 4] for n in range(N)], dtype=torch.float32)
+    return torch.stack([t, gx.reshape(-1), gy.reshape(-1)], -1).unsqueeze(0).to(dev)
+
+
+def run(name, m, q, host, video=None):
+    if name == "stream":
+        return drivers.track_stream(m, chunks(host), q, iters=6, slots=SLOTS)
+    if name == "queries":
+        return drivers.track_queries(m, video, q, iters=6)
+    return drivers.track_chained(m, video, q[:, :, 1:], iters=6)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t
+
+
+def peak(fn):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    start = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - start
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=100)
+    ap.add_argument("--long", type=int, default=1000, help="video length of the second memory point (0: skip)")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--only", default="all", choices=["all", "stream"], help="stream: time the stream alone (kernel trace)")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    m = Pips(S=8, stride=STRIDE)
+    m.load_state_dict(init_state_dict(0, tamed=True))
+    m = m.to(dev).eval()
+    q = queries(dev)
+    names = ["stream"] if a.only == "stream" else ["stream", "queries", "chained"]
+    res = {"config": "360x640 stride 4, N=256 over frames 0/33/66/99, chunks of 16, slots 24", "T": a.T}
+    host = frames(0, a.T)                                               # host uint8 video: the stream is fed host chunks
+    video = None if a.only == "stream" else host.to(dev)
+    for name in names:
+        run(name, m, q, host, video)                                    # warm-up: weights, workspaces
+        ts = [timed(lambda: run(name, m, q, host, video)) for _ in range(a.reps)]
+        res[f"{name}_s"] = round(statistics.median(ts), 4)
+    del video
+    if a.only == "all":
+        for T in [a.T] + ([a.long] if a.long else []):
+            host = frames(0, T)
+            for name in names:
+                def call():
+                    v = None if name == "stream" else host.to(dev)
+                    run(name, m, q, host, v)
+                try:
+                    res[f"{name}_peak_MiB_T{T}"] = round(peak(call) / 2**20, 1)
+                except torch.cuda.OutOfMemoryError:
+                    res[f"{name}_peak_MiB_T{T}"] = None
+                    torch.cuda.empty_cache()
+    lib = _lib.load()
+    fl = lib.pips_pyramid_mirror_offset(1, H, W, STRIDE)
+    res["pyramid_MiB_per_frame"] = round(lib.pips_pyramid_floats(1, H, W, STRIDE) * 4 / 2**20, 2)
+    res["append_bytes_per_frame"] = fl * (4 + 4 + 2)
+    res["frames_appended"] = (1 + a.reps) * a.T if "stream" in names else 0
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
