@@ -160,30 +160,8 @@ __global__ void cvt_bf16_kernel(const float* __restrict__ src, __bf16* __restric
 
 static inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 
-}  // namespace pips
-
-using namespace pips;
-
-extern "C" {
-
-const char* pips_last_error(void) { return g_err; }
-int pips_abi_version(void) { return 3; }
-
-size_t pips_weight_arena_bytes(void) { return pips_weight_arena_bytes_s(PIPS_S); }
-int pips_delta_stride(int S) { return (S < 1 || S > PIPS_S_MAX) ? 0 : arena_layout(S).nout_pad; }
-size_t pips_weight_arena_bytes_s(int S) {
-    if (S < 1 || S > PIPS_S_MAX) return 0;
-    return arena_layout(S).total_all * sizeof(float);
-}
-
-int pips_repack_weights(const void* const* params, int nparams, void* arena_v, void* stream) {
-    return pips_repack_weights_s(params, nparams, arena_v, PIPS_S, PIPS_PACK_FP32 | PIPS_PACK_BF16 | PIPS_PACK_SPLIT, stream);
-}
-int pips_repack_weights_ex(const void* const* params, int nparams, void* arena_v, int sections, void* stream) {
-    return pips_repack_weights_s(params, nparams, arena_v, PIPS_S, sections, stream);
-}
-
-int pips_repack_weights_s(const void* const* params, int nparams, void* arena_v, int S, int sections, void* stream) {
+// pips_repack_weights*: the sections of the arena for window length S, from the reference state dict
+static int repack_weights(const void* const* params, int nparams, void* arena_v, int S, int sections, void* stream) {
     PIPS_CHECK_ARG(arena_v != nullptr, "repack: null pointer");
     PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "repack: S=%d outside 1..%d", S, PIPS_S_MAX);
     PIPS_CHECK_ARG(sections != 0 && (sections & ~(PIPS_PACK_FP32 | PIPS_PACK_BF16 | PIPS_PACK_SPLIT)) == 0, "repack: bad section mask %d", sections);
@@ -271,91 +249,133 @@ int pips_repack_weights_s(const void* const* params, int nparams, void* arena_v,
     return PIPS_OK;
 }
 
-// ------------------------------------------------------------------ building blocks
-int pips_gemm_f32(const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int N,
-                  int K, int epi, const float* R, int ldr, void* stream) {
-    PIPS_CHECK_ARG(A && W && C, "gemm: null pointer");
-    PIPS_CHECK_ARG((epi & 0xff) <= 2 && ((epi & 0xff) != EPI_RESIDUAL || R != nullptr), "gemm: bad epilogue");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.W = W; g.bias = bias; g.C = C; g.R = R;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.epi = epi;
-    return launch_gemm(g, (hipStream_t)stream);
-}
+}  // namespace pips
 
-int pips_split_bf16x3(const float* src, size_t n, void* dst3, void* stream) {
-    PIPS_CHECK_ARG(src && dst3, "split_bf16x3: null pointer");
-    return launch_split_bf16x3(src, n, dst3, (hipStream_t)stream);
-}
+using namespace pips;
 
-int pips_gemm_f32x3(const float* A, int lda, const void* W3, const float* bias, float* C, int ldc, int M, int N,
-                    int K, int epi, const float* R, int ldr, void* stream) {
-    PIPS_CHECK_ARG(A && W3 && C, "gemm_x3: null pointer");
-    PIPS_CHECK_ARG((epi & 0xff) <= 2 && ((epi & 0xff) != EPI_RESIDUAL || R != nullptr), "gemm_x3: bad epilogue");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.W = (const float*)W3; g.bias = bias; g.C = C; g.R = R;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.epi = epi;
-    return launch_gemm_x3(g, (hipStream_t)stream);
-}
-
-// mm: 0 exact-fp32 MFMA, 1 bf16 operands (RNE), 2 split-bf16 (wgt points at the matching weight form)
-// in_bf16 / out_bf16 (mm == 1 only): the NHWC maps themselves are bf16; in_norm: see GemmArgs
-static int conv_nhwc(const float* in, int F, int H, int W, int Cin, const float* wgt, const float* bias, int Cout,
-                     int k, int s, int p, float* out, float* stats, int* tiles, hipStream_t st, int bf16 = 0,
-                     int in_bf16 = 0, int out_bf16 = 0, const float* in_norm = nullptr, int parts_cap = 0) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = in; g.W = wgt; g.bias = bias; g.C = out; g.stats = stats; g.in_norm = in_norm; g.stats_parts_cap = parts_cap;
-    g.H = H; g.Win = W; g.Cin = Cin; g.KH = g.KW = k; g.cstride = s; g.pad = p;
-    g.Ho = conv_out(H, k, s, p); g.Wo = conv_out(W, k, s, p);
-    g.M = g.Ho * g.Wo; g.N = Cout; g.K = k * k * Cin; g.ldc = Cout; g.epi = EPI_BIAS;
-    PIPS_CHECK_ARG(g.Ho > 0 && g.Wo > 0, "conv: empty output");
-    if (bf16 == 2) return launch_conv_x3(g, F, tiles, st);
-    PIPS_CHECK_ARG(bf16 == 1 || (!in_bf16 && !out_bf16 && !in_norm), "conv: bf16 maps need the bf16-operand kernels");
-    return bf16 ? launch_conv_bf16(g, F, tiles, st, in_bf16, out_bf16) : launch_conv(g, F, tiles, st);   // bf16: wgt points at bf16 data
-}
-
-int pips_conv_nhwc_bf16_maps(const void* in_bf16, const float* in_norm, int F, int H, int W, int Cin, const void* wgt_bf16,
-                             const float* bias, int Cout, int ksize, int cstride, int pad, void* out, int out_is_bf16,
-                             float* stats, int stats_parts_cap, int* tiles_m_host, void* stream) {
-    PIPS_CHECK_ARG(in_bf16 && wgt_bf16 && out, "conv_bf16_maps: null pointer");
-    return conv_nhwc((const float*)in_bf16, F, H, W, Cin, (const float*)wgt_bf16, bias, Cout, ksize, cstride, pad, (float*)out,
-                     stats, tiles_m_host, (hipStream_t)stream, 1, 1, out_is_bf16 ? 1 : 0, in_norm, stats_parts_cap);
-}
-
-int pips_conv_nhwc_f32x3(const float* in, int F, int H, int W, int Cin, const void* wgt3, const float* bias,
-                         int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
-                         void* stream) {
-    PIPS_CHECK_ARG(in && wgt3 && out, "conv_x3: null pointer");
-    return conv_nhwc(in, F, H, W, Cin, (const float*)wgt3, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host,
-                     (hipStream_t)stream, 2);
-}
-
-int pips_conv_nhwc_bf16(const float* in, int F, int H, int W, int Cin, const void* wgt_bf16, const float* bias,
-                        int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
-                        void* stream) {
-    PIPS_CHECK_ARG(in && wgt_bf16 && out, "conv_bf16: null pointer");
-    return conv_nhwc(in, F, H, W, Cin, (const float*)wgt_bf16, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host,
-                     (hipStream_t)stream, 1);
-}
-
-int pips_conv_nhwc_f32(const float* in, int F, int H, int W, int Cin, const float* wgt, const float* bias,
-                       int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
-                       void* stream) {
-    PIPS_CHECK_ARG(in && wgt && out, "conv: null pointer");
-    return conv_nhwc(in, F, H, W, Cin, wgt, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host,
-                     (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------ encoder
+// ------------------------------------------------------------------ host-side plumbing
+// Everything down to the extern "C" block at the end of the file is internal: ONE implementation per stage, taking a
+// zero-initialised call descriptor the exported wrappers fill field by field.
 namespace {
+
+#define RUN(x) do { int rc__ = (x); if (rc__ != PIPS_OK) return rc__; } while (0)
 
 struct Bump {
     size_t off = 0;
     size_t take(size_t floats) { size_t o = off; off += (floats + 63) / 64 * 64; return o; }
 };
 
+// How the matrix products of a stage run: exact-fp32 MFMA, bf16 operands (RNE), or split-bf16 (fp32-grade, three bf16 planes)
+enum MatMode { EXACT, BF16, SPLIT };
+// the encoder's convolutions; BF16 also means bf16 activation maps (the rounding points of the reference under
+// torch.autocast(bfloat16)); SPLIT wins over BF16
+MatMode encoder_mode(int flags) {
+    if (flags & PIPS_FLAG_SPLIT_BF16) return SPLIT;
+    return (flags & PIPS_FLAG_BF16_ENCODER) ? BF16 : EXACT;
+}
+// the mixer's Linears.  bf16_stream (BF16 only, honoured at S = 8 only): the residual stream x is stored as bf16 -- written by
+// the input projection, read and rewritten by token mixing and the down-projection (whose fp32 sums take the bf16 residual and are
+// rounded once), read by the final LayerNorm; what PreNormResidual holds under autocast (nets/pips.py:93-100)
+struct MixerMode { MatMode mode; bool bf16_stream; };
+MixerMode mixer_mode(int flags) {
+    MixerMode m = {EXACT, false};
+    if (flags & PIPS_FLAG_SPLIT_BF16) m.mode = SPLIT;
+    else if (flags & PIPS_FLAG_BF16_MIXER) { m.mode = BF16; m.bf16_stream = (flags & PIPS_FLAG_BF16_STREAM) != 0; }
+    return m;
+}
+
+// HIP events of a timed entry point: created together, destroyed with the scope whatever happens in between
+struct Events {
+    static constexpr int CAP = 2 * (2 * PIPS_DEPTH + 2);
+    hipEvent_t ev[CAP];
+    int want, made = 0;
+    explicit Events(int n) : want(n) { while (made < want && hipEventCreate(&ev[made]) == hipSuccess) ++made; }
+    ~Events() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]); }
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    bool ok() const { if (made != want) set_error("hipEventCreate failed"); return made == want; }
+    void record(int i, hipStream_t st) { (void)hipEventRecord(ev[i], st); }
+    bool wait(int i) { return hipEventSynchronize(ev[i]) == hipSuccess; }
+    float elapsed(int i, int j) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[i], ev[j]); return ms; }
+};
+
+// ------------------------------------------------------------------ building blocks
+bool epi_ok(int epi, const float* R) { return (epi & 0xff) <= 2 && ((epi & 0xff) != EPI_RESIDUAL || R != nullptr); }
+
+// C[M][ldc] = epi(A[M][lda] W[N][K]^T + bias (+ R[M][ldr])): the argument order of the pips_gemm_* entry points
+GemmArgs gemm_args(const void* A, int lda, const void* W, const float* bias, void* C, int ldc, int M, int N, int K, int epi,
+                   const float* R, int ldr) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = (const float*)A; g.W = (const float*)W; g.bias = bias; g.C = (float*)C; g.R = R;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.epi = epi;
+    return g;
+}
+// the dense problem the *_route queries describe: bias and residual present (only their null-ness is inspected)
+GemmArgs route_args(int M, int N, int K, int epi) {
+    static const float dummy = 0.f;
+    return gemm_args(nullptr, K, nullptr, &dummy, nullptr, N, M, N, K, epi, &dummy, N);
+}
+
+// One NHWC convolution.  wgt points at the weight form of `mode` (fp32, bf16 copy, split planes), handed over as float*.
+// in_bf16 / out_bf16 / in_norm / parts_cap (BF16 only): the maps themselves are bf16; see GemmArgs for the last two.
+struct ConvCall {
+    const float* in; int F, H, W, Cin;
+    const float* wgt; const float* bias; int Cout, k, stride, pad;
+    float* out; float* stats; int* tiles;
+    MatMode mode; bool in_bf16, out_bf16; const float* in_norm; int parts_cap;
+};
+// the geometry part, in the argument order of the pips_conv_nhwc_* entry points; mode and map types are left EXACT / fp32
+ConvCall conv_call(const void* in, int F, int H, int W, int Cin, const void* wgt, const float* bias, int Cout, int k, int stride,
+                   int pad, void* out, float* stats, int* tiles) {
+    ConvCall c;
+    memset(&c, 0, sizeof(c));
+    c.in = (const float*)in; c.F = F; c.H = H; c.W = W; c.Cin = Cin;
+    c.wgt = (const float*)wgt; c.bias = bias; c.Cout = Cout; c.k = k; c.stride = stride; c.pad = pad;
+    c.out = (float*)out; c.stats = stats; c.tiles = tiles;
+    return c;
+}
+int conv_nhwc(const ConvCall& c, hipStream_t st) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = c.in; g.W = c.wgt; g.bias = c.bias; g.C = c.out; g.stats = c.stats; g.in_norm = c.in_norm; g.stats_parts_cap = c.parts_cap;
+    g.H = c.H; g.Win = c.W; g.Cin = c.Cin; g.KH = g.KW = c.k; g.cstride = c.stride; g.pad = c.pad;
+    g.Ho = conv_out(c.H, c.k, c.stride, c.pad); g.Wo = conv_out(c.W, c.k, c.stride, c.pad);
+    g.M = g.Ho * g.Wo; g.N = c.Cout; g.K = c.k * c.k * c.Cin; g.ldc = c.Cout; g.epi = EPI_BIAS;
+    PIPS_CHECK_ARG(g.Ho > 0 && g.Wo > 0, "conv: empty output");
+    if (c.mode == SPLIT) return launch_conv_x3(g, c.F, c.tiles, st);
+    PIPS_CHECK_ARG(c.mode == BF16 || (!c.in_bf16 && !c.out_bf16 && !c.in_norm), "conv: bf16 maps need the bf16-operand kernels");
+    return c.mode == BF16 ? launch_conv_bf16(g, c.F, c.tiles, st, c.in_bf16, c.out_bf16) : launch_conv(g, c.F, c.tiles, st);
+}
+
+// ------------------------------------------------------------------ pyramid layout
+// THE level table of a packed pyramid of `frames` frames with H8 x W8 level-0 pixels, in floats: the fp32 levels at off[l]
+// (lh[l] x lw[l] pixels, 256-byte aligned), their bf16 mirror (same element offsets, half the bytes) behind all of them at
+// `levels` -- written by the bf16 encoder, pips_pyramid_mirror or pips_pyramid_append, read by the gather under
+// PIPS_FLAG_BF16_MAPS -- and a slack of a few map rows of the coarsest level (+ a pixel block) behind the mirror:
+// gather_mfma_kernel fetches whole 8 x 4 pixel blocks; the slots of a border block that hang over the last level's last frame must
+// still lie inside the buffer (their values are never used)
+struct PyramidView {
+    size_t off[PIPS_LEVELS];
+    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
+    size_t levels, mirror, slack;        // floats: the fp32 levels (= where the mirror starts), the mirror, the slack
+    size_t total() const { return levels + mirror + slack; }
+    bool empty() const { return lh[PIPS_LEVELS - 1] < 1 || lw[PIPS_LEVELS - 1] < 1; }     // too small for four levels
+};
+PyramidView pyramid_view(int frames, int H8, int W8) {
+    PyramidView v;
+    v.levels = 0;
+    for (int l = 0; l < PIPS_LEVELS; ++l) {
+        v.lh[l] = l ? v.lh[l - 1] / 2 : H8; v.lw[l] = l ? v.lw[l - 1] / 2 : W8;
+        v.off[l] = v.levels;
+        v.levels += ((size_t)frames * v.lh[l] * v.lw[l] * PIPS_C + 63) / 64 * 64;
+    }
+    v.mirror = (v.levels / 2 + 63) / 64 * 64;
+    v.slack = (((size_t)4 * v.lw[PIPS_LEVELS - 1] + 16) * PIPS_C / 2 + 63) / 64 * 64;      // (4 rows + 16 pixels) of bf16 channels
+    return v;
+}
+
+// ------------------------------------------------------------------ encoder
 struct EncPlan {
     int F, H, W, stride;
     int Hs[5], Ws[5];         // stem/layer1, layer2, layer3, layer4 resolutions; [4] = target H8,W8
@@ -403,240 +423,127 @@ EncPlan plan_encoder(int F, int H, int W, int stride) {
     return P;
 }
 
-void pyramid_dims(int H, int W, int stride, int* lh, int* lw) {
-    lh[0] = H / stride; lw[0] = W / stride;
-    for (int l = 1; l < PIPS_LEVELS; ++l) { lh[l] = lh[l - 1] / 2; lw[l] = lw[l - 1] / 2; }
-}
-
 int check_geometry(int F, int H, int W, int stride) {
     PIPS_CHECK_ARG(F > 0 && H > 0 && W > 0 && stride >= 1, "bad geometry F=%d H=%d W=%d stride=%d", F, H, W, stride);
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
-    PIPS_CHECK_ARG(lh[PIPS_LEVELS - 1] >= 1 && lw[PIPS_LEVELS - 1] >= 1,
-                   "input %dx%d too small for a 4-level pyramid at stride %d", H, W, stride);
+    PIPS_CHECK_ARG(!pyramid_view(F, H / stride, W / stride).empty(), "input %dx%d too small for a 4-level pyramid at stride %d", H, W,
+                   stride);
     return PIPS_OK;
 }
 
-#define RUN(x) do { int rc__ = (x); if (rc__ != PIPS_OK) return rc__; } while (0)
-
-// Matrix mode of one convolution.  mm: 0 exact-fp32 MFMA, 1 bf16 operands, 2 split-bf16.  The
-// split path is used where it measured faster than the exact kernel (tools/x3_check.py): every
-// layer with >= 8000 output pixels over the batch (at config 2: all but the 23x31 maps).
-int layer_mm(const ConvW& c, int F, int H, int W, int mm) {
-    if (mm != 2) return mm;
+// Matrix mode of one convolution.  The split path is used where it measured faster than the exact kernel
+// (tools/x3_check.py): every layer with >= 8000 output pixels over the batch (at config 2: all but the 23x31 maps).
+MatMode layer_mm(const ConvW& c, int F, int H, int W, MatMode mode) {
+    if (mode != SPLIT) return mode;
     const long rows = (long)F * conv_out(H, c.k, c.stride, c.pad) * conv_out(W, c.k, c.stride, c.pad);
-    return rows >= 8000 ? 2 : 0;
+    return rows >= 8000 ? SPLIT : EXACT;
 }
 // weight pointer for that mode, handed over as float* (bf16 copy / split planes live behind the fp32 arena)
-const float* conv_w(const float* arena, const ArenaLayout& A, int ci, int mm) {
-    if (mm == 0) return arena + A.conv[ci].w;
+const float* conv_w(const float* arena, const ArenaLayout& A, int ci, MatMode mode) {
+    if (mode == EXACT) return arena + A.conv[ci].w;
     const unsigned short* hb = reinterpret_cast<const unsigned short*>(arena + A.total);
-    return reinterpret_cast<const float*>(mm == 1 ? hb + A.h_conv[ci] : hb + A.total_h + A.t_conv[ci]);
+    return reinterpret_cast<const float*>(mode == BF16 ? hb + A.h_conv[ci] : hb + A.total_h + A.t_conv[ci]);
 }
 
-// conv -> partial stats -> mean/rstd
-int conv_stats(const float* arena, const ArenaLayout& A, int ci, const float* in, int F, int H, int W, float* out,
-               float* partial, float* mean_rstd, hipStream_t st, int mm) {
-    const ConvW& c = A.conv[ci];
-    const int lm = layer_mm(c, F, H, W, mm);
+// One encoder pass.  mode == BF16 (PIPS_FLAG_BF16_ENCODER; kernels: encoder_bf16.hip, conv_bf16_c64.hip, gemm_bf16.hip): every
+// activation map is bf16 -- the buffers are the fp32 plan's, used as bf16, hence the void* maps below; statistics, normalisation,
+// adds and resizes are fp32 arithmetic and the pyramid is fp32 in every mode.
+struct Enc {
+    const float* arena; const ArenaLayout& A;
+    int F; float* ws; const EncPlan& P; hipStream_t st; MatMode mode;
+};
+
+// layer ci of the arena on a map of H x W pixels, in the mode layer_mm() picks for it; bf16 maps in (and out, if out_bf16)
+ConvCall enc_conv(const Enc& e, int ci, const void* in, int H, int W, void* out, bool out_bf16) {
+    const ConvW& c = e.A.conv[ci];
+    const MatMode lm = layer_mm(c, e.F, H, W, e.mode);
+    ConvCall cc = conv_call(in, e.F, H, W, c.cin, conv_w(e.arena, e.A, ci, lm), e.arena + c.b, c.cout, c.k, c.stride, c.pad, out,
+                            nullptr, nullptr);
+    cc.mode = lm;
+    cc.in_bf16 = e.mode == BF16;
+    cc.out_bf16 = out_bf16;
+    return cc;
+}
+
+// conv (BF16: optional normalise-on-load of the input map by in_norm) -> raw map + partial stats -> {mean, rstd}
+int conv_stats(const Enc& e, int ci, const void* in, const float* in_norm, int H, int W, void* out, float* partial,
+               float* mean_rstd) {
+    const ConvW& c = e.A.conv[ci];
     int tiles = 0;
-    RUN(conv_nhwc(in, F, H, W, c.cin, conv_w(arena, A, ci, lm), arena + c.b, c.cout, c.k, c.stride, c.pad, out, partial,
-                  &tiles, st, lm));
-    return launch_inorm_finalize_pivot(partial, F, tiles, c.cout, mean_rstd, st);
+    ConvCall cc = enc_conv(e, ci, in, H, W, out, e.mode == BF16);
+    cc.stats = partial; cc.tiles = &tiles; cc.in_norm = in_norm;
+    if (e.mode == BF16) cc.parts_cap = enc_parts_cap(conv_out(H, c.k, c.stride, c.pad), conv_out(W, c.k, c.stride, c.pad));
+    RUN(conv_nhwc(cc, e.st));
+    return launch_inorm_finalize_pivot(partial, e.F, tiles, c.cout, mean_rstd, e.st);
+}
+
+// y = relu(n(x))  |  relu(res + relu(n(x)))  |  relu(n2(res) + relu(n(x))), by the null-ness of res / res_stats
+int inorm_apply(const Enc& e, const void* x, const float* stats, const void* res, const float* res_stats, void* y, int HW, int C) {
+    if (e.mode == BF16)
+        return launch_inorm_apply_bf16(x, stats, res, res_stats, res == nullptr ? 0 : res_stats == nullptr ? 1 : 2, y, e.F, HW, C, e.st);
+    return launch_inorm_apply((const float*)x, stats, (const float*)res, res_stats, (float*)y, e.F, HW, C, e.st);
 }
 
 // ResidualBlock.forward, nets/pips.py:173-181
-int res_block(const float* arena, const ArenaLayout& A, int& ci, bool down, const float* x, int F, int H, int W,
-              float* ws, const EncPlan& P, float* out, hipStream_t st, int bf16) {
+int res_block(const Enc& e, int& ci, bool down, const void* x, int H, int W, void* out) {
     const int i1 = ci++, i2 = ci++;
-    const ConvW& c1 = A.conv[i1];
-    const ConvW& c2 = A.conv[i2];
+    const ConvW& c1 = e.A.conv[i1];
+    const ConvW& c2 = e.A.conv[i2];
     const int Ho = conv_out(H, 3, c1.stride, 1), Wo = conv_out(W, 3, c1.stride, 1);
-    float* raw = ws + P.raw; float* mid = ws + P.mid;
-    RUN(conv_stats(arena, A, i1, x, F, H, W, raw, ws + P.partial, ws + P.st_a, st, bf16));
-    RUN(launch_inorm_apply(raw, ws + P.st_a, nullptr, nullptr, mid, F, Ho * Wo, c1.cout, st));
-    RUN(conv_stats(arena, A, i2, mid, F, Ho, Wo, raw, ws + P.partial, ws + P.st_a, st, bf16));
-    if (down) {
-        const int id = ci++;
-        RUN(conv_stats(arena, A, id, x, F, H, W, ws + P.ds, ws + P.partial2, ws + P.st_b, st, bf16));
-        RUN(launch_inorm_apply(raw, ws + P.st_a, ws + P.ds, ws + P.st_b, out, F, Ho * Wo, c2.cout, st));
-    } else {
-        RUN(launch_inorm_apply(raw, ws + P.st_a, x, nullptr, out, F, Ho * Wo, c2.cout, st));
-    }
-    return PIPS_OK;
-}
-
-// ---- the encoder with every activation in bf16 (PIPS_FLAG_BF16_ENCODER; kernels: encoder_bf16.hip, conv_bf16_c64.hip,
-// gemm_bf16.hip).  Buffers are the fp32 plan's, used as bf16.
-// conv (bf16 map in, optional normalise-on-load) -> bf16 raw map + partials -> {mean, rstd}
-int conv_stats_h(const float* arena, const ArenaLayout& A, int ci, const void* in, const float* in_norm, int F, int H, int W,
-                 void* out, float* partial, float* mean_rstd, hipStream_t st) {
-    const ConvW& c = A.conv[ci];
-    int tiles = 0;
-    RUN(conv_nhwc((const float*)in, F, H, W, c.cin, conv_w(arena, A, ci, 1), arena + c.b, c.cout, c.k, c.stride, c.pad,
-                  (float*)out, partial, &tiles, st, 1, 1, 1, in_norm,
-                  enc_parts_cap(conv_out(H, c.k, c.stride, c.pad), conv_out(W, c.k, c.stride, c.pad))));
-    return launch_inorm_finalize_pivot(partial, F, tiles, c.cout, mean_rstd, st);
-}
-
-// ResidualBlock.forward (nets/pips.py:173-181), materialised bf16 activations
-int res_block_h(const float* arena, const ArenaLayout& A, int& ci, bool down, const void* x, int F, int H, int W, float* ws,
-                const EncPlan& P, void* out, hipStream_t st) {
-    const int i1 = ci++, i2 = ci++;
-    const ConvW& c1 = A.conv[i1];
-    const ConvW& c2 = A.conv[i2];
-    const int Ho = conv_out(H, 3, c1.stride, 1), Wo = conv_out(W, 3, c1.stride, 1);
+    float* ws = e.ws; const EncPlan& P = e.P;
     void* raw = ws + P.raw; void* mid = ws + P.mid;
-    RUN(conv_stats_h(arena, A, i1, x, nullptr, F, H, W, raw, ws + P.partial, ws + P.st_a, st));
-    RUN(launch_inorm_apply_bf16(raw, ws + P.st_a, nullptr, nullptr, 0, mid, F, Ho * Wo, c1.cout, st));
-    RUN(conv_stats_h(arena, A, i2, mid, nullptr, F, Ho, Wo, raw, ws + P.partial, ws + P.st_a, st));
+    RUN(conv_stats(e, i1, x, nullptr, H, W, raw, ws + P.partial, ws + P.st_a));
+    RUN(inorm_apply(e, raw, ws + P.st_a, nullptr, nullptr, mid, Ho * Wo, c1.cout));
+    RUN(conv_stats(e, i2, mid, nullptr, Ho, Wo, raw, ws + P.partial, ws + P.st_a));
     if (down) {
         const int id = ci++;
-        RUN(conv_stats_h(arena, A, id, x, nullptr, F, H, W, ws + P.ds, ws + P.partial2, ws + P.st_b, st));
-        return launch_inorm_apply_bf16(raw, ws + P.st_a, ws + P.ds, ws + P.st_b, 2, out, F, Ho * Wo, c2.cout, st);
+        RUN(conv_stats(e, id, x, nullptr, H, W, ws + P.ds, ws + P.partial2, ws + P.st_b));
+        return inorm_apply(e, raw, ws + P.st_a, ws + P.ds, ws + P.st_b, out, Ho * Wo, c2.cout);
     }
-    return launch_inorm_apply_bf16(raw, ws + P.st_a, x, nullptr, 1, out, F, Ho * Wo, c2.cout, st);
+    return inorm_apply(e, raw, ws + P.st_a, x, nullptr, out, Ho * Wo, c2.cout);
 }
 
-int encoder_bf16_acts(const float* arena, const ArenaLayout& A, const void* rgbs, int rgb_u8, int F, int H, int W, int stride,
-                      float* pyramid, float* ws, const EncPlan& P, hipStream_t st) {
+// stem + layer1 with fp32 maps (nets/pips.py:251-253, 265) -> ws + P.outs[0]
+int enc_front_f32(const Enc& e, const void* rgbs, int rgb_u8, int H, int W, int& ci) {
+    float* ws = e.ws; const EncPlan& P = e.P;
     const int H0 = P.Hs[0], W0 = P.Ws[0];
-    int tiles = 0, ci = 1;
+    int tiles = 0;
+    RUN(launch_stem(rgbs, rgb_u8, e.arena + e.A.conv[0].w, e.arena + e.A.conv[0].b, ws + P.raw, ws + P.partial, e.F, H, W, H0, W0,
+                    &tiles, e.st));
+    RUN(launch_inorm_finalize_pivot(ws + P.partial, e.F, tiles, 64, ws + P.st_a, e.st));
+    RUN(launch_inorm_apply(ws + P.raw, ws + P.st_a, nullptr, nullptr, ws + P.xa, e.F, H0 * W0, 64, e.st));
+    RUN(res_block(e, ci, false, ws + P.xa, H0, W0, ws + P.xb));
+    return res_block(e, ci, false, ws + P.xb, H0, W0, ws + P.outs[0]);
+}
+
+// the same with bf16 maps -> ws + P.outs[0]
+int enc_front_bf16(const Enc& e, const void* rgbs, int rgb_u8, int H, int W, int& ci) {
+    float* ws = e.ws; const EncPlan& P = e.P; const ArenaLayout& A = e.A; hipStream_t st = e.st;
+    const int F = e.F, H0 = P.Hs[0], W0 = P.Ws[0];
+    int tiles = 0;
     void* xa = ws + P.xa; void* xb = ws + P.xb; void* raw = ws + P.raw; void* mid = ws + P.mid;
     float* st_a = ws + P.st_a; float* st_b = ws + P.st_b;
     // stem: conv1 (:251); its norm1 + relu (:252-253) is applied by the consumers
-    RUN(launch_stem_bf16(rgbs, rgb_u8, arena + A.conv[0].w, arena + A.conv[0].b, xa, ws + P.partial, F, H, W, H0, W0, &tiles, st));
+    RUN(launch_stem_bf16(rgbs, rgb_u8, e.arena + A.conv[0].w, e.arena + A.conv[0].b, xa, ws + P.partial, F, H, W, H0, W0, &tiles, st));
     RUN(launch_inorm_finalize_pivot(ws + P.partial, F, tiles, 64, st_a, st));
-    const void* x;
     if (conv3x3_c64_takes(H0, W0, F)) {
         // layer1 on the LDS-resident 64 -> 64 kernel: a convolution normalises its input while staging it, so relu(norm(.))
         // of the stem and of each block's first convolution never goes to HBM.  xa = raw stem map (statistics st_a).
-        RUN(conv_stats_h(arena, A, ci++, xa, st_a, F, H0, W0, raw, ws + P.partial, st_b, st));          // block 1 conv1
-        RUN(conv_stats_h(arena, A, ci++, raw, st_b, F, H0, W0, mid, ws + P.partial, st_b, st));         // block 1 conv2
+        RUN(conv_stats(e, ci++, xa, st_a, H0, W0, raw, ws + P.partial, st_b));          // block 1 conv1
+        RUN(conv_stats(e, ci++, raw, st_b, H0, W0, mid, ws + P.partial, st_b));         // block 1 conv2
         // relu(x + y), x = relu(norm1(stem)) recomputed from the raw stem map, y = relu(norm2(conv2)) (:176-181)
         RUN(launch_inorm_apply_bf16(mid, st_b, xa, st_a, 3, xb, F, H0 * W0, 64, st));
-        RUN(conv_stats_h(arena, A, ci++, xb, nullptr, F, H0, W0, raw, ws + P.partial, st_a, st));       // block 2 conv1
-        RUN(conv_stats_h(arena, A, ci++, raw, st_a, F, H0, W0, mid, ws + P.partial, st_b, st));         // block 2 conv2
-        RUN(launch_inorm_apply_bf16(mid, st_b, xb, nullptr, 1, ws + P.outs[0], F, H0 * W0, 64, st));
-    } else {
-        RUN(launch_inorm_apply_bf16(xa, st_a, nullptr, nullptr, 0, xb, F, H0 * W0, 64, st));
-        RUN(res_block_h(arena, A, ci, false, xb, F, H0, W0, ws, P, xa, st));
-        RUN(res_block_h(arena, A, ci, false, xa, F, H0, W0, ws, P, ws + P.outs[0], st));
+        RUN(conv_stats(e, ci++, xb, nullptr, H0, W0, raw, ws + P.partial, st_a));       // block 2 conv1
+        RUN(conv_stats(e, ci++, raw, st_a, H0, W0, mid, ws + P.partial, st_b));         // block 2 conv2
+        return launch_inorm_apply_bf16(mid, st_b, xb, nullptr, 1, ws + P.outs[0], F, H0 * W0, 64, st);
     }
-    x = ws + P.outs[0];
-    int Hc = H0, Wc = W0;
-    for (int l = 1; l < 4; ++l) {
-        RUN(res_block_h(arena, A, ci, true, x, F, Hc, Wc, ws, P, xb, st));
-        Hc = P.Hs[l]; Wc = P.Ws[l];
-        RUN(res_block_h(arena, A, ci, false, xb, F, Hc, Wc, ws, P, ws + P.outs[l], st));
-        x = ws + P.outs[l];
-    }
-    const int ch[4] = {64, 96, 128, 128};
-    const int H8 = P.Hs[4], W8 = P.Ws[4];
-    for (int l = 0, coff = 0; l < 4; coff += ch[l], ++l)
-        RUN(launch_resize_into_bf16(ws + P.outs[l], F, P.Hs[l], P.Ws[l], ch[l], ws + P.cat, H8, W8, 416, coff, st));
-    const int i2 = ci++, i3 = ci++;
-    const ConvW& c3 = A.conv[i3];
-    RUN(conv_stats_h(arena, A, i2, ws + P.cat, nullptr, F, H8, W8, raw, ws + P.partial, st_a, st));
-    RUN(launch_inorm_apply_bf16(raw, st_a, nullptr, nullptr, 0, mid, F, H8 * W8, 256, st));
-    // conv3 writes the fp32 level-0 map of the correlation pyramid
-    RUN(conv_nhwc((const float*)mid, F, H8, W8, 256, conv_w(arena, A, i3, 1), arena + c3.b, 128, 1, 1, 0, pyramid, nullptr, nullptr,
-                  st, 1, 1, 0));
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
-    for (int l = 1; l < PIPS_LEVELS; ++l)
-        RUN(launch_avgpool2(pyramid + pips_pyramid_offset(F, H, W, stride, l - 1), F, lh[l - 1], lw[l - 1], PIPS_C,
-                            pyramid + pips_pyramid_offset(F, H, W, stride, l), st));
-    // the bf16 mirror the gather of the bf16 mode reads (PIPS_FLAG_BF16_MAPS)
-    RUN(pips_pyramid_mirror(pyramid, F, H, W, stride, st));
-    return PIPS_OK;
+    RUN(launch_inorm_apply_bf16(xa, st_a, nullptr, nullptr, 0, xb, F, H0 * W0, 64, st));
+    RUN(res_block(e, ci, false, xb, H0, W0, xa));
+    return res_block(e, ci, false, xa, H0, W0, ws + P.outs[0]);
 }
 
-}  // namespace
-
-size_t pips_encoder_workspace_bytes(int F, int H, int W, int stride) {
-    if (F <= 0 || H <= 0 || W <= 0 || stride < 1) return 0;
-    return plan_encoder(F, H, W, stride).total * sizeof(float);
-}
-
-// fp32 levels (pips_pyramid_offset) + the bf16 mirror of all of them behind (pips_pyramid_mirror_offset; written by the
-// bf16 encoder or pips_pyramid_mirror, read by the gather under PIPS_FLAG_BF16_MAPS)
-size_t pips_pyramid_mirror_offset(int F, int H, int W, int stride) {
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
-    size_t n = 0;
-    for (int l = 0; l < PIPS_LEVELS; ++l) n += ((size_t)F * lh[l] * lw[l] * PIPS_C + 63) / 64 * 64;
-    return n;
-}
-size_t pips_pyramid_floats(int F, int H, int W, int stride) {
-    const size_t n = pips_pyramid_mirror_offset(F, H, W, stride);
-    // behind the mirror: a slack of a few map rows of the coarsest level (+ a pixel block).  gather_mfma_kernel fetches whole
-    // 8 x 4 pixel blocks; the slots of a border block that hang over the last level's last frame must still lie inside the buffer
-    // (their values are never used)
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
-    const size_t slack = ((size_t)4 * lw[PIPS_LEVELS - 1] + 16) * PIPS_C / 2;          // floats: (4 rows + 16 pixels) of bf16 channels
-    return n + (n / 2 + 63) / 64 * 64 + (slack + 63) / 64 * 64;
-}
-int pips_pyramid_mirror(float* pyramid, int F, int H, int W, int stride, void* stream) {
-    PIPS_CHECK_ARG(pyramid != nullptr && F > 0, "pyramid_mirror: bad argument");
-    const size_t n = pips_pyramid_mirror_offset(F, H, W, stride);
-    return launch_pyramid_mirror(pyramid, n, pyramid + n, (hipStream_t)stream);
-}
-
-size_t pips_pyramid_offset(int F, int H, int W, int stride, int level) {
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
-    size_t n = 0;
-    for (int l = 0; l < level && l < PIPS_LEVELS; ++l) n += ((size_t)F * lh[l] * lw[l] * PIPS_C + 63) / 64 * 64;
-    return n;
-}
-
-int pips_pyramid_append(const float* src, int k, float* ring, int R, int T0, int H, int W, int stride, void* stream) {
-    PIPS_CHECK_ARG(src != nullptr && ring != nullptr, "pyramid_append: null pointer");
-    PIPS_CHECK_ARG(R >= 1 && T0 >= 0 && k >= 1 && k <= R, "pyramid_append: need R >= 1, T0 >= 0 and 1 <= k <= R (k=%d, R=%d, T0=%d)",
-                   k, R, T0);
-    PIPS_CHECK_ARG(H > 0 && W > 0 && stride >= 1, "pyramid_append: bad geometry");
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS], pf8[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
-    PIPS_CHECK_ARG(lh[PIPS_LEVELS - 1] >= 1 && lw[PIPS_LEVELS - 1] >= 1, "pyramid_append: map too small");
-    size_t so[PIPS_LEVELS], dof[PIPS_LEVELS];
-    for (int l = 0; l < PIPS_LEVELS; ++l) {
-        so[l] = pips_pyramid_offset(k, H, W, stride, l);
-        dof[l] = pips_pyramid_offset(R, H, W, stride, l);
-        pf8[l] = lh[l] * lw[l] * PIPS_C / 8;
-    }
-    return launch_pyramid_append(src, so, k, ring, dof, ring + pips_pyramid_mirror_offset(R, H, W, stride), pf8, R, T0,
-                                 (hipStream_t)stream);
-}
-
-static int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int W, int stride, float* pyramid,
-                        void* workspace, size_t workspace_bytes, void* stream, int mode);
-
-int pips_encoder_fwd(const void* arena_v, const float* rgbs, int F, int H, int W, int stride, float* pyramid,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-    return encoder_impl(arena_v, rgbs, F, H, W, stride, pyramid, workspace, workspace_bytes, stream, 0);
-}
-
-int pips_encoder_fwd_bf16(const void* arena_v, const float* rgbs, int F, int H, int W, int stride, float* pyramid,
-                          void* workspace, size_t workspace_bytes, void* stream) {
-    return encoder_impl(arena_v, rgbs, F, H, W, stride, pyramid, workspace, workspace_bytes, stream, 1);
-}
-
-int pips_encoder_fwd_ex(const void* arena_v, const void* rgbs, int F, int H, int W, int stride, int flags,
-                        float* pyramid, void* workspace, size_t workspace_bytes, void* stream) {
-    return encoder_impl(arena_v, rgbs, F, H, W, stride, pyramid, workspace, workspace_bytes, stream,
-                        ((flags & PIPS_FLAG_BF16_ENCODER) ? 1 : 0) | ((flags & PIPS_FLAG_RGB_U8) ? 2 : 0) |
-                            ((flags & PIPS_FLAG_SPLIT_BF16) ? 4 : 0));
-}
-
-// mode bit0: bf16 MFMA operands in all 22 convolutions AND bf16 activation maps (the rounding points of the reference
-// under torch.autocast(bfloat16)); statistics, normalisation, adds and resizes are fp32 arithmetic, the pyramid is fp32;
-// mode bit1: rgbs is uint8 (B,S,3,H,W) instead of float;
-// mode bit2: split-bf16 (fp32-grade) convolutions where layer_mm() picks them; wins over bit0
-static int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int W, int stride, float* pyramid,
-                        void* workspace, size_t workspace_bytes, void* stream, int mode) {
-    const int bf16 = (mode & 4) ? 2 : (mode & 1);      // matrix mode handed to the convolutions
+// flags: PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_SPLIT_BF16 (encoder_mode) and PIPS_FLAG_RGB_U8: rgbs is uint8 (B,S,3,H,W) instead of float
+int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int W, int stride, int flags, float* pyramid, void* workspace,
+                 size_t workspace_bytes, hipStream_t st) {
     PIPS_CHECK_ARG(arena_v && rgbs && pyramid && workspace, "encoder: null pointer");
     RUN(check_geometry(F, H, W, stride));
     const EncPlan P = plan_encoder(F, H, W, stride);
@@ -644,51 +551,523 @@ static int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int
         set_error("encoder: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
         return PIPS_E_WORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream;
-    const ArenaLayout& A = arena_layout();
-    const float* arena = (const float*)arena_v;
     float* ws = (float*)workspace;
-    if (bf16 == 1)
-        return encoder_bf16_acts(arena, A, rgbs, (mode & 2) ? 1 : 0, F, H, W, stride, pyramid, ws, P, st);
+    const Enc e = {(const float*)arena_v, arena_layout(), F, ws, P, st, encoder_mode(flags)};
+    const bool h = e.mode == BF16;
+    const int rgb_u8 = (flags & PIPS_FLAG_RGB_U8) ? 1 : 0;
 
-    // stem: conv1 + norm1 + relu (nets/pips.py:251-253)
-    int tiles = 0;
-    RUN(launch_stem(rgbs, (mode & 2) ? 1 : 0, arena + A.conv[0].w, arena + A.conv[0].b, ws + P.raw, ws + P.partial, F, H, W, P.Hs[0],
-                    P.Ws[0], &tiles, st));
-    RUN(launch_inorm_finalize_pivot(ws + P.partial, F, tiles, 64, ws + P.st_a, st));
-    RUN(launch_inorm_apply(ws + P.raw, ws + P.st_a, nullptr, nullptr, ws + P.xa, F, P.Hs[0] * P.Ws[0], 64, st));
-
-    // layer1..4 (:265-268)
+    // stem + layer1 (nets/pips.py:251-253, 265)
     int ci = 1;
-    const float* x = ws + P.xa;
+    RUN(h ? enc_front_bf16(e, rgbs, rgb_u8, H, W, ci) : enc_front_f32(e, rgbs, rgb_u8, H, W, ci));
+    // layer2..4 (:266-268)
+    const void* x = ws + P.outs[0];
     int Hc = P.Hs[0], Wc = P.Ws[0];
-    for (int l = 0; l < 4; ++l) {
-        const bool down = l > 0;
-        RUN(res_block(arena, A, ci, down, x, F, Hc, Wc, ws, P, ws + P.xb, st, bf16));
+    for (int l = 1; l < 4; ++l) {
+        RUN(res_block(e, ci, true, x, Hc, Wc, ws + P.xb));
         Hc = P.Hs[l]; Wc = P.Ws[l];
-        RUN(res_block(arena, A, ci, false, ws + P.xb, F, Hc, Wc, ws, P, ws + P.outs[l], st, bf16));
+        RUN(res_block(e, ci, false, ws + P.xb, Hc, Wc, ws + P.outs[l]));
         x = ws + P.outs[l];
     }
     // resize a,b,c,d to (H//stride, W//stride) and concatenate (:269-273)
     const int ch[4] = {64, 96, 128, 128};
     const int H8 = P.Hs[4], W8 = P.Ws[4];
     for (int l = 0, coff = 0; l < 4; coff += ch[l], ++l)
-        RUN(launch_resize_into(ws + P.outs[l], F, P.Hs[l], P.Ws[l], ch[l], ws + P.cat, H8, W8, 416, coff, st));
-    // conv2 + norm2 + relu + conv3 (:273-276)
+        RUN(h ? launch_resize_into_bf16(ws + P.outs[l], F, P.Hs[l], P.Ws[l], ch[l], ws + P.cat, H8, W8, 416, coff, st)
+              : launch_resize_into(ws + P.outs[l], F, P.Hs[l], P.Ws[l], ch[l], ws + P.cat, H8, W8, 416, coff, st));
+    // conv2 + norm2 + relu + conv3 (:273-276); conv3 writes the fp32 level-0 map of the correlation pyramid
     const int i2 = ci++, i3 = ci++;
-    const ConvW& c3 = A.conv[i3];
-    RUN(conv_stats(arena, A, i2, ws + P.cat, F, H8, W8, ws + P.raw, ws + P.partial, ws + P.st_a, st, bf16));
-    RUN(launch_inorm_apply(ws + P.raw, ws + P.st_a, nullptr, nullptr, ws + P.mid, F, H8 * W8, 256, st));
-    const int m3 = layer_mm(c3, F, H8, W8, bf16);
-    RUN(conv_nhwc(ws + P.mid, F, H8, W8, 256, conv_w(arena, A, i3, m3), arena + c3.b, 128, 1, 1, 0, pyramid, nullptr,
-                  nullptr, st, m3));
+    RUN(conv_stats(e, i2, ws + P.cat, nullptr, H8, W8, ws + P.raw, ws + P.partial, ws + P.st_a));
+    RUN(inorm_apply(e, ws + P.raw, ws + P.st_a, nullptr, nullptr, ws + P.mid, H8 * W8, 256));
+    RUN(conv_nhwc(enc_conv(e, i3, ws + P.mid, H8, W8, pyramid, false), st));
     // CorrBlock.__init__ pyramid (:346-352)
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_dims(H, W, stride, lh, lw);
+    const PyramidView v = pyramid_view(F, H8, W8);
     for (int l = 1; l < PIPS_LEVELS; ++l)
-        RUN(launch_avgpool2(pyramid + pips_pyramid_offset(F, H, W, stride, l - 1), F, lh[l - 1], lw[l - 1], PIPS_C,
-                            pyramid + pips_pyramid_offset(F, H, W, stride, l), st));
+        RUN(launch_avgpool2(pyramid + v.off[l - 1], F, v.lh[l - 1], v.lw[l - 1], PIPS_C, pyramid + v.off[l], st));
+    // the bf16 mirror the gather of the bf16 mode reads (PIPS_FLAG_BF16_MAPS)
+    if (h) RUN(launch_pyramid_mirror(pyramid, v.levels, pyramid + v.levels, st));
     return PIPS_OK;
+}
+
+// ------------------------------------------------------------------ correlation gather
+enum GatherRoute { GATHER_AUTO, GATHER_DIRECT, GATHER_TILED };   // AUTO: tiled for a dense query set if the call allows it
+
+// pyramid: B clips x R frame slots holding T logical frames (frame f in slot f mod R; T is the clamp bound; a linear cache
+// has R = T); S = window length = mixer rows per particle.  win_dir (per-particle time direction, sign) is read with win_start only.
+// bf16_maps: the gather reads the bf16 mirror behind the fp32 levels.  The tiled kernels need scratch, a dense un-windowed
+// query set and R = T = S = PIPS_S; ev != null (tiled only): 4 events around their three launches.
+struct GatherCall {
+    const float* pyramid; int B, T, R, S, H8, W8;
+    const float* ffeats; const float* coords; const float* times; int N;
+    const int* win_start; const int* win_dir;
+    float* X;
+    bool bf16_maps; GatherRoute route;
+    void* scratch; size_t scratch_bytes; hipEvent_t* ev;
+    hipStream_t st;
+};
+
+int mixer_input(const GatherCall& g) {
+    PIPS_CHECK_ARG(g.pyramid && g.ffeats && g.coords && g.times && g.X, "mixer_input: null pointer");
+    PIPS_CHECK_ARG(g.T >= 1 && g.R >= 1 && g.B > 0 && g.N > 0, "mixer_input: need T, R, B, N >= 1");
+    PIPS_CHECK_ARG(g.S >= 1 && g.S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", g.S, PIPS_S_MAX);
+    const PyramidView v = pyramid_view(g.B * g.R, g.H8, g.W8);
+    PIPS_CHECK_ARG(!v.empty(), "mixer_input: map too small");
+    const float* mirror = g.pyramid + v.levels;
+    const bool can_tile = g.scratch != nullptr && g.win_start == nullptr && g.win_dir == nullptr && g.R == PIPS_S && g.T == g.R &&
+                          g.S == PIPS_S && g.scratch_bytes >= tiled_gather_scratch_bytes(g.B, g.N, g.H8, g.W8);
+    const bool tiled = g.route == GATHER_AUTO ? tiled_gather_wanted(g.B, g.N, g.H8, g.W8, g.bf16_maps) : g.route == GATHER_TILED;
+    if (tiled && can_tile)      // (bf16 mode: the same work items on the matrix cores, reading the bf16 mirror)
+        return launch_mixer_input_tiled(g.pyramid, v.off, v.lh, v.lw, g.B, g.R, g.ffeats, g.coords, g.times, g.N, g.X, g.scratch,
+                                        g.scratch_bytes, g.st, g.ev,
+                                        g.bf16_maps ? reinterpret_cast<const unsigned short*>(mirror) : nullptr);
+    PIPS_CHECK_ARG(g.route != GATHER_TILED, "tiled gather needs scratch of %zu bytes, no win_start and 8 frames per clip",
+                   tiled_gather_scratch_bytes(g.B, g.N, g.H8, g.W8));
+    PIPS_CHECK_ARG(g.win_dir == nullptr || g.win_start != nullptr, "mixer_input: win_dir needs win_start");
+    if (g.bf16_maps)
+        return launch_mixer_input_bf16maps(mirror, v.off, v.lh, v.lw, g.B, g.R, g.T, g.ffeats, g.coords, g.times, g.N, g.win_start,
+                                           g.win_dir, g.X, g.st, g.S);
+    return launch_mixer_input(g.pyramid, v.off, v.lh, v.lw, g.B, g.R, g.T, g.ffeats, g.coords, g.times, g.N, g.win_start, g.win_dir,
+                              g.X, g.st, g.S);
+}
+
+// the tiled kernels on a PIPS_S-frame clip; ms3_host != null: the durations of the three launches, and a stream synchronisation
+int mixer_input_tiled(GatherCall g, float* ms3_host) {
+    PIPS_CHECK_ARG(g.scratch != nullptr, "mixer_input_tiled: null pointer");
+    PIPS_CHECK_ARG(g.R == PIPS_S, "mixer_input_tiled: S must be %d", PIPS_S);
+    g.route = GATHER_TILED;
+    if (ms3_host == nullptr) return mixer_input(g);
+    Events ev(4);
+    if (!ev.ok()) return PIPS_E_LAUNCH;
+    g.ev = ev.ev;
+    int rc = mixer_input(g);
+    if (rc == PIPS_OK && !ev.wait(3)) rc = PIPS_E_LAUNCH;
+    if (rc == PIPS_OK)
+        for (int i = 0; i < 3; ++i) ms3_host[i] = ev.elapsed(i, i + 1);
+    return rc;
+}
+
+// ------------------------------------------------------------------ mixer
+struct MixerPlan { size_t x, xn, h, pooled, total; };      // floats; M rows of S tokens per particle
+MixerPlan plan_mixer(int M, int S) {
+    MixerPlan P;
+    Bump b;
+    P.x = b.take((size_t)M * PIPS_DMIX); P.xn = b.take((size_t)M * PIPS_DMIX); P.h = b.take((size_t)M * 4 * PIPS_DMIX);
+    P.pooled = b.take((size_t)(M / S) * PIPS_DMIX);
+    P.total = b.off;
+    return P;
+}
+size_t mixer_workspace_bytes(int M, int S) {
+    if (M <= 0 || S < 1 || S > PIPS_S_MAX) return 0;
+    return plan_mixer(M, S).total * sizeof(float);
+}
+
+// One Linear of the mixer on dense rows: out[M][N] = epi(in[M][K] W^T + bias), EPI_RESIDUAL adding out in place.  w / w_bf16 /
+// w_split are the arena offsets of the weight's three forms (floats, ushorts of the bf16 section, ushorts of the split section);
+// in_bf16 / out_bf16 say which activations the BF16 mode keeps as bf16 (the other modes are fp32 throughout).
+struct Linear { size_t w, w_bf16, w_split, bias; int K, N, epi; bool in_bf16, out_bf16; };
+
+Linear in_proj(const ArenaLayout& A, bool x_bf16) {
+    return {A.w_in, A.h_in, A.t_in, A.b_in, PIPS_KIN_PAD, PIPS_DMIX, EPI_BIAS, false, x_bf16};
+}
+Linear up_proj(const ArenaLayout& A, int d) {
+    return {A.mix[d].w1, A.h_w1[d], A.t_w1[d], A.mix[d].b1, PIPS_DMIX, 4 * PIPS_DMIX, EPI_GELU, true, true};
+}
+Linear down_proj(const ArenaLayout& A, int d, bool x_bf16) {
+    return {A.mix[d].w2, A.h_w2[d], A.t_w2[d], A.mix[d].b2, 4 * PIPS_DMIX, PIPS_DMIX, EPI_RESIDUAL | (x_bf16 ? EPI_RES_BF16 : 0),
+            true, x_bf16};
+}
+Linear head_proj(const ArenaLayout& A) {
+    return {A.w_head, A.h_head, A.t_head, A.b_head, PIPS_DMIX, A.nout_pad, EPI_BIAS, false, false};
+}
+
+int linear(MatMode mode, const float* arena, const ArenaLayout& A, const Linear& L, const float* in, float* out, int M, hipStream_t st) {
+    const unsigned short* hw = reinterpret_cast<const unsigned short*>(arena + A.total);
+    const bool res = (L.epi & 0xff) == EPI_RESIDUAL;
+    const void* W = mode == EXACT ? (const void*)(arena + L.w) : mode == BF16 ? (const void*)(hw + L.w_bf16)
+                                                                               : (const void*)(hw + A.total_h + L.w_split);
+    const GemmArgs g = gemm_args(in, L.K, W, arena + L.bias, out, L.N, M, L.N, L.K, L.epi, res ? out : nullptr, res ? L.N : 0);
+    if (mode == SPLIT) return launch_gemm_x3(g, st);
+    return mode == BF16 ? launch_gemm_bf16(g, L.in_bf16, L.out_bf16, st) : launch_gemm(g, st);
+}
+
+// X (M, 544) -> delta (M / S, nout_pad(S)).  S: the window length the arena was packed for (tokens per particle).
+// ev != nullptr: record ev[2g], ev[2g+1] around GEMM g (g = 0 in-proj, 1+2d up, 2+2d down, 25 head)
+int mixer_impl(const void* arena_v, const float* X, int M, int S, MixerMode mm, float* delta, void* workspace, size_t workspace_bytes,
+               hipStream_t st, hipEvent_t* ev) {
+    PIPS_CHECK_ARG(arena_v && X && delta && workspace, "mixer: null pointer");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer: S=%d outside 1..%d", S, PIPS_S_MAX);
+    PIPS_CHECK_ARG(M > 0 && M % S == 0, "mixer: M=%d must be a positive multiple of S=%d", M, S);
+    if (workspace_bytes < mixer_workspace_bytes(M, S)) {
+        set_error("mixer: workspace %zu < %zu bytes", workspace_bytes, mixer_workspace_bytes(M, S));
+        return PIPS_E_WORKSPACE;
+    }
+    const ArenaLayout& A = arena_layout(S);
+    const float* arena = (const float*)arena_v;
+    const MixerPlan W = plan_mixer(M, S);
+    float* ws = (float*)workspace;
+    float* x = ws + W.x; float* xn = ws + W.xn; float* h = ws + W.h; float* pooled = ws + W.pooled;
+    const int P = M / S;
+    const bool bf16 = mm.mode == BF16;                 // bf16 operands: the LayerNorm-2 output xn and the hidden activation h are bf16
+    const bool xb = bf16 && mm.bf16_stream && S == PIPS_S;
+    int g = 0;
+    auto timed = [&](const Linear& L, const float* in, float* out, int rows) {
+        if (ev) (void)hipEventRecord(ev[2 * g], st);
+        RUN(linear(mm.mode, arena, A, L, in, out, rows, st));
+        if (ev) (void)hipEventRecord(ev[2 * g + 1], st);
+        ++g;
+        return (int)PIPS_OK;
+    };
+    RUN(timed(in_proj(A, xb), X, x, M));
+    for (int d = 0; d < PIPS_DEPTH; ++d) {
+        RUN(launch_token_mix(arena, A.mix[d], x, xn, P, st, bf16, S, xb));
+        RUN(timed(up_proj(A, d), xn, h, M));
+        RUN(timed(down_proj(A, d, xb), h, x, M));
+    }
+    RUN(launch_ln_mean(x, arena + A.lnf_g, arena + A.lnf_b, pooled, P, st, S, xb));
+    return timed(head_proj(A), pooled, delta, P);
+}
+
+int mixer_timed(const void* arena_v, const float* X, int M, int flags, float* delta, void* workspace, size_t workspace_bytes,
+                hipStream_t st, float* ms_host) {
+    PIPS_CHECK_ARG(ms_host != nullptr, "mixer_timed: null output");
+    constexpr int NG = 2 * PIPS_DEPTH + 2;
+    constexpr int NCAL = 8;                      // empty event pairs: the marker-to-marker overhead
+    Events ev(2 * NG), cal(2 * NCAL);
+    if (!ev.ok() || !cal.ok()) return PIPS_E_LAUNCH;
+    int rc = mixer_impl(arena_v, X, M, PIPS_S, mixer_mode(flags), delta, workspace, workspace_bytes, st, ev.ev);
+    for (int i = 0; i < 2 * NCAL; ++i) cal.record(i, st);
+    if (rc == PIPS_OK && !cal.wait(2 * NCAL - 1)) rc = PIPS_E_LAUNCH;
+    if (rc != PIPS_OK) return rc;
+    float up = 0.f, down = 0.f, ovh = 0.f;
+    for (int i = 0; i < NCAL; ++i) ovh += cal.elapsed(2 * i, 2 * i + 1);
+    for (int d = 0; d < PIPS_DEPTH; ++d) {
+        up += ev.elapsed(2 * (1 + 2 * d), 2 * (1 + 2 * d) + 1);
+        down += ev.elapsed(2 * (2 + 2 * d), 2 * (2 + 2 * d) + 1);
+    }
+    ms_host[0] = ev.elapsed(0, 1);
+    ms_host[1] = up / PIPS_DEPTH;
+    ms_host[2] = down / PIPS_DEPTH;
+    ms_host[3] = ev.elapsed(2 * (NG - 1), 2 * (NG - 1) + 1);
+    ms_host[4] = ovh / NCAL;
+    return PIPS_OK;
+}
+
+// The two channel-mix GEMM shapes as launch TRAINS: the 12 layers' up-projections (then their down-projections) back to back on the
+// layers' own weights between ONE event pair, reps times -> ms2_host = {up, down} milliseconds per launch.  No per-launch event and
+// no overhead to subtract: start-to-start durations as the forward pays them (what a rocprofv3 kernel trace of the forward shows).
+// The workspace must hold the activations of a mixer pass at this M (pips_mixer_fwd* on the same workspace first).
+int mixer_gemm_train(const void* arena_v, int M, int flags, void* workspace, size_t workspace_bytes, hipStream_t st, int reps,
+                     float* ms2_host) {
+    PIPS_CHECK_ARG(arena_v && workspace && ms2_host && reps > 0, "mixer_gemm_train: bad argument");
+    PIPS_CHECK_ARG(M > 0 && M % PIPS_S == 0, "mixer_gemm_train: M=%d must be a positive multiple of %d", M, PIPS_S);
+    if (workspace_bytes < mixer_workspace_bytes(M, PIPS_S)) {
+        set_error("mixer_gemm_train: workspace %zu < %zu bytes", workspace_bytes, mixer_workspace_bytes(M, PIPS_S));
+        return PIPS_E_WORKSPACE;
+    }
+    // the mode pips_mixer_fwd_s derives from the same flags (incl. PIPS_FLAG_BF16_STREAM: the workspace's x is then a bf16 stream and
+    // the down-projection the bf16-residual kernel the forward launches)
+    const MixerMode mm = mixer_mode(flags);
+    const bool xb = mm.mode == BF16 && mm.bf16_stream;
+    const ArenaLayout& A = arena_layout(PIPS_S);
+    const float* arena = (const float*)arena_v;
+    const MixerPlan W = plan_mixer(M, PIPS_S);
+    float* ws = (float*)workspace;
+    float* x = ws + W.x; float* xn = ws + W.xn; float* h = ws + W.h;
+    Events ev(3);
+    if (!ev.ok()) return PIPS_E_LAUNCH;
+    int rc = PIPS_OK;
+    auto up = [&](int d) { return linear(mm.mode, arena, A, up_proj(A, d), xn, h, M, st); };
+    auto down = [&](int d) { return linear(mm.mode, arena, A, down_proj(A, d, xb), h, x, M, st); };    // in place, like the mixer
+    for (int d = 0; d < PIPS_DEPTH && rc == PIPS_OK; ++d) rc = up(d);                   // warm: clocks, caches
+    ev.record(0, st);
+    for (int r = 0; r < reps && rc == PIPS_OK; ++r)
+        for (int d = 0; d < PIPS_DEPTH && rc == PIPS_OK; ++d) rc = up(d);
+    ev.record(1, st);
+    for (int r = 0; r < reps && rc == PIPS_OK; ++r)
+        for (int d = 0; d < PIPS_DEPTH && rc == PIPS_OK; ++d) rc = down(d);
+    ev.record(2, st);
+    if (rc == PIPS_OK && !ev.wait(2)) rc = PIPS_E_LAUNCH;
+    if (rc == PIPS_OK) {
+        ms2_host[0] = ev.elapsed(0, 1) / (float)(reps * PIPS_DEPTH);
+        ms2_host[1] = ev.elapsed(1, 2) / (float)(reps * PIPS_DEPTH);
+    }
+    return rc;
+}
+
+// ------------------------------------------------------------------ tracker driver / whole forward
+struct TrackPlan { size_t coords, coords0, ffeats, ffeat0, X, delta, mixer, total; };   // floats
+TrackPlan plan_track(int B, int N, int S) {
+    TrackPlan P;
+    Bump b;
+    const int M = B * N * S;
+    P.coords = b.take((size_t)M * 2);
+    P.coords0 = b.take((size_t)M * 2);
+    P.ffeats = b.take((size_t)M * PIPS_C);
+    P.ffeat0 = b.take((size_t)B * N * PIPS_C);
+    P.X = b.take((size_t)M * PIPS_KIN_PAD);
+    P.delta = b.take((size_t)B * N * arena_layout(S).nout_pad);
+    P.mixer = b.take(mixer_workspace_bytes(M, S) / sizeof(float));
+    P.total = b.off;
+    return P;
+}
+struct FwdPlan { size_t pyramid, enc, track, total; };   // floats
+FwdPlan plan_forward(int B, int S, int H, int W, int N, int stride) {
+    FwdPlan P;
+    Bump b;
+    const int F = B * S;
+    P.pyramid = b.take(pyramid_view(F, H / stride, W / stride).total());
+    P.enc = b.take(plan_encoder(F, H, W, stride).total);
+    P.track = b.take(plan_track(B, N, S).total);
+    P.total = b.off;
+    return P;
+}
+
+size_t score_map_workspace_bytes(int B, int S, int H8, int W8) {
+    if (B <= 0 || S <= 0 || H8 <= 0 || W8 <= 0) return 0;
+    return (size_t)B * S * H8 * W8 * PIPS_C * sizeof(float);
+}
+int score_map_prepare(const float* pyramid, int B, int S, int H8, int W8, float* U, hipStream_t st) {
+    PIPS_CHECK_ARG(pyramid && U && B > 0 && S > 0 && H8 >= 8 && W8 >= 8, "score_map_prepare: bad argument");
+    const PyramidView v = pyramid_view(B * S, H8, W8);
+    return launch_score_upsum(pyramid, v.off, v.lh, v.lw, B * S, U, st);
+}
+
+// The tracker on cached maps.  pyramid: B clips x R frame slots of H8 x W8 level-0 pixels holding T logical frames (a linear
+// cache has R = T); S = window length (tokens per particle) the arena was packed for, S == PIPS_S runs the specialised kernels.
+// win_start / win_dir / coords_init / feat_init / out_ffeat0 and the score-map block ce_* may be null.
+struct TrackCall {
+    const void* arena; const float* pyramid;
+    int B, T, R, S, H8, W8;
+    const float* xys; const float* coords_init; const float* feat_init;
+    const int* win_start; const int* win_dir;
+    const float* times; int N, stride, iters, flags;
+    void* workspace; size_t workspace_bytes;
+    float* out_trajs; float* out_vis; float* out_ffeat0;
+    const float* ce_tgt; float* ce_terms; void* ce_ws; size_t ce_ws_bytes;
+    hipStream_t st;
+};
+
+int track_impl(const TrackCall& c) {
+    PIPS_CHECK_ARG(c.arena && c.pyramid && c.xys && c.times && c.workspace && c.out_trajs && c.out_vis, "track: null pointer");
+    PIPS_CHECK_ARG(c.B > 0 && c.N > 0 && c.T >= 1 && c.R >= 1 && c.iters >= 0 && c.stride >= 1,
+                   "track: need B,N,T,R,stride >= 1 and iters >= 0");
+    PIPS_CHECK_ARG(c.S >= 1 && c.S <= PIPS_S_MAX, "track: window length S=%d outside 1..%d", c.S, PIPS_S_MAX);
+    PIPS_CHECK_ARG(c.H8 >= 8 && c.W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", c.H8, c.W8);
+    PIPS_CHECK_ARG(c.win_dir == nullptr || c.win_start != nullptr, "track: win_dir needs win_start");
+    const int B = c.B, N = c.N, S = c.S;
+    const TrackPlan P = plan_track(B, N, S);
+    if (c.workspace_bytes < P.total * sizeof(float)) {
+        set_error("track: workspace %zu < %zu bytes", c.workspace_bytes, P.total * sizeof(float));
+        return PIPS_E_WORKSPACE;
+    }
+    hipStream_t st = c.st;
+    const float* arena = (const float*)c.arena;
+    float* ws = (float*)c.workspace;
+    const int M = B * N * S;
+    float* coords = ws + P.coords; float* coords0 = ws + P.coords0; float* ffeats = ws + P.ffeats;
+    float* ffeat0 = c.out_ffeat0 != nullptr ? c.out_ffeat0 : ws + P.ffeat0;
+    const size_t traj_sz = (size_t)B * S * N * 2;
+    RUN(launch_init_coords(c.xys, c.coords_init, B, N, (float)c.stride, coords, coords0, c.out_trajs, st, S));
+    if (c.feat_init != nullptr) {
+        if (c.feat_init != ffeat0)
+            (void)hipMemcpyAsync(ffeat0, c.feat_init, (size_t)B * N * PIPS_C * sizeof(float), hipMemcpyDeviceToDevice, st);
+    } else {
+        RUN(launch_point_sample_strided(c.pyramid, B, c.R, c.T, c.H8, c.W8, coords, S * 2, N, c.win_start, ffeat0, st));   // :463
+    }
+    RUN(launch_init_ffeats(ffeat0, B * N, ffeats, st, S));                                                    // :466
+    if (c.ce_tgt != nullptr) {          // score-map loss terms of every iteration (:501-511, 58-92): evaluation only
+        PIPS_CHECK_ARG(c.ce_terms && c.ce_ws && c.win_start == nullptr && c.T == S && c.R == c.T,
+                       "track: score-map terms need their output and workspace, S frames per clip and no windows");
+        if (c.ce_ws_bytes < score_map_workspace_bytes(B, c.T, c.H8, c.W8)) {
+            set_error("track: score-map workspace %zu < %zu bytes", c.ce_ws_bytes, score_map_workspace_bytes(B, c.T, c.H8, c.W8));
+            return PIPS_E_WORKSPACE;
+        }
+        RUN(score_map_prepare(c.pyramid, B, c.T, c.H8, c.W8, (float*)c.ce_ws, st));
+    }
+    if (c.iters == 0)     // the loop body never runs: vis_e comes from the initial features (:559)
+        RUN(launch_vis_head(arena, ffeats, B, N, c.out_vis, st, S));
+    // the mixer workspace is idle while the gather runs: it doubles as the binning scratch
+    GatherCall g;
+    memset(&g, 0, sizeof(g));
+    g.pyramid = c.pyramid; g.B = B; g.T = c.T; g.R = c.R; g.S = S; g.H8 = c.H8; g.W8 = c.W8;
+    g.ffeats = ffeats; g.coords = coords; g.times = c.times; g.N = N;
+    g.win_start = c.win_start; g.win_dir = c.win_dir;
+    g.X = ws + P.X;
+    g.bf16_maps = (c.flags & PIPS_FLAG_BF16_MAPS) != 0;
+    g.route = GATHER_AUTO;
+    g.scratch = ws + P.mixer; g.scratch_bytes = mixer_workspace_bytes(M, S);
+    g.st = st;
+    for (int it = 0; it < c.iters; ++it) {                                                                   // :499
+        if (c.ce_tgt != nullptr)         // fcorr_fn.corr(ffeats) of this iteration (:501), before the update
+            RUN(launch_score_terms((const float*)c.ce_ws, B, S, c.H8, c.W8, ffeats, N, c.ce_tgt, c.ce_terms + (size_t)it * M * 2, st));
+        RUN(mixer_input(g));
+        RUN(mixer_impl(arena, ws + P.X, M, S, mixer_mode(c.flags), ws + P.delta, ws + P.mixer, mixer_workspace_bytes(M, S), st, nullptr));
+        RUN(launch_state_update(arena, ws + P.delta, ffeats, coords, coords0, B, N, (float)c.stride,
+                                c.out_trajs + (size_t)(it + 1) * traj_sz, it + 1 == c.iters ? c.out_vis : nullptr, st, S));
+    }
+    PIPS_CHECK_LAUNCH("pips_track");
+    return PIPS_OK;
+}
+
+// what every pips_track* form shares; the caller names R, S, win_dir and the score-map block
+TrackCall track_call(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys, const float* coords_init,
+                     const float* feat_init, const int* win_start, const float* times, int N, int stride, int iters, int flags,
+                     void* workspace, size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
+    TrackCall c;
+    memset(&c, 0, sizeof(c));
+    c.arena = arena; c.pyramid = pyramid; c.B = B; c.T = T; c.H8 = H8; c.W8 = W8;
+    c.xys = xys; c.coords_init = coords_init; c.feat_init = feat_init; c.win_start = win_start;
+    c.times = times; c.N = N; c.stride = stride; c.iters = iters; c.flags = flags;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.out_trajs = out_trajs; c.out_vis = out_vis; c.out_ffeat0 = out_ffeat0;
+    c.st = (hipStream_t)stream;
+    c.R = T; c.S = PIPS_S;               // a linear cache and the window of the shipped checkpoints, unless the caller says otherwise
+    return c;
+}
+
+// what every pips_mixer_input_build* form shares: a linear cache of `frames` frames per clip, windows of PIPS_S rows, no
+// per-particle window table, fp32 maps, route AUTO
+GatherCall gather_call(const float* pyramid, int B, int frames, int H8, int W8, const float* ffeats, const float* coords,
+                       const float* times, int N, float* X, void* stream) {
+    GatherCall g;
+    memset(&g, 0, sizeof(g));
+    g.pyramid = pyramid; g.B = B; g.T = g.R = frames; g.S = PIPS_S; g.H8 = H8; g.W8 = W8;
+    g.ffeats = ffeats; g.coords = coords; g.times = times; g.N = N; g.X = X;
+    g.st = (hipStream_t)stream;
+    return g;
+}
+
+}  // namespace
+
+// ================================================================== the C ABI (include/pips_hip.h)
+// Argument checks that belong to one entry point, the descriptor, one call.  Nothing below launches a kernel itself.
+extern "C" {
+
+const char* pips_last_error(void) { return g_err; }
+int pips_abi_version(void) { return 3; }
+int pips_device_cus(void) { return device_cus(); }
+
+// ---- weights
+size_t pips_weight_arena_bytes(void) { return pips_weight_arena_bytes_s(PIPS_S); }
+int pips_delta_stride(int S) { return (S < 1 || S > PIPS_S_MAX) ? 0 : arena_layout(S).nout_pad; }
+size_t pips_weight_arena_bytes_s(int S) {
+    if (S < 1 || S > PIPS_S_MAX) return 0;
+    return arena_layout(S).total_all * sizeof(float);
+}
+int pips_repack_weights(const void* const* params, int nparams, void* arena, void* stream) {
+    return repack_weights(params, nparams, arena, PIPS_S, PIPS_PACK_FP32 | PIPS_PACK_BF16 | PIPS_PACK_SPLIT, stream);
+}
+int pips_repack_weights_ex(const void* const* params, int nparams, void* arena, int sections, void* stream) {
+    return repack_weights(params, nparams, arena, PIPS_S, sections, stream);
+}
+int pips_repack_weights_s(const void* const* params, int nparams, void* arena, int S, int sections, void* stream) {
+    return repack_weights(params, nparams, arena, S, sections, stream);
+}
+
+// ---- building blocks
+int pips_gemm_f32(const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int N,
+                  int K, int epi, const float* R, int ldr, void* stream) {
+    PIPS_CHECK_ARG(A && W && C, "gemm: null pointer");
+    PIPS_CHECK_ARG(epi_ok(epi, R), "gemm: bad epilogue");
+    return launch_gemm(gemm_args(A, lda, W, bias, C, ldc, M, N, K, epi, R, ldr), (hipStream_t)stream);
+}
+int pips_gemm_f32x3(const float* A, int lda, const void* W3, const float* bias, float* C, int ldc, int M, int N,
+                    int K, int epi, const float* R, int ldr, void* stream) {
+    PIPS_CHECK_ARG(A && W3 && C, "gemm_x3: null pointer");
+    PIPS_CHECK_ARG(epi_ok(epi, R), "gemm_x3: bad epilogue");
+    return launch_gemm_x3(gemm_args(A, lda, W3, bias, C, ldc, M, N, K, epi, R, ldr), (hipStream_t)stream);
+}
+int pips_gemm_bf16(const void* A, int a_bf16, int lda, const void* W, const float* bias, void* C, int out_bf16, int ldc,
+                   int M, int N, int K, int epi, const float* R, int ldr, void* stream) {
+    PIPS_CHECK_ARG(A && W && C, "gemm_bf16: null pointer");
+    return launch_gemm_bf16(gemm_args(A, lda, W, bias, C, ldc, M, N, K, epi, R, ldr), a_bf16, out_bf16, (hipStream_t)stream);
+}
+int pips_gemm_bf16_route(int M, int N, int K, int epi, int a_bf16, int out_bf16) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return gemm_bf16_asm_route(route_args(M, N, K, epi), a_bf16, out_bf16);
+}
+int pips_gemm_f32_route(int M, int N, int K, int epi) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return gemm_f32_t4_route(route_args(M, N, K, epi), nullptr);
+}
+int pips_split_bf16x3(const float* src, size_t n, void* dst3, void* stream) {
+    PIPS_CHECK_ARG(src && dst3, "split_bf16x3: null pointer");
+    return launch_split_bf16x3(src, n, dst3, (hipStream_t)stream);
+}
+
+int pips_conv_nhwc_f32(const float* in, int F, int H, int W, int Cin, const float* wgt, const float* bias,
+                       int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
+                       void* stream) {
+    PIPS_CHECK_ARG(in && wgt && out, "conv: null pointer");
+    return conv_nhwc(conv_call(in, F, H, W, Cin, wgt, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host), (hipStream_t)stream);
+}
+int pips_conv_nhwc_bf16(const float* in, int F, int H, int W, int Cin, const void* wgt_bf16, const float* bias,
+                        int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
+                        void* stream) {
+    PIPS_CHECK_ARG(in && wgt_bf16 && out, "conv_bf16: null pointer");
+    ConvCall c = conv_call(in, F, H, W, Cin, wgt_bf16, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host);
+    c.mode = BF16;
+    return conv_nhwc(c, (hipStream_t)stream);
+}
+int pips_conv_nhwc_f32x3(const float* in, int F, int H, int W, int Cin, const void* wgt3, const float* bias,
+                         int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
+                         void* stream) {
+    PIPS_CHECK_ARG(in && wgt3 && out, "conv_x3: null pointer");
+    ConvCall c = conv_call(in, F, H, W, Cin, wgt3, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host);
+    c.mode = SPLIT;
+    return conv_nhwc(c, (hipStream_t)stream);
+}
+int pips_conv_nhwc_bf16_maps(const void* in_bf16, const float* in_norm, int F, int H, int W, int Cin, const void* wgt_bf16,
+                             const float* bias, int Cout, int ksize, int cstride, int pad, void* out, int out_is_bf16,
+                             float* stats, int stats_parts_cap, int* tiles_m_host, void* stream) {
+    PIPS_CHECK_ARG(in_bf16 && wgt_bf16 && out, "conv_bf16_maps: null pointer");
+    ConvCall c = conv_call(in_bf16, F, H, W, Cin, wgt_bf16, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host);
+    c.mode = BF16;
+    c.in_bf16 = true;
+    c.out_bf16 = out_is_bf16 != 0;
+    c.in_norm = in_norm;
+    c.parts_cap = stats_parts_cap;
+    return conv_nhwc(c, (hipStream_t)stream);
+}
+
+// ---- encoder and pyramid
+size_t pips_encoder_workspace_bytes(int F, int H, int W, int stride) {
+    if (F <= 0 || H <= 0 || W <= 0 || stride < 1) return 0;
+    return plan_encoder(F, H, W, stride).total * sizeof(float);
+}
+size_t pips_pyramid_offset(int F, int H, int W, int stride, int level) {
+    const PyramidView v = pyramid_view(F, H / stride, W / stride);
+    return level <= 0 ? 0 : level < PIPS_LEVELS ? v.off[level] : v.levels;
+}
+size_t pips_pyramid_mirror_offset(int F, int H, int W, int stride) { return pyramid_view(F, H / stride, W / stride).levels; }
+size_t pips_pyramid_floats(int F, int H, int W, int stride) { return pyramid_view(F, H / stride, W / stride).total(); }
+int pips_pyramid_mirror(float* pyramid, int F, int H, int W, int stride, void* stream) {
+    PIPS_CHECK_ARG(pyramid != nullptr && F > 0, "pyramid_mirror: bad argument");
+    const size_t n = pyramid_view(F, H / stride, W / stride).levels;
+    return launch_pyramid_mirror(pyramid, n, pyramid + n, (hipStream_t)stream);
+}
+int pips_pyramid_append(const float* src, int k, float* ring, int R, int T0, int H, int W, int stride, void* stream) {
+    PIPS_CHECK_ARG(src != nullptr && ring != nullptr, "pyramid_append: null pointer");
+    PIPS_CHECK_ARG(R >= 1 && T0 >= 0 && k >= 1 && k <= R, "pyramid_append: need R >= 1, T0 >= 0 and 1 <= k <= R (k=%d, R=%d, T0=%d)",
+                   k, R, T0);
+    PIPS_CHECK_ARG(H > 0 && W > 0 && stride >= 1, "pyramid_append: bad geometry");
+    const PyramidView from = pyramid_view(k, H / stride, W / stride), to = pyramid_view(R, H / stride, W / stride);
+    PIPS_CHECK_ARG(!to.empty(), "pyramid_append: map too small");
+    int pf8[PIPS_LEVELS];
+    for (int l = 0; l < PIPS_LEVELS; ++l) pf8[l] = to.lh[l] * to.lw[l] * PIPS_C / 8;
+    return launch_pyramid_append(src, from.off, k, ring, to.off, ring + to.levels, pf8, R, T0, (hipStream_t)stream);
+}
+
+int pips_encoder_fwd(const void* arena, const float* rgbs, int F, int H, int W, int stride, float* pyramid,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return encoder_impl(arena, rgbs, F, H, W, stride, 0, pyramid, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int pips_encoder_fwd_bf16(const void* arena, const float* rgbs, int F, int H, int W, int stride, float* pyramid,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    return encoder_impl(arena, rgbs, F, H, W, stride, PIPS_FLAG_BF16_ENCODER, pyramid, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int pips_encoder_fwd_ex(const void* arena, const void* rgbs, int F, int H, int W, int stride, int flags,
+                        float* pyramid, void* workspace, size_t workspace_bytes, void* stream) {
+    return encoder_impl(arena, rgbs, F, H, W, stride, flags, pyramid, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int pips_resize_frames(const void* src, int src_is_u8, int planes, int h, int w, float* dst, int H, int W, void* stream) {
@@ -697,412 +1076,105 @@ int pips_resize_frames(const void* src, int src_is_u8, int planes, int h, int w,
     return launch_resize_frames(src, src_is_u8, planes, h, w, dst, H, W, (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------ tracker stages
+// ---- tracker stages
 int pips_point_sample(const float* level0, int B, int S, int H8, int W8, const float* xy, int N, float* out,
                       void* stream) {
     PIPS_CHECK_ARG(level0 && xy && out && B > 0 && N > 0 && S > 0, "point_sample: bad argument");
     return launch_point_sample(level0, B, S, H8, W8, xy, N, out, (hipStream_t)stream);
 }
 
-// scratch != null and a dense, un-windowed query set: LDS-tiled kernel; otherwise the direct one
-static int mixer_input(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats, const float* coords,
-                       const float* times, int N, const int* win_start, float* X, hipStream_t st,
-                       void* scratch = nullptr, size_t scratch_bytes = 0, int force_tiled = -1, hipEvent_t* ev = nullptr,
-                       int Sw = PIPS_S,         // S: frames per clip in the pyramid; Sw: window length = mixer rows per particle
-                       bool bf16_maps = false,     // the direct gather reads the bf16 mirror behind the fp32 levels
-                       const int* win_dir = nullptr,     // per-particle time direction (sign), read with win_start only
-                       int T = 0) {             // logical frames (the clamp bound), 0 = S; frame f lies in slot f mod S
-    if (T == 0) T = S;
-    size_t off[PIPS_LEVELS];
-    int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    lh[0] = H8; lw[0] = W8;
-    for (int l = 1; l < PIPS_LEVELS; ++l) { lh[l] = lh[l - 1] / 2; lw[l] = lw[l - 1] / 2; }
-    size_t o = 0;
-    for (int l = 0; l < PIPS_LEVELS; ++l) {
-        off[l] = o;
-        o += ((size_t)B * S * lh[l] * lw[l] * PIPS_C + 63) / 64 * 64;
-    }
-    PIPS_CHECK_ARG(lh[PIPS_LEVELS - 1] >= 1 && lw[PIPS_LEVELS - 1] >= 1, "mixer_input: map too small");
-    const bool can_tile = scratch != nullptr && win_start == nullptr && win_dir == nullptr && S == PIPS_S && T == S && Sw == PIPS_S &&
-                          scratch_bytes >= tiled_gather_scratch_bytes(B, N, H8, W8);
-    const bool tiled = force_tiled >= 0 ? (force_tiled != 0) : tiled_gather_wanted(B, N, H8, W8, bf16_maps);
-    if (tiled && can_tile)      // (bf16 mode: the same work items on the matrix cores, reading the bf16 mirror behind the fp32 levels)
-        return launch_mixer_input_tiled(pyramid, off, lh, lw, B, S, ffeats, coords, times, N, X, scratch, scratch_bytes, st, ev,
-                                        bf16_maps ? reinterpret_cast<const unsigned short*>(pyramid + o) : nullptr);
-    PIPS_CHECK_ARG(force_tiled != 1, "tiled gather needs scratch of %zu bytes, no win_start and 8 frames per clip",
-                   tiled_gather_scratch_bytes(B, N, H8, W8));
-    PIPS_CHECK_ARG(win_dir == nullptr || win_start != nullptr, "mixer_input: win_dir needs win_start");
-    if (bf16_maps)
-        return launch_mixer_input_bf16maps(pyramid + o, off, lh, lw, B, S, T, ffeats, coords, times, N, win_start, win_dir, X, st,
-                                           Sw);
-    return launch_mixer_input(pyramid, off, lh, lw, B, S, T, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
-}
-
 int pips_mixer_input_build(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
                            const float* coords, const float* times, int N, float* X, void* stream) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X, "mixer_input: null pointer");
-    PIPS_CHECK_ARG(S >= 1 && B > 0 && N > 0, "mixer_input: empty problem");
-    return mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, nullptr, X, (hipStream_t)stream);
+    return mixer_input(gather_call(pyramid, B, S, H8, W8, ffeats, coords, times, N, X, stream));
 }
-
 int pips_mixer_input_build_ex(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats, const float* coords,
                               const float* times, int N, const int* win_start, int flags, float* X, void* stream) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X, "mixer_input: null pointer");
-    PIPS_CHECK_ARG(S >= 1 && B > 0 && N > 0, "mixer_input: empty problem");
-    return mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
-                       PIPS_S, (flags & PIPS_FLAG_BF16_MAPS) != 0);
+    GatherCall g = gather_call(pyramid, B, S, H8, W8, ffeats, coords, times, N, X, stream);
+    g.win_start = win_start;
+    g.bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
+    g.route = GATHER_DIRECT;
+    return mixer_input(g);
 }
-
 int pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, int W8, const float* ffeats, const float* coords,
                                const float* times, int N, const int* win_start, const int* win_dir, int flags, int S, float* X,
                                void* stream) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X, "mixer_input: null pointer");
-    PIPS_CHECK_ARG(T >= 1 && B > 0 && N > 0, "mixer_input: empty problem");
-    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", S, PIPS_S_MAX);
-    return mixer_input(pyramid, B, T, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
-                       S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir);
+    return pips_mixer_input_build_ring(pyramid, B, T, T, H8, W8, ffeats, coords, times, N, win_start, win_dir, flags, S, X, stream);
 }
-
 int pips_mixer_input_build_ring(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
                                 const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
                                 int flags, int S, float* X, void* stream) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X, "mixer_input: null pointer");
-    PIPS_CHECK_ARG(T >= 1 && R >= 1 && B > 0 && N > 0, "mixer_input: need T, R, B, N >= 1");
-    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", S, PIPS_S_MAX);
-    return mixer_input(pyramid, B, R, H8, W8, ffeats, coords, times, N, win_start, X, (hipStream_t)stream, nullptr, 0, 0, nullptr,
-                       S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir, T);
+    GatherCall g = gather_call(pyramid, B, T, H8, W8, ffeats, coords, times, N, X, stream);
+    g.R = R;
+    g.S = S;
+    g.win_start = win_start;
+    g.win_dir = win_dir;
+    g.bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
+    g.route = GATHER_DIRECT;
+    return mixer_input(g);
 }
 
 size_t pips_gather_scratch_bytes(int B, int N, int H8, int W8) {
     if (B <= 0 || N <= 0 || H8 <= 0 || W8 <= 0) return 0;
     return tiled_gather_scratch_bytes(B, N, H8, W8);
 }
-
-int pips_mixer_input_build_tiled(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
-                                 const float* coords, const float* times, int N, float* X, void* scratch,
-                                 size_t scratch_bytes, void* stream) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X && scratch, "mixer_input_tiled: null pointer");
-    PIPS_CHECK_ARG(S == PIPS_S && B > 0 && N > 0, "mixer_input_tiled: S must be %d", PIPS_S);
-    return mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, nullptr, X, (hipStream_t)stream, scratch,
-                       scratch_bytes, 1);
-}
-
-int pips_mixer_input_build_tiled_timed(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
-                                       const float* coords, const float* times, int N, float* X, void* scratch,
-                                       size_t scratch_bytes, void* stream, float* ms3_host) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X && scratch && ms3_host, "mixer_input_tiled_timed: null pointer");
-    PIPS_CHECK_ARG(S == PIPS_S && B > 0 && N > 0, "mixer_input_tiled: S must be %d", PIPS_S);
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) { set_error("hipEventCreate failed"); return PIPS_E_LAUNCH; }
-    int rc = mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, nullptr, X, (hipStream_t)stream, scratch,
-                         scratch_bytes, 1, ev);
-    if (rc == PIPS_OK && hipEventSynchronize(ev[3]) != hipSuccess) rc = PIPS_E_LAUNCH;
-    if (rc == PIPS_OK)
-        for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms3_host[i], ev[i], ev[i + 1]);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ev[i]);
-    return rc;
-}
-
 int pips_gather_route(int B, int N, int H8, int W8, int flags) {
     if (B <= 0 || N <= 0 || H8 <= 0 || W8 <= 0) return 0;
     if (!tiled_gather_wanted(B, N, H8, W8, (flags & PIPS_FLAG_BF16_MAPS) != 0)) return 0;
     return (flags & PIPS_FLAG_BF16_MAPS) ? 2 : 1;
 }
-
 int pips_mixer_input_build_tiled_ex(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats, const float* coords,
                                     const float* times, int N, int flags, float* X, void* scratch, size_t scratch_bytes,
                                     void* stream, float* ms3_host) {
-    PIPS_CHECK_ARG(pyramid && ffeats && coords && times && X && scratch, "mixer_input_tiled: null pointer");
-    PIPS_CHECK_ARG(S == PIPS_S && B > 0 && N > 0, "mixer_input_tiled: S must be %d", PIPS_S);
-    const bool bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
-    if (ms3_host == nullptr)
-        return mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, nullptr, X, (hipStream_t)stream, scratch, scratch_bytes, 1,
-                           nullptr, PIPS_S, bf16_maps);
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) { set_error("hipEventCreate failed"); return PIPS_E_LAUNCH; }
-    int rc = mixer_input(pyramid, B, S, H8, W8, ffeats, coords, times, N, nullptr, X, (hipStream_t)stream, scratch, scratch_bytes, 1,
-                         ev, PIPS_S, bf16_maps);
-    if (rc == PIPS_OK && hipEventSynchronize(ev[3]) != hipSuccess) rc = PIPS_E_LAUNCH;
-    if (rc == PIPS_OK)
-        for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms3_host[i], ev[i], ev[i + 1]);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ev[i]);
-    return rc;
+    GatherCall g = gather_call(pyramid, B, S, H8, W8, ffeats, coords, times, N, X, stream);
+    g.bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
+    g.scratch = scratch;
+    g.scratch_bytes = scratch_bytes;
+    return mixer_input_tiled(g, ms3_host);
+}
+int pips_mixer_input_build_tiled(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
+                                 const float* coords, const float* times, int N, float* X, void* scratch,
+                                 size_t scratch_bytes, void* stream) {
+    return pips_mixer_input_build_tiled_ex(pyramid, B, S, H8, W8, ffeats, coords, times, N, 0, X, scratch, scratch_bytes, stream,
+                                           nullptr);
+}
+int pips_mixer_input_build_tiled_timed(const float* pyramid, int B, int S, int H8, int W8, const float* ffeats,
+                                       const float* coords, const float* times, int N, float* X, void* scratch,
+                                       size_t scratch_bytes, void* stream, float* ms3_host) {
+    PIPS_CHECK_ARG(ms3_host != nullptr, "mixer_input_tiled_timed: null pointer");
+    return pips_mixer_input_build_tiled_ex(pyramid, B, S, H8, W8, ffeats, coords, times, N, 0, X, scratch, scratch_bytes, stream,
+                                           ms3_host);
 }
 
-size_t pips_mixer_workspace_bytes(int M) { return pips_mixer_workspace_bytes_s(M, PIPS_S); }
-size_t pips_mixer_workspace_bytes_s(int M, int S) {
-    if (M <= 0 || S < 1 || S > PIPS_S_MAX) return 0;
-    Bump b;
-    b.take((size_t)M * PIPS_DMIX); b.take((size_t)M * PIPS_DMIX); b.take((size_t)M * 4 * PIPS_DMIX);
-    b.take((size_t)(M / S) * PIPS_DMIX);
-    return b.off * sizeof(float);
-}
+size_t pips_mixer_workspace_bytes(int M) { return mixer_workspace_bytes(M, PIPS_S); }
+size_t pips_mixer_workspace_bytes_s(int M, int S) { return mixer_workspace_bytes(M, S); }
 
-// ev != nullptr: record ev[2g], ev[2g+1] around GEMM g (g = 0 in-proj, 1+2d up, 2+2d down, 25 head)
-static int gemm_h(const float* A, int a_bf16, int lda, const unsigned short* W, const float* bias, float* C,
-                  int out_bf16, int ldc, int M, int N, int K, int epi, const float* R, int ldr, hipStream_t st) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.W = reinterpret_cast<const float*>(W); g.bias = bias; g.C = C; g.R = R;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.epi = epi;
-    return launch_gemm_bf16(g, a_bf16, out_bf16, st);
-}
-
-int pips_gemm_bf16(const void* A, int a_bf16, int lda, const void* W, const float* bias, void* C, int out_bf16, int ldc,
-                   int M, int N, int K, int epi, const float* R, int ldr, void* stream) {
-    PIPS_CHECK_ARG(A && W && C, "gemm_bf16: null pointer");
-    return gemm_h(reinterpret_cast<const float*>(A), a_bf16, lda, reinterpret_cast<const unsigned short*>(W), bias,
-                  reinterpret_cast<float*>(C), out_bf16, ldc, M, N, K, epi, R, ldr, (hipStream_t)stream);
-}
-
-int pips_gemm_bf16_route(int M, int N, int K, int epi, int a_bf16, int out_bf16) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    static const float dummy = 0.f;                     // only null-ness of bias / R is inspected
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.bias = &dummy; g.R = &dummy;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N; g.epi = epi;
-    return gemm_bf16_asm_route(g, a_bf16, out_bf16);
-}
-
-int pips_device_cus(void) { return device_cus(); }
-
-int pips_gemm_f32_route(int M, int N, int K, int epi) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    static const float dummy = 0.f;                     // only null-ness of bias / R is inspected
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.bias = &dummy; g.R = &dummy;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N; g.epi = epi;
-    return gemm_f32_t4_route(g, nullptr);
-}
-
-// bf16 == 1: bf16 MFMA operands for every Linear of the mixer (weights pre-converted; the LayerNorm-2 output and the
-// 2048-wide hidden activation stored as bf16, everything else fp32); the 544-wide input projection rides
-// 32-element K blocks (544 = 17 x 32).
-// S: the window length the arena was packed for (tokens per particle); delta rows are nout_pad(S) wide.
-// matrix mode of the mixer from the PIPS_FLAG_* word: 0 exact fp32, 1 bf16 operands, 2 split-bf16, 3 bf16 operands + bf16 residual stream
-static int mixer_mode(int flags) {
-    if (flags & PIPS_FLAG_SPLIT_BF16) return 2;
-    if (flags & PIPS_FLAG_BF16_MIXER) return (flags & PIPS_FLAG_BF16_STREAM) ? 3 : 1;
-    return 0;
-}
-
-// bf16 == 3: bf16 operands AND a bf16 residual stream (PIPS_FLAG_BF16_STREAM, S = 8): x is stored as bf16 -- written by the input
-// projection, read and rewritten by token mixing and the down-projection (whose fp32 sums take the bf16 residual and are rounded
-// once), read by the final LayerNorm; what PreNormResidual holds under autocast (nets/pips.py:93-100).
-static int mixer_impl(const void* arena_v, const float* X, int M, float* delta, void* workspace,
-                      size_t workspace_bytes, void* stream, hipEvent_t* ev, int bf16 = 0, int S = PIPS_S) {
-    PIPS_CHECK_ARG(arena_v && X && delta && workspace, "mixer: null pointer");
-    const int xb = (bf16 == 3 && S == PIPS_S) ? 1 : 0;
-    if (bf16 == 3) bf16 = 1;
-    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "mixer: S=%d outside 1..%d", S, PIPS_S_MAX);
-    PIPS_CHECK_ARG(M > 0 && M % S == 0, "mixer: M=%d must be a positive multiple of S=%d", M, S);
-    if (workspace_bytes < pips_mixer_workspace_bytes_s(M, S)) {
-        set_error("mixer: workspace %zu < %zu bytes", workspace_bytes, pips_mixer_workspace_bytes_s(M, S));
-        return PIPS_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const ArenaLayout& A = arena_layout(S);
-    const int NOUT = A.nout_pad;
-    const float* arena = (const float*)arena_v;
-    Bump b;
-    float* ws = (float*)workspace;
-    float* x = ws + b.take((size_t)M * PIPS_DMIX);
-    float* xn = ws + b.take((size_t)M * PIPS_DMIX);
-    float* h = ws + b.take((size_t)M * 4 * PIPS_DMIX);
-    float* pooled = ws + b.take((size_t)(M / S) * PIPS_DMIX);
-    const int P = M / S;
-    int g = 0;
-#define TIMED(call)                                                        \
-    do {                                                                   \
-        if (ev) (void)hipEventRecord(ev[2 * g], st);                       \
-        RUN(call);                                                         \
-        if (ev) (void)hipEventRecord(ev[2 * g + 1], st);                   \
-        ++g;                                                               \
-    } while (0)
-
-    const unsigned short* tw = reinterpret_cast<const unsigned short*>(arena + A.total) + A.total_h;
-    if (bf16 == 2) {                                   // split-bf16: every GEMM of the mixer
-        TIMED(pips_gemm_f32x3(X, PIPS_KIN_PAD, tw + A.t_in, arena + A.b_in, x, PIPS_DMIX, M, PIPS_DMIX, PIPS_KIN_PAD,
-                              EPI_BIAS, nullptr, 0, stream));
-        for (int d = 0; d < PIPS_DEPTH; ++d) {
-            const MixLayerW& L = A.mix[d];
-            RUN(launch_token_mix(arena, L, x, xn, P, st, 0, S));
-            TIMED(pips_gemm_f32x3(xn, PIPS_DMIX, tw + A.t_w1[d], arena + L.b1, h, 4 * PIPS_DMIX, M, 4 * PIPS_DMIX,
-                                  PIPS_DMIX, EPI_GELU, nullptr, 0, stream));
-            TIMED(pips_gemm_f32x3(h, 4 * PIPS_DMIX, tw + A.t_w2[d], arena + L.b2, x, PIPS_DMIX, M, PIPS_DMIX,
-                                  4 * PIPS_DMIX, EPI_RESIDUAL, x, PIPS_DMIX, stream));
-        }
-        RUN(launch_ln_mean(x, arena + A.lnf_g, arena + A.lnf_b, pooled, P, st, S));
-        TIMED(pips_gemm_f32x3(pooled, PIPS_DMIX, tw + A.t_head, arena + A.b_head, delta, NOUT, P, NOUT,
-                              PIPS_DMIX, EPI_BIAS, nullptr, 0, stream));
-        return PIPS_OK;
-    }
-    if (bf16) {
-        const unsigned short* hw = reinterpret_cast<const unsigned short*>(arena + A.total);
-        TIMED(gemm_h(X, 0, PIPS_KIN_PAD, hw + A.h_in, arena + A.b_in, x, xb, PIPS_DMIX, M, PIPS_DMIX, PIPS_KIN_PAD,
-                     EPI_BIAS, nullptr, 0, st));
-    } else {
-        TIMED(pips_gemm_f32(X, PIPS_KIN_PAD, arena + A.w_in, arena + A.b_in, x, PIPS_DMIX, M, PIPS_DMIX, PIPS_KIN_PAD,
-                            EPI_BIAS, nullptr, 0, stream));
-    }
-    for (int d = 0; d < PIPS_DEPTH; ++d) {
-        const MixLayerW& L = A.mix[d];
-        RUN(launch_token_mix(arena, L, x, xn, P, st, bf16 == 1, S, xb));
-        if (bf16) {
-            const unsigned short* hw = reinterpret_cast<const unsigned short*>(arena + A.total);
-            TIMED(gemm_h(xn, 1, PIPS_DMIX, hw + A.h_w1[d], arena + L.b1, h, 1, 4 * PIPS_DMIX, M, 4 * PIPS_DMIX,
-                         PIPS_DMIX, EPI_GELU, nullptr, 0, st));
-            TIMED(gemm_h(h, 1, 4 * PIPS_DMIX, hw + A.h_w2[d], arena + L.b2, x, xb, PIPS_DMIX, M, PIPS_DMIX,
-                         4 * PIPS_DMIX, EPI_RESIDUAL | (xb ? EPI_RES_BF16 : 0), x, PIPS_DMIX, st));
-            continue;
-        }
-        TIMED(pips_gemm_f32(xn, PIPS_DMIX, arena + L.w1, arena + L.b1, h, 4 * PIPS_DMIX, M, 4 * PIPS_DMIX, PIPS_DMIX,
-                            EPI_GELU, nullptr, 0, stream));
-        TIMED(pips_gemm_f32(h, 4 * PIPS_DMIX, arena + L.w2, arena + L.b2, x, PIPS_DMIX, M, PIPS_DMIX, 4 * PIPS_DMIX,
-                            EPI_RESIDUAL, x, PIPS_DMIX, stream));
-    }
-    RUN(launch_ln_mean(x, arena + A.lnf_g, arena + A.lnf_b, pooled, P, st, S, xb));
-    if (bf16) {
-        const unsigned short* hw = reinterpret_cast<const unsigned short*>(arena + A.total);
-        TIMED(gemm_h(pooled, 0, PIPS_DMIX, hw + A.h_head, arena + A.b_head, delta, 0, NOUT, P, NOUT,
-                     PIPS_DMIX, EPI_BIAS, nullptr, 0, st));
-    } else {
-        TIMED(pips_gemm_f32(pooled, PIPS_DMIX, arena + A.w_head, arena + A.b_head, delta, NOUT, P, NOUT,
-                            PIPS_DMIX, EPI_BIAS, nullptr, 0, stream));
-    }
-#undef TIMED
-    return PIPS_OK;
-}
-
-int pips_mixer_fwd(const void* arena_v, const float* X, int M, float* delta, void* workspace, size_t workspace_bytes,
-                   void* stream) {
-    return mixer_impl(arena_v, X, M, delta, workspace, workspace_bytes, stream, nullptr);
-}
-
-int pips_mixer_fwd_bf16(const void* arena_v, const float* X, int M, float* delta, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-    return mixer_impl(arena_v, X, M, delta, workspace, workspace_bytes, stream, nullptr, 1);
-}
-
-int pips_mixer_fwd_x3(const void* arena_v, const float* X, int M, float* delta, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    return mixer_impl(arena_v, X, M, delta, workspace, workspace_bytes, stream, nullptr, 2);
-}
-
-int pips_mixer_fwd_s(const void* arena_v, const float* X, int M, int S, int flags, float* delta, void* workspace,
+int pips_mixer_fwd_s(const void* arena, const float* X, int M, int S, int flags, float* delta, void* workspace,
                      size_t workspace_bytes, void* stream) {
-    return mixer_impl(arena_v, X, M, delta, workspace, workspace_bytes, stream, nullptr, mixer_mode(flags), S);
+    return mixer_impl(arena, X, M, S, mixer_mode(flags), delta, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
 }
-
-int pips_mixer_fwd_timed(const void* arena_v, const float* X, int M, float* delta, void* workspace,
-                         size_t workspace_bytes, void* stream, float* ms_host) {
-    return pips_mixer_fwd_timed_ex(arena_v, X, M, 0, delta, workspace, workspace_bytes, stream, ms_host);
+int pips_mixer_fwd(const void* arena, const float* X, int M, float* delta, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    return pips_mixer_fwd_s(arena, X, M, PIPS_S, 0, delta, workspace, workspace_bytes, stream);
 }
-
-int pips_mixer_fwd_timed_ex(const void* arena_v, const float* X, int M, int flags, float* delta, void* workspace,
+int pips_mixer_fwd_bf16(const void* arena, const float* X, int M, float* delta, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    return pips_mixer_fwd_s(arena, X, M, PIPS_S, PIPS_FLAG_BF16_MIXER, delta, workspace, workspace_bytes, stream);
+}
+int pips_mixer_fwd_x3(const void* arena, const float* X, int M, float* delta, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return pips_mixer_fwd_s(arena, X, M, PIPS_S, PIPS_FLAG_SPLIT_BF16, delta, workspace, workspace_bytes, stream);
+}
+int pips_mixer_fwd_timed_ex(const void* arena, const float* X, int M, int flags, float* delta, void* workspace,
                             size_t workspace_bytes, void* stream, float* ms_host) {
-    PIPS_CHECK_ARG(ms_host != nullptr, "mixer_timed: null output");
-    const int mm = mixer_mode(flags);
-    constexpr int NG = 2 * PIPS_DEPTH + 2;
-    constexpr int NCAL = 8;                      // empty event pairs: the marker-to-marker overhead
-    hipEvent_t ev[2 * NG], cal[2 * NCAL];
-    for (int i = 0; i < 2 * NG; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) { set_error("hipEventCreate failed"); return PIPS_E_LAUNCH; }
-    for (int i = 0; i < 2 * NCAL; ++i)
-        if (hipEventCreate(&cal[i]) != hipSuccess) { set_error("hipEventCreate failed"); return PIPS_E_LAUNCH; }
-    hipStream_t st = (hipStream_t)stream;
-    int rc = mixer_impl(arena_v, X, M, delta, workspace, workspace_bytes, stream, ev, mm);
-    for (int i = 0; i < 2 * NCAL; ++i) (void)hipEventRecord(cal[i], st);
-    if (rc == PIPS_OK && hipEventSynchronize(cal[2 * NCAL - 1]) != hipSuccess) rc = PIPS_E_LAUNCH;
-    if (rc == PIPS_OK) {
-        float up = 0.f, down = 0.f, t = 0.f, ovh = 0.f;
-        for (int i = 0; i < NCAL; ++i) { (void)hipEventElapsedTime(&t, cal[2 * i], cal[2 * i + 1]); ovh += t; }
-        ovh /= NCAL;
-        (void)hipEventElapsedTime(&ms_host[0], ev[0], ev[1]);
-        for (int d = 0; d < PIPS_DEPTH; ++d) {
-            (void)hipEventElapsedTime(&t, ev[2 * (1 + 2 * d)], ev[2 * (1 + 2 * d) + 1]); up += t;
-            (void)hipEventElapsedTime(&t, ev[2 * (2 + 2 * d)], ev[2 * (2 + 2 * d) + 1]); down += t;
-        }
-        ms_host[1] = up / PIPS_DEPTH;
-        ms_host[2] = down / PIPS_DEPTH;
-        (void)hipEventElapsedTime(&ms_host[3], ev[2 * (NG - 1)], ev[2 * (NG - 1) + 1]);
-        ms_host[4] = ovh;
-    }
-    for (int i = 0; i < 2 * NG; ++i) (void)hipEventDestroy(ev[i]);
-    for (int i = 0; i < 2 * NCAL; ++i) (void)hipEventDestroy(cal[i]);
-    return rc;
+    return mixer_timed(arena, X, M, flags, delta, workspace, workspace_bytes, (hipStream_t)stream, ms_host);
 }
-
-// The two channel-mix GEMM shapes as launch TRAINS: the 12 layers' up-projections (then their down-projections) back to back on the
-// layers' own weights between ONE event pair, reps times -> ms2_host = {up, down} milliseconds per launch.  No per-launch event and
-// no overhead to subtract: start-to-start durations as the forward pays them (what a rocprofv3 kernel trace of the forward shows).
-// The workspace must hold the activations of a mixer pass at this M (pips_mixer_fwd* on the same workspace first).
-int pips_mixer_gemm_train(const void* arena_v, int M, int flags, void* workspace, size_t workspace_bytes, void* stream, int reps,
+int pips_mixer_fwd_timed(const void* arena, const float* X, int M, float* delta, void* workspace,
+                         size_t workspace_bytes, void* stream, float* ms_host) {
+    return mixer_timed(arena, X, M, 0, delta, workspace, workspace_bytes, (hipStream_t)stream, ms_host);
+}
+int pips_mixer_gemm_train(const void* arena, int M, int flags, void* workspace, size_t workspace_bytes, void* stream, int reps,
                           float* ms2_host) {
-    PIPS_CHECK_ARG(arena_v && workspace && ms2_host && reps > 0, "mixer_gemm_train: bad argument");
-    PIPS_CHECK_ARG(M > 0 && M % PIPS_S == 0, "mixer_gemm_train: M=%d must be a positive multiple of %d", M, PIPS_S);
-    if (workspace_bytes < pips_mixer_workspace_bytes_s(M, PIPS_S)) {
-        set_error("mixer_gemm_train: workspace %zu < %zu bytes", workspace_bytes, pips_mixer_workspace_bytes_s(M, PIPS_S));
-        return PIPS_E_WORKSPACE;
-    }
-    // the mode pips_mixer_fwd_s derives from the same flags (incl. PIPS_FLAG_BF16_STREAM: the workspace's x is then a bf16 stream and
-    // the down-projection the bf16-residual kernel the forward launches)
-    const int mm0 = mixer_mode(flags);
-    const int xb = mm0 == 3 ? 1 : 0;
-    const int mm = mm0 == 3 ? 1 : mm0;
-    hipStream_t st = (hipStream_t)stream;
-    const ArenaLayout& A = arena_layout(PIPS_S);
-    const float* arena = (const float*)arena_v;
-    Bump b;
-    float* ws = (float*)workspace;
-    float* x = ws + b.take((size_t)M * PIPS_DMIX);
-    float* xn = ws + b.take((size_t)M * PIPS_DMIX);
-    float* h = ws + b.take((size_t)M * 4 * PIPS_DMIX);
-    const unsigned short* hw = reinterpret_cast<const unsigned short*>(arena + A.total);
-    const unsigned short* tw = hw + A.total_h;
-    hipEvent_t ev[3];
-    for (int i = 0; i < 3; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) { set_error("hipEventCreate failed"); return PIPS_E_LAUNCH; }
-    int rc = PIPS_OK;
-    auto up = [&](int d) {
-        const MixLayerW& L = A.mix[d];
-        if (mm == 2) return pips_gemm_f32x3(xn, PIPS_DMIX, tw + A.t_w1[d], arena + L.b1, h, 4 * PIPS_DMIX, M, 4 * PIPS_DMIX, PIPS_DMIX,
-                                            EPI_GELU, nullptr, 0, stream);
-        if (mm == 1) return gemm_h(xn, 1, PIPS_DMIX, hw + A.h_w1[d], arena + L.b1, h, 1, 4 * PIPS_DMIX, M, 4 * PIPS_DMIX, PIPS_DMIX,
-                                   EPI_GELU, nullptr, 0, st);
-        return pips_gemm_f32(xn, PIPS_DMIX, arena + L.w1, arena + L.b1, h, 4 * PIPS_DMIX, M, 4 * PIPS_DMIX, PIPS_DMIX, EPI_GELU,
-                             nullptr, 0, stream);
-    };
-    auto down = [&](int d) {                            // C = x (in place, like the mixer): R = x
-        const MixLayerW& L = A.mix[d];
-        if (mm == 2) return pips_gemm_f32x3(h, 4 * PIPS_DMIX, tw + A.t_w2[d], arena + L.b2, x, PIPS_DMIX, M, PIPS_DMIX, 4 * PIPS_DMIX,
-                                            EPI_RESIDUAL, x, PIPS_DMIX, stream);
-        if (mm == 1) return gemm_h(h, 1, 4 * PIPS_DMIX, hw + A.h_w2[d], arena + L.b2, x, xb, PIPS_DMIX, M, PIPS_DMIX, 4 * PIPS_DMIX,
-                                   EPI_RESIDUAL | (xb ? EPI_RES_BF16 : 0), x, PIPS_DMIX, st);
-        return pips_gemm_f32(h, 4 * PIPS_DMIX, arena + L.w2, arena + L.b2, x, PIPS_DMIX, M, PIPS_DMIX, 4 * PIPS_DMIX, EPI_RESIDUAL,
-                             x, PIPS_DMIX, stream);
-    };
-    for (int d = 0; d < PIPS_DEPTH && rc == PIPS_OK; ++d) rc = up(d);                   // warm: clocks, caches
-    (void)hipEventRecord(ev[0], st);
-    for (int r = 0; r < reps && rc == PIPS_OK; ++r)
-        for (int d = 0; d < PIPS_DEPTH && rc == PIPS_OK; ++d) rc = up(d);
-    (void)hipEventRecord(ev[1], st);
-    for (int r = 0; r < reps && rc == PIPS_OK; ++r)
-        for (int d = 0; d < PIPS_DEPTH && rc == PIPS_OK; ++d) rc = down(d);
-    (void)hipEventRecord(ev[2], st);
-    if (rc == PIPS_OK && hipEventSynchronize(ev[2]) != hipSuccess) rc = PIPS_E_LAUNCH;
-    if (rc == PIPS_OK) {
-        (void)hipEventElapsedTime(&ms2_host[0], ev[0], ev[1]);
-        (void)hipEventElapsedTime(&ms2_host[1], ev[1], ev[2]);
-        ms2_host[0] /= (float)(reps * PIPS_DEPTH);
-        ms2_host[1] /= (float)(reps * PIPS_DEPTH);
-    }
-    for (int i = 0; i < 3; ++i) (void)hipEventDestroy(ev[i]);
-    return rc;
+    return mixer_gemm_train(arena, M, flags, workspace, workspace_bytes, (hipStream_t)stream, reps, ms2_host);
 }
 
 int pips_state_update(const void* arena, const float* delta, float* ffeats, float* coords, const float* coords0,
@@ -1113,200 +1185,72 @@ int pips_state_update(const void* arena, const float* delta, float* ffeats, floa
                                (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------ tracker driver / whole forward
-namespace {
-struct TrackPlan { size_t coords, coords0, ffeats, ffeat0, X, delta, mixer, total; };   // floats
-TrackPlan plan_track(int B, int N, int S = PIPS_S) {
-    TrackPlan P;
-    Bump b;
-    const int M = B * N * S;
-    P.coords = b.take((size_t)M * 2);
-    P.coords0 = b.take((size_t)M * 2);
-    P.ffeats = b.take((size_t)M * PIPS_C);
-    P.ffeat0 = b.take((size_t)B * N * PIPS_C);
-    P.X = b.take((size_t)M * PIPS_KIN_PAD);
-    P.delta = b.take((size_t)B * N * arena_layout(S).nout_pad);
-    P.mixer = b.take(pips_mixer_workspace_bytes_s(M, S) / sizeof(float));
-    P.total = b.off;
-    return P;
-}
-struct FwdPlan { size_t pyramid, enc, track, total; };   // floats
-FwdPlan plan_forward(int B, int S, int H, int W, int N, int stride) {
-    FwdPlan P;
-    Bump b;
-    const int F = B * S;
-    P.pyramid = b.take(pips_pyramid_floats(F, H, W, stride));
-    P.enc = b.take(pips_encoder_workspace_bytes(F, H, W, stride) / sizeof(float));
-    P.track = b.take(plan_track(B, N, S).total);
-    P.total = b.off;
-    return P;
-}
-}  // namespace
-
-size_t pips_track_workspace_bytes(int B, int N) { return pips_track_workspace_bytes_s(B, N, PIPS_S); }
-size_t pips_track_workspace_bytes_s(int B, int N, int S) {
-    if (B <= 0 || N <= 0 || S < 1 || S > PIPS_S_MAX) return 0;
-    return plan_track(B, N, S).total * sizeof(float);
-}
-
-// level table of a pyramid with frames*H8*W8 level-0 pixels (pips_pyramid_offset's packing)
-static void pyramid_table(int frames, int H8, int W8, size_t* off, int* lh, int* lw) {
-    lh[0] = H8; lw[0] = W8;
-    for (int l = 1; l < PIPS_LEVELS; ++l) { lh[l] = lh[l - 1] / 2; lw[l] = lw[l - 1] / 2; }
-    size_t o = 0;
-    for (int l = 0; l < PIPS_LEVELS; ++l) {
-        off[l] = o;
-        o += ((size_t)frames * lh[l] * lw[l] * PIPS_C + 63) / 64 * 64;
-    }
-}
-
-size_t pips_score_map_workspace_bytes(int B, int S, int H8, int W8) {
-    if (B <= 0 || S <= 0 || H8 <= 0 || W8 <= 0) return 0;
-    return (size_t)B * S * H8 * W8 * PIPS_C * sizeof(float);
-}
-
+size_t pips_score_map_workspace_bytes(int B, int S, int H8, int W8) { return score_map_workspace_bytes(B, S, H8, W8); }
 int pips_score_map_prepare(const float* pyramid, int B, int S, int H8, int W8, float* U, void* stream) {
-    PIPS_CHECK_ARG(pyramid && U && B > 0 && S > 0 && H8 >= 8 && W8 >= 8, "score_map_prepare: bad argument");
-    size_t off[PIPS_LEVELS]; int lh[PIPS_LEVELS], lw[PIPS_LEVELS];
-    pyramid_table(B * S, H8, W8, off, lh, lw);
-    return launch_score_upsum(pyramid, off, lh, lw, B * S, U, (hipStream_t)stream);
+    return score_map_prepare(pyramid, B, S, H8, W8, U, (hipStream_t)stream);
 }
-
 int pips_score_map_terms(const float* U, int B, int S, int H8, int W8, const float* ffeats, int N, const float* tgt,
                          float* out, void* stream) {
     PIPS_CHECK_ARG(U && ffeats && tgt && out && B > 0 && S > 0 && N > 0, "score_map_terms: bad argument");
     return launch_score_terms(U, B, S, H8, W8, ffeats, N, tgt, out, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
-// S = window length (tokens per particle) the arena was packed for; S == PIPS_S runs the specialised kernels
-static int track_impl(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
-                      const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
-                      const float* times, int N, int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
-                      float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
-                      size_t ce_ws_bytes, void* stream);
-
-extern "C" {
+// ---- tracker on cached maps
+size_t pips_track_workspace_bytes(int B, int N) { return pips_track_workspace_bytes_s(B, N, PIPS_S); }
+size_t pips_track_workspace_bytes_s(int B, int N, int S) {
+    if (B <= 0 || N <= 0 || S < 1 || S > PIPS_S_MAX) return 0;
+    return plan_track(B, N, S).total * sizeof(float);
+}
 
 int pips_track(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
                const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
                int stride, int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs,
                float* out_vis, float* out_ffeat0, void* stream) {
-    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
-                      flags, PIPS_S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
-                      stream);
+    return track_impl(track_call(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters, flags,
+                                 workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream));
 }
-
 int pips_track_s(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
                  const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
                  int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
                  float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                  size_t ce_ws_bytes, void* stream) {
-    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
-                      flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes,
-                      stream);
+    TrackCall c = track_call(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters, flags,
+                             workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream);
+    c.S = S;
+    c.ce_tgt = ce_tgt; c.ce_terms = ce_terms; c.ce_ws = ce_ws; c.ce_ws_bytes = ce_ws_bytes;
+    return track_impl(c);
 }
-
 int pips_track_ce(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
                   const float* coords_init, const float* feat_init, const int* win_start, const float* times, int N,
                   int stride, int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs,
                   float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
                   size_t ce_ws_bytes, void* stream) {
-    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, nullptr, times, N, stride, iters,
-                      flags, PIPS_S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws,
-                      ce_ws_bytes, stream);
+    return pips_track_s(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters, flags, PIPS_S,
+                        workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes, stream);
 }
-
-int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
-                   const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
-                   const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
-                   size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
-    return track_impl(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
-                      flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
-                      stream);
-}
-
 int pips_track_ring(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
                     const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
                     const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
                     size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
-    return track_impl(arena, pyramid, B, T, R, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
-                      flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0,
-                      stream);
+    TrackCall c = track_call(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters, flags,
+                             workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream);
+    c.R = R;
+    c.S = S;
+    c.win_dir = win_dir;
+    return track_impl(c);
+}
+int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
+                   const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                   const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
+                   size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
+    return pips_track_ring(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
+                           flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream);
 }
 
-}  // extern "C"
-
-static int track_impl(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
-                      const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
-                      const float* times, int N, int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
-                      float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws,
-                      size_t ce_ws_bytes, void* stream) {
-    PIPS_CHECK_ARG(arena && pyramid && xys && times && workspace && out_trajs && out_vis, "track: null pointer");
-    PIPS_CHECK_ARG(B > 0 && N > 0 && T >= 1 && R >= 1 && iters >= 0 && stride >= 1,
-                   "track: need B,N,T,R,stride >= 1 and iters >= 0");
-    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "track: window length S=%d outside 1..%d", S, PIPS_S_MAX);
-    PIPS_CHECK_ARG(H8 >= 8 && W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", H8, W8);
-    PIPS_CHECK_ARG(win_dir == nullptr || win_start != nullptr, "track: win_dir needs win_start");
-    const TrackPlan P = plan_track(B, N, S);
-    if (workspace_bytes < P.total * sizeof(float)) {
-        set_error("track: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
-        return PIPS_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    float* ws = (float*)workspace;
-    const int M = B * N * S;
-    float* coords = ws + P.coords; float* coords0 = ws + P.coords0; float* ffeats = ws + P.ffeats;
-    float* ffeat0 = out_ffeat0 != nullptr ? out_ffeat0 : ws + P.ffeat0;
-    const size_t traj_sz = (size_t)B * S * N * 2;
-    RUN(launch_init_coords(xys, coords_init, B, N, (float)stride, coords, coords0, out_trajs, st, S));
-    if (feat_init != nullptr) {
-        if (feat_init != ffeat0)
-            (void)hipMemcpyAsync(ffeat0, feat_init, (size_t)B * N * PIPS_C * sizeof(float), hipMemcpyDeviceToDevice, st);
-    } else {
-        RUN(launch_point_sample_strided(pyramid, B, R, T, H8, W8, coords, S * 2, N, win_start, ffeat0, st));   // :463
-    }
-    RUN(launch_init_ffeats(ffeat0, B * N, ffeats, st, S));                                                    // :466
-    if (ce_tgt != nullptr) {            // score-map loss terms of every iteration (:501-511, 58-92): evaluation only
-        PIPS_CHECK_ARG(ce_terms && ce_ws && win_start == nullptr && T == S && R == T,
-                       "track: score-map terms need their output and workspace, S frames per clip and no windows");
-        if (ce_ws_bytes < pips_score_map_workspace_bytes(B, T, H8, W8)) {
-            set_error("track: score-map workspace %zu < %zu bytes", ce_ws_bytes, pips_score_map_workspace_bytes(B, T, H8, W8));
-            return PIPS_E_WORKSPACE;
-        }
-        RUN(pips_score_map_prepare(pyramid, B, T, H8, W8, (float*)ce_ws, stream));
-    }
-    if (iters == 0)       // the loop body never runs: vis_e comes from the initial features (:559)
-        RUN(launch_vis_head((const float*)arena, ffeats, B, N, out_vis, st, S));
-    for (int it = 0; it < iters; ++it) {                                                                     // :499
-        if (ce_tgt != nullptr)           // fcorr_fn.corr(ffeats) of this iteration (:501), before the update
-            RUN(launch_score_terms((const float*)ce_ws, B, S, H8, W8, ffeats, N, ce_tgt, ce_terms + (size_t)it * M * 2, st));
-        // the mixer workspace is idle while the gather runs: it doubles as the binning scratch
-        RUN(mixer_input(pyramid, B, R, H8, W8, ffeats, coords, times, N, win_start, ws + P.X, st, ws + P.mixer,
-                        pips_mixer_workspace_bytes_s(M, S), -1, nullptr, S, (flags & PIPS_FLAG_BF16_MAPS) != 0, win_dir, T));
-        RUN(mixer_impl(arena, ws + P.X, M, ws + P.delta, ws + P.mixer, pips_mixer_workspace_bytes_s(M, S), stream, nullptr,
-                       mixer_mode(flags), S));
-        RUN(launch_state_update((const float*)arena, ws + P.delta, ffeats, coords, coords0, B, N, (float)stride,
-                                out_trajs + (size_t)(it + 1) * traj_sz, it + 1 == iters ? out_vis : nullptr, st, S));
-    }
-    PIPS_CHECK_LAUNCH("pips_track");
-    return PIPS_OK;
-}
-
-extern "C" {
-
+// ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;
     return plan_forward(B, S, H, W, N, stride).total * sizeof(float);
-}
-
-int pips_forward(const void* arena, const float* rgbs, const float* xys, const float* coords_init,
-                 const float* feat_init, const float* times, int B, int S, int H, int W, int N, int stride,
-                 int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs, float* out_vis,
-                 float* out_ffeat0, void* stream) {
-    return pips_forward_ce(arena, rgbs, xys, coords_init, feat_init, times, B, S, H, W, N, stride, iters, flags, workspace,
-                           workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int pips_forward_ce(const void* arena, const float* rgbs, const float* xys, const float* coords_init,
@@ -1327,19 +1271,26 @@ int pips_forward_ce(const void* arena, const float* rgbs, const float* xys, cons
     float* ws = (float*)workspace;
     float* pyramid = ws + P.pyramid;
     if (!(flags & PIPS_FLAG_REUSE_MAPS))
-        RUN(encoder_impl(arena, rgbs, B * S, H, W, stride, pyramid, ws + P.enc,
-                         pips_encoder_workspace_bytes(B * S, H, W, stride), stream,
-                         ((flags & PIPS_FLAG_BF16_ENCODER) ? 1 : 0) | ((flags & PIPS_FLAG_RGB_U8) ? 2 : 0) |
-                             ((flags & PIPS_FLAG_SPLIT_BF16) ? 4 : 0)));
+        RUN(encoder_impl(arena, rgbs, B * S, H, W, stride, flags, pyramid, ws + P.enc, plan_encoder(B * S, H, W, stride).total * sizeof(float),
+                         (hipStream_t)stream));
     // both bf16 modes on: the bf16 encoder wrote the mirror with the maps and the gather reads it (with REUSE_MAPS the flags
     // describe the call that produced the maps, so the same forward gives the same result with and without the encoder pass)
     if (!(flags & PIPS_FLAG_SPLIT_BF16) &&
         (flags & (PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_BF16_MIXER)) == (PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_BF16_MIXER) &&
         PIPS_TUNE("PIPS_BF16_MAPS", 1))
         flags |= PIPS_FLAG_BF16_MAPS;
-    return track_impl(arena, pyramid, B, S, S, H / stride, W / stride, xys, coords_init, feat_init, nullptr, nullptr, times, N,
-                      stride, iters, flags, S, ws + P.track, plan_track(B, N, S).total * sizeof(float), out_trajs, out_vis,
-                      out_ffeat0, ce_tgt, ce_terms, ce_ws, ce_ws_bytes, stream);
+    TrackCall c = track_call(arena, pyramid, B, S, H / stride, W / stride, xys, coords_init, feat_init, nullptr, times, N, stride, iters,
+                             flags, ws + P.track, plan_track(B, N, S).total * sizeof(float), out_trajs, out_vis, out_ffeat0, stream);
+    c.S = S;
+    c.ce_tgt = ce_tgt; c.ce_terms = ce_terms; c.ce_ws = ce_ws; c.ce_ws_bytes = ce_ws_bytes;
+    return track_impl(c);
+}
+int pips_forward(const void* arena, const float* rgbs, const float* xys, const float* coords_init,
+                 const float* feat_init, const float* times, int B, int S, int H, int W, int N, int stride,
+                 int iters, int flags, void* workspace, size_t workspace_bytes, float* out_trajs, float* out_vis,
+                 float* out_ffeat0, void* stream) {
+    return pips_forward_ce(arena, rgbs, xys, coords_init, feat_init, times, B, S, H, W, N, stride, iters, flags, workspace,
+                           workspace_bytes, out_trajs, out_vis, out_ffeat0, nullptr, nullptr, nullptr, 0, stream);
 }
 
 }  // extern "C"

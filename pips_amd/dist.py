@@ -124,10 +124,7 @@ def encode_sharded(model, rgbs, group=None):
         g = _all_gather_cat(src.reshape(B, per, *src.shape[1:]), 1, group)
         dst.copy_(g.reshape(B * T, *src.shape[1:]))
     if part.bf16_maps:                                                    # the bf16 mirror follows the whole buffer's layout
-        import ctypes as C
-        with torch.cuda.device(pyr.device):
-            _lib.check(lib.pips_pyramid_mirror(_lib.ptr(pyr), B * T, H, W, st,
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pips_pyramid_mirror")
+        ops.pyramid_mirror(pyr, B * T, H, W, st)
     return FeatureCache(pyr, B, T, H, W, st, bf16_maps=part.bf16_maps)
 
 

@@ -130,7 +130,8 @@ class Pips(nn.Module):
         of split planes.  ``need`` = ops.PACK_* mask (default: what self._flags() implies)."""
         if need is None:
             fl = self._flags()
-            need = ops.PACK_FP32 | (ops.PACK_BF16 if fl & 6 else 0) | (ops.PACK_SPLIT if fl & 16 else 0)
+            need = ops.PACK_FP32 | (ops.PACK_BF16 if fl & (ops.FLAG_BF16_MIXER | ops.FLAG_BF16_ENCODER) else 0) | \
+                (ops.PACK_SPLIT if fl & ops.FLAG_SPLIT_BF16 else 0)
         if self._plist is None:
             # (owning module, leaf name) of every parameter: the LIVE object is looked up on every forward, so a
             # parameter that was replaced (load_state_dict(assign=True), ``node.weight = nn.Parameter(...)``) is seen
@@ -158,17 +159,17 @@ class Pips(nn.Module):
         ac = torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
         if self.matmul not in ("exact", "split"):
             raise ValueError(f"Pips.matmul must be 'exact' or 'split', not {self.matmul!r}")
-        bf = (2 if ac or self.mixer_dtype == torch.bfloat16 else 0) | \
-             (4 if ac or self.encoder_dtype == torch.bfloat16 else 0)     # PIPS_FLAG_BF16_MIXER | _ENCODER
-        if (bf & 2) and self.S == 8 and self.mixer_stream_dtype in (None, torch.bfloat16):
-            bf |= 64                                                      # PIPS_FLAG_BF16_STREAM
+        bf = (ops.FLAG_BF16_MIXER if ac or self.mixer_dtype == torch.bfloat16 else 0) | \
+             (ops.FLAG_BF16_ENCODER if ac or self.encoder_dtype == torch.bfloat16 else 0)
+        if (bf & ops.FLAG_BF16_MIXER) and self.S == 8 and self.mixer_stream_dtype in (None, torch.bfloat16):
+            bf |= ops.FLAG_BF16_STREAM
         if bf and self.matmul == "split" and not self._warned_precedence:
             # a bf16 request (autocast or mixer_dtype / encoder_dtype) wins over matmul="split": say so once
             import warnings
             warnings.warn("pips_amd.Pips: bf16 operands requested (autocast or *_dtype = bfloat16): matmul='split' is "
                           "ignored for those stages", stacklevel=3)
             self._warned_precedence = True
-        return bf if bf or self.matmul == "exact" else 16                 # PIPS_FLAG_SPLIT_BF16
+        return bf if bf or self.matmul == "exact" else ops.FLAG_SPLIT_BF16
 
     def _workspace(self, lib, dims, device):
         """Scratch of one forward: one buffer per (device, stream), replaced when the problem size changes."""
@@ -241,7 +242,7 @@ class Pips(nn.Module):
                 ce_ws = torch.empty(lib.pips_score_map_workspace_bytes(B, S, H8, W8) // 4, dtype=f32, device=dev)
             rc = lib.pips_forward_ce(_lib.ptr(arena), _lib.ptr(rgbs_c), _lib.ptr(xys_c), _lib.ptr(ci), _lib.ptr(fi),
                                      _lib.ptr(times), B, S, H, W, N, int(self.stride), int(iters),
-                                     self._flags() | (8 if u8 else 0),
+                                     self._flags() | (ops.FLAG_RGB_U8 if u8 else 0),
                                      _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs), _lib.ptr(vis_e), _lib.ptr(ffeat),
                                      _lib.ptr(ce_tgt), _lib.ptr(ce_terms), _lib.ptr(ce_ws),
                                      0 if ce_ws is None else ce_ws.numel() * 4,
@@ -299,8 +300,8 @@ class Pips(nn.Module):
             arena = self._aux(dev)[0]
             frames = (rgbs.contiguous() if rgbs.dtype == torch.uint8 else rgbs.contiguous().to(torch.float32))
             frames = frames.reshape(F, 3, H, W)
-            eb = bool(self._flags() & 4)
-            sp = bool(self._flags() & 16)
+            eb = bool(self._flags() & ops.FLAG_BF16_ENCODER)
+            sp = bool(self._flags() & ops.FLAG_SPLIT_BF16)
             if F <= frames_per_pass:
                 pyr = ops.encoder_fwd(arena, frames, st, bf16=eb, split=sp)
             else:
@@ -312,8 +313,7 @@ class Pips(nn.Module):
                     for d, p in zip(dst, ops.pyramid_levels(part, f1 - f0, H, W, st)):
                         d[f0:f1].copy_(p)
                 if eb:          # the parts' mirrors were laid out for their own frame counts: rewrite the whole one
-                    _lib.check(lib.pips_pyramid_mirror(_lib.ptr(pyr), F, H, W, st, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                               "pips_pyramid_mirror")
+                    ops.pyramid_mirror(pyr, F, H, W, st)
         return FeatureCache(pyr, B, T, H, W, st, bf16_maps=eb and not sp)
 
     def _append(self, rgbs, frames_per_pass, cache):
@@ -325,8 +325,8 @@ class Pips(nn.Module):
         step = max(1, min(int(frames_per_pass), cache.slots))
         with torch.cuda.device(dev):
             arena = self._aux(dev)[0]
-            eb = bool(self._flags() & 4)
-            sp = bool(self._flags() & 16)
+            eb = bool(self._flags() & ops.FLAG_BF16_ENCODER)
+            sp = bool(self._flags() & ops.FLAG_SPLIT_BF16)
             for f0 in range(0, T, step):
                 f1 = min(T, f0 + step)
                 part = rgbs[0, f0:f1].to(dev)
@@ -368,8 +368,8 @@ class Pips(nn.Module):
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
             fl = self._flags()
-            if cache.bf16_maps and (fl & 2) and not (fl & 16):
-                fl |= 32        # PIPS_FLAG_BF16_MAPS: bf16 mixer on maps of the bf16 encoder -> the gather reads their bf16 mirror
+            if cache.bf16_maps and (fl & ops.FLAG_BF16_MIXER) and not (fl & ops.FLAG_SPLIT_BF16):
+                fl |= ops.FLAG_BF16_MAPS        # bf16 mixer on maps of the bf16 encoder -> the gather reads their bf16 mirror
             nb = lib.pips_track_workspace_bytes_s(B, N, S)
             # ONE tracker workspace per (device, stream), grown on demand: chained tracking calls this with
             # a different (shrinking) N at every hop

@@ -60,6 +60,42 @@ def test_library_exports_every_declared_symbol():
     assert lib.pips_pyramid_floats(8, 368, 496, 8) >= 8 * 128 * (46 * 62 + 23 * 31 + 11 * 15 + 5 * 7)
 
 
+def test_binding_table_matches_every_prototype():
+    """Each SIGNATURES row against its prototype in include/pips_hip.h: the number of arguments, the kind of each one
+    (pointer / int / size_t / float) and the kind of the return value.  The names alone (the test above) would let a row
+    that dropped or swapped an argument through, and ctypes would then marshal a corrupted call."""
+    import ctypes as C
+    from pips_amd import _lib
+
+    def c_kind(decl):
+        if "*" in decl:
+            return "pointer"
+        kinds = [t for t in decl.split() if t in ("int", "size_t", "float")]
+        assert len(kinds) == 1, f"cannot classify {decl!r}"
+        return kinds[0]
+
+    def ctypes_kind(t):
+        if t in (C.c_void_p, C.c_char_p) or isinstance(t, type(C.POINTER(C.c_int))):
+            return "pointer"
+        return {C.c_int: "int", C.c_size_t: "size_t", C.c_float: "float"}[t]
+
+    hdr = open(os.path.join(ROOT, "include", "pips_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = "\n".join(l for l in hdr.splitlines() if not l.lstrip().startswith("#"))
+    protos = re.findall(r"([\w\s\*]+?)\b(pips_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)
+    assert {name for _, name, _ in protos} == set(_lib.SIGNATURES) and len(protos) == len(_lib.SIGNATURES)
+    for ret, name, params in protos:
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        res, args = _lib.SIGNATURES[name]
+        assert ctypes_kind(res) == c_kind(ret), f"{name}: returns {ret.strip()!r}"
+        assert len(args) == len(params), f"{name}: {len(params)} parameters declared, {len(args)} bound"
+        for i, (a, p) in enumerate(zip(args, params)):
+            assert ctypes_kind(a) == c_kind(p), f"{name}: argument {i} is {p!r}"
+    # the check has teeth: a 24-argument row with one c_int dropped, or an int bound as a pointer, is caught
+    assert ctypes_kind(C.POINTER(C.c_float)) == "pointer" and c_kind("const void* const* params_host") == "pointer"
+    assert c_kind("size_t workspace_bytes") == "size_t" != ctypes_kind(C.c_int)
+
+
 def test_no_cpu_fallback():
     from pips_amd import Pips, PipsHipError
     m = Pips()

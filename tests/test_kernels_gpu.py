@@ -818,7 +818,10 @@ def test_resize_frames_matches_interpolate(src_hw, dst_hw, u8):
 
 def test_fixed_window_entry_points_equal_the_general_ones(weights_raw):
     """The S = 8 / fixed-mode entry points are thin forms of the general ones: pips_repack_weights(_ex) = pips_repack_weights_s(8),
-    pips_encoder_fwd / _bf16 = pips_encoder_fwd_ex(flags), pips_track_ce = pips_track_s(S = 8) -- bit-identical results."""
+    pips_encoder_fwd / _bf16 = pips_encoder_fwd_ex(flags), pips_track_ce = pips_track_s(S = 8) -- bit-identical results.  So are the forms the Python package reaches only through their
+    general ones: pips_track (= _win without win_dir = _ring with R = T), pips_mixer_input_build (= _ex = _win = _ring),
+    pips_mixer_input_build_tiled / _tiled_timed (= _tiled_ex), pips_mixer_fwd / _bf16 / _x3 (= pips_mixer_fwd_s(8, flags)) and
+    pips_mixer_fwd_timed (= _timed_ex(0))."""
     import ctypes as C
     from pips_amd import _lib, ops
     from pips_amd.weights import param_table
@@ -866,6 +869,72 @@ def test_fixed_window_entry_points_equal_the_general_ones(weights_raw):
         outs.append((trajs, vis, ff))
     for x, y in zip(*outs):
         assert torch.equal(x, y)
+    # ---- the thin forms pips_amd itself no longer calls: each once through the binding, against its general form
+    H8, W8 = H // 8, W // 8
+    FL_BF16, FL_SPLIT = 2, 16                                                 # PIPS_FLAG_BF16_MIXER, PIPS_FLAG_SPLIT_BF16
+    # tracker: pips_track = pips_track_win(win_dir = NULL) = pips_track_ring(R = T)
+    outs = []
+    for which in ("track", "win", "ring"):
+        wst = torch.empty(nbt // 4, device=dev)
+        trajs = torch.empty(3, B, 8, N, 2, device=dev); vis = torch.empty(B, 8, N, device=dev); ff = torch.empty(B, N, 128, device=dev)
+        pre = [_lib.ptr(a0), _lib.ptr(p2), B, 8] + ([8] if which == "ring" else []) + [H8, W8, _lib.ptr(xys), None, None, None]
+        mid = [_lib.ptr(times), N, 8, 2, 0]                                   # times, N, stride, iters, flags
+        tail = [_lib.ptr(wst), nbt, _lib.ptr(trajs), _lib.ptr(vis), _lib.ptr(ff), st()]
+        if which == "track":
+            rc = lib.pips_track(*pre, *mid, *tail)
+        else:
+            rc = getattr(lib, "pips_track_" + which)(*pre, None, *mid, 8, *tail)      # + win_dir = NULL ... S = 8
+        _lib.check(rc, "pips_track_" + which)
+        torch.cuda.synchronize()
+        outs.append((trajs, vis, ff))
+    for o in outs[1:]:
+        for x, y in zip(outs[0], o):
+            assert torch.equal(x, y) and bool(torch.isfinite(x).all())
+    # gather: pips_mixer_input_build = _ex = _win(T = S) = _ring(R = T); _tiled = _tiled_timed = _tiled_ex
+    Ng = 77
+    Mg = B * Ng * 8
+    gg = torch.Generator().manual_seed(6)
+    ffe = torch.randn(Mg, 128, generator=gg).to(dev)
+    co = (torch.rand(Mg, 2, generator=gg) * torch.tensor([W8 + 4.0, H8 + 4.0]) - 2.0).to(dev)
+    gat = [_lib.ptr(p2), B, 8, H8, W8, _lib.ptr(ffe), _lib.ptr(co), _lib.ptr(times), Ng]
+    nbs = lib.pips_gather_scratch_bytes(B, Ng, H8, W8)
+    scratch = torch.empty(nbs, dtype=torch.uint8, device=dev)
+    ms3 = (C.c_float * 3)()
+
+    def gather(name, *rest):
+        X = torch.zeros(Mg, 544, device=dev)
+        args = list(gat)
+        if name == "pips_mixer_input_build_ring":
+            args.insert(3, 8)                                                 # R, behind T
+        _lib.check(getattr(lib, name)(*args, *[_lib.ptr(X) if r is Ellipsis else r for r in rest]), name)
+        torch.cuda.synchronize()
+        return X
+    Xd = gather("pips_mixer_input_build", ..., st())
+    assert bool(torch.isfinite(Xd).all()) and float(Xd[:, 128:324].abs().max()) > 0
+    assert torch.equal(Xd, gather("pips_mixer_input_build_ex", None, 0, ..., st()))
+    assert torch.equal(Xd, gather("pips_mixer_input_build_win", None, None, 0, 8, ..., st()))
+    assert torch.equal(Xd, gather("pips_mixer_input_build_ring", None, None, 0, 8, ..., st()))
+    Xt = gather("pips_mixer_input_build_tiled_ex", 0, ..., _lib.ptr(scratch), nbs, st(), None)
+    assert bool(torch.isfinite(Xt).all()) and float(Xt[:, 128:324].abs().max()) > 0
+    assert torch.equal(Xt, gather("pips_mixer_input_build_tiled", ..., _lib.ptr(scratch), nbs, st()))
+    assert torch.equal(Xt, gather("pips_mixer_input_build_tiled_timed", ..., _lib.ptr(scratch), nbs, st(), ms3))
+    assert all(ms3[i] >= 0 for i in range(3))
+    # mixer on those rows: pips_mixer_fwd / _bf16 / _x3 = pips_mixer_fwd_s(S = 8, flags); pips_mixer_fwd_timed = _timed_ex(flags = 0)
+    nbm = lib.pips_mixer_workspace_bytes(Mg)
+    ms5 = (C.c_float * 5)()
+
+    def mixer(name, before=(), after=()):
+        d = torch.zeros(Mg // 8, 1040, device=dev)
+        wsm = torch.empty(nbm // 4, device=dev)
+        _lib.check(getattr(lib, name)(_lib.ptr(a0), _lib.ptr(Xd), Mg, *before, _lib.ptr(d), _lib.ptr(wsm), nbm, st(), *after), name)
+        torch.cuda.synchronize()
+        return d
+    for name, fl in (("pips_mixer_fwd", 0), ("pips_mixer_fwd_bf16", FL_BF16), ("pips_mixer_fwd_x3", FL_SPLIT)):
+        d1, d2 = mixer(name), mixer("pips_mixer_fwd_s", before=(8, fl))
+        assert torch.equal(d1, d2) and bool(torch.isfinite(d1).all()) and float(d1.abs().max()) > 0
+    d0 = mixer("pips_mixer_fwd")
+    assert torch.equal(mixer("pips_mixer_fwd_timed", after=(ms5,)), mixer("pips_mixer_fwd_timed_ex", before=(0,), after=(ms5,)))
+    assert torch.equal(mixer("pips_mixer_fwd_timed", after=(ms5,)), d0)
 
 
 def test_gather_mfma_batches():
