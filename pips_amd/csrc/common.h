@@ -99,6 +99,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // half step did).  Register dependences on outstanding loads are still tracked by the compiler's own s_waitcnt insertion.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Scalar operands ("s") of the generated assembly statements (*_asm.inc): the compiler must hold the value in an SGPR, which it
+// does for what it knows to be wave-uniform -- readfirstlane says so.  A pointer goes in as its two halves (buffer descriptor words).
+__device__ __forceinline__ unsigned asm_sgpr(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+#define ASM_PTR_LO(ptr) asm_sgpr((unsigned)(unsigned long long)reinterpret_cast<uintptr_t>(ptr))
+#define ASM_PTR_HI(ptr) asm_sgpr((unsigned)((unsigned long long)reinterpret_cast<uintptr_t>(ptr) >> 32))
+
 // ---------------------------------------------------------------- bf16 activations (bf16 encoder mode)
 // two floats -> one dword of two bf16 (hardware round-to-nearest-even, v_cvt_pk_bf16_f32); lo in bits 0-15
 __device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {

@@ -30,10 +30,6 @@ constexpr int T4C_C = 96, T4C_PIX = 256, T4C_ROWB = 256;                   // ch
 constexpr int T4C_LDS_A = T4C_PIX * T4C_ROWB, T4C_LDS_W = T4C_C * T4C_ROWB;   // 65 536 + 24 576
 constexpr int T4C_LDS = T4C_LDS_A + T4C_LDS_W;
 
-__device__ __forceinline__ unsigned t4c_sgpr(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-#define T4C_LO(ptr) t4c_sgpr((unsigned)(unsigned long long)reinterpret_cast<uintptr_t>(ptr))
-#define T4C_HI(ptr) t4c_sgpr((unsigned)((unsigned long long)reinterpret_cast<uintptr_t>(ptr) >> 32))
-
 // grid = frames x bpf blocks; block (f, b) walks tiles b, b + bpf, ... of frame f
 __global__ __launch_bounds__(256) void conv3x3_c96_t4_kernel(const unsigned short* __restrict__ in, const unsigned short* __restrict__ wgt,
                                                              const float* __restrict__ bias, unsigned short* __restrict__ out, int M,
@@ -83,11 +79,11 @@ __global__ __launch_bounds__(256) void conv3x3_c96_t4_kernel(const unsigned shor
     asm volatile(PIPS_T4C_TEXT
                  :
                  : [rA0] "v"(rA[0]), [rA1] "v"(rA[1]), [rA2] "v"(rA[2]), [rW0] "v"(rW[0]), [rW1] "v"(rW[1]), [rW2] "v"(rW[2]),
-                   [tab] "v"(tabaddr), [voC] "v"(voC), [voB] "v"(voB), [alo] "s"(T4C_LO(Ab)), [ahi] "s"(T4C_HI(Ab)), [wlo] "s"(T4C_LO(wgt)),
-                   [whi] "s"(T4C_HI(wgt)), [clo] "s"(T4C_LO(Cb)), [chi] "s"(T4C_HI(Cb)), [blo] "s"(T4C_LO(bias)), [bhi] "s"(T4C_HI(bias)),
-                   [nrec] "s"(t4c_sgpr(nrec)), [p0] "s"(t4c_sgpr(p0)), [pstep] "s"(t4c_sgpr(pstep)), [plast] "s"(t4c_sgpr(plast)),
-                   [ntile] "s"(t4c_sgpr((unsigned)ntile)), [imgW] "s"(t4c_sgpr((unsigned)Wimg)), [wm1] "s"(t4c_sgpr((unsigned)(Wimg - 1))),
-                   [invW] "s"(t4c_sgpr(invW))
+                   [tab] "v"(tabaddr), [voC] "v"(voC), [voB] "v"(voB), [alo] "s"(ASM_PTR_LO(Ab)), [ahi] "s"(ASM_PTR_HI(Ab)),
+                   [wlo] "s"(ASM_PTR_LO(wgt)), [whi] "s"(ASM_PTR_HI(wgt)), [clo] "s"(ASM_PTR_LO(Cb)), [chi] "s"(ASM_PTR_HI(Cb)),
+                   [blo] "s"(ASM_PTR_LO(bias)), [bhi] "s"(ASM_PTR_HI(bias)), [nrec] "s"(asm_sgpr(nrec)), [p0] "s"(asm_sgpr(p0)),
+                   [pstep] "s"(asm_sgpr(pstep)), [plast] "s"(asm_sgpr(plast)), [ntile] "s"(asm_sgpr((unsigned)ntile)),
+                   [imgW] "s"(asm_sgpr((unsigned)Wimg)), [wm1] "s"(asm_sgpr((unsigned)(Wimg - 1))), [invW] "s"(asm_sgpr(invW))
                  : PIPS_T4C_CLOBBER);
 }
 

@@ -21,10 +21,6 @@ namespace pips {
 
 constexpr int CF4_ROW = 144;                                  // LDS row: 32 channels + 16 bytes
 
-__device__ __forceinline__ unsigned cf4_sgpr(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-#define CF4_LO(ptr) cf4_sgpr((unsigned)(unsigned long long)reinterpret_cast<uintptr_t>(ptr))
-#define CF4_HI(ptr) cf4_sgpr((unsigned)((unsigned long long)reinterpret_cast<uintptr_t>(ptr) >> 32))
-
 struct ConvT4Args {
     const float* in; const float* wgt; const float* bias; float* out; float* stats;
     int M, Wimg, bpf, tiles, parts; unsigned invW;
@@ -81,15 +77,15 @@ __global__ __launch_bounds__(256) void conv3x3_f32_t4_kernel(ConvT4Args p) {
     const unsigned p0 = (unsigned)b * PX, pstep = (unsigned)p.bpf * PX, plast = (unsigned)(p.tiles - 1) * PX;
     const unsigned sbytes = 64u * C::COUT / PX;
 #define CF4_OPERANDS                                                                                                               \
-    : [rA0] "v"(rA0), [rA1] "v"(rA1), [rA2] "v"(rA2), [rW0] "v"(rW0), [rW1] "v"(rW1), [rW2] "v"(rW2), [wb0] "v"(wb0),            \
-      [wb1] "v"(wb1), [wb2] "v"(wb2), [voA] "v"(voA), [voW] "v"(voW), [voB] "v"(voB), [voC] "v"(voC), [voS] "v"(voS),            \
-      [vlr] "v"(vlr), [vrow] "v"(vrow), [vl31x4] "v"(vl31x4), [vswap] "v"(vswap), [alo] "s"(CF4_LO(Ab)), [ahi] "s"(CF4_HI(Ab)),   \
-      [wlo] "s"(CF4_LO(Wb)), [whi] "s"(CF4_HI(Wb)), [clo] "s"(CF4_LO(Cb)), [chi] "s"(CF4_HI(Cb)), [blo] "s"(CF4_LO(p.bias)),      \
-      [bhi] "s"(CF4_HI(p.bias)), [slo] "s"(CF4_LO(Sb)), [shi] "s"(CF4_HI(Sb)), [nrecA] "s"(cf4_sgpr(nrecA)),                      \
-      [nrecC] "s"(cf4_sgpr(nrecC)), [nrecS] "s"(cf4_sgpr(nrecS)), [p0] "s"(cf4_sgpr(p0)), [pstep] "s"(cf4_sgpr(pstep)),            \
-      [plast] "s"(cf4_sgpr(plast)), [ntile] "s"(cf4_sgpr((unsigned)ntile)), [imgW] "s"(cf4_sgpr((unsigned)p.Wimg)),               \
-      [wm1] "s"(cf4_sgpr((unsigned)(p.Wimg - 1))), [invW] "s"(cf4_sgpr(p.invW)), [npix] "s"(cf4_sgpr((unsigned)p.M)),             \
-      [sbytes] "s"(cf4_sgpr(sbytes))
+    : [rA0] "v"(rA0), [rA1] "v"(rA1), [rA2] "v"(rA2), [rW0] "v"(rW0), [rW1] "v"(rW1), [rW2] "v"(rW2), [wb0] "v"(wb0),              \
+      [wb1] "v"(wb1), [wb2] "v"(wb2), [voA] "v"(voA), [voW] "v"(voW), [voB] "v"(voB), [voC] "v"(voC), [voS] "v"(voS),              \
+      [vlr] "v"(vlr), [vrow] "v"(vrow), [vl31x4] "v"(vl31x4), [vswap] "v"(vswap), [alo] "s"(ASM_PTR_LO(Ab)),                       \
+      [ahi] "s"(ASM_PTR_HI(Ab)), [wlo] "s"(ASM_PTR_LO(Wb)), [whi] "s"(ASM_PTR_HI(Wb)), [clo] "s"(ASM_PTR_LO(Cb)),                  \
+      [chi] "s"(ASM_PTR_HI(Cb)), [blo] "s"(ASM_PTR_LO(p.bias)), [bhi] "s"(ASM_PTR_HI(p.bias)), [slo] "s"(ASM_PTR_LO(Sb)),          \
+      [shi] "s"(ASM_PTR_HI(Sb)), [nrecA] "s"(asm_sgpr(nrecA)), [nrecC] "s"(asm_sgpr(nrecC)), [nrecS] "s"(asm_sgpr(nrecS)),         \
+      [p0] "s"(asm_sgpr(p0)), [pstep] "s"(asm_sgpr(pstep)), [plast] "s"(asm_sgpr(plast)), [ntile] "s"(asm_sgpr((unsigned)ntile)),  \
+      [imgW] "s"(asm_sgpr((unsigned)p.Wimg)), [wm1] "s"(asm_sgpr((unsigned)(p.Wimg - 1))), [invW] "s"(asm_sgpr(p.invW)),           \
+      [npix] "s"(asm_sgpr((unsigned)p.M)), [sbytes] "s"(asm_sgpr(sbytes))
     if (CFG == 0)      asm volatile(PIPS_CF32T4_C64_TEXT : CF4_OPERANDS : PIPS_CF32T4_CLOBBER);
     else if (CFG == 1) asm volatile(PIPS_CF32T4_C96_TEXT : CF4_OPERANDS : PIPS_CF32T4_CLOBBER);
     else               asm volatile(PIPS_CF32T4_C416_TEXT : CF4_OPERANDS : PIPS_CF32T4_CLOBBER);

@@ -35,10 +35,6 @@ namespace pips {
 constexpr int T4_BM = 128, T4_BN = 256, T4_BK = 64;
 constexpr int T4_LDS = (T4_BM + T4_BN) * T4_BK * 2;          // 49 152 bytes: one buffer, [A rows 0..127 | W rows 0..255] x 128 B
 
-__device__ __forceinline__ unsigned t4_sgpr(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-#define T4_LO(ptr) t4_sgpr((unsigned)(unsigned long long)reinterpret_cast<uintptr_t>(ptr))
-#define T4_HI(ptr) t4_sgpr((unsigned)((unsigned long long)reinterpret_cast<uintptr_t>(ptr) >> 32))
-
 #ifdef PIPS_T4_CLOCK
 // tools/t4_clock.py (variant build): per wave of the LAST launch of either kernel, shader clocks (s_memtime) and 100 MHz ticks (s_memrealtime)
 // around the generated statement -- the clock the kernel actually ran at, and a wave's share of the launch
@@ -102,10 +98,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_res_kernel(GemmArgs p, int t
     const unsigned kt = (unsigned)(p.K / T4_BK);
 #define T4_OPERANDS \
                  : [rA0] "v"(rA0), [rW0] "v"(rW0), [rA1] "v"(rA1), [rW1] "v"(rW1), [wA] "v"(wA), [wW] "v"(wW), [voA] "v"(voA), \
-                   [voW] "v"(voW), [voR] "v"(voR), [voC] "v"(voC), [voB] "v"(voB), [alo] "s"(T4_LO(Ab)), [ahi] "s"(T4_HI(Ab)), \
-                   [wlo] "s"(T4_LO(Wb)), [whi] "s"(T4_HI(Wb)), [rlo] "s"(T4_LO(Rb)), [rhi] "s"(T4_HI(Rb)), [clo] "s"(T4_LO(Cb)), \
-                   [chi] "s"(T4_HI(Cb)), [blo] "s"(T4_LO(Bb)), [bhi] "s"(T4_HI(Bb)), [passA] "s"(t4_sgpr(passA)), \
-                   [passW] "s"(t4_sgpr(passW)), [rstep] "s"(t4_sgpr(rstep)), [cstep] "s"(t4_sgpr(cstep)), [kt] "s"(t4_sgpr(kt))
+                   [voW] "v"(voW), [voR] "v"(voR), [voC] "v"(voC), [voB] "v"(voB), [alo] "s"(ASM_PTR_LO(Ab)), \
+                   [ahi] "s"(ASM_PTR_HI(Ab)), [wlo] "s"(ASM_PTR_LO(Wb)), [whi] "s"(ASM_PTR_HI(Wb)), [rlo] "s"(ASM_PTR_LO(Rb)), \
+                   [rhi] "s"(ASM_PTR_HI(Rb)), [clo] "s"(ASM_PTR_LO(Cb)), [chi] "s"(ASM_PTR_HI(Cb)), [blo] "s"(ASM_PTR_LO(Bb)), \
+                   [bhi] "s"(ASM_PTR_HI(Bb)), [passA] "s"(asm_sgpr(passA)), [passW] "s"(asm_sgpr(passW)), \
+                   [rstep] "s"(asm_sgpr(rstep)), [cstep] "s"(asm_sgpr(cstep)), [kt] "s"(asm_sgpr(kt))
     PIPS_T4_CLOCK_BEGIN
     if (SB) asm volatile(PIPS_T4B_TEXT : T4_OPERANDS : PIPS_T4_CLOBBER);
     else asm volatile(PIPS_T4_TEXT : T4_OPERANDS : PIPS_T4_CLOBBER);
@@ -155,10 +152,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_gelu_kernel(GemmArgs p, int 
     asm volatile(PIPS_T4UP_TEXT
                  :
                  : [rA0] "v"(rA0), [rW0] "v"(rW0), [rA1] "v"(rA1), [rW1] "v"(rW1), [wA] "v"(wA), [wW] "v"(wW), [voA] "v"(voA),
-                   [voW] "v"(voW), [voC] "v"(voC), [voB] "v"(voB), [alo] "s"(T4_LO(Ab)), [ahi] "s"(T4_HI(Ab)), [wlo] "s"(T4_LO(Wb)),
-                   [whi] "s"(T4_HI(Wb)), [clo] "s"(T4_LO(Cb)), [chi] "s"(T4_HI(Cb)), [blo] "s"(T4_LO(Bb)), [bhi] "s"(T4_HI(Bb)),
-                   [passA] "s"(t4_sgpr(passA)), [passW] "s"(t4_sgpr(passW)), [cstep] "s"(t4_sgpr(cstep)), [tstepC] "s"(t4_sgpr(tstepC)),
-                   [tstepA] "s"(t4_sgpr(tstepA)), [ntile] "s"(t4_sgpr((unsigned)tpb))
+                   [voW] "v"(voW), [voC] "v"(voC), [voB] "v"(voB), [alo] "s"(ASM_PTR_LO(Ab)), [ahi] "s"(ASM_PTR_HI(Ab)),
+                   [wlo] "s"(ASM_PTR_LO(Wb)), [whi] "s"(ASM_PTR_HI(Wb)), [clo] "s"(ASM_PTR_LO(Cb)), [chi] "s"(ASM_PTR_HI(Cb)),
+                   [blo] "s"(ASM_PTR_LO(Bb)), [bhi] "s"(ASM_PTR_HI(Bb)), [passA] "s"(asm_sgpr(passA)), [passW] "s"(asm_sgpr(passW)),
+                   [cstep] "s"(asm_sgpr(cstep)), [tstepC] "s"(asm_sgpr(tstepC)), [tstepA] "s"(asm_sgpr(tstepA)),
+                   [ntile] "s"(asm_sgpr((unsigned)tpb))
                  : PIPS_T4UP_CLOBBER);
     PIPS_T4_CLOCK_END(0)
 }

@@ -30,17 +30,14 @@ constexpr int F4_LDS_U = 2 * 256 * F4_ROW;                   // 73 728 bytes: tw
 constexpr int F4_STAGE_D = 128 * F4_ROW;                     // a stage of shape D: [A rows 0..63 | W rows 0..63]
 constexpr int F4_LDS_D = 4 * F4_STAGE_D;                     // 73 728 bytes: four stages; the four partial tiles at the end use 64 KiB of it
 
-__device__ __forceinline__ unsigned f4_sgpr(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-#define F4_LO(ptr) f4_sgpr((unsigned)(unsigned long long)reinterpret_cast<uintptr_t>(ptr))
-#define F4_HI(ptr) f4_sgpr((unsigned)((unsigned long long)reinterpret_cast<uintptr_t>(ptr) >> 32))
-#define F4_OPERANDS                                                                                                              \
-    : [rA0] "v"(rA0), [rW0] "v"(rW0), [rA1] "v"(rA1), [rW1] "v"(rW1), [wA0] "v"(wA0), [wW0] "v"(wW0), [wA1] "v"(wA1),          \
-      [wW1] "v"(wW1), [voA] "v"(voA), [voW] "v"(voW), [voR] "v"(voR), [voC] "v"(voC), [voB] "v"(voB), [redW] "v"(redW),        \
-      [redR] "v"(redR), [alo] "s"(F4_LO(Ab)), [ahi] "s"(F4_HI(Ab)), [wlo] "s"(F4_LO(Wb)), [whi] "s"(F4_HI(Wb)),                 \
-      [rlo] "s"(F4_LO(Rb)), [rhi] "s"(F4_HI(Rb)), [clo] "s"(F4_LO(Cb)), [chi] "s"(F4_HI(Cb)), [blo] "s"(F4_LO(Bb)),             \
-      [bhi] "s"(F4_HI(Bb)), [passA] "s"(f4_sgpr(passA)), [passW] "s"(f4_sgpr(passW)), [rstep] "s"(f4_sgpr(rstep)),              \
-      [cstep] "s"(f4_sgpr(cstep)), [kt] "s"(f4_sgpr(kt)), [tstepA] "s"(f4_sgpr(tstepA)), [tstepC] "s"(f4_sgpr(tstepC)),         \
-      [tstepR] "s"(f4_sgpr(tstepR)), [ntile] "s"(f4_sgpr(ntile))
+#define F4_OPERANDS                                                                                                                 \
+    : [rA0] "v"(rA0), [rW0] "v"(rW0), [rA1] "v"(rA1), [rW1] "v"(rW1), [wA0] "v"(wA0), [wW0] "v"(wW0), [wA1] "v"(wA1),               \
+      [wW1] "v"(wW1), [voA] "v"(voA), [voW] "v"(voW), [voR] "v"(voR), [voC] "v"(voC), [voB] "v"(voB), [redW] "v"(redW),             \
+      [redR] "v"(redR), [alo] "s"(ASM_PTR_LO(Ab)), [ahi] "s"(ASM_PTR_HI(Ab)), [wlo] "s"(ASM_PTR_LO(Wb)), [whi] "s"(ASM_PTR_HI(Wb)), \
+      [rlo] "s"(ASM_PTR_LO(Rb)), [rhi] "s"(ASM_PTR_HI(Rb)), [clo] "s"(ASM_PTR_LO(Cb)), [chi] "s"(ASM_PTR_HI(Cb)),                   \
+      [blo] "s"(ASM_PTR_LO(Bb)), [bhi] "s"(ASM_PTR_HI(Bb)), [passA] "s"(asm_sgpr(passA)), [passW] "s"(asm_sgpr(passW)),             \
+      [rstep] "s"(asm_sgpr(rstep)), [cstep] "s"(asm_sgpr(cstep)), [kt] "s"(asm_sgpr(kt)), [tstepA] "s"(asm_sgpr(tstepA)),           \
+      [tstepC] "s"(asm_sgpr(tstepC)), [tstepR] "s"(asm_sgpr(tstepR)), [ntile] "s"(asm_sgpr(ntile))
 
 // Block -> (row unit, column tile).  Blocks go to the XCDs round robin (block & 7), every XCD has its own L2, and the operands
 // come out of the Infinity Cache: in the linear order (column tile fastest) the eight column tiles of the M = 2048 down-projection
@@ -172,9 +169,10 @@ __global__ __launch_bounds__(256) void gemm_f32_t4e_kernel(GemmArgs p, F4Grid gr
     asm volatile(PIPS_F32T4_E_RES_TEXT
                  :
                  : [rA0] "v"(rA0), [rW0] "v"(rW0), [vo0] "v"(vo0), [vo1] "v"(vo1), [voR] "v"(voR), [voC] "v"(voC), [voB] "v"(voB),
-                   [redW] "v"(redW), [redR] "v"(redR), [xlo] "s"(F4_LO(Xb)), [xhi] "s"(F4_HI(Xb)), [rlo] "s"(F4_LO(Rb)), [rhi] "s"(F4_HI(Rb)),
-                   [clo] "s"(F4_LO(Cb)), [chi] "s"(F4_HI(Cb)), [blo] "s"(F4_LO(Bb)), [bhi] "s"(F4_HI(Bb)), [pass2] "s"(f4_sgpr(pass2)),
-                   [ldsw] "s"(f4_sgpr(ldsw)), [kt] "s"(f4_sgpr(kt))
+                   [redW] "v"(redW), [redR] "v"(redR), [xlo] "s"(ASM_PTR_LO(Xb)), [xhi] "s"(ASM_PTR_HI(Xb)),
+                   [rlo] "s"(ASM_PTR_LO(Rb)), [rhi] "s"(ASM_PTR_HI(Rb)), [clo] "s"(ASM_PTR_LO(Cb)), [chi] "s"(ASM_PTR_HI(Cb)),
+                   [blo] "s"(ASM_PTR_LO(Bb)), [bhi] "s"(ASM_PTR_HI(Bb)), [pass2] "s"(asm_sgpr(pass2)), [ldsw] "s"(asm_sgpr(ldsw)),
+                   [kt] "s"(asm_sgpr(kt))
                  : PIPS_F32T4_CLOBBER);
 }
 

@@ -206,37 +206,28 @@ def test_packed_weights_follow_parameter_changes():
         ops.pack_weights = orig
 
 
+GENERATED_ASM = (("gen_gather_asm.py", "gather_item_asm.inc"), ("gen_gemm_bf16_t4.py", "gemm_bf16_t4_asm.inc"),
+                 ("gen_gemm_bf16_t4up.py", "gemm_bf16_t4up_asm.inc"), ("gen_conv_bf16_t4c.py", "conv_bf16_t4c_asm.inc"),
+                 ("gen_gemm_f32_t4.py", "gemm_f32_t4_asm.inc"), ("gen_conv_f32_t4.py", "conv_f32_t4_asm.inc"))
+
+
 def test_build_script_dependencies_exist_and_asm_is_current(tmp_path):
-    """The build script's dependency list names real files (a stale name makes every rebuild fail), and the committed
-    generated assembly is what tools/gen_gather_asm.py / tools/gen_gemm_bf16_t4.py / tools/gen_gemm_bf16_t4up.py emit today."""
+    """The build script's dependency list names real files (a stale name makes every rebuild fail), and every committed generated
+    assembly file is what its generator in tools/ emits today (in the default environment: the generators' tuning switches are
+    taken out of the child's)."""
     import subprocess, sys
     from pips_amd import _build
     for h in _build.headers():
         assert os.path.exists(h), h
-    out = tmp_path / "gather_item_asm.inc"
-    env = dict(os.environ, PIPS_GEN_OUT=str(out))
-    for k in ("PIPS_GEN_ABLATE", "PIPS_GEN_TRACE"):
+    env = dict(os.environ)
+    for k in ("PIPS_GEN_ABLATE", "PIPS_GEN_TRACE", "PIPS_GEN_STORE_POLICY", "PIPS_GEN_D4"):
         env.pop(k, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.check_call([sys.executable, os.path.join(root, "tools", "gen_gather_asm.py")], env=env, stdout=subprocess.DEVNULL)
-    assert out.read_text() == open(os.path.join(root, "pips_amd", "csrc", "gather_item_asm.inc")).read()
-    out3 = tmp_path / "gemm_bf16_t4_asm.inc"
-    env["PIPS_GEN_OUT"] = str(out3)
-    subprocess.check_call([sys.executable, os.path.join(root, "tools", "gen_gemm_bf16_t4.py")], env=env, stdout=subprocess.DEVNULL)
-    assert out3.read_text() == open(os.path.join(root, "pips_amd", "csrc", "gemm_bf16_t4_asm.inc")).read()
-    out4 = tmp_path / "gemm_bf16_t4up_asm.inc"
-    env["PIPS_GEN_OUT"] = str(out4)
-    subprocess.check_call([sys.executable, os.path.join(root, "tools", "gen_gemm_bf16_t4up.py")], env=env, stdout=subprocess.DEVNULL)
-    assert out4.read_text() == open(os.path.join(root, "pips_amd", "csrc", "gemm_bf16_t4up_asm.inc")).read()
-    out5 = tmp_path / "conv_bf16_t4c_asm.inc"
-    env["PIPS_GEN_OUT"] = str(out5)
-    subprocess.check_call([sys.executable, os.path.join(root, "tools", "gen_conv_bf16_t4c.py")], env=env, stdout=subprocess.DEVNULL)
-    assert out5.read_text() == open(os.path.join(root, "pips_amd", "csrc", "conv_bf16_t4c_asm.inc")).read()
-    for gen, inc in (("gen_gemm_f32_t4.py", "gemm_f32_t4_asm.inc"), ("gen_conv_f32_t4.py", "conv_f32_t4_asm.inc")):
-        out6 = tmp_path / inc
-        env["PIPS_GEN_OUT"] = str(out6)
+    for gen, inc in GENERATED_ASM:
+        out = tmp_path / inc
+        env["PIPS_GEN_OUT"] = str(out)
         subprocess.check_call([sys.executable, os.path.join(root, "tools", gen)], env=env, stdout=subprocess.DEVNULL)
-        assert out6.read_text() == open(os.path.join(root, "pips_amd", "csrc", inc)).read()
+        assert out.read_text() == open(os.path.join(root, "pips_amd", "csrc", inc)).read(), inc
 
 
 def _lint():
@@ -277,14 +268,26 @@ def test_hazard_table_matches_the_compilers_recognizer():
 
 def test_generators_take_their_wait_states_from_one_place():
     """The five pasted `s_nop 15; s_nop 15` pairs of rounds 4-5 are gone: every generator takes its guards from tools/asm_guards.py,
-    whose numbers are the lint's table."""
+    whose numbers are the lint's table.  The same for what counts the s_waitcnt: the issue model, the buffer descriptor, the GELU and
+    the float literal live in tools/asm_emit.py alone -- no generator, the parked ones of tools/experiments included, has a copy."""
     import glob
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     gens = sorted(glob.glob(os.path.join(root, "tools", "gen_*.py")))
     assert len(gens) == 6
+    assert [os.path.basename(g) for g in gens] == sorted(gen for gen, _ in GENERATED_ASM)
     for g in gens:
         src = open(g).read()
         assert "import asm_guards" in src and "s_nop 15" not in src, g
+    parked = sorted(glob.glob(os.path.join(root, "tools", "experiments", "gen_*.py")))
+    assert parked
+    for g in gens + parked:
+        src = open(g).read()
+        assert re.search(r"^(from asm_emit import|import asm_emit)\b", src, re.M), g
+        for copy in ("class Emit", "def descriptor", "def f32(", "def gelu4("):
+            assert copy not in src, (g, copy)
+    shared = open(os.path.join(root, "tools", "asm_emit.py")).read()
+    for one in ("class Emit", "def descriptor(", "def f32(", "def gelu4(", "def write_inc(", "def out_path("):
+        assert shared.count(one) == 1, one
 
 
 def test_profiles_readme_is_generated_from_the_files():

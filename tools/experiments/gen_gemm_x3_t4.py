@@ -30,10 +30,13 @@ Registers (all clobbered; v[216:255] stay with the compiler):
     s[84:97] loop state
 """
 import os
-import struct
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "gemm_x3_t4_asm.inc"))
+sys.path.insert(0, os.path.dirname(HERE))
+from asm_emit import Emit, descriptor, f32, gelu4, out_path, write_inc  # noqa: E402  (the issue model, shared by every generator)
+
+OUT = out_path("gemm_x3_t4_asm.inc", directory=HERE)
 
 LDROW = 80
 PLANE = 128 * LDROW                 # 10 240
@@ -50,57 +53,6 @@ COEF = [3.208326405e-07, -6.917509381e-06, 6.041429151e-05, -2.428356966e-04, -5
         -5.246259645e-02, -4.592153430e-01, -1.151104689e+00]
 TMAX = 5.65685425
 PRODUCTS = [(2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)]      # (A plane, W plane): l h, h l, m m, m h, h m, h h
-
-
-def f32(x):
-    return "0x%08x" % struct.unpack("<I", struct.pack("<f", x))[0]
-
-
-class Emit:
-    """Instruction list + in-order issue model of the two counters (see gen_gemm_bf16_t4.py)."""
-
-    def __init__(self):
-        self.lines, self.lgkm, self.vm = [], [], []
-
-    def raw(self, s):
-        self.lines.append(s)
-
-    def lds(self, s, tag):
-        self.lines.append(s)
-        self.lgkm.append(tag)
-
-    def vmem(self, s, tag):
-        self.lines.append(s)
-        self.vm.append(tag)
-
-    def need_lds(self, tags):
-        idx = [k for k, t in enumerate(self.lgkm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.lgkm) - 1 - max(idx), 15)
-        self.lines.append("s_waitcnt lgkmcnt(%d)" % left)
-        self.lgkm = self.lgkm[len(self.lgkm) - left:] if left else []
-
-    def need_vm(self, tags):
-        idx = [k for k, t in enumerate(self.vm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.vm) - 1 - max(idx), 63)
-        self.lines.append("s_waitcnt vmcnt(%d)" % left)
-        self.vm = self.vm[len(self.vm) - left:] if left else []
-
-    def need_loads(self):
-        self.need_vm({t for t in self.vm if t[0] != "out"})
-
-    def barrier(self):
-        if self.lgkm:
-            self.lines.append("s_waitcnt lgkmcnt(0)")
-            self.lgkm = []
-        self.lines.append("s_barrier")
-
-    def drain(self):
-        self.lines.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        self.lgkm, self.vm = [], []
 
 
 def acc(i, j):
@@ -125,13 +77,6 @@ def mfma(e, pa, pw, hset, i, j, zero):
     a = acc(i, j)
     e.raw("v_mfma_f32_32x32x16_bf16 a[%d:%d], v[%d:%d], v[%d:%d], %s" %
           (a, a + 15, rw, rw + 3, ra, ra + 3, "0" if zero else "a[%d:%d]" % (a, a + 15)))
-
-
-def descriptor(e, base, lo, hi):
-    e.raw("s_mov_b32 s%d, %s" % (base, lo))
-    e.raw("s_and_b32 s%d, %s, 0xffff" % (base + 1, hi))
-    e.raw("s_mov_b32 s%d, 0x7fffffff" % (base + 2))
-    e.raw("s_mov_b32 s%d, 0x00020000" % (base + 3))
 
 
 def advance_a(e):
@@ -263,33 +208,6 @@ def kstep(e, t, ks, first, extra=()):
                 n += 1
 
 
-def gelu4(e, X, T, Q):
-    """exact GELU of the 8 values v[X:X+7] in place: gelu_exact2's arithmetic (common.h), four pairs side by side"""
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_min_f32_e64 v%d, |v%d|, s%d" % (T + 2 * p + h, X + 2 * p + h, S_GC + 18))
-    for p in range(4):
-        e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], s[%d:%d], v[%d:%d] op_sel_hi:[1,0,1]" %
-              (Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1, S_GC, S_GC + 1, VC, VC + 1))
-    for c in range(2, len(COEF)):
-        for p in range(4):
-            e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], s[%d:%d] op_sel_hi:[1,1,0]" %
-                  (Q + 2 * p, Q + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1, S_GC + 2 * c, S_GC + 2 * c + 1))
-    for p in range(4):
-        e.raw("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (Q + 2 * p, Q + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1))
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_exp_f32_e32 v%d, v%d" % (Q + 2 * p + h, Q + 2 * p + h))
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_max_f32_e32 v%d, 0, v%d" % (X + 2 * p + h, X + 2 * p + h))
-    for p in range(4):
-        e.raw("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (T + 2 * p, T + 2 * p + 1, T + 2 * p, T + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1))
-    for p in range(4):
-        e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], -0.5, v[%d:%d] op_sel_hi:[1,0,1]" %
-              (X + 2 * p, X + 2 * p + 1, T + 2 * p, T + 2 * p + 1, X + 2 * p, X + 2 * p + 1))
-
-
 def residual_loads():
     """the tile's residual quads -> a[64:127] (issued in the slots of the tile's last K step)"""
     ops = []
@@ -324,7 +242,7 @@ def epilogue(e, epi):
                 for p in range(4):
                     e.raw("v_pk_add_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (X + 2 * p, X + 2 * p + 1, X + 2 * p, X + 2 * p + 1, T + 2 * p, T + 2 * p + 1))
                 if epi == "gelu":
-                    gelu4(e, X, T, Q)
+                    gelu4(e, X, T, Q, S_GC, VC, len(COEF))
                 else:
                     for h in range(2):
                         q = 2 * qq + h
@@ -455,19 +373,8 @@ def body(epi):
 
 
 def main():
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % i for i in range(160)] + ['"v%d"' % i for i in range(NV)] + \
-           ['"s%d"' % i for i in range(40, 94)]
-    with open(OUT, "w") as f:
-        f.write("// generated by tools/gen_gemm_x3_t4.py -- do not edit\n")
-        for name, epi in (("U_GELU", "gelu"), ("U_RES", "res")):
-            lines = body(epi)
-            f.write("#define PIPS_X3T4_%s_TEXT \\\n" % name)
-            for ln in lines:
-                f.write('    "%s\\n\\t" \\\n' % ln)
-            f.write('    ""\n\n')
-            print("PIPS_X3T4_%s_TEXT: %d instructions, %d MFMAs" % (name, len(lines), sum("v_mfma" in ln for ln in lines)))
-        f.write("#define PIPS_X3T4_CLOBBER " + ", ".join(clob) + "\n")
-    print("wrote", OUT)
+    bodies = [("PIPS_X3T4_%s_TEXT" % name, body(epi)) for name, epi in (("U_GELU", "gelu"), ("U_RES", "res"))]
+    write_inc(OUT, "gen_gemm_x3_t4.py", bodies, "PIPS_X3T4_CLOBBER", 160, NV, range(40, 94))
 
 
 if __name__ == "__main__":

@@ -32,9 +32,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_guards as G  # noqa: E402  (wait-state guards: the numbers live in tools/asm_hazard_lint.py)
+from asm_emit import Emit, descriptor, out_path, write_inc  # noqa: E402  (the issue model, shared by every generator)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "..", "pips_amd", "csrc", "conv_bf16_t4c_asm.inc"))
+OUT = out_path("conv_bf16_t4c_asm.inc")
 
 NI, NJ, NKS, NTAP = 4, 6, 3, 9      # 16-pixel / 16-channel blocks of the wave tile, K steps (32 channels) per tap, taps
 FA = [0, 40]
@@ -48,50 +48,6 @@ S_TAP = 56                          # s[56:64]: ((kh - 1) W + (kw - 1)) * 192 of
 S_M0, S_TL, S_T, S_T2, S_NEXT, S_WOFF = 65, 66, 67, 68, 69, 70
 S_P, S_PNEXT = 76, 77               # first pixel of this / the next tile (S_M0 / S_NEXT: the same x 192 bytes)
 TAB = 46                            # per-thread table entries the kernel leaves in LDS: entry k of thread t at tab + 1024 k + 4 t
-
-
-class Emit:
-    """Instruction list + in-order issue model of the two counters (see gen_gemm_bf16_t4.py)."""
-
-    def __init__(self):
-        self.lines, self.lgkm, self.vm = [], [], []
-
-    def raw(self, s):
-        self.lines.append(s)
-
-    def lds(self, s, tag):
-        self.lines.append(s)
-        self.lgkm.append(tag)
-
-    def vmem(self, s, tag):
-        self.lines.append(s)
-        self.vm.append(tag)
-
-    def need_lds(self, tags):
-        idx = [k for k, t in enumerate(self.lgkm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.lgkm) - 1 - max(idx), 15)
-        self.lines.append("s_waitcnt lgkmcnt(%d)" % left)
-        self.lgkm = self.lgkm[len(self.lgkm) - left:] if left else []
-
-    def need_vm(self, tags):
-        idx = [k for k, t in enumerate(self.vm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.vm) - 1 - max(idx), 63)
-        self.lines.append("s_waitcnt vmcnt(%d)" % left)
-        self.vm = self.vm[len(self.vm) - left:] if left else []
-
-    def barrier(self):
-        if self.lgkm:
-            self.lines.append("s_waitcnt lgkmcnt(0)")
-            self.lgkm = []
-        self.lines.append("s_barrier")
-
-    def drain(self):
-        self.lines.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        self.lgkm, self.vm = [], []
 
 
 def acc(i, j):
@@ -144,13 +100,6 @@ def load_piece(e, s, kw):
         e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], 0 offen" % (reg, reg + 3, off, RS_A, RS_A + 3), ("st", s))
     else:
         e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen" % (reg, reg + 3, VOW + s - NPA, RS_W, RS_W + 3, S_WOFF), ("st", s))
-
-
-def descriptor(e, base, lo, hi, nrec):
-    e.raw("s_mov_b32 s%d, %s" % (base, lo))
-    e.raw("s_and_b32 s%d, %s, 0xffff" % (base + 1, hi))
-    e.raw("s_mov_b32 s%d, %s" % (base + 2, nrec))
-    e.raw("s_mov_b32 s%d, 0x00020000" % (base + 3))
 
 
 def request_offsets(e, tap, next_tile):
@@ -272,9 +221,9 @@ def tile(e, p0):
 def body():
     e = Emit()
     descriptor(e, RS_A, "%[alo]", "%[ahi]", "%[nrec]")
-    descriptor(e, RS_W, "%[wlo]", "%[whi]", "0x7fffffff")
+    descriptor(e, RS_W, "%[wlo]", "%[whi]")
     descriptor(e, RS_C, "%[clo]", "%[chi]", "%[nrec]")
-    descriptor(e, RS_B, "%[blo]", "%[bhi]", "0x7fffffff")
+    descriptor(e, RS_B, "%[blo]", "%[bhi]")
     order = [VOA + s for s in range(NPA)] + [LDA + s for s in range(NPA)] + [PIX + s for s in range(NPA)] + \
             [VOW + s for s in range(NPW)] + [LDW + s for s in range(NPW)]
     assert len(order) == TAB
@@ -332,18 +281,7 @@ def body():
 
 
 def main():
-    lines = body()
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % i for i in range(96)] + ['"v%d"' % i for i in range(218)] + \
-           ['"s%d"' % i for i in range(40, 78)]
-    with open(OUT, "w") as f:
-        f.write("// generated by tools/gen_conv_bf16_t4c.py -- do not edit\n")
-        f.write("#define PIPS_T4C_TEXT \\\n")
-        for ln in lines:
-            f.write('    "%s\\n\\t" \\\n' % ln)
-        f.write('    ""\n\n')
-        f.write("#define PIPS_T4C_CLOBBER " + ", ".join(clob) + "\n")
-    print("PIPS_T4C_TEXT: %d instructions, %d MFMAs" % (len(lines), sum("v_mfma" in ln for ln in lines)))
-    print("wrote", OUT)
+    write_inc(OUT, "gen_conv_bf16_t4c.py", [("PIPS_T4C_TEXT", body())], "PIPS_T4C_CLOBBER", 96, 218, range(40, 78))
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 """Emit pips_amd/csrc/conv_f32_t4_asm.inc: the bodies of the kernels of conv_f32_t4.hip, each ONE assembly statement -- the 3x3 /
 stride 1 / pad 1 convolutions of the fp32 encoder on channel-last maps as exact-fp32 implicit GEMMs (v_mfma_f32_32x32x2_f32,
 igemm_f32_kernel's arithmetic and K order: tap-major, 32 channels per stage) on four waves, one per SIMD, in the style of
-tools/gen_gemm_f32_t4.py (static schedule, counted waits) with the operand addressing of tools/gen_conv_bf16_t4c.py.
+tools/gen_gemm_f32_t4.py (static schedule, waits counted by tools/asm_emit.py) with the operand addressing of
+tools/gen_conv_bf16_t4c.py.
 
 A block tile is 128 NI pixels x 32 NJ channels: wave w owns pixels 32 NI w .. of it and all 32 NJ channels (NI x NJ MFMA blocks,
 16 NI NJ AccVGPRs).  With the pixels of a frame numbered row-major, tap (kh, kw) of output pixel p reads input pixel
@@ -30,9 +31,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_guards as G  # noqa: E402  (wait-state guards: the numbers live in tools/asm_hazard_lint.py)
+from asm_emit import Emit, descriptor, out_path, write_inc  # noqa: E402  (the issue model, shared by every generator)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "..", "pips_amd", "csrc", "conv_f32_t4_asm.inc"))
+OUT = out_path("conv_f32_t4_asm.inc")
 
 LDROW = 144
 NV = 216
@@ -77,53 +78,6 @@ class Cfg:
         return 16 * (i + self.ni * j)
 
 
-class Emit:
-    """Instruction list + in-order issue model of the two counters (see gen_gemm_bf16_t4.py)."""
-
-    def __init__(self):
-        self.lines, self.lgkm, self.vm = [], [], []
-
-    def raw(self, s):
-        self.lines.append(s)
-
-    def lds(self, s, tag):
-        self.lines.append(s)
-        self.lgkm.append(tag)
-
-    def vmem(self, s, tag):
-        self.lines.append(s)
-        self.vm.append(tag)
-
-    def need_lds(self, tags):
-        idx = [k for k, t in enumerate(self.lgkm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.lgkm) - 1 - max(idx), 15)
-        self.lines.append("s_waitcnt lgkmcnt(%d)" % left)
-        self.lgkm = self.lgkm[len(self.lgkm) - left:] if left else []
-
-    def need_vm(self, tags):
-        idx = [k for k, t in enumerate(self.vm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.vm) - 1 - max(idx), 63)
-        self.lines.append("s_waitcnt vmcnt(%d)" % left)
-        self.vm = self.vm[len(self.vm) - left:] if left else []
-
-    def need_loads(self):
-        self.need_vm({t for t in self.vm if t[0] != "out"})
-
-    def barrier(self):
-        if self.lgkm:
-            self.lines.append("s_waitcnt lgkmcnt(0)")
-            self.lgkm = []
-        self.lines.append("s_barrier")
-
-    def drain(self):
-        self.lines.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        self.lgkm, self.vm = [], []
-
-
 def frag_read(e, c, buf, fset, kk, which, idx):
     """fragment `idx` (A: pixel block i, W: channel block j) of the 8 K values kk of the stage in LDS buffer `buf`, into set `fset`"""
     reg = (c.fa if which == "a" else c.fw)[fset] + 4 * idx
@@ -162,13 +116,6 @@ def load_piece(e, c, ring, s, kw):
     else:
         e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen" % (reg, reg + 3, c.vow + s - c.npa, RS_W, RS_W + 3, S_WOFF),
                ("st", ring, s))
-
-
-def descriptor(e, base, lo, hi, nrec):
-    e.raw("s_mov_b32 s%d, %s" % (base, lo))
-    e.raw("s_and_b32 s%d, %s, 0xffff" % (base + 1, hi))
-    e.raw("s_mov_b32 s%d, %s" % (base + 2, nrec))
-    e.raw("s_mov_b32 s%d, 0x00020000" % (base + 3))
 
 
 def request_offsets(e, c, t):
@@ -330,9 +277,9 @@ def tile_advance(e, c):
 def body(c):
     e = Emit()
     descriptor(e, RS_A, "%[alo]", "%[ahi]", "%[nrecA]")
-    descriptor(e, RS_W, "%[wlo]", "%[whi]", "0x7fffffff")
+    descriptor(e, RS_W, "%[wlo]", "%[whi]")
     descriptor(e, RS_C, "%[clo]", "%[chi]", "%[nrecC]")
-    descriptor(e, RS_B, "%[blo]", "%[bhi]", "0x7fffffff")
+    descriptor(e, RS_B, "%[blo]", "%[bhi]")
     descriptor(e, RS_S, "%[slo]", "%[shi]", "%[nrecS]")
     e.raw("v_mov_b32 v%d, %%[voA]" % c.voa)
     for s in range(1, c.npa):
@@ -388,22 +335,9 @@ CONFIGS = [Cfg("C64", 64, 64, 2, 2), Cfg("C96", 96, 96, 1, 3), Cfg("C416", 416, 
 
 
 def main():
-    with open(OUT, "w") as f:
-        f.write("// generated by tools/gen_conv_f32_t4.py -- do not edit\n")
-        nacc = 0
-        for c in CONFIGS:
-            lines = body(c)
-            f.write("#define PIPS_CF32T4_%s_TEXT \\\n" % c.name)
-            for ln in lines:
-                f.write('    "%s\\n\\t" \\\n' % ln)
-            f.write('    ""\n\n')
-            nacc = max(nacc, 16 * c.ni * c.nj)
-            print("PIPS_CF32T4_%s_TEXT: %d instructions, %d MFMAs, LDS %d bytes" %
-                  (c.name, len(lines), sum("v_mfma" in ln for ln in lines), 3 * c.stage_bytes))
-        clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % i for i in range(nacc)] + ['"v%d"' % i for i in range(NV)] + \
-               ['"s%d"' % i for i in range(40, 82)]
-        f.write("#define PIPS_CF32T4_CLOBBER " + ", ".join(clob) + "\n")
-    print("wrote", OUT)
+    bodies = [("PIPS_CF32T4_%s_TEXT" % c.name, body(c)) for c in CONFIGS]
+    write_inc(OUT, "gen_conv_f32_t4.py", bodies, "PIPS_CF32T4_CLOBBER", max(16 * c.ni * c.nj for c in CONFIGS), NV, range(40, 82),
+              notes=[", LDS %d bytes" % (3 * c.stage_bytes) for c in CONFIGS])
 
 
 if __name__ == "__main__":

@@ -25,9 +25,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_guards as G  # noqa: E402  (wait-state guards: the numbers live in tools/asm_hazard_lint.py)
+from asm_emit import out_path  # noqa: E402  (this generator has no issue model: its few waits are written out by hand)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "..", "pips_amd", "csrc", "gather_item_asm.inc"))
+OUT = out_path("gather_item_asm.inc")
 TRACE = os.environ.get("PIPS_GEN_TRACE", "") == "1"   # tuning builds: per-stage clock counts in the lanes of %[tr]
 ABL = os.environ.get("PIPS_GEN_ABLATE", "")        # tuning builds: any of reads,feats,fma,dma,warm,epi (wrong results)
 

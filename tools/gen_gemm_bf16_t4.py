@@ -4,7 +4,7 @@ statement -- the bf16 down-projection C = R + A.W^T + bias on a 128 x 256 tile, 
 v_mfma_f32_16x16x32_bf16, operands global -> registers -> LDS (two tiles ahead), one LDS buffer, two barriers per 64 K values.
 
 The schedule is static, so it is written down instruction by instruction: ONE memory instruction between two MFMAs wherever
-there is one to place, every s_waitcnt counted by the issue model below (LDS and vector-memory operations return in order, so
+there is one to place, every s_waitcnt counted by the issue model of tools/asm_emit.py (LDS and vector-memory operations return in order, so
 "operation X has landed" = "at most as many operations are outstanding as were issued after X").
 
 Registers (all clobbered by the statement):
@@ -21,9 +21,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_guards as G  # noqa: E402  (wait-state guards: the numbers live in tools/asm_hazard_lint.py)
+from asm_emit import Emit, descriptor, out_path, write_inc  # noqa: E402  (the issue model, shared by every generator)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "..", "pips_amd", "csrc", "gemm_bf16_t4_asm.inc"))
+OUT = out_path("gemm_bf16_t4_asm.inc")
 POLICY = os.environ.get("PIPS_GEN_STORE_POLICY", "")      # tuning builds: cache-policy bits of the output stores, e.g. " sc1"
 
 FA = [0, 48]          # A fragment base register of K step 0 / 1
@@ -36,49 +36,6 @@ S_KT, S_SO, S_T = 60, 61, 62           # iterations left, byte offset of the til
 S_RR = 64                               # s[64:67]: i * 16 * ldr * 4 (residual row-block offsets); s[68:71]: the same for C
 S_CR = 68
 S_LAST = 72                             # (KT - 1) * 128
-
-
-class Emit:
-    """Instruction list + in-order issue model of the two counters."""
-
-    def __init__(self):
-        self.lines = []
-        self.lgkm = []          # outstanding LDS operations, oldest first (tags)
-        self.vm = []            # outstanding vector-memory operations
-
-    def raw(self, s):
-        self.lines.append(s)
-
-    def lds(self, s, tag):
-        self.lines.append(s)
-        self.lgkm.append(tag)
-
-    def vmem(self, s, tag):
-        self.lines.append(s)
-        self.vm.append(tag)
-
-    def need_lds(self, tags):
-        """wait until every LDS operation in `tags` has returned"""
-        idx = [k for k, t in enumerate(self.lgkm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.lgkm) - 1 - max(idx), 15)       # (4-bit counter: waiting for a little more than needed is correct)
-        self.lines.append("s_waitcnt lgkmcnt(%d)" % left)
-        self.lgkm = self.lgkm[len(self.lgkm) - left:] if left else []
-
-    def need_vm(self, tags):
-        idx = [k for k, t in enumerate(self.vm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.vm) - 1 - max(idx), 63)
-        self.lines.append("s_waitcnt vmcnt(%d)" % left)
-        self.vm = self.vm[len(self.vm) - left:] if left else []
-
-    def barrier(self):
-        if self.lgkm:
-            self.lines.append("s_waitcnt lgkmcnt(0)")
-            self.lgkm = []
-        self.lines.append("s_barrier")
 
 
 def acc(i, j):
@@ -120,13 +77,6 @@ def load_piece(e, s, soff):
     reg = ST + 4 * s
     rs = RS_A if s < 4 else RS_W
     e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], %s offen" % (reg, reg + 3, VO + s, rs, rs + 3, soff), ("st", s))
-
-
-def descriptor(e, base, lo, hi):
-    e.raw("s_mov_b32 s%d, %s" % (base, lo))
-    e.raw("s_and_b32 s%d, %s, 0xffff" % (base + 1, hi))
-    e.raw("s_mov_b32 s%d, 0x7fffffff" % (base + 2))
-    e.raw("s_mov_b32 s%d, 0x00020000" % (base + 3))
 
 
 def staging_slots():
@@ -236,8 +186,7 @@ def body(stream_bf16=False):
     e.raw("s_cbranch_scc1 1b")
     # ---- epilogue: + bias, 16-byte stores.  (the last iteration's speculative fragment reads / tile loads must have landed
     #      before their registers are reused)
-    e.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-    e.lgkm, e.vm = [], []
+    e.drain()
     for j in range(8):
         e.vmem("buffer_load_dwordx4 v[%d:%d], %%[voB], s[%d:%d], 0 offen offset:%d" % (4 * j, 4 * j + 3, RS_B, RS_B + 3, 64 * j), ("bias", j))
     G.emit_mfma_result_guard(e.raw, "v_mfma_f32_16x16x32_bf16")    # MFMA results -> v_accvgpr_read
@@ -265,19 +214,8 @@ def body(stream_bf16=False):
 
 
 def main():
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % i for i in range(128)] + ['"v%d"' % i for i in range(160)] + \
-           ['"s%d"' % i for i in range(40, 76)]
-    with open(OUT, "w") as f:
-        f.write("// generated by tools/gen_gemm_bf16_t4.py -- do not edit\n")
-        for name in ("PIPS_T4_TEXT", "PIPS_T4B_TEXT"):
-            lines = body(stream_bf16=name == "PIPS_T4B_TEXT")
-            f.write("#define %s \\\n" % name)
-            for ln in lines:
-                f.write('    "%s\\n\\t" \\\n' % ln)
-            f.write('    ""\n\n')
-            print("%s: %d instructions, %d MFMAs" % (name, len(lines), sum("v_mfma" in ln for ln in lines)))
-        f.write("#define PIPS_T4_CLOBBER " + ", ".join(clob) + "\n")
-    print("wrote", OUT)
+    bodies = [("PIPS_T4_TEXT", body(stream_bf16=False)), ("PIPS_T4B_TEXT", body(stream_bf16=True))]
+    write_inc(OUT, "gen_gemm_bf16_t4.py", bodies, "PIPS_T4_CLOBBER", 128, 160, range(40, 76))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ statement -- the bf16 up-projection C = bf16(gelu(bf16(A.W^T + bias))) (K = 512)
 wave tile 128 x 128 on v_mfma_f32_16x16x32_bf16 with all 256 AccVGPRs as accumulators, operands global -> registers -> LDS two
 K blocks ahead, one LDS buffer (64 KiB), two barriers per 64 K values, a block walking `ntile` consecutive row tiles of one
 column tile with the K pipeline running on across the tile boundary (the next tile's first blocks arrive under this tile's
-epilogue).  Same issue model / counted waits as tools/gen_gemm_bf16_t4.py.
+epilogue).  Issue model / counted waits: tools/asm_emit.py.
 
 Registers (all clobbered by the statement):
     a[0:255]     accumulators: tile (i, j) = rows 16 i.., columns 16 j.. of the wave tile -> a[4 (i + 8 j) : +3]
@@ -21,10 +21,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_guards as G  # noqa: E402  (wait-state guards: the numbers live in tools/asm_hazard_lint.py)
-import struct
+from asm_emit import Emit, descriptor, f32, gelu4, out_path, write_inc  # noqa: E402  (the issue model, shared by every generator)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "..", "pips_amd", "csrc", "gemm_bf16_t4up_asm.inc"))
+OUT = out_path("gemm_bf16_t4up_asm.inc")
 ABL = os.environ.get("PIPS_GEN_ABLATE", "")                 # timing probes (wrong results): gelu = no GELU arithmetic in the epilogue; vmwait / barrier / fragwait =
                                                             # the K loop without its waits on staged loads / its barriers / its waits on fragments
 POLICY = os.environ.get("PIPS_GEN_STORE_POLICY", "")      # tuning builds: cache-policy bits of the output stores, e.g. " sc1"
@@ -48,57 +47,6 @@ KT = 8                              # K = 512
 # rounding of the result (2^-9), five times below the LDS table it replaces (2.4e-5); three packed FMAs per pair fewer than A8
 COEF = [2.554670494e-05, -6.529359078e-04, 7.452824686e-03, -5.192063601e-02, -4.602978599e-01, -1.150685204e+00]
 TMAX = 5.65685425
-
-
-def f32(x):
-    return "0x%08x" % struct.unpack("<I", struct.pack("<f", x))[0]
-
-
-class Emit:
-    """Instruction list + in-order issue model of the two counters (see gen_gemm_bf16_t4.py)."""
-
-    def __init__(self):
-        self.lines, self.lgkm, self.vm = [], [], []
-
-    def raw(self, s):
-        self.lines.append(s)
-
-    def lds(self, s, tag):
-        self.lines.append(s)
-        self.lgkm.append(tag)
-
-    def vmem(self, s, tag):
-        self.lines.append(s)
-        self.vm.append(tag)
-
-    def need_lds(self, tags, emit=True):
-        idx = [k for k, t in enumerate(self.lgkm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.lgkm) - 1 - max(idx), 15)
-        if emit:
-            self.lines.append("s_waitcnt lgkmcnt(%d)" % left)
-        self.lgkm = self.lgkm[len(self.lgkm) - left:] if left else []
-
-    def need_vm(self, tags, emit=True):
-        idx = [k for k, t in enumerate(self.vm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.vm) - 1 - max(idx), 63)
-        if emit:
-            self.lines.append("s_waitcnt vmcnt(%d)" % left)
-        self.vm = self.vm[len(self.vm) - left:] if left else []
-
-    def barrier(self):
-        if self.lgkm:
-            self.lines.append("s_waitcnt lgkmcnt(0)")
-            self.lgkm = []
-        if "barrier" not in ABL:                             # (timing probe: the waves of a block run unsynchronised)
-            self.lines.append("s_barrier")
-
-    def drain(self):
-        self.lines.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        self.lgkm, self.vm = [], []
 
 
 def acc(i, j):
@@ -150,13 +98,6 @@ def load_piece(e, s):
         e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen" % (reg, reg + 3, VO + s, RS_W, RS_W + 3, S_SOW), ("st", s))
 
 
-def descriptor(e, base, lo, hi):
-    e.raw("s_mov_b32 s%d, %s" % (base, lo))
-    e.raw("s_and_b32 s%d, %s, 0xffff" % (base + 1, hi))
-    e.raw("s_mov_b32 s%d, 0x7fffffff" % (base + 2))
-    e.raw("s_mov_b32 s%d, 0x00020000" % (base + 3))
-
-
 def advance_request(e):
     """offsets of the K block to request next: one block further; behind a tile's last block comes the next tile's first
     (same W tile, A rows + strideA); behind the block's last tile the last block again (never used)"""
@@ -199,33 +140,6 @@ def iteration(e, first):
             e.barrier()
 
 
-def gelu4(e, X, T, Q):
-    """GELU of the 8 values v[X:X+7] in place (gelu_exact2's form (common.h) with the degree-5 exponent polynomial, four pairs side by side); T, Q: 8 scratch registers each"""
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_min_f32_e64 v%d, |v%d|, s%d" % (T + 2 * p + h, X + 2 * p + h, S_GC + 18))
-    for p in range(4):          # q = t c5 + c4
-        e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], s[%d:%d], v[%d:%d] op_sel_hi:[1,0,1]" %
-              (Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1, S_GC, S_GC + 1, VC, VC + 1))
-    for c in range(2, len(COEF)):
-        for p in range(4):
-            e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], s[%d:%d] op_sel_hi:[1,1,0]" %
-                  (Q + 2 * p, Q + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1, S_GC + 2 * c, S_GC + 2 * c + 1))
-    for p in range(4):
-        e.raw("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (Q + 2 * p, Q + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1))
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_exp_f32_e32 v%d, v%d" % (Q + 2 * p + h, Q + 2 * p + h))
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_max_f32_e32 v%d, 0, v%d" % (X + 2 * p + h, X + 2 * p + h))
-    for p in range(4):
-        e.raw("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (T + 2 * p, T + 2 * p + 1, T + 2 * p, T + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1))
-    for p in range(4):
-        e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], -0.5, v[%d:%d] op_sel_hi:[1,0,1]" %
-              (X + 2 * p, X + 2 * p + 1, T + 2 * p, T + 2 * p + 1, X + 2 * p, X + 2 * p + 1))
-
-
 def epilogue(e):
     """the finished tile: + bias, rounded to bf16 (the Linear's output under autocast), exact GELU, bf16, 16-byte stores.
     Entered with a full wait (the next tile's first fragments / blocks have landed under the K loop's tail); left with its
@@ -256,7 +170,7 @@ def epilogue(e):
                 e.raw("v_lshlrev_b32 v%d, 16, v%d" % (X + 2 * p, O + p))
                 e.raw("v_and_b32 v%d, 0xffff0000, v%d" % (X + 2 * p + 1, O + p))
             if "gelu" not in ABL:
-                gelu4(e, X, T, Q)
+                gelu4(e, X, T, Q, S_GC, VC, len(COEF))
             for p in range(4):
                 e.raw("v_cvt_pk_bf16_f32 v%d, v%d, v%d" % (O + p, X + 2 * p, X + 2 * p + 1))
             e.vmem("buffer_store_dwordx4 v[%d:%d], %%[voC], s[%d:%d], s%d offen offset:%d" % (O, O + 3, RS_C, RS_C + 3, S_CR + i, jp * 64) + POLICY,
@@ -268,7 +182,7 @@ def epilogue(e):
 
 
 def body():
-    e = Emit()
+    e = Emit(barriers="barrier" not in ABL)                 # (timing probe: the waves of a block run unsynchronised)
     descriptor(e, RS_A, "%[alo]", "%[ahi]")
     descriptor(e, RS_W, "%[wlo]", "%[whi]")
     descriptor(e, RS_C, "%[clo]", "%[chi]")
@@ -327,18 +241,7 @@ def body():
 
 
 def main():
-    lines = body()
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % i for i in range(256)] + ['"v%d"' % i for i in range(218)] + \
-           ['"s%d"' % i for i in range(40, 92)]
-    with open(OUT, "w") as f:
-        f.write("// generated by tools/gen_gemm_bf16_t4up.py -- do not edit\n")
-        f.write("#define PIPS_T4UP_TEXT \\\n")
-        for ln in lines:
-            f.write('    "%s\\n\\t" \\\n' % ln)
-        f.write('    ""\n\n')
-        f.write("#define PIPS_T4UP_CLOBBER " + ", ".join(clob) + "\n")
-    print("PIPS_T4UP_TEXT: %d instructions, %d MFMAs" % (len(lines), sum("v_mfma" in ln for ln in lines)))
-    print("wrote", OUT)
+    write_inc(OUT, "gen_gemm_bf16_t4up.py", [("PIPS_T4UP_TEXT", body())], "PIPS_T4UP_CLOBBER", 256, 218, range(40, 92))
 
 
 if __name__ == "__main__":

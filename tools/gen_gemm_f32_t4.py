@@ -38,10 +38,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_guards as G  # noqa: E402  (wait-state guards: the numbers live in tools/asm_hazard_lint.py)
-import struct
+from asm_emit import Emit, descriptor, f32, gelu4, out_path, write_inc  # noqa: E402  (the issue model, shared by every generator)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("PIPS_GEN_OUT", os.path.join(HERE, "..", "pips_amd", "csrc", "gemm_f32_t4_asm.inc"))
+OUT = out_path("gemm_f32_t4_asm.inc")
 POLICY = os.environ.get("PIPS_GEN_STORE_POLICY", "")      # tuning builds: cache-policy bits of the output stores, e.g. " sc1"
 
 LDROW = 144                         # LDS row stride in bytes
@@ -57,58 +56,6 @@ S_KL, S_SOA, S_SOW, S_TL, S_RQK, S_LASTA, S_T, S_KSTEP = 84, 85, 86, 87, 88, 89,
 COEF = [3.208326405e-07, -6.917509381e-06, 6.041429151e-05, -2.428356966e-04, -5.105399032e-05, 6.989960559e-03,
         -5.246259645e-02, -4.592153430e-01, -1.151104689e+00]
 TMAX = 5.65685425
-
-
-def f32(x):
-    return "0x%08x" % struct.unpack("<I", struct.pack("<f", x))[0]
-
-
-class Emit:
-    """Instruction list + in-order issue model of the two counters (see gen_gemm_bf16_t4.py)."""
-
-    def __init__(self):
-        self.lines, self.lgkm, self.vm = [], [], []
-
-    def raw(self, s):
-        self.lines.append(s)
-
-    def lds(self, s, tag):
-        self.lines.append(s)
-        self.lgkm.append(tag)
-
-    def vmem(self, s, tag):
-        self.lines.append(s)
-        self.vm.append(tag)
-
-    def need_lds(self, tags):
-        idx = [k for k, t in enumerate(self.lgkm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.lgkm) - 1 - max(idx), 15)
-        self.lines.append("s_waitcnt lgkmcnt(%d)" % left)
-        self.lgkm = self.lgkm[len(self.lgkm) - left:] if left else []
-
-    def need_vm(self, tags):
-        idx = [k for k, t in enumerate(self.vm) if t in tags]
-        if not idx:
-            return
-        left = min(len(self.vm) - 1 - max(idx), 63)
-        self.lines.append("s_waitcnt vmcnt(%d)" % left)
-        self.vm = self.vm[len(self.vm) - left:] if left else []
-
-    def need_loads(self):
-        """every load issued so far has landed (stores may stay in flight)"""
-        self.need_vm({t for t in self.vm if t[0] != "out"})
-
-    def barrier(self):
-        if self.lgkm:
-            self.lines.append("s_waitcnt lgkmcnt(0)")
-            self.lgkm = []
-        self.lines.append("s_barrier")
-
-    def drain(self):
-        self.lines.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        self.lgkm, self.vm = [], []
 
 
 class Shape:
@@ -183,13 +130,6 @@ def load_piece(e, sh, ring, s):
         e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen" % (reg, reg + 3, sh.vo + s, RS_A, RS_A + 3, S_SOA), ("st", ring, s))
     else:
         e.vmem("buffer_load_dwordx4 v[%d:%d], v%d, s[%d:%d], s%d offen" % (reg, reg + 3, sh.vo + s, RS_W, RS_W + 3, S_SOW), ("st", ring, s))
-
-
-def descriptor(e, base, lo, hi):
-    e.raw("s_mov_b32 s%d, %s" % (base, lo))
-    e.raw("s_and_b32 s%d, %s, 0xffff" % (base + 1, hi))
-    e.raw("s_mov_b32 s%d, 0x7fffffff" % (base + 2))
-    e.raw("s_mov_b32 s%d, 0x00020000" % (base + 3))
 
 
 def advance_request(e):
@@ -299,33 +239,6 @@ def stage_d4(e, sh, t, first, extra=()):
             n += 1
 
 
-def gelu4(e, X, T, Q, VC):
-    """exact GELU of the 8 values v[X:X+7] in place: gelu_exact2's arithmetic (common.h), four pairs side by side"""
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_min_f32_e64 v%d, |v%d|, s%d" % (T + 2 * p + h, X + 2 * p + h, S_GC + 18))
-    for p in range(4):          # q = c0 t + c1
-        e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], s[%d:%d], v[%d:%d] op_sel_hi:[1,0,1]" %
-              (Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1, S_GC, S_GC + 1, VC, VC + 1))
-    for c in range(2, len(COEF)):
-        for p in range(4):
-            e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], v[%d:%d], s[%d:%d] op_sel_hi:[1,1,0]" %
-                  (Q + 2 * p, Q + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1, S_GC + 2 * c, S_GC + 2 * c + 1))
-    for p in range(4):
-        e.raw("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (Q + 2 * p, Q + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1, T + 2 * p, T + 2 * p + 1))
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_exp_f32_e32 v%d, v%d" % (Q + 2 * p + h, Q + 2 * p + h))
-    for p in range(4):
-        for h in range(2):
-            e.raw("v_max_f32_e32 v%d, 0, v%d" % (X + 2 * p + h, X + 2 * p + h))
-    for p in range(4):
-        e.raw("v_pk_mul_f32 v[%d:%d], v[%d:%d], v[%d:%d]" % (T + 2 * p, T + 2 * p + 1, T + 2 * p, T + 2 * p + 1, Q + 2 * p, Q + 2 * p + 1))
-    for p in range(4):
-        e.raw("v_pk_fma_f32 v[%d:%d], v[%d:%d], -0.5, v[%d:%d] op_sel_hi:[1,0,1]" %
-              (X + 2 * p, X + 2 * p + 1, T + 2 * p, T + 2 * p + 1, X + 2 * p, X + 2 * p + 1))
-
-
 def res_index(sh, i, j, q):
     return sh.res + 4 * (q + 4 * j + 8 * i)
 
@@ -374,7 +287,7 @@ def epilogue_u(e, sh, epi):
                         e.raw("v_pk_add_f32 v[%d:%d], v[%d:%d], v[%d:%d]" %
                               (X + 4 * h + 2 * p, X + 4 * h + 2 * p + 1, X + 4 * h + 2 * p, X + 4 * h + 2 * p + 1, b + 2 * p, b + 2 * p + 1))
                 if epi == "gelu":
-                    gelu4(e, X, T, Q, sh.vc)
+                    gelu4(e, X, T, Q, S_GC, sh.vc, len(COEF))
                 else:
                     for h in range(2):
                         r = res_index(sh, i, j, 2 * qq + h)
@@ -629,25 +542,10 @@ def body_e():
 
 
 def main():
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % i for i in range(64)] + ['"v%d"' % i for i in range(NV)] + \
-           ['"s%d"' % i for i in range(40, 92)]
-    with open(OUT, "w") as f:
-        f.write("// generated by tools/gen_gemm_f32_t4.py -- do not edit\n")
-        for name, shape, epi in (("U_GELU", "U", "gelu"), ("U_RES", "U", "res"), ("D_RES", "D", "res")):
-            lines = body(shape, epi)
-            f.write("#define PIPS_F32T4_%s_TEXT \\\n" % name)
-            for ln in lines:
-                f.write('    "%s\\n\\t" \\\n' % ln)
-            f.write('    ""\n\n')
-            print("PIPS_F32T4_%s_TEXT: %d instructions, %d MFMAs" % (name, len(lines), sum("v_mfma" in ln for ln in lines)))
-        lines = body_e()
-        f.write("#define PIPS_F32T4_E_RES_TEXT \\\n")
-        for ln in lines:
-            f.write('    "%s\\n\\t" \\\n' % ln)
-        f.write('    ""\n\n')
-        print("PIPS_F32T4_E_RES_TEXT: %d instructions, %d MFMAs" % (len(lines), sum("v_mfma" in ln for ln in lines)))
-        f.write("#define PIPS_F32T4_CLOBBER " + ", ".join(clob) + "\n")
-    print("wrote", OUT)
+    bodies = [("PIPS_F32T4_%s_TEXT" % name, body(shape, epi))
+              for name, shape, epi in (("U_GELU", "U", "gelu"), ("U_RES", "U", "res"), ("D_RES", "D", "res"))]
+    bodies.append(("PIPS_F32T4_E_RES_TEXT", body_e()))
+    write_inc(OUT, "gen_gemm_f32_t4.py", bodies, "PIPS_F32T4_CLOBBER", 64, NV, range(40, 92))
 
 
 if __name__ == "__main__":
