@@ -35,6 +35,66 @@ WINDOW_CASES = {
 }
 
 
+# The same forwards on weights whose 26 affine normalisation pairs are not the identity (trained_like_state_dict below):
+# border queries on two clips at S = 8, and the odd window length.
+TRAINED_CASES = {
+    "s8_trained_i6": dict(B=2, N=16, H=136, W=200, stride=8, iters=6, tamed=True, border=True, affine="trained_like"),
+    "w5_trained_i3": dict(S=5, B=1, N=6, H=128, W=160, stride=8, iters=3, tamed=True, border=False, affine="trained_like"),
+}
+
+
+def trained_like_state_dict(seed: int = 0, S: int = 8, tamed: bool = False):
+    """init_state_dict(seed, S, tamed) with every affine normalisation tensor replaced by values a trained checkpoint
+    could hold: the 26 scales (param_table kind "ones": 24 mixer LayerNorms, the final LayerNorm, the GroupNorm in
+    front of ffeat_updater) become exp(0.35 randn) with ~3 % of the entries negative, the 26 shifts (kind "zeros")
+    0.3 randn.  One generator per tensor, keyed by its position in the table: every pair, and every channel of a
+    pair, is different, so a kernel that drops, swaps or permutes them cannot agree with the oracle."""
+    from pips_amd.weights import init_state_dict, param_table
+    sd = init_state_dict(seed, S=S, tamed=tamed)
+    for i, (name, (shape, kind)) in enumerate(param_table(S).items()):
+        g = torch.Generator().manual_seed((seed + 1234) * 7919 + i)
+        if kind == "ones":
+            w = torch.exp(0.35 * torch.randn(shape, generator=g))
+            sd[name] = w * torch.where(torch.rand(shape, generator=g) < 0.03, -1.0, 1.0)
+        elif kind == "zeros":
+            sd[name] = 0.3 * torch.randn(shape, generator=g)
+    return sd
+
+
+def affine_keys(S: int = 8):
+    """names of the 52 affine normalisation tensors, in table order, with their identity value (1.0 or 0.0)"""
+    from pips_amd.weights import param_table
+    return [(k, 1.0 if kind == "ones" else 0.0) for k, (_, kind) in param_table(S).items() if kind in ("ones", "zeros")]
+
+
+def case_state_dict(case: dict):
+    """the seeded weights a case runs on: init_state_dict, or the trained-like dict when the case says so"""
+    from pips_amd.weights import init_state_dict
+    S = case.get("S", 8)
+    if case.get("affine") == "trained_like":
+        return trained_like_state_dict(0, S=S, tamed=case["tamed"])
+    return init_state_dict(0, S=S, tamed=case["tamed"])
+
+
+def mixer_rows(P: int, S: int = 8, seed: int = 3):
+    """(P, S, 519) token rows for the mixer stage tests: randn, beyond 256 particles the first 256 repeated with a
+    small perturbation (as tests/test_kernels_gpu.py does, bounded generator time)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(min(P, 256), S, 519, generator=g)
+    if P > 256:
+        x = x.repeat((P + 255) // 256, 1, 1)[:P] + 0.01 * torch.randn(P, S, 519, generator=g)
+    return x
+
+
+def state_update_inputs(B: int, N: int, seed: int = 11, S: int = 8):
+    """(ffeats (B,S,N,128), coords, coords0 (B,S,N,2), delta (B*N,S,130)) of tests/test_kernels_gpu.py::test_state_update"""
+    g = torch.Generator().manual_seed(seed)
+    ffeats = torch.randn(B, S, N, 128, generator=g)
+    coords = torch.rand(B, S, N, 2, generator=g) * 40
+    delta = torch.randn(B * N, S, 130, generator=g)
+    return ffeats, coords, coords + 0.5, delta
+
+
 def make_inputs(case: dict, seed: int = 1, S: int = 8):
     """(xys, rgbs, coords_init, feat_init) on CPU, fp32.  The window length is case["S"] when the case names one."""
     S = case.get("S", S)

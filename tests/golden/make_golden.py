@@ -1,6 +1,7 @@
 """Generate the golden vectors by running the UNMODIFIED reference (build container only).
 
-    python tests/golden/make_golden.py              (--windows: only the Pips(S != 8) cases; --fresh: main_fresh)
+    python tests/golden/make_golden.py              (--windows: only the Pips(S != 8) cases; --fresh: main_fresh;
+                                                     --trained: only the trained-like-affine cases)
 
 For every case of cases.py: load seeded weights into /root/reference/nets/pips.py's Pips,
 run forward on the seeded inputs, store coord_predictions / vis_e / ffeat as float32 in
@@ -42,7 +43,7 @@ def make_demo_frames():
 def run_case(name, case):
     """one forward of the unmodified reference -> tests/golden/<name>.npz; returns the reference module"""
     S = case.get("S", 8)
-    sd = init_state_dict(0, S=S, tamed=case["tamed"])
+    sd = G.case_state_dict(case)
     xys, rgbs, ci, fi = G.make_inputs(case)
     ref = R.load_reference_pips(sd, stride=case["stride"], S=S)
     with torch.no_grad():
@@ -82,9 +83,9 @@ def main_losses(name="s8_raw_i3"):
     """(seq_loss, vis_loss, ce_loss) of the reference forward called with trajs_g / vis_g / valids
     (nets/pips.py:600-606, the way test_on_flt.py:87 calls it) -> <case>_losses.npz."""
     assert R.available(), "reference not mounted at /root/reference"
-    case = G.CASES[name] if name in G.CASES else G.WINDOW_CASES[name]
+    case = {**G.CASES, **G.WINDOW_CASES, **G.TRAINED_CASES}[name]
     S = case.get("S", 8)
-    sd = init_state_dict(0, S=S, tamed=case["tamed"])
+    sd = G.case_state_dict(case)
     xys, rgbs, ci, fi = G.make_inputs(case)
     trajs_g, vis_g, valids = G.make_targets(case)
     ref = R.load_reference_pips(sd, stride=case["stride"], S=S)
@@ -114,7 +115,18 @@ def main_fresh():
     print("fresh_s7_raw_i2 trajs", tuple(torch.stack(p).shape), "score_map_loss", float(loss))
 
 
+def main_trained():
+    """cases.TRAINED_CASES (non-identity norm scales and shifts) and the losses of the S = 8 one; nothing else is rewritten"""
+    assert R.available(), "reference not mounted at /root/reference"
+    for name, case in G.TRAINED_CASES.items():
+        run_case(name, case)
+    main_losses("s8_trained_i6")
+
+
 if __name__ == "__main__":
+    if "--trained" in sys.argv:
+        main_trained()
+        sys.exit(0)
     if "--fresh" in sys.argv:                # only the fresh-seed forward and the score_map_loss value
         main_fresh()
         sys.exit(0)

@@ -170,3 +170,98 @@ def test_oracle_score_map_loss_equals_live_reference_function():
     assert float(got) == pytest.approx(float(gold["loss"]), rel=1e-6)
     if R.available():
         assert torch.equal(got, R.reference_module().score_map_loss(*args))
+
+
+# ------------------------------------------------------------------ trained-like weights (non-identity norm scales / shifts)
+@pytest.mark.parametrize("name", list(G.TRAINED_CASES))
+def test_oracle_matches_golden_trained_like(name):
+    """cases.TRAINED_CASES: the unmodified reference run on cases.trained_like_state_dict (make_golden.py --trained).  With
+    init_state_dict every LayerNorm / GroupNorm is `x * 1 + 0`; these vectors pin the oracle's handling of real scales and
+    shifts (which tensor goes to which layer, scale before shift) to the reference's."""
+    case = G.TRAINED_CASES[name]
+    S = case.get("S", 8)
+    gold = np.load(os.path.join(GOLD, name + ".npz"))
+    sd = G.case_state_dict(case)
+    xys, rgbs, ci, fi = G.make_inputs(case)
+    assert rgbs.shape[1] == S
+    preds, preds2, vis, ffeat = O.forward(sd, xys, rgbs, iters=case["iters"], stride=case["stride"])
+    assert len(preds2) == case["iters"] + 4
+    err = np.abs(torch.stack(preds).numpy() - gold["trajs"]).reshape(case["iters"], -1).max(axis=1)
+    print(name, "oracle vs reference, per-iteration max |dtraj| px:", err)
+    assert gold["trajs"].shape[2] == S and err.max() < 1e-3
+    assert np.abs(vis.numpy() - gold["vis"]).max() < 1e-3
+    assert np.abs(ffeat.numpy() - gold["ffeat"]).max() < 1e-4
+    assert np.abs(preds2[0].numpy() - gold["traj0"]).max() < 1e-5
+    # the fixture is not the identity-affine answer in disguise: the same forward on init_state_dict is far away
+    from pips_amd.weights import init_state_dict
+    plain = O.forward(init_state_dict(0, S=S, tamed=True), xys, rgbs, iters=case["iters"], stride=case["stride"])[0]
+    assert float((plain[-1] - preds[-1]).abs().max()) > 100 * 1e-3
+
+
+def test_oracle_losses_match_reference_golden_trained_like():
+    """(seq_loss, vis_loss, ce_loss) on the trained-like S = 8 case.  Bound: the fixture may come from a run with another
+    thread count (summation order); this forward's own fp32-vs-fp64 distance is < 3e-5 px on trajectories whose mean error
+    against the targets is 1.4 px, i.e. 2e-5 relative -- gate at 1e-4, half of what the HIP forward is held to."""
+    name = "s8_trained_i6"
+    case = G.TRAINED_CASES[name]
+    gold = np.load(os.path.join(GOLD, name + "_losses.npz"))
+    xys, rgbs, ci, fi = G.make_inputs(case)
+    tg, vg, va = G.make_targets(case)
+    seq, vis, ce = O.losses(G.case_state_dict(case), xys, rgbs, tg, vg, va, iters=case["iters"], stride=case["stride"])
+    for got, key in ((seq, "seq_loss"), (vis, "vis_loss"), (ce, "ce_loss")):
+        assert float(got) == pytest.approx(float(gold[key]), rel=1e-4), (name, key)
+
+
+def test_trained_like_state_dict_is_what_it_says():
+    """52 affine tensors replaced, nothing else; every pair different from every other; some scales negative; the values do
+    not depend on `tamed`."""
+    from pips_amd.weights import init_state_dict
+    for S in (8, 5):
+        base, sd = init_state_dict(0, S=S), G.trained_like_state_dict(0, S=S)
+        aff = G.affine_keys(S)
+        assert len(aff) == 52 and list(sd) == list(base)
+        names = {k for k, _ in aff}
+        for k in sd:
+            assert sd[k].shape == base[k].shape and sd[k].dtype == torch.float32
+            assert torch.equal(sd[k], base[k]) != (k in names), k
+        scales = [sd[k] for k, one in aff if one == 1.0]
+        shifts = [sd[k] for k, one in aff if one == 0.0]
+        assert len(scales) == 26 and len(shifts) == 26
+        for group in (scales, shifts):
+            for i, a in enumerate(group):
+                assert a.unique().numel() == a.numel()                       # every channel different
+                for b in group[i + 1:]:
+                    if a.shape == b.shape:
+                        assert float((a - b).abs().max()) > 0.5              # every tensor different
+        assert sum(int((s < 0).sum()) for s in scales) > 26 * 5
+        tamed = G.trained_like_state_dict(0, S=S, tamed=True)
+        assert all(torch.equal(tamed[k], sd[k]) for k in names)
+
+
+def test_trained_like_weights_have_teeth():
+    """The premise of tests/test_trained_like_gpu.py: at the inputs it uses, NO single affine tensor is invisible.  Each of
+    the 52 in turn is reset to its identity value (ones / zeros); the oracle's output must then move by more than 10x the
+    tolerance the GPU test applies to that output -- the mixer's 1e-4 * max(1, |ref|) for the 50 tensors the mixer reads
+    (P = 32 rows, S = 8), the state update's 2e-5 on the features and on the visibility logits for `norm.*`."""
+    sd = G.trained_like_state_dict(0)
+    x = G.mixer_rows(32)
+    ref = O.mixer(sd, x)
+    scale = max(1.0, float(ref.abs().max()))
+    ffeats, coords, coords0, delta = G.state_update_inputs(2, 19)
+    ff_ref, _ = O.update_step(sd, ffeats, coords, coords0, delta)
+    vis = lambda s, ff: torch.nn.functional.linear(ff.reshape(-1, 128), s["vis_predictor.0.weight"], s["vis_predictor.0.bias"])
+    vis_ref = vis(sd, ff_ref)
+    weakest = {}
+    for k, ident in G.affine_keys(8):
+        s = dict(sd)
+        s[k] = torch.full_like(sd[k], ident)
+        if k.startswith("norm."):
+            ff, _ = O.update_step(s, ffeats, coords, coords0, delta)
+            moved = {"state ffeats": float((ff - ff_ref).abs().max()) / 2e-5, "state vis": float((vis(s, ff) - vis_ref).abs().max()) / 2e-5}
+        else:
+            moved = {"mixer": float((O.mixer(s, x) - ref).abs().max()) / (1e-4 * scale)}
+        for what, m in moved.items():
+            assert m > 10, f"{k} reset to {ident}: {what} moves by only {m:.1f}x its tolerance"
+            if m < weakest.get(what, (float("inf"), ""))[0]:
+                weakest[what] = (m, k)
+    print("least visible affine tensor per output (movement / tolerance):", weakest)
