@@ -406,18 +406,21 @@ __global__ __launch_bounds__(512) void conv3x3_c64_pp_kernel(const unsigned shor
             // full row segment: a lane packs its channel's pixel PAIR (r, r+1), trades the dword with the neighbouring lane
             // (channel n ^ 1) and keeps, by one byte permute, {n, n+1} of pixel r (even lanes) or {n-1, n} of pixel r+1 (odd
             // lanes): cvt + dpp + perm + one dword store at an immediate offset per two values; statistics on packed pairs
-            // Statistics: sums of x and x^2 about pivot 0, four independent chains per sum (the issue of a lone wave is
-            // latency-bound); the bf16 mode's maps carry 2^-9 rounding anyway, the pivoted form is kept on the edge path.
+            // Statistics: sums of x - p and (x - p)^2 about the wave's first pixel like every other writer (the sums are taken
+            // from the fp32 accumulators: a plain sum of squares loses the variance of a channel with |mean| >> std whatever the
+            // store rounds to), four independent chains per sum (the issue of a lone wave is latency-bound).
             char* base = reinterpret_cast<char*>(orow) + lane_out;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
+                const float pivot = __shfl(acc[j][0], l31);                  // the wave's first pixel (lanes of half 0, r = 0)
                 float cs4[4] = {0.f, 0.f, 0.f, 0.f}, cq4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int rr = 0; rr < 8; ++rr) {
                     const int r0 = 2 * rr;
                     const float va = acc[j][r0], vb = acc[j][r0 + 1];
-                    cs4[rr & 1] += va; cs4[2 + (rr & 1)] += vb;
-                    cq4[rr & 1] = fmaf(va, va, cq4[rr & 1]); cq4[2 + (rr & 1)] = fmaf(vb, vb, cq4[2 + (rr & 1)]);
+                    const float da = va - pivot, db = vb - pivot;
+                    cs4[rr & 1] += da; cs4[2 + (rr & 1)] += db;
+                    cq4[rr & 1] = fmaf(da, da, cq4[rr & 1]); cq4[2 + (rr & 1)] = fmaf(db, db, cq4[2 + (rr & 1)]);
                     const unsigned own = pack2_bf16(va, vb);
                     const unsigned nbr = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xf, 0xf, false);
                     const unsigned o = __builtin_amdgcn_perm(nbr, own, perm_sel);
@@ -427,7 +430,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_pp_kernel(const unsigned shor
                 const f2 cs = {cs4[0] + cs4[1], cs4[2] + cs4[3]}, cq = {cq4[0] + cq4[1], cq4[2] + cq4[3]};
                 if (stats != nullptr)
                     store_conv_partial(stats, f, tiles_per_frame * 4, tt * 4 + gw, 64, j * 32 + l31, half, cs.x + cs.y, cq.x + cq.y,
-                                       0.f, PP_COLS);
+                                       pivot, PP_COLS);
             }
             return;
         }
