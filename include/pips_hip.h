@@ -96,7 +96,8 @@ const char* pips_last_error(void);
  * the two GEMMs again in round 4 -- tools/experiments/) are gone.
  * Still 3 after additions that change no existing entry point: pips_track_win and pips_mixer_input_build_win (per-particle
  * time direction win_dir); pips_track_ring, pips_mixer_input_build_ring and pips_pyramid_append (a ring of R frame slots
- * for streamed video). */
+ * for streamed video); pips_chain_hop, pips_chain_gather, pips_chain_step, pips_chain_workspace_bytes and pips_chain_threshold
+ * (the visibility-aware chaining of chain_demo.py:40-83, one call per hop). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -200,6 +201,60 @@ int    pips_track_ring(const void* arena, const float* pyramid, int B, int T, in
                        const int* win_start, const int* win_dir, const float* times, int N, int stride, int iters,
                        int flags, int S, void* workspace, size_t workspace_bytes,
                        float* out_trajs, float* out_vis, float* out_ffeat0, void* stream);
+
+/* ---- visibility-aware chaining: one call per hop ----------------------------------------
+ * Replaces: the hop loop body of chain_demo.py:40-83 (test_on_badja.py:64-112) for a whole set of particles -- read the
+ * start position at the window start (:47), run the model on the 8-frame window (:54-57, features carried from the first
+ * window), write the window into the trajectory (:59-61), scan frames 7..2 for the latest one whose sigmoid visibility
+ * beats the threshold 0.9, lowered by 0.02 whenever the scan reaches frame 1 (:63-77), advance the window start by that step
+ * (:79) -- and the bookkeeping of which particles are still inside the video.  Window length 8 only (the scan is written for it).
+ *
+ * The caller owns the state, all of it on the device:
+ *   trajs   float (L,n,2)  trajectories; logical frame f lives in row ((f + base) mod L + L) mod L
+ *   vis     float (L,n)    visibility logits, same rows; may be NULL
+ *   cur     int32 (n)      window start of each particle (logical frame)
+ *   dir     int32 (n)      time direction, only the sign is used (< 0: backward, pips_track_win's win_dir); NULL = all forward
+ *   feat    float (n,128)  features carried from each particle's first window
+ *   active  int32 (n_act)  the particles of this hop: strictly ascending indices into [0, n)
+ * The library does not verify `active` (that would take a pass over device memory): ascending order is the caller's to keep.
+ * A member outside [0, n) is never dereferenced and is IGNORED -- the gather stages zeros for it, the step writes no row, no
+ * cur / feat / steps element and never lists it in next_active -- so a corrupt list cannot write out of bounds; the tracker
+ * still runs a window for it, and its results are dropped.  Frame arithmetic (cur + dir * s, f + base) is plain int: keep
+ * |cur| + |base| + 8 below 2^31.
+ * L >= 8 keeps the 8 rows of a window apart.  A linear buffer over a video of T frames with windows that may run past either
+ * end is L = T + 14, base = 7; a ring over a streamed video is base = 0 with the caller reusing rows.
+ *
+ * pips_chain_hop = pips_chain_gather, pips_track_ring on (B = 1, N = n_act) windows, pips_chain_step, on `stream`:
+ *   sample_feat != 0  the windows sample their features at the start positions (feat_init = NULL) and feat[q] receives them
+ *                     (a particle's first window); 0: the windows run on feat[q], which stays as it is
+ *   next_active       int32, room for n_act: the members of active with 0 <= cur < T after the step, IN THEIR ORDER
+ *                     (a block scan, not atomics); may not alias active; elements past *next_count are not written
+ *   next_count        device int32: their number.  The library does not synchronise: the caller copies it back
+ *   steps             int32 (n_act) or NULL: the step si in 2..7 of each active particle (7 for NaN logits, as the reference's
+ *                     comparison admits no frame)
+ * n_act == 0: PIPS_OK, *next_count = 0, nothing else.  PIPS_E_ARG: n_act < 0 or > n, L < 8, R < 1, T < 1, a NULL active / trajs /
+ * cur / feat / next_active / next_count; PIPS_E_WORKSPACE: workspace_bytes < pips_chain_workspace_bytes(n_act, iters)
+ * (= pips_track_workspace_bytes_s(1, n_act, 8) + the staging arrays and the windows).  A rejected call writes nothing.
+ * pips_chain_threshold(k), k in 0..63: the k-th threshold (host function; the subtraction in double, rounded to fp32).
+ * The two stages on their own (parity tests):
+ *   pips_chain_gather  xy (n_act,2) = trajs[row(cur[q]), q], ws = cur[q], wd = dir ? dir[q] : 1, fi (n_act,128) = feat[q]
+ *                      (fi is not written with sample_feat): the xys / win_start / win_dir / feat_init of pips_track_ring
+ *   pips_chain_step    win_trajs (8,n_act,2), win_vis (8,n_act), win_ffeat0 (n_act,128; read with sample_feat): the write-back,
+ *                      scan, cur / feat update and compaction; every other element of trajs / vis stays bit-identical */
+float  pips_chain_threshold(int k);
+size_t pips_chain_workspace_bytes(int n_act, int iters);
+int    pips_chain_gather(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const float* feat,
+                         const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, void* stream);
+int    pips_chain_step(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int n, const int* active,
+                       int n_act, int sample_feat, float* trajs, float* vis, int L, int base, int* cur, const int* dir,
+                       float* feat, int* next_active, int* next_count, int* steps, void* stream);
+int    pips_chain_hop(const void* arena, const float* pyramid, int T, int R, int H8, int W8,
+                      const float* times, int stride, int iters, int flags,
+                      int n, const int* active, int n_act, int sample_feat,
+                      float* trajs, float* vis, int L, int base,
+                      int* cur, const int* dir, float* feat,
+                      int* next_active, int* next_count, int* steps,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 

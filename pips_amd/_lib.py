@@ -47,6 +47,14 @@ SIGNATURES = {
                                c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, c_void_p]),
     "pips_track_ring": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_void_p, c_void_p, fp, c_int, c_int,
                                 c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, c_void_p]),
+    "pips_chain_threshold": (c_float, [c_int]),
+    "pips_chain_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "pips_chain_gather": (c_int, [fp, c_int, c_int, c_int, c_void_p, c_void_p, fp, c_void_p, c_int, c_int, fp, c_void_p, c_void_p, fp,
+                                  c_void_p]),
+    "pips_chain_step": (c_int, [fp, fp, fp, c_int, c_int, c_void_p, c_int, c_int, fp, fp, c_int, c_int, c_void_p, c_void_p, fp,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pips_chain_hop": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, fp, fp,
+                               c_int, c_int, c_void_p, c_void_p, fp, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pips_encoder_workspace_bytes": (c_size_t, [c_int] * 4),
     "pips_pyramid_floats": (c_size_t, [c_int] * 4),
     "pips_pyramid_offset": (c_size_t, [c_int] * 5),

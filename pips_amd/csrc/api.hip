@@ -936,6 +936,68 @@ GatherCall gather_call(const float* pyramid, int B, int frames, int H8, int W8, 
     return g;
 }
 
+// ------------------------------------------------------------------ chaining (chain_demo.py:40-83)
+// The caller-owned state of a set of chained particles: trajs (L,n,2) / vis (L,n) hold frame f in row (f + base) mod L, cur
+// (n) the window starts, dir (n) the time directions (sign; null = forward), feat (n,128) the carried features; active
+// (n_act) the particles of this hop, strictly ascending.  vis and dir may be null.
+struct ChainState {
+    int n; const int* active; int n_act; int sample_feat;
+    float* trajs; float* vis; int L, base;
+    int* cur; const int* dir; float* feat;
+};
+int check_chain_state(const ChainState& s, const char* who) {
+    PIPS_CHECK_ARG(s.n_act >= 0 && s.n_act <= s.n, "%s: need 0 <= n_act <= n (n_act=%d, n=%d)", who, s.n_act, s.n);
+    PIPS_CHECK_ARG(s.L >= PIPS_S, "%s: a window of %d frames needs L >= %d rows (L=%d)", who, PIPS_S, PIPS_S, s.L);
+    PIPS_CHECK_ARG(s.active && s.trajs && s.cur && s.feat, "%s: null pointer", who);
+    return PIPS_OK;
+}
+// a hop over no particle: *next_count = 0 on the stream and nothing else; a memset that fails is reported as a failed launch is
+int clear_chain_count(int* next_count, const char* who, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(next_count, 0, sizeof(int), st);
+    if (e != hipSuccess) {
+        set_error("%s: clearing next_count: %s", who, hipGetErrorString(e));
+        return PIPS_E_LAUNCH;
+    }
+    return PIPS_OK;
+}
+
+// workspace of one hop, in floats: the tracker's for (B = 1, N = n_act, S = 8), the staging arrays of chain_gather and the windows
+// the tracker returns (every iterate of the trajectories: the last one is written back)
+struct ChainPlan { size_t track, xy, ws, wd, fi, win_trajs, win_vis, win_ffeat0, total; };
+ChainPlan plan_chain(int n_act, int iters) {
+    ChainPlan P;
+    Bump b;
+    P.track = b.take(plan_track(1, n_act, PIPS_S).total);
+    P.xy = b.take((size_t)n_act * 2);
+    P.ws = b.take(n_act);
+    P.wd = b.take(n_act);
+    P.fi = b.take((size_t)n_act * PIPS_C);
+    P.win_trajs = b.take((size_t)(iters + 1) * PIPS_S * n_act * 2);
+    P.win_vis = b.take((size_t)PIPS_S * n_act);
+    P.win_ffeat0 = b.take((size_t)n_act * PIPS_C);
+    P.total = b.off;
+    return P;
+}
+
+int chain_gather(const ChainState& s, float* xy, int* ws, int* wd, float* fi, hipStream_t st) {
+    RUN(check_chain_state(s, "chain_gather"));
+    PIPS_CHECK_ARG(xy && ws && wd && (fi || s.sample_feat), "chain_gather: null pointer");
+    if (s.n_act == 0) return PIPS_OK;
+    return launch_chain_gather(s.trajs, s.L, s.base, s.n, s.cur, s.dir, s.feat, s.active, s.n_act, s.sample_feat, xy, ws, wd, fi, st);
+}
+
+int chain_step(const ChainState& s, const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int* next_active,
+               int* next_count, int* steps, hipStream_t st) {
+    RUN(check_chain_state(s, "chain_step"));
+    PIPS_CHECK_ARG(T >= 1, "chain_step: need T >= 1 (T=%d)", T);
+    PIPS_CHECK_ARG(next_active && next_count, "chain_step: null pointer");
+    PIPS_CHECK_ARG(next_active != s.active, "chain_step: next_active may not alias active");
+    if (s.n_act == 0) return clear_chain_count(next_count, "chain_step", st);
+    PIPS_CHECK_ARG(win_trajs && win_vis && (win_ffeat0 || !s.sample_feat), "chain_step: null pointer");
+    return launch_chain_step(win_trajs, win_vis, win_ffeat0, s.n, s.active, s.n_act, s.sample_feat, s.trajs, s.vis, s.L, s.base, T, s.cur,
+                             s.dir, s.feat, next_active, next_count, steps, st);
+}
+
 }  // namespace
 
 // ================================================================== the C ABI (include/pips_hip.h)
@@ -1245,6 +1307,58 @@ int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8
                    size_t workspace_bytes, float* out_trajs, float* out_vis, float* out_ffeat0, void* stream) {
     return pips_track_ring(arena, pyramid, B, T, T, H8, W8, xys, coords_init, feat_init, win_start, win_dir, times, N, stride, iters,
                            flags, S, workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream);
+}
+
+// ---- chaining
+float pips_chain_threshold(int k) { return chain_threshold(k); }
+size_t pips_chain_workspace_bytes(int n_act, int iters) {
+    if (n_act <= 0 || iters < 0) return 0;
+    return plan_chain(n_act, iters).total * sizeof(float);
+}
+int pips_chain_gather(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const float* feat,
+                      const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, void* stream) {
+    const ChainState s = {n, active, n_act, sample_feat, const_cast<float*>(trajs), nullptr, L, base, const_cast<int*>(cur), dir,
+                          const_cast<float*>(feat)};
+    return chain_gather(s, xy, ws, wd, fi, (hipStream_t)stream);
+}
+int pips_chain_step(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int n, const int* active,
+                    int n_act, int sample_feat, float* trajs, float* vis, int L, int base, int* cur, const int* dir, float* feat,
+                    int* next_active, int* next_count, int* steps, void* stream) {
+    const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat};
+    return chain_step(s, win_trajs, win_vis, win_ffeat0, T, next_active, next_count, steps, (hipStream_t)stream);
+}
+int pips_chain_hop(const void* arena, const float* pyramid, int T, int R, int H8, int W8, const float* times, int stride, int iters,
+                   int flags, int n, const int* active, int n_act, int sample_feat, float* trajs, float* vis, int L, int base,
+                   int* cur, const int* dir, float* feat, int* next_active, int* next_count, int* steps, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat};
+    // every check ahead of the first launch: a rejected call leaves the caller's state as it was
+    RUN(check_chain_state(s, "chain_hop"));
+    PIPS_CHECK_ARG(R >= 1 && T >= 1, "chain_hop: need R >= 1 and T >= 1 (R=%d, T=%d)", R, T);
+    PIPS_CHECK_ARG(next_active && next_count, "chain_hop: null pointer");
+    PIPS_CHECK_ARG(next_active != active, "chain_hop: next_active may not alias active");
+    PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "chain_hop: need iters >= 0, stride >= 1 and a map of at least 8x8");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_act == 0) return clear_chain_count(next_count, "chain_hop", st);
+    PIPS_CHECK_ARG(arena && pyramid && times && workspace, "chain_hop: null pointer");
+    const ChainPlan P = plan_chain(n_act, iters);
+    if (workspace_bytes < P.total * sizeof(float)) {
+        set_error("chain_hop: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
+        return PIPS_E_WORKSPACE;
+    }
+    float* ws = (float*)workspace;
+    float* xy = ws + P.xy; float* fi = ws + P.fi;
+    int* win_start = reinterpret_cast<int*>(ws + P.ws); int* win_dir = reinterpret_cast<int*>(ws + P.wd);
+    float* win_trajs = ws + P.win_trajs; float* win_vis = ws + P.win_vis; float* win_ffeat0 = ws + P.win_ffeat0;
+    RUN(chain_gather(s, xy, win_start, win_dir, fi, st));
+    // the first window samples its features at the start position (feat_init = NULL) and returns them; later ones carry feat
+    TrackCall c = track_call(arena, pyramid, 1, T, H8, W8, xy, nullptr, sample_feat ? nullptr : fi, win_start, times, n_act, stride,
+                             iters, flags, ws + P.track, plan_track(1, n_act, PIPS_S).total * sizeof(float), win_trajs, win_vis,
+                             sample_feat ? win_ffeat0 : nullptr, stream);
+    c.R = R;
+    c.win_dir = dir != nullptr ? win_dir : nullptr;
+    RUN(track_impl(c));
+    return chain_step(s, win_trajs + (size_t)iters * PIPS_S * n_act * 2, win_vis, win_ffeat0, T, next_active, next_count, steps, st);
 }
 
 // ---- whole forward

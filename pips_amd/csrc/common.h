@@ -426,4 +426,15 @@ int launch_state_update(const float* arena, const float* delta, float* ffeats, f
                         const float* coords0, int B, int N, float stride, float* out_traj,
                         float* out_vis, hipStream_t st, int Sw = PIPS_S);
 
+// ---------------------------------------------------------------- chaining bookkeeping (chain.hip)
+// thr after k decrements of chain_demo.py:64,75 (doubles, rounded to fp32), k in 0..63; host function
+float chain_threshold(int k);
+// the staging arrays of one hop (B = 1, N = n_act) for the particles active[0..n_act) of a caller-owned chaining state
+int launch_chain_gather(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const float* feat,
+                        const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, hipStream_t st);
+// write-back of the hop's windows, skip scan, new window starts and the stable compaction of the live particles
+int launch_chain_step(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int n, const int* active, int n_act,
+                      int sample_feat, float* trajs, float* vis, int L, int base, int T, int* cur, const int* dir, float* feat,
+                      int* next_active, int* next_count, int* steps, hipStream_t st);
+
 }  // namespace pips

@@ -145,30 +145,30 @@ def track_sharded_particles(model, xys, rgbs, iters=6, group=None, encode="repli
     return trajs[:, :, :n].contiguous(), vis[:, :, :n].contiguous()
 
 
-def track_chained_sharded(model, rgbs, xy0, iters=6, group=None):
+def track_chained_sharded(model, rgbs, xy0, iters=6, group=None, engine="torch"):
     """``drivers.track_chained`` (chain_demo.py:40-83) with the particles split over the ranks -- the reference's loop
     handles one particle at a time (chain_demo.py:40), so their chains are independent: every rank encodes the video
     (per-frame maps, no exchange), chains N/G particles and one all-gather on the particle axis collects
-    ``trajs_e (1,T,N,2)``."""
+    ``trajs_e (1,T,N,2)``.  ``engine``: ``drivers.track_chained``'s."""
     from . import drivers
     rank, world = _world(group)
     xp, n = pad_to_world(xy0, world, dim=1)
     lo, hi = shard_range(xp.shape[1], rank, world)
-    mine = drivers.track_chained(model, rgbs, xp[:, lo:hi], iters=iters)          # (1,T,n/G,2)
+    mine = drivers.track_chained(model, rgbs, xp[:, lo:hi], iters=iters, engine=engine)          # (1,T,n/G,2)
     if not _live(group):
         return mine
     return _all_gather_cat(mine, 2, group)[:, :, :n].contiguous()
 
 
-def track_queries_sharded(model, rgbs, queries, iters=6, group=None):
+def track_queries_sharded(model, rgbs, queries, iters=6, group=None, engine="torch"):
     """``drivers.track_queries`` with the queries split over the ranks -- every query's two chains are independent of the
     other queries', so, as in ``track_chained_sharded``, every rank encodes the video, tracks N/G queries (padded to the world
     size by repeating the last one) and one all-gather of the packed ``[x, y, vis_logit]`` on the particle axis collects
-    ``trajs_e (1,T,N,2)`` and ``vis_e (1,T,N)``."""
+    ``trajs_e (1,T,N,2)`` and ``vis_e (1,T,N)``.  ``engine``: ``drivers.track_queries``'s."""
     from . import drivers
     rank, world = _world(group)
     qp, n = pad_to_world(queries, world, dim=1)
     lo, hi = shard_range(qp.shape[1], rank, world)
-    trajs, vis = drivers.track_queries(model, rgbs, qp[:, lo:hi], iters=iters)
+    trajs, vis = drivers.track_queries(model, rgbs, qp[:, lo:hi], iters=iters, engine=engine)
     trajs, vis = all_gather_result(trajs, vis, group=group, dim=2)
     return trajs[:, :, :n].contiguous(), vis[:, :, :n].contiguous()

@@ -15,6 +15,12 @@
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
+
+The chaining drivers take ``engine="torch" | "native"``.  ``"torch"`` (the default) keeps the hop's bookkeeping -- the indexed
+read of the start positions, the scatters into the trajectory, the sigmoid, ``skip_scan``, the index update -- as the torch ops
+of ``_hop``; ``"native"`` runs the whole hop as ONE library call (``Pips.chain_hop`` = ``pips_chain_hop``: the same bookkeeping
+as HIP kernels around the same tracker launches, state held as int32) and reads the live count back, one host sync per hop
+either way.  Both engines give the same hops and the same bits.
 """
 from __future__ import annotations
 
@@ -86,7 +92,50 @@ def _hop(model, cache, trajs, vis_p, base, cur, active, feat, d=None, iters=6):
     return c + (si if d is None else si * d), si, ffeat[0]
 
 
-def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
+ENGINES = ("torch", "native")
+
+
+def _check_engine(engine):
+    if engine not in ENGINES:
+        raise ValueError(f"engine must be one of {ENGINES}, not {engine!r}")
+
+
+def _chain_native(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, want_log=True):
+    """``_chain`` with every hop as one ``pips_chain_hop`` call: the state (window starts, directions, the two ping-pong
+    lists of active particles) is int32 on the device and the loop reads the live count where ``_chain`` reads it."""
+    dev = xy.device
+    pad = 7
+    n = xy.shape[0]
+    i32 = torch.int32
+    trajs = torch.zeros(T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
+    vis_p = torch.zeros(T + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
+    trajs[f0 + pad, torch.arange(n, device=dev)] = xy.to(torch.float32)
+    cur = f0.to(i32).contiguous()
+    d32 = None if dirs is None else dirs.to(i32).contiguous()
+    feat = torch.empty(n, 128, dtype=torch.float32, device=dev)                  # written by the first hop (sample_feat)
+    active, nxt = torch.arange(n, dtype=i32, device=dev), torch.empty(n, dtype=i32, device=dev)
+    count = torch.zeros(1, dtype=i32, device=dev)
+    steps = torch.empty(n, dtype=i32, device=dev) if want_log else None
+    log, n_act, first = [], n, True
+    while n_act > 0:
+        model.chain_hop(cache, active, n_act, trajs, vis_p, pad, cur, d32, feat, nxt, count, steps, iters=iters, sample_feat=first)
+        if want_log:
+            log.append((active[:n_act].clone(), steps[:n_act].clone()))
+        n_act = int(count.item())                                                 # (one host sync per hop: the live count)
+        active, nxt, first = nxt, active, False
+    return trajs[pad:pad + T], None if vis_p is None else vis_p[pad:pad + T], log
+
+
+def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, engine="torch", want_log=True):
+    """The hop loop on the chosen engine -> (trajs, vis, hop log).  ``want_log=False`` spares the native engine the two copies
+    per hop that keep ``active`` / ``steps`` for the log (its buffers are reused by the next hop) and its log comes back
+    empty; the torch engine's log is made of the tensors the hop produced anyway, so it is returned either way."""
+    if engine == "native":
+        return _chain_native(model, cache, T, xy, f0, dirs, iters, with_vis, want_log)
+    return _chain_torch(model, cache, T, xy, f0, dirs, iters, with_vis)
+
+
+def _chain_torch(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
     """The hop loop of chain_demo.py:40-83 for all particles at once.  xy (n,2) px at frames f0 (n,) int64; dirs (n,) +1 / -1
     per particle or None (all forward).  A backward particle runs the loop on the time-reversed video: its window rows
     read f, f-1, ... (``Pips.track``'s ``win_dir``) and it is finished when its start passes frame 0.
@@ -124,17 +173,18 @@ def _hops(log, n):
 
 
 @torch.no_grad()
-def track_chained(model, rgbs, xy0, iters=6, return_hops=False):
+def track_chained(model, rgbs, xy0, iters=6, return_hops=False, engine="torch"):
     """rgbs (1,T,3,H,W), xy0 (1,N,2) px at frame 0 -> trajs_e (1,T,N,2) (chain_demo.run_model).
     ``return_hops=True``: also the list, per particle, of the frame steps ``si`` its windows advanced by
-    (chain_demo.py:63-79) -- what a parity test compares hop for hop."""
+    (chain_demo.py:63-79) -- what a parity test compares hop for hop.  ``engine``: see the module docstring."""
+    _check_engine(engine)
     assert rgbs.shape[0] == 1, "the reference chains one video at a time (chain_demo.py:24)"
     assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
     dev = rgbs.device
     T, N = rgbs.shape[1], xy0.shape[1]
     cache = model.encode(rgbs)
     trajs, _, log = _chain(model, cache, T, xy0[0].to(dev), torch.zeros(N, dtype=torch.int64, device=dev), iters=iters,
-                           with_vis=False)
+                           with_vis=False, engine=engine, want_log=return_hops)
     out = trajs.unsqueeze(0).contiguous()
     if not return_hops:
         return out
@@ -155,7 +205,7 @@ def _query_frames(queries, T=None):
 
 
 @torch.no_grad()
-def track_queries(model, rgbs, queries, iters=6, return_hops=False):
+def track_queries(model, rgbs, queries, iters=6, return_hops=False, engine="torch"):
     """Track query points from any frame over the whole video, forwards and backwards in time.
 
     rgbs (1,T,3,H,W), queries (1,N,3) = (t, x, y): ``t`` an integer frame index, ``x, y`` in pixels -- PIPs' xy order, not
@@ -166,7 +216,8 @@ def track_queries(model, rgbs, queries, iters=6, return_hops=False):
     that wrote a frame gives its position and visibility.  The video is encoded once; every query is a forward particle,
     plus a backward one when t_q > 0, and all of them advance together, one ``model.track`` call per hop.
     ``return_hops=True``: also ``(forward, backward)``, per query the frame steps of each chain's windows (backward: [] when
-    t_q = 0)."""
+    t_q = 0).  ``engine``: see the module docstring."""
+    _check_engine(engine)
     assert rgbs.shape[0] == 1 and queries.shape[0] == 1, "one video at a time, as track_chained"
     assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
     dev = rgbs.device
@@ -179,7 +230,7 @@ def track_queries(model, rgbs, queries, iters=6, return_hops=False):
     f0 = torch.cat([tq_d, tq_d[back_d]])
     dirs = torch.cat([torch.ones(N, dtype=torch.int64, device=dev), torch.full((nb,), -1, dtype=torch.int64, device=dev)])
     cache = model.encode(rgbs)
-    tr, vi, log = _chain(model, cache, T, torch.cat([xy, xy[back_d]]), f0, dirs, iters=iters)
+    tr, vi, log = _chain(model, cache, T, torch.cat([xy, xy[back_d]]), f0, dirs, iters=iters, engine=engine, want_log=return_hops)
     trajs, vis = tr[:, :N].clone(), vi[:, :N].clone()
     before = torch.arange(T, device=dev).unsqueeze(1) < tq_d[back_d].unsqueeze(0)     # (T,nb): frames of the backward chain
     trajs[:, back_d] = torch.where(before.unsqueeze(-1), tr[:, N:], trajs[:, back_d])
@@ -208,11 +259,15 @@ class StreamTracker:
     call over every ready particle, new ones joining with their first-window features (the same point sample as
     ``feat_init=None``).  A frame is final when it lies below every unfinished particle's window start.  ``push`` splits
     a chunk so that no slot is overwritten while a pending window can still read it: ``slots >= 9`` keeps the 8 frames of
-    a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query."""
+    a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query.
+    ``engine="native"``: each round's hop is one ``pips_chain_hop`` call (window starts held as int32); which particles are ready
+    and which are finished stays decided here."""
 
     S = 8
 
-    def __init__(self, model, queries, iters=6, slots=24, record_hops=False):
+    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch"):
+        _check_engine(engine)
+        self.engine = engine
         assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
         if int(slots) < self.S + 1:
             raise ValueError(f"slots must be at least {self.S + 1} (one window and a new frame), not {slots}")
@@ -235,6 +290,11 @@ class StreamTracker:
         self.tq = self.tq_host.to(dev)
         self.xy = self.xy_in.to(dev, torch.float32)
         self.cur = self.tq.clone()                                                # window start (= t_q until it joins)
+        if self.engine == "native":                                               # pips_chain_hop's state
+            self.cur = self.cur.to(torch.int32)
+            self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.next_active = torch.empty(self.N, dtype=torch.int32, device=dev)
+            self.steps = torch.empty(self.N, dtype=torch.int32, device=dev)
         self.joined = torch.zeros(self.N, dtype=torch.bool, device=dev)
         self.done = torch.zeros(self.N, dtype=torch.bool, device=dev)
         self.feat = None                                                          # (N,128) features of the first windows
@@ -298,8 +358,14 @@ class StreamTracker:
                     self.feat = ff.new_zeros(self.N, ff.shape[-1])
                 self.feat[new] = ff[0]
                 self.joined[new] = True
-            c, si, _ = _hop(self.model, self.cache, self.trajs, self.vis, 0, self.cur, active, self.feat, None, self.iters)
-            self.cur[active] = c
+            if self.engine == "native":
+                act = active.to(torch.int32)
+                self.model.chain_hop(self.cache, act, act.numel(), self.trajs, self.vis, 0, self.cur, None, self.feat,
+                                     self.next_active, self.count, self.steps, iters=self.iters)
+                c, si = self.cur[active], self.steps[:act.numel()]
+            else:
+                c, si, _ = _hop(self.model, self.cache, self.trajs, self.vis, 0, self.cur, active, self.feat, None, self.iters)
+                self.cur[active] = c
             if final:
                 self.done[active] = c >= T
             if self.hops is not None:
@@ -328,10 +394,10 @@ class StreamTracker:
 
 
 @torch.no_grad()
-def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False):
+def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, engine="torch"):
     """``StreamTracker`` over an iterable of ``(1,k,3,H,W)`` chunks -> trajs_e (1,T,N,2) px and vis_e (1,T,N) logits, NaN
     before each query's frame.  ``return_hops=True``: also, per query, the frame steps of its windows."""
-    st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=return_hops)
+    st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=return_hops, engine=engine)
     parts = [st.push(c) for c in chunks]
     parts.append(st.finish())
     trajs = torch.cat([p[1] for p in parts], dim=1)

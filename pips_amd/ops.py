@@ -262,6 +262,61 @@ def state_update(arena, delta, ffeats, coords, coords0, B, N, stride, want_vis=F
     return traj, vis
 
 
+def chain_thresholds() -> torch.Tensor:
+    """The 64 thresholds of the library's skip scan (pips_chain_threshold; host function) as a float32 CPU tensor."""
+    lib = _lib.load()
+    return torch.tensor([lib.pips_chain_threshold(k) for k in range(64)], dtype=torch.float32)
+
+
+def _i32(t):
+    assert t is None or (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()), "chaining state is contiguous int32 on the GPU"
+    return _lib.ptr(t)
+
+
+def _chain_f32(t):
+    assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()), "chaining state is contiguous float32 on the GPU"
+    return _lib.ptr(t)
+
+
+def chain_gather(trajs, base, cur, dirs, feat, active, n_act, sample_feat=False):
+    """pips_chain_gather: the staging arrays of one hop for ``active[:n_act]`` -> (xy (n_act,2), ws, wd (n_act) int32,
+    fi (n_act,128); fi is left unwritten with ``sample_feat``).  trajs (L,n,2); cur / dirs / active int32, dirs may be None."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    dev = trajs.device
+    xy = torch.empty(n_act, 2, dtype=torch.float32, device=dev)
+    ws = torch.empty(n_act, dtype=torch.int32, device=dev)
+    wd = torch.empty(n_act, dtype=torch.int32, device=dev)
+    fi = torch.empty(n_act, LATENT, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _call("pips_chain_gather", _chain_f32(trajs), L, int(base), n, _i32(cur), _i32(dirs), _chain_f32(feat), _i32(active), int(n_act),
+              int(bool(sample_feat)), _lib.ptr(xy), _lib.ptr(ws), _lib.ptr(wd), _lib.ptr(fi), _stream())
+    return xy, ws, wd, fi
+
+
+def chain_step(win_trajs, win_vis, win_ffeat0, T, active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count,
+               steps=None, sample_feat=False):
+    """pips_chain_step, in place on the caller's state: write-back of the windows win_trajs (8,n_act,2) / win_vis (8,n_act),
+    skip scan, ``cur`` (and, with ``sample_feat``, ``feat`` from win_ffeat0 (n_act,128)) update, and the live members of
+    ``active[:n_act]`` in their order in ``next_active`` with their number in ``next_count`` (device int32, not read back here)."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    with torch.cuda.device(trajs.device):
+        _call("pips_chain_step", _chain_f32(win_trajs), _chain_f32(win_vis), _chain_f32(win_ffeat0), int(T), n, _i32(active), int(n_act),
+              int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L, int(base), _i32(cur), _i32(dirs), _chain_f32(feat),
+              _i32(next_active), _i32(next_count), _i32(steps), _stream())
+
+
+def chain_hop(arena, pyr, T, R, H8, W8, times, stride, iters, flags, active, n_act, trajs, vis, base, cur, dirs, feat,
+              next_active, next_count, steps, workspace, sample_feat=False):
+    """pips_chain_hop: one hop of chain_demo.py:40-83 for ``active[:n_act]``, in place on the caller's state (see chain_step),
+    on the packed pyramid ``pyr`` of R frame slots holding T logical frames.  No host synchronisation."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    with torch.cuda.device(trajs.device):
+        _call("pips_chain_hop", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
+              int(iters), int(flags), n, _i32(active), int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L,
+              int(base), _i32(cur), _i32(dirs), _chain_f32(feat), _i32(next_active), _i32(next_count), _i32(steps),
+              _lib.ptr(workspace), workspace.numel() * 4, _stream())
+
+
 def gemm(A, W, bias=None, epi=0, R=None):
     """C = epi(A @ W.T + bias).  epi: 0 none, 1 GELU, 2 + R."""
     A, W = _f32(A), _f32(W)

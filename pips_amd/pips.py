@@ -367,9 +367,7 @@ class Pips(nn.Module):
             assert tuple(wd_i.shape) == (B, N)
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
-            fl = self._flags()
-            if cache.bf16_maps and (fl & ops.FLAG_BF16_MIXER) and not (fl & ops.FLAG_SPLIT_BF16):
-                fl |= ops.FLAG_BF16_MAPS        # bf16 mixer on maps of the bf16 encoder -> the gather reads their bf16 mirror
+            fl = self._track_flags(cache)
             nb = lib.pips_track_workspace_bytes_s(B, N, S)
             # ONE tracker workspace per (device, stream), grown on demand: chained tracking calls this with
             # a different (shrinking) N at every hop
@@ -391,6 +389,35 @@ class Pips(nn.Module):
         if return_feat:
             return preds, preds2, vis_e, ffeat, None
         return preds, preds2, vis_e, None
+
+    def _track_flags(self, cache):
+        fl = self._flags()
+        if cache.bf16_maps and (fl & ops.FLAG_BF16_MIXER) and not (fl & ops.FLAG_SPLIT_BF16):
+            fl |= ops.FLAG_BF16_MAPS        # bf16 mixer on maps of the bf16 encoder -> the gather reads their bf16 mirror
+        return fl
+
+    @torch.no_grad()
+    def chain_hop(self, cache: FeatureCache, active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps=None,
+                  iters=6, sample_feat=False):
+        """One hop of the visibility-aware chaining (chain_demo.py:40-83) for the particles ``active[:n_act]``, in one library
+        call (``pips_chain_hop``): what ``track`` plus the driver's indexed reads, scatters and skip scan do, in place on the
+        caller's device state -- trajs (L,n,2) and vis (L,n) or None (frame f in row (f + base) % L), cur / dirs (None: all
+        forward) / active int32, feat (n,128); the live particles land in ``next_active`` in their order and their number in
+        ``next_count`` (device int32: the caller reads it back), the steps in ``steps``.  S = 8 and one video (B = 1) only."""
+        assert self.S == 8 and cache.B == 1, "the reference chains 8-frame windows of one video (chain_demo.py:24,63-77)"
+        dev = cache.pyr.device
+        H8, W8 = cache.map_size
+        with torch.cuda.device(dev):
+            arena, times = self._aux(dev)
+            nb = _lib.load().pips_chain_workspace_bytes(int(n_act), int(iters))
+            key = ("chain", str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
+            with self._lock:
+                ws = self._ws.get(key)
+                if ws is None or ws.numel() * 4 < nb:           # grown on demand: n_act shrinks from hop to hop
+                    ws = self._ws[key] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+            ops.chain_hop(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache),
+                          active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps, ws,
+                          sample_feat=sample_feat)
 
 
 def _masked_mean(x, mask):
