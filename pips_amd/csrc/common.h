@@ -178,6 +178,9 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // getenv, no mutable state reachable from the drop-in.  `python -m pips_amd._build --tuning` builds libpips_hip_tune.so
 // (load it through PIPS_LIB_PATH) in which every hook is read from the environment ONCE per call site, in a C++11
 // function-local static initialiser (thread-safe).  The A/B numbers quoted in DESIGN.md come from that build.
+// A kernel that only a hook can select exists only in a tuning build: a table of hook-selected instantiations (the forced tiles of
+// gemm.hip / gemm_x3.hip) is compiled under #ifdef PIPS_TUNING, since naming an instantiation emits its kernel whether or not the
+// folded default can reach it.  Hooks that choose among kernels the product launches anyway need no #ifdef.
 #ifdef PIPS_TUNING
 int tune_env(const char* name, int dflt);
 #define PIPS_TUNE(name, dflt) ([]() -> int { static const int v__ = ::pips::tune_env(name, dflt); return v__; }())

@@ -18,6 +18,7 @@
 // ds_read_b128 per operand feeds four MFMAs.  Two LDS stages, one barrier per K block:
 //   global(kb+1) -> registers  ||  MFMA on stage kb&1 ;  registers -> stage (kb+1)&1.
 #include "common.h"
+#include "gemm_launch.h"
 
 #include <cstdlib>
 
@@ -404,8 +405,8 @@ extern "C" int pips_trace_read(void* host, size_t bytes) {
 // the rows; convolutions: no effect at 8 x 368x496, 32 x 720x1280 (fp32) or 64 x 368x496 (bf16 maps).  So: plain GEMMs whose
 // wide operand exceeds the Infinity Cache.  PIPS_GEMM_SWZ (tuning builds): 0 off, 1 on wherever there are >= 64 tiles.
 static int swizzle_on(bool conv, long tiles, const GemmArgs& a) {
-    const int force = PIPS_TUNE("PIPS_GEMM_SWZ", -1);
-    if (force >= 0) return force != 0 && tiles >= 64;
+    const int forced = swizzle_forced(PIPS_TUNE("PIPS_GEMM_SWZ", -1), tiles);
+    if (forced >= 0) return forced;
     return !conv && (long long)a.M * (a.N > a.K ? a.N : a.K) * 4 > (256ll << 20);
 }
 
@@ -414,50 +415,29 @@ static int launch_tile(const GemmArgs& a_in, int frames, hipStream_t st) {
     static_assert(!CONV || KS == 1, "conv statistics assume KS == 1");
     GemmArgs a = a_in;
     dim3 grid(cdiv(a.M, BM), cdiv(a.N, BN), frames);
-    dim3 block(WGM * WGN * KS * 64);
     a.swz = swizzle_on(CONV, (long)grid.x * grid.y * grid.z, a);
-    size_t lds = (size_t)2 * (BM + BN) * (32 * KS + 4) * sizeof(float);
-    auto kern = igemm_f32_kernel<BM, BN, WGM, WGN, KS, CONV>;
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> raised{0};      // per instantiation, one bit per device
-        const int rc = ensure_dynamic_lds(raised, (const void*)kern, lds);
-        if (rc != PIPS_OK) return rc;
-    }
 #ifdef PIPS_GEMM_TRACE
     a.trace = trace_buffer();
 #endif
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    PIPS_CHECK_LAUNCH("igemm_f32_kernel");
-    return PIPS_OK;
-}
-
-// Debug/tuning hooks: PIPS_GEMM_TILE=<id> forces one tile configuration for plain GEMMs;
-// PIPS_GEMM_TILE_UP / PIPS_GEMM_TILE_DOWN do so only for N > K / N < K (the mixer's up- and
-// down-projections), for in-situ A/B runs of tools/mixer_bench.py.
-static int forced_tile(const GemmArgs& a) {
-    const int all = PIPS_TUNE("PIPS_GEMM_TILE", -1), up = PIPS_TUNE("PIPS_GEMM_TILE_UP", -1),
-              down = PIPS_TUNE("PIPS_GEMM_TILE_DOWN", -1);
-    (void)up; (void)down;
-    if (all >= 0) return all;
-    if (a.N > a.K && up >= 0) return up;
-    if (a.N < a.K && down >= 0) return down;
-    return -1;
+    return launch_tiles<igemm_f32_kernel<BM, BN, WGM, WGN, KS, CONV>>("igemm_f32_kernel", grid, dim3(WGM * WGN * KS * 64),
+                                                                   (size_t)2 * (BM + BN) * (32 * KS + 4) * sizeof(float), a, st);
 }
 
 int launch_gemm(const GemmArgs& a, hipStream_t st) {
-    PIPS_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem");
-    PIPS_CHECK_ARG(a.K % 32 == 0, "gemm: K=%d must be a multiple of 32", a.K);
-    PIPS_CHECK_ARG((a.lda % 4) == 0, "gemm: lda must be a multiple of 4 floats");
-    PIPS_CHECK_ARG((unsigned long long)a.M * (unsigned long long)a.lda < (1ull << 32) &&
-                       (unsigned long long)a.N * (unsigned long long)a.K < (1ull << 32),
-                   "gemm: operand exceeds 2^32 elements");
+    if (const int rc = check_gemm_operands(a, "gemm", 4)) return rc;
     const bool k64 = a.K % 64 == 0;
-    if (forced_tile(a) < 0) {                              // the four-wave assembly kernels of gemm_f32_t4.hip (up- / down-projection forms)
+    int forced = -1;
+#ifdef PIPS_TUNING
+    // PIPS_GEMM_TILE=<id> forces one tile configuration for plain GEMMs, PIPS_GEMM_TILE_UP / _DOWN for N > K / N < K only
+    forced = forced_tile(PIPS_TUNE("PIPS_GEMM_TILE", -1), PIPS_TUNE("PIPS_GEMM_TILE_UP", -1), PIPS_TUNE("PIPS_GEMM_TILE_DOWN", -1), a);
+#endif
+    if (forced < 0) {                                      // the four-wave assembly kernels of gemm_f32_t4.hip (up- / down-projection forms)
         int tpb = 1;
         const int route = gemm_f32_t4_route(a, &tpb);
         if (route) return launch_gemm_f32_t4(a, route, tpb, st);
     }
-    switch (forced_tile(a)) {
+#ifdef PIPS_TUNING       // tiles that only a hook selects exist only in a tuning build (common.h)
+    switch (forced) {
         case 0: return launch_tile<128, 128, 2, 2, 1, false>(a, 1, st);
         case 1: return launch_tile<128, 64, 2, 2, 1, false>(a, 1, st);
         case 2: return launch_tile<64, 128, 2, 2, 1, false>(a, 1, st);
@@ -471,6 +451,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t st) {
         case 10: return launch_tile<256, 128, 4, 2, 1, false>(a, 1, st);   // down-proj: within 0.5 % of KS=2
         default: break;
     }
+#endif
     // Measured on MI355X (tools/gemm_bench.py): with >= ~2 blocks per CU of 128x128 the big
     // tile wins (90-105 TF at M=16384); the M=2048 mixer GEMMs are prologue/epilogue bound
     // and want many small blocks (64x64: 86 TF at N=2048) or, when even 64x64 gives only one

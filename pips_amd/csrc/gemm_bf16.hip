@@ -11,6 +11,7 @@
 // (lane -> row lane&31, 16 bytes at 32*kk + 16*(lane>>5)) carry over unchanged: per MFMA a lane
 // supplies 8 consecutive K values.
 #include "common.h"
+#include "gemm_launch.h"
 
 #include <cstdlib>
 
@@ -334,29 +335,16 @@ __global__ __launch_bounds__(WGM * WGN * KS * 64, (BM * BN >= 128 * 128 && WGM *
     }
 }
 
-// XCD-aware tile order (common.h).  PIPS_BF16_SWZ (tuning builds): 0 off, 1 on from 64 tiles; default -1 = by kind and size.
-static int bf16_swizzle_on(bool conv, long tiles) {
-    const int force = PIPS_TUNE("PIPS_BF16_SWZ", -1);
-    if (force >= 0) return force != 0 && tiles >= 64;
-    return 0;
-}
+// XCD-aware tile order (common.h): off.  PIPS_BF16_SWZ (tuning builds): 0 off, 1 on from 64 tiles.
+static int bf16_swizzle_on(long tiles) { return swizzle_forced(PIPS_TUNE("PIPS_BF16_SWZ", -1), tiles) > 0; }
 
 template <int BM, int BN, int WGM, int WGN, int KS, bool A_BF16, bool OUT_BF16, int BKE = 64>
 static int launch_bf16_tile(const GemmArgs& a_in, hipStream_t st) {
     GemmArgs a = a_in;
     dim3 grid(cdiv(a.M, BM), cdiv(a.N, BN), 1);
-    a.swz = bf16_swizzle_on(false, (long)grid.x * grid.y);
-    dim3 block(WGM * WGN * KS * 64);
-    const size_t lds = (size_t)2 * (BM + BN) * (BKE * KS * 2 + 16);
-    auto kern = gemm_bf16_kernel<BM, BN, WGM, WGN, KS, A_BF16, OUT_BF16, BKE>;
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> raised{0};      // per instantiation, one bit per device
-        const int rc = ensure_dynamic_lds(raised, (const void*)kern, lds);
-        if (rc != PIPS_OK) return rc;
-    }
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    PIPS_CHECK_LAUNCH("gemm_bf16_kernel");
-    return PIPS_OK;
+    a.swz = bf16_swizzle_on((long)grid.x * grid.y);
+    return launch_tiles<gemm_bf16_kernel<BM, BN, WGM, WGN, KS, A_BF16, OUT_BF16, BKE>>(
+        "gemm_bf16_kernel", grid, dim3(WGM * WGN * KS * 64), (size_t)2 * (BM + BN) * (BKE * KS * 2 + 16), a, st);
 }
 
 template <bool A_BF16, bool OUT_BF16>
@@ -386,12 +374,9 @@ template <int BM, int BN, int BKE, bool A_BF16, bool OUT_BF16>
 static int launch_conv_tile_t(const GemmArgs& a_in, int frames, hipStream_t st) {
     GemmArgs a = a_in;
     dim3 grid(cdiv(a.M, BM), cdiv(a.N, BN), frames);
-    a.swz = bf16_swizzle_on(true, (long)grid.x * grid.y * grid.z);
-    const size_t lds = (size_t)2 * (BM + BN) * (BKE * 2 + 16);
-    auto kern = gemm_bf16_kernel<BM, BN, 2, 2, 1, A_BF16, OUT_BF16, BKE, true>;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-    PIPS_CHECK_LAUNCH("gemm_bf16_kernel<conv>");
-    return PIPS_OK;
+    a.swz = bf16_swizzle_on((long)grid.x * grid.y * grid.z);
+    return launch_tiles<gemm_bf16_kernel<BM, BN, 2, 2, 1, A_BF16, OUT_BF16, BKE, true>>(
+        "gemm_bf16_kernel<conv>", grid, dim3(256), (size_t)2 * (BM + BN) * (BKE * 2 + 16), a, st);
 }
 // map types: 0 = fp32 in / fp32 out (pips_conv_nhwc_bf16), 1 = bf16 in / bf16 out, 2 = bf16 in / fp32 out (conv3 -> pyramid)
 template <int BM, int BN, int BKE>
@@ -434,12 +419,8 @@ int launch_conv_bf16(const GemmArgs& a, int frames, int* tiles_m, hipStream_t st
 
 // A: fp32 [M][lda] (a_bf16 = 0) or bf16 [M][lda]; W: bf16 [N][K]; C: fp32 or bf16 [M][ldc]
 int launch_gemm_bf16(const GemmArgs& a, int a_bf16, int out_bf16, hipStream_t st) {
-    PIPS_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0, "gemm_bf16: empty problem");
-    PIPS_CHECK_ARG(a.K % 32 == 0, "gemm_bf16: K=%d must be a multiple of 32", a.K);
-    PIPS_CHECK_ARG(a.N % 4 == 0 && a.ldc % 4 == 0 && a.lda % 8 == 0, "gemm_bf16: N, ldc %% 4 and lda %% 8 required");
-    PIPS_CHECK_ARG((unsigned long long)a.M * (unsigned long long)a.lda < (1ull << 32) &&
-                       (unsigned long long)a.N * (unsigned long long)a.K < (1ull << 32),
-                   "gemm_bf16: operand exceeds 2^32 elements");
+    if (const int rc = check_gemm_operands(a, "gemm_bf16", 8)) return rc;
+    PIPS_CHECK_ARG(a.N % 4 == 0 && a.ldc % 4 == 0, "gemm_bf16: N, ldc %% 4 required");
     // a bf16 residual exists only beside a bf16 output of the residual epilogue: anything else would read a bf16 R as fp32
     PIPS_CHECK_ARG(!(a.epi & EPI_RES_BF16) || (out_bf16 && (a.epi & 0xff) == EPI_RESIDUAL),
                    "gemm_bf16: PIPS_EPI_RES_BF16 needs out_bf16 and the residual epilogue (epi = PIPS_EPI_RESIDUAL | PIPS_EPI_RES_BF16)");

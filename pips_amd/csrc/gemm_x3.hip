@@ -18,6 +18,7 @@
 // bound).  Measured (PMC): the bf16 matrix pipe is ~30 % busy -- the global -> VGPR -> LDS staging
 // does not hide behind the MFMAs of a wave that is alone on its SIMD.
 #include "gemm_tail.h"
+#include "gemm_launch.h"
 
 #include <cstdlib>
 
@@ -343,44 +344,19 @@ template <int BM, int BN, int WGM, int WGN, int KS, bool CONV, int BKE = 32>
 static int launch_x3_tile(const GemmArgs& a_in, int frames, hipStream_t st) {
     GemmArgs a = a_in;
     dim3 grid(cdiv(a.M, BM), cdiv(a.N, BN), frames);
-    {   // XCD-aware tile order (common.h).  PIPS_X3_SWZ (tuning builds): 0 off, 1 on from 64 tiles; default -1 = by kind and size
-        const int force = PIPS_TUNE("PIPS_X3_SWZ", -1);
-        const long tiles = (long)grid.x * grid.y * grid.z;
-        a.swz = force >= 0 ? (force != 0 && tiles >= 64) : 0;
-    }
-    dim3 block(WGM * WGN * KS * 64);
-    const size_t lds = (size_t)2 * 3 * (BM + BN) * (BKE * KS * 2);
-    auto kern = gemm_x3_kernel<BM, BN, WGM, WGN, KS, CONV, BKE>;
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> raised{0};      // per instantiation, one bit per device
-        const int rc = ensure_dynamic_lds(raised, (const void*)kern, lds);
-        if (rc != PIPS_OK) return rc;
-    }
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-    PIPS_CHECK_LAUNCH("gemm_x3_kernel");
-    return PIPS_OK;
-}
-
-// tuning hooks: PIPS_X3_TILE=<id> for every GEMM, PIPS_X3_TILE_UP / _DOWN for N > K / N < K only
-static int x3_forced_tile(const GemmArgs& a) {
-    const int all = PIPS_TUNE("PIPS_X3_TILE", -1), up = PIPS_TUNE("PIPS_X3_TILE_UP", -1),
-              down = PIPS_TUNE("PIPS_X3_TILE_DOWN", -1);
-    (void)up; (void)down;
-    if (all >= 0) return all;
-    if (a.N > a.K && up >= 0) return up;
-    if (a.N < a.K && down >= 0) return down;
-    return -1;
+    // XCD-aware tile order (common.h): off.  PIPS_X3_SWZ (tuning builds): 0 off, 1 on from 64 tiles
+    a.swz = swizzle_forced(PIPS_TUNE("PIPS_X3_SWZ", -1), (long)grid.x * grid.y * grid.z) > 0;
+    return launch_tiles<gemm_x3_kernel<BM, BN, WGM, WGN, KS, CONV, BKE>>("gemm_x3_kernel", grid, dim3(WGM * WGN * KS * 64),
+                                                                       (size_t)2 * 3 * (BM + BN) * (BKE * KS * 2), a, st);
 }
 
 // A fp32 [M][lda]; W: split planes [3][N][K] bf16; C fp32 [M][ldc]
 int launch_gemm_x3(const GemmArgs& a, hipStream_t st) {
-    PIPS_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0, "gemm_x3: empty problem");
-    PIPS_CHECK_ARG(a.K % 32 == 0 && a.lda % 4 == 0, "gemm_x3: K %% 32 and lda %% 4 required");
-    PIPS_CHECK_ARG((unsigned long long)a.M * (unsigned long long)a.lda < (1ull << 32) &&
-                       (unsigned long long)a.N * (unsigned long long)a.K < (1ull << 32),
-                   "gemm_x3: operand exceeds 2^32 elements");
+    if (const int rc = check_gemm_operands(a, "gemm_x3", 4)) return rc;
     const bool k64 = a.K % 64 == 0;
-    switch (x3_forced_tile(a)) {
+#ifdef PIPS_TUNING       // tiles that only a hook selects exist only in a tuning build (common.h)
+    // PIPS_X3_TILE=<id> for every GEMM, PIPS_X3_TILE_UP / _DOWN for N > K / N < K only
+    switch (forced_tile(PIPS_TUNE("PIPS_X3_TILE", -1), PIPS_TUNE("PIPS_X3_TILE_UP", -1), PIPS_TUNE("PIPS_X3_TILE_DOWN", -1), a)) {
         case 0: return launch_x3_tile<128, 128, 2, 2, 1, false>(a, 1, st);
         case 1: return launch_x3_tile<128, 64, 2, 2, 1, false>(a, 1, st);
         case 2: return launch_x3_tile<64, 128, 2, 2, 1, false>(a, 1, st);
@@ -391,6 +367,7 @@ int launch_gemm_x3(const GemmArgs& a, hipStream_t st) {
         case 9: return launch_x3_tile<128, 256, 2, 4, 1, false>(a, 1, st);
         default: break;
     }
+#endif
     const long b128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
     // one tile per CU or more of 256x128 (8 waves of 64x64, 25 % fewer staged bytes per MFMA): measured
     // 233 -> 194 us (up-projection) and 204 -> 172 us (down-projection) at M = 16384

@@ -118,6 +118,34 @@ struct LevelTable {
     int H[PIPS_LEVELS], W[PIPS_LEVELS];
 };
 
+// Where the 8x8 pixel window of a level lies: east / south weights (wx, wy) of the 49 taps and the window's first pixel (bx, by).
+__device__ __forceinline__ void level_sample_geometry(float cxm, float cym, int lvl, int H, int W, float& wx, float& wy, int& bx, int& by) {
+    const float inv = 1.0f / (float)(1 << lvl);
+    const float cx = cxm * inv, cy = cym * inv;        // coords / 2**i  (:373)
+    // bilinear_sampler normalisation (:318-319) and grid_sample's un-normalisation
+    // (align_corners=True, CPU form (g+1)*((size-1)/2)), reproduced op by op
+    const float gx = __fsub_rn(__fdiv_rn(2.0f * cx, (float)(W - 1)), 1.0f);
+    const float gy = __fsub_rn(__fdiv_rn(2.0f * cy, (float)(H - 1)), 1.0f);
+    const float ix = __fmul_rn(__fadd_rn(gx, 1.0f), (float)(W - 1) / 2.0f);
+    const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), (float)(H - 1) / 2.0f);
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    wx = ix - fx0, wy = iy - fy0;                      // east / south weights
+    bx = (int)fx0 - PIPS_RADIUS, by = (int)fy0 - PIPS_RADIUS;
+}
+
+// One step of the transpose-reduce of v[] over the lanes that differ in bit O: lane r ends with the sum of v[r]
+// (a macro instance per step: a two-variable loop here was left rolled by hipcc and
+// v[] became a 4000-instruction compare/select emulation of dynamic register indexing)
+#define PIPS_TR_STEP(O, NH)                                                \
+    {                                                                      \
+        const bool up = (lane & (O)) != 0;                                 \
+        _Pragma("unroll") for (int k = 0; k < (NH); ++k) {                 \
+            const float send = up ? v[k] : v[k + (NH)];                    \
+            const float keep = up ? v[k + (NH)] : v[k];                    \
+            v[k] = keep + __shfl_xor(send, (O));                           \
+        }                                                                  \
+    }
+
 // waves_per_eu(2,4): let the compiler spend up to 128 VGPRs so 16 x 1 KiB loads stay in flight per
 // wave (left alone it squeezes into 64 VGPRs for 8 waves/SIMD and issues the loads two at a time)
 // SCT: window length (mixer rows per particle) as a compile-time constant, 0 = the run-time argument Srt (Pips(S != 8))
@@ -157,17 +185,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     // ---- correlation window of this wave's level
     {
         const int H = lv.H[lvl], W = lv.W[lvl];
-        const float inv = 1.0f / (float)(1 << lvl);
-        const float cx = cxm * inv, cy = cym * inv;        // coords / 2**i  (:373)
-        // bilinear_sampler normalisation (:318-319) and grid_sample's un-normalisation
-        // (align_corners=True, CPU form (g+1)*((size-1)/2)), reproduced op by op
-        const float gx = __fsub_rn(__fdiv_rn(2.0f * cx, (float)(W - 1)), 1.0f);
-        const float gy = __fsub_rn(__fdiv_rn(2.0f * cy, (float)(H - 1)), 1.0f);
-        const float ix = __fmul_rn(__fadd_rn(gx, 1.0f), (float)(W - 1) / 2.0f);
-        const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), (float)(H - 1) / 2.0f);
-        const float fx0 = floorf(ix), fy0 = floorf(iy);
-        const float wx = ix - fx0, wy = iy - fy0;          // east / south weights
-        const int bx = (int)fx0 - PIPS_RADIUS, by = (int)fy0 - PIPS_RADIUS;
+        float wx, wy;
+        int bx, by;
+        level_sample_geometry(cxm, cym, lvl, H, W, wx, wy, bx, by);
 
         const int hsel = lane >> 5, c4 = lane & 31;
         const float4 f4 = *reinterpret_cast<const float4*>(ff + c4 * 4);
@@ -199,20 +219,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
                 v[hb * 16 + e] = ok[e] ? d : 0.f;
             }
         }
-        // transpose-reduce over the 32 lanes of each half: lane r ends with sum of v[r]
-        // (one macro instance per level: a two-variable loop here was left rolled by hipcc and
-        // v[] became a 4000-instruction compare/select emulation of dynamic register indexing)
-#define PIPS_TR_STEP(O, NH)                                                    \
-        {                                                                      \
-            const bool up = (lane & (O)) != 0;                                 \
-            _Pragma("unroll") for (int k = 0; k < (NH); ++k) {                 \
-                const float send = up ? v[k] : v[k + (NH)];                    \
-                const float keep = up ? v[k + (NH)] : v[k];                    \
-                v[k] = keep + __shfl_xor(send, (O));                           \
-            }                                                                  \
-        }
+        // transpose-reduce over the 32 lanes of each half
         PIPS_TR_STEP(16, 16) PIPS_TR_STEP(8, 8) PIPS_TR_STEP(4, 4) PIPS_TR_STEP(2, 2) PIPS_TR_STEP(1, 1)
-#undef PIPS_TR_STEP
         // lane (hsel, r=c4): window row j = r>>2, column 2*(r&3) + hsel
         const float scale = sqrtf((float)C);
         Dw[lvl][(c4 >> 2) * 8 + 2 * (c4 & 3) + hsel] = v[0] / scale;     // corrs / sqrt(C) (:397)
@@ -258,6 +266,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 // BASELINE configs[2]); with 8 channels per lane a wave load covers FOUR pixels, 16 loads per level instead of 32.
 // Lane = (pixel of the group lane >> 4, channel octet lane & 15); 16 partial dot products per lane, transpose-reduced over the 16
 // lanes of a pixel group: lane r of group g ends with window row r >> 1, column 4 * (r & 1) + g.
+// The window frame, the 49-tap blend and the tail after the correlation block are mixer_input_kernel's, statement for statement (its
+// comments hold): written as shared inline functions they made hipcc emit different code for both kernels, so they stay in the bodies.
 template <int SCT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void mixer_input_bf16maps_kernel(
     const unsigned short* __restrict__ mirror, LevelTable lv, int S_, int T_, int Srt, const float* __restrict__ ffeats,
@@ -281,15 +291,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     const float* ff = ffeats + (size_t)m * C;
     {
         const int H = lv.H[lvl], W = lv.W[lvl];
-        const float inv = 1.0f / (float)(1 << lvl);
-        const float cx = cxm * inv, cy = cym * inv;
-        const float gx = __fsub_rn(__fdiv_rn(2.0f * cx, (float)(W - 1)), 1.0f);
-        const float gy = __fsub_rn(__fdiv_rn(2.0f * cy, (float)(H - 1)), 1.0f);
-        const float ix = __fmul_rn(__fadd_rn(gx, 1.0f), (float)(W - 1) / 2.0f);
-        const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), (float)(H - 1) / 2.0f);
-        const float fx0 = floorf(ix), fy0 = floorf(iy);
-        const float wx = ix - fx0, wy = iy - fy0;
-        const int bx = (int)fx0 - PIPS_RADIUS, by = (int)fy0 - PIPS_RADIUS;
+        float wx, wy;
+        int bx, by;
+        level_sample_geometry(cxm, cym, lvl, H, W, wx, wy, bx, by);
 
         const int psel = lane >> 4, c8 = lane & 15;
         // BOTH operands are bf16 (round 6): under autocast torch.matmul casts the track features as well as the maps
@@ -331,17 +335,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
             d = fmaf(bf16_hi(u.w), fb.w, d);
             v[e] = ok[e] ? d : 0.f;
         }
-#define PIPS_TR_STEP(O, NH)                                                    \
-        {                                                                      \
-            const bool up = (lane & (O)) != 0;                                 \
-            _Pragma("unroll") for (int k = 0; k < (NH); ++k) {                 \
-                const float send = up ? v[k] : v[k + (NH)];                    \
-                const float keep = up ? v[k + (NH)] : v[k];                    \
-                v[k] = keep + __shfl_xor(send, (O));                           \
-            }                                                                  \
-        }
         PIPS_TR_STEP(8, 8) PIPS_TR_STEP(4, 4) PIPS_TR_STEP(2, 2) PIPS_TR_STEP(1, 1)
-#undef PIPS_TR_STEP
         const float scale = sqrtf((float)C);
         Dw[lvl][(c8 >> 1) * 8 + 4 * (c8 & 1) + psel] = v[0] / scale;
         __syncthreads();
@@ -375,21 +369,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         xrow[PIPS_KIN + (tid - 195)] = 0.f;
     }
 }
+#undef PIPS_TR_STEP
+
+// Both direct gathers: bf16_maps = the maps are the pyramid's bf16 mirror (mixer_input_bf16maps_kernel)
+static int launch_direct_gather(const void* maps, bool bf16_maps, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B,
+                                int S_, int T_, const float* ffeats, const float* coords, const float* times, int N,
+                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
+    LevelTable lv;
+    for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
+    auto launch = [&](auto kern, auto* typed_maps) {
+        hipLaunchKernelGGL(kern, dim3(B * N * Sw), dim3(256), 0, st, typed_maps, lv, S_, T_, Sw, ffeats, coords, times, N,
+                           win_start, win_dir, X);
+    };
+    if (bf16_maps) {
+        const unsigned short* mp = reinterpret_cast<const unsigned short*>(maps);
+        if (Sw == PIPS_S) launch(mixer_input_bf16maps_kernel<PIPS_S>, mp); else launch(mixer_input_bf16maps_kernel<0>, mp);
+    } else {
+        const float* pp = reinterpret_cast<const float*>(maps);
+        if (Sw == PIPS_S) launch(mixer_input_kernel<PIPS_S>, pp); else launch(mixer_input_kernel<0>, pp);
+    }
+    PIPS_CHECK_LAUNCH(bf16_maps ? "mixer_input_bf16maps_kernel" : "mixer_input_kernel");
+    return PIPS_OK;
+}
+
+int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
+                       int B, int S_, int T_, const float* ffeats, const float* coords, const float* times,
+                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
+    return launch_direct_gather(pyramid, false, lvl_off, lvlH, lvlW, B, S_, T_, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
+}
 
 int launch_mixer_input_bf16maps(const void* mirror, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B, int S_,
                                 int T_, const float* ffeats, const float* coords, const float* times, int N,
                                 const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
-    LevelTable lv;
-    for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
-    const unsigned short* mp = reinterpret_cast<const unsigned short*>(mirror);
-    if (Sw == PIPS_S)
-        hipLaunchKernelGGL(mixer_input_bf16maps_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, mp, lv, S_, T_, Sw, ffeats,
-                           coords, times, N, win_start, win_dir, X);
-    else
-        hipLaunchKernelGGL(mixer_input_bf16maps_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, mp, lv, S_, T_, Sw, ffeats,
-                           coords, times, N, win_start, win_dir, X);
-    PIPS_CHECK_LAUNCH("mixer_input_bf16maps_kernel");
-    return PIPS_OK;
+    return launch_direct_gather(mirror, true, lvl_off, lvlH, lvlW, B, S_, T_, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
 }
 
 // fp32 pyramid -> its bf16 mirror (same element offsets), 8 values per thread
@@ -457,21 +469,6 @@ int launch_pyramid_append(const float* src, const size_t* src_off, int k, float*
     hipLaunchKernelGGL(pyramid_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst,
                        reinterpret_cast<uint4*>(dst_mirror), t, R, T0 % R);
     PIPS_CHECK_LAUNCH("pyramid_append_kernel");
-    return PIPS_OK;
-}
-
-int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
-                       int B, int S_, int T_, const float* ffeats, const float* coords, const float* times,
-                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
-    LevelTable lv;
-    for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
-    if (Sw == PIPS_S)
-        hipLaunchKernelGGL(mixer_input_kernel<PIPS_S>, dim3(B * N * S), dim3(256), 0, st, pyramid, lv, S_, T_, Sw, ffeats,
-                           coords, times, N, win_start, win_dir, X);
-    else
-        hipLaunchKernelGGL(mixer_input_kernel<0>, dim3(B * N * Sw), dim3(256), 0, st, pyramid, lv, S_, T_, Sw, ffeats,
-                           coords, times, N, win_start, win_dir, X);
-    PIPS_CHECK_LAUNCH("mixer_input_kernel");
     return PIPS_OK;
 }
 

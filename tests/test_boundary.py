@@ -255,6 +255,31 @@ def test_asm_hazard_lint_passes_head_and_flags_the_round5_scatter():
     assert sorted(f["have"] for f in neg) == [4, 6, 8, 10] and all(f["need"] == 12 for f in neg)
 
 
+def test_product_library_ships_only_reachable_gemm_tiles():
+    """A kernel that only a tuning hook can select exists only in a tuning build (common.h): the product library holds exactly the
+    igemm_f32_kernel / gemm_x3_kernel instantiations that launch_gemm / launch_conv / launch_gemm_x3 / launch_conv_x3 can reach
+    without a hook -- template arguments (BM, BN, WGM, WGN, KS, CONV[, BKE]) -- and the register-staged bf16 family keeps its 51."""
+    L, _ = _lint()
+    from pips_amd import _build
+    names = {n for text in L.disassemble(_build.build_library(verbose=False)) for n in L.parse_objdump(text)}
+
+    def instantiations(kernel):
+        out = set()
+        for n in names:
+            m = re.match(r"_ZN4pips\d+%sI((?:L[ib]\d+E)+)E" % kernel, n)
+            if m:
+                out.add(tuple(int(v) for v in re.findall(r"L[ib](\d+)E", m.group(1))))
+        return out
+
+    assert instantiations("igemm_f32_kernel") == {
+        (128, 128, 2, 2, 1, 0), (64, 64, 2, 2, 1, 0), (64, 64, 2, 2, 2, 0),
+        (128, 128, 2, 2, 1, 1), (64, 128, 2, 2, 1, 1), (128, 96, 4, 1, 1, 1), (64, 96, 2, 1, 1, 1), (128, 64, 2, 2, 1, 1), (64, 64, 2, 2, 1, 1)}
+    assert instantiations("gemm_x3_kernel") == {
+        (256, 128, 4, 2, 1, 0, 32), (128, 128, 2, 2, 2, 0, 16), (128, 128, 2, 2, 1, 0, 32), (64, 64, 2, 2, 2, 0, 32), (64, 64, 2, 2, 1, 0, 32),
+        (256, 128, 4, 2, 1, 1, 32), (128, 128, 2, 2, 1, 1, 32), (128, 64, 2, 2, 1, 1, 32), (64, 128, 2, 2, 1, 1, 32), (64, 64, 2, 2, 1, 1, 32)}
+    assert len(instantiations("gemm_bf16_kernel")) == 51
+
+
 def test_hazard_table_matches_the_compilers_recognizer():
     """gfx950's wait-state table is not in this image; the lint's numbers are pinned against hipcc's own hazard recognizer: one probe
     kernel per producer / consumer pair (tools/asm_hazard_probe.hip, builtins + sched_barriers), the s_nops hipcc inserts are the
