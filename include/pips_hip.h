@@ -97,7 +97,9 @@ const char* pips_last_error(void);
  * Still 3 after additions that change no existing entry point: pips_track_win and pips_mixer_input_build_win (per-particle
  * time direction win_dir); pips_track_ring, pips_mixer_input_build_ring and pips_pyramid_append (a ring of R frame slots
  * for streamed video); pips_chain_hop, pips_chain_gather, pips_chain_step, pips_chain_workspace_bytes and pips_chain_threshold
- * (the visibility-aware chaining of chain_demo.py:40-83, one call per hop). */
+ * (the visibility-aware chaining of chain_demo.py:40-83, one call per hop); pips_track_clips, pips_mixer_input_build_clips,
+ * pips_chain_hop_clips, pips_chain_gather_clips and pips_chain_step_clips (the windows of several videos on one flat cache:
+ * a per-particle video index).  pips_chain_workspace_bytes grew by the staged video indices: size with THIS library. */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -201,6 +203,27 @@ int    pips_track_ring(const void* arena, const float* pyramid, int B, int T, in
                        const int* win_start, const int* win_dir, const float* times, int N, int stride, int iters,
                        int flags, int S, void* workspace, size_t workspace_bytes,
                        float* out_trajs, float* out_vis, float* out_ffeat0, void* stream);
+/* Several videos in one call.  The pyramid is ONE flat linear cache (B = 1, R = T) whose frame axis holds the frames of V
+ * videos of the same frame size one after the other, T = the sum of their lengths, each video's frames encoded as if alone:
+ *   clip_first  (V) device int32: first flat frame of video v
+ *   clip_frames (V) device int32: frames of video v
+ *   win_clip    (N) device int32: the video of each particle, or NULL
+ * Row s of particle n's window reads flat frame clip_first[v] + clamp(win_start + dir*s, 0, clip_frames[v]-1), v = win_clip[n]:
+ * win_start counts frames of the particle's OWN video, and the repeats past its last frame and before its frame 0 stop at
+ * that video, never at a neighbour's.  The point sample of feat_init = NULL reads row 0's frame.  Results per particle are what
+ * pips_track_win gives on that video's own cache (bit for bit while the mixer's GEMMs take the same route at both row counts).
+ * Containment: v is clamped to [0, V-1] and the flat frame to [0, T-1] -- a corrupt index reads a wrong frame, never outside
+ * the buffer.  Windowed particles take the direct gather.  win_clip = NULL: exactly pips_track_ring plus the score-map block of
+ * pips_track_s (V and the tables are not read).  With win_clip, PIPS_E_ARG ahead of any launch for: V < 1, a NULL clip_first /
+ * clip_frames, a NULL win_start, B != 1, R != T, a non-NULL ce_tgt. */
+int    pips_track_clips(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8,
+                        const float* xys, const float* coords_init, const float* feat_init,
+                        const int* win_start, const int* win_dir,
+                        const int* win_clip, const int* clip_first, const int* clip_frames, int V,
+                        const float* times, int N, int stride, int iters, int flags, int S,
+                        void* workspace, size_t workspace_bytes,
+                        float* out_trajs, float* out_vis, float* out_ffeat0,
+                        const float* ce_tgt, float* ce_terms, void* ce_ws, size_t ce_ws_bytes, void* stream);
 
 /* ---- visibility-aware chaining: one call per hop ----------------------------------------
  * Replaces: the hop loop body of chain_demo.py:40-83 (test_on_badja.py:64-112) for a whole set of particles -- read the
@@ -255,6 +278,30 @@ int    pips_chain_hop(const void* arena, const float* pyramid, int T, int R, int
                       int* cur, const int* dir, float* feat,
                       int* next_active, int* next_count, int* steps,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a state that holds the particles of V videos (pips_track_clips: one flat linear cache, T = all its frames, R = T):
+ *   clip        int32 (n)  the video of each particle, or NULL (= the forms above; the tables and V are then not read)
+ *   clip_first / clip_frames / V   the clip table of pips_track_clips
+ * cur counts frames of the particle's own video and a particle stays live while 0 <= cur < clip_frames[clip[q]] (clip[q] clamped
+ * to [0, V-1]) instead of < T.  trajs / vis stay (L,n,2) / (L,n) with one base: L is sized for the LONGEST video (L = max
+ * clip_frames + 14, base = 7), and a particle of a shorter video finishes while the others go on.  pips_chain_gather_clips also
+ * stages wc (n_act) = clip[q] (0 for a member outside [0, n)), the win_clip of pips_track_clips.  Compaction order, NaN handling
+ * and the thresholds are those of the forms above.  With clip, PIPS_E_ARG ahead of any launch also for: V < 1, a NULL clip_first
+ * (hop) / clip_frames (hop, step) / wc (gather), R != T (hop). */
+int    pips_chain_gather_clips(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const int* clip,
+                               const float* feat, const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd,
+                               int* wc, float* fi, void* stream);
+int    pips_chain_step_clips(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int n,
+                             const int* active, int n_act, int sample_feat, float* trajs, float* vis, int L, int base, int* cur,
+                             const int* dir, const int* clip, const int* clip_frames, int V, float* feat, int* next_active,
+                             int* next_count, int* steps, void* stream);
+int    pips_chain_hop_clips(const void* arena, const float* pyramid, int T, int R, int H8, int W8,
+                            const float* times, int stride, int iters, int flags,
+                            int n, const int* active, int n_act, int sample_feat,
+                            float* trajs, float* vis, int L, int base,
+                            int* cur, const int* dir,
+                            const int* clip, const int* clip_first, const int* clip_frames, int V,
+                            float* feat, int* next_active, int* next_count, int* steps,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 
@@ -312,6 +359,11 @@ int    pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, in
 int    pips_mixer_input_build_ring(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
                                    const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
                                    int flags, int S, float* X, void* stream);
+/* pips_mixer_input_build_ring with the clip table of pips_track_clips (win_clip = NULL: exactly pips_mixer_input_build_ring) */
+int    pips_mixer_input_build_clips(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
+                                    const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
+                                    const int* win_clip, const int* clip_first, const int* clip_frames, int V,
+                                    int flags, int S, float* X, void* stream);
 
 /* Same result as pips_mixer_input_build through the LDS-tiled kernels meant for dense query sets
  * (BASELINE configs[3], test_on_davis.py:103-130): particles binned by 16x16 map tile, the tile's

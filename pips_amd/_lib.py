@@ -47,6 +47,9 @@ SIGNATURES = {
                                c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, c_void_p]),
     "pips_track_ring": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_void_p, c_void_p, fp, c_int, c_int,
                                 c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, c_void_p]),
+    "pips_track_clips": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int, fp, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, fp, fp,
+                                 c_void_p, c_size_t, c_void_p]),
     "pips_chain_threshold": (c_float, [c_int]),
     "pips_chain_workspace_bytes": (c_size_t, [c_int, c_int]),
     "pips_chain_gather": (c_int, [fp, c_int, c_int, c_int, c_void_p, c_void_p, fp, c_void_p, c_int, c_int, fp, c_void_p, c_void_p, fp,
@@ -55,6 +58,13 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "pips_chain_hop": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, fp, fp,
                                c_int, c_int, c_void_p, c_void_p, fp, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pips_chain_gather_clips": (c_int, [fp, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, fp, c_void_p, c_int, c_int, fp, c_void_p,
+                                        c_void_p, c_void_p, fp, c_void_p]),
+    "pips_chain_step_clips": (c_int, [fp, fp, fp, c_int, c_int, c_void_p, c_int, c_int, fp, fp, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int, fp, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pips_chain_hop_clips": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                     fp, fp, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, fp, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pips_encoder_workspace_bytes": (c_size_t, [c_int] * 4),
     "pips_pyramid_floats": (c_size_t, [c_int] * 4),
     "pips_pyramid_offset": (c_size_t, [c_int] * 5),
@@ -66,6 +76,8 @@ SIGNATURES = {
                                            fp, c_void_p]),
     "pips_mixer_input_build_ring": (c_int, [fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_int, c_void_p, c_void_p, c_int,
                                             c_int, fp, c_void_p]),
+    "pips_mixer_input_build_clips": (c_int, [fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_int, c_int, fp, c_void_p]),
     "pips_encoder_fwd": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, fp, c_void_p, c_size_t, c_void_p]),
     "pips_encoder_fwd_bf16": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, fp, c_void_p, c_size_t, c_void_p]),
     "pips_encoder_fwd_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, fp, c_void_p, c_size_t,

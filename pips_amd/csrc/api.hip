@@ -588,6 +588,20 @@ int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int W, int
     return PIPS_OK;
 }
 
+// ------------------------------------------------------------------ windows of several videos
+// The checks every clip form shares, ahead of any launch, and the table the kernels take.  win_clip == null: no table, no check.
+int clip_table(const int* win_clip, const int* clip_first, const int* clip_frames, int V, const int* win_start, int B, int T, int R,
+               const char* who, ClipTable& ct) {
+    ct = ClipTable{win_clip, clip_first, clip_frames, V};
+    if (win_clip == nullptr) return PIPS_OK;
+    PIPS_CHECK_ARG(V >= 1, "%s: a clip table needs V >= 1 videos (V=%d)", who, V);
+    PIPS_CHECK_ARG(clip_first && clip_frames, "%s: win_clip needs clip_first and clip_frames", who);
+    PIPS_CHECK_ARG(win_start != nullptr, "%s: win_clip needs win_start", who);
+    PIPS_CHECK_ARG(B == 1, "%s: the videos of a clip table share ONE flat cache, B = 1 (B=%d)", who, B);
+    PIPS_CHECK_ARG(R == T, "%s: a clip table needs a linear cache, R = T (R=%d, T=%d)", who, R, T);
+    return PIPS_OK;
+}
+
 // ------------------------------------------------------------------ correlation gather
 enum GatherRoute { GATHER_AUTO, GATHER_DIRECT, GATHER_TILED };   // AUTO: tiled for a dense query set if the call allows it
 
@@ -595,10 +609,13 @@ enum GatherRoute { GATHER_AUTO, GATHER_DIRECT, GATHER_TILED };   // AUTO: tiled 
 // has R = T); S = window length = mixer rows per particle.  win_dir (per-particle time direction, sign) is read with win_start only.
 // bf16_maps: the gather reads the bf16 mirror behind the fp32 levels.  The tiled kernels need scratch, a dense un-windowed
 // query set and R = T = S = PIPS_S; ev != null (tiled only): 4 events around their three launches.
+// win_clip (per-particle video index) + clip_first / clip_frames (V videos): the windows of several videos on one flat linear
+// cache, B = 1 and R = T = all frames (ClipTable, common.h); read with win_start only.
 struct GatherCall {
     const float* pyramid; int B, T, R, S, H8, W8;
     const float* ffeats; const float* coords; const float* times; int N;
     const int* win_start; const int* win_dir;
+    const int* win_clip; const int* clip_first; const int* clip_frames; int V;
     float* X;
     bool bf16_maps; GatherRoute route;
     void* scratch; size_t scratch_bytes; hipEvent_t* ev;
@@ -611,6 +628,9 @@ int mixer_input(const GatherCall& g) {
     PIPS_CHECK_ARG(g.S >= 1 && g.S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", g.S, PIPS_S_MAX);
     const PyramidView v = pyramid_view(g.B * g.R, g.H8, g.W8);
     PIPS_CHECK_ARG(!v.empty(), "mixer_input: map too small");
+    ClipTable ct;
+    RUN(clip_table(g.win_clip, g.clip_first, g.clip_frames, g.V, g.win_start, g.B, g.T, g.R, "mixer_input", ct));
+    const ClipTable* clips = g.win_clip != nullptr ? &ct : nullptr;
     const float* mirror = g.pyramid + v.levels;
     const bool can_tile = g.scratch != nullptr && g.win_start == nullptr && g.win_dir == nullptr && g.R == PIPS_S && g.T == g.R &&
                           g.S == PIPS_S && g.scratch_bytes >= tiled_gather_scratch_bytes(g.B, g.N, g.H8, g.W8);
@@ -624,9 +644,9 @@ int mixer_input(const GatherCall& g) {
     PIPS_CHECK_ARG(g.win_dir == nullptr || g.win_start != nullptr, "mixer_input: win_dir needs win_start");
     if (g.bf16_maps)
         return launch_mixer_input_bf16maps(mirror, v.off, v.lh, v.lw, g.B, g.R, g.T, g.ffeats, g.coords, g.times, g.N, g.win_start,
-                                           g.win_dir, g.X, g.st, g.S);
+                                           g.win_dir, g.X, g.st, g.S, clips);
     return launch_mixer_input(g.pyramid, v.off, v.lh, v.lw, g.B, g.R, g.T, g.ffeats, g.coords, g.times, g.N, g.win_start, g.win_dir,
-                              g.X, g.st, g.S);
+                              g.X, g.st, g.S, clips);
 }
 
 // the tiled kernels on a PIPS_S-frame clip; ms3_host != null: the durations of the three launches, and a stream synchronisation
@@ -833,12 +853,14 @@ int score_map_prepare(const float* pyramid, int B, int S, int H8, int W8, float*
 
 // The tracker on cached maps.  pyramid: B clips x R frame slots of H8 x W8 level-0 pixels holding T logical frames (a linear
 // cache has R = T); S = window length (tokens per particle) the arena was packed for, S == PIPS_S runs the specialised kernels.
-// win_start / win_dir / coords_init / feat_init / out_ffeat0 and the score-map block ce_* may be null.
+// win_start / win_dir / coords_init / feat_init / out_ffeat0 and the score-map block ce_* may be null; so may win_clip, with
+// which the pyramid is ONE flat linear cache of V videos (B = 1, R = T = all frames; clip_first / clip_frames: GatherCall).
 struct TrackCall {
     const void* arena; const float* pyramid;
     int B, T, R, S, H8, W8;
     const float* xys; const float* coords_init; const float* feat_init;
     const int* win_start; const int* win_dir;
+    const int* win_clip; const int* clip_first; const int* clip_frames; int V;
     const float* times; int N, stride, iters, flags;
     void* workspace; size_t workspace_bytes;
     float* out_trajs; float* out_vis; float* out_ffeat0;
@@ -853,6 +875,9 @@ int track_impl(const TrackCall& c) {
     PIPS_CHECK_ARG(c.S >= 1 && c.S <= PIPS_S_MAX, "track: window length S=%d outside 1..%d", c.S, PIPS_S_MAX);
     PIPS_CHECK_ARG(c.H8 >= 8 && c.W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", c.H8, c.W8);
     PIPS_CHECK_ARG(c.win_dir == nullptr || c.win_start != nullptr, "track: win_dir needs win_start");
+    ClipTable ct;
+    RUN(clip_table(c.win_clip, c.clip_first, c.clip_frames, c.V, c.win_start, c.B, c.T, c.R, "track", ct));
+    PIPS_CHECK_ARG(c.win_clip == nullptr || c.ce_tgt == nullptr, "track: no score-map terms on a clip table");
     const int B = c.B, N = c.N, S = c.S;
     const TrackPlan P = plan_track(B, N, S);
     if (c.workspace_bytes < P.total * sizeof(float)) {
@@ -871,7 +896,8 @@ int track_impl(const TrackCall& c) {
         if (c.feat_init != ffeat0)
             (void)hipMemcpyAsync(ffeat0, c.feat_init, (size_t)B * N * PIPS_C * sizeof(float), hipMemcpyDeviceToDevice, st);
     } else {
-        RUN(launch_point_sample_strided(c.pyramid, B, c.R, c.T, c.H8, c.W8, coords, S * 2, N, c.win_start, ffeat0, st));   // :463
+        RUN(launch_point_sample_strided(c.pyramid, B, c.R, c.T, c.H8, c.W8, coords, S * 2, N, c.win_start, ffeat0, st,
+                                        c.win_clip != nullptr ? &ct : nullptr));                                  // :463
     }
     RUN(launch_init_ffeats(ffeat0, B * N, ffeats, st, S));                                                    // :466
     if (c.ce_tgt != nullptr) {          // score-map loss terms of every iteration (:501-511, 58-92): evaluation only
@@ -891,6 +917,7 @@ int track_impl(const TrackCall& c) {
     g.pyramid = c.pyramid; g.B = B; g.T = c.T; g.R = c.R; g.S = S; g.H8 = c.H8; g.W8 = c.W8;
     g.ffeats = ffeats; g.coords = coords; g.times = c.times; g.N = N;
     g.win_start = c.win_start; g.win_dir = c.win_dir;
+    g.win_clip = c.win_clip; g.clip_first = c.clip_first; g.clip_frames = c.clip_frames; g.V = c.V;
     g.X = ws + P.X;
     g.bf16_maps = (c.flags & PIPS_FLAG_BF16_MAPS) != 0;
     g.route = GATHER_AUTO;
@@ -939,16 +966,24 @@ GatherCall gather_call(const float* pyramid, int B, int frames, int H8, int W8, 
 // ------------------------------------------------------------------ chaining (chain_demo.py:40-83)
 // The caller-owned state of a set of chained particles: trajs (L,n,2) / vis (L,n) hold frame f in row (f + base) mod L, cur
 // (n) the window starts, dir (n) the time directions (sign; null = forward), feat (n,128) the carried features; active
-// (n_act) the particles of this hop, strictly ascending.  vis and dir may be null.
+// (n_act) the particles of this hop, strictly ascending.  vis and dir may be null; so may clip (n), the video of each particle
+// in a state that holds the particles of V videos of clip_frames[v] frames each (one trajs / vis buffer, one base, L for the longest).
 struct ChainState {
     int n; const int* active; int n_act; int sample_feat;
     float* trajs; float* vis; int L, base;
     int* cur; const int* dir; float* feat;
+    const int* clip; const int* clip_frames; int V;
 };
 int check_chain_state(const ChainState& s, const char* who) {
     PIPS_CHECK_ARG(s.n_act >= 0 && s.n_act <= s.n, "%s: need 0 <= n_act <= n (n_act=%d, n=%d)", who, s.n_act, s.n);
     PIPS_CHECK_ARG(s.L >= PIPS_S, "%s: a window of %d frames needs L >= %d rows (L=%d)", who, PIPS_S, PIPS_S, s.L);
     PIPS_CHECK_ARG(s.active && s.trajs && s.cur && s.feat, "%s: null pointer", who);
+    return PIPS_OK;
+}
+// the video lengths the live test of a state over several videos reads
+int check_chain_clips(const ChainState& s, const char* who) {
+    PIPS_CHECK_ARG(s.clip == nullptr || s.V >= 1, "%s: a clip table needs V >= 1 videos (V=%d)", who, s.V);
+    PIPS_CHECK_ARG(s.clip == nullptr || s.clip_frames != nullptr, "%s: clip needs clip_frames", who);
     return PIPS_OK;
 }
 // a hop over no particle: *next_count = 0 on the stream and nothing else; a memset that fails is reported as a failed launch is
@@ -963,7 +998,7 @@ int clear_chain_count(int* next_count, const char* who, hipStream_t st) {
 
 // workspace of one hop, in floats: the tracker's for (B = 1, N = n_act, S = 8), the staging arrays of chain_gather and the windows
 // the tracker returns (every iterate of the trajectories: the last one is written back)
-struct ChainPlan { size_t track, xy, ws, wd, fi, win_trajs, win_vis, win_ffeat0, total; };
+struct ChainPlan { size_t track, xy, ws, wd, fi, win_trajs, win_vis, win_ffeat0, wc, total; };
 ChainPlan plan_chain(int n_act, int iters) {
     ChainPlan P;
     Bump b;
@@ -975,27 +1010,30 @@ ChainPlan plan_chain(int n_act, int iters) {
     P.win_trajs = b.take((size_t)(iters + 1) * PIPS_S * n_act * 2);
     P.win_vis = b.take((size_t)PIPS_S * n_act);
     P.win_ffeat0 = b.take((size_t)n_act * PIPS_C);
+    P.wc = b.take(n_act);                              // (the staged video indices of a hop over several videos)
     P.total = b.off;
     return P;
 }
 
-int chain_gather(const ChainState& s, float* xy, int* ws, int* wd, float* fi, hipStream_t st) {
+int chain_gather(const ChainState& s, float* xy, int* ws, int* wd, int* wc, float* fi, hipStream_t st) {
     RUN(check_chain_state(s, "chain_gather"));
-    PIPS_CHECK_ARG(xy && ws && wd && (fi || s.sample_feat), "chain_gather: null pointer");
+    PIPS_CHECK_ARG(xy && ws && wd && (fi || s.sample_feat) && (wc || !s.clip), "chain_gather: null pointer");
     if (s.n_act == 0) return PIPS_OK;
-    return launch_chain_gather(s.trajs, s.L, s.base, s.n, s.cur, s.dir, s.feat, s.active, s.n_act, s.sample_feat, xy, ws, wd, fi, st);
+    return launch_chain_gather(s.trajs, s.L, s.base, s.n, s.cur, s.dir, s.feat, s.active, s.n_act, s.sample_feat, xy, ws, wd, fi, st,
+                               s.clip, wc);
 }
 
 int chain_step(const ChainState& s, const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int* next_active,
                int* next_count, int* steps, hipStream_t st) {
     RUN(check_chain_state(s, "chain_step"));
+    RUN(check_chain_clips(s, "chain_step"));
     PIPS_CHECK_ARG(T >= 1, "chain_step: need T >= 1 (T=%d)", T);
     PIPS_CHECK_ARG(next_active && next_count, "chain_step: null pointer");
     PIPS_CHECK_ARG(next_active != s.active, "chain_step: next_active may not alias active");
     if (s.n_act == 0) return clear_chain_count(next_count, "chain_step", st);
     PIPS_CHECK_ARG(win_trajs && win_vis && (win_ffeat0 || !s.sample_feat), "chain_step: null pointer");
     return launch_chain_step(win_trajs, win_vis, win_ffeat0, s.n, s.active, s.n_act, s.sample_feat, s.trajs, s.vis, s.L, s.base, T, s.cur,
-                             s.dir, s.feat, next_active, next_count, steps, st);
+                             s.dir, s.feat, next_active, next_count, steps, st, s.clip, s.clip_frames, s.V);
 }
 
 }  // namespace
@@ -1165,11 +1203,19 @@ int pips_mixer_input_build_win(const float* pyramid, int B, int T, int H8, int W
 int pips_mixer_input_build_ring(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
                                 const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
                                 int flags, int S, float* X, void* stream) {
+    return pips_mixer_input_build_clips(pyramid, B, T, R, H8, W8, ffeats, coords, times, N, win_start, win_dir, nullptr, nullptr,
+                                        nullptr, 0, flags, S, X, stream);
+}
+int pips_mixer_input_build_clips(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
+                                 const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
+                                 const int* win_clip, const int* clip_first, const int* clip_frames, int V, int flags, int S,
+                                 float* X, void* stream) {
     GatherCall g = gather_call(pyramid, B, T, H8, W8, ffeats, coords, times, N, X, stream);
     g.R = R;
     g.S = S;
     g.win_start = win_start;
     g.win_dir = win_dir;
+    g.win_clip = win_clip; g.clip_first = clip_first; g.clip_frames = clip_frames; g.V = V;
     g.bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
     g.route = GATHER_DIRECT;
     return mixer_input(g);
@@ -1301,6 +1347,21 @@ int pips_track_ring(const void* arena, const float* pyramid, int B, int T, int R
     c.win_dir = win_dir;
     return track_impl(c);
 }
+int pips_track_clips(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8, const float* xys,
+                     const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                     const int* win_clip, const int* clip_first, const int* clip_frames, int V, const float* times, int N,
+                     int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
+                     float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws, size_t ce_ws_bytes,
+                     void* stream) {
+    TrackCall c = track_call(arena, pyramid, B, T, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters, flags,
+                             workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream);
+    c.R = R;
+    c.S = S;
+    c.win_dir = win_dir;
+    c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = clip_frames; c.V = V;
+    c.ce_tgt = ce_tgt; c.ce_terms = ce_terms; c.ce_ws = ce_ws; c.ce_ws_bytes = ce_ws_bytes;
+    return track_impl(c);
+}
 int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
                    const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
                    const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
@@ -1317,24 +1378,49 @@ size_t pips_chain_workspace_bytes(int n_act, int iters) {
 }
 int pips_chain_gather(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const float* feat,
                       const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, void* stream) {
+    return pips_chain_gather_clips(trajs, L, base, n, cur, dir, nullptr, feat, active, n_act, sample_feat, xy, ws, wd, nullptr, fi,
+                                   stream);
+}
+int pips_chain_gather_clips(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const int* clip,
+                            const float* feat, const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, int* wc,
+                            float* fi, void* stream) {
     const ChainState s = {n, active, n_act, sample_feat, const_cast<float*>(trajs), nullptr, L, base, const_cast<int*>(cur), dir,
-                          const_cast<float*>(feat)};
-    return chain_gather(s, xy, ws, wd, fi, (hipStream_t)stream);
+                          const_cast<float*>(feat), clip, nullptr, 0};          // (the gather reads no video length)
+    return chain_gather(s, xy, ws, wd, wc, fi, (hipStream_t)stream);
 }
 int pips_chain_step(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int n, const int* active,
                     int n_act, int sample_feat, float* trajs, float* vis, int L, int base, int* cur, const int* dir, float* feat,
                     int* next_active, int* next_count, int* steps, void* stream) {
-    const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat};
+    return pips_chain_step_clips(win_trajs, win_vis, win_ffeat0, T, n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir,
+                                 nullptr, nullptr, 0, feat, next_active, next_count, steps, stream);
+}
+int pips_chain_step_clips(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int T, int n, const int* active,
+                          int n_act, int sample_feat, float* trajs, float* vis, int L, int base, int* cur, const int* dir,
+                          const int* clip, const int* clip_frames, int V, float* feat, int* next_active, int* next_count,
+                          int* steps, void* stream) {
+    const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat, clip, clip_frames, V};
     return chain_step(s, win_trajs, win_vis, win_ffeat0, T, next_active, next_count, steps, (hipStream_t)stream);
 }
 int pips_chain_hop(const void* arena, const float* pyramid, int T, int R, int H8, int W8, const float* times, int stride, int iters,
                    int flags, int n, const int* active, int n_act, int sample_feat, float* trajs, float* vis, int L, int base,
                    int* cur, const int* dir, float* feat, int* next_active, int* next_count, int* steps, void* workspace,
                    size_t workspace_bytes, void* stream) {
-    const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat};
+    return pips_chain_hop_clips(arena, pyramid, T, R, H8, W8, times, stride, iters, flags, n, active, n_act, sample_feat, trajs, vis, L,
+                                base, cur, dir, nullptr, nullptr, nullptr, 0, feat, next_active, next_count, steps, workspace,
+                                workspace_bytes, stream);
+}
+int pips_chain_hop_clips(const void* arena, const float* pyramid, int T, int R, int H8, int W8, const float* times, int stride,
+                         int iters, int flags, int n, const int* active, int n_act, int sample_feat, float* trajs, float* vis, int L,
+                         int base, int* cur, const int* dir, const int* clip, const int* clip_first, const int* clip_frames, int V,
+                         float* feat, int* next_active, int* next_count, int* steps, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat, clip, clip_frames, V};
     // every check ahead of the first launch: a rejected call leaves the caller's state as it was
     RUN(check_chain_state(s, "chain_hop"));
+    RUN(check_chain_clips(s, "chain_hop"));
     PIPS_CHECK_ARG(R >= 1 && T >= 1, "chain_hop: need R >= 1 and T >= 1 (R=%d, T=%d)", R, T);
+    PIPS_CHECK_ARG(clip == nullptr || clip_first != nullptr, "chain_hop: clip needs clip_first and clip_frames");
+    PIPS_CHECK_ARG(clip == nullptr || R == T, "chain_hop: a clip table needs a linear cache, R = T (R=%d, T=%d)", R, T);
     PIPS_CHECK_ARG(next_active && next_count, "chain_hop: null pointer");
     PIPS_CHECK_ARG(next_active != active, "chain_hop: next_active may not alias active");
     PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "chain_hop: need iters >= 0, stride >= 1 and a map of at least 8x8");
@@ -1349,14 +1435,16 @@ int pips_chain_hop(const void* arena, const float* pyramid, int T, int R, int H8
     float* ws = (float*)workspace;
     float* xy = ws + P.xy; float* fi = ws + P.fi;
     int* win_start = reinterpret_cast<int*>(ws + P.ws); int* win_dir = reinterpret_cast<int*>(ws + P.wd);
+    int* win_clip = reinterpret_cast<int*>(ws + P.wc);
     float* win_trajs = ws + P.win_trajs; float* win_vis = ws + P.win_vis; float* win_ffeat0 = ws + P.win_ffeat0;
-    RUN(chain_gather(s, xy, win_start, win_dir, fi, st));
+    RUN(chain_gather(s, xy, win_start, win_dir, win_clip, fi, st));
     // the first window samples its features at the start position (feat_init = NULL) and returns them; later ones carry feat
     TrackCall c = track_call(arena, pyramid, 1, T, H8, W8, xy, nullptr, sample_feat ? nullptr : fi, win_start, times, n_act, stride,
                              iters, flags, ws + P.track, plan_track(1, n_act, PIPS_S).total * sizeof(float), win_trajs, win_vis,
                              sample_feat ? win_ffeat0 : nullptr, stream);
     c.R = R;
     c.win_dir = dir != nullptr ? win_dir : nullptr;
+    if (clip != nullptr) { c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = clip_frames; c.V = V; }
     RUN(track_impl(c));
     return chain_step(s, win_trajs + (size_t)iters * PIPS_S * n_act * 2, win_vis, win_ffeat0, T, next_active, next_count, steps, st);
 }

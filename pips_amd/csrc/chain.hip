@@ -36,12 +36,14 @@ __device__ __forceinline__ int chain_row(int f, int base, int L) {
     return r < 0 ? r + L : r;
 }
 
-// One block per active particle j (q = active[j]): its start position, window start, direction and carried features.
+// One block per active particle j (q = active[j]): its start position, window start, direction and carried features -- and, in a
+// state that holds several videos (clip != null), the video it belongs to.
 __global__ __launch_bounds__(PIPS_C) void chain_gather_kernel(const float* __restrict__ trajs, int L, int base, int n,
                                                               const int* __restrict__ cur, const int* __restrict__ dir,
                                                               const float* __restrict__ feat, const int* __restrict__ active,
                                                               int n_act, int sample_feat, float* __restrict__ xy,
-                                                              int* __restrict__ ws, int* __restrict__ wd, float* __restrict__ fi) {
+                                                              int* __restrict__ ws, int* __restrict__ wd, float* __restrict__ fi,
+                                                              const int* __restrict__ clip, int* __restrict__ wc) {
     const int j = blockIdx.x;
     if (j >= n_act) return;
     const int q = active[j];
@@ -55,6 +57,7 @@ __global__ __launch_bounds__(PIPS_C) void chain_gather_kernel(const float* __res
         xy[2 * j + 1] = ok ? trajs[src + 1] : 0.f;
         ws[j] = c;
         wd[j] = (ok && dir != nullptr) ? dir[q] : 1;
+        if (clip != nullptr) wc[j] = ok ? clip[q] : 0;
     }
     if (!sample_feat) fi[(size_t)j * PIPS_C + t] = ok ? feat[(size_t)q * PIPS_C + t] : 0.f;
 }
@@ -65,9 +68,11 @@ struct StepArgs {
     const float* win_ffeat0;     // (n_act, 128), read with sample_feat
     const int* active;
     const int* dir;
+    const int* clip;             // (n) video of each particle, or null: one video of T frames
+    const int* clip_frames;      // (V) frames of each video
     float* trajs; float* vis; float* feat;
     int* cur; int* next_active; int* next_count; int* steps;
-    int n, n_act, sample_feat, L, base, T;
+    int n, n_act, sample_feat, L, base, T, V;
     ThrTable thr;
 };
 
@@ -112,7 +117,9 @@ __global__ __launch_bounds__(STEP_THREADS) void chain_step_kernel(const StepArgs
                 const int nc = c + d * si;
                 a.cur[q] = nc;
                 if (a.steps != nullptr) a.steps[j] = si;
-                live = nc >= 0 && nc < a.T;
+                // inside the particle's own video (a video index outside the table is clamped into it, as the gather kernels do)
+                const int Tq = a.clip != nullptr ? a.clip_frames[min(max(a.clip[q], 0), a.V - 1)] : a.T;
+                live = nc >= 0 && nc < Tq;
             }
         }
         if (a.sample_feat) {           // the features of a particle's first window are carried from here on (chain_demo.py:57)
@@ -145,19 +152,21 @@ __global__ __launch_bounds__(STEP_THREADS) void chain_step_kernel(const StepArgs
 float chain_threshold(int k) { return (k < 0 || k >= CHAIN_THR) ? 0.f : thresholds().v[k]; }
 
 int launch_chain_gather(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const float* feat,
-                        const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, hipStream_t st) {
+                        const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, hipStream_t st,
+                        const int* clip, int* wc) {
     hipLaunchKernelGGL(chain_gather_kernel, dim3(n_act), dim3(PIPS_C), 0, st, trajs, L, base, n, cur, dir, feat, active, n_act,
-                       sample_feat, xy, ws, wd, fi);
+                       sample_feat, xy, ws, wd, fi, clip, wc);
     PIPS_CHECK_LAUNCH("chain_gather");
     return PIPS_OK;
 }
 
 int launch_chain_step(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int n, const int* active, int n_act,
                       int sample_feat, float* trajs, float* vis, int L, int base, int T, int* cur, const int* dir, float* feat,
-                      int* next_active, int* next_count, int* steps, hipStream_t st) {
+                      int* next_active, int* next_count, int* steps, hipStream_t st, const int* clip, const int* clip_frames, int V) {
     StepArgs a;
     a.win_trajs = win_trajs; a.win_vis = win_vis; a.win_ffeat0 = win_ffeat0; a.active = active; a.dir = dir;
     a.trajs = trajs; a.vis = vis; a.feat = feat; a.cur = cur; a.next_active = next_active; a.next_count = next_count; a.steps = steps;
+    a.clip = clip; a.clip_frames = clip_frames; a.V = V;
     a.n = n; a.n_act = n_act; a.sample_feat = sample_feat; a.L = L; a.base = base; a.T = T;
     a.thr = thresholds();
     hipLaunchKernelGGL(chain_step_kernel, dim3(1), dim3(STEP_THREADS), 0, st, a);

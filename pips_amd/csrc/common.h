@@ -144,6 +144,21 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // slot of logical frame f >= 0 in a ring of R frame slots (a linear cache, R = frames, never wraps)
 __device__ __forceinline__ int ring_slot(int f, int R) { return f < R ? f : f % R; }
 
+// Several videos on ONE flat linear cache (B = 1): video v holds frames[v] frames from flat frame first[v] on, and particle pn
+// belongs to video win_clip[pn].  All three are device int32 arrays; win_clip == null = no table (one video per clip).
+struct ClipTable {
+    const int* win_clip;     // (particles)
+    const int* first;        // (V)
+    const int* frames;       // (V)
+    int V;
+};
+// flat frame of frame f of particle pn's video: f is clamped to the video's own ends -- the repeats past the last frame and
+// before frame 0 never reach a neighbour -- and, containment, v to [0, V-1] and the result to the F frames of the buffer
+__device__ __forceinline__ int clip_frame(const ClipTable& ct, int pn, int f, int F) {
+    const int v = min(max(ct.win_clip[pn], 0), ct.V - 1);
+    return min(max(ct.first[v] + min(max(f, 0), ct.frames[v] - 1), 0), F - 1);
+}
+
 // InstanceNorm partials of a convolution tile, one per WAVE ROW (m tile, wm) and channel, about a PIVOT -- the value of
 // the wave's first output row in that channel: {sum(x-p), sum((x-p)^2), p, n}.  E[x^2] - mean^2 of raw fp32 sums loses
 // digits where |mean| >> std (flat or letterboxed frames, large biases); sums about a value of the data do not, and
@@ -387,8 +402,10 @@ int launch_resize_into_bf16(const void* src, int F, int Hs, int Ws, int C, void*
 int launch_point_sample(const float* level0, int B, int S, int H8, int W8, const float* xy, int N,
                         float* out, hipStream_t st);
 // S: frame slots per clip in the buffer; T: logical frames (window starts are clamped to T - 1, then taken mod S)
+// clips (last argument of the windowed launchers): the video table of windows on a flat cache of several videos, or null
 int launch_point_sample_strided(const float* level0, int B, int S, int T, int H8, int W8, const float* xy,
-                                int xy_stride, int N, const int* win_start, float* out, hipStream_t st);
+                                int xy_stride, int N, const int* win_start, float* out, hipStream_t st,
+                                const ClipTable* clips = nullptr);
 // Sw (last argument of the tracker launchers): the window length = mixer rows per particle; PIPS_S runs the specialised kernels
 int launch_init_coords(const float* xys, const float* coords_init, int B, int N, float stride,
                        float* coords, float* coords0, float* out_traj0, hipStream_t st, int Sw = PIPS_S);
@@ -396,12 +413,14 @@ int launch_init_ffeats(const float* ffeat0, int BN, float* ffeats, hipStream_t s
 // S: frame slots per clip in the pyramid, T: logical frames (the clamp bound; frame f is read from slot f mod S)
 int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
                        int B, int S, int T, const float* ffeats, const float* coords, const float* times,
-                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S);
+                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S,
+                       const ClipTable* clips = nullptr);
 // win_dir (B*N, sign = time direction of each particle's window, null = forward) is read only with win_start
 // the direct gather on the bf16 mirror of the pyramid (PIPS_FLAG_BF16_MAPS), and the pass that writes the mirror
 int launch_mixer_input_bf16maps(const void* mirror, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B, int S,
                                 int T, const float* ffeats, const float* coords, const float* times, int N,
-                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S);
+                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw = PIPS_S,
+                                const ClipTable* clips = nullptr);
 int launch_pyramid_mirror(const float* pyramid, size_t floats, void* mirror, hipStream_t st);
 // k encoded frames (levels at src_off, pf8[l] = 8-float groups per frame of level l) -> ring slots (T0 + i) mod R of a pyramid
 // with levels at dst_off and its bf16 mirror at dst_mirror (same element offsets as the fp32 levels), in one pass
@@ -433,11 +452,15 @@ int launch_state_update(const float* arena, const float* delta, float* ffeats, f
 // thr after k decrements of chain_demo.py:64,75 (doubles, rounded to fp32), k in 0..63; host function
 float chain_threshold(int k);
 // the staging arrays of one hop (B = 1, N = n_act) for the particles active[0..n_act) of a caller-owned chaining state
+// clip (n) + clip_frames (V): the video of each particle and the videos' lengths (several videos in one state), or null; wc
+// (n_act) then receives the staged video indices next to ws / wd
 int launch_chain_gather(const float* trajs, int L, int base, int n, const int* cur, const int* dir, const float* feat,
-                        const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, hipStream_t st);
+                        const int* active, int n_act, int sample_feat, float* xy, int* ws, int* wd, float* fi, hipStream_t st,
+                        const int* clip = nullptr, int* wc = nullptr);
 // write-back of the hop's windows, skip scan, new window starts and the stable compaction of the live particles
 int launch_chain_step(const float* win_trajs, const float* win_vis, const float* win_ffeat0, int n, const int* active, int n_act,
                       int sample_feat, float* trajs, float* vis, int L, int base, int T, int* cur, const int* dir, float* feat,
-                      int* next_active, int* next_count, int* steps, hipStream_t st);
+                      int* next_active, int* next_count, int* steps, hipStream_t st, const int* clip = nullptr,
+                      const int* clip_frames = nullptr, int V = 0);
 
 }  // namespace pips

@@ -17,10 +17,12 @@ constexpr int C = PIPS_C;
 // in the reference's order (samp.py:59-65).  128 threads = 128 channels of one point.
 // The map buffer holds R frame slots per clip; T_ logical frames: window start f reads slot
 // clamp(f, 0, T_-1) mod R (ring_slot).  A linear cache is R = T_.
+// ct.win_clip != null (several videos on one flat linear cache, B = 1, T_ = all frames): particle pn belongs to video
+// v = ct.win_clip[pn] and its window start is a frame of that video -- flat frame ct.first[v] + clamp(f, 0, ct.frames[v]-1).
 __global__ __launch_bounds__(128) void point_sample_kernel(const float* __restrict__ level0, int S_, int T_,
                                                            int H, int W, const float* __restrict__ xy,
                                                            int xy_stride, int N,
-                                                           const int* __restrict__ win_start,
+                                                           const int* __restrict__ win_start, const ClipTable ct,
                                                            float* __restrict__ out) {
     const int pn = blockIdx.x;            // b*N + n
     const int b = pn / N;
@@ -31,7 +33,8 @@ __global__ __launch_bounds__(128) void point_sample_kernel(const float* __restri
     const int y0 = min(max((int)y0f, 0), H - 1), y1 = min(max((int)y0f + 1, 0), H - 1);
     const float w00 = __fmul_rn(x1f - x, y1f - y), w01 = __fmul_rn(x - x0f, y1f - y);
     const float w10 = __fmul_rn(x1f - x, y - y0f), w11 = __fmul_rn(x - x0f, y - y0f);
-    const int f_first = win_start != nullptr ? ring_slot(min(max(win_start[pn], 0), T_ - 1), S_) : 0;
+    int f_first = win_start != nullptr ? ring_slot(min(max(win_start[pn], 0), T_ - 1), S_) : 0;
+    if (ct.win_clip != nullptr) f_first = clip_frame(ct, pn, win_start[pn], T_);
     const float* f0 = level0 + ((size_t)b * S_ + f_first) * H * W * C;   // first frame of the window
     const int c = threadIdx.x;
     const float v00 = f0[((size_t)y0 * W + x0) * C + c], v01 = f0[((size_t)y0 * W + x1) * C + c];
@@ -43,9 +46,9 @@ __global__ __launch_bounds__(128) void point_sample_kernel(const float* __restri
 }
 
 int launch_point_sample_strided(const float* level0, int B, int S_, int T_, int H8, int W8, const float* xy,
-                                int xy_stride, int N, const int* win_start, float* out, hipStream_t st) {
+                                int xy_stride, int N, const int* win_start, float* out, hipStream_t st, const ClipTable* clips) {
     hipLaunchKernelGGL(point_sample_kernel, dim3(B * N), dim3(128), 0, st, level0, S_, T_, H8, W8, xy,
-                       xy_stride, N, win_start, out);
+                       xy_stride, N, win_start, clips != nullptr ? *clips : ClipTable{}, out);
     PIPS_CHECK_LAUNCH("point_sample_kernel");
     return PIPS_OK;
 }
@@ -149,14 +152,16 @@ __device__ __forceinline__ void level_sample_geometry(float cxm, float cym, int 
 // waves_per_eu(2,4): let the compiler spend up to 128 VGPRs so 16 x 1 KiB loads stay in flight per
 // wave (left alone it squeezes into 64 VGPRs for 8 waves/SIMD and issues the loads two at a time)
 // SCT: window length (mixer rows per particle) as a compile-time constant, 0 = the run-time argument Srt (Pips(S != 8))
-template <int SCT>
+// CLIP: the windows carry a video index (ct.win_clip, see point_sample_kernel).  A template parameter, so that the plain
+// instantiations are the code they were before the clip table existed (ct is an unread kernel argument there).
+template <int SCT, bool CLIP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void mixer_input_kernel(const float* __restrict__ pyramid,
                                                           LevelTable lv, int S_, int T_, int Srt,
                                                           const float* __restrict__ ffeats,
                                                           const float* __restrict__ coords,
                                                           const float* __restrict__ times, int N,
                                                           const int* __restrict__ win_start,
-                                                          const int* __restrict__ win_dir,
+                                                          const int* __restrict__ win_dir, const ClipTable ct,
                                                           float* __restrict__ X) {
     __shared__ float Dw[PIPS_LEVELS][64];
     const int S = SCT ? SCT : Srt;                       // (shadows the file-scope constant)
@@ -175,7 +180,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         fstart = win_start[pn];
         if (win_dir != nullptr) dir = win_dir[pn] < 0 ? -1 : 1;
     }
-    const int frame = b * S_ + ring_slot(min(max(fstart + dir * s, 0), T_ - 1), S_);
+    // CLIP: the clamp stops at the ends of the particle's own video (B = 1, T_ = the frames of all videos)
+    const int frame = CLIP ? clip_frame(ct, pn, fstart + dir * s, T_) : b * S_ + ring_slot(min(max(fstart + dir * s, 0), T_ - 1), S_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lvl = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float cxm = coords[(size_t)m * 2 + 0], cym = coords[(size_t)m * 2 + 1];
@@ -268,11 +274,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 // lanes of a pixel group: lane r of group g ends with window row r >> 1, column 4 * (r & 1) + g.
 // The window frame, the 49-tap blend and the tail after the correlation block are mixer_input_kernel's, statement for statement (its
 // comments hold): written as shared inline functions they made hipcc emit different code for both kernels, so they stay in the bodies.
-template <int SCT>
+template <int SCT, bool CLIP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void mixer_input_bf16maps_kernel(
     const unsigned short* __restrict__ mirror, LevelTable lv, int S_, int T_, int Srt, const float* __restrict__ ffeats,
     const float* __restrict__ coords, const float* __restrict__ times, int N, const int* __restrict__ win_start,
-    const int* __restrict__ win_dir, float* __restrict__ X) {
+    const int* __restrict__ win_dir, const ClipTable ct, float* __restrict__ X) {
     __shared__ float Dw[PIPS_LEVELS][64];
     const int S = SCT ? SCT : Srt;
     const int m = blockIdx.x;
@@ -283,7 +289,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         fstart = win_start[pn];
         if (win_dir != nullptr) dir = win_dir[pn] < 0 ? -1 : 1;
     }
-    const int frame = b * S_ + ring_slot(min(max(fstart + dir * s, 0), T_ - 1), S_);
+    // CLIP: the clamp stops at the ends of the particle's own video (B = 1, T_ = the frames of all videos)
+    const int frame = CLIP ? clip_frame(ct, pn, fstart + dir * s, T_) : b * S_ + ring_slot(min(max(fstart + dir * s, 0), T_ - 1), S_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lvl = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float cxm = coords[(size_t)m * 2 + 0], cym = coords[(size_t)m * 2 + 1];
@@ -371,22 +378,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 }
 #undef PIPS_TR_STEP
 
-// Both direct gathers: bf16_maps = the maps are the pyramid's bf16 mirror (mixer_input_bf16maps_kernel)
+// Both direct gathers: bf16_maps = the maps are the pyramid's bf16 mirror (mixer_input_bf16maps_kernel); clips: the windows'
+// video table (the CLIP instantiations), null = one video per clip of the batch
 static int launch_direct_gather(const void* maps, bool bf16_maps, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B,
                                 int S_, int T_, const float* ffeats, const float* coords, const float* times, int N,
-                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
+                                const int* win_start, const int* win_dir, const ClipTable* clips, float* X, hipStream_t st, int Sw) {
     LevelTable lv;
     for (int l = 0; l < PIPS_LEVELS; ++l) { lv.off[l] = lvl_off[l]; lv.H[l] = lvlH[l]; lv.W[l] = lvlW[l]; }
+    const ClipTable ct = clips != nullptr ? *clips : ClipTable{};
     auto launch = [&](auto kern, auto* typed_maps) {
         hipLaunchKernelGGL(kern, dim3(B * N * Sw), dim3(256), 0, st, typed_maps, lv, S_, T_, Sw, ffeats, coords, times, N,
-                           win_start, win_dir, X);
+                           win_start, win_dir, ct, X);
     };
+    const bool s8 = Sw == PIPS_S, clip = ct.win_clip != nullptr;
     if (bf16_maps) {
         const unsigned short* mp = reinterpret_cast<const unsigned short*>(maps);
-        if (Sw == PIPS_S) launch(mixer_input_bf16maps_kernel<PIPS_S>, mp); else launch(mixer_input_bf16maps_kernel<0>, mp);
+        if (clip) { if (s8) launch(mixer_input_bf16maps_kernel<PIPS_S, true>, mp); else launch(mixer_input_bf16maps_kernel<0, true>, mp); }
+        else if (s8) launch(mixer_input_bf16maps_kernel<PIPS_S, false>, mp);
+        else launch(mixer_input_bf16maps_kernel<0, false>, mp);
     } else {
         const float* pp = reinterpret_cast<const float*>(maps);
-        if (Sw == PIPS_S) launch(mixer_input_kernel<PIPS_S>, pp); else launch(mixer_input_kernel<0>, pp);
+        if (clip) { if (s8) launch(mixer_input_kernel<PIPS_S, true>, pp); else launch(mixer_input_kernel<0, true>, pp); }
+        else if (s8) launch(mixer_input_kernel<PIPS_S, false>, pp);
+        else launch(mixer_input_kernel<0, false>, pp);
     }
     PIPS_CHECK_LAUNCH(bf16_maps ? "mixer_input_bf16maps_kernel" : "mixer_input_kernel");
     return PIPS_OK;
@@ -394,14 +408,14 @@ static int launch_direct_gather(const void* maps, bool bf16_maps, const size_t* 
 
 int launch_mixer_input(const float* pyramid, const size_t* lvl_off, const int* lvlH, const int* lvlW,
                        int B, int S_, int T_, const float* ffeats, const float* coords, const float* times,
-                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
-    return launch_direct_gather(pyramid, false, lvl_off, lvlH, lvlW, B, S_, T_, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
+                       int N, const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw, const ClipTable* clips) {
+    return launch_direct_gather(pyramid, false, lvl_off, lvlH, lvlW, B, S_, T_, ffeats, coords, times, N, win_start, win_dir, clips, X, st, Sw);
 }
 
 int launch_mixer_input_bf16maps(const void* mirror, const size_t* lvl_off, const int* lvlH, const int* lvlW, int B, int S_,
                                 int T_, const float* ffeats, const float* coords, const float* times, int N,
-                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw) {
-    return launch_direct_gather(mirror, true, lvl_off, lvlH, lvlW, B, S_, T_, ffeats, coords, times, N, win_start, win_dir, X, st, Sw);
+                                const int* win_start, const int* win_dir, float* X, hipStream_t st, int Sw, const ClipTable* clips) {
+    return launch_direct_gather(mirror, true, lvl_off, lvlH, lvlW, B, S_, T_, ffeats, coords, times, N, win_start, win_dir, clips, X, st, Sw);
 }
 
 // fp32 pyramid -> its bf16 mirror (same element offsets), 8 values per thread

@@ -12,6 +12,9 @@
 * ``StreamTracker`` / ``track_stream`` -- ``track_queries``' forward chains on a video fed in chunks: frames are
   encoded into a ring of ``slots`` frames (``Pips.ring_cache``) and trajectories come back as frames become final,
   so device memory does not grow with the length of the video.
+* ``track_chained_batch`` / ``track_queries_batch`` -- the same two drivers over a LIST of videos (equal frame size, any
+  lengths) in one set of hop launches: the videos share one flat cache (``Pips.encode_videos``), every particle carries the
+  index of its video (``Pips.track``'s ``win_clip``), and each video gets what its single-video driver returns, bit for bit.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -65,11 +68,12 @@ def skip_scan(vis):
     return last + 2
 
 
-def _hop(model, cache, trajs, vis_p, base, cur, active, feat, d=None, iters=6):
+def _hop(model, cache, trajs, vis_p, base, cur, active, feat, d=None, iters=6, clip=None):
     """One window of chain_demo.py:40-83 for each particle in ``active``: its start position is its trajectory at its window
     start ``cur[active]`` (logical frames), its rows are written back and ``skip_scan`` gives the step.  trajs (L,n,2) and
     vis_p (L,n) (or None) hold frame f in row (f + base) mod L.  feat: (n,128) features carried from the first window, or
-    None (the track call samples them); d: the active particles' directions (+1 / -1) or None (all forward).
+    None (the track call samples them); d: the active particles' directions (+1 / -1) or None (all forward); clip: the active
+    particles' videos on a cache of several (``cur`` then counts frames of the particle's own video) or None.
     -> (the new window starts of ``active``, their steps si, the features of this call (n_active,128))."""
     S = 8
     L = trajs.shape[0]
@@ -81,6 +85,8 @@ def _hop(model, cache, trajs, vis_p, base, cur, active, feat, d=None, iters=6):
     if d is not None:
         kw["win_dir"] = d.to(torch.int32).unsqueeze(0)
         rows = rows * d.unsqueeze(0)                                              # row s of a window is frame c + d * s
+    if clip is not None:
+        kw["win_clip"] = clip.to(torch.int32).unsqueeze(0)
     preds, _, vis, ffeat, _ = model.track(cache, start_xy, iters=iters, feat_init=fi,
                                           win_start=c.to(torch.int32).unsqueeze(0), return_feat=True, **kw)
     rows = (c.unsqueeze(0) + rows + base) % L                                     # (S,n)
@@ -100,13 +106,21 @@ def _check_engine(engine):
         raise ValueError(f"engine must be one of {ENGINES}, not {engine!r}")
 
 
-def _chain_native(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, want_log=True):
+def _rows(T):
+    """T = frames of the one video, or (n,) frames of each particle's video -> the frames the output buffer holds"""
+    return int(T.max()) if torch.is_tensor(T) else T
+
+
+def _chain_native(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, want_log=True, clip=None):
     """``_chain`` with every hop as one ``pips_chain_hop`` call: the state (window starts, directions, the two ping-pong
-    lists of active particles) is int32 on the device and the loop reads the live count where ``_chain`` reads it."""
+    lists of active particles) is int32 on the device and the loop reads the live count where ``_chain`` reads it.  With
+    ``clip`` the library takes the videos' lengths from the cache's clip table; ``T`` only sizes the output."""
     dev = xy.device
     pad = 7
     n = xy.shape[0]
     i32 = torch.int32
+    T = _rows(T)
+    c32 = None if clip is None else clip.to(i32).contiguous()
     trajs = torch.zeros(T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
     vis_p = torch.zeros(T + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
     trajs[f0 + pad, torch.arange(n, device=dev)] = xy.to(torch.float32)
@@ -118,7 +132,8 @@ def _chain_native(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, wa
     steps = torch.empty(n, dtype=i32, device=dev) if want_log else None
     log, n_act, first = [], n, True
     while n_act > 0:
-        model.chain_hop(cache, active, n_act, trajs, vis_p, pad, cur, d32, feat, nxt, count, steps, iters=iters, sample_feat=first)
+        model.chain_hop(cache, active, n_act, trajs, vis_p, pad, cur, d32, feat, nxt, count, steps, iters=iters, sample_feat=first,
+                        clip=c32)
         if want_log:
             log.append((active[:n_act].clone(), steps[:n_act].clone()))
         n_act = int(count.item())                                                 # (one host sync per hop: the live count)
@@ -126,16 +141,18 @@ def _chain_native(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, wa
     return trajs[pad:pad + T], None if vis_p is None else vis_p[pad:pad + T], log
 
 
-def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, engine="torch", want_log=True):
+def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, engine="torch", want_log=True, clip=None):
     """The hop loop on the chosen engine -> (trajs, vis, hop log).  ``want_log=False`` spares the native engine the two copies
     per hop that keep ``active`` / ``steps`` for the log (its buffers are reused by the next hop) and its log comes back
-    empty; the torch engine's log is made of the tensors the hop produced anyway, so it is returned either way."""
+    empty; the torch engine's log is made of the tensors the hop produced anyway, so it is returned either way.
+    ``clip`` (n,) int64: the particles of several videos on one cache (``Pips.encode_videos``) -- the video of each particle,
+    ``T`` then (n,) int64, the frames of each particle's video; trajs / vis come back with max(T) rows."""
     if engine == "native":
-        return _chain_native(model, cache, T, xy, f0, dirs, iters, with_vis, want_log)
-    return _chain_torch(model, cache, T, xy, f0, dirs, iters, with_vis)
+        return _chain_native(model, cache, T, xy, f0, dirs, iters, with_vis, want_log, clip)
+    return _chain_torch(model, cache, T, xy, f0, dirs, iters, with_vis, clip)
 
 
-def _chain_torch(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
+def _chain_torch(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, clip=None):
     """The hop loop of chain_demo.py:40-83 for all particles at once.  xy (n,2) px at frames f0 (n,) int64; dirs (n,) +1 / -1
     per particle or None (all forward).  A backward particle runs the loop on the time-reversed video: its window rows
     read f, f-1, ... (``Pips.track``'s ``win_dir``) and it is finished when its start passes frame 0.
@@ -144,6 +161,7 @@ def _chain_torch(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
     dev = xy.device
     pad = 7
     n = xy.shape[0]
+    Tq, T = T, _rows(T)                                                            # per-particle bound (clip) or the int itself
     # S - 1 frames of padding on both sides of the video: a window that runs past either end is written whole and cut off
     # on return (no per-row masks, no host round trips inside a hop)
     trajs = torch.zeros(T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
@@ -154,12 +172,14 @@ def _chain_torch(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True):
     feat = None
     log = []
     while active.numel() > 0:
-        c, si, ffeat = _hop(model, cache, trajs, vis_p, pad, cur, active, feat, None if dirs is None else dirs[active], iters)
+        c, si, ffeat = _hop(model, cache, trajs, vis_p, pad, cur, active, feat, None if dirs is None else dirs[active], iters,
+                            None if clip is None else clip[active])
         if feat is None:
             feat = ffeat.clone()                                                   # carried forever (:57)
         cur[active] = c
         log.append((active, si))
-        live = c < T if dirs is None else (c < T) & (c >= 0)
+        end = T if clip is None else Tq[active]                                   # the end of each particle's own video
+        live = c < end if dirs is None else (c < end) & (c >= 0)
         active = active[live]                                                     # (one host sync per hop: the live count)
     return trajs[pad:pad + T], None if vis_p is None else vis_p[pad:pad + T], log
 
@@ -222,6 +242,19 @@ def track_queries(model, rgbs, queries, iters=6, return_hops=False, engine="torc
     assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
     dev = rgbs.device
     T, N = rgbs.shape[1], queries.shape[1]
+    xy, f0, dirs, tq_d, back = _query_particles(queries, T, dev)
+    cache = model.encode(rgbs)
+    tr, vi, log = _chain(model, cache, T, xy, f0, dirs, iters=iters, engine=engine, want_log=return_hops)
+    trajs, vis = _join_directions(tr, vi, N, tq_d, back.to(dev))
+    if not return_hops:
+        return trajs, vis
+    return trajs, vis, _query_hops(_hops(log, N + back.numel()), N, back)
+
+
+def _query_particles(queries, T, dev):
+    """The particles of one video's queries (1,N,3): the N forward ones, then a backward one for every query with t > 0.
+    -> (xy (n,2), f0 (n,), dirs (n,), the query frames on the device, the queries that have a backward particle (host))."""
+    N = queries.shape[1]
     tq = _query_frames(queries, T)
     back = torch.nonzero(tq > 0).squeeze(1)
     nb = back.numel()
@@ -229,20 +262,89 @@ def track_queries(model, rgbs, queries, iters=6, return_hops=False, engine="torc
     tq_d, back_d = tq.to(dev), back.to(dev)
     f0 = torch.cat([tq_d, tq_d[back_d]])
     dirs = torch.cat([torch.ones(N, dtype=torch.int64, device=dev), torch.full((nb,), -1, dtype=torch.int64, device=dev)])
-    cache = model.encode(rgbs)
-    tr, vi, log = _chain(model, cache, T, torch.cat([xy, xy[back_d]]), f0, dirs, iters=iters, engine=engine, want_log=return_hops)
+    return torch.cat([xy, xy[back_d]]), f0, dirs, tq_d, back
+
+
+def _join_directions(tr, vi, N, tq_d, back_d):
+    """tr (T,N+nb,2), vi (T,N+nb) of ``_query_particles``' particles -> trajs (1,T,N,2), vis (1,T,N): frames before a query's
+    frame come from its backward chain."""
+    T = tr.shape[0]
     trajs, vis = tr[:, :N].clone(), vi[:, :N].clone()
-    before = torch.arange(T, device=dev).unsqueeze(1) < tq_d[back_d].unsqueeze(0)     # (T,nb): frames of the backward chain
+    before = torch.arange(T, device=tr.device).unsqueeze(1) < tq_d[back_d].unsqueeze(0)     # (T,nb): frames of the backward chain
     trajs[:, back_d] = torch.where(before.unsqueeze(-1), tr[:, N:], trajs[:, back_d])
     vis[:, back_d] = torch.where(before, vi[:, N:], vis[:, back_d])
-    trajs, vis = trajs.unsqueeze(0), vis.unsqueeze(0)
-    if not return_hops:
-        return trajs, vis
-    hops = _hops(log, N + nb)
+    return trajs.unsqueeze(0), vis.unsqueeze(0)
+
+
+def _query_hops(hops, N, back):
+    """the hop lists of ``_query_particles``' particles -> (forward, backward) per query"""
     bwd = [[] for _ in range(N)]
     for j, q in enumerate(back.tolist()):
         bwd[q] = hops[N + j]
-    return trajs, vis, (hops[:N], bwd)
+    return hops[:N], bwd
+
+
+def _check_videos(model, videos, per_video, what):
+    """The argument checks of the batch drivers -> the videos' lengths."""
+    assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
+    videos, per_video = list(videos), list(per_video)
+    if not videos or len(videos) != len(per_video):
+        raise ValueError(f"{len(videos)} videos but {len(per_video)} {what}")
+    for v in videos:
+        if v.dim() != 5 or v.shape[0] != 1:
+            raise ValueError(f"every video must be (1,T,3,H,W), not {tuple(v.shape)}")
+        if tuple(v.shape[2:]) != tuple(videos[0].shape[2:]):
+            raise ValueError(f"the videos of one call share a frame size: {tuple(v.shape[2:])} against {tuple(videos[0].shape[2:])}")
+    return [int(v.shape[1]) for v in videos]
+
+
+@torch.no_grad()
+def track_chained_batch(model, videos, xy0s, iters=6, return_hops=False, engine="torch"):
+    """``track_chained`` over several videos in one set of hop launches.  videos: list of (1,T_v,3,H,W) of one frame size,
+    xy0s: list of (1,N_v,2) px at frame 0 of each -> the list, per video, of what ``track_chained(model, video, xy0)`` returns
+    (bit for bit while the mixer's GEMMs take the same route at the batched and at the single-video row counts)."""
+    _check_engine(engine)
+    lengths = _check_videos(model, videos, xy0s, "start point sets")
+    dev = videos[0].device
+    counts = [int(x.shape[1]) for x in xy0s]
+    n = sum(counts)
+    clip = torch.repeat_interleave(torch.arange(len(lengths)), torch.tensor(counts)).to(dev)
+    Tq = torch.tensor(lengths)[clip.cpu()].to(dev)
+    cache = model.encode_videos(videos)
+    trajs, _, log = _chain(model, cache, Tq, torch.cat([x[0].to(dev) for x in xy0s]), torch.zeros(n, dtype=torch.int64, device=dev),
+                           iters=iters, with_vis=False, engine=engine, want_log=return_hops, clip=clip)
+    hops = _hops(log, n) if return_hops else None
+    out, p0 = [], 0
+    for T, N in zip(lengths, counts):
+        tr = trajs[:T, p0:p0 + N].unsqueeze(0).contiguous()
+        out.append((tr, hops[p0:p0 + N]) if return_hops else tr)
+        p0 += N
+    return out
+
+
+@torch.no_grad()
+def track_queries_batch(model, videos, queries, iters=6, return_hops=False, engine="torch"):
+    """``track_queries`` over several videos in one set of hop launches.  videos: list of (1,T_v,3,H,W) of one frame size,
+    queries: list of (1,N_v,3) = (t, x, y) with ``t`` a frame of ITS video -> the list, per video, of the ``(trajs, vis[, hops])``
+    of ``track_queries(model, video, queries_v)`` (bit for bit, as ``track_chained_batch``)."""
+    _check_engine(engine)
+    lengths = _check_videos(model, videos, queries, "query sets")
+    dev = videos[0].device
+    parts = [_query_particles(q, T, dev) for q, T in zip(queries, lengths)]        # (a query frame past its OWN video raises here)
+    counts = [p[0].shape[0] for p in parts]
+    clip = torch.repeat_interleave(torch.arange(len(lengths)), torch.tensor(counts)).to(dev)
+    Tq = torch.tensor(lengths)[clip.cpu()].to(dev)
+    cache = model.encode_videos(videos)
+    tr, vi, log = _chain(model, cache, Tq, torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]),
+                         torch.cat([p[2] for p in parts]), iters=iters, engine=engine, want_log=return_hops, clip=clip)
+    hops = _hops(log, sum(counts)) if return_hops else None
+    out, p0 = [], 0
+    for T, n, q, (_, _, _, tq_d, back) in zip(lengths, counts, queries, parts):
+        N = q.shape[1]
+        res = _join_directions(tr[:T, p0:p0 + n], vi[:T, p0:p0 + n], N, tq_d, back.to(dev))
+        out.append(res + (_query_hops(hops[p0:p0 + n], N, back),) if return_hops else res)
+        p0 += n
+    return out
 
 
 class StreamTracker:

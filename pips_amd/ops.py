@@ -147,6 +147,22 @@ def mixer_input_build(pyr, B, H8, W8, ffeats, coords, bf16_maps=False):
     return X
 
 
+def mixer_input_build_clips(pyr, T, H8, W8, ffeats, coords, win_start, win_dir, win_clip, clip_first, clip_frames,
+                            bf16_maps=False, S=8):
+    """pips_mixer_input_build_clips on a linear cache of T frames (B = 1): ffeats (N*S,128), coords (N*S,2) particle-major,
+    win_start / win_dir / win_clip (N) int32 (the last two may be None) and the clip table -> X (N*S, 544).  win_clip = None is
+    pips_mixer_input_build_win."""
+    ffeats, coords = _f32(ffeats), _f32(coords)
+    M = ffeats.shape[0]
+    X = torch.empty(M, KIN_PAD, dtype=torch.float32, device=ffeats.device)
+    tt = times_table(ffeats.device, S)
+    with torch.cuda.device(ffeats.device):
+        _call("pips_mixer_input_build_clips", _lib.ptr(pyr), 1, int(T), int(T), int(H8), int(W8), _lib.ptr(ffeats), _lib.ptr(coords),
+              _lib.ptr(tt), M // S, _i32(win_start), _i32(win_dir), _i32(win_clip), _i32(clip_first), _i32(clip_frames),
+              0 if clip_frames is None else clip_frames.numel(), FLAG_BF16_MAPS if bf16_maps else 0, int(S), _lib.ptr(X), _stream())
+    return X
+
+
 def pyramid_mirror(pyr, F, H, W, stride):
     """(re)write the bf16 mirror of a packed pyramid buffer from its fp32 levels (pips_pyramid_mirror)"""
     with torch.cuda.device(pyr.device):
@@ -278,15 +294,23 @@ def _chain_f32(t):
     return _lib.ptr(t)
 
 
-def chain_gather(trajs, base, cur, dirs, feat, active, n_act, sample_feat=False):
+def chain_gather(trajs, base, cur, dirs, feat, active, n_act, sample_feat=False, clip=None):
     """pips_chain_gather: the staging arrays of one hop for ``active[:n_act]`` -> (xy (n_act,2), ws, wd (n_act) int32,
-    fi (n_act,128); fi is left unwritten with ``sample_feat``).  trajs (L,n,2); cur / dirs / active int32, dirs may be None."""
+    fi (n_act,128); fi is left unwritten with ``sample_feat``).  trajs (L,n,2); cur / dirs / active int32, dirs may be None.
+    ``clip`` (n) int32: pips_chain_gather_clips -> (xy, ws, wd, wc, fi), wc (n_act) the staged video indices."""
     L, n = trajs.shape[0], trajs.shape[1]
     dev = trajs.device
     xy = torch.empty(n_act, 2, dtype=torch.float32, device=dev)
     ws = torch.empty(n_act, dtype=torch.int32, device=dev)
     wd = torch.empty(n_act, dtype=torch.int32, device=dev)
     fi = torch.empty(n_act, LATENT, dtype=torch.float32, device=dev)
+    if clip is not None:
+        wc = torch.empty(n_act, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _call("pips_chain_gather_clips", _chain_f32(trajs), L, int(base), n, _i32(cur), _i32(dirs), _i32(clip), _chain_f32(feat),
+                  _i32(active), int(n_act), int(bool(sample_feat)), _lib.ptr(xy), _lib.ptr(ws), _lib.ptr(wd), _lib.ptr(wc), _lib.ptr(fi),
+                  _stream())
+        return xy, ws, wd, wc, fi
     with torch.cuda.device(dev):
         _call("pips_chain_gather", _chain_f32(trajs), L, int(base), n, _i32(cur), _i32(dirs), _chain_f32(feat), _i32(active), int(n_act),
               int(bool(sample_feat)), _lib.ptr(xy), _lib.ptr(ws), _lib.ptr(wd), _lib.ptr(fi), _stream())
@@ -294,23 +318,38 @@ def chain_gather(trajs, base, cur, dirs, feat, active, n_act, sample_feat=False)
 
 
 def chain_step(win_trajs, win_vis, win_ffeat0, T, active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count,
-               steps=None, sample_feat=False):
+               steps=None, sample_feat=False, clips=None):
     """pips_chain_step, in place on the caller's state: write-back of the windows win_trajs (8,n_act,2) / win_vis (8,n_act),
     skip scan, ``cur`` (and, with ``sample_feat``, ``feat`` from win_ffeat0 (n_act,128)) update, and the live members of
-    ``active[:n_act]`` in their order in ``next_active`` with their number in ``next_count`` (device int32, not read back here)."""
+    ``active[:n_act]`` in their order in ``next_active`` with their number in ``next_count`` (device int32, not read back here).
+    ``clips`` = (clip (n), clip_frames (V)) int32: pips_chain_step_clips, live = inside the particle's own video."""
     L, n = trajs.shape[0], trajs.shape[1]
     with torch.cuda.device(trajs.device):
+        if clips is not None:
+            clip, frames = clips
+            _call("pips_chain_step_clips", _chain_f32(win_trajs), _chain_f32(win_vis), _chain_f32(win_ffeat0), int(T), n, _i32(active),
+                  int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L, int(base), _i32(cur), _i32(dirs), _i32(clip),
+                  _i32(frames), frames.numel(), _chain_f32(feat), _i32(next_active), _i32(next_count), _i32(steps), _stream())
+            return
         _call("pips_chain_step", _chain_f32(win_trajs), _chain_f32(win_vis), _chain_f32(win_ffeat0), int(T), n, _i32(active), int(n_act),
               int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L, int(base), _i32(cur), _i32(dirs), _chain_f32(feat),
               _i32(next_active), _i32(next_count), _i32(steps), _stream())
 
 
 def chain_hop(arena, pyr, T, R, H8, W8, times, stride, iters, flags, active, n_act, trajs, vis, base, cur, dirs, feat,
-              next_active, next_count, steps, workspace, sample_feat=False):
+              next_active, next_count, steps, workspace, sample_feat=False, clips=None):
     """pips_chain_hop: one hop of chain_demo.py:40-83 for ``active[:n_act]``, in place on the caller's state (see chain_step),
-    on the packed pyramid ``pyr`` of R frame slots holding T logical frames.  No host synchronisation."""
+    on the packed pyramid ``pyr`` of R frame slots holding T logical frames.  No host synchronisation.
+    ``clips`` = (clip (n), clip_first (V), clip_frames (V)) int32: pips_chain_hop_clips on a flat cache of V videos."""
     L, n = trajs.shape[0], trajs.shape[1]
     with torch.cuda.device(trajs.device):
+        if clips is not None:
+            clip, first, frames = clips
+            _call("pips_chain_hop_clips", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
+                  int(iters), int(flags), n, _i32(active), int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L,
+                  int(base), _i32(cur), _i32(dirs), _i32(clip), _i32(first), _i32(frames), frames.numel(), _chain_f32(feat),
+                  _i32(next_active), _i32(next_count), _i32(steps), _lib.ptr(workspace), workspace.numel() * 4, _stream())
+            return
         _call("pips_chain_hop", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
               int(iters), int(flags), n, _i32(active), int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L,
               int(base), _i32(cur), _i32(dirs), _chain_f32(feat), _i32(next_active), _i32(next_count), _i32(steps),

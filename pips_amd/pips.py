@@ -42,12 +42,17 @@ class FeatureCache:
     ``slots``: frame slots the buffer is laid out for (default ``T``: a linear cache).  A ring cache
     (``Pips.ring_cache``) has a fixed number of slots and grows ``T`` as frames are appended
     (``Pips.encode(..., into=cache)``); logical frame ``f`` lives in slot ``f % slots``, so only the
-    last ``slots`` frames are held."""
+    last ``slots`` frames are held.
+
+    A cache of several videos (``Pips.encode_videos``) is linear with ``B = 1``: its ``T`` frames are the videos' frames one
+    after the other, ``clip_lengths`` (host list) / ``clip_frames`` (device int32) the frames of each video and ``clip_first``
+    (device int32) its first flat frame -- the clip table of ``pips_track_clips``.  ``None`` on every other cache."""
 
     def __init__(self, pyr, B, T, H, W, stride, bf16_maps=False, slots=None):
         self.pyr, self.B, self.T, self.H, self.W, self.stride = pyr, B, T, H, W, stride
         self.bf16_maps = bf16_maps          # the buffer's bf16 mirror is valid (written by the bf16 encoder): PIPS_FLAG_BF16_MAPS
         self.slots = T if slots is None else int(slots)
+        self.clip_first = self.clip_frames = self.clip_lengths = None
 
     @property
     def map_size(self):
@@ -316,6 +321,53 @@ class Pips(nn.Module):
                     ops.pyramid_mirror(pyr, F, H, W, st)
         return FeatureCache(pyr, B, T, H, W, st, bf16_maps=eb and not sp)
 
+    @torch.no_grad()
+    def encode_videos(self, videos, frames_per_pass: int = 16) -> FeatureCache:
+        """One flat ``FeatureCache`` for a list of videos ``(1,T_v,3,H,W)`` of equal ``H, W`` (lengths may differ): B = 1, the
+        frames of video 0, then of video 1, ...  Every video goes through the encoder passes ``encode`` would run for it alone
+        (at most ``frames_per_pass`` frames each, counted from its own frame 0) and the passes are copied into the flat levels,
+        so each video's maps are the bits of ``encode(video)``; the bf16 mirror is written once, over the whole buffer.  The
+        cache carries the clip table ``track(..., win_clip=)`` and ``chain_hop(..., clip=)`` read."""
+        videos = list(videos)
+        if not videos:
+            raise ValueError("encode_videos needs at least one video")
+        H, W = videos[0].shape[-2:]
+        for v in videos:
+            if v.dim() != 5 or v.shape[0] != 1 or v.shape[2] != 3 or v.shape[1] < 1:
+                raise ValueError(f"every video must be (1,T,3,H,W) with T >= 1, not {tuple(v.shape)}")
+            if tuple(v.shape[-2:]) != (H, W):
+                raise ValueError(f"the videos of one cache share a frame size: {tuple(v.shape[-2:])} against {(H, W)}")
+            if not v.is_cuda or v.device != videos[0].device:
+                raise _lib.PipsHipError("pips_amd.Pips needs CUDA/HIP tensors on one device; there is no CPU fallback")
+        lib = _lib.load()
+        dev, st = videos[0].device, int(self.stride)
+        lengths = [int(v.shape[1]) for v in videos]
+        F = sum(lengths)
+        step = max(1, int(frames_per_pass))
+        with torch.cuda.device(dev):
+            arena = self._aux(dev)[0]
+            eb = bool(self._flags() & ops.FLAG_BF16_ENCODER)
+            sp = bool(self._flags() & ops.FLAG_SPLIT_BF16)
+            pyr = torch.empty(lib.pips_pyramid_floats(F, H, W, st), dtype=torch.float32, device=dev)
+            dst = ops.pyramid_levels(pyr, F, H, W, st)
+            first = 0
+            for v, T in zip(videos, lengths):
+                frames = (v.contiguous() if v.dtype == torch.uint8 else v.contiguous().to(torch.float32)).reshape(T, 3, H, W)
+                for f0 in range(0, T, step):                               # encode()'s passes for this video
+                    f1 = min(T, f0 + step)
+                    part = ops.encoder_fwd(arena, frames[f0:f1], st, bf16=eb, split=sp)
+                    for d, p in zip(dst, ops.pyramid_levels(part, f1 - f0, H, W, st)):
+                        d[first + f0:first + f1].copy_(p)
+                first += T
+            if eb:
+                ops.pyramid_mirror(pyr, F, H, W, st)
+            cache = FeatureCache(pyr, 1, F, H, W, st, bf16_maps=eb and not sp)
+            frames_t = torch.tensor(lengths, dtype=torch.int32)
+            cache.clip_lengths = lengths
+            cache.clip_frames = frames_t.to(dev)
+            cache.clip_first = (torch.cumsum(frames_t, 0, dtype=torch.int32) - frames_t).to(dev)
+        return cache
+
     def _append(self, rgbs, frames_per_pass, cache):
         lib = _lib.load()
         B, T, C3, H, W = rgbs.shape
@@ -340,7 +392,7 @@ class Pips(nn.Module):
 
     @torch.no_grad()
     def track(self, cache: FeatureCache, xys, coords_init=None, feat_init=None, iters=3, win_start=None,
-              return_feat=False, win_dir=None):
+              return_feat=False, win_dir=None, win_clip=None):
         """The update loop of ``forward`` (nets/pips.py:450-563) on cached maps.  ``win_start``
         ``(B,N)`` int = first frame of each particle's 8-frame window inside the ``T`` cached
         frames (default 0); frames past the end repeat the last one (chain_demo.py:50-52).
@@ -348,6 +400,9 @@ class Pips(nn.Module):
         forward): row ``s`` of a backward window reads frame ``win_start - s``, frames before 0 repeat
         frame 0 -- the same loop on the time-reversed video.  On a ring cache (``cache.slots != cache.T``)
         frame ``f`` is read from slot ``f % cache.slots``: every frame a window reads must still be held.
+        ``win_clip`` ``(1,N)`` int, on a cache of several videos (``encode_videos``): the video of each particle.
+        ``win_start`` then counts frames of that video, and the repeats past its last frame and before its frame 0 stay
+        inside it; each particle gets what ``track`` on ``encode`` of its own video gives.
         Returns the same tuple as ``forward`` (losses = None)."""
         lib = _lib.load()
         B, N, D = xys.shape
@@ -365,6 +420,11 @@ class Pips(nn.Module):
             ws_i = torch.zeros(B, N, dtype=torch.int32, device=dev)
         if wd_i is not None:
             assert tuple(wd_i.shape) == (B, N)
+        wc_i = None if win_clip is None else win_clip.to(dev).contiguous().to(torch.int32)
+        if wc_i is not None:
+            if cache.clip_first is None:
+                raise ValueError("win_clip needs a cache of several videos (Pips.encode_videos)")
+            assert tuple(wc_i.shape) == (B, N) and B == 1
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
             fl = self._track_flags(cache)
@@ -379,11 +439,20 @@ class Pips(nn.Module):
             trajs = torch.empty(iters + 1, B, S, N, 2, dtype=f32, device=dev)
             vis_e = torch.empty(B, S, N, dtype=f32, device=dev)
             ffeat = torch.empty(B, N, self.latent_dim, dtype=f32, device=dev)
-            rc = lib.pips_track_ring(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
-                                     _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(times), N,
-                                     int(cache.stride), int(iters), fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs),
-                                     _lib.ptr(vis_e), _lib.ptr(ffeat), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "pips_track_ring")
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if wc_i is not None:
+                rc = lib.pips_track_clips(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
+                                          _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(wc_i),
+                                          _lib.ptr(cache.clip_first), _lib.ptr(cache.clip_frames), len(cache.clip_lengths),
+                                          _lib.ptr(times), N, int(cache.stride), int(iters), fl, S, _lib.ptr(ws), ws.numel() * 4,
+                                          _lib.ptr(trajs), _lib.ptr(vis_e), _lib.ptr(ffeat), None, None, None, 0, stream)
+                _lib.check(rc, "pips_track_clips")
+            else:
+                rc = lib.pips_track_ring(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
+                                         _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(times), N,
+                                         int(cache.stride), int(iters), fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs),
+                                         _lib.ptr(vis_e), _lib.ptr(ffeat), stream)
+                _lib.check(rc, "pips_track_ring")
         preds = [trajs[i + 1] for i in range(iters)]
         preds2 = [trajs[0], trajs[0]] + preds + [trajs[iters], trajs[iters]]
         if return_feat:
@@ -398,13 +467,18 @@ class Pips(nn.Module):
 
     @torch.no_grad()
     def chain_hop(self, cache: FeatureCache, active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps=None,
-                  iters=6, sample_feat=False):
+                  iters=6, sample_feat=False, clip=None):
         """One hop of the visibility-aware chaining (chain_demo.py:40-83) for the particles ``active[:n_act]``, in one library
         call (``pips_chain_hop``): what ``track`` plus the driver's indexed reads, scatters and skip scan do, in place on the
         caller's device state -- trajs (L,n,2) and vis (L,n) or None (frame f in row (f + base) % L), cur / dirs (None: all
         forward) / active int32, feat (n,128); the live particles land in ``next_active`` in their order and their number in
-        ``next_count`` (device int32: the caller reads it back), the steps in ``steps``.  S = 8 and one video (B = 1) only."""
+        ``next_count`` (device int32: the caller reads it back), the steps in ``steps``.  S = 8 and B = 1 only.
+        ``clip`` (n) int32, on a cache of several videos (``encode_videos``): the video of each particle
+        (``pips_chain_hop_clips``) -- ``cur`` counts frames of that video and a particle is live inside its own video."""
         assert self.S == 8 and cache.B == 1, "the reference chains 8-frame windows of one video (chain_demo.py:24,63-77)"
+        if clip is not None and cache.clip_first is None:
+            raise ValueError("clip needs a cache of several videos (Pips.encode_videos)")
+        table = None if clip is None else (clip, cache.clip_first, cache.clip_frames)
         dev = cache.pyr.device
         H8, W8 = cache.map_size
         with torch.cuda.device(dev):
@@ -417,7 +491,7 @@ class Pips(nn.Module):
                     ws = self._ws[key] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
             ops.chain_hop(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache),
                           active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps, ws,
-                          sample_feat=sample_feat)
+                          sample_feat=sample_feat, clips=table)
 
 
 def _masked_mean(x, mask):
