@@ -99,7 +99,9 @@ const char* pips_last_error(void);
  * for streamed video); pips_chain_hop, pips_chain_gather, pips_chain_step, pips_chain_workspace_bytes and pips_chain_threshold
  * (the visibility-aware chaining of chain_demo.py:40-83, one call per hop); pips_track_clips, pips_mixer_input_build_clips,
  * pips_chain_hop_clips, pips_chain_gather_clips and pips_chain_step_clips (the windows of several videos on one flat cache:
- * a per-particle video index).  pips_chain_workspace_bytes grew by the staged video indices: size with THIS library. */
+ * a per-particle video index).  pips_chain_workspace_bytes grew by the staged video indices: size with THIS library.
+ * pips_stream_select, pips_stream_round, pips_stream_emit and pips_stream_workspace_bytes (the rounds of a streamed video: which
+ * queries are ready, which join, one hop, which frames are final -- one call per round). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -302,6 +304,68 @@ int    pips_chain_hop_clips(const void* arena, const float* pyramid, int T, int 
                             const int* clip, const int* clip_first, const int* clip_frames, int V,
                             float* feat, int* next_active, int* next_count, int* steps,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- streamed chaining: one call per round ------------------------------------------------
+ * Replaces: the per-round bookkeeping of a tracker that follows query points through a video that arrives in chunks -- the
+ * forward chains of chain_demo.py:40-83 from each query's own frame, run while frames are still being appended to a ring of R
+ * frame slots (pips_pyramid_append) and handed out as soon as no pending window can change them.  Which queries have their 8
+ * window frames, which of them start with this round (their start row and first-window features), the hop itself
+ * (pips_chain_hop, base = 0), which queries are finished and which frames are final are all decided here; the host reads four
+ * ints per round.
+ *
+ * The caller owns the state, all of it on the device, for n queries:
+ *   tq      int32 (n)      query frame
+ *   xy      float (n,2)    query position, pixels
+ *   cur     int32 (n)      window start; the caller sets cur = tq, the hops advance it
+ *   status  int32 (n)      0 = waiting, 1 = joined, 2 = done; the caller sets 0
+ *   feat    float (n,128)  features of each query's first window (written when it joins)
+ *   trajs   float (L,n,2)  logical frame f lives in row f mod L (base = 0); L >= 16
+ *   vis     float (L,n)    visibility logits, same rows
+ *   active / new_list  int32, room for n each;  counts  int32 (4) = {n_act, n_new, low, 0}
+ * n grows by the caller re-allocating the arrays and copying (new queries: cur = tq, status 0, rows as the caller fills unused
+ * rows); the library only sees a larger n.
+ *
+ * pips_stream_select, the first call after an append (T = logical frames appended so far), one pass over the n queries:
+ *   final != 0: a joined query with cur >= T becomes done (status 2)
+ *   a query is READY when it is not done and (final ? cur < T : cur + 8 <= T)
+ *   active   <- the ready queries, ascending;  new_list <- the ready queries with status 0, ascending (a block scan, not
+ *               atomics); elements past the counts are not written
+ *   for each member of new_list: trajs[tq mod L, q] = xy[q], status = 1
+ *   counts[0] = n_act, counts[1] = n_new, counts[2] = low = min cur over the queries that are not done (INT_MAX: none), counts[3] = 0
+ * pips_stream_round(n_act, n_new as read from counts), on `stream`:
+ *   join     feat[q] for q in new_list[0..n_new) = the point sample of pips_track_ring(feat_init = NULL, win_start = tq[q],
+ *            iters = 0) at xy[q]
+ *   hop      pips_chain_hop over active[0..n_act) with sample_feat = 0, base = 0, dir = NULL; steps int32 (n_act) or NULL
+ *            receives the step of each active query
+ *   select   pips_stream_select(T, final) again: active / new_list / counts hold the NEXT round
+ * The loop of one append (or of the end of the video, final = 1): select, copy counts back, then round and copy counts back
+ * while counts[0] > 0 -- one host read per round.  With counts[0] == 0, frames [emitted, min(low, T)) are final:
+ * pips_stream_emit(f0, f1), 0 <= f1 - f0 <= L, copies rows f mod L of trajs / vis to the dense out_trajs (f1-f0, n, 2) /
+ * out_vis (f1-f0, n) and stores the fp32 quiet NaN 0x7fc00000 into those rows; every other row stays bit-identical.  Rows whose
+ * length is a multiple of 16 bytes (in 16-byte aligned buffers) move as 16-byte pieces, other rows word by word.
+ *
+ * The caller keeps true:
+ *   - no frame slot is overwritten while a pending window can read it: append at most up to T <= low + R (low of the last counts;
+ *     with R >= 9 this always leaves room for one new frame);
+ *   - the final rounds are not started with a waiting query whose tq >= T (it could never join: the loop would end with it
+ *     pending and its frames never final);
+ *   - tq >= 0 and tq >= the first frame not yet emitted when a query is added; |cur| + 8 below 2^31.
+ * A member of active / new_list outside [0, n) is never dereferenced (pips_chain_hop's rule).
+ * n_act == 0 (round) or f0 == f1 (emit): PIPS_OK and nothing is done.  PIPS_E_ARG ahead of any launch: n < 1; n_act or n_new
+ * outside [0, n]; n_new > n_act; L < 16; R < 9; T < 1; f1 < f0 or f1 - f0 > L; a NULL array (steps may be NULL).
+ * PIPS_E_WORKSPACE: workspace_bytes < pips_stream_workspace_bytes(n, iters) (= pips_chain_workspace_bytes(n, iters) + the staging
+ * of the join + the hop's unused compacted list).  A rejected call writes nothing.  No allocation, no synchronisation. */
+size_t pips_stream_workspace_bytes(int n, int iters);
+int    pips_stream_select(int T, int final, int n, const int* tq, const float* xy, int* cur, int* status, float* trajs, int L,
+                          int* active, int* new_list, int* counts, void* stream);
+int    pips_stream_round(const void* arena, const float* pyramid, int T, int R, int H8, int W8,
+                         const float* times, int stride, int iters, int flags, int final,
+                         int n, int n_act, int n_new,
+                         const int* tq, const float* xy, int* cur, int* status, float* feat,
+                         float* trajs, float* vis, int L,
+                         int* active, int* new_list, int* counts, int* steps,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int    pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 

@@ -1036,6 +1036,64 @@ int chain_step(const ChainState& s, const float* win_trajs, const float* win_vis
                              s.dir, s.feat, next_active, next_count, steps, st, s.clip, s.clip_frames, s.V);
 }
 
+// One hop: chain_gather, the tracker on (B = 1, N = n_act) windows, chain_step.  Shared by pips_chain_hop* and pips_stream_round.
+int chain_hop(const ChainState& s, const void* arena, const float* pyramid, int T, int R, int H8, int W8, const float* times, int stride,
+              int iters, int flags, const int* clip_first, int* next_active, int* next_count, int* steps, void* workspace,
+              size_t workspace_bytes, hipStream_t st) {
+    const int n_act = s.n_act;
+    // every check ahead of the first launch: a rejected call leaves the caller's state as it was
+    RUN(check_chain_state(s, "chain_hop"));
+    RUN(check_chain_clips(s, "chain_hop"));
+    PIPS_CHECK_ARG(R >= 1 && T >= 1, "chain_hop: need R >= 1 and T >= 1 (R=%d, T=%d)", R, T);
+    PIPS_CHECK_ARG(s.clip == nullptr || clip_first != nullptr, "chain_hop: clip needs clip_first and clip_frames");
+    PIPS_CHECK_ARG(s.clip == nullptr || R == T, "chain_hop: a clip table needs a linear cache, R = T (R=%d, T=%d)", R, T);
+    PIPS_CHECK_ARG(next_active && next_count, "chain_hop: null pointer");
+    PIPS_CHECK_ARG(next_active != s.active, "chain_hop: next_active may not alias active");
+    PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "chain_hop: need iters >= 0, stride >= 1 and a map of at least 8x8");
+    if (n_act == 0) return clear_chain_count(next_count, "chain_hop", st);
+    PIPS_CHECK_ARG(arena && pyramid && times && workspace, "chain_hop: null pointer");
+    const ChainPlan P = plan_chain(n_act, iters);
+    if (workspace_bytes < P.total * sizeof(float)) {
+        set_error("chain_hop: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
+        return PIPS_E_WORKSPACE;
+    }
+    float* ws = (float*)workspace;
+    float* xy = ws + P.xy; float* fi = ws + P.fi;
+    int* win_start = reinterpret_cast<int*>(ws + P.ws); int* win_dir = reinterpret_cast<int*>(ws + P.wd);
+    int* win_clip = reinterpret_cast<int*>(ws + P.wc);
+    float* win_trajs = ws + P.win_trajs; float* win_vis = ws + P.win_vis; float* win_ffeat0 = ws + P.win_ffeat0;
+    RUN(chain_gather(s, xy, win_start, win_dir, win_clip, fi, st));
+    // the first window samples its features at the start position (feat_init = NULL) and returns them; later ones carry feat
+    TrackCall c = track_call(arena, pyramid, 1, T, H8, W8, xy, nullptr, s.sample_feat ? nullptr : fi, win_start, times, n_act, stride,
+                             iters, flags, ws + P.track, plan_track(1, n_act, PIPS_S).total * sizeof(float), win_trajs, win_vis,
+                             s.sample_feat ? win_ffeat0 : nullptr, st);
+    c.R = R;
+    c.win_dir = s.dir != nullptr ? win_dir : nullptr;
+    if (s.clip != nullptr) { c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = s.clip_frames; c.V = s.V; }
+    RUN(track_impl(c));
+    return chain_step(s, win_trajs + (size_t)iters * PIPS_S * n_act * 2, win_vis, win_ffeat0, T, next_active, next_count, steps, st);
+}
+
+// ------------------------------------------------------------------ streamed chaining (drivers.StreamTracker)
+// workspace of one round over a state of n queries, in floats: a hop's for n_act = n, the staging of the joining queries' point
+// sample (its tracker workspace is the hop's, idle until the hop starts) and the hop's compacted list and count, which a stream
+// does not read (stream_select_kernel decides who is ready)
+struct StreamPlan { size_t chain, jxy, jtq, jfeat, jtrajs, jvis, next_active, next_count, total; };
+StreamPlan plan_stream(int n, int iters) {
+    StreamPlan P;
+    Bump b;
+    P.chain = b.take(plan_chain(n, iters).total);
+    P.jxy = b.take((size_t)n * 2);
+    P.jtq = b.take(n);
+    P.jfeat = b.take((size_t)n * PIPS_C);
+    P.jtrajs = b.take((size_t)PIPS_S * n * 2);
+    P.jvis = b.take((size_t)PIPS_S * n);
+    P.next_active = b.take(n);
+    P.next_count = b.take(1);
+    P.total = b.off;
+    return P;
+}
+
 }  // namespace
 
 // ================================================================== the C ABI (include/pips_hip.h)
@@ -1415,38 +1473,72 @@ int pips_chain_hop_clips(const void* arena, const float* pyramid, int T, int R, 
                          float* feat, int* next_active, int* next_count, int* steps, void* workspace, size_t workspace_bytes,
                          void* stream) {
     const ChainState s = {n, active, n_act, sample_feat, trajs, vis, L, base, cur, dir, feat, clip, clip_frames, V};
+    return chain_hop(s, arena, pyramid, T, R, H8, W8, times, stride, iters, flags, clip_first, next_active, next_count, steps, workspace,
+                     workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- streamed chaining
+size_t pips_stream_workspace_bytes(int n, int iters) {
+    if (n <= 0 || iters < 0) return 0;
+    return plan_stream(n, iters).total * sizeof(float);
+}
+int pips_stream_select(int T, int final, int n, const int* tq, const float* xy, int* cur, int* status, float* trajs, int L,
+                       int* active, int* new_list, int* counts, void* stream) {
+    PIPS_CHECK_ARG(n >= 1 && T >= 1, "stream_select: need n >= 1 and T >= 1 (n=%d, T=%d)", n, T);
+    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_select: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
+    PIPS_CHECK_ARG(tq && xy && cur && status && trajs && active && new_list && counts, "stream_select: null pointer");
+    return launch_stream_select(T, final, n, tq, xy, cur, status, trajs, L, active, new_list, counts, (hipStream_t)stream);
+}
+int pips_stream_round(const void* arena, const float* pyramid, int T, int R, int H8, int W8, const float* times, int stride, int iters,
+                      int flags, int final, int n, int n_act, int n_new, const int* tq, const float* xy, int* cur, int* status,
+                      float* feat, float* trajs, float* vis, int L, int* active, int* new_list, int* counts, int* steps,
+                      void* workspace, size_t workspace_bytes, void* stream) {
     // every check ahead of the first launch: a rejected call leaves the caller's state as it was
-    RUN(check_chain_state(s, "chain_hop"));
-    RUN(check_chain_clips(s, "chain_hop"));
-    PIPS_CHECK_ARG(R >= 1 && T >= 1, "chain_hop: need R >= 1 and T >= 1 (R=%d, T=%d)", R, T);
-    PIPS_CHECK_ARG(clip == nullptr || clip_first != nullptr, "chain_hop: clip needs clip_first and clip_frames");
-    PIPS_CHECK_ARG(clip == nullptr || R == T, "chain_hop: a clip table needs a linear cache, R = T (R=%d, T=%d)", R, T);
-    PIPS_CHECK_ARG(next_active && next_count, "chain_hop: null pointer");
-    PIPS_CHECK_ARG(next_active != active, "chain_hop: next_active may not alias active");
-    PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "chain_hop: need iters >= 0, stride >= 1 and a map of at least 8x8");
-    hipStream_t st = (hipStream_t)stream;
-    if (n_act == 0) return clear_chain_count(next_count, "chain_hop", st);
-    PIPS_CHECK_ARG(arena && pyramid && times && workspace, "chain_hop: null pointer");
-    const ChainPlan P = plan_chain(n_act, iters);
-    if (workspace_bytes < P.total * sizeof(float)) {
-        set_error("chain_hop: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
+    PIPS_CHECK_ARG(n >= 1, "stream_round: need n >= 1 (n=%d)", n);
+    PIPS_CHECK_ARG(n_act >= 0 && n_act <= n && n_new >= 0 && n_new <= n_act,
+                   "stream_round: need 0 <= n_new <= n_act <= n (n_new=%d, n_act=%d, n=%d)", n_new, n_act, n);
+    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_round: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
+    PIPS_CHECK_ARG(R >= PIPS_S + 1, "stream_round: a frame ring needs R >= %d slots, a window and a new frame (R=%d)", PIPS_S + 1, R);
+    PIPS_CHECK_ARG(T >= 1, "stream_round: need T >= 1 (T=%d)", T);
+    PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "stream_round: need iters >= 0, stride >= 1 and a map of at least 8x8");
+    PIPS_CHECK_ARG(arena && pyramid && times && tq && xy && cur && status && feat && trajs && vis && active && new_list && counts &&
+                   workspace, "stream_round: null pointer");
+    // the hop's and the point sample's own plans lie inside the regions sized for n (n_new <= n_act <= n)
+    const StreamPlan P = plan_stream(n, iters);
+    const ChainPlan CP = plan_chain(n, iters);
+    const size_t join_track = n_new > 0 ? plan_track(1, n_new, PIPS_S).total : 0;
+    const size_t hop = n_act > 0 ? plan_chain(n_act, iters).total : 0;
+    if (workspace_bytes < P.total * sizeof(float) || hop > CP.total || join_track > plan_track(1, n, PIPS_S).total) {
+        set_error("stream_round: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
         return PIPS_E_WORKSPACE;
     }
+    if (n_act == 0) return PIPS_OK;
+    hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    float* xy = ws + P.xy; float* fi = ws + P.fi;
-    int* win_start = reinterpret_cast<int*>(ws + P.ws); int* win_dir = reinterpret_cast<int*>(ws + P.wd);
-    int* win_clip = reinterpret_cast<int*>(ws + P.wc);
-    float* win_trajs = ws + P.win_trajs; float* win_vis = ws + P.win_vis; float* win_ffeat0 = ws + P.win_ffeat0;
-    RUN(chain_gather(s, xy, win_start, win_dir, win_clip, fi, st));
-    // the first window samples its features at the start position (feat_init = NULL) and returns them; later ones carry feat
-    TrackCall c = track_call(arena, pyramid, 1, T, H8, W8, xy, nullptr, sample_feat ? nullptr : fi, win_start, times, n_act, stride,
-                             iters, flags, ws + P.track, plan_track(1, n_act, PIPS_S).total * sizeof(float), win_trajs, win_vis,
-                             sample_feat ? win_ffeat0 : nullptr, stream);
-    c.R = R;
-    c.win_dir = dir != nullptr ? win_dir : nullptr;
-    if (clip != nullptr) { c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = clip_frames; c.V = V; }
-    RUN(track_impl(c));
-    return chain_step(s, win_trajs + (size_t)iters * PIPS_S * n_act * 2, win_vis, win_ffeat0, T, next_active, next_count, steps, st);
+    if (n_new > 0) {
+        // the joining queries' first-window features: the point sample of a track call without feat_init, at their own frames
+        float* jxy = ws + P.jxy; int* jtq = reinterpret_cast<int*>(ws + P.jtq); float* jfeat = ws + P.jfeat;
+        RUN(launch_stream_join_gather(new_list, n_new, n, xy, tq, jxy, jtq, st));
+        TrackCall c = track_call(arena, pyramid, 1, T, H8, W8, jxy, nullptr, nullptr, jtq, times, n_new, stride, 0, flags,
+                                 ws + P.chain + CP.track, join_track * sizeof(float), ws + P.jtrajs, ws + P.jvis, jfeat,
+                                 st);
+        c.R = R;
+        RUN(track_impl(c));
+        RUN(launch_stream_join_scatter(new_list, n_new, n, jfeat, feat, st));
+    }
+    const ChainState s = {n, active, n_act, 0, trajs, vis, L, 0, cur, nullptr, feat, nullptr, nullptr, 0};
+    RUN(chain_hop(s, arena, pyramid, T, R, H8, W8, times, stride, iters, flags, nullptr, reinterpret_cast<int*>(ws + P.next_active),
+                  reinterpret_cast<int*>(ws + P.next_count), steps, ws + P.chain, CP.total * sizeof(float), st));
+    return launch_stream_select(T, final, n, tq, xy, cur, status, trajs, L, active, new_list, counts, st);
+}
+int pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, void* stream) {
+    PIPS_CHECK_ARG(n >= 1, "stream_emit: need n >= 1 (n=%d)", n);
+    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_emit: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
+    PIPS_CHECK_ARG(f1 >= f0 && (long long)f1 - f0 <= L, "stream_emit: need 0 <= f1 - f0 <= L (f0=%d, f1=%d, L=%d)", f0, f1, L);
+    PIPS_CHECK_ARG(trajs && vis, "stream_emit: null pointer");
+    if (f0 == f1) return PIPS_OK;                 // (no frame: the outputs are empty and may be NULL)
+    PIPS_CHECK_ARG(out_trajs && out_vis, "stream_emit: null pointer");
+    return launch_stream_emit(trajs, vis, L, n, f0, f1, out_trajs, out_vis, (hipStream_t)stream);
 }
 
 // ---- whole forward

@@ -463,4 +463,16 @@ int launch_chain_step(const float* win_trajs, const float* win_vis, const float*
                       int* next_active, int* next_count, int* steps, hipStream_t st, const int* clip = nullptr,
                       const int* clip_frames = nullptr, int V = 0);
 
+// ---------------------------------------------------------------- streamed chaining bookkeeping (stream.hip)
+// one pass over the n queries of a caller-owned stream state: the ready ones in `active`, the ready ones still waiting in
+// `new_list` (their start rows seeded, status 1), both ascending; counts = {n_act, n_new, lowest pending window start, 0}
+int launch_stream_select(int T, int final_, int n, const int* tq, const float* xy, const int* cur, int* status, float* trajs, int L,
+                         int* active, int* new_list, int* counts, hipStream_t st);
+// the xys / win_start of the joining queries' point sample, and the scatter of the features it returned into feat
+int launch_stream_join_gather(const int* new_list, int n_new, int n, const float* xy, const int* tq, float* sxy, int* stq,
+                              hipStream_t st);
+int launch_stream_join_scatter(const int* new_list, int n_new, int n, const float* sfeat, float* feat, hipStream_t st);
+// rows (f mod L), f in [f0, f1), of trajs (L,n,2) / vis (L,n) to dense outputs; those rows are reset to the fp32 quiet NaN
+int launch_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, hipStream_t st);
+
 }  // namespace pips

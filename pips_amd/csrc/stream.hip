@@ -1,0 +1,195 @@
+// Streamed chaining (drivers.StreamTracker) as device-side bookkeeping around the tracker and pips_chain_hop: which queries of a
+// caller-owned state are ready for a window, which of them join with this round, the lowest window start still pending
+// (stream_select_kernel), the staging and the scatter of a joining query's first-window features (stream_join_*_kernel) and the
+// move of the frames that became final out of the row ring (stream_emit_kernel).  Plain HIP; built with the default floating-point
+// flags, as chain.hip is.  No atomics: the order of the two lists is part of the contract.
+#include <climits>
+
+#include "common.h"
+
+namespace pips {
+
+namespace {
+
+constexpr int SEL_THREADS = 256;
+constexpr int SEL_WAVES = SEL_THREADS / 64;
+constexpr int STREAM_S = PIPS_S;
+constexpr unsigned STREAM_NAN = 0x7fc00000u;      // the fp32 quiet NaN of torch's float("nan") fill
+
+// row of logical frame f in a ring of L rows (base 0; Python's modulo: never negative)
+__device__ __forceinline__ int stream_row(int f, int L) {
+    const int r = f % L;
+    return r < 0 ? r + L : r;
+}
+
+struct SelectArgs {
+    const int* tq; const float* xy; const int* cur;
+    int* status; float* trajs; int* active; int* new_list; int* counts;
+    int T, final_, n, L;
+};
+
+// ONE block walks the n queries in chunks of SEL_THREADS, a thread per query.  The ready queries of a chunk get consecutive
+// slots of `active`, the ready ones that were still waiting consecutive slots of `new_list`, by a block scan each (ballot inside a
+// wave, the waves' counts through LDS) on top of the offsets carried from the chunks before: both lists ascend.  The lowest
+// window start of the queries that are not done is a wave reduction plus LDS at the end of the same walk.
+__global__ __launch_bounds__(SEL_THREADS) void stream_select_kernel(const SelectArgs a) {
+    __shared__ int wave_act[SEL_WAVES];
+    __shared__ int wave_new[SEL_WAVES];
+    __shared__ int wave_low[SEL_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carried_act = 0, carried_new = 0, low = INT_MAX;
+    for (int q0 = 0; q0 < a.n; q0 += SEL_THREADS) {
+        const int q = q0 + tid;
+        bool ready = false, fresh = false;
+        if (q < a.n) {
+            int s = a.status[q];
+            const int c = a.cur[q];
+            if (a.final_ && s == 1 && c >= a.T) {          // its last window ran past the end of the video
+                s = 2;
+                a.status[q] = 2;
+            }
+            if (s != 2) {
+                low = min(low, c);
+                ready = a.final_ ? c < a.T : c <= a.T - STREAM_S;      // all 8 frames of its window have arrived
+                fresh = ready && s == 0;
+            }
+        }
+        const unsigned long long ma = __ballot(ready), mn = __ballot(fresh);
+        if (lane == 0) {
+            wave_act[wave] = __popcll(ma);
+            wave_new[wave] = __popcll(mn);
+        }
+        __syncthreads();
+        int off_act = carried_act, off_new = carried_new, tot_act = 0, tot_new = 0;
+#pragma unroll
+        for (int w = 0; w < SEL_WAVES; ++w) {
+            const int ca = wave_act[w], cn = wave_new[w];
+            if (w < wave) { off_act += ca; off_new += cn; }
+            tot_act += ca;
+            tot_new += cn;
+        }
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (ready) a.active[off_act + __popcll(ma & below)] = q;
+        if (fresh) {       // first window: the start is the query itself, at its own frame
+            a.new_list[off_new + __popcll(mn & below)] = q;
+            const size_t o = ((size_t)stream_row(a.tq[q], a.L) * a.n + q) * 2;
+            a.trajs[o] = a.xy[2 * q];
+            a.trajs[o + 1] = a.xy[2 * q + 1];
+            a.status[q] = 1;
+        }
+        carried_act += tot_act;
+        carried_new += tot_new;
+        __syncthreads();                // the wave counts are rewritten by the next chunk
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) low = min(low, __shfl_xor(low, d));
+    if (lane == 0) wave_low[wave] = low;
+    __syncthreads();
+    if (tid == 0) {
+        int m = wave_low[0];
+#pragma unroll
+        for (int w = 1; w < SEL_WAVES; ++w) m = min(m, wave_low[w]);
+        a.counts[0] = carried_act;
+        a.counts[1] = carried_new;
+        a.counts[2] = m;
+        a.counts[3] = 0;
+    }
+}
+
+// the start positions and query frames of the joining queries new_list[0..n_new): the xys / win_start of their point sample.  A
+// member outside [0, n) is never dereferenced: zeros are staged for it and the scatter ignores it.
+__global__ __launch_bounds__(SEL_THREADS) void stream_join_gather_kernel(const int* __restrict__ new_list, int n_new, int n,
+                                                                         const float* __restrict__ xy, const int* __restrict__ tq,
+                                                                         float* __restrict__ sxy, int* __restrict__ stq) {
+    const int j = blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (j >= n_new) return;
+    const int q = new_list[j];
+    const bool ok = (unsigned)q < (unsigned)n;
+    sxy[2 * j] = ok ? xy[2 * q] : 0.f;
+    sxy[2 * j + 1] = ok ? xy[2 * q + 1] : 0.f;
+    stq[j] = ok ? tq[q] : 0;
+}
+
+// one block per joining query: feat[q] = the features its point sample returned
+__global__ __launch_bounds__(PIPS_C) void stream_join_scatter_kernel(const int* __restrict__ new_list, int n_new, int n,
+                                                                     const float* __restrict__ sfeat, float* __restrict__ feat) {
+    const int j = blockIdx.x;
+    if (j >= n_new) return;
+    const int q = new_list[j];
+    if ((unsigned)q >= (unsigned)n) return;
+    feat[(size_t)q * PIPS_C + threadIdx.x] = sfeat[(size_t)j * PIPS_C + threadIdx.x];
+}
+
+// `len` 32-bit words of one ring row to its dense output row, the ring row reset to NaN; bit patterns, not floats.  vec: the row
+// length is a multiple of 4 words and both buffers are 16-byte aligned, so every row starts on a 16-byte boundary and moves as
+// 16-byte pieces; any other row moves word by word (the scalar tail is then the whole row).
+__device__ __forceinline__ void emit_row(unsigned* __restrict__ src, unsigned* __restrict__ dst, int len, bool vec, int t, int nt) {
+    const int nv = vec ? len / 4 : 0;
+    const uint4 nan4 = make_uint4(STREAM_NAN, STREAM_NAN, STREAM_NAN, STREAM_NAN);
+    uint4* s4 = reinterpret_cast<uint4*>(src);
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    for (int i = t; i < nv; i += nt) {
+        d4[i] = s4[i];
+        s4[i] = nan4;
+    }
+    for (int i = 4 * nv + t; i < len; i += nt) {
+        dst[i] = src[i];
+        src[i] = STREAM_NAN;
+    }
+}
+
+// blockIdx.y = frame f0 + y of the emitted range; the blocks of one frame share its two rows
+__global__ __launch_bounds__(SEL_THREADS) void stream_emit_kernel(unsigned* __restrict__ trajs, unsigned* __restrict__ vis, int L, int n,
+                                                                  int f0, int m, unsigned* __restrict__ out_trajs,
+                                                                  unsigned* __restrict__ out_vis, int vec_trajs, int vec_vis) {
+    const int i = blockIdx.y;
+    if (i >= m) return;
+    const int r = stream_row(f0 + i, L);
+    const int t = blockIdx.x * SEL_THREADS + threadIdx.x, nt = gridDim.x * SEL_THREADS;
+    emit_row(trajs + (size_t)r * n * 2, out_trajs + (size_t)i * n * 2, n * 2, vec_trajs != 0, t, nt);
+    emit_row(vis + (size_t)r * n, out_vis + (size_t)i * n, n, vec_vis != 0, t, nt);
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+int launch_stream_select(int T, int final_, int n, const int* tq, const float* xy, const int* cur, int* status, float* trajs, int L,
+                         int* active, int* new_list, int* counts, hipStream_t st) {
+    SelectArgs a;
+    a.tq = tq; a.xy = xy; a.cur = cur; a.status = status; a.trajs = trajs; a.active = active; a.new_list = new_list; a.counts = counts;
+    a.T = T; a.final_ = final_ != 0; a.n = n; a.L = L;
+    hipLaunchKernelGGL(stream_select_kernel, dim3(1), dim3(SEL_THREADS), 0, st, a);
+    PIPS_CHECK_LAUNCH("stream_select");
+    return PIPS_OK;
+}
+
+int launch_stream_join_gather(const int* new_list, int n_new, int n, const float* xy, const int* tq, float* sxy, int* stq,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(stream_join_gather_kernel, dim3((n_new + SEL_THREADS - 1) / SEL_THREADS), dim3(SEL_THREADS), 0, st, new_list,
+                       n_new, n, xy, tq, sxy, stq);
+    PIPS_CHECK_LAUNCH("stream_join_gather");
+    return PIPS_OK;
+}
+
+int launch_stream_join_scatter(const int* new_list, int n_new, int n, const float* sfeat, float* feat, hipStream_t st) {
+    hipLaunchKernelGGL(stream_join_scatter_kernel, dim3(n_new), dim3(PIPS_C), 0, st, new_list, n_new, n, sfeat, feat);
+    PIPS_CHECK_LAUNCH("stream_join_scatter");
+    return PIPS_OK;
+}
+
+int launch_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, hipStream_t st) {
+    const int m = f1 - f0;
+    const int vec_trajs = (2 * n) % 4 == 0 && aligned16(trajs) && aligned16(out_trajs);
+    const int vec_vis = n % 4 == 0 && aligned16(vis) && aligned16(out_vis);
+    // a thread moves one 16-byte piece (or one word) of the longer row per pass; 64 blocks per frame at the most
+    const int per_row = vec_trajs ? (2 * n) / 4 : 2 * n;
+    const int bx = min(max((per_row + SEL_THREADS - 1) / SEL_THREADS, 1), 64);
+    hipLaunchKernelGGL(stream_emit_kernel, dim3(bx, m), dim3(SEL_THREADS), 0, st, reinterpret_cast<unsigned*>(trajs),
+                       reinterpret_cast<unsigned*>(vis), L, n, f0, m, reinterpret_cast<unsigned*>(out_trajs),
+                       reinterpret_cast<unsigned*>(out_vis), vec_trajs, vec_vis);
+    PIPS_CHECK_LAUNCH("stream_emit");
+    return PIPS_OK;
+}
+
+}  // namespace pips

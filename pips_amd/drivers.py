@@ -23,7 +23,9 @@ The chaining drivers take ``engine="torch" | "native"``.  ``"torch"`` (the defau
 read of the start positions, the scatters into the trajectory, the sigmoid, ``skip_scan``, the index update -- as the torch ops
 of ``_hop``; ``"native"`` runs the whole hop as ONE library call (``Pips.chain_hop`` = ``pips_chain_hop``: the same bookkeeping
 as HIP kernels around the same tracker launches, state held as int32) and reads the live count back, one host sync per hop
-either way.  Both engines give the same hops and the same bits.
+either way.  Both engines give the same hops and the same bits.  ``StreamTracker`` also takes ``rounds="torch" | "library"``:
+with ``"library"`` the round itself -- who is ready, who joins, the hop, which frames are final -- is one ``pips_stream_round``
+call on int32 state, and queries can be added while the video runs (``add_queries``, either value).
 """
 from __future__ import annotations
 
@@ -347,6 +349,9 @@ def track_queries_batch(model, videos, queries, iters=6, return_hops=False, engi
     return out
 
 
+ROUNDS = ("torch", "library")
+
+
 class StreamTracker:
     """``track_queries``' forward chains on a video that arrives in chunks, in bounded device memory.
 
@@ -355,21 +360,30 @@ class StreamTracker:
     for the frames ``[f0, f0+m)`` that became final (``m`` may be 0); ``finish()`` ends the video and returns the rest.
     Frame ``t >= t_q`` of a query is the reference's chaining loop (chain_demo.py:40-83) on ``rgbs[:, t_q:]`` -- the forward
     frames of ``track_queries`` -- and frames before ``t_q`` are NaN (no backward tracking).
+    ``add_queries(queries)`` takes further queries while the video runs, on any frame not yet returned; the outputs of the
+    calls after it have their columns behind the earlier ones, each what a stream given that query up front returns.
 
     Frames are encoded once into a ring of ``slots`` frames (``Pips.ring_cache``).  A window runs once its 8 frames have
-    arrived (at ``finish()``, past the last frame it repeats it, chain_demo.py:50-52); each round is one ``model.track``
-    call over every ready particle, new ones joining with their first-window features (the same point sample as
-    ``feat_init=None``).  A frame is final when it lies below every unfinished particle's window start.  ``push`` splits
+    arrived (at ``finish()``, past the last frame it repeats it, chain_demo.py:50-52); each round is one hop over every
+    ready particle, new ones joining with their first-window features (the same point sample as ``feat_init=None``).  A
+    frame is final when it lies below every unfinished particle's window start.  ``push`` splits
     a chunk so that no slot is overwritten while a pending window can still read it: ``slots >= 9`` keeps the 8 frames of
     a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query.
-    ``engine="native"``: each round's hop is one ``pips_chain_hop`` call (window starts held as int32); which particles are ready
-    and which are finished stays decided here."""
+
+    ``rounds="torch"`` (the default): which particles are ready, which join and which are finished is decided here in torch ops,
+    a ``model.track`` call per round -- or, with ``engine="native"``, one ``pips_chain_hop`` call (window starts held as int32).
+    ``rounds="library"``: the state is the int32 / float arrays of ``pips_stream_round`` (include/pips_hip.h) and a round is
+    ONE library call -- join, hop and the selection of the next round; the host reads four ints per round (the numbers of ready
+    and of joining queries, the lowest pending window start) and moves the final frames out with ``pips_stream_emit``.  The hop
+    is the library's, so ``engine`` is not looked at.  Same hops and the same bits as ``rounds="torch"``."""
 
     S = 8
 
-    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch"):
+    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
         _check_engine(engine)
-        self.engine = engine
+        if rounds not in ROUNDS:
+            raise ValueError(f"rounds must be one of {ROUNDS}, not {rounds!r}")
+        self.engine, self.rounds = engine, rounds
         assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
         if int(slots) < self.S + 1:
             raise ValueError(f"slots must be at least {self.S + 1} (one window and a new frame), not {slots}")
@@ -379,6 +393,7 @@ class StreamTracker:
         self.N = self.tq_host.numel()
         self.cache = None
         self.finished = False
+        self.emitted = 0                                                          # frames [0, emitted) returned
         self.hops = [[] for _ in range(self.N)] if record_hops else None       # frame steps per query (grows with T)
 
     def _start(self, frames):
@@ -392,6 +407,16 @@ class StreamTracker:
         self.tq = self.tq_host.to(dev)
         self.xy = self.xy_in.to(dev, torch.float32)
         self.cur = self.tq.clone()                                                # window start (= t_q until it joins)
+        self.emitted = 0
+        if self.rounds == "library":                                              # pips_stream_round's state
+            i32 = torch.int32
+            self.tq, self.cur, self.xy = self.tq.to(i32), self.cur.to(i32), self.xy.contiguous()
+            self.status = torch.zeros(self.N, dtype=i32, device=dev)              # 0 waiting, 1 joined, 2 done
+            self.feat = torch.zeros(self.N, 128, dtype=torch.float32, device=dev)
+            self.counts = torch.zeros(4, dtype=i32, device=dev)
+            self._lists()
+            self.low = None if self.N == 0 else int(self.tq_host.min())           # host copy of counts[2]
+            return
         if self.engine == "native":                                               # pips_chain_hop's state
             self.cur = self.cur.to(torch.int32)
             self.count = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -400,10 +425,64 @@ class StreamTracker:
         self.joined = torch.zeros(self.N, dtype=torch.bool, device=dev)
         self.done = torch.zeros(self.N, dtype=torch.bool, device=dev)
         self.feat = None                                                          # (N,128) features of the first windows
-        self.emitted = 0                                                          # frames [0, emitted) returned
+
+    def _lists(self):
+        """the lists a library round writes, for N queries (their contents do not outlive a push)"""
+        dev = self.trajs.device
+        self.active = torch.empty(self.N, dtype=torch.int32, device=dev)
+        self.new_list = torch.empty(self.N, dtype=torch.int32, device=dev)
+        self.steps = torch.empty(self.N, dtype=torch.int32, device=dev) if self.hops is not None else None
+
+    def add_queries(self, queries):
+        """Further queries (1,m,3) = (t, x, y) while the video runs -> the columns (m,) they take in the outputs of the ``push``
+        / ``finish`` calls from now on, behind the queries already there.  ``t`` is an integer frame that was not returned yet
+        (``t >= self.emitted``; it may lie beyond the frames pushed so far): such a frame is still in the ring, so the new
+        column is what a stream given the query up front returns -- NaN before ``t``, the forward chain from ``t`` on.
+        ValueError, with the tracker left as it was, for any other ``t`` and after ``finish()``."""
+        if self.finished:
+            raise ValueError("add_queries() after finish()")
+        t = _query_frames(queries)
+        if bool((t < self.emitted).any()):
+            raise ValueError(f"a query frame lies before frame {self.emitted}: frames [0, {self.emitted}) were returned already")
+        m, N = t.numel(), self.N
+        xy = queries[0, :, 1:3]
+        self.tq_host = torch.cat([self.tq_host, t])
+        self.xy_in = torch.cat([self.xy_in, xy.to(self.xy_in.device, self.xy_in.dtype)])
+        self.N = N + m
+        if self.hops is not None:
+            self.hops += [[] for _ in range(m)]
+        if self.cache is not None and m > 0:
+            self._grow(t, xy, m)
+        return torch.arange(N, N + m)
+
+    def _grow(self, t, xy, m):
+        """the device state with m more columns: the old ones copied, the new ones as ``_start`` makes them"""
+        dev = self.trajs.device
+
+        def wider(old, fill):
+            return torch.cat([old, torch.full((old.shape[0], m) + tuple(old.shape[2:]), fill, dtype=old.dtype, device=dev)], dim=1)
+
+        def longer(old, new):
+            return torch.cat([old, new.to(dev, old.dtype).reshape((m,) + tuple(old.shape[1:]))])
+
+        self.trajs, self.vis = wider(self.trajs, float("nan")), wider(self.vis, float("nan"))
+        self.tq, self.xy, self.cur = longer(self.tq, t), longer(self.xy, xy), longer(self.cur, t)
+        if self.feat is not None:
+            self.feat = longer(self.feat, torch.zeros(m, self.feat.shape[1]))
+        if self.rounds == "library":
+            self.status = longer(self.status, torch.zeros(m))
+            self._lists()
+            self.low = int(t.min()) if self.low is None else min(self.low, int(t.min()))
+            return
+        if self.engine == "native":
+            self.next_active = torch.empty(self.N, dtype=torch.int32, device=dev)
+            self.steps = torch.empty(self.N, dtype=torch.int32, device=dev)
+        self.joined, self.done = longer(self.joined, torch.zeros(m)), longer(self.done, torch.zeros(m))
 
     def _pending(self):
         """lowest window start of the unfinished particles (None when all are finished)"""
+        if self.rounds == "library":
+            return self.low
         live = self.cur[~self.done]
         return None if live.numel() == 0 else int(live.min())
 
@@ -444,6 +523,8 @@ class StreamTracker:
 
     def _rounds(self, final):
         """hop rounds until no particle is ready: one whose 8 window frames have all arrived (final: every unfinished one)"""
+        if self.rounds == "library":
+            return self._rounds_library(final)
         T = self.cache.T
         while True:
             ready = ~self.done & ((self.cur < T) if final else (self.cur + self.S <= T))
@@ -474,12 +555,36 @@ class StreamTracker:
                 for q, h in zip(active.tolist(), si.tolist()):
                     self.hops[q].append(h)
 
+    def _rounds_library(self, final):
+        """the same rounds with the state in the library's hands: select, then one ``pips_stream_round`` call per round while
+        any query is ready (one host sync per round: the four ints of ``counts``)"""
+        if self.N == 0:
+            return
+        from . import ops
+        ops.stream_select(self.cache.T, final, self.tq, self.xy, self.cur, self.status, self.trajs, self.active, self.new_list,
+                          self.counts)
+        n_act, n_new, low, _ = self.counts.tolist()
+        while n_act > 0:
+            act = self.active[:n_act].clone() if self.hops is not None else None      # the round rewrites the list
+            self.model.stream_round(self.cache, final, n_act, n_new, self.tq, self.xy, self.cur, self.status, self.feat, self.trajs,
+                                    self.vis, self.active, self.new_list, self.counts, self.steps, iters=self.iters)
+            if self.hops is not None:
+                for q, h in zip(act.tolist(), self.steps[:n_act].tolist()):
+                    self.hops[q].append(h)
+            n_act, n_new, low, _ = self.counts.tolist()
+        self.low = None if low == 2 ** 31 - 1 else low
+
     def _emit(self):
         """the rows of the frames that became final, moved out of the ring (their rows are reset to NaN for reuse)"""
         low = self._pending()
         end = self.cache.T if low is None else min(low, self.cache.T)
         if end <= self.emitted:
             return None
+        if self.rounds == "library" and self.N > 0:
+            from . import ops
+            out = ops.stream_emit(self.trajs, self.vis, self.emitted, end)
+            self.emitted = end
+            return out
         rows = torch.arange(self.emitted, end, device=self.trajs.device) % self.L
         out = (self.trajs[rows], self.vis[rows])
         self.trajs[rows] = float("nan")
@@ -496,10 +601,11 @@ class StreamTracker:
 
 
 @torch.no_grad()
-def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, engine="torch"):
+def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, engine="torch", rounds="torch"):
     """``StreamTracker`` over an iterable of ``(1,k,3,H,W)`` chunks -> trajs_e (1,T,N,2) px and vis_e (1,T,N) logits, NaN
-    before each query's frame.  ``return_hops=True``: also, per query, the frame steps of its windows."""
-    st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=return_hops, engine=engine)
+    before each query's frame.  ``return_hops=True``: also, per query, the frame steps of its windows.  ``engine`` / ``rounds``:
+    see ``StreamTracker``."""
+    st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=return_hops, engine=engine, rounds=rounds)
     parts = [st.push(c) for c in chunks]
     parts.append(st.finish())
     trajs = torch.cat([p[1] for p in parts], dim=1)

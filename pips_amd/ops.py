@@ -356,6 +356,46 @@ def chain_hop(arena, pyr, T, R, H8, W8, times, stride, iters, flags, active, n_a
               _lib.ptr(workspace), workspace.numel() * 4, _stream())
 
 
+def stream_workspace_bytes(n, iters):
+    """pips_stream_workspace_bytes: the workspace of one round over a state of ``n`` queries (host function)."""
+    return _lib.load().pips_stream_workspace_bytes(int(n), int(iters))
+
+
+def stream_select(T, final, tq, xy, cur, status, trajs, active, new_list, counts):
+    """pips_stream_select, in place on the caller's stream state (include/pips_hip.h): tq / cur / status (n) int32, xy (n,2), trajs
+    (L,n,2); ``active`` / ``new_list`` (n) int32 receive the ready queries and the ones that join, ``counts`` (4) int32 their
+    numbers and the lowest pending window start (device: the caller reads it back)."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    with torch.cuda.device(trajs.device):
+        _call("pips_stream_select", int(T), int(bool(final)), n, _i32(tq), _chain_f32(xy), _i32(cur), _i32(status), _chain_f32(trajs), L,
+              _i32(active), _i32(new_list), _i32(counts), _stream())
+
+
+def stream_round(arena, pyr, T, R, H8, W8, times, stride, iters, flags, final, n_act, n_new, tq, xy, cur, status, feat, trajs, vis,
+                 active, new_list, counts, steps, workspace):
+    """pips_stream_round: the join of ``new_list[:n_new]``, one hop of ``active[:n_act]`` and the selection of the next round, in
+    place on the caller's stream state, on the packed ring pyramid ``pyr`` of R frame slots holding T logical frames.  No host
+    synchronisation."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    with torch.cuda.device(trajs.device):
+        _call("pips_stream_round", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
+              int(iters), int(flags), int(bool(final)), n, int(n_act), int(n_new), _i32(tq), _chain_f32(xy), _i32(cur), _i32(status),
+              _chain_f32(feat), _chain_f32(trajs), _chain_f32(vis), L, _i32(active), _i32(new_list), _i32(counts), _i32(steps),
+              _lib.ptr(workspace), workspace.numel() * 4, _stream())
+
+
+def stream_emit(trajs, vis, f0, f1):
+    """pips_stream_emit: frames [f0, f1) of the row ring trajs (L,n,2) / vis (L,n) -> dense (f1-f0,n,2) and (f1-f0,n); their ring
+    rows are reset to NaN."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    m = max(int(f1) - int(f0), 0)
+    out_t = torch.empty(m, n, 2, dtype=torch.float32, device=trajs.device)
+    out_v = torch.empty(m, n, dtype=torch.float32, device=trajs.device)
+    with torch.cuda.device(trajs.device):
+        _call("pips_stream_emit", _chain_f32(trajs), _chain_f32(vis), L, n, int(f0), int(f1), _lib.ptr(out_t), _lib.ptr(out_v), _stream())
+    return out_t, out_v
+
+
 def gemm(A, W, bias=None, epi=0, R=None):
     """C = epi(A @ W.T + bias).  epi: 0 none, 1 GELU, 2 + R."""
     A, W = _f32(A), _f32(W)

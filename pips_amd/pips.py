@@ -493,6 +493,30 @@ class Pips(nn.Module):
                           active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps, ws,
                           sample_feat=sample_feat, clips=table)
 
+    @torch.no_grad()
+    def stream_round(self, cache: FeatureCache, final, n_act, n_new, tq, xy, cur, status, feat, trajs, vis, active, new_list, counts,
+                     steps=None, iters=6):
+        """One round of a streamed video (``drivers.StreamTracker(rounds="library")``) in one library call (``pips_stream_round``):
+        the queries ``new_list[:n_new]`` join with their first-window features, the ready queries ``active[:n_act]`` hop
+        (``chain_hop`` on the ring cache, base 0) and the next round is selected -- in place on the caller's device state
+        (include/pips_hip.h: tq / cur / status / active / new_list int32, xy (n,2), feat (n,128), trajs (L,n,2), vis (L,n));
+        ``counts`` (4) int32 then holds the next round's numbers and the lowest pending window start (the caller reads it back),
+        ``steps`` the steps of this round's hop.  S = 8 and B = 1 only."""
+        assert self.S == 8 and cache.B == 1, "the reference chains 8-frame windows of one video (chain_demo.py:24,63-77)"
+        dev = cache.pyr.device
+        H8, W8 = cache.map_size
+        n = trajs.shape[1]
+        with torch.cuda.device(dev):
+            arena, times = self._aux(dev)
+            nb = ops.stream_workspace_bytes(n, iters)
+            key = ("stream", str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
+            with self._lock:
+                ws = self._ws.get(key)
+                if ws is None or ws.numel() * 4 < nb:           # grown on demand: n grows with add_queries
+                    ws = self._ws[key] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+            ops.stream_round(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache), final,
+                             n_act, n_new, tq, xy, cur, status, feat, trajs, vis, active, new_list, counts, steps, ws)
+
 
 def _masked_mean(x, mask):
     return (x * mask).sum() / (mask.sum() + 1e-6)           # utils.basic.reduce_masked_mean (EPS = 1e-6)

@@ -7,7 +7,10 @@ on the host, chunks of 16 frames, a ring of 24 slots.  Prints one JSON line:
   * peak torch.cuda.max_memory_allocated above the pre-call allocation at T = 100 and T = --long (1000), the device video of
     the linear drivers included;
   * the bytes pips_pyramid_append moves per frame (fp32 read + fp32 write + bf16 mirror write), for the kernel-trace run.
-The append kernel's time comes from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only stream``."""
+The append kernel's time comes from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only stream``.
+``--rounds``: instead, the stream under ``rounds="torch"`` and ``rounds="library"`` (one pips_stream_round call per round) at T,
+alternating on one GPU after a warm-up of each, medians of --reps calls; the rounds of one call are counted and the two outputs
+compared bit for bit."""
 import argparse
 import json
 import os
@@ -49,9 +52,9 @@ def queries(dev):
     return torch.stack([t, gx.reshape(-1), gy.reshape(-1)], -1).unsqueeze(0).to(dev)
 
 
-def run(name, m, q, host, video=None):
+def run(name, m, q, host, video=None, rounds="torch"):
     if name == "stream":
-        return drivers.track_stream(m, chunks(host), q, iters=6, slots=SLOTS)
+        return drivers.track_stream(m, chunks(host), q, iters=6, slots=SLOTS, rounds=rounds)
     if name == "queries":
         return drivers.track_queries(m, video, q, iters=6)
     return drivers.track_chained(m, video, q[:, :, 1:], iters=6)
@@ -75,12 +78,35 @@ def peak(fn):
     return torch.cuda.max_memory_allocated() - start
 
 
+def compare_rounds(m, q, host, reps):
+    """both values of ``rounds`` on the same chunks -> their median times, the rounds of one call, outputs equal as bit patterns"""
+    out, ts = {}, {"torch": [], "library": []}
+    count = [0]
+    real = m.stream_round
+
+    def counted(*a, **kw):
+        count[0] += 1
+        return real(*a, **kw)
+
+    m.stream_round = counted
+    for mode in ts:                                                     # warm-up: weights, workspaces (and the count)
+        out[mode] = run("stream", m, q, host, rounds=mode)
+    m.stream_round = real
+    for _ in range(reps):
+        for mode in ts:
+            ts[mode].append(timed(lambda: run("stream", m, q, host, rounds=mode)))
+    same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(out["torch"], out["library"]))
+    return {"stream_rounds_torch_s": round(statistics.median(ts["torch"]), 4),
+            "stream_rounds_library_s": round(statistics.median(ts["library"]), 4), "rounds": count[0], "bit_equal": same}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--long", type=int, default=1000, help="video length of the second memory point (0: skip)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default="all", choices=["all", "stream"], help="stream: time the stream alone (kernel trace)")
+    ap.add_argument("--rounds", action="store_true", help='time rounds="torch" against rounds="library" and nothing else')
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = Pips(S=8, stride=STRIDE)
@@ -90,6 +116,10 @@ def main():
     names = ["stream"] if a.only == "stream" else ["stream", "queries", "chained"]
     res = {"config": "360x640 stride 4, N=256 over frames 0/33/66/99, chunks of 16, slots 24", "T": a.T}
     host = frames(0, a.T)                                               # host uint8 video: the stream is fed host chunks
+    if a.rounds:
+        res.update(compare_rounds(m, q, host, a.reps))
+        print(json.dumps(res))
+        return
     video = None if a.only == "stream" else host.to(dev)
     for name in names:
         run(name, m, q, host, video)                                    # warm-up: weights, workspaces
