@@ -19,17 +19,20 @@
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
 
-The chaining drivers take ``engine="torch" | "native"``.  ``"torch"`` (the default) keeps the hop's bookkeeping -- the indexed
-read of the start positions, the scatters into the trajectory, the sigmoid, ``skip_scan``, the index update -- as the torch ops
-of ``_hop``; ``"native"`` runs the whole hop as ONE library call (``Pips.chain_hop`` = ``pips_chain_hop``: the same bookkeeping
-as HIP kernels around the same tracker launches, state held as int32) and reads the live count back, one host sync per hop
-either way.  Both engines give the same hops and the same bits.  ``StreamTracker`` also takes ``rounds="torch" | "library"``:
-with ``"library"`` the round itself -- who is ready, who joins, the hop, which frames are final -- is one ``pips_stream_round``
-call on int32 state, and queries can be added while the video runs (``add_queries``, either value).
+The chaining drivers take ``engine="torch" | "native"``: one hop loop (``_chain``) on one of two engine classes that hold the chain
+state.  ``_TorchEngine`` (the default) keeps the hop's bookkeeping -- the indexed read of the start positions, the scatters into
+the trajectory, the sigmoid, ``skip_scan``, the index update -- as the torch ops of ``_hop``; ``_NativeEngine`` runs the whole hop as
+ONE library call (``Pips.chain_hop``: the same bookkeeping as HIP kernels around the same tracker launches, state held as int32)
+and reads the live count back, one host sync per hop either way.  Both give the same hops and the same bits.  ``StreamTracker``
+also takes ``rounds="torch" | "library"`` and keeps its device state in one object per value: ``_TorchRounds`` decides who is ready,
+who joins and which frames are final in torch ops and hops on the chosen engine; for ``_LibraryRounds`` the round itself is one
+``pips_stream_round`` call on int32 state.  Queries can be added while the video runs (``add_queries``, either value).
 """
 from __future__ import annotations
 
 import torch
+
+from . import ops
 
 
 @torch.no_grad()
@@ -100,7 +103,79 @@ def _hop(model, cache, trajs, vis_p, base, cur, active, feat, d=None, iters=6, c
     return c + (si if d is None else si * d), si, ffeat[0]
 
 
-ENGINES = ("torch", "native")
+class _TorchEngine:
+    """The chain state of ``engine="torch"``: int64 window starts ``cur`` and the shrinking list ``active`` of live particles.
+    trajs (L,n,2) / vis_p (L,n) or None hold frame f in row (f + base) % L; ``cur0`` (n,) the first window starts, ``dirs`` (n,)
+    +1 / -1 or None (all forward), ``clip`` (n,) the particles' videos or None, ``end`` the frames of the video (or (n,), of each
+    particle's own).  ``feat`` (n,128): the features carried from the first window; while None, the next window samples them.
+    The log is made of the tensors a hop produced anyway, so it is kept whether or not ``want_log`` is set."""
+
+    def __init__(self, model, cache, trajs, vis_p, base, cur0, dirs, clip, end, iters, want_log):
+        self.model, self.cache, self.trajs, self.vis_p, self.base, self.iters = model, cache, trajs, vis_p, base, iters
+        self.dirs, self.clip, self.end = dirs, clip, end
+        self.cur, self.active = cur0.clone(), torch.arange(cur0.shape[0], device=cur0.device)
+        self.feat, self.log = None, []
+
+    def window(self, active):
+        """``_hop`` for the particles ``active`` (int64) -> (their new window starts, their steps)"""
+        c, si, ffeat = _hop(self.model, self.cache, self.trajs, self.vis_p, self.base, self.cur, active, self.feat,
+                            None if self.dirs is None else self.dirs[active], self.iters, None if self.clip is None else self.clip[active])
+        if self.feat is None:
+            self.feat = ffeat.clone()                                              # carried forever (:57)
+        self.cur[active] = c
+        return c, si
+
+    def hop(self):
+        """every live particle advances by one window -> the number still live (one host sync: the live count)"""
+        active = self.active
+        c, si = self.window(active)
+        self.log.append((active, si))
+        end = self.end[active] if torch.is_tensor(self.end) else self.end        # the end of each particle's own video
+        self.active = active[c < end if self.dirs is None else (c < end) & (c >= 0)]
+        return self.active.numel()
+
+
+class _NativeEngine:
+    """The chain state of ``engine="native"``, a window being one ``Pips.chain_hop`` call: int32 ``cur`` / ``dirs`` / ``clip``, the
+    ping-pong lists ``active`` / ``next`` of live particles, their ``count`` and the ``steps``.  Arguments as ``_TorchEngine``; the
+    library takes the videos' lengths from the cache, so ``end`` is not looked at.  ``want_log=False`` spares the two copies per
+    hop that keep ``active`` / ``steps`` for the log (the buffers are reused by the next hop): the log then stays empty."""
+
+    def __init__(self, model, cache, trajs, vis_p, base, cur0, dirs, clip, end, iters, want_log):
+        self.model, self.cache, self.trajs, self.vis_p, self.base, self.iters = model, cache, trajs, vis_p, base, iters
+        i32, dev, n = torch.int32, cur0.device, cur0.shape[0]
+        self.cur = cur0.to(i32).contiguous()
+        self.dirs, self.clip = (None if x is None else x.to(i32).contiguous() for x in (dirs, clip))
+        self.active, self.next, self.n_act = torch.arange(n, dtype=i32, device=dev), torch.empty(n, dtype=i32, device=dev), n
+        self.count, self.steps = torch.zeros(1, dtype=i32, device=dev), torch.empty(n, dtype=i32, device=dev)
+        self.feat, self.want_log, self.log = None, want_log, []
+
+    def _launch(self, act):
+        sample = self.feat is None
+        if sample:                                                                  # written by this window (sample_feat)
+            self.feat = torch.empty(self.cur.shape[0], 128, dtype=torch.float32, device=self.cur.device)
+        self.model.chain_hop(self.cache, act, act.numel(), self.trajs, self.vis_p, self.base, self.cur, self.dirs, self.feat, self.next,
+                             self.count, self.steps, iters=self.iters, sample_feat=sample, clip=self.clip)
+
+    def window(self, active):
+        """one library hop for the particles ``active`` (ascending) -> (their new window starts, their steps)"""
+        act = active.to(torch.int32)
+        self._launch(act)
+        return self.cur[active], self.steps[:act.numel()]
+
+    def hop(self):
+        """every live particle advances by one window -> the number still live (one host sync: the live count)"""
+        act = self.active[:self.n_act]
+        self._launch(act)
+        if self.want_log:
+            self.log.append((act.clone(), self.steps[:self.n_act].clone()))
+        self.n_act = int(self.count.item())
+        self.active, self.next = self.next, self.active
+        return self.n_act
+
+
+_ENGINES = {"torch": _TorchEngine, "native": _NativeEngine}
+ENGINES = tuple(_ENGINES)
 
 
 def _check_engine(engine):
@@ -108,82 +183,25 @@ def _check_engine(engine):
         raise ValueError(f"engine must be one of {ENGINES}, not {engine!r}")
 
 
-def _rows(T):
-    """T = frames of the one video, or (n,) frames of each particle's video -> the frames the output buffer holds"""
-    return int(T.max()) if torch.is_tensor(T) else T
-
-
-def _chain_native(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, want_log=True, clip=None):
-    """``_chain`` with every hop as one ``pips_chain_hop`` call: the state (window starts, directions, the two ping-pong
-    lists of active particles) is int32 on the device and the loop reads the live count where ``_chain`` reads it.  With
-    ``clip`` the library takes the videos' lengths from the cache's clip table; ``T`` only sizes the output."""
-    dev = xy.device
-    pad = 7
-    n = xy.shape[0]
-    i32 = torch.int32
-    T = _rows(T)
-    c32 = None if clip is None else clip.to(i32).contiguous()
-    trajs = torch.zeros(T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
-    vis_p = torch.zeros(T + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
-    trajs[f0 + pad, torch.arange(n, device=dev)] = xy.to(torch.float32)
-    cur = f0.to(i32).contiguous()
-    d32 = None if dirs is None else dirs.to(i32).contiguous()
-    feat = torch.empty(n, 128, dtype=torch.float32, device=dev)                  # written by the first hop (sample_feat)
-    active, nxt = torch.arange(n, dtype=i32, device=dev), torch.empty(n, dtype=i32, device=dev)
-    count = torch.zeros(1, dtype=i32, device=dev)
-    steps = torch.empty(n, dtype=i32, device=dev) if want_log else None
-    log, n_act, first = [], n, True
-    while n_act > 0:
-        model.chain_hop(cache, active, n_act, trajs, vis_p, pad, cur, d32, feat, nxt, count, steps, iters=iters, sample_feat=first,
-                        clip=c32)
-        if want_log:
-            log.append((active[:n_act].clone(), steps[:n_act].clone()))
-        n_act = int(count.item())                                                 # (one host sync per hop: the live count)
-        active, nxt, first = nxt, active, False
-    return trajs[pad:pad + T], None if vis_p is None else vis_p[pad:pad + T], log
-
-
 def _chain(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, engine="torch", want_log=True, clip=None):
-    """The hop loop on the chosen engine -> (trajs, vis, hop log).  ``want_log=False`` spares the native engine the two copies
-    per hop that keep ``active`` / ``steps`` for the log (its buffers are reused by the next hop) and its log comes back
-    empty; the torch engine's log is made of the tensors the hop produced anyway, so it is returned either way.
-    ``clip`` (n,) int64: the particles of several videos on one cache (``Pips.encode_videos``) -- the video of each particle,
-    ``T`` then (n,) int64, the frames of each particle's video; trajs / vis come back with max(T) rows."""
-    if engine == "native":
-        return _chain_native(model, cache, T, xy, f0, dirs, iters, with_vis, want_log, clip)
-    return _chain_torch(model, cache, T, xy, f0, dirs, iters, with_vis, clip)
-
-
-def _chain_torch(model, cache, T, xy, f0, dirs=None, iters=6, with_vis=True, clip=None):
-    """The hop loop of chain_demo.py:40-83 for all particles at once.  xy (n,2) px at frames f0 (n,) int64; dirs (n,) +1 / -1
-    per particle or None (all forward).  A backward particle runs the loop on the time-reversed video: its window rows
-    read f, f-1, ... (``Pips.track``'s ``win_dir``) and it is finished when its start passes frame 0.
-    -> trajs (T,n,2), vis (T,n) logits (None without ``with_vis``) -- each frame from the last window that wrote it -- and
-    the hop log [(active, si)]."""
-    dev = xy.device
-    pad = 7
-    n = xy.shape[0]
-    Tq, T = T, _rows(T)                                                            # per-particle bound (clip) or the int itself
+    """The hop loop of chain_demo.py:40-83 for all particles at once, on the chosen engine.  xy (n,2) px at frames f0 (n,) int64;
+    dirs (n,) +1 / -1 per particle or None (all forward).  A backward particle runs the loop on the time-reversed video: its
+    window rows read f, f-1, ... (``Pips.track``'s ``win_dir``) and it is finished when its start passes frame 0.
+    ``clip`` (n,) int64: the video of each particle, for several videos on one cache (``Pips.encode_videos``); ``T`` is then (n,)
+    int64, the frames of each particle's video, and trajs / vis come back with max(T) rows.  -> trajs (T,n,2), vis (T,n) logits
+    (None without ``with_vis``), each frame from the last window that wrote it, and the engine's hop log [(active, si)]."""
+    dev, pad, n = xy.device, 7, xy.shape[0]
+    rows = int(T.max()) if torch.is_tensor(T) else T                              # the frames the output buffer holds
     # S - 1 frames of padding on both sides of the video: a window that runs past either end is written whole and cut off
     # on return (no per-row masks, no host round trips inside a hop)
-    trajs = torch.zeros(T + 2 * pad, n, 2, dtype=torch.float32, device=dev)
-    vis_p = torch.zeros(T + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
-    active = torch.arange(n, device=dev)
-    cur = f0.clone()                                                               # window starts
-    trajs[cur + pad, active] = xy.to(torch.float32)
-    feat = None
-    log = []
-    while active.numel() > 0:
-        c, si, ffeat = _hop(model, cache, trajs, vis_p, pad, cur, active, feat, None if dirs is None else dirs[active], iters,
-                            None if clip is None else clip[active])
-        if feat is None:
-            feat = ffeat.clone()                                                   # carried forever (:57)
-        cur[active] = c
-        log.append((active, si))
-        end = T if clip is None else Tq[active]                                   # the end of each particle's own video
-        live = c < end if dirs is None else (c < end) & (c >= 0)
-        active = active[live]                                                     # (one host sync per hop: the live count)
-    return trajs[pad:pad + T], None if vis_p is None else vis_p[pad:pad + T], log
+    trajs = torch.zeros(rows + 2 * pad, n, 2, dtype=torch.float32, device=dev)
+    vis_p = torch.zeros(rows + 2 * pad, n, dtype=torch.float32, device=dev) if with_vis else None
+    trajs[f0 + pad, torch.arange(n, device=dev)] = xy.to(torch.float32)
+    eng = _ENGINES[engine](model, cache, trajs, vis_p, pad, f0, dirs, clip, T, iters, want_log)
+    live = n
+    while live > 0:
+        live = eng.hop()
+    return trajs[pad:pad + rows], None if vis_p is None else vis_p[pad:pad + rows], eng.log
 
 
 def _hops(log, n):
@@ -349,7 +367,148 @@ def track_queries_batch(model, videos, queries, iters=6, return_hops=False, engi
     return out
 
 
-ROUNDS = ("torch", "library")
+def _wider(old, m):                                       # the row ring (L,n[,2]) with m more NaN columns
+    return torch.cat([old, old.new_full((old.shape[0], m) + tuple(old.shape[2:]), float("nan"))], dim=1)
+
+
+def _longer(old, new):                                    # the per-query array (n[,k]) with the rows ``new`` behind it, in its type
+    return torch.cat([old, new.to(old.device, old.dtype).reshape((-1,) + tuple(old.shape[1:]))])
+
+
+class _Rounds:
+    """The device state of a ``StreamTracker``, in the form its ``rounds`` value takes.  Both forms hold the output rows -- trajs
+    (L,N,2) and vis (L,N), frame f in row f % L, NaN where nothing was written -- and the queries ``tq`` / ``xy``, and offer
+      start(dev) / grow(t, xy, m)   the state of the tracker's N queries, none joined / m more columns, the old ones copied
+      pending()      lowest window start of the unfinished queries (None when all are finished)
+      run(final)     hop rounds until no query is ready -- one whose 8 window frames have all arrived (final: every unfinished
+                     one); yields (active indices, steps) per round ((None, None) when a library round keeps no steps)
+      emit(f0, f1)   the rows of frames [f0, f1) moved out of the ring (their rows are reset to NaN for reuse)"""
+
+    def __init__(self, tracker, engine):
+        self.t, self.engine = tracker, engine
+
+    def start(self, dev):
+        t = self.t
+        L = t.slots + t.S                                                         # output rows: frames f live in row f % L
+        self.trajs = torch.full((L, t.N, 2), float("nan"), dtype=torch.float32, device=dev)
+        self.vis = torch.full((L, t.N), float("nan"), dtype=torch.float32, device=dev)
+        self.tq, self.xy = t.tq_host.to(dev), t.xy_in.to(dev, torch.float32)
+
+    def grow(self, t, xy, m):
+        self.trajs, self.vis = _wider(self.trajs, m), _wider(self.vis, m)
+        self.tq, self.xy = _longer(self.tq, t), _longer(self.xy, xy)
+
+
+class _TorchRounds(_Rounds):
+    """``rounds="torch"``: which queries are ready, which join (``joined``) and which are finished (``done``) is decided here in
+    torch ops; the hop is a window of the chosen hop engine on the row ring (base 0), which holds the window starts ``cur``
+    (= t_q until a query joins) and the first-window features."""
+
+    def _engine(self, cur0, feat=None):
+        t = self.t
+        self.eng = _ENGINES[self.engine](t.model, t.cache, self.trajs, self.vis, 0, cur0, None, None, None, t.iters, False)
+        self.eng.feat = feat
+
+    cur = property(lambda self: self.eng.cur)
+
+    def start(self, dev):
+        super().start(dev)
+        self.joined, self.done = (torch.zeros(self.t.N, dtype=torch.bool, device=dev) for _ in range(2))
+        self._engine(self.tq)
+
+    def grow(self, t, xy, m):
+        super().grow(t, xy, m)
+        self.joined, self.done = _longer(self.joined, torch.zeros(m)), _longer(self.done, torch.zeros(m))
+        feat = self.eng.feat
+        self._engine(_longer(self.eng.cur, t), None if feat is None else _longer(feat, torch.zeros(m, feat.shape[1])))
+
+    def pending(self):
+        live = self.eng.cur[~self.done]
+        return None if live.numel() == 0 else int(live.min())
+
+    def run(self, final):
+        t, eng, T, L = self.t, self.eng, self.t.cache.T, self.trajs.shape[0]
+        while True:
+            ready = ~self.done & ((eng.cur < T) if final else (eng.cur + t.S <= T))
+            active = torch.nonzero(ready).squeeze(1)
+            if active.numel() == 0:
+                return
+            new = active[~self.joined[active]]
+            if new.numel() > 0:
+                # first window: the start is the query and the features are its point sample at t_q (feat_init=None)
+                self.trajs[self.tq[new] % L, new] = self.xy[new]
+                ff = t.model.track(t.cache, self.xy[new].unsqueeze(0), iters=0, return_feat=True,
+                                   win_start=self.tq[new].to(torch.int32).unsqueeze(0))[3]
+                if eng.feat is None:
+                    eng.feat = ff.new_zeros(self.tq.shape[0], ff.shape[-1])
+                eng.feat[new] = ff[0]
+                self.joined[new] = True
+            c, si = eng.window(active)
+            if final:
+                self.done[active] = c >= T
+            yield active, si
+
+    def emit(self, f0, f1):
+        rows = torch.arange(f0, f1, device=self.trajs.device) % self.trajs.shape[0]
+        out = (self.trajs[rows], self.vis[rows])
+        self.trajs[rows] = self.vis[rows] = float("nan")
+        return out
+
+
+class _LibraryRounds(_Rounds):
+    """``rounds="library"``: the int32 / float arrays of ``pips_stream_round`` (include/pips_hip.h) -- ``status`` (0 waiting, 1
+    joined, 2 done), ``cur``, ``feat``, the lists ``active`` / ``new_list`` / ``steps`` a round writes and its four ``counts`` -- and
+    ``low``, the host copy of counts[2].  The hop is the library's, so the engine is not looked at."""
+
+    def _lists(self):
+        """the lists a round writes, for the queries there are now (their contents do not outlive a push)"""
+        n, dev = self.tq.shape[0], self.tq.device
+        self.active, self.new_list = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        self.steps = torch.empty(n, dtype=torch.int32, device=dev) if self.t.hops is not None else None
+
+    def start(self, dev):
+        super().start(dev)
+        n, i32 = self.t.N, torch.int32
+        self.tq, self.xy = self.tq.to(i32), self.xy.contiguous()
+        self.cur = self.tq.clone()                                                # window start (= t_q until it joins)
+        self.status, self.counts = torch.zeros(n, dtype=i32, device=dev), torch.zeros(4, dtype=i32, device=dev)
+        self.feat = torch.zeros(n, 128, dtype=torch.float32, device=dev)
+        self._lists()
+        self.low = None if n == 0 else int(self.t.tq_host.min())
+
+    def grow(self, t, xy, m):
+        super().grow(t, xy, m)
+        self.cur, self.status = _longer(self.cur, t), _longer(self.status, torch.zeros(m))
+        self.feat = _longer(self.feat, torch.zeros(m, self.feat.shape[1]))
+        self._lists()
+        self.low = int(t.min()) if self.low is None else min(self.low, int(t.min()))
+
+    def pending(self):
+        return self.low
+
+    def run(self, final):
+        # select, then one pips_stream_round call per round while any query is ready (one host sync per round: the four counts)
+        t = self.t
+        if self.tq.shape[0] == 0:
+            return
+        ops.stream_select(t.cache.T, final, self.tq, self.xy, self.cur, self.status, self.trajs, self.active, self.new_list, self.counts)
+        n_act, n_new, low, _ = self.counts.tolist()
+        while n_act > 0:
+            act = self.active[:n_act].clone() if self.steps is not None else None      # the round rewrites the list
+            t.model.stream_round(t.cache, final, n_act, n_new, self.tq, self.xy, self.cur, self.status, self.feat, self.trajs,
+                                 self.vis, self.active, self.new_list, self.counts, self.steps, iters=t.iters)
+            yield act, None if act is None else self.steps[:n_act]
+            n_act, n_new, low, _ = self.counts.tolist()
+        self.low = None if low == 2 ** 31 - 1 else low
+
+    def emit(self, f0, f1):
+        if self.tq.shape[0] == 0:                                                 # (the library takes no empty state)
+            return self.trajs.new_empty(f1 - f0, 0, 2), self.vis.new_empty(f1 - f0, 0)
+        return ops.stream_emit(self.trajs, self.vis, f0, f1)
+
+
+_ROUNDS = {"torch": _TorchRounds, "library": _LibraryRounds}
+ROUNDS = tuple(_ROUNDS)
 
 
 class StreamTracker:
@@ -370,12 +529,10 @@ class StreamTracker:
     a chunk so that no slot is overwritten while a pending window can still read it: ``slots >= 9`` keeps the 8 frames of
     a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query.
 
-    ``rounds="torch"`` (the default): which particles are ready, which join and which are finished is decided here in torch ops,
-    a ``model.track`` call per round -- or, with ``engine="native"``, one ``pips_chain_hop`` call (window starts held as int32).
-    ``rounds="library"``: the state is the int32 / float arrays of ``pips_stream_round`` (include/pips_hip.h) and a round is
-    ONE library call -- join, hop and the selection of the next round; the host reads four ints per round (the numbers of ready
-    and of joining queries, the lowest pending window start) and moves the final frames out with ``pips_stream_emit``.  The hop
-    is the library's, so ``engine`` is not looked at.  Same hops and the same bits as ``rounds="torch"``."""
+    The tracker keeps what every ``rounds`` / ``engine`` value shares; the device state and the rounds are ``self.state``:
+    ``_TorchRounds`` (``rounds="torch"``, the default: a ``model.track`` call per round or, with ``engine="native"``, one
+    ``pips_chain_hop`` call) or ``_LibraryRounds`` (``rounds="library"``: a round is ONE ``pips_stream_round`` call, ``engine`` is not
+    looked at).  Same hops and the same bits either way."""
 
     S = 8
 
@@ -395,43 +552,10 @@ class StreamTracker:
         self.finished = False
         self.emitted = 0                                                          # frames [0, emitted) returned
         self.hops = [[] for _ in range(self.N)] if record_hops else None       # frame steps per query (grows with T)
+        self.state = _ROUNDS[rounds](self, engine)                                # the device state, made at the first push
 
-    def _start(self, frames):
-        self.size = tuple(frames.shape[3:])
-        self.cache = c = self.model.ring_cache(*self.size, self.slots)
-        dev = c.device
-        L = self.slots + self.S                                                   # output rows: frames f live in row f % L
-        self.L = L
-        self.trajs = torch.full((L, self.N, 2), float("nan"), dtype=torch.float32, device=dev)
-        self.vis = torch.full((L, self.N), float("nan"), dtype=torch.float32, device=dev)
-        self.tq = self.tq_host.to(dev)
-        self.xy = self.xy_in.to(dev, torch.float32)
-        self.cur = self.tq.clone()                                                # window start (= t_q until it joins)
-        self.emitted = 0
-        if self.rounds == "library":                                              # pips_stream_round's state
-            i32 = torch.int32
-            self.tq, self.cur, self.xy = self.tq.to(i32), self.cur.to(i32), self.xy.contiguous()
-            self.status = torch.zeros(self.N, dtype=i32, device=dev)              # 0 waiting, 1 joined, 2 done
-            self.feat = torch.zeros(self.N, 128, dtype=torch.float32, device=dev)
-            self.counts = torch.zeros(4, dtype=i32, device=dev)
-            self._lists()
-            self.low = None if self.N == 0 else int(self.tq_host.min())           # host copy of counts[2]
-            return
-        if self.engine == "native":                                               # pips_chain_hop's state
-            self.cur = self.cur.to(torch.int32)
-            self.count = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.next_active = torch.empty(self.N, dtype=torch.int32, device=dev)
-            self.steps = torch.empty(self.N, dtype=torch.int32, device=dev)
-        self.joined = torch.zeros(self.N, dtype=torch.bool, device=dev)
-        self.done = torch.zeros(self.N, dtype=torch.bool, device=dev)
-        self.feat = None                                                          # (N,128) features of the first windows
-
-    def _lists(self):
-        """the lists a library round writes, for N queries (their contents do not outlive a push)"""
-        dev = self.trajs.device
-        self.active = torch.empty(self.N, dtype=torch.int32, device=dev)
-        self.new_list = torch.empty(self.N, dtype=torch.int32, device=dev)
-        self.steps = torch.empty(self.N, dtype=torch.int32, device=dev) if self.hops is not None else None
+    # the state's output rows (slots + 8, N, 2) / (slots + 8, N) and window starts (N,)
+    trajs, vis, cur = (property(lambda self, k=k: getattr(self.state, k)) for k in ("trajs", "vis", "cur"))
 
     def add_queries(self, queries):
         """Further queries (1,m,3) = (t, x, y) while the video runs -> the columns (m,) they take in the outputs of the ``push``
@@ -452,39 +576,8 @@ class StreamTracker:
         if self.hops is not None:
             self.hops += [[] for _ in range(m)]
         if self.cache is not None and m > 0:
-            self._grow(t, xy, m)
+            self.state.grow(t, xy, m)
         return torch.arange(N, N + m)
-
-    def _grow(self, t, xy, m):
-        """the device state with m more columns: the old ones copied, the new ones as ``_start`` makes them"""
-        dev = self.trajs.device
-
-        def wider(old, fill):
-            return torch.cat([old, torch.full((old.shape[0], m) + tuple(old.shape[2:]), fill, dtype=old.dtype, device=dev)], dim=1)
-
-        def longer(old, new):
-            return torch.cat([old, new.to(dev, old.dtype).reshape((m,) + tuple(old.shape[1:]))])
-
-        self.trajs, self.vis = wider(self.trajs, float("nan")), wider(self.vis, float("nan"))
-        self.tq, self.xy, self.cur = longer(self.tq, t), longer(self.xy, xy), longer(self.cur, t)
-        if self.feat is not None:
-            self.feat = longer(self.feat, torch.zeros(m, self.feat.shape[1]))
-        if self.rounds == "library":
-            self.status = longer(self.status, torch.zeros(m))
-            self._lists()
-            self.low = int(t.min()) if self.low is None else min(self.low, int(t.min()))
-            return
-        if self.engine == "native":
-            self.next_active = torch.empty(self.N, dtype=torch.int32, device=dev)
-            self.steps = torch.empty(self.N, dtype=torch.int32, device=dev)
-        self.joined, self.done = longer(self.joined, torch.zeros(m)), longer(self.done, torch.zeros(m))
-
-    def _pending(self):
-        """lowest window start of the unfinished particles (None when all are finished)"""
-        if self.rounds == "library":
-            return self.low
-        live = self.cur[~self.done]
-        return None if live.numel() == 0 else int(live.min())
 
     @torch.no_grad()
     def push(self, frames):
@@ -493,20 +586,21 @@ class StreamTracker:
         if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[2] != 3:
             raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(frames.shape)}")
         if self.cache is None:
-            self._start(frames)
+            self.size = tuple(frames.shape[3:])
+            self.cache = self.model.ring_cache(*self.size, self.slots)
+            self.state.start(self.cache.device)
         elif tuple(frames.shape[3:]) != self.size:
             raise ValueError(f"frames of {tuple(frames.shape[3:])} pushed to a stream of {self.size}")
         f0, outs = self.emitted, []
         k, i = frames.shape[1], 0
         while i < k:
-            low = self._pending()
+            low = self.state.pending()
             # the slot of frame T + j holds frame T + j - slots until then: no pending window may still read that one
             room = self.slots if low is None else min(self.slots, low + self.slots - self.cache.T)
             n = min(k - i, room)
             self.model.encode(frames[:, i:i + n], into=self.cache)
             i += n
-            self._rounds(final=False)
-            outs.append(self._emit())
+            outs.append(self._rounds(final=False))
         return self._cat(f0, outs)
 
     @torch.no_grad()
@@ -517,80 +611,20 @@ class StreamTracker:
         if bool((self.tq_host > T - 1).any()):
             raise ValueError(f"a query frame lies beyond the last frame of the video ({T - 1})")
         self.finished = True
-        f0 = self.emitted
-        self._rounds(final=True)
-        return self._cat(f0, [self._emit()])
+        return self._cat(self.emitted, [self._rounds(final=True)])
 
     def _rounds(self, final):
-        """hop rounds until no particle is ready: one whose 8 window frames have all arrived (final: every unfinished one)"""
-        if self.rounds == "library":
-            return self._rounds_library(final)
-        T = self.cache.T
-        while True:
-            ready = ~self.done & ((self.cur < T) if final else (self.cur + self.S <= T))
-            active = torch.nonzero(ready).squeeze(1)
-            if active.numel() == 0:
-                return
-            new = active[~self.joined[active]]
-            if new.numel() > 0:
-                # first window: the start is the query and the features are its point sample at t_q (feat_init=None)
-                self.trajs[self.tq[new] % self.L, new] = self.xy[new]
-                ff = self.model.track(self.cache, self.xy[new].unsqueeze(0), iters=0, return_feat=True,
-                                      win_start=self.tq[new].to(torch.int32).unsqueeze(0))[3]
-                if self.feat is None:
-                    self.feat = ff.new_zeros(self.N, ff.shape[-1])
-                self.feat[new] = ff[0]
-                self.joined[new] = True
-            if self.engine == "native":
-                act = active.to(torch.int32)
-                self.model.chain_hop(self.cache, act, act.numel(), self.trajs, self.vis, 0, self.cur, None, self.feat,
-                                     self.next_active, self.count, self.steps, iters=self.iters)
-                c, si = self.cur[active], self.steps[:act.numel()]
-            else:
-                c, si, _ = _hop(self.model, self.cache, self.trajs, self.vis, 0, self.cur, active, self.feat, None, self.iters)
-                self.cur[active] = c
-            if final:
-                self.done[active] = c >= T
+        """the state's hop rounds, their steps recorded per query -> the rows of the frames that became final (None: none did)"""
+        for active, steps in self.state.run(final):
             if self.hops is not None:
-                for q, h in zip(active.tolist(), si.tolist()):
+                for q, h in zip(active.tolist(), steps.tolist()):
                     self.hops[q].append(h)
-
-    def _rounds_library(self, final):
-        """the same rounds with the state in the library's hands: select, then one ``pips_stream_round`` call per round while
-        any query is ready (one host sync per round: the four ints of ``counts``)"""
-        if self.N == 0:
-            return
-        from . import ops
-        ops.stream_select(self.cache.T, final, self.tq, self.xy, self.cur, self.status, self.trajs, self.active, self.new_list,
-                          self.counts)
-        n_act, n_new, low, _ = self.counts.tolist()
-        while n_act > 0:
-            act = self.active[:n_act].clone() if self.hops is not None else None      # the round rewrites the list
-            self.model.stream_round(self.cache, final, n_act, n_new, self.tq, self.xy, self.cur, self.status, self.feat, self.trajs,
-                                    self.vis, self.active, self.new_list, self.counts, self.steps, iters=self.iters)
-            if self.hops is not None:
-                for q, h in zip(act.tolist(), self.steps[:n_act].tolist()):
-                    self.hops[q].append(h)
-            n_act, n_new, low, _ = self.counts.tolist()
-        self.low = None if low == 2 ** 31 - 1 else low
-
-    def _emit(self):
-        """the rows of the frames that became final, moved out of the ring (their rows are reset to NaN for reuse)"""
-        low = self._pending()
-        end = self.cache.T if low is None else min(low, self.cache.T)
-        if end <= self.emitted:
+        low = self.state.pending()
+        f0, f1 = self.emitted, self.cache.T if low is None else min(low, self.cache.T)
+        if f1 <= f0:
             return None
-        if self.rounds == "library" and self.N > 0:
-            from . import ops
-            out = ops.stream_emit(self.trajs, self.vis, self.emitted, end)
-            self.emitted = end
-            return out
-        rows = torch.arange(self.emitted, end, device=self.trajs.device) % self.L
-        out = (self.trajs[rows], self.vis[rows])
-        self.trajs[rows] = float("nan")
-        self.vis[rows] = float("nan")
-        self.emitted = end
-        return out
+        self.emitted = f1
+        return self.state.emit(f0, f1)
 
     def _cat(self, f0, outs):
         outs = [o for o in outs if o is not None]

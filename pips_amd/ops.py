@@ -295,65 +295,51 @@ def _chain_f32(t):
 
 
 def chain_gather(trajs, base, cur, dirs, feat, active, n_act, sample_feat=False, clip=None):
-    """pips_chain_gather: the staging arrays of one hop for ``active[:n_act]`` -> (xy (n_act,2), ws, wd (n_act) int32,
+    """pips_chain_gather_clips: the staging arrays of one hop for ``active[:n_act]`` -> (xy (n_act,2), ws, wd (n_act) int32,
     fi (n_act,128); fi is left unwritten with ``sample_feat``).  trajs (L,n,2); cur / dirs / active int32, dirs may be None.
-    ``clip`` (n) int32: pips_chain_gather_clips -> (xy, ws, wd, wc, fi), wc (n_act) the staged video indices."""
+    ``clip`` (n) int32 -> (xy, ws, wd, wc, fi), wc (n_act) the staged video indices; None: a NULL table, the one-video form."""
     L, n = trajs.shape[0], trajs.shape[1]
     dev = trajs.device
     xy = torch.empty(n_act, 2, dtype=torch.float32, device=dev)
     ws = torch.empty(n_act, dtype=torch.int32, device=dev)
     wd = torch.empty(n_act, dtype=torch.int32, device=dev)
+    wc = None if clip is None else torch.empty(n_act, dtype=torch.int32, device=dev)
     fi = torch.empty(n_act, LATENT, dtype=torch.float32, device=dev)
-    if clip is not None:
-        wc = torch.empty(n_act, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _call("pips_chain_gather_clips", _chain_f32(trajs), L, int(base), n, _i32(cur), _i32(dirs), _i32(clip), _chain_f32(feat),
-                  _i32(active), int(n_act), int(bool(sample_feat)), _lib.ptr(xy), _lib.ptr(ws), _lib.ptr(wd), _lib.ptr(wc), _lib.ptr(fi),
-                  _stream())
-        return xy, ws, wd, wc, fi
     with torch.cuda.device(dev):
-        _call("pips_chain_gather", _chain_f32(trajs), L, int(base), n, _i32(cur), _i32(dirs), _chain_f32(feat), _i32(active), int(n_act),
-              int(bool(sample_feat)), _lib.ptr(xy), _lib.ptr(ws), _lib.ptr(wd), _lib.ptr(fi), _stream())
-    return xy, ws, wd, fi
+        _call("pips_chain_gather_clips", _chain_f32(trajs), L, int(base), n, _i32(cur), _i32(dirs), _i32(clip), _chain_f32(feat),
+              _i32(active), int(n_act), int(bool(sample_feat)), _lib.ptr(xy), _lib.ptr(ws), _lib.ptr(wd), _lib.ptr(wc), _lib.ptr(fi),
+              _stream())
+    return (xy, ws, wd, fi) if clip is None else (xy, ws, wd, wc, fi)
 
 
 def chain_step(win_trajs, win_vis, win_ffeat0, T, active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count,
                steps=None, sample_feat=False, clips=None):
-    """pips_chain_step, in place on the caller's state: write-back of the windows win_trajs (8,n_act,2) / win_vis (8,n_act),
+    """pips_chain_step_clips, in place on the caller's state: write-back of the windows win_trajs (8,n_act,2) / win_vis (8,n_act),
     skip scan, ``cur`` (and, with ``sample_feat``, ``feat`` from win_ffeat0 (n_act,128)) update, and the live members of
     ``active[:n_act]`` in their order in ``next_active`` with their number in ``next_count`` (device int32, not read back here).
-    ``clips`` = (clip (n), clip_frames (V)) int32: pips_chain_step_clips, live = inside the particle's own video."""
+    ``clips`` = (clip (n), clip_frames (V)) int32: live = inside the particle's own video; None: a NULL table, inside the T frames."""
     L, n = trajs.shape[0], trajs.shape[1]
+    clip, frames = (None, None) if clips is None else clips
     with torch.cuda.device(trajs.device):
-        if clips is not None:
-            clip, frames = clips
-            _call("pips_chain_step_clips", _chain_f32(win_trajs), _chain_f32(win_vis), _chain_f32(win_ffeat0), int(T), n, _i32(active),
-                  int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L, int(base), _i32(cur), _i32(dirs), _i32(clip),
-                  _i32(frames), frames.numel(), _chain_f32(feat), _i32(next_active), _i32(next_count), _i32(steps), _stream())
-            return
-        _call("pips_chain_step", _chain_f32(win_trajs), _chain_f32(win_vis), _chain_f32(win_ffeat0), int(T), n, _i32(active), int(n_act),
-              int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L, int(base), _i32(cur), _i32(dirs), _chain_f32(feat),
-              _i32(next_active), _i32(next_count), _i32(steps), _stream())
+        _call("pips_chain_step_clips", _chain_f32(win_trajs), _chain_f32(win_vis), _chain_f32(win_ffeat0), int(T), n, _i32(active),
+              int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L, int(base), _i32(cur), _i32(dirs), _i32(clip),
+              _i32(frames), 0 if frames is None else frames.numel(), _chain_f32(feat), _i32(next_active), _i32(next_count),
+              _i32(steps), _stream())
 
 
 def chain_hop(arena, pyr, T, R, H8, W8, times, stride, iters, flags, active, n_act, trajs, vis, base, cur, dirs, feat,
               next_active, next_count, steps, workspace, sample_feat=False, clips=None):
-    """pips_chain_hop: one hop of chain_demo.py:40-83 for ``active[:n_act]``, in place on the caller's state (see chain_step),
-    on the packed pyramid ``pyr`` of R frame slots holding T logical frames.  No host synchronisation.
-    ``clips`` = (clip (n), clip_first (V), clip_frames (V)) int32: pips_chain_hop_clips on a flat cache of V videos."""
+    """pips_chain_hop_clips: one hop of chain_demo.py:40-83 for ``active[:n_act]``, in place on the caller's state (see
+    chain_step), on the packed pyramid ``pyr`` of R frame slots holding T logical frames.  No host synchronisation.
+    ``clips`` = (clip (n), clip_first (V), clip_frames (V)) int32: a flat cache of V videos; None: a NULL table, one video."""
     L, n = trajs.shape[0], trajs.shape[1]
+    clip, first, frames = (None, None, None) if clips is None else clips
     with torch.cuda.device(trajs.device):
-        if clips is not None:
-            clip, first, frames = clips
-            _call("pips_chain_hop_clips", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
-                  int(iters), int(flags), n, _i32(active), int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L,
-                  int(base), _i32(cur), _i32(dirs), _i32(clip), _i32(first), _i32(frames), frames.numel(), _chain_f32(feat),
-                  _i32(next_active), _i32(next_count), _i32(steps), _lib.ptr(workspace), workspace.numel() * 4, _stream())
-            return
-        _call("pips_chain_hop", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
+        _call("pips_chain_hop_clips", _lib.ptr(arena), _lib.ptr(pyr), int(T), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
               int(iters), int(flags), n, _i32(active), int(n_act), int(bool(sample_feat)), _chain_f32(trajs), _chain_f32(vis), L,
-              int(base), _i32(cur), _i32(dirs), _chain_f32(feat), _i32(next_active), _i32(next_count), _i32(steps),
-              _lib.ptr(workspace), workspace.numel() * 4, _stream())
+              int(base), _i32(cur), _i32(dirs), _i32(clip), _i32(first), _i32(frames), 0 if frames is None else frames.numel(),
+              _chain_f32(feat), _i32(next_active), _i32(next_count), _i32(steps), _lib.ptr(workspace), workspace.numel() * 4,
+              _stream())
 
 
 def stream_workspace_bytes(n, iters):

@@ -189,6 +189,16 @@ class Pips(nn.Module):
                 ent = self._ws[slot] = (dims, torch.empty(nb // 4, dtype=torch.float32, device=device))
             return ent[1]
 
+    def _grown_ws(self, kind, dev, nbytes):
+        """Scratch of the tracker entry points: ONE buffer per (kind, device, stream), grown on demand -- chained tracking asks
+        with a different (shrinking) particle count at every hop, a stream with more queries after ``add_queries``."""
+        key = (kind, str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
+        with self._lock:
+            ws = self._ws.get(key)
+            if ws is None or ws.numel() * 4 < nbytes:
+                ws = self._ws[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            return ws
+
     def _aux(self, dev):
         """(packed weights, frame-time table) for ``dev`` -- built or refreshed under the module lock."""
         with self._lock:
@@ -281,6 +291,38 @@ class Pips(nn.Module):
         pyr = torch.zeros(lib.pips_pyramid_floats(int(slots), H, W, st), dtype=torch.float32, device=dev)
         return FeatureCache(pyr, 1, 0, H, W, st, slots=int(slots))
 
+    def _encoder_modes(self):                            # (bf16 conv operands, split-bf16 convs) under the current flags
+        fl = self._flags()
+        return bool(fl & ops.FLAG_BF16_ENCODER), bool(fl & ops.FLAG_SPLIT_BF16)
+
+    def _passes(self, frames, step, dev):
+        """frames (T,3,H,W), 0..255, uint8 or float, host or device -> (f0, f1, the packed pyramid of frames[f0:f1]) for each
+        encoder pass of at most ``step`` frames.  Iterate under ``torch.cuda.device(dev)``."""
+        arena = self._aux(dev)[0]
+        eb, sp = self._encoder_modes()
+        step = max(1, int(step))
+        for f0 in range(0, frames.shape[0], step):
+            f1 = min(frames.shape[0], f0 + step)
+            yield f0, f1, ops.encoder_fwd(arena, frames[f0:f1].to(dev), int(self.stride), bf16=eb, split=sp)
+
+    def _encode_flat(self, clips, step, dev, B, T):
+        """clips: list of (T_v,3,H,W) of one frame size, B x T frames in all -> their cache: each clip's passes, counted from its
+        own frame 0, copied into the flat levels; then the whole bf16 mirror (the parts' were laid out for their frame counts)."""
+        H, W = clips[0].shape[-2:]
+        st, F = int(self.stride), sum(c.shape[0] for c in clips)
+        pyr = torch.empty(_lib.load().pips_pyramid_floats(F, H, W, st), dtype=torch.float32, device=dev)
+        dst = ops.pyramid_levels(pyr, F, H, W, st)
+        first = 0
+        for c in clips:
+            for f0, f1, part in self._passes(c, step, dev):
+                for d, p in zip(dst, ops.pyramid_levels(part, f1 - f0, H, W, st)):
+                    d[first + f0:first + f1].copy_(p)
+            first += c.shape[0]
+        eb, sp = self._encoder_modes()
+        if eb:
+            ops.pyramid_mirror(pyr, F, H, W, st)
+        return FeatureCache(pyr, B, T, H, W, st, bf16_maps=eb and not sp)
+
     @torch.no_grad()
     def encode(self, rgbs, frames_per_pass: int = 16, into: FeatureCache = None) -> FeatureCache:
         """BasicEncoder + pyramid of every frame of ``rgbs (B,T,3,H,W)`` (0..255), once.
@@ -296,30 +338,16 @@ class Pips(nn.Module):
             return self._append(rgbs, frames_per_pass, into)
         if not rgbs.is_cuda:
             raise _lib.PipsHipError("pips_amd.Pips needs CUDA/HIP tensors; there is no CPU fallback")
-        lib = _lib.load()
         B, T, C3, H, W = rgbs.shape
         assert C3 == 3
-        dev, st = rgbs.device, int(self.stride)
-        F = B * T
+        dev, F = rgbs.device, B * T
+        frames = rgbs.reshape(F, 3, H, W)
         with torch.cuda.device(dev):
-            arena = self._aux(dev)[0]
-            frames = (rgbs.contiguous() if rgbs.dtype == torch.uint8 else rgbs.contiguous().to(torch.float32))
-            frames = frames.reshape(F, 3, H, W)
-            eb = bool(self._flags() & ops.FLAG_BF16_ENCODER)
-            sp = bool(self._flags() & ops.FLAG_SPLIT_BF16)
-            if F <= frames_per_pass:
-                pyr = ops.encoder_fwd(arena, frames, st, bf16=eb, split=sp)
-            else:
-                pyr = torch.empty(lib.pips_pyramid_floats(F, H, W, st), dtype=torch.float32, device=dev)
-                dst = ops.pyramid_levels(pyr, F, H, W, st)
-                for f0 in range(0, F, frames_per_pass):
-                    f1 = min(F, f0 + frames_per_pass)
-                    part = ops.encoder_fwd(arena, frames[f0:f1], st, bf16=eb, split=sp)
-                    for d, p in zip(dst, ops.pyramid_levels(part, f1 - f0, H, W, st)):
-                        d[f0:f1].copy_(p)
-                if eb:          # the parts' mirrors were laid out for their own frame counts: rewrite the whole one
-                    ops.pyramid_mirror(pyr, F, H, W, st)
-        return FeatureCache(pyr, B, T, H, W, st, bf16_maps=eb and not sp)
+            if F > frames_per_pass:
+                return self._encode_flat([frames], frames_per_pass, dev, B, T)
+            eb, sp = self._encoder_modes()                  # one pass: the encoder's own buffer, no copy
+            pyr = ops.encoder_fwd(self._aux(dev)[0], frames, int(self.stride), bf16=eb, split=sp)
+        return FeatureCache(pyr, B, T, H, W, int(self.stride), bf16_maps=eb and not sp)
 
     @torch.no_grad()
     def encode_videos(self, videos, frames_per_pass: int = 16) -> FeatureCache:
@@ -339,29 +367,10 @@ class Pips(nn.Module):
                 raise ValueError(f"the videos of one cache share a frame size: {tuple(v.shape[-2:])} against {(H, W)}")
             if not v.is_cuda or v.device != videos[0].device:
                 raise _lib.PipsHipError("pips_amd.Pips needs CUDA/HIP tensors on one device; there is no CPU fallback")
-        lib = _lib.load()
-        dev, st = videos[0].device, int(self.stride)
+        dev = videos[0].device
         lengths = [int(v.shape[1]) for v in videos]
-        F = sum(lengths)
-        step = max(1, int(frames_per_pass))
         with torch.cuda.device(dev):
-            arena = self._aux(dev)[0]
-            eb = bool(self._flags() & ops.FLAG_BF16_ENCODER)
-            sp = bool(self._flags() & ops.FLAG_SPLIT_BF16)
-            pyr = torch.empty(lib.pips_pyramid_floats(F, H, W, st), dtype=torch.float32, device=dev)
-            dst = ops.pyramid_levels(pyr, F, H, W, st)
-            first = 0
-            for v, T in zip(videos, lengths):
-                frames = (v.contiguous() if v.dtype == torch.uint8 else v.contiguous().to(torch.float32)).reshape(T, 3, H, W)
-                for f0 in range(0, T, step):                               # encode()'s passes for this video
-                    f1 = min(T, f0 + step)
-                    part = ops.encoder_fwd(arena, frames[f0:f1], st, bf16=eb, split=sp)
-                    for d, p in zip(dst, ops.pyramid_levels(part, f1 - f0, H, W, st)):
-                        d[first + f0:first + f1].copy_(p)
-                first += T
-            if eb:
-                ops.pyramid_mirror(pyr, F, H, W, st)
-            cache = FeatureCache(pyr, 1, F, H, W, st, bf16_maps=eb and not sp)
+            cache = self._encode_flat([v[0] for v in videos], frames_per_pass, dev, 1, sum(lengths))
             frames_t = torch.tensor(lengths, dtype=torch.int32)
             cache.clip_lengths = lengths
             cache.clip_frames = frames_t.to(dev)
@@ -369,24 +378,16 @@ class Pips(nn.Module):
         return cache
 
     def _append(self, rgbs, frames_per_pass, cache):
-        lib = _lib.load()
         B, T, C3, H, W = rgbs.shape
         if B != 1 or cache.B != 1 or C3 != 3 or (H, W) != (cache.H, cache.W) or int(self.stride) != cache.stride:
             raise ValueError(f"frames {tuple(rgbs.shape)} do not fit a ring cache of 1 x {cache.H} x {cache.W}, stride {cache.stride}")
-        dev, st = cache.device, cache.stride
-        step = max(1, min(int(frames_per_pass), cache.slots))
+        dev = cache.device
         with torch.cuda.device(dev):
-            arena = self._aux(dev)[0]
-            eb = bool(self._flags() & ops.FLAG_BF16_ENCODER)
-            sp = bool(self._flags() & ops.FLAG_SPLIT_BF16)
-            for f0 in range(0, T, step):
-                f1 = min(T, f0 + step)
-                part = rgbs[0, f0:f1].to(dev)
-                part = part if part.dtype == torch.uint8 else part.to(torch.float32)
-                pyr = ops.encoder_fwd(arena, part, st, bf16=eb, split=sp)
-                _lib.check(lib.pips_pyramid_append(_lib.ptr(pyr), f1 - f0, _lib.ptr(cache.pyr), cache.slots, cache.T, H, W, st,
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pips_pyramid_append")
+            for f0, f1, pyr in self._passes(rgbs[0], min(int(frames_per_pass), cache.slots), dev):
+                ops._call("pips_pyramid_append", _lib.ptr(pyr), f1 - f0, _lib.ptr(cache.pyr), cache.slots, cache.T, H, W, cache.stride,
+                          ops._stream())
                 cache.T += f1 - f0
+            eb, sp = self._encoder_modes()
         cache.bf16_maps = eb and not sp          # as for a cache encode() returns: the gather may read the mirror
         return cache
 
@@ -428,31 +429,18 @@ class Pips(nn.Module):
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
             fl = self._track_flags(cache)
-            nb = lib.pips_track_workspace_bytes_s(B, N, S)
-            # ONE tracker workspace per (device, stream), grown on demand: chained tracking calls this with
-            # a different (shrinking) N at every hop
-            key = ("track", str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
-            with self._lock:
-                ws = self._ws.get(key)
-                if ws is None or ws.numel() * 4 < nb:
-                    ws = self._ws[key] = torch.empty(nb // 4, dtype=f32, device=dev)
+            ws = self._grown_ws("track", dev, lib.pips_track_workspace_bytes_s(B, N, S))
             trajs = torch.empty(iters + 1, B, S, N, 2, dtype=f32, device=dev)
             vis_e = torch.empty(B, S, N, dtype=f32, device=dev)
             ffeat = torch.empty(B, N, self.latent_dim, dtype=f32, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if wc_i is not None:
-                rc = lib.pips_track_clips(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
-                                          _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(wc_i),
-                                          _lib.ptr(cache.clip_first), _lib.ptr(cache.clip_frames), len(cache.clip_lengths),
-                                          _lib.ptr(times), N, int(cache.stride), int(iters), fl, S, _lib.ptr(ws), ws.numel() * 4,
-                                          _lib.ptr(trajs), _lib.ptr(vis_e), _lib.ptr(ffeat), None, None, None, 0, stream)
-                _lib.check(rc, "pips_track_clips")
-            else:
-                rc = lib.pips_track_ring(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
-                                         _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(times), N,
-                                         int(cache.stride), int(iters), fl, S, _lib.ptr(ws), ws.numel() * 4, _lib.ptr(trajs),
-                                         _lib.ptr(vis_e), _lib.ptr(ffeat), stream)
-                _lib.check(rc, "pips_track_ring")
+            # the superset entry point: without win_clip a NULL table (the one-video ring form); no score-map block
+            first, frames, V = (None, None, 0) if wc_i is None else (cache.clip_first, cache.clip_frames, len(cache.clip_lengths))
+            rc = lib.pips_track_clips(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
+                                      _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(wc_i), _lib.ptr(first),
+                                      _lib.ptr(frames), V, _lib.ptr(times), N, int(cache.stride), int(iters), fl, S, _lib.ptr(ws),
+                                      ws.numel() * 4, _lib.ptr(trajs), _lib.ptr(vis_e), _lib.ptr(ffeat), None, None, None, 0,
+                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.check(rc, "pips_track_clips")
         preds = [trajs[i + 1] for i in range(iters)]
         preds2 = [trajs[0], trajs[0]] + preds + [trajs[iters], trajs[iters]]
         if return_feat:
@@ -469,12 +457,12 @@ class Pips(nn.Module):
     def chain_hop(self, cache: FeatureCache, active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps=None,
                   iters=6, sample_feat=False, clip=None):
         """One hop of the visibility-aware chaining (chain_demo.py:40-83) for the particles ``active[:n_act]``, in one library
-        call (``pips_chain_hop``): what ``track`` plus the driver's indexed reads, scatters and skip scan do, in place on the
+        call (``pips_chain_hop_clips``): what ``track`` plus the driver's indexed reads, scatters and skip scan do, in place on the
         caller's device state -- trajs (L,n,2) and vis (L,n) or None (frame f in row (f + base) % L), cur / dirs (None: all
         forward) / active int32, feat (n,128); the live particles land in ``next_active`` in their order and their number in
         ``next_count`` (device int32: the caller reads it back), the steps in ``steps``.  S = 8 and B = 1 only.
-        ``clip`` (n) int32, on a cache of several videos (``encode_videos``): the video of each particle
-        (``pips_chain_hop_clips``) -- ``cur`` counts frames of that video and a particle is live inside its own video."""
+        ``clip`` (n) int32, on a cache of several videos (``encode_videos``): the video of each particle (None: a NULL clip
+        table, the one-video form) -- ``cur`` counts frames of that video and a particle is live inside its own video."""
         assert self.S == 8 and cache.B == 1, "the reference chains 8-frame windows of one video (chain_demo.py:24,63-77)"
         if clip is not None and cache.clip_first is None:
             raise ValueError("clip needs a cache of several videos (Pips.encode_videos)")
@@ -483,12 +471,7 @@ class Pips(nn.Module):
         H8, W8 = cache.map_size
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
-            nb = _lib.load().pips_chain_workspace_bytes(int(n_act), int(iters))
-            key = ("chain", str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
-            with self._lock:
-                ws = self._ws.get(key)
-                if ws is None or ws.numel() * 4 < nb:           # grown on demand: n_act shrinks from hop to hop
-                    ws = self._ws[key] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+            ws = self._grown_ws("chain", dev, _lib.load().pips_chain_workspace_bytes(int(n_act), int(iters)))
             ops.chain_hop(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache),
                           active, n_act, trajs, vis, base, cur, dirs, feat, next_active, next_count, steps, ws,
                           sample_feat=sample_feat, clips=table)
@@ -508,12 +491,7 @@ class Pips(nn.Module):
         n = trajs.shape[1]
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
-            nb = ops.stream_workspace_bytes(n, iters)
-            key = ("stream", str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
-            with self._lock:
-                ws = self._ws.get(key)
-                if ws is None or ws.numel() * 4 < nb:           # grown on demand: n grows with add_queries
-                    ws = self._ws[key] = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+            ws = self._grown_ws("stream", dev, ops.stream_workspace_bytes(n, iters))
             ops.stream_round(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache), final,
                              n_act, n_new, tq, xy, cur, status, feat, trajs, vis, active, new_list, counts, steps, ws)
 

@@ -89,7 +89,7 @@ def _synthetic(layout, seed):
 
 
 def _expected_step(s, with_vis, sample_feat):
-    """The lines of drivers._hop after the track call, and of drivers._chain after the hop, on the CPU."""
+    """The lines of drivers._hop after the track call, and of drivers._TorchEngine.hop after it, on the CPU."""
     from pips_amd import drivers
     L, base, T = s["L"], s["base"], s["T"]
     active = s["active"].long()
@@ -352,3 +352,80 @@ def test_chain_hop_rejects_bad_arguments_and_leaves_the_state_alone():
         untouched()
     assert step(n_act=0) == 0
     untouched(but_count=0)
+
+
+# ------------------------------------------------------------------ the forwarding entry points
+def test_forwarding_entry_points_equal_the_wrappers_clip_forms(weights_tamed):
+    """pips_track_ring, pips_chain_gather, pips_chain_step and pips_chain_hop stay in the ABI as one-line forwards, and no Python
+    wrapper reaches them any more (Pips.track and ops.chain_* call the _clips forms with a NULL table).  Each is called here through
+    the binding table and its outputs and updated state are held, bit for bit, to the wrapper's: one video of 10 frames at 128x160,
+    3 particles -- from frame 0, a window 5..12 that runs past the last frame, a backward one (win_dir = -1) from frame 6 that runs
+    past frame 0 -- iters = 1, exact fp32."""
+    from pips_amd import _lib, ops
+    lib, P = _lib.load(), _lib.ptr
+    m = _model(weights_tamed)
+    T, H, W, n, iters, L, base = 10, 128, 160, 3, 1, 24, 7
+    cache = m.encode(_video(T, H, W, seed=34).to(DEV))
+    H8, W8 = cache.map_size
+    arena, times = m._aux(cache.device)
+    flags, stride = m._track_flags(cache), int(cache.stride)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g = torch.Generator().manual_seed(35)
+    xy = (torch.rand(n, 2, generator=g) * torch.tensor([W - 17.0, H - 17.0]) + 8.0).to(DEV)
+    feat0 = (torch.randn(n, 128, generator=g) * 0.1).to(DEV)
+    cur = torch.tensor([0, 5, 6], dtype=I32, device=DEV)
+    dirs = torch.tensor([1, 1, -1], dtype=I32, device=DEV)
+    active = torch.arange(n, dtype=I32, device=DEV)
+
+    def same(got, want, what):
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert a.dtype == b.dtype and torch.equal(_bits(a), _bits(b)), (what, k)
+
+    # tracker: Pips.track = pips_track_clips(win_clip = NULL)
+    preds, preds2, vis, ffeat, _ = m.track(cache, xy[None], iters=iters, win_start=cur[None], win_dir=dirs[None], return_feat=True)
+    nb = lib.pips_track_workspace_bytes_s(1, n, 8)
+    ws = torch.empty(nb // 4, device=DEV)
+    tr, vi, ff = torch.zeros(iters + 1, 1, 8, n, 2, device=DEV), torch.zeros(1, 8, n, device=DEV), torch.zeros(1, n, 128, device=DEV)
+    assert lib.pips_track_ring(P(arena), P(cache.pyr), 1, T, T, H8, W8, P(xy), None, None, P(cur), P(dirs), P(times), n, stride, iters,
+                               flags, 8, P(ws), nb, P(tr), P(vi), P(ff), stream) == 0
+    same((tr[0], tr[1], vi, ff), (preds2[0], preds[-1], vis, ffeat), "track")
+    assert bool(torch.isfinite(tr).all()) and not torch.equal(tr[1, 0, 0], tr[1, 0, 7])
+
+    def state():
+        s = dict(trajs=_nan_filled(L, n, 2).to(DEV), vis=_nan_filled(L, n).to(DEV), cur=cur.clone(), feat=feat0.clone(),
+                 nxt=torch.full((n,), -77, dtype=I32, device=DEV), count=torch.full((1,), -1, dtype=I32, device=DEV),
+                 steps=torch.full((n,), -1, dtype=I32, device=DEV))
+        s["trajs"][(cur.long() + base) % L, torch.arange(n, device=DEV)] = xy
+        return s
+
+    # gather (the carried features are staged: sample_feat = 0)
+    a = state()
+    want = ops.chain_gather(a["trajs"], base, a["cur"], dirs, a["feat"], active, n)
+    got = [torch.zeros_like(t) for t in want]
+    assert len(want) == 4
+    assert lib.pips_chain_gather(P(a["trajs"]), L, base, n, P(a["cur"]), P(dirs), P(a["feat"]), P(active), n, 0, *[P(t) for t in got],
+                                 stream) == 0
+    same(got, want, "gather")
+    assert torch.equal(got[0], xy) and got[2].tolist() == [1, 1, -1]
+    # step, on the windows the tracker gave (first window: the features are taken from it)
+    win = (tr[1, 0].contiguous(), vi[0].contiguous(), ff[0].contiguous())
+    a, b = state(), state()
+    ops.chain_step(*win, T, active, n, a["trajs"], a["vis"], base, a["cur"], dirs, a["feat"], a["nxt"], a["count"], a["steps"],
+                   sample_feat=True)
+    assert lib.pips_chain_step(*[P(t) for t in win], T, n, P(active), n, 1, P(b["trajs"]), P(b["vis"]), L, base, P(b["cur"]), P(dirs),
+                               P(b["feat"]), P(b["nxt"]), P(b["count"]), P(b["steps"]), stream) == 0
+    same(b.values(), a.values(), "step")
+    assert all(2 <= s <= 7 for s in b["steps"].tolist()) and torch.equal(b["feat"], ff[0])
+    # hop
+    a, b = state(), state()
+    m.chain_hop(cache, active, n, a["trajs"], a["vis"], base, a["cur"], dirs, a["feat"], a["nxt"], a["count"], a["steps"], iters=iters,
+                sample_feat=True)
+    nb = lib.pips_chain_workspace_bytes(n, iters)
+    ws = torch.empty(nb // 4, device=DEV)
+    assert lib.pips_chain_hop(P(arena), P(cache.pyr), T, T, H8, W8, P(times), stride, iters, flags, n, P(active), n, 1, P(b["trajs"]),
+                              P(b["vis"]), L, base, P(b["cur"]), P(dirs), P(b["feat"]), P(b["nxt"]), P(b["count"]), P(b["steps"]), P(ws),
+                              nb, stream) == 0
+    same(b.values(), a.values(), "hop")
+    k = int(b["count"].item())
+    assert all(2 <= s <= 7 for s in b["steps"].tolist()) and 0 <= k <= n and bool((b["nxt"][k:] == -77).all())
+    assert int((_bits(b["trajs"]) != NAN_FILL).sum()) == 8 * n * 2 and not torch.equal(b["cur"], cur)

@@ -357,7 +357,7 @@ def _synthetic(seed):
 
 
 def _expected_step(s, with_vis, sample_feat):
-    """The lines of drivers._hop after the track call and of drivers._chain_torch after the hop, on the CPU."""
+    """The lines of drivers._hop after the track call and of drivers._TorchEngine.hop after it, on the CPU."""
     from pips_amd import drivers
     L, base = s["L"], s["base"]
     active = s["active"].long()
@@ -383,7 +383,7 @@ def _expected_step(s, with_vis, sample_feat):
 @pytest.mark.parametrize("with_vis", [True, False])
 def test_chain_stages_with_clips_are_the_torch_lines_of_hop(with_vis, sample_feat):
     """pips_chain_gather_clips and pips_chain_step_clips on 23 of 37 particles of three videos (T = 9, 21, 13; L = 35, base 7)
-    against skip_scan and _hop's indexed assignments with the live test of _chain_torch, c < T of the particle's own video:
+    against skip_scan and _hop's indexed assignments with the live test of _TorchEngine.hop, c < T of the particle's own video:
     the staged video indices, steps, window starts, the compacted list and its count, the carried features, and trajs / vis as
     bit patterns over the whole NaN-payload buffers.  A particle of the 9-frame video finishes on frame 9 while the same step
     in the 21-frame video stays live."""

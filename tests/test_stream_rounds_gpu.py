@@ -59,7 +59,7 @@ def _select_state(n, seed, all_done=False):
 
 
 def _expected_select(s, final):
-    """the lines of drivers.StreamTracker._rounds / _pending that pips_stream_select stands for, on the CPU"""
+    """the lines of drivers._TorchRounds.run / pending that pips_stream_select stands for, on the CPU"""
     T, L = SEL_T, SEL_L
     status, cur, tq = s["status"].clone().long(), s["cur"].long(), s["tq"].long()
     trajs = s["trajs"].clone()
