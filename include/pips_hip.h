@@ -101,7 +101,10 @@ const char* pips_last_error(void);
  * pips_chain_hop_clips, pips_chain_gather_clips and pips_chain_step_clips (the windows of several videos on one flat cache:
  * a per-particle video index).  pips_chain_workspace_bytes grew by the staged video indices: size with THIS library.
  * pips_stream_select, pips_stream_round, pips_stream_emit and pips_stream_workspace_bytes (the rounds of a streamed video: which
- * queries are ready, which join, one hop, which frames are final -- one call per round). */
+ * queries are ready, which join, one hop, which frames are final -- one call per round); pips_track_rings,
+ * pips_mixer_input_build_rings, pips_pyramid_append_at, pips_stream_select_clips, pips_stream_round_clips,
+ * pips_stream_workspace_bytes_clips and pips_stream_emit_cols (several streamed videos on one flat cache of rings: one state and
+ * one round for all of them). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -219,6 +222,25 @@ int    pips_track_ring(const void* arena, const float* pyramid, int B, int T, in
  * pips_track_s (V and the tables are not read).  With win_clip, PIPS_E_ARG ahead of any launch for: V < 1, a NULL clip_first /
  * clip_frames, a NULL win_start, B != 1, R != T, a non-NULL ce_tgt. */
 int    pips_track_clips(const void* arena, const float* pyramid, int B, int T, int R, int H8, int W8,
+                        const float* xys, const float* coords_init, const float* feat_init,
+                        const int* win_start, const int* win_dir,
+                        const int* win_clip, const int* clip_first, const int* clip_frames, int V,
+                        const float* times, int N, int stride, int iters, int flags, int S,
+                        void* workspace, size_t workspace_bytes,
+                        float* out_trajs, float* out_vis, float* out_ffeat0,
+                        const float* ce_tgt, float* ce_terms, void* ce_ws, size_t ce_ws_bytes, void* stream);
+/* Several STREAMED videos in one call: the flat cache holds V rings of R frame slots each (R is one value per cache) instead of
+ * V linear videos.  The arguments are those of pips_track_clips with F in the place of T -- the pyramid is laid out for F frame
+ * slots (pips_pyramid_floats(F, ...)), F >= V*R -- and R = the slots of each video's ring:
+ *   clip_first  (V) device int32: first flat slot of video v's ring (v*R for rings laid side by side)
+ *   clip_frames (V) device int32: logical frames appended to video v so far; may exceed R; the caller updates it as it appends
+ *                                 (pips_pyramid_append_at)
+ * Row s of particle n's window reads flat slot clip_first[v] + (clamp(win_start + dir*s, 0, clip_frames[v]-1) mod R), v =
+ * win_clip[n]; the caller keeps every frame a window can read in its ring (pips_track_ring's rule, per video).  Containment as
+ * for pips_track_clips: v is clamped to [0, V-1], the flat slot to [0, F-1].  Results per particle are what pips_track_ring gives
+ * on that video's own ring (bit for bit while the mixer's GEMMs take the same route at both row counts).  PIPS_E_ARG ahead of any
+ * launch for: V < 1, R < 1, a NULL win_clip / clip_first / clip_frames / win_start, B != 1, F < V*R, a non-NULL ce_tgt. */
+int    pips_track_rings(const void* arena, const float* pyramid, int B, int F, int R, int H8, int W8,
                         const float* xys, const float* coords_init, const float* feat_init,
                         const int* win_start, const int* win_dir,
                         const int* win_clip, const int* clip_first, const int* clip_frames, int V,
@@ -366,6 +388,45 @@ int    pips_stream_round(const void* arena, const float* pyramid, int T, int R, 
                          int* active, int* new_list, int* counts, int* steps,
                          void* workspace, size_t workspace_bytes, void* stream);
 int    pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, void* stream);
+/* Several streams in one state: V videos of one frame size, each with its own length and its own end, on one flat cache of V
+ * rings of R slots (pips_track_rings).  The state of pips_stream_round, plus
+ *   clip        int32 (n)  the stream of each query (clamped to [0, V-1] where it is read)
+ *   clip_first  int32 (V)  first flat slot of each stream's ring
+ *   clip_frames int32 (V)  logical frames appended to each stream so far (the T of that stream's queries)
+ *   clip_final  int32 (V)  != 0: the stream has ended (the `final` of that stream's queries)
+ *   counts      int32 (4 + V) = {n_act, n_new, low over all streams, 0, low_0 .. low_{V-1}}; low_v = min cur over the queries of
+ *               stream v that are not done (INT_MAX: none)
+ * cur, tq and the rows of trajs / vis (frame f in row f mod L) count frames of the query's OWN stream.  A query of stream v is
+ * done / ready by pips_stream_select's rule with T = clip_frames[v] and final = clip_final[v]; the lists keep their ascending order
+ * (the same block scan).  The round stages clip[q] next to tq[q] for the join's point sample and hops with the clip table
+ * (pips_chain_hop over pips_track_rings).  The host loop of one wave of appends: pips_pyramid_append_at per stream (and the new
+ * clip_frames), pips_stream_select_clips, the counts copied back, then pips_stream_round_clips and the counts copied back while
+ * counts[0] > 0; frames [emitted_v, min(low_v, clip_frames[v])) of stream v are then final: pips_stream_emit_cols on its columns.
+ * Each stream keeps pips_stream_round's rules on its own (append up to clip_frames[v] <= low_v + R; no final rounds with a waiting
+ * query whose tq >= clip_frames[v]).  V <= PIPS_STREAM_V_MAX.
+ * PIPS_E_ARG ahead of any launch: what pips_stream_select / pips_stream_round answer it for, V < 1 or > PIPS_STREAM_V_MAX, a NULL
+ * clip / table, F < V*R.  PIPS_E_WORKSPACE: workspace_bytes < pips_stream_workspace_bytes_clips(n, iters, V) (0 for a V outside
+ * the range).  A rejected call writes nothing.
+ * pips_stream_emit_cols: pips_stream_emit for the columns cols[0..m) only (device int32, ascending, not verified) -- streams become
+ * final at different frames.  Rows f mod L, f in [f0, f1), of those columns go to the dense out_trajs (f1-f0, m, 2) / out_vis
+ * (f1-f0, m) as bit patterns, and 0x7fc00000 is stored back into exactly those elements; every other element stays bit-identical.
+ * A member of cols outside [0, n) is skipped: nothing is read or reset, and its output elements receive the same NaN.  f0 == f1
+ * or m == 0: PIPS_OK and nothing is done.  PIPS_E_ARG: n < 1, L < 16, m < 0, f1 < f0 or f1 - f0 > L, a NULL array. */
+#define PIPS_STREAM_V_MAX 64
+size_t pips_stream_workspace_bytes_clips(int n, int iters, int V);
+int    pips_stream_select_clips(int n, const int* tq, const float* xy, int* cur, int* status, const int* clip,
+                                const int* clip_frames, const int* clip_final, int V, float* trajs, int L,
+                                int* active, int* new_list, int* counts, void* stream);
+int    pips_stream_round_clips(const void* arena, const float* pyramid, int F, int R, int H8, int W8,
+                               const float* times, int stride, int iters, int flags,
+                               int n, int n_act, int n_new,
+                               const int* tq, const float* xy, int* cur, int* status, const int* clip, float* feat,
+                               float* trajs, float* vis, int L,
+                               const int* clip_first, const int* clip_frames, const int* clip_final, int V,
+                               int* active, int* new_list, int* counts, int* steps,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int    pips_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1, const int* cols, int m,
+                             float* out_trajs, float* out_vis, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 
@@ -383,6 +444,12 @@ int    pips_pyramid_mirror(float* pyramid, int F, int H, int W, int stride, void
  * the bf16 mirror of those slots from the fp32 levels in the same pass (pips_pyramid_mirror's rounding).  One launch.
  * Needs R >= 1, T0 >= 0 and 1 <= k <= R. */
 int    pips_pyramid_append(const float* src, int k, float* ring, int R, int T0, int H, int W, int stride, void* stream);
+/* The same between two positions: frames [src_first, src_first + k) of an encoder pyramid of F_src frames go into slots
+ * ring_first + (T0 + i) mod R, i < k, of a pyramid laid out for F slots (one ring of a cache of several, pips_track_rings), the
+ * bf16 mirror of those slots in the same pass.  One launch.  Checks as pips_pyramid_append, plus 0 <= src_first, src_first + k <=
+ * F_src, 0 <= ring_first and ring_first + R <= F: both ranges lie inside their buffers. */
+int    pips_pyramid_append_at(const float* src, int F_src, int src_first, int k, float* dst, int F, int ring_first, int R, int T0,
+                              int H, int W, int stride, void* stream);
 int    pips_encoder_fwd(const void* arena, const float* rgbs, int F, int H, int W, int stride,
                         float* pyramid, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -425,6 +492,11 @@ int    pips_mixer_input_build_ring(const float* pyramid, int B, int T, int R, in
                                    int flags, int S, float* X, void* stream);
 /* pips_mixer_input_build_ring with the clip table of pips_track_clips (win_clip = NULL: exactly pips_mixer_input_build_ring) */
 int    pips_mixer_input_build_clips(const float* pyramid, int B, int T, int R, int H8, int W8, const float* ffeats,
+                                    const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
+                                    const int* win_clip, const int* clip_first, const int* clip_frames, int V,
+                                    int flags, int S, float* X, void* stream);
+/* the gather of pips_track_rings: V rings of R slots on a pyramid laid out for F slots (checks as pips_track_rings) */
+int    pips_mixer_input_build_rings(const float* pyramid, int B, int F, int R, int H8, int W8, const float* ffeats,
                                     const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
                                     const int* win_clip, const int* clip_first, const int* clip_frames, int V,
                                     int flags, int S, float* X, void* stream);

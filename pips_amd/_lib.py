@@ -50,6 +50,9 @@ SIGNATURES = {
     "pips_track_clips": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, fp, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, fp, fp,
                                  c_void_p, c_size_t, c_void_p]),
+    "pips_track_rings": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int, fp, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, fp, fp, fp, fp, fp,
+                                 c_void_p, c_size_t, c_void_p]),
     "pips_chain_threshold": (c_float, [c_int]),
     "pips_chain_workspace_bytes": (c_size_t, [c_int, c_int]),
     "pips_chain_gather": (c_int, [fp, c_int, c_int, c_int, c_void_p, c_void_p, fp, c_void_p, c_int, c_int, fp, c_void_p, c_void_p, fp,
@@ -72,12 +75,22 @@ SIGNATURES = {
                                   c_void_p, fp, c_void_p, c_void_p, fp, fp, fp, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),
     "pips_stream_emit": (c_int, [fp, fp, c_int, c_int, c_int, c_int, fp, fp, c_void_p]),
+    "pips_stream_workspace_bytes_clips": (c_size_t, [c_int, c_int, c_int]),
+    "pips_stream_select_clips": (c_int, [c_int, c_void_p, fp, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, fp, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pips_stream_round_clips": (c_int, [c_void_p, fp, c_int, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p, fp, c_void_p, c_void_p, c_void_p, fp, fp, fp, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pips_stream_emit_cols": (c_int, [fp, fp, c_int, c_int, c_int, c_int, c_void_p, c_int, fp, fp, c_void_p]),
     "pips_encoder_workspace_bytes": (c_size_t, [c_int] * 4),
     "pips_pyramid_floats": (c_size_t, [c_int] * 4),
     "pips_pyramid_offset": (c_size_t, [c_int] * 5),
     "pips_pyramid_mirror_offset": (c_size_t, [c_int] * 4),
     "pips_pyramid_mirror": (c_int, [fp, c_int, c_int, c_int, c_int, c_void_p]),
     "pips_pyramid_append": (c_int, [fp, c_int, fp, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "pips_pyramid_append_at": (c_int, [fp, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "pips_mixer_input_build_rings": (c_int, [fp, c_int, c_int, c_int, c_int, c_int, fp, fp, fp, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_int, c_int, fp, c_void_p]),
     "pips_mixer_input_build_ex": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, fp, c_int, c_void_p, c_int, fp, c_void_p]),
     "pips_mixer_input_build_win": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, fp, c_int, c_void_p, c_void_p, c_int, c_int,
                                            fp, c_void_p]),

@@ -590,17 +590,24 @@ int encoder_impl(const void* arena_v, const void* rgbs, int F, int H, int W, int
 
 // ------------------------------------------------------------------ windows of several videos
 // The checks every clip form shares, ahead of any launch, and the table the kernels take.  win_clip == null: no table, no check.
+// ring == 0: the videos lie one after the other on a linear cache (R = T).  ring > 0 (the _rings forms; a table is then required):
+// every video is a ring of `ring` slots on a buffer of R = T = F flat slots.
 int clip_table(const int* win_clip, const int* clip_first, const int* clip_frames, int V, const int* win_start, int B, int T, int R,
-               const char* who, ClipTable& ct) {
-    ct = ClipTable{win_clip, clip_first, clip_frames, V};
-    if (win_clip == nullptr) return PIPS_OK;
+               int ring, const char* who, ClipTable& ct) {
+    ct = ClipTable{win_clip, clip_first, clip_frames, V, ring > 0 ? ring : R};
+    if (ring == 0 && win_clip == nullptr) return PIPS_OK;
+    PIPS_CHECK_ARG(ring >= 0, "%s: a ring needs R >= 1 slots (R=%d)", who, ring);
     PIPS_CHECK_ARG(V >= 1, "%s: a clip table needs V >= 1 videos (V=%d)", who, V);
-    PIPS_CHECK_ARG(clip_first && clip_frames, "%s: win_clip needs clip_first and clip_frames", who);
+    PIPS_CHECK_ARG(win_clip && clip_first && clip_frames, "%s: win_clip needs clip_first and clip_frames", who);
     PIPS_CHECK_ARG(win_start != nullptr, "%s: win_clip needs win_start", who);
     PIPS_CHECK_ARG(B == 1, "%s: the videos of a clip table share ONE flat cache, B = 1 (B=%d)", who, B);
     PIPS_CHECK_ARG(R == T, "%s: a clip table needs a linear cache, R = T (R=%d, T=%d)", who, R, T);
+    PIPS_CHECK_ARG(ring == 0 || (long long)V * ring <= T, "%s: %d rings of %d slots need a buffer of %lld slots (F=%d)", who, V, ring,
+                   (long long)V * ring, T);
     return PIPS_OK;
 }
+// the slots-per-video argument of a _rings entry point as the `ring` of the descriptors: a value < 1 stays invalid
+int ring_arg(int R) { return R >= 1 ? R : -1; }
 
 // ------------------------------------------------------------------ correlation gather
 enum GatherRoute { GATHER_AUTO, GATHER_DIRECT, GATHER_TILED };   // AUTO: tiled for a dense query set if the call allows it
@@ -610,12 +617,13 @@ enum GatherRoute { GATHER_AUTO, GATHER_DIRECT, GATHER_TILED };   // AUTO: tiled 
 // bf16_maps: the gather reads the bf16 mirror behind the fp32 levels.  The tiled kernels need scratch, a dense un-windowed
 // query set and R = T = S = PIPS_S; ev != null (tiled only): 4 events around their three launches.
 // win_clip (per-particle video index) + clip_first / clip_frames (V videos): the windows of several videos on one flat linear
-// cache, B = 1 and R = T = all frames (ClipTable, common.h); read with win_start only.
+// cache, B = 1 and R = T = all frames (ClipTable, common.h); read with win_start only.  ring > 0: the videos are rings of `ring`
+// slots each on that buffer (R = T = its flat slots).
 struct GatherCall {
     const float* pyramid; int B, T, R, S, H8, W8;
     const float* ffeats; const float* coords; const float* times; int N;
     const int* win_start; const int* win_dir;
-    const int* win_clip; const int* clip_first; const int* clip_frames; int V;
+    const int* win_clip; const int* clip_first; const int* clip_frames; int V, ring;
     float* X;
     bool bf16_maps; GatherRoute route;
     void* scratch; size_t scratch_bytes; hipEvent_t* ev;
@@ -629,7 +637,7 @@ int mixer_input(const GatherCall& g) {
     const PyramidView v = pyramid_view(g.B * g.R, g.H8, g.W8);
     PIPS_CHECK_ARG(!v.empty(), "mixer_input: map too small");
     ClipTable ct;
-    RUN(clip_table(g.win_clip, g.clip_first, g.clip_frames, g.V, g.win_start, g.B, g.T, g.R, "mixer_input", ct));
+    RUN(clip_table(g.win_clip, g.clip_first, g.clip_frames, g.V, g.win_start, g.B, g.T, g.R, g.ring, "mixer_input", ct));
     const ClipTable* clips = g.win_clip != nullptr ? &ct : nullptr;
     const float* mirror = g.pyramid + v.levels;
     const bool can_tile = g.scratch != nullptr && g.win_start == nullptr && g.win_dir == nullptr && g.R == PIPS_S && g.T == g.R &&
@@ -854,13 +862,14 @@ int score_map_prepare(const float* pyramid, int B, int S, int H8, int W8, float*
 // The tracker on cached maps.  pyramid: B clips x R frame slots of H8 x W8 level-0 pixels holding T logical frames (a linear
 // cache has R = T); S = window length (tokens per particle) the arena was packed for, S == PIPS_S runs the specialised kernels.
 // win_start / win_dir / coords_init / feat_init / out_ffeat0 and the score-map block ce_* may be null; so may win_clip, with
-// which the pyramid is ONE flat linear cache of V videos (B = 1, R = T = all frames; clip_first / clip_frames: GatherCall).
+// which the pyramid is ONE flat linear cache of V videos (B = 1, R = T = all frames; clip_first / clip_frames: GatherCall) or,
+// with ring > 0, of V rings of `ring` slots.
 struct TrackCall {
     const void* arena; const float* pyramid;
     int B, T, R, S, H8, W8;
     const float* xys; const float* coords_init; const float* feat_init;
     const int* win_start; const int* win_dir;
-    const int* win_clip; const int* clip_first; const int* clip_frames; int V;
+    const int* win_clip; const int* clip_first; const int* clip_frames; int V, ring;
     const float* times; int N, stride, iters, flags;
     void* workspace; size_t workspace_bytes;
     float* out_trajs; float* out_vis; float* out_ffeat0;
@@ -876,7 +885,7 @@ int track_impl(const TrackCall& c) {
     PIPS_CHECK_ARG(c.H8 >= 8 && c.W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", c.H8, c.W8);
     PIPS_CHECK_ARG(c.win_dir == nullptr || c.win_start != nullptr, "track: win_dir needs win_start");
     ClipTable ct;
-    RUN(clip_table(c.win_clip, c.clip_first, c.clip_frames, c.V, c.win_start, c.B, c.T, c.R, "track", ct));
+    RUN(clip_table(c.win_clip, c.clip_first, c.clip_frames, c.V, c.win_start, c.B, c.T, c.R, c.ring, "track", ct));
     PIPS_CHECK_ARG(c.win_clip == nullptr || c.ce_tgt == nullptr, "track: no score-map terms on a clip table");
     const int B = c.B, N = c.N, S = c.S;
     const TrackPlan P = plan_track(B, N, S);
@@ -917,7 +926,7 @@ int track_impl(const TrackCall& c) {
     g.pyramid = c.pyramid; g.B = B; g.T = c.T; g.R = c.R; g.S = S; g.H8 = c.H8; g.W8 = c.W8;
     g.ffeats = ffeats; g.coords = coords; g.times = c.times; g.N = N;
     g.win_start = c.win_start; g.win_dir = c.win_dir;
-    g.win_clip = c.win_clip; g.clip_first = c.clip_first; g.clip_frames = c.clip_frames; g.V = c.V;
+    g.win_clip = c.win_clip; g.clip_first = c.clip_first; g.clip_frames = c.clip_frames; g.V = c.V; g.ring = c.ring;
     g.X = ws + P.X;
     g.bf16_maps = (c.flags & PIPS_FLAG_BF16_MAPS) != 0;
     g.route = GATHER_AUTO;
@@ -1036,10 +1045,11 @@ int chain_step(const ChainState& s, const float* win_trajs, const float* win_vis
                              s.dir, s.feat, next_active, next_count, steps, st, s.clip, s.clip_frames, s.V);
 }
 
-// One hop: chain_gather, the tracker on (B = 1, N = n_act) windows, chain_step.  Shared by pips_chain_hop* and pips_stream_round.
+// One hop: chain_gather, the tracker on (B = 1, N = n_act) windows, chain_step.  Shared by pips_chain_hop* and pips_stream_round*.
+// ring > 0: the videos of the clip table are rings of `ring` slots (TrackCall).
 int chain_hop(const ChainState& s, const void* arena, const float* pyramid, int T, int R, int H8, int W8, const float* times, int stride,
               int iters, int flags, const int* clip_first, int* next_active, int* next_count, int* steps, void* workspace,
-              size_t workspace_bytes, hipStream_t st) {
+              size_t workspace_bytes, hipStream_t st, int ring = 0) {
     const int n_act = s.n_act;
     // every check ahead of the first launch: a rejected call leaves the caller's state as it was
     RUN(check_chain_state(s, "chain_hop"));
@@ -1069,7 +1079,7 @@ int chain_hop(const ChainState& s, const void* arena, const float* pyramid, int 
                              s.sample_feat ? win_ffeat0 : nullptr, st);
     c.R = R;
     c.win_dir = s.dir != nullptr ? win_dir : nullptr;
-    if (s.clip != nullptr) { c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = s.clip_frames; c.V = s.V; }
+    if (s.clip != nullptr) { c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = s.clip_frames; c.V = s.V; c.ring = ring; }
     RUN(track_impl(c));
     return chain_step(s, win_trajs + (size_t)iters * PIPS_S * n_act * 2, win_vis, win_ffeat0, T, next_active, next_count, steps, st);
 }
@@ -1078,8 +1088,9 @@ int chain_hop(const ChainState& s, const void* arena, const float* pyramid, int 
 // workspace of one round over a state of n queries, in floats: a hop's for n_act = n, the staging of the joining queries' point
 // sample (its tracker workspace is the hop's, idle until the hop starts) and the hop's compacted list and count, which a stream
 // does not read (stream_select_kernel decides who is ready)
-struct StreamPlan { size_t chain, jxy, jtq, jfeat, jtrajs, jvis, next_active, next_count, total; };
-StreamPlan plan_stream(int n, int iters) {
+// clips: a state over several streams also stages the joining queries' stream indices
+struct StreamPlan { size_t chain, jxy, jtq, jfeat, jtrajs, jvis, next_active, next_count, jclip, total; };
+StreamPlan plan_stream(int n, int iters, bool clips = false) {
     StreamPlan P;
     Bump b;
     P.chain = b.take(plan_chain(n, iters).total);
@@ -1090,8 +1101,77 @@ StreamPlan plan_stream(int n, int iters) {
     P.jvis = b.take((size_t)PIPS_S * n);
     P.next_active = b.take(n);
     P.next_count = b.take(1);
+    P.jclip = clips ? b.take(n) : 0;
     P.total = b.off;
     return P;
+}
+
+// One round of a stream state (pips_stream_round) or of a state over V streams (pips_stream_round_clips: clips != null, T = R = the
+// flat slots of the cache, ring = the slots of each stream's ring).  Every check ahead of the first launch.
+struct StreamRound {
+    const void* arena; const float* pyramid; int T, R, ring, H8, W8; const float* times; int stride, iters, flags, final_;
+    int n, n_act, n_new; const int* tq; const float* xy; int* cur; int* status; float* feat; float* trajs; float* vis; int L;
+    int* active; int* new_list; int* counts; int* steps; void* workspace; size_t workspace_bytes;
+    const StreamClips* clips; const int* clip_first;
+};
+int check_stream_clips(const StreamClips& k, const char* who) {
+    PIPS_CHECK_ARG(k.V >= 1 && k.V <= STREAM_V_MAX, "%s: need 1 <= V <= %d streams (V=%d)", who, STREAM_V_MAX, k.V);
+    PIPS_CHECK_ARG(k.clip && k.frames && k.final_, "%s: null pointer", who);
+    return PIPS_OK;
+}
+int stream_round(const StreamRound& r, hipStream_t st) {
+    const int n = r.n, n_act = r.n_act, n_new = r.n_new, iters = r.iters;
+    const bool clips = r.clips != nullptr;
+    PIPS_CHECK_ARG(n >= 1, "stream_round: need n >= 1 (n=%d)", n);
+    PIPS_CHECK_ARG(n_act >= 0 && n_act <= n && n_new >= 0 && n_new <= n_act,
+                   "stream_round: need 0 <= n_new <= n_act <= n (n_new=%d, n_act=%d, n=%d)", n_new, n_act, n);
+    PIPS_CHECK_ARG(r.L >= 2 * PIPS_S, "stream_round: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, r.L);
+    const int slots = clips ? r.ring : r.R;
+    PIPS_CHECK_ARG(slots >= PIPS_S + 1, "stream_round: a frame ring needs R >= %d slots, a window and a new frame (R=%d)", PIPS_S + 1,
+                   slots);
+    PIPS_CHECK_ARG(r.T >= 1, "stream_round: need T >= 1 (T=%d)", r.T);
+    PIPS_CHECK_ARG(iters >= 0 && r.stride >= 1 && r.H8 >= 8 && r.W8 >= 8,
+                   "stream_round: need iters >= 0, stride >= 1 and a map of at least 8x8");
+    PIPS_CHECK_ARG(r.arena && r.pyramid && r.times && r.tq && r.xy && r.cur && r.status && r.feat && r.trajs && r.vis && r.active &&
+                   r.new_list && r.counts && r.workspace, "stream_round: null pointer");
+    if (clips) {
+        RUN(check_stream_clips(*r.clips, "stream_round"));
+        PIPS_CHECK_ARG(r.clip_first != nullptr, "stream_round: null pointer");
+        PIPS_CHECK_ARG((long long)r.clips->V * r.ring <= r.T, "stream_round: %d rings of %d slots need a buffer of %lld slots (F=%d)",
+                       r.clips->V, r.ring, (long long)r.clips->V * r.ring, r.T);
+    }
+    // the hop's and the point sample's own plans lie inside the regions sized for n (n_new <= n_act <= n)
+    const StreamPlan P = plan_stream(n, iters, clips);
+    const ChainPlan CP = plan_chain(n, iters);
+    const size_t join_track = n_new > 0 ? plan_track(1, n_new, PIPS_S).total : 0;
+    const size_t hop = n_act > 0 ? plan_chain(n_act, iters).total : 0;
+    if (r.workspace_bytes < P.total * sizeof(float) || hop > CP.total || join_track > plan_track(1, n, PIPS_S).total) {
+        set_error("stream_round: workspace %zu < %zu bytes", r.workspace_bytes, P.total * sizeof(float));
+        return PIPS_E_WORKSPACE;
+    }
+    if (n_act == 0) return PIPS_OK;
+    float* ws = (float*)r.workspace;
+    const int* clip = clips ? r.clips->clip : nullptr;
+    const int* frames = clips ? r.clips->frames : nullptr;
+    const int V = clips ? r.clips->V : 0, ring = clips ? r.ring : 0;
+    if (n_new > 0) {
+        // the joining queries' first-window features: the point sample of a track call without feat_init, at their own frames
+        float* jxy = ws + P.jxy; int* jtq = reinterpret_cast<int*>(ws + P.jtq); float* jfeat = ws + P.jfeat;
+        int* jclip = clips ? reinterpret_cast<int*>(ws + P.jclip) : nullptr;
+        RUN(launch_stream_join_gather(r.new_list, n_new, n, r.xy, r.tq, jxy, jtq, st, clip, jclip));
+        TrackCall c = track_call(r.arena, r.pyramid, 1, r.T, r.H8, r.W8, jxy, nullptr, nullptr, jtq, r.times, n_new, r.stride, 0, r.flags,
+                                 ws + P.chain + CP.track, join_track * sizeof(float), ws + P.jtrajs, ws + P.jvis, jfeat,
+                                 st);
+        c.R = r.R;
+        if (clips) { c.win_clip = jclip; c.clip_first = r.clip_first; c.clip_frames = frames; c.V = V; c.ring = ring; }
+        RUN(track_impl(c));
+        RUN(launch_stream_join_scatter(r.new_list, n_new, n, jfeat, r.feat, st));
+    }
+    const ChainState s = {n, r.active, n_act, 0, r.trajs, r.vis, r.L, 0, r.cur, nullptr, r.feat, clip, frames, V};
+    RUN(chain_hop(s, r.arena, r.pyramid, r.T, r.R, r.H8, r.W8, r.times, r.stride, iters, r.flags, r.clip_first,
+                  reinterpret_cast<int*>(ws + P.next_active), reinterpret_cast<int*>(ws + P.next_count), r.steps, ws + P.chain,
+                  CP.total * sizeof(float), st, ring));
+    return launch_stream_select(r.T, r.final_, n, r.tq, r.xy, r.cur, r.status, r.trajs, r.L, r.active, r.new_list, r.counts, st, r.clips);
 }
 
 }  // namespace
@@ -1214,6 +1294,22 @@ int pips_pyramid_append(const float* src, int k, float* ring, int R, int T0, int
     for (int l = 0; l < PIPS_LEVELS; ++l) pf8[l] = to.lh[l] * to.lw[l] * PIPS_C / 8;
     return launch_pyramid_append(src, from.off, k, ring, to.off, ring + to.levels, pf8, R, T0, (hipStream_t)stream);
 }
+int pips_pyramid_append_at(const float* src, int F_src, int src_first, int k, float* dst, int F, int ring_first, int R, int T0, int H,
+                           int W, int stride, void* stream) {
+    PIPS_CHECK_ARG(src != nullptr && dst != nullptr, "pyramid_append_at: null pointer");
+    PIPS_CHECK_ARG(R >= 1 && T0 >= 0 && k >= 1 && k <= R, "pyramid_append_at: need R >= 1, T0 >= 0 and 1 <= k <= R (k=%d, R=%d, T0=%d)",
+                   k, R, T0);
+    PIPS_CHECK_ARG(H > 0 && W > 0 && stride >= 1, "pyramid_append_at: bad geometry");
+    PIPS_CHECK_ARG(src_first >= 0 && F_src >= 1 && (long long)src_first + k <= F_src,
+                   "pyramid_append_at: frames [%d, %d + %d) lie outside a source of %d frames", src_first, src_first, k, F_src);
+    PIPS_CHECK_ARG(ring_first >= 0 && F >= 1 && (long long)ring_first + R <= F,
+                   "pyramid_append_at: slots [%d, %d + %d) lie outside a buffer of %d slots", ring_first, ring_first, R, F);
+    const PyramidView from = pyramid_view(F_src, H / stride, W / stride), to = pyramid_view(F, H / stride, W / stride);
+    PIPS_CHECK_ARG(!to.empty(), "pyramid_append_at: map too small");
+    int pf8[PIPS_LEVELS];
+    for (int l = 0; l < PIPS_LEVELS; ++l) pf8[l] = to.lh[l] * to.lw[l] * PIPS_C / 8;
+    return launch_pyramid_append(src, from.off, k, dst, to.off, dst + to.levels, pf8, R, T0, (hipStream_t)stream, src_first, ring_first);
+}
 
 int pips_encoder_fwd(const void* arena, const float* rgbs, int F, int H, int W, int stride, float* pyramid,
                      void* workspace, size_t workspace_bytes, void* stream) {
@@ -1274,6 +1370,20 @@ int pips_mixer_input_build_clips(const float* pyramid, int B, int T, int R, int 
     g.win_start = win_start;
     g.win_dir = win_dir;
     g.win_clip = win_clip; g.clip_first = clip_first; g.clip_frames = clip_frames; g.V = V;
+    g.bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
+    g.route = GATHER_DIRECT;
+    return mixer_input(g);
+}
+
+int pips_mixer_input_build_rings(const float* pyramid, int B, int F, int R, int H8, int W8, const float* ffeats,
+                                 const float* coords, const float* times, int N, const int* win_start, const int* win_dir,
+                                 const int* win_clip, const int* clip_first, const int* clip_frames, int V, int flags, int S,
+                                 float* X, void* stream) {
+    GatherCall g = gather_call(pyramid, B, F, H8, W8, ffeats, coords, times, N, X, stream);
+    g.S = S;
+    g.win_start = win_start;
+    g.win_dir = win_dir;
+    g.win_clip = win_clip; g.clip_first = clip_first; g.clip_frames = clip_frames; g.V = V; g.ring = ring_arg(R);
     g.bf16_maps = (flags & PIPS_FLAG_BF16_MAPS) != 0;
     g.route = GATHER_DIRECT;
     return mixer_input(g);
@@ -1420,6 +1530,20 @@ int pips_track_clips(const void* arena, const float* pyramid, int B, int T, int 
     c.ce_tgt = ce_tgt; c.ce_terms = ce_terms; c.ce_ws = ce_ws; c.ce_ws_bytes = ce_ws_bytes;
     return track_impl(c);
 }
+int pips_track_rings(const void* arena, const float* pyramid, int B, int F, int R, int H8, int W8, const float* xys,
+                     const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
+                     const int* win_clip, const int* clip_first, const int* clip_frames, int V, const float* times, int N,
+                     int stride, int iters, int flags, int S, void* workspace, size_t workspace_bytes, float* out_trajs,
+                     float* out_vis, float* out_ffeat0, const float* ce_tgt, float* ce_terms, void* ce_ws, size_t ce_ws_bytes,
+                     void* stream) {
+    TrackCall c = track_call(arena, pyramid, B, F, H8, W8, xys, coords_init, feat_init, win_start, times, N, stride, iters, flags,
+                             workspace, workspace_bytes, out_trajs, out_vis, out_ffeat0, stream);
+    c.S = S;
+    c.win_dir = win_dir;
+    c.win_clip = win_clip; c.clip_first = clip_first; c.clip_frames = clip_frames; c.V = V; c.ring = ring_arg(R);
+    c.ce_tgt = ce_tgt; c.ce_terms = ce_terms; c.ce_ws = ce_ws; c.ce_ws_bytes = ce_ws_bytes;
+    return track_impl(c);
+}
 int pips_track_win(const void* arena, const float* pyramid, int B, int T, int H8, int W8, const float* xys,
                    const float* coords_init, const float* feat_init, const int* win_start, const int* win_dir,
                    const float* times, int N, int stride, int iters, int flags, int S, void* workspace,
@@ -1493,43 +1617,33 @@ int pips_stream_round(const void* arena, const float* pyramid, int T, int R, int
                       int flags, int final, int n, int n_act, int n_new, const int* tq, const float* xy, int* cur, int* status,
                       float* feat, float* trajs, float* vis, int L, int* active, int* new_list, int* counts, int* steps,
                       void* workspace, size_t workspace_bytes, void* stream) {
-    // every check ahead of the first launch: a rejected call leaves the caller's state as it was
-    PIPS_CHECK_ARG(n >= 1, "stream_round: need n >= 1 (n=%d)", n);
-    PIPS_CHECK_ARG(n_act >= 0 && n_act <= n && n_new >= 0 && n_new <= n_act,
-                   "stream_round: need 0 <= n_new <= n_act <= n (n_new=%d, n_act=%d, n=%d)", n_new, n_act, n);
-    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_round: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
-    PIPS_CHECK_ARG(R >= PIPS_S + 1, "stream_round: a frame ring needs R >= %d slots, a window and a new frame (R=%d)", PIPS_S + 1, R);
-    PIPS_CHECK_ARG(T >= 1, "stream_round: need T >= 1 (T=%d)", T);
-    PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "stream_round: need iters >= 0, stride >= 1 and a map of at least 8x8");
-    PIPS_CHECK_ARG(arena && pyramid && times && tq && xy && cur && status && feat && trajs && vis && active && new_list && counts &&
-                   workspace, "stream_round: null pointer");
-    // the hop's and the point sample's own plans lie inside the regions sized for n (n_new <= n_act <= n)
-    const StreamPlan P = plan_stream(n, iters);
-    const ChainPlan CP = plan_chain(n, iters);
-    const size_t join_track = n_new > 0 ? plan_track(1, n_new, PIPS_S).total : 0;
-    const size_t hop = n_act > 0 ? plan_chain(n_act, iters).total : 0;
-    if (workspace_bytes < P.total * sizeof(float) || hop > CP.total || join_track > plan_track(1, n, PIPS_S).total) {
-        set_error("stream_round: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));
-        return PIPS_E_WORKSPACE;
-    }
-    if (n_act == 0) return PIPS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    float* ws = (float*)workspace;
-    if (n_new > 0) {
-        // the joining queries' first-window features: the point sample of a track call without feat_init, at their own frames
-        float* jxy = ws + P.jxy; int* jtq = reinterpret_cast<int*>(ws + P.jtq); float* jfeat = ws + P.jfeat;
-        RUN(launch_stream_join_gather(new_list, n_new, n, xy, tq, jxy, jtq, st));
-        TrackCall c = track_call(arena, pyramid, 1, T, H8, W8, jxy, nullptr, nullptr, jtq, times, n_new, stride, 0, flags,
-                                 ws + P.chain + CP.track, join_track * sizeof(float), ws + P.jtrajs, ws + P.jvis, jfeat,
-                                 st);
-        c.R = R;
-        RUN(track_impl(c));
-        RUN(launch_stream_join_scatter(new_list, n_new, n, jfeat, feat, st));
-    }
-    const ChainState s = {n, active, n_act, 0, trajs, vis, L, 0, cur, nullptr, feat, nullptr, nullptr, 0};
-    RUN(chain_hop(s, arena, pyramid, T, R, H8, W8, times, stride, iters, flags, nullptr, reinterpret_cast<int*>(ws + P.next_active),
-                  reinterpret_cast<int*>(ws + P.next_count), steps, ws + P.chain, CP.total * sizeof(float), st));
-    return launch_stream_select(T, final, n, tq, xy, cur, status, trajs, L, active, new_list, counts, st);
+    const StreamRound r = {arena, pyramid, T, R, 0, H8, W8, times, stride, iters, flags, final, n, n_act, n_new, tq, xy, cur, status, feat,
+                           trajs, vis, L, active, new_list, counts, steps, workspace, workspace_bytes, nullptr, nullptr};
+    return stream_round(r, (hipStream_t)stream);
+}
+size_t pips_stream_workspace_bytes_clips(int n, int iters, int V) {
+    if (n <= 0 || iters < 0 || V < 1 || V > STREAM_V_MAX) return 0;
+    return plan_stream(n, iters, true).total * sizeof(float);
+}
+int pips_stream_select_clips(int n, const int* tq, const float* xy, int* cur, int* status, const int* clip, const int* clip_frames,
+                             const int* clip_final, int V, float* trajs, int L, int* active, int* new_list, int* counts,
+                             void* stream) {
+    const StreamClips k = {clip, clip_frames, clip_final, V};
+    PIPS_CHECK_ARG(n >= 1, "stream_select: need n >= 1 (n=%d)", n);
+    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_select: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
+    PIPS_CHECK_ARG(tq && xy && cur && status && trajs && active && new_list && counts, "stream_select: null pointer");
+    RUN(check_stream_clips(k, "stream_select"));
+    return launch_stream_select(0, 0, n, tq, xy, cur, status, trajs, L, active, new_list, counts, (hipStream_t)stream, &k);
+}
+int pips_stream_round_clips(const void* arena, const float* pyramid, int F, int R, int H8, int W8, const float* times, int stride,
+                            int iters, int flags, int n, int n_act, int n_new, const int* tq, const float* xy, int* cur, int* status,
+                            const int* clip, float* feat, float* trajs, float* vis, int L, const int* clip_first,
+                            const int* clip_frames, const int* clip_final, int V, int* active, int* new_list, int* counts, int* steps,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    const StreamClips k = {clip, clip_frames, clip_final, V};
+    const StreamRound r = {arena, pyramid, F, F, R, H8, W8, times, stride, iters, flags, 0, n, n_act, n_new, tq, xy, cur, status, feat,
+                           trajs, vis, L, active, new_list, counts, steps, workspace, workspace_bytes, &k, clip_first};
+    return stream_round(r, (hipStream_t)stream);
 }
 int pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, void* stream) {
     PIPS_CHECK_ARG(n >= 1, "stream_emit: need n >= 1 (n=%d)", n);
@@ -1539,6 +1653,16 @@ int pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, flo
     if (f0 == f1) return PIPS_OK;                 // (no frame: the outputs are empty and may be NULL)
     PIPS_CHECK_ARG(out_trajs && out_vis, "stream_emit: null pointer");
     return launch_stream_emit(trajs, vis, L, n, f0, f1, out_trajs, out_vis, (hipStream_t)stream);
+}
+int pips_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1, const int* cols, int m, float* out_trajs,
+                          float* out_vis, void* stream) {
+    PIPS_CHECK_ARG(n >= 1 && m >= 0, "stream_emit_cols: need n >= 1 and m >= 0 (n=%d, m=%d)", n, m);
+    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_emit_cols: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
+    PIPS_CHECK_ARG(f1 >= f0 && (long long)f1 - f0 <= L, "stream_emit_cols: need 0 <= f1 - f0 <= L (f0=%d, f1=%d, L=%d)", f0, f1, L);
+    PIPS_CHECK_ARG(trajs && vis, "stream_emit_cols: null pointer");
+    if (f0 == f1 || m == 0) return PIPS_OK;                 // (nothing to move: the outputs are empty and may be NULL)
+    PIPS_CHECK_ARG(cols && out_trajs && out_vis, "stream_emit_cols: null pointer");
+    return launch_stream_emit_cols(trajs, vis, L, n, f0, f1, cols, m, out_trajs, out_vis, (hipStream_t)stream);
 }
 
 // ---- whole forward

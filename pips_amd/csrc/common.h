@@ -144,19 +144,21 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // slot of logical frame f >= 0 in a ring of R frame slots (a linear cache, R = frames, never wraps)
 __device__ __forceinline__ int ring_slot(int f, int R) { return f < R ? f : f % R; }
 
-// Several videos on ONE flat linear cache (B = 1): video v holds frames[v] frames from flat frame first[v] on, and particle pn
-// belongs to video win_clip[pn].  All three are device int32 arrays; win_clip == null = no table (one video per clip).
+// Several videos on ONE flat cache (B = 1): video v holds frames[v] logical frames in a ring of R slots from flat slot first[v]
+// on, and particle pn belongs to video win_clip[pn].  All three are device int32 arrays; win_clip == null = no table (one video
+// per clip).  The linear form (the videos one after the other) is the ring that never wraps: R >= every frames[v].
 struct ClipTable {
     const int* win_clip;     // (particles)
     const int* first;        // (V)
     const int* frames;       // (V)
     int V;
+    int R;                   // slots of each video's ring
 };
-// flat frame of frame f of particle pn's video: f is clamped to the video's own ends -- the repeats past the last frame and
-// before frame 0 never reach a neighbour -- and, containment, v to [0, V-1] and the result to the F frames of the buffer
+// flat slot of frame f of particle pn's video: f is clamped to the video's own ends -- the repeats past the last frame and
+// before frame 0 never reach a neighbour -- and, containment, v to [0, V-1] and the result to the F slots of the buffer
 __device__ __forceinline__ int clip_frame(const ClipTable& ct, int pn, int f, int F) {
     const int v = min(max(ct.win_clip[pn], 0), ct.V - 1);
-    return min(max(ct.first[v] + min(max(f, 0), ct.frames[v] - 1), 0), F - 1);
+    return min(max(ct.first[v] + ring_slot(min(max(f, 0), ct.frames[v] - 1), ct.R), 0), F - 1);
 }
 
 // InstanceNorm partials of a convolution tile, one per WAVE ROW (m tile, wm) and channel, about a PIVOT -- the value of
@@ -425,7 +427,8 @@ int launch_pyramid_mirror(const float* pyramid, size_t floats, void* mirror, hip
 // k encoded frames (levels at src_off, pf8[l] = 8-float groups per frame of level l) -> ring slots (T0 + i) mod R of a pyramid
 // with levels at dst_off and its bf16 mirror at dst_mirror (same element offsets as the fp32 levels), in one pass
 int launch_pyramid_append(const float* src, const size_t* src_off, int k, float* dst, const size_t* dst_off, void* dst_mirror,
-                          const int* pf8, int R, int T0, hipStream_t st);
+                          const int* pf8, int R, int T0, hipStream_t st, int src_first = 0, int dst_first = 0);
+// (src_first: the first of the k frames inside src; dst_first: the first flat slot of the ring inside dst)
 // LDS-tiled gather for dense query sets (gather_tiled.hip)
 size_t tiled_gather_scratch_bytes(int B, int N, int H8, int W8);
 bool tiled_gather_wanted(int B, int N, int H8, int W8, bool bf16_maps = false);
@@ -466,13 +469,22 @@ int launch_chain_step(const float* win_trajs, const float* win_vis, const float*
 // ---------------------------------------------------------------- streamed chaining bookkeeping (stream.hip)
 // one pass over the n queries of a caller-owned stream state: the ready ones in `active`, the ready ones still waiting in
 // `new_list` (their start rows seeded, status 1), both ascending; counts = {n_act, n_new, lowest pending window start, 0}
+// clips: the state follows V streams -- clip (n) the stream of each query, frames / final_ (V) device int32 the frames appended to
+// each stream so far and whether it has ended (they replace T / final_); counts is then (4 + V), the lowest pending window
+// start of each stream behind the four
+constexpr int STREAM_V_MAX = PIPS_STREAM_V_MAX;
+struct StreamClips { const int* clip; const int* frames; const int* final_; int V; };
 int launch_stream_select(int T, int final_, int n, const int* tq, const float* xy, const int* cur, int* status, float* trajs, int L,
-                         int* active, int* new_list, int* counts, hipStream_t st);
-// the xys / win_start of the joining queries' point sample, and the scatter of the features it returned into feat
+                         int* active, int* new_list, int* counts, hipStream_t st, const StreamClips* clips = nullptr);
+// the xys / win_start (and, with clip, win_clip in sclip) of the joining queries' point sample, and the scatter of the features it
+// returned into feat
 int launch_stream_join_gather(const int* new_list, int n_new, int n, const float* xy, const int* tq, float* sxy, int* stq,
-                              hipStream_t st);
+                              hipStream_t st, const int* clip = nullptr, int* sclip = nullptr);
 int launch_stream_join_scatter(const int* new_list, int n_new, int n, const float* sfeat, float* feat, hipStream_t st);
 // rows (f mod L), f in [f0, f1), of trajs (L,n,2) / vis (L,n) to dense outputs; those rows are reset to the fp32 quiet NaN
 int launch_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, float* out_trajs, float* out_vis, hipStream_t st);
+// the same for the columns cols[0..m) only (device int32): dense (f1-f0, m, 2) / (f1-f0, m) outputs, those elements reset to NaN
+int launch_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1, const int* cols, int m, float* out_trajs,
+                            float* out_vis, hipStream_t st);
 
 }  // namespace pips

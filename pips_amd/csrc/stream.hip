@@ -1,8 +1,9 @@
 // Streamed chaining (drivers.StreamTracker) as device-side bookkeeping around the tracker and pips_chain_hop: which queries of a
 // caller-owned state are ready for a window, which of them join with this round, the lowest window start still pending
 // (stream_select_kernel), the staging and the scatter of a joining query's first-window features (stream_join_*_kernel) and the
-// move of the frames that became final out of the row ring (stream_emit_kernel).  Plain HIP; built with the default floating-point
-// flags, as chain.hip is.  No atomics: the order of the two lists is part of the contract.
+// move of the frames that became final out of the row ring (stream_emit_kernel; stream_emit_cols_kernel for the columns of one
+// stream of several).  Plain HIP; built with the default floating-point flags, as chain.hip is.  No atomics on the lists: their
+// order is part of the contract.
 #include <climits>
 
 #include "common.h"
@@ -26,31 +27,50 @@ struct SelectArgs {
     const int* tq; const float* xy; const int* cur;
     int* status; float* trajs; int* active; int* new_list; int* counts;
     int T, final_, n, L;
+    // CLIPS: V streams in one state -- the stream of each query, the frames appended to each stream and whether it has ended
+    const int* clip; const int* clip_frames; const int* clip_final; int V;
 };
 
 // ONE block walks the n queries in chunks of SEL_THREADS, a thread per query.  The ready queries of a chunk get consecutive
 // slots of `active`, the ready ones that were still waiting consecutive slots of `new_list`, by a block scan each (ballot inside a
 // wave, the waves' counts through LDS) on top of the offsets carried from the chunks before: both lists ascend.  The lowest
 // window start of the queries that are not done is a wave reduction plus LDS at the end of the same walk.
+// CLIPS: a query is judged by the frames and the end of its own stream, and counts[4 + v] receives the lowest window start of
+// stream v -- an integer minimum through LDS (order-independent).  A template parameter, so that the one-stream instantiation is
+// the code it was.
+template <bool CLIPS>
 __global__ __launch_bounds__(SEL_THREADS) void stream_select_kernel(const SelectArgs a) {
     __shared__ int wave_act[SEL_WAVES];
     __shared__ int wave_new[SEL_WAVES];
     __shared__ int wave_low[SEL_WAVES];
+    __shared__ int clip_low[CLIPS ? STREAM_V_MAX : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int carried_act = 0, carried_new = 0, low = INT_MAX;
+    if (CLIPS) {
+        if (tid < STREAM_V_MAX) clip_low[tid] = INT_MAX;
+        __syncthreads();
+    }
     for (int q0 = 0; q0 < a.n; q0 += SEL_THREADS) {
         const int q = q0 + tid;
         bool ready = false, fresh = false;
         if (q < a.n) {
             int s = a.status[q];
             const int c = a.cur[q];
-            if (a.final_ && s == 1 && c >= a.T) {          // its last window ran past the end of the video
+            int T = a.T, v = 0;
+            bool final_ = a.final_ != 0;
+            if (CLIPS) {
+                v = min(max(a.clip[q], 0), a.V - 1);
+                T = a.clip_frames[v];
+                final_ = a.clip_final[v] != 0;
+            }
+            if (final_ && s == 1 && c >= T) {          // its last window ran past the end of the video
                 s = 2;
                 a.status[q] = 2;
             }
             if (s != 2) {
                 low = min(low, c);
-                ready = a.final_ ? c < a.T : c <= a.T - STREAM_S;      // all 8 frames of its window have arrived
+                if (CLIPS) atomicMin(&clip_low[v], c);                  // (LDS)
+                ready = final_ ? c < T : c <= T - STREAM_S;      // all 8 frames of its window have arrived
                 fresh = ready && s == 0;
             }
         }
@@ -94,13 +114,15 @@ __global__ __launch_bounds__(SEL_THREADS) void stream_select_kernel(const Select
         a.counts[2] = m;
         a.counts[3] = 0;
     }
+    if (CLIPS && tid < a.V) a.counts[4 + tid] = clip_low[tid];      // (the barrier above orders the LDS minima)
 }
 
 // the start positions and query frames of the joining queries new_list[0..n_new): the xys / win_start of their point sample.  A
 // member outside [0, n) is never dereferenced: zeros are staged for it and the scatter ignores it.
 __global__ __launch_bounds__(SEL_THREADS) void stream_join_gather_kernel(const int* __restrict__ new_list, int n_new, int n,
                                                                          const float* __restrict__ xy, const int* __restrict__ tq,
-                                                                         float* __restrict__ sxy, int* __restrict__ stq) {
+                                                                         float* __restrict__ sxy, int* __restrict__ stq,
+                                                                         const int* __restrict__ clip, int* __restrict__ sclip) {
     const int j = blockIdx.x * SEL_THREADS + threadIdx.x;
     if (j >= n_new) return;
     const int q = new_list[j];
@@ -108,6 +130,7 @@ __global__ __launch_bounds__(SEL_THREADS) void stream_join_gather_kernel(const i
     sxy[2 * j] = ok ? xy[2 * q] : 0.f;
     sxy[2 * j + 1] = ok ? xy[2 * q + 1] : 0.f;
     stq[j] = ok ? tq[q] : 0;
+    if (clip != nullptr) sclip[j] = ok ? clip[q] : 0;         // (several streams: the stream of the query, its win_clip)
 }
 
 // one block per joining query: feat[q] = the features its point sample returned
@@ -150,24 +173,58 @@ __global__ __launch_bounds__(SEL_THREADS) void stream_emit_kernel(unsigned* __re
     emit_row(vis + (size_t)r * n, out_vis + (size_t)i * n, n, vec_vis != 0, t, nt);
 }
 
+// the same for the columns cols[0..m) of the state: thread j of a frame's blocks moves column cols[j] -- two words of trajs (as one
+// 8-byte piece where both buffers allow it) and one of vis.  A column outside [0, n) is not touched; its outputs get the NaN.
+__global__ __launch_bounds__(SEL_THREADS) void stream_emit_cols_kernel(unsigned* __restrict__ trajs, unsigned* __restrict__ vis, int L,
+                                                                       int n, int f0, int nf, const int* __restrict__ cols, int m,
+                                                                       unsigned* __restrict__ out_trajs, unsigned* __restrict__ out_vis,
+                                                                       int vec) {
+    const int i = blockIdx.y, j = blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (i >= nf || j >= m) return;
+    const int c = cols[j];
+    const size_t o = (size_t)i * m + j;
+    if ((unsigned)c >= (unsigned)n) {
+        out_trajs[2 * o] = out_trajs[2 * o + 1] = out_vis[o] = STREAM_NAN;
+        return;
+    }
+    const size_t e = (size_t)stream_row(f0 + i, L) * n + c;
+    if (vec) {
+        uint2* s2 = reinterpret_cast<uint2*>(trajs);
+        reinterpret_cast<uint2*>(out_trajs)[o] = s2[e];
+        s2[e] = make_uint2(STREAM_NAN, STREAM_NAN);
+    } else {
+        out_trajs[2 * o] = trajs[2 * e];
+        out_trajs[2 * o + 1] = trajs[2 * e + 1];
+        trajs[2 * e] = trajs[2 * e + 1] = STREAM_NAN;
+    }
+    out_vis[o] = vis[e];
+    vis[e] = STREAM_NAN;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
 int launch_stream_select(int T, int final_, int n, const int* tq, const float* xy, const int* cur, int* status, float* trajs, int L,
-                         int* active, int* new_list, int* counts, hipStream_t st) {
+                         int* active, int* new_list, int* counts, hipStream_t st, const StreamClips* clips) {
     SelectArgs a;
     a.tq = tq; a.xy = xy; a.cur = cur; a.status = status; a.trajs = trajs; a.active = active; a.new_list = new_list; a.counts = counts;
     a.T = T; a.final_ = final_ != 0; a.n = n; a.L = L;
-    hipLaunchKernelGGL(stream_select_kernel, dim3(1), dim3(SEL_THREADS), 0, st, a);
+    a.clip = a.clip_frames = a.clip_final = nullptr; a.V = 0;
+    if (clips != nullptr) {
+        a.clip = clips->clip; a.clip_frames = clips->frames; a.clip_final = clips->final_; a.V = clips->V;
+        hipLaunchKernelGGL(stream_select_kernel<true>, dim3(1), dim3(SEL_THREADS), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(stream_select_kernel<false>, dim3(1), dim3(SEL_THREADS), 0, st, a);
+    }
     PIPS_CHECK_LAUNCH("stream_select");
     return PIPS_OK;
 }
 
 int launch_stream_join_gather(const int* new_list, int n_new, int n, const float* xy, const int* tq, float* sxy, int* stq,
-                              hipStream_t st) {
+                              hipStream_t st, const int* clip, int* sclip) {
     hipLaunchKernelGGL(stream_join_gather_kernel, dim3((n_new + SEL_THREADS - 1) / SEL_THREADS), dim3(SEL_THREADS), 0, st, new_list,
-                       n_new, n, xy, tq, sxy, stq);
+                       n_new, n, xy, tq, sxy, stq, clip, sclip);
     PIPS_CHECK_LAUNCH("stream_join_gather");
     return PIPS_OK;
 }
@@ -189,6 +246,16 @@ int launch_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, f
                        reinterpret_cast<unsigned*>(vis), L, n, f0, m, reinterpret_cast<unsigned*>(out_trajs),
                        reinterpret_cast<unsigned*>(out_vis), vec_trajs, vec_vis);
     PIPS_CHECK_LAUNCH("stream_emit");
+    return PIPS_OK;
+}
+
+int launch_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1, const int* cols, int m, float* out_trajs,
+                            float* out_vis, hipStream_t st) {
+    const int vec = ((reinterpret_cast<uintptr_t>(trajs) | reinterpret_cast<uintptr_t>(out_trajs)) & 7u) == 0;
+    hipLaunchKernelGGL(stream_emit_cols_kernel, dim3((m + SEL_THREADS - 1) / SEL_THREADS, f1 - f0), dim3(SEL_THREADS), 0, st,
+                       reinterpret_cast<unsigned*>(trajs), reinterpret_cast<unsigned*>(vis), L, n, f0, f1 - f0, cols, m,
+                       reinterpret_cast<unsigned*>(out_trajs), reinterpret_cast<unsigned*>(out_vis), vec);
+    PIPS_CHECK_LAUNCH("stream_emit_cols");
     return PIPS_OK;
 }
 

@@ -17,8 +17,9 @@ constexpr int C = PIPS_C;
 // in the reference's order (samp.py:59-65).  128 threads = 128 channels of one point.
 // The map buffer holds R frame slots per clip; T_ logical frames: window start f reads slot
 // clamp(f, 0, T_-1) mod R (ring_slot).  A linear cache is R = T_.
-// ct.win_clip != null (several videos on one flat linear cache, B = 1, T_ = all frames): particle pn belongs to video
-// v = ct.win_clip[pn] and its window start is a frame of that video -- flat frame ct.first[v] + clamp(f, 0, ct.frames[v]-1).
+// ct.win_clip != null (several videos on one flat cache, B = 1, T_ = all its frame slots): particle pn belongs to video
+// v = ct.win_clip[pn] and its window start is a frame of that video -- flat slot ct.first[v] + clamp(f, 0, ct.frames[v]-1) mod ct.R
+// (a linear cache never wraps: ct.R = T_).
 __global__ __launch_bounds__(128) void point_sample_kernel(const float* __restrict__ level0, int S_, int T_,
                                                            int H, int W, const float* __restrict__ xy,
                                                            int xy_stride, int N,
@@ -468,12 +469,13 @@ __global__ __launch_bounds__(256) void pyramid_append_kernel(const float* __rest
 }
 
 int launch_pyramid_append(const float* src, const size_t* src_off, int k, float* dst, const size_t* dst_off, void* dst_mirror,
-                          const int* pf8, int R, int T0, hipStream_t st) {
+                          const int* pf8, int R, int T0, hipStream_t st, int src_first, int dst_first) {
     AppendTable t;
     size_t n = 0;
     for (int l = 0; l < PIPS_LEVELS; ++l) {
-        t.src_off[l] = src_off[l];
-        t.dst_off[l] = dst_off[l];
+        // the k frames start at frame src_first of the source, the ring at flat slot dst_first of the destination
+        t.src_off[l] = src_off[l] + (size_t)src_first * pf8[l] * 8;
+        t.dst_off[l] = dst_off[l] + (size_t)dst_first * pf8[l] * 8;
         t.pf8[l] = (unsigned)pf8[l];
         t.first[l] = (unsigned)n;
         n += (size_t)k * pf8[l];

@@ -15,6 +15,9 @@
 * ``track_chained_batch`` / ``track_queries_batch`` -- the same two drivers over a LIST of videos (equal frame size, any
   lengths) in one set of hop launches: the videos share one flat cache (``Pips.encode_videos``), every particle carries the
   index of its video (``Pips.track``'s ``win_clip``), and each video gets what its single-video driver returns, bit for bit.
+* ``MultiStreamTracker`` / ``track_streams`` -- ``StreamTracker`` for a LIST of streams (equal frame size; own lengths, chunking,
+  queries and ends) on one cache of rings (``Pips.ring_cache_videos``) and one state: a round hops the ready queries of every
+  stream together, and each stream gets what its own ``StreamTracker`` returns, bit for bit.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -647,3 +650,325 @@ def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, e
     if not return_hops:
         return trajs, vis
     return trajs, vis, st.hops
+
+
+# ---------------------------------------------------------------------------------------------- several streams at once
+_NO_LOW = 2 ** 31 - 1                                         # the library's "no pending query" (INT_MAX)
+
+
+class _MultiTorchRounds(_Rounds):
+    """``MultiStreamTracker(rounds="torch")``: ``_TorchRounds`` over the queries of V streams in one state.  ``clip`` (n) is the
+    stream of each query; a query is ready, or finished, by the frames and the end of its OWN stream (``cache.clip_frames`` /
+    ``final``), and the hop is ``_hop(..., clip=)`` on the cache of rings."""
+
+    def _engine(self, cur0, feat=None):
+        t = self.t
+        self.eng = _TorchEngine(t.model, t.cache, self.trajs, self.vis, 0, cur0, None, self.clip, None, t.iters, False)
+        self.eng.feat = feat
+
+    cur = property(lambda self: self.eng.cur)
+
+    def start(self, dev):
+        super().start(dev)
+        t = self.t
+        self.clip = t.clip_host.to(dev)
+        self.joined, self.done = (torch.zeros(t.N, dtype=torch.bool, device=dev) for _ in range(2))
+        self.final = torch.zeros(t.V, dtype=torch.bool, device=dev)
+        self._engine(self.tq)
+
+    def grow(self, t, xy, m, v):
+        super().grow(t, xy, m)
+        self.clip = _longer(self.clip, torch.full((m,), v))
+        self.joined, self.done = _longer(self.joined, torch.zeros(m)), _longer(self.done, torch.zeros(m))
+        feat = self.eng.feat
+        self._engine(_longer(self.eng.cur, t), None if feat is None else _longer(feat, torch.zeros(m, feat.shape[1])))
+
+    def end(self, v):
+        self.final[v] = True
+
+    def lows(self):
+        """per stream, the lowest window start of its unfinished queries (None: it has none); one host read"""
+        live = ~self.done
+        low = torch.full((self.t.V,), _NO_LOW, dtype=torch.int64, device=self.done.device)
+        low = low.scatter_reduce(0, self.clip[live], self.eng.cur[live], "amin")
+        return [None if x == _NO_LOW else x for x in low.tolist()]
+
+    def run(self):
+        t, eng, L = self.t, self.eng, self.trajs.shape[0]
+        while True:
+            T, fin = t.cache.clip_frames.to(torch.int64)[self.clip], self.final[self.clip]      # of each query's own stream
+            ready = ~self.done & torch.where(fin, eng.cur < T, eng.cur + t.S <= T)
+            active = torch.nonzero(ready).squeeze(1)
+            if active.numel() == 0:
+                return
+            new = active[~self.joined[active]]
+            if new.numel() > 0:
+                self.trajs[self.tq[new] % L, new] = self.xy[new]
+                ff = t.model.track(t.cache, self.xy[new].unsqueeze(0), iters=0, return_feat=True,
+                                   win_start=self.tq[new].to(torch.int32).unsqueeze(0),
+                                   win_clip=self.clip[new].to(torch.int32).unsqueeze(0))[3]
+                if eng.feat is None:
+                    eng.feat = ff.new_zeros(self.tq.shape[0], ff.shape[-1])
+                eng.feat[new] = ff[0]
+                self.joined[new] = True
+            c, si = eng.window(active)
+            self.done[active] = fin[active] & (c >= T[active])
+            yield active, si
+
+    def emit(self, f0, f1, cols):
+        rows = (torch.arange(f0, f1, device=self.trajs.device) % self.trajs.shape[0]).unsqueeze(1)
+        cols = cols.to(torch.int64).unsqueeze(0)
+        out = (self.trajs[rows, cols], self.vis[rows, cols])
+        self.trajs[rows, cols] = float("nan")
+        self.vis[rows, cols] = float("nan")
+        return out
+
+
+class _MultiLibraryRounds(_Rounds):
+    """``MultiStreamTracker(rounds="library")``: the arrays of ``pips_stream_round_clips`` (include/pips_hip.h) -- those of
+    ``_LibraryRounds`` plus ``clip`` (n), ``final`` (V) int32 and ``counts`` (4 + V), whose tail is kept on the host as ``low``."""
+
+    def _lists(self):
+        n, dev = self.tq.shape[0], self.tq.device
+        self.active, self.new_list = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        self.steps = torch.empty(n, dtype=torch.int32, device=dev) if self.t.hops is not None else None
+
+    def start(self, dev):
+        super().start(dev)
+        t, i32 = self.t, torch.int32
+        self.tq, self.xy = self.tq.to(i32), self.xy.contiguous()
+        self.cur, self.clip = self.tq.clone(), t.clip_host.to(dev, i32)
+        self.status = torch.zeros(t.N, dtype=i32, device=dev)
+        self.counts, self.final = torch.zeros(4 + t.V, dtype=i32, device=dev), torch.zeros(t.V, dtype=i32, device=dev)
+        self.feat = torch.zeros(t.N, 128, dtype=torch.float32, device=dev)
+        self._lists()
+        self.low = [None] * t.V
+        for v, tq in zip(t.clip_host.tolist(), t.tq_host.tolist()):
+            self.low[v] = tq if self.low[v] is None else min(self.low[v], tq)
+
+    def grow(self, t, xy, m, v):
+        super().grow(t, xy, m)
+        self.cur, self.status = _longer(self.cur, t), _longer(self.status, torch.zeros(m))
+        self.clip = _longer(self.clip, torch.full((m,), v))
+        self.feat = _longer(self.feat, torch.zeros(m, self.feat.shape[1]))
+        self._lists()
+        self.low[v] = int(t.min()) if self.low[v] is None else min(self.low[v], int(t.min()))
+
+    def end(self, v):
+        self.final[v:v + 1].fill_(1)
+
+    def lows(self):
+        return list(self.low)
+
+    def run(self):
+        # select, then one pips_stream_round_clips call per round while any query of any stream is ready (one host read per round)
+        t = self.t
+        if self.tq.shape[0] == 0:
+            return
+        cache = t.cache
+        ops.stream_select_clips(self.tq, self.xy, self.cur, self.status, self.clip, cache.clip_frames, self.final, self.trajs,
+                                self.active, self.new_list, self.counts)
+        counts = self.counts.tolist()
+        while counts[0] > 0:
+            n_act, n_new = counts[:2]
+            act = self.active[:n_act].clone() if self.steps is not None else None      # the round rewrites the list
+            t.model.stream_round(cache, self.final, n_act, n_new, self.tq, self.xy, self.cur, self.status, self.feat, self.trajs,
+                                 self.vis, self.active, self.new_list, self.counts, self.steps, iters=t.iters, clip=self.clip)
+            yield act, None if act is None else self.steps[:n_act]
+            counts = self.counts.tolist()
+        self.low = [None if x == _NO_LOW else x for x in counts[4:]]
+
+    def emit(self, f0, f1, cols):
+        return ops.stream_emit_cols(self.trajs, self.vis, f0, f1, cols)
+
+
+_MULTI_ROUNDS = {"torch": _MultiTorchRounds, "library": _MultiLibraryRounds}
+
+
+class MultiStreamTracker:
+    """``StreamTracker`` for V videos of one frame size at once: each stream has its own length, its own chunking, its own queries
+    and its own end, and gets what a ``StreamTracker`` given that stream alone (same chunks, same ``slots``) returns -- bit for bit,
+    hop lists included, while the mixer's GEMMs take the same route at both row counts (the contract of ``track_*_batch``).
+
+    The streams share ONE cache of V rings of ``slots`` slots (``Pips.ring_cache_videos``) and ONE state, whose columns are the
+    queries of stream 0, then of stream 1, ... (and, behind them, the ones ``add_queries`` brought), so a round is one hop over
+    the ready queries of EVERY stream: V cameras fill the mixer's rows together instead of running V rounds of a few rows each.
+      push(chunks)          a list with one ``(1,k_v,3,H,W)`` tensor or ``None`` per stream (the ``k_v`` may differ) -> per stream
+                            ``(f0, trajs (1,m,N_v,2), vis (1,m,N_v))``, the frames of that stream that became final
+      finish(v=None)        ends stream ``v`` (-> its tuple) or every stream still running (-> the list; None for one ended before)
+      add_queries(v, q)     ``StreamTracker.add_queries`` for stream ``v``, against that stream's ``emitted[v]``
+    Each stream's chunk is split by its own room, ``min(slots, low_v + slots - T_v)``; after each wave of appends the rounds run
+    until no query of any stream is ready, and frames ``[emitted_v, min(low_v, T_v))`` are handed out per stream.
+    ``rounds="torch"`` hops with ``_hop(..., clip=)``; ``rounds="library"`` makes one ``pips_stream_round_clips`` call per round.
+    ``joint_encode=True`` sends the frames one wave appends across all streams through shared encoder passes
+    (``Pips.encode_streams(joint=True)``): fuller passes, and maps that differ from the per-stream ones by the encoder's
+    tile-order noise instead of matching bit for bit."""
+
+    S = 8
+
+    def __init__(self, model, queries_list, iters=6, slots=24, record_hops=False, rounds="torch", joint_encode=False):
+        if rounds not in ROUNDS:
+            raise ValueError(f"rounds must be one of {ROUNDS}, not {rounds!r}")
+        assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
+        if int(slots) < self.S + 1:
+            raise ValueError(f"slots must be at least {self.S + 1} (one window and a new frame), not {slots}")
+        queries_list = list(queries_list)
+        if not queries_list:
+            raise ValueError("MultiStreamTracker needs at least one stream")
+        self.model, self.iters, self.slots, self.rounds, self.joint_encode = model, iters, int(slots), rounds, bool(joint_encode)
+        self.V = len(queries_list)
+        tqs = [_query_frames(q) for q in queries_list]
+        self.tq_host = torch.cat(tqs)
+        self.xy_in = torch.cat([q[0, :, 1:3] for q in queries_list])
+        self.clip_host = torch.cat([torch.full((t.numel(),), v, dtype=torch.int64) for v, t in enumerate(tqs)])
+        self.N = self.tq_host.numel()
+        self.cache = None
+        self.finished, self.emitted = [False] * self.V, [0] * self.V                # per stream; frames [0, emitted[v]) returned
+        self.hops = [[] for _ in range(self.N)] if record_hops else None          # per column of the shared state
+        self.state = _MULTI_ROUNDS[rounds](self, "torch")
+
+    trajs, vis, cur = (property(lambda self, k=k: getattr(self.state, k)) for k in ("trajs", "vis", "cur"))
+
+    def columns(self, v):
+        """the columns of the shared state that hold stream ``v``'s queries, in the order of its outputs (host int64)"""
+        return torch.nonzero(self.clip_host == v).squeeze(1)
+
+    def stream_hops(self, v):
+        """the frame steps of each query of stream ``v`` (``record_hops=True``), as ``StreamTracker.hops``"""
+        return [self.hops[c] for c in self.columns(v).tolist()]
+
+    def frames(self, v):
+        return 0 if self.cache is None else self.cache.clip_lengths[v]
+
+    def _stream(self, v):
+        if not (isinstance(v, int) and 0 <= v < self.V):
+            raise ValueError(f"stream must be an int in [0, {self.V - 1}], not {v!r}")
+        return v
+
+    def add_queries(self, v, queries):
+        """Further queries (1,m,3) for stream ``v`` while it runs -> the positions (m,) they take among stream ``v``'s output
+        columns.  ValueError, with the tracker left as it was, for a frame of that stream returned already and after its end."""
+        v = self._stream(v)
+        if self.finished[v]:
+            raise ValueError(f"add_queries() after stream {v} was finished")
+        t = _query_frames(queries)
+        if bool((t < self.emitted[v]).any()):
+            raise ValueError(f"a query frame lies before frame {self.emitted[v]} of stream {v}: those frames were returned already")
+        m, n_v = t.numel(), int((self.clip_host == v).sum())
+        xy = queries[0, :, 1:3]
+        self.tq_host = torch.cat([self.tq_host, t])
+        self.xy_in = torch.cat([self.xy_in, xy.to(self.xy_in.device, self.xy_in.dtype)])
+        self.clip_host = torch.cat([self.clip_host, torch.full((m,), v, dtype=torch.int64)])
+        self.N += m
+        if self.hops is not None:
+            self.hops += [[] for _ in range(m)]
+        if self.cache is not None and m > 0:
+            self.state.grow(t, xy, m, v)
+        return torch.arange(n_v, n_v + m)
+
+    @torch.no_grad()
+    def push(self, chunks):
+        chunks = list(chunks)
+        if len(chunks) != self.V:
+            raise ValueError(f"push() takes one chunk (or None) per stream: {self.V}, not {len(chunks)}")
+        size = getattr(self, "size", None)
+        for v, c in enumerate(chunks):                                             # every check ahead of the first append
+            if c is None:
+                continue
+            if self.finished[v]:
+                raise ValueError(f"push() to stream {v} after it was finished")
+            if c.dim() != 5 or c.shape[0] != 1 or c.shape[2] != 3:
+                raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(c.shape)}")
+            size = tuple(c.shape[3:]) if size is None else size
+            if tuple(c.shape[3:]) != size:
+                raise ValueError(f"frames of {tuple(c.shape[3:])} pushed to streams of {size}")
+        if self.cache is None and size is not None:
+            self.size = size
+            self.cache = self.model.ring_cache_videos(*size, self.slots, self.V)
+            self.state.start(self.cache.device)
+        f0, outs = list(self.emitted), [[] for _ in range(self.V)]
+        left = [0 if c is None else c.shape[1] for c in chunks]
+        while any(left):
+            lows, wave = self.state.lows(), []
+            for v, c in enumerate(chunks):
+                if left[v] == 0:
+                    continue
+                # the slot of frame T + j holds frame T + j - slots until then: no pending window of this stream may still read it
+                room = self.slots if lows[v] is None else min(self.slots, lows[v] + self.slots - self.frames(v))
+                n, i = min(left[v], room), c.shape[1] - left[v]
+                wave.append((v, c[:, i:i + n]))
+                left[v] -= n
+            if self.joint_encode:
+                self.model.encode_streams(self.cache, wave, joint=True)
+            else:
+                for v, c in wave:
+                    self.model.encode(c, into=self.cache, clip=v)
+            self._rounds(outs)
+        return [self._cat(v, f0[v], outs[v]) for v in range(self.V)]
+
+    @torch.no_grad()
+    def finish(self, v=None):
+        which = [u for u in range(self.V) if not self.finished[u]] if v is None else [self._stream(v)]
+        for u in which:                                                             # every check ahead of the first change
+            if self.finished[u]:
+                raise ValueError(f"finish() of stream {u} called twice")
+            T = self.frames(u)
+            if bool((self.tq_host[self.clip_host == u] > T - 1).any()):
+                raise ValueError(f"a query frame lies beyond the last frame of stream {u} ({T - 1})")
+        f0, outs = list(self.emitted), [[] for _ in range(self.V)]
+        for u in which:
+            self.finished[u] = True
+            if self.cache is not None:
+                self.state.end(u)
+        if self.cache is not None and which:
+            self._rounds(outs)
+        res = [self._cat(u, f0[u], outs[u]) if u in which else None for u in range(self.V)]
+        return res if v is None else res[v]
+
+    def _rounds(self, outs):
+        """the state's hop rounds over every stream, their steps recorded -> the rows that became final, appended per stream"""
+        for active, steps in self.state.run():
+            if self.hops is not None:
+                for q, h in zip(active.tolist(), steps.tolist()):
+                    self.hops[q].append(h)
+        lows = self.state.lows()
+        for v in range(self.V):
+            T = self.frames(v)
+            f1 = T if lows[v] is None else min(lows[v], T)
+            if f1 > self.emitted[v]:
+                cols = self.columns(v).to(self.cache.device, torch.int32)
+                outs[v].append(self.state.emit(self.emitted[v], f1, cols))
+                self.emitted[v] = f1
+
+    def _cat(self, v, f0, outs):
+        if not outs:
+            dev = self.cache.device if self.cache is not None else self.xy_in.device
+            n = int((self.clip_host == v).sum())
+            return f0, torch.empty(1, 0, n, 2, device=dev), torch.empty(1, 0, n, device=dev)
+        return f0, torch.cat([o[0] for o in outs]).unsqueeze(0), torch.cat([o[1] for o in outs]).unsqueeze(0)
+
+
+@torch.no_grad()
+def track_streams(model, chunk_lists, queries_list, iters=6, slots=24, return_hops=False, rounds="torch", joint_encode=False):
+    """``MultiStreamTracker`` over V lists of ``(1,k,3,H,W)`` chunks (the lists may differ in length: a stream whose list has run
+    out is finished while the others go on) -> per stream what ``track_stream`` returns: ``(trajs_e (1,T_v,N_v,2), vis_e
+    (1,T_v,N_v))``, with its hop lists behind them under ``return_hops=True``."""
+    chunk_lists = [list(c) for c in chunk_lists]
+    mt = MultiStreamTracker(model, queries_list, iters=iters, slots=slots, record_hops=return_hops, rounds=rounds,
+                            joint_encode=joint_encode)
+    if len(chunk_lists) != mt.V:
+        raise ValueError(f"{len(chunk_lists)} chunk lists for {mt.V} streams")
+    parts = [[] for _ in range(mt.V)]
+    for i in range(max(len(c) for c in chunk_lists) + 1):
+        for v, c in enumerate(chunk_lists):
+            if len(c) == i:                                                        # its last chunk went in with the wave before
+                parts[v].append(mt.finish(v))
+        wave = [c[i] if i < len(c) else None for c in chunk_lists]
+        if any(w is not None for w in wave):
+            for v, p in enumerate(mt.push(wave)):
+                parts[v].append(p)
+    out = []
+    for v in range(mt.V):
+        res = (torch.cat([p[1] for p in parts[v]], dim=1), torch.cat([p[2] for p in parts[v]], dim=1))
+        out.append(res + (mt.stream_hops(v),) if return_hops else res)
+    return out

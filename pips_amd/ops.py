@@ -163,6 +163,30 @@ def mixer_input_build_clips(pyr, T, H8, W8, ffeats, coords, win_start, win_dir, 
     return X
 
 
+def mixer_input_build_rings(pyr, F, R, H8, W8, ffeats, coords, win_start, win_dir, win_clip, clip_first, clip_frames,
+                            bf16_maps=False, S=8):
+    """pips_mixer_input_build_rings on a flat cache of F slots holding V rings of R slots (B = 1): the arguments of
+    ``mixer_input_build_clips``, clip_frames the logical frames appended to each ring so far -> X (N*S, 544)."""
+    ffeats, coords = _f32(ffeats), _f32(coords)
+    M = ffeats.shape[0]
+    X = torch.empty(M, KIN_PAD, dtype=torch.float32, device=ffeats.device)
+    tt = times_table(ffeats.device, S)
+    with torch.cuda.device(ffeats.device):
+        _call("pips_mixer_input_build_rings", _lib.ptr(pyr), 1, int(F), int(R), int(H8), int(W8), _lib.ptr(ffeats), _lib.ptr(coords),
+              _lib.ptr(tt), M // S, _i32(win_start), _i32(win_dir), _i32(win_clip), _i32(clip_first), _i32(clip_frames),
+              0 if clip_frames is None else clip_frames.numel(), FLAG_BF16_MAPS if bf16_maps else 0, int(S), _lib.ptr(X), _stream())
+    return X
+
+
+def pyramid_append_at(src, F_src, src_first, k, dst, F, ring_first, R, T0, H, W, stride):
+    """pips_pyramid_append_at: frames [src_first, src_first + k) of the encoder pyramid ``src`` of F_src frames -> slots ring_first +
+    (T0 + i) % R of the pyramid ``dst`` laid out for F slots, fp32 levels and bf16 mirror."""
+    with torch.cuda.device(dst.device):
+        _call("pips_pyramid_append_at", _lib.ptr(src), int(F_src), int(src_first), int(k), _lib.ptr(dst), int(F), int(ring_first),
+              int(R), int(T0), int(H), int(W), int(stride), _stream())
+    return dst
+
+
 def pyramid_mirror(pyr, F, H, W, stride):
     """(re)write the bf16 mirror of a packed pyramid buffer from its fp32 levels (pips_pyramid_mirror)"""
     with torch.cuda.device(pyr.device):
@@ -379,6 +403,46 @@ def stream_emit(trajs, vis, f0, f1):
     out_v = torch.empty(m, n, dtype=torch.float32, device=trajs.device)
     with torch.cuda.device(trajs.device):
         _call("pips_stream_emit", _chain_f32(trajs), _chain_f32(vis), L, n, int(f0), int(f1), _lib.ptr(out_t), _lib.ptr(out_v), _stream())
+    return out_t, out_v
+
+
+def stream_workspace_bytes_clips(n, iters, V):
+    """pips_stream_workspace_bytes_clips: the workspace of one round over a state of ``n`` queries of V streams (host function)."""
+    return _lib.load().pips_stream_workspace_bytes_clips(int(n), int(iters), int(V))
+
+
+def stream_select_clips(tq, xy, cur, status, clip, clip_frames, clip_final, trajs, active, new_list, counts):
+    """pips_stream_select_clips, in place on a state over V streams (include/pips_hip.h): ``stream_select`` with the stream of each
+    query ``clip`` (n) and the tables ``clip_frames`` / ``clip_final`` (V) int32 in the place of T / final; ``counts`` is (4 + V)."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    with torch.cuda.device(trajs.device):
+        _call("pips_stream_select_clips", n, _i32(tq), _chain_f32(xy), _i32(cur), _i32(status), _i32(clip), _i32(clip_frames),
+              _i32(clip_final), clip_frames.numel(), _chain_f32(trajs), L, _i32(active), _i32(new_list), _i32(counts), _stream())
+
+
+def stream_round_clips(arena, pyr, F, R, H8, W8, times, stride, iters, flags, n_act, n_new, tq, xy, cur, status, clip, feat, trajs, vis,
+                       clip_first, clip_frames, clip_final, active, new_list, counts, steps, workspace):
+    """pips_stream_round_clips: ``stream_round`` on a state over V streams, on the packed pyramid ``pyr`` of F slots holding V rings
+    of R slots.  No host synchronisation."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    with torch.cuda.device(trajs.device):
+        _call("pips_stream_round_clips", _lib.ptr(arena), _lib.ptr(pyr), int(F), int(R), int(H8), int(W8), _lib.ptr(times), int(stride),
+              int(iters), int(flags), n, int(n_act), int(n_new), _i32(tq), _chain_f32(xy), _i32(cur), _i32(status), _i32(clip),
+              _chain_f32(feat), _chain_f32(trajs), _chain_f32(vis), L, _i32(clip_first), _i32(clip_frames), _i32(clip_final),
+              clip_frames.numel(), _i32(active), _i32(new_list), _i32(counts), _i32(steps), _lib.ptr(workspace),
+              workspace.numel() * 4, _stream())
+
+
+def stream_emit_cols(trajs, vis, f0, f1, cols):
+    """pips_stream_emit_cols: frames [f0, f1) of the columns ``cols`` (m) int32 of the row ring trajs (L,n,2) / vis (L,n) -> dense
+    (f1-f0,m,2) and (f1-f0,m); exactly those elements are reset to NaN."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    nf, m = max(int(f1) - int(f0), 0), cols.numel()
+    out_t = torch.empty(nf, m, 2, dtype=torch.float32, device=trajs.device)
+    out_v = torch.empty(nf, m, dtype=torch.float32, device=trajs.device)
+    with torch.cuda.device(trajs.device):
+        _call("pips_stream_emit_cols", _chain_f32(trajs), _chain_f32(vis), L, n, int(f0), int(f1), _i32(cols), m, _lib.ptr(out_t),
+              _lib.ptr(out_v), _stream())
     return out_t, out_v
 
 

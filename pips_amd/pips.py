@@ -46,13 +46,18 @@ class FeatureCache:
 
     A cache of several videos (``Pips.encode_videos``) is linear with ``B = 1``: its ``T`` frames are the videos' frames one
     after the other, ``clip_lengths`` (host list) / ``clip_frames`` (device int32) the frames of each video and ``clip_first``
-    (device int32) its first flat frame -- the clip table of ``pips_track_clips``.  ``None`` on every other cache."""
+    (device int32) its first flat frame -- the clip table of ``pips_track_clips``.  ``None`` on every other cache.
+
+    A cache of several STREAMED videos (``Pips.ring_cache_videos``) holds ``rings`` rings of ``slots`` slots each (``B = 1``,
+    ``T = rings * slots`` flat slots; ``rings`` is ``None`` on every other cache): ``clip_first[v] = v * slots``, and
+    ``clip_lengths[v]`` / ``clip_frames[v]`` count the frames appended to stream ``v`` so far (``Pips.encode(..., into=cache,
+    clip=v)``) -- the clip table of ``pips_track_rings``."""
 
     def __init__(self, pyr, B, T, H, W, stride, bf16_maps=False, slots=None):
         self.pyr, self.B, self.T, self.H, self.W, self.stride = pyr, B, T, H, W, stride
         self.bf16_maps = bf16_maps          # the buffer's bf16 mirror is valid (written by the bf16 encoder): PIPS_FLAG_BF16_MAPS
         self.slots = T if slots is None else int(slots)
-        self.clip_first = self.clip_frames = self.clip_lengths = None
+        self.clip_first = self.clip_frames = self.clip_lengths = self.rings = None
 
     @property
     def map_size(self):
@@ -291,6 +296,22 @@ class Pips(nn.Module):
         pyr = torch.zeros(lib.pips_pyramid_floats(int(slots), H, W, st), dtype=torch.float32, device=dev)
         return FeatureCache(pyr, 1, 0, H, W, st, slots=int(slots))
 
+    @torch.no_grad()
+    def ring_cache_videos(self, H: int, W: int, slots: int, V: int, device=None) -> FeatureCache:
+        """An empty ``FeatureCache`` of ``V`` rings of ``slots`` frame slots each, for ``V`` streamed videos of ``H x W`` frames, on
+        one flat buffer (B = 1).  Fill stream ``v`` with ``encode(rgbs, into=cache, clip=v)``; ``track(..., win_clip=)`` and
+        ``stream_round(..., clip=)`` read it through its clip table."""
+        V = int(V)
+        if V < 1:
+            raise ValueError("a cache of rings needs at least one video")
+        cache = self.ring_cache(H, W, int(slots) * V, device)
+        dev = cache.device
+        cache.slots, cache.rings, cache.T = int(slots), V, int(slots) * V
+        cache.clip_lengths = [0] * V
+        cache.clip_frames = torch.zeros(V, dtype=torch.int32, device=dev)
+        cache.clip_first = (torch.arange(V, dtype=torch.int32) * int(slots)).to(dev)
+        return cache
+
     def _encoder_modes(self):                            # (bf16 conv operands, split-bf16 convs) under the current flags
         fl = self._flags()
         return bool(fl & ops.FLAG_BF16_ENCODER), bool(fl & ops.FLAG_SPLIT_BF16)
@@ -324,7 +345,7 @@ class Pips(nn.Module):
         return FeatureCache(pyr, B, T, H, W, st, bf16_maps=eb and not sp)
 
     @torch.no_grad()
-    def encode(self, rgbs, frames_per_pass: int = 16, into: FeatureCache = None) -> FeatureCache:
+    def encode(self, rgbs, frames_per_pass: int = 16, into: FeatureCache = None, clip: int = None) -> FeatureCache:
         """BasicEncoder + pyramid of every frame of ``rgbs (B,T,3,H,W)`` (0..255), once.
         Replaces the per-chunk / per-hop encoder re-runs of test_on_davis.py:116-118 and
         chain_demo.py:54.  Frames are encoded ``frames_per_pass`` at a time to bound the
@@ -333,9 +354,15 @@ class Pips(nn.Module):
         ``into``: a ring cache (``ring_cache``) the frames are appended to instead, B = 1: each pass of at most
         ``frames_per_pass`` (and ``into.slots``) frames is copied into the next slots, wrapping, with its bf16 mirror
         (``pips_pyramid_append``), and ``into.T`` grows by the number of frames.  ``rgbs`` may then be a host tensor, uint8
-        or float.  Returns ``into``."""
+        or float.  Returns ``into``.  ``clip``: on a cache of several rings (``ring_cache_videos``), the stream the frames belong
+        to -- they go through the passes an append to that stream's own ring would run (the same bytes) and into its ring
+        (``pips_pyramid_append_at``)."""
         if into is not None:
-            return self._append(rgbs, frames_per_pass, into)
+            if (clip is None) != (into.rings is None):
+                raise ValueError("clip= goes with a cache of several rings (Pips.ring_cache_videos), and such a cache needs it")
+            return self._append(rgbs, frames_per_pass, into) if clip is None else self.encode_streams(into, [(clip, rgbs)], frames_per_pass)
+        if clip is not None:
+            raise ValueError("clip= needs into=, a cache of several rings (Pips.ring_cache_videos)")
         if not rgbs.is_cuda:
             raise _lib.PipsHipError("pips_amd.Pips needs CUDA/HIP tensors; there is no CPU fallback")
         B, T, C3, H, W = rgbs.shape
@@ -392,6 +419,57 @@ class Pips(nn.Module):
         return cache
 
     @torch.no_grad()
+    def encode_streams(self, cache: FeatureCache, chunks, frames_per_pass: int = 16, joint: bool = False) -> FeatureCache:
+        """Append to several streams of a cache of rings (``ring_cache_videos``): ``chunks`` is a list of ``(v, rgbs (1,k,3,H,W))``,
+        ``k <= cache.slots``, at most one entry per stream.  By default every entry runs the encoder passes an append to its own
+        ring would run, so its slots hold the bytes of a single ring's.  ``joint=True``: the frames of all entries go through
+        SHARED passes of at most ``frames_per_pass`` frames (one ``pips_pyramid_append_at`` call per stream and pass): fewer,
+        fuller passes, whose maps differ from the per-stream ones by the encoder's tile-order noise."""
+        if cache.rings is None:
+            raise ValueError("encode_streams needs a cache of several rings (Pips.ring_cache_videos)")
+        H, W, st, R, F = cache.H, cache.W, cache.stride, cache.slots, cache.T
+        seen = set()
+        for v, rgbs in chunks:
+            if not 0 <= int(v) < cache.rings or int(v) in seen:
+                raise ValueError(f"stream {v}: a cache of {cache.rings} rings takes one chunk per stream, 0..{cache.rings - 1}")
+            seen.add(int(v))
+            if rgbs.dim() != 5 or rgbs.shape[0] != 1 or rgbs.shape[2] != 3 or tuple(rgbs.shape[3:]) != (H, W) or int(self.stride) != st:
+                raise ValueError(f"frames {tuple(rgbs.shape)} do not fit a ring cache of 1 x {H} x {W}, stride {st}")
+            if joint and rgbs.shape[1] > R:
+                raise ValueError(f"{rgbs.shape[1]} frames of stream {v} in one joint append to rings of {R} slots")
+        dev = cache.device
+        with torch.cuda.device(dev):
+            if joint:
+                # (frame, stream) of every frame of the wave; a pass holds runs of consecutive frames of one or more streams
+                owner = [int(v) for v, rgbs in chunks for _ in range(rgbs.shape[1])]
+                frames = torch.cat([rgbs[0] for _, rgbs in chunks]) if chunks else None
+                groups = [] if frames is None or frames.shape[0] == 0 else self._passes(frames, frames_per_pass, dev)
+            else:
+                owner = None
+                groups = ((v, f0, f1, pyr) for v, rgbs in chunks
+                          for f0, f1, pyr in self._passes(rgbs[0], min(int(frames_per_pass), R), dev))
+            for g in groups:
+                if joint:
+                    f0, f1, pyr = g
+                    runs, i = [], f0
+                    while i < f1:
+                        j = i
+                        while j < f1 and owner[j] == owner[i]:
+                            j += 1
+                        runs.append((owner[i], i - f0, j - i))
+                        i = j
+                else:
+                    v, f0, f1, pyr = g
+                    runs = [(int(v), 0, f1 - f0)]
+                for v, first, k in runs:
+                    ops.pyramid_append_at(pyr, f1 - f0, first, k, cache.pyr, F, v * R, R, cache.clip_lengths[v], H, W, st)
+                    cache.clip_lengths[v] += k
+                    cache.clip_frames[v:v + 1].fill_(cache.clip_lengths[v])        # (stream-ordered, no host copy)
+            eb, sp = self._encoder_modes()
+        cache.bf16_maps = eb and not sp
+        return cache
+
+    @torch.no_grad()
     def track(self, cache: FeatureCache, xys, coords_init=None, feat_init=None, iters=3, win_start=None,
               return_feat=False, win_dir=None, win_clip=None):
         """The update loop of ``forward`` (nets/pips.py:450-563) on cached maps.  ``win_start``
@@ -403,7 +481,9 @@ class Pips(nn.Module):
         frame ``f`` is read from slot ``f % cache.slots``: every frame a window reads must still be held.
         ``win_clip`` ``(1,N)`` int, on a cache of several videos (``encode_videos``): the video of each particle.
         ``win_start`` then counts frames of that video, and the repeats past its last frame and before its frame 0 stay
-        inside it; each particle gets what ``track`` on ``encode`` of its own video gives.
+        inside it; each particle gets what ``track`` on ``encode`` of its own video gives.  On a cache of several rings
+        (``ring_cache_videos``) ``win_clip`` is the stream of each particle and required (``pips_track_rings``): frame ``f`` of
+        stream ``v`` is read from slot ``f % cache.slots`` of its ring.
         Returns the same tuple as ``forward`` (losses = None)."""
         lib = _lib.load()
         B, N, D = xys.shape
@@ -426,6 +506,8 @@ class Pips(nn.Module):
             if cache.clip_first is None:
                 raise ValueError("win_clip needs a cache of several videos (Pips.encode_videos)")
             assert tuple(wc_i.shape) == (B, N) and B == 1
+        elif cache.rings is not None:
+            raise ValueError("a cache of several rings (Pips.ring_cache_videos) needs win_clip")
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
             fl = self._track_flags(cache)
@@ -435,12 +517,13 @@ class Pips(nn.Module):
             ffeat = torch.empty(B, N, self.latent_dim, dtype=f32, device=dev)
             # the superset entry point: without win_clip a NULL table (the one-video ring form); no score-map block
             first, frames, V = (None, None, 0) if wc_i is None else (cache.clip_first, cache.clip_frames, len(cache.clip_lengths))
-            rc = lib.pips_track_clips(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
+            entry = "pips_track_clips" if cache.rings is None else "pips_track_rings"      # (T, R) or (F, slots per ring)
+            rc = getattr(lib, entry)(_lib.ptr(arena), _lib.ptr(cache.pyr), B, cache.T, cache.slots, H8, W8, _lib.ptr(xys_c),
                                       _lib.ptr(ci), _lib.ptr(fi), _lib.ptr(ws_i), _lib.ptr(wd_i), _lib.ptr(wc_i), _lib.ptr(first),
                                       _lib.ptr(frames), V, _lib.ptr(times), N, int(cache.stride), int(iters), fl, S, _lib.ptr(ws),
                                       ws.numel() * 4, _lib.ptr(trajs), _lib.ptr(vis_e), _lib.ptr(ffeat), None, None, None, 0,
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "pips_track_clips")
+            _lib.check(rc, entry)
         preds = [trajs[i + 1] for i in range(iters)]
         preds2 = [trajs[0], trajs[0]] + preds + [trajs[iters], trajs[iters]]
         if return_feat:
@@ -478,19 +561,30 @@ class Pips(nn.Module):
 
     @torch.no_grad()
     def stream_round(self, cache: FeatureCache, final, n_act, n_new, tq, xy, cur, status, feat, trajs, vis, active, new_list, counts,
-                     steps=None, iters=6):
+                     steps=None, iters=6, clip=None):
         """One round of a streamed video (``drivers.StreamTracker(rounds="library")``) in one library call (``pips_stream_round``):
         the queries ``new_list[:n_new]`` join with their first-window features, the ready queries ``active[:n_act]`` hop
         (``chain_hop`` on the ring cache, base 0) and the next round is selected -- in place on the caller's device state
         (include/pips_hip.h: tq / cur / status / active / new_list int32, xy (n,2), feat (n,128), trajs (L,n,2), vis (L,n));
         ``counts`` (4) int32 then holds the next round's numbers and the lowest pending window start (the caller reads it back),
-        ``steps`` the steps of this round's hop.  S = 8 and B = 1 only."""
+        ``steps`` the steps of this round's hop.  S = 8 and B = 1 only.
+        ``clip`` (n) int32, on a cache of several rings (``ring_cache_videos``): the stream of each query, one state for all
+        streams (``pips_stream_round_clips``).  ``final`` is then a device int32 tensor (V), non-zero where a stream has ended, and
+        ``counts`` is (4 + V): the lowest pending window start of each stream behind the four."""
         assert self.S == 8 and cache.B == 1, "the reference chains 8-frame windows of one video (chain_demo.py:24,63-77)"
+        if (clip is None) != (cache.rings is None):
+            raise ValueError("clip= goes with a cache of several rings (Pips.ring_cache_videos), and such a cache needs it")
         dev = cache.pyr.device
         H8, W8 = cache.map_size
         n = trajs.shape[1]
         with torch.cuda.device(dev):
             arena, times = self._aux(dev)
+            if clip is not None:
+                ws = self._grown_ws("stream", dev, ops.stream_workspace_bytes_clips(n, iters, cache.rings))
+                ops.stream_round_clips(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache),
+                                       n_act, n_new, tq, xy, cur, status, clip, feat, trajs, vis, cache.clip_first, cache.clip_frames,
+                                       final, active, new_list, counts, steps, ws)
+                return
             ws = self._grown_ws("stream", dev, ops.stream_workspace_bytes(n, iters))
             ops.stream_round(arena, cache.pyr, cache.T, cache.slots, H8, W8, times, cache.stride, iters, self._track_flags(cache), final,
                              n_act, n_new, tq, xy, cur, status, feat, trajs, vis, active, new_list, counts, steps, ws)
