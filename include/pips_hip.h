@@ -586,6 +586,20 @@ int    pips_gemm_f32(const float* A, int lda, const float* W, const float* bias,
 int    pips_conv_nhwc_f32(const float* in, int F, int H, int W, int Cin,
                           const float* wgt, const float* bias, int Cout, int ksize, int cstride, int pad,
                           float* out, float* stats, int* tiles_m_host, void* stream);
+/* pips_conv_nhwc_f32 on a named kernel (exposed for unit tests): PIPS_CONV_ROUTE_AUTO = the kernel the shape selects (what
+ * pips_conv_nhwc_f32 runs), PIPS_CONV_ROUTE_IGEMM = igemm_f32_kernel, PIPS_CONV_ROUTE_E = the 64 x 64 LDS-DMA body (1x1 or 3x3,
+ * stride 1 or 2, pad = ksize / 2, Cin 64 / 96 / 128 and, 1x1 only, 256, bias required; PIPS_E_ARG otherwise).  Both named kernels
+ * write 2*ceil(Ho*Wo/64) parts per frame on 64-row tiles. */
+#define PIPS_CONV_ROUTE_AUTO   0
+#define PIPS_CONV_ROUTE_IGEMM  1
+#define PIPS_CONV_ROUTE_E      2
+int    pips_conv_nhwc_f32_route(const float* in, int F, int H, int W, int Cin,
+                                const float* wgt, const float* bias, int Cout, int ksize, int cstride, int pad,
+                                float* out, float* stats, int* tiles_m_host, int route, void* stream);
+
+/* The finalize of those partials (exposed for unit tests): partial (F, parts, C) float4 -> mean_rstd (F, C, 2) = {mean,
+ * 1 / sqrt(var + 1e-5)}, combined in fp64; C % 16 == 0. */
+int    pips_inorm_finalize_pivot(const float* partial, int F, int parts, int C, float* mean_rstd, void* stream);
 
 /* epi values of the GEMM building blocks; PIPS_EPI_RES_BF16 is OR-ed to PIPS_EPI_RESIDUAL for pips_gemm_bf16 with out_bf16 = 1:
  * the residual R is a bf16 tensor too (the mixer's bf16 residual stream, PIPS_FLAG_BF16_STREAM).  Any other combination with it is

@@ -125,6 +125,9 @@ SIGNATURES = {
     "pips_gemm_f32": (c_int, [fp, c_int, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, c_int, c_void_p]),
     "pips_conv_nhwc_f32": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_int, c_int, fp, fp,
                                    C.POINTER(c_int), c_void_p]),
+    "pips_conv_nhwc_f32_route": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_int, c_int, fp, fp,
+                                         C.POINTER(c_int), c_int, c_void_p]),
+    "pips_inorm_finalize_pivot": (c_int, [fp, c_int, c_int, c_int, fp, c_void_p]),
     "pips_gemm_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, fp, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, c_int,
                        c_void_p]),
     "pips_gemm_bf16_route": (c_int, [c_int] * 6),

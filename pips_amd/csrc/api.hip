@@ -324,6 +324,7 @@ struct ConvCall {
     const float* wgt; const float* bias; int Cout, k, stride, pad;
     float* out; float* stats; int* tiles;
     MatMode mode; bool in_bf16, out_bf16; const float* in_norm; int parts_cap;
+    int route;               // EXACT only: GemmArgs::conv_route
 };
 // the geometry part, in the argument order of the pips_conv_nhwc_* entry points; mode and map types are left EXACT / fp32
 ConvCall conv_call(const void* in, int F, int H, int W, int Cin, const void* wgt, const float* bias, int Cout, int k, int stride,
@@ -339,6 +340,7 @@ int conv_nhwc(const ConvCall& c, hipStream_t st) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = c.in; g.W = c.wgt; g.bias = c.bias; g.C = c.out; g.stats = c.stats; g.in_norm = c.in_norm; g.stats_parts_cap = c.parts_cap;
+    g.conv_route = c.route;
     g.H = c.H; g.Win = c.W; g.Cin = c.Cin; g.KH = g.KW = c.k; g.cstride = c.stride; g.pad = c.pad;
     g.Ho = conv_out(c.H, c.k, c.stride, c.pad); g.Wo = conv_out(c.W, c.k, c.stride, c.pad);
     g.M = g.Ho * g.Wo; g.N = c.Cout; g.K = c.k * c.k * c.Cin; g.ldc = c.Cout; g.epi = EPI_BIAS;
@@ -1237,6 +1239,19 @@ int pips_conv_nhwc_f32(const float* in, int F, int H, int W, int Cin, const floa
                        void* stream) {
     PIPS_CHECK_ARG(in && wgt && out, "conv: null pointer");
     return conv_nhwc(conv_call(in, F, H, W, Cin, wgt, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host), (hipStream_t)stream);
+}
+int pips_conv_nhwc_f32_route(const float* in, int F, int H, int W, int Cin, const float* wgt, const float* bias,
+                             int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
+                             int route, void* stream) {
+    PIPS_CHECK_ARG(in && wgt && out, "conv: null pointer");
+    PIPS_CHECK_ARG(route >= PIPS_CONV_ROUTE_AUTO && route <= PIPS_CONV_ROUTE_E, "conv: unknown route %d", route);
+    ConvCall c = conv_call(in, F, H, W, Cin, wgt, bias, Cout, ksize, cstride, pad, out, stats, tiles_m_host);
+    c.route = route;
+    return conv_nhwc(c, (hipStream_t)stream);
+}
+int pips_inorm_finalize_pivot(const float* partial, int F, int parts, int C, float* mean_rstd, void* stream) {
+    PIPS_CHECK_ARG(partial && mean_rstd && F > 0 && parts > 0 && C > 0 && C % 16 == 0, "inorm_finalize_pivot: bad arguments");
+    return launch_inorm_finalize_pivot(partial, F, parts, C, mean_rstd, (hipStream_t)stream);
 }
 int pips_conv_nhwc_bf16(const float* in, int F, int H, int W, int Cin, const void* wgt_bf16, const float* bias,
                         int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,

@@ -253,6 +253,7 @@ struct GemmArgs {
     // to the bf16 input map while it is staged (conv_bf16_c64.hip only); null = the map is read as it is
     const float* in_norm;
     int stats_parts_cap;     // room in stats in partials per frame; 0 = the documented 2*ceil(Ho*Wo/64)+4
+    int conv_route;          // fp32 convolutions: 0 = the kernel launch_conv picks for the shape, PIPS_CONV_ROUTE_IGEMM / _E = that kernel
 #ifdef PIPS_GEMM_TRACE
     unsigned long long* trace;   // tools/gemm_trace.py: per-block phase timestamps
 #endif
@@ -328,6 +329,9 @@ int launch_conv(const GemmArgs& a, int frames, int* tiles_m, hipStream_t st);
 // that takes a layer (-1: none); *parts_out = InstanceNorm partials per frame
 int conv_f32_t4_config(const GemmArgs& a, int frames);
 int launch_conv_f32_t4(const GemmArgs& a, int cfg, int frames, int* parts_out, hipStream_t st);
+// 1x1 / 3x3, stride 1 / 2 convolutions on 64 x 64 tiles staged by LDS-DMA (conv_f32_e.hip): can the body run the layer, and its launcher
+bool conv_f32_e_admits(const GemmArgs& a);
+int launch_conv_f32_e(const GemmArgs& a, int frames, int* parts_out, hipStream_t st);
 // bf16-operand GEMM (gemm_bf16.hip): A fp32 or bf16, W bf16, C fp32 or bf16; pointers passed as float*
 int launch_gemm_bf16(const GemmArgs& a, int a_bf16, int out_bf16, hipStream_t st);
 // in_bf16 / out_bf16: the NHWC maps are bf16 instead of fp32 (the bf16 encoder keeps every activation in bf16)

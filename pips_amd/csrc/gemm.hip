@@ -476,13 +476,33 @@ static void conv_tile(int rows, int cout, int frames, int* bm, int* bn) {
     if (force_bm == 64 || force_bm == 128) *bm = force_bm;
 }
 
+// The layers the 64 x 64 LDS-DMA body (conv_f32_e.hip) takes from igemm_f32_kernel, by shape alone: the 3x3 convolutions with 96 or 128
+// input channels and whole 64-channel column tiles -- at 8 x 368 x 496 the eight 3x3 layers of the 1/8 and 1/16 resolution blocks
+// (per-layer A/B, three runs: profiles/conv_e_layers_ab.txt -- 54 -> 50, 69 -> 63 and, at 192 tiles, 39-41 -> 22 us).  Measured slower on
+// the new body and left on igemm_f32_kernel: the 64 -> 96 stride-2 entry (126 -> 140 us: half-empty second column tile), the 1x1
+// shortcuts and the final 1x1 (2 .. 8 stages of K do not pay for the prologue and the reduction through LDS).
+static bool conv_e_takes(const GemmArgs& a, int frames) {
+    if (!conv_f32_e_admits(a)) return false;
+    const int forced = PIPS_TUNE("PIPS_CONV_F32_E", -1);    // tuning hook: 0 = igemm_f32_kernel everywhere, 1 = the new body wherever it can run
+    if (forced >= 0) return forced != 0 && ((PIPS_TUNE("PIPS_CONV_F32_E_MASK", 15) >> (a.KH == 1 ? 3 : a.Cin / 32 - 2)) & 1) &&
+                            (long)cdiv(a.M, 64) * frames >= PIPS_TUNE("PIPS_CONV_F32_E_MINROWTILES", 0);
+    return a.KH == 3 && a.Cin >= 96 && a.N % 64 == 0;
+}
+
 int launch_conv(const GemmArgs& a, int frames, int* tiles_m, hipStream_t st) {
     PIPS_CHECK_ARG(a.Cin % 32 == 0, "conv: Cin=%d must be a multiple of 32", a.Cin);
     PIPS_CHECK_ARG(a.N % 32 == 0 && (a.N % 64 == 0 || a.N % 96 == 0), "conv: unsupported Cout=%d", a.N);
     PIPS_CHECK_ARG(a.K == a.KH * a.KW * a.Cin, "conv: K mismatch");
-    {                                                        // the four-wave assembly kernels of conv_f32_t4.hip (the big 3x3 layers)
+    if (a.conv_route == PIPS_CONV_ROUTE_E) {
+        PIPS_CHECK_ARG(conv_f32_e_admits(a), "conv: the 64 x 64 LDS-DMA body does not take this layer (k=%d stride=%d pad=%d Cin=%d)", a.KH,
+                       a.cstride, a.pad, a.Cin);
+        return launch_conv_f32_e(a, frames, tiles_m, st);
+    }
+    if (a.conv_route != PIPS_CONV_ROUTE_IGEMM) {
+        // the four-wave assembly kernels: conv_f32_t4.hip (the big 3x3 layers), conv_f32_e.hip (64 x 64 tiles on shape E's pipeline)
         const int cfg = conv_f32_t4_config(a, frames);
         if (cfg >= 0) return launch_conv_f32_t4(a, cfg, frames, tiles_m, st);
+        if (conv_e_takes(a, frames)) return launch_conv_f32_e(a, frames, tiles_m, st);
     }
     int bm, bn;
     conv_tile(a.M, a.N, frames, &bm, &bn);

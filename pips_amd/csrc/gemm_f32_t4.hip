@@ -18,6 +18,7 @@
 //         at M = 2048: 64 of them)
 //     E   shape D staged by LDS-DMA (no staging registers, no ds_write): what the product runs for shape D's problems; bitwise D
 #include "common.h"
+#include "f4_grid.h"      // F4Grid, f4_tile, f4_grid: the XCD-aware tile grid
 #ifndef PIPS_F32T4_INC
 #define PIPS_F32T4_INC "gemm_f32_t4_asm.inc"      // tuning builds point this at another schedule of the generator
 #endif
@@ -38,32 +39,6 @@ constexpr int F4_LDS_D = 4 * F4_STAGE_D;                     // 73 728 bytes: fo
       [blo] "s"(ASM_PTR_LO(Bb)), [bhi] "s"(ASM_PTR_HI(Bb)), [passA] "s"(asm_sgpr(passA)), [passW] "s"(asm_sgpr(passW)),             \
       [rstep] "s"(asm_sgpr(rstep)), [cstep] "s"(asm_sgpr(cstep)), [kt] "s"(asm_sgpr(kt)), [tstepA] "s"(asm_sgpr(tstepA)),           \
       [tstepC] "s"(asm_sgpr(tstepC)), [tstepR] "s"(asm_sgpr(tstepR)), [ntile] "s"(asm_sgpr(ntile))
-
-// Block -> (row unit, column tile).  Blocks go to the XCDs round robin (block & 7), every XCD has its own L2, and the operands
-// come out of the Infinity Cache: in the linear order (column tile fastest) the eight column tiles of the M = 2048 down-projection
-// land on eight XCDs and EVERY XCD pulls all of A through its L2 -- 132 MB per launch for 20 MB of operands.  Instead the XCDs
-// split the tile grid gm x gn (host: the split with the smallest per-XCD footprint) and each works through its own sub-grid.
-struct F4Grid { int units_m, tiles_n, gm, gn; };
-__device__ __forceinline__ void f4_tile(const F4Grid& g, int* um, int* tn) {
-    const int b = blockIdx.x;
-    if (g.gm == 0) { *um = b / g.tiles_n; *tn = b - *um * g.tiles_n; return; }
-    const int xcd = b & 7, local = b >> 3, xm = xcd / g.gn, xn = xcd - xm * g.gn;
-    const int pm = g.units_m / g.gm, pn = g.tiles_n / g.gn, lm = local / pn, ln = local - lm * pn;
-    *um = xm * pm + lm; *tn = xn * pn + ln;
-    (void)pm;
-}
-static F4Grid f4_grid(int units_m, int tiles_n, long bytes_unit_m, long bytes_tile_n) {
-    F4Grid g = {units_m, tiles_n, 0, 1};
-    if (!PIPS_TUNE("PIPS_F32_T4_XCD", 1) || ((long)units_m * tiles_n) % 8 != 0) return g;
-    long best = -1;
-    for (int gm = 8; gm >= 1; gm >>= 1) {
-        const int gn = 8 / gm;
-        if (units_m % gm != 0 || tiles_n % gn != 0) continue;
-        const long foot = (units_m / gm) * bytes_unit_m + (tiles_n / gn) * bytes_tile_n;
-        if (best < 0 || foot < best) { best = foot; g.gm = gm; g.gn = gn; }
-    }
-    return g;
-}
 
 // EPI: 0 = + bias + GELU, 1 = + bias + residual
 template <int EPI>

@@ -505,7 +505,17 @@ def partial_sums(stats):
     return (n * p + s).sum(dim=1), (q + 2 * p * s + n * p * p).sum(dim=1)
 
 
-def _conv(name, x, w, bias, ksize, stride, pad, want_stats, in_norm=None, out_dtype=torch.float32):
+def inorm_finalize(stats):
+    """Pivoted InstanceNorm partials (F, parts, C, 4) -> (F, C, 2) = {mean, rstd}: the encoder's own finalize kernel."""
+    st = _f32(stats)
+    F, parts, Cc, _ = st.shape
+    out = torch.empty(F, Cc, 2, dtype=torch.float32, device=st.device)
+    with torch.cuda.device(st.device):
+        _call("pips_inorm_finalize_pivot", _lib.ptr(st), F, parts, Cc, _lib.ptr(out), _stream())
+    return out
+
+
+def _conv(name, x, w, bias, ksize, stride, pad, want_stats, in_norm=None, out_dtype=torch.float32, route=None, out=None):
     """One NHWC convolution entry point: x (F,H,W,Cin), w with Cout = ``w.shape[-4]`` -> (F,Ho,Wo,Cout) [+ its pivoted partial
     statistics (F, parts, Cout, 4), cut to the parts the kernel reports].  ``pips_conv_nhwc_bf16_maps`` also takes in_norm,
     the output type and the room for partials (the larger bound of the LDS-resident 64 -> 64 kernel)."""
@@ -514,7 +524,9 @@ def _conv(name, x, w, bias, ksize, stride, pad, want_stats, in_norm=None, out_dt
     Cout = w.shape[-4]
     Ho = (H + 2 * pad - ksize) // stride + 1
     Wo = (W + 2 * pad - ksize) // stride + 1
-    out = torch.empty(F, Ho, Wo, Cout, dtype=out_dtype, device=x.device)
+    if out is None:
+        out = torch.empty(F, Ho, Wo, Cout, dtype=out_dtype, device=x.device)
+    assert out.shape == (F, Ho, Wo, Cout) and out.dtype == out_dtype and out.is_contiguous() and out.device == x.device
     cap = 2 * ((Ho * Wo + 63) // 64) + 4
     if maps:
         cap = max(cap, ((Wo + 31) // 32) * ((Ho + 3) // 4) * 4)
@@ -525,6 +537,8 @@ def _conv(name, x, w, bias, ksize, stride, pad, want_stats, in_norm=None, out_dt
         if maps:
             _call(name, _lib.ptr(x), _lib.ptr(in_norm), *geom, 1 if out_dtype == torch.bfloat16 else 0, _lib.ptr(stats), cap,
                   C.byref(tiles), _stream())
+        elif route is not None:
+            _call(name, _lib.ptr(x), *geom, _lib.ptr(stats), C.byref(tiles), route, _stream())
         else:
             _call(name, _lib.ptr(x), *geom, _lib.ptr(stats), C.byref(tiles), _stream())
     if want_stats:
@@ -532,10 +546,15 @@ def _conv(name, x, w, bias, ksize, stride, pad, want_stats, in_norm=None, out_dt
     return out
 
 
-def conv_nhwc(x, w_packed, bias, ksize, stride, pad, want_stats=False):
+def conv_nhwc(x, w_packed, bias, ksize, stride, pad, want_stats=False, route=None, out=None):
     """x (F,H,W,Cin) NHWC, w_packed (Cout, k, k, Cin) -> (F,Ho,Wo,Cout) [+ pivoted partial stats (F, parts, Cout, 4),
-    parts = m tiles x wave rows: see partial_sums()]."""
-    return _conv("pips_conv_nhwc_f32", _f32(x), _f32(w_packed), bias, ksize, stride, pad, want_stats)
+    parts = m tiles x wave rows: see partial_sums()].  route: None = the kernel the shape selects, "igemm" = igemm_f32_kernel,
+    "e" = the 64 x 64 LDS-DMA body of conv_f32_e.hip (pips_conv_nhwc_f32_route).  out: a contiguous (F,Ho,Wo,Cout) fp32 tensor to
+    write into (it may be a view of a larger buffer)."""
+    if route is None:
+        return _conv("pips_conv_nhwc_f32", _f32(x), _f32(w_packed), bias, ksize, stride, pad, want_stats, out=out)
+    return _conv("pips_conv_nhwc_f32_route", _f32(x), _f32(w_packed), bias, ksize, stride, pad, want_stats,
+                 route={"igemm": 1, "e": 2}[route], out=out)
 
 
 def conv_nhwc_bf16(x, w_bf16, bias, ksize, stride, pad, want_stats=False):
