@@ -104,7 +104,8 @@ const char* pips_last_error(void);
  * queries are ready, which join, one hop, which frames are final -- one call per round); pips_track_rings,
  * pips_mixer_input_build_rings, pips_pyramid_append_at, pips_stream_select_clips, pips_stream_round_clips,
  * pips_stream_workspace_bytes_clips and pips_stream_emit_cols (several streamed videos on one flat cache of rings: one state and
- * one round for all of them). */
+ * one round for all of them); pips_stream_keep (queries leave a running stream: the kept columns of the state in narrower
+ * arrays). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -427,6 +428,28 @@ int    pips_stream_round_clips(const void* arena, const float* pyramid, int F, i
                                void* workspace, size_t workspace_bytes, void* stream);
 int    pips_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1, const int* cols, int m,
                              float* out_trajs, float* out_vis, void* stream);
+/* Queries leave a running stream: pips_stream_keep copies the columns keep[0..m) (device int32, strictly ascending, not verified;
+ * 0 <= m <= n) of the state of pips_stream_round / pips_stream_round_clips for n queries into caller-owned arrays sized for m
+ * queries -- tq_out / cur_out / status_out (m), xy_out (m,2), feat_out (m,128), trajs_out (L,m,2), vis_out (L,m), and clip_out (m)
+ * with clip -- none of which may alias an input.  Column j of every output is column keep[j] of the input: the integer arrays, xy
+ * and feat verbatim, the rows of trajs / vis as bit patterns (NaN payloads survive, as in pips_stream_emit); the inputs stay
+ * bit-identical, and the caller releases them and goes on with the narrower state (active / new_list / steps need room for m, the
+ * workspace is sized for m).  counts receives {0, 0, low, 0[, low_0 .. low_{V-1}]}: low = min cur over the kept queries whose
+ * status is not 2 (INT_MAX: none), low_v the same over those of stream v (clip clamped to [0, V-1]) -- what pips_stream_select*
+ * would report for the kept set, so the host sizes its next append without a select (a second select would mark waiting queries
+ * joined without their join having run: this entry point never selects).  clip == NULL: the one-stream state -- V and clip_out are
+ * not read, counts has 4 ints; with clip, 1 <= V <= PIPS_STREAM_V_MAX and counts has 4 + V.
+ * A member of keep outside [0, n) is never dereferenced: its output column becomes a finished, empty query -- status 2, tq = cur = 0,
+ * clip = 0, xy and feat zero, rows 0x7fc00000 (pips_stream_emit_cols' rule for a bad column) -- and enters no low.
+ * m == 0: PIPS_OK, only counts is written (keep and the *_out arrays are not looked at).  PIPS_E_ARG ahead of any launch: n < 1,
+ * m < 0, m > n, L < 16, a NULL array (clip and clip_out are NULL together or not at all), V out of range with clip.  A rejected
+ * call writes nothing.  Two launches; no allocation, no synchronisation, no workspace. */
+int    pips_stream_keep(int n, const int* keep, int m,
+                        const int* tq, const float* xy, const int* cur, const int* status, const int* clip, const float* feat,
+                        const float* trajs, const float* vis, int L,
+                        int* tq_out, float* xy_out, int* cur_out, int* status_out, int* clip_out, float* feat_out,
+                        float* trajs_out, float* vis_out,
+                        int V, int* counts, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 

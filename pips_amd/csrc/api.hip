@@ -1679,6 +1679,22 @@ int pips_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1
     PIPS_CHECK_ARG(cols && out_trajs && out_vis, "stream_emit_cols: null pointer");
     return launch_stream_emit_cols(trajs, vis, L, n, f0, f1, cols, m, out_trajs, out_vis, (hipStream_t)stream);
 }
+int pips_stream_keep(int n, const int* keep, int m, const int* tq, const float* xy, const int* cur, const int* status, const int* clip,
+                     const float* feat, const float* trajs, const float* vis, int L, int* tq_out, float* xy_out, int* cur_out,
+                     int* status_out, int* clip_out, float* feat_out, float* trajs_out, float* vis_out, int V, int* counts,
+                     void* stream) {
+    PIPS_CHECK_ARG(n >= 1 && m >= 0 && m <= n, "stream_keep: need n >= 1 and 0 <= m <= n (n=%d, m=%d)", n, m);
+    PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_keep: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
+    PIPS_CHECK_ARG(tq && xy && cur && status && feat && trajs && vis && counts, "stream_keep: null pointer");
+    if (clip != nullptr) PIPS_CHECK_ARG(V >= 1 && V <= STREAM_V_MAX, "stream_keep: need 1 <= V <= %d streams (V=%d)", STREAM_V_MAX, V);
+    if (m > 0) {                      // (m == 0: counts alone is written; keep and the empty outputs are not looked at)
+        PIPS_CHECK_ARG(keep && tq_out && xy_out && cur_out && status_out && feat_out && trajs_out && vis_out, "stream_keep: null pointer");
+        PIPS_CHECK_ARG((clip != nullptr) == (clip_out != nullptr), "stream_keep: clip and clip_out go together");
+    }
+    const StreamState in = {tq, xy, cur, status, clip, feat, trajs, vis};
+    const StreamStateOut out = {tq_out, xy_out, cur_out, status_out, clip_out, feat_out, trajs_out, vis_out};
+    return launch_stream_keep(n, keep, m, in, out, L, clip != nullptr ? V : 0, counts, (hipStream_t)stream);
+}
 
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {

@@ -490,5 +490,15 @@ int launch_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, f
 // the same for the columns cols[0..m) only (device int32): dense (f1-f0, m, 2) / (f1-f0, m) outputs, those elements reset to NaN
 int launch_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1, const int* cols, int m, float* out_trajs,
                             float* out_vis, hipStream_t st);
+// the columns keep[0..m) of a state of n queries into arrays sized for m (a member outside [0, n): a finished, empty query) and
+// counts = {0, 0, low, 0[, low_0 .. low_{V-1}]} of the kept set; clip == nullptr: one stream, V and clip_out are not read.  m == 0
+// writes counts alone.
+struct StreamState {
+    const int* tq; const float* xy; const int* cur; const int* status; const int* clip; const float* feat;
+    const float* trajs; const float* vis;
+};
+struct StreamStateOut { int* tq; float* xy; int* cur; int* status; int* clip; float* feat; float* trajs; float* vis; };
+int launch_stream_keep(int n, const int* keep, int m, const StreamState& in, const StreamStateOut& out, int L, int V, int* counts,
+                       hipStream_t st);
 
 }  // namespace pips

@@ -2,7 +2,8 @@
 // caller-owned state are ready for a window, which of them join with this round, the lowest window start still pending
 // (stream_select_kernel), the staging and the scatter of a joining query's first-window features (stream_join_*_kernel) and the
 // move of the frames that became final out of the row ring (stream_emit_kernel; stream_emit_cols_kernel for the columns of one
-// stream of several).  Plain HIP; built with the default floating-point flags, as chain.hip is.  No atomics on the lists: their
+// stream of several), and the copy of the kept columns of a state into narrower arrays when queries leave the stream
+// (stream_keep_state_kernel, stream_keep_rows_kernel).  Plain HIP; built with the default floating-point flags, as chain.hip is.  No atomics on the lists: their
 // order is part of the contract.
 #include <climits>
 
@@ -201,6 +202,118 @@ __global__ __launch_bounds__(SEL_THREADS) void stream_emit_cols_kernel(unsigned*
     vis[e] = STREAM_NAN;
 }
 
+struct KeepArgs {
+    StreamState in; StreamStateOut out;
+    const int* keep; int* counts;
+    int n, m, V;
+};
+
+// Queries leave the state.  ONE block walks keep[0..m) in chunks of SEL_THREADS, a thread per kept query: the per-query scalars of
+// column keep[j] go to column j of the narrower arrays (xy as bit patterns), and the lowest window start of the kept queries that
+// are not done is reduced the way stream_select_kernel does it -- a wave reduction plus LDS at the end of the walk, an LDS integer
+// minimum per stream (CLIPS) -- so counts is what a select over the kept set would report.  A member outside [0, n) is never
+// dereferenced: a done, empty query stands in its column and enters no minimum.  m == 0: counts alone.
+template <bool CLIPS>
+__global__ __launch_bounds__(SEL_THREADS) void stream_keep_state_kernel(const KeepArgs a) {
+    __shared__ int wave_low[SEL_WAVES];
+    __shared__ int clip_low[CLIPS ? STREAM_V_MAX : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned* xy = reinterpret_cast<const unsigned*>(a.in.xy);
+    unsigned* xy_out = reinterpret_cast<unsigned*>(a.out.xy);
+    int low = INT_MAX;
+    if (CLIPS) {
+        if (tid < STREAM_V_MAX) clip_low[tid] = INT_MAX;
+        __syncthreads();
+    }
+    for (int j0 = 0; j0 < a.m; j0 += SEL_THREADS) {
+        const int j = j0 + tid;
+        if (j >= a.m) continue;
+        const int c = a.keep[j];
+        const bool ok = (unsigned)c < (unsigned)a.n;
+        const int s = ok ? a.in.status[c] : 2;
+        const int cu = ok ? a.in.cur[c] : 0;
+        a.out.tq[j] = ok ? a.in.tq[c] : 0;
+        a.out.cur[j] = cu;
+        a.out.status[j] = s;
+        xy_out[2 * j] = ok ? xy[2 * c] : 0u;
+        xy_out[2 * j + 1] = ok ? xy[2 * c + 1] : 0u;
+        int v = 0;
+        if (CLIPS) {
+            const int cl = ok ? a.in.clip[c] : 0;
+            a.out.clip[j] = cl;
+            v = min(max(cl, 0), a.V - 1);
+        }
+        if (s != 2) {
+            low = min(low, cu);
+            if (CLIPS) atomicMin(&clip_low[v], cu);                  // (LDS)
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) low = min(low, __shfl_xor(low, d));
+    if (lane == 0) wave_low[wave] = low;
+    __syncthreads();
+    if (tid == 0) {
+        int lo = wave_low[0];
+#pragma unroll
+        for (int w = 1; w < SEL_WAVES; ++w) lo = min(lo, wave_low[w]);
+        a.counts[0] = 0;
+        a.counts[1] = 0;
+        a.counts[2] = lo;
+        a.counts[3] = 0;
+    }
+    if (CLIPS && tid < a.V) a.counts[4 + tid] = clip_low[tid];      // (the barrier above orders the LDS minima)
+}
+
+constexpr int KEEP_FEAT_Y = 4;       // rows of blocks that move feat, behind the rows of blocks that move the row ring
+constexpr int KEEP_ROWS_Y = 4096;    // ... of which a launch has at most this many (a longer ring: several rows per block)
+
+// The first min(L, KEEP_ROWS_Y) rows of blocks move the ring: blockIdx.y takes rows y, y + their number, ...  Thread j of a row's
+// blocks moves column keep[j] -- two words of trajs (one 8-byte piece where both buffers allow it) and one of vis -- to column j:
+// keep ascends, so neighbouring lanes read neighbouring kept columns of one row (every fetched line is used as far as it holds
+// kept columns) and write a dense run.  A gathered row has no 16-byte pieces: its columns are not neighbours in the source.
+// The last KEEP_FEAT_Y rows of blocks move the feature rows, 512 contiguous bytes each: in 16-byte pieces where both buffers are
+// 16-byte aligned, word by word otherwise; 32 (128) neighbouring lanes share a row.  Bit patterns throughout.  A column outside
+// [0, n) is not read: its rows get the NaN and its features zero.
+__global__ __launch_bounds__(SEL_THREADS) void stream_keep_rows_kernel(const unsigned* __restrict__ trajs, const unsigned* __restrict__ vis,
+                                                                       const unsigned* __restrict__ feat, int L, int n,
+                                                                       const int* __restrict__ keep, int m, unsigned* __restrict__ trajs_out,
+                                                                       unsigned* __restrict__ vis_out, unsigned* __restrict__ feat_out,
+                                                                       int vec_trajs, int vec_feat) {
+    const int ry = gridDim.y - KEEP_FEAT_Y;                          // rows of blocks on the ring: min(L, KEEP_ROWS_Y)
+    if ((int)blockIdx.y < ry) {
+        for (int j = blockIdx.x * SEL_THREADS + threadIdx.x; j < m; j += gridDim.x * SEL_THREADS) {
+            const int c = keep[j];
+            const bool ok = (unsigned)c < (unsigned)n;
+            for (int y = blockIdx.y; y < L; y += ry) {
+                const size_t o = (size_t)y * m + j, e = (size_t)y * n + (ok ? c : 0);
+                if (!ok) {
+                    trajs_out[2 * o] = trajs_out[2 * o + 1] = vis_out[o] = STREAM_NAN;
+                } else if (vec_trajs) {
+                    reinterpret_cast<uint2*>(trajs_out)[o] = reinterpret_cast<const uint2*>(trajs)[e];
+                    vis_out[o] = vis[e];
+                } else {
+                    trajs_out[2 * o] = trajs[2 * e];
+                    trajs_out[2 * o + 1] = trajs[2 * e + 1];
+                    vis_out[o] = vis[e];
+                }
+            }
+        }
+        return;
+    }
+    const int per = vec_feat ? PIPS_C / 4 : PIPS_C;                  // pieces of one feature row
+    const size_t total = (size_t)m * per, stride = (size_t)gridDim.x * SEL_THREADS * KEEP_FEAT_Y;
+    for (size_t p = ((size_t)(blockIdx.y - ry) * gridDim.x + blockIdx.x) * SEL_THREADS + threadIdx.x; p < total; p += stride) {
+        const int j = (int)(p / per), i = (int)(p % per);
+        const int c = keep[j];
+        const bool ok = (unsigned)c < (unsigned)n;
+        if (vec_feat) {
+            reinterpret_cast<uint4*>(feat_out)[p] = ok ? reinterpret_cast<const uint4*>(feat)[(size_t)c * per + i] : make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            feat_out[p] = ok ? feat[(size_t)c * per + i] : 0u;
+        }
+    }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -256,6 +369,29 @@ int launch_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int 
                        reinterpret_cast<unsigned*>(trajs), reinterpret_cast<unsigned*>(vis), L, n, f0, f1 - f0, cols, m,
                        reinterpret_cast<unsigned*>(out_trajs), reinterpret_cast<unsigned*>(out_vis), vec);
     PIPS_CHECK_LAUNCH("stream_emit_cols");
+    return PIPS_OK;
+}
+
+int launch_stream_keep(int n, const int* keep, int m, const StreamState& in, const StreamStateOut& out, int L, int V, int* counts,
+                       hipStream_t st) {
+    KeepArgs a;
+    a.in = in; a.out = out; a.keep = keep; a.counts = counts; a.n = n; a.m = m; a.V = V;
+    if (in.clip != nullptr)
+        hipLaunchKernelGGL(stream_keep_state_kernel<true>, dim3(1), dim3(SEL_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL(stream_keep_state_kernel<false>, dim3(1), dim3(SEL_THREADS), 0, st, a);
+    PIPS_CHECK_LAUNCH("stream_keep_state");
+    if (m == 0) return PIPS_OK;
+    const auto aligned8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; };
+    const int vec_trajs = aligned8(in.trajs) && aligned8(out.trajs);
+    const int vec_feat = aligned16(in.feat) && aligned16(out.feat);
+    // a thread moves one kept column of a row per pass; 64 blocks per row at the most
+    const int bx = min((m + SEL_THREADS - 1) / SEL_THREADS, 64);
+    hipLaunchKernelGGL(stream_keep_rows_kernel, dim3(bx, min(L, KEEP_ROWS_Y) + KEEP_FEAT_Y), dim3(SEL_THREADS), 0, st,
+                       reinterpret_cast<const unsigned*>(in.trajs), reinterpret_cast<const unsigned*>(in.vis),
+                       reinterpret_cast<const unsigned*>(in.feat), L, n, keep, m, reinterpret_cast<unsigned*>(out.trajs),
+                       reinterpret_cast<unsigned*>(out.vis), reinterpret_cast<unsigned*>(out.feat), vec_trajs, vec_feat);
+    PIPS_CHECK_LAUNCH("stream_keep_rows");
     return PIPS_OK;
 }
 

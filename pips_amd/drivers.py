@@ -29,7 +29,9 @@ ONE library call (``Pips.chain_hop``: the same bookkeeping as HIP kernels around
 and reads the live count back, one host sync per hop either way.  Both give the same hops and the same bits.  ``StreamTracker``
 also takes ``rounds="torch" | "library"`` and keeps its device state in one object per value: ``_TorchRounds`` decides who is ready,
 who joins and which frames are final in torch ops and hops on the chosen engine; for ``_LibraryRounds`` the round itself is one
-``pips_stream_round`` call on int32 state.  Queries can be added while the video runs (``add_queries``, either value).
+``pips_stream_round`` call on int32 state.  Queries can be added while the video runs (``add_queries``, either value) and taken
+away again (``remove_queries``: the state's ``keep`` copies the remaining columns into narrower arrays -- ``pips_stream_keep`` under
+``rounds="library"``), so the device state follows the number of queries being tracked, not the number ever given.
 """
 from __future__ import annotations
 
@@ -382,6 +384,7 @@ class _Rounds:
     """The device state of a ``StreamTracker``, in the form its ``rounds`` value takes.  Both forms hold the output rows -- trajs
     (L,N,2) and vis (L,N), frame f in row f % L, NaN where nothing was written -- and the queries ``tq`` / ``xy``, and offer
       start(dev) / grow(t, xy, m)   the state of the tracker's N queries, none joined / m more columns, the old ones copied
+      keep(idx)      only the columns idx (host int64, ascending) remain, in narrower arrays; the others are forgotten
       pending()      lowest window start of the unfinished queries (None when all are finished)
       run(final)     hop rounds until no query is ready -- one whose 8 window frames have all arrived (final: every unfinished
                      one); yields (active indices, steps) per round ((None, None) when a library round keeps no steps)
@@ -400,6 +403,14 @@ class _Rounds:
     def grow(self, t, xy, m):
         self.trajs, self.vis = _wider(self.trajs, m), _wider(self.vis, m)
         self.tq, self.xy = _longer(self.tq, t), _longer(self.xy, xy)
+
+    def _keep_torch(self, idx, names):
+        """the torch form of ``keep``: the arrays ``names`` indexed on their query axis -> idx on the device"""
+        i = idx.to(self.tq.device)
+        self.trajs, self.vis = self.trajs.index_select(1, i), self.vis.index_select(1, i)       # (new, contiguous tensors)
+        for k in names:
+            setattr(self, k, getattr(self, k)[i])
+        return i
 
 
 class _TorchRounds(_Rounds):
@@ -424,6 +435,11 @@ class _TorchRounds(_Rounds):
         self.joined, self.done = _longer(self.joined, torch.zeros(m)), _longer(self.done, torch.zeros(m))
         feat = self.eng.feat
         self._engine(_longer(self.eng.cur, t), None if feat is None else _longer(feat, torch.zeros(m, feat.shape[1])))
+
+    def keep(self, idx):
+        cur, feat = self.eng.cur, self.eng.feat
+        i = self._keep_torch(idx, ("tq", "xy", "joined", "done"))
+        self._engine(cur[i], None if feat is None else feat[i])                    # (the engine is rebuilt as ``grow`` rebuilds it)
 
     def pending(self):
         live = self.eng.cur[~self.done]
@@ -486,6 +502,15 @@ class _LibraryRounds(_Rounds):
         self._lists()
         self.low = int(t.min()) if self.low is None else min(self.low, int(t.min()))
 
+    def keep(self, idx):
+        # one pips_stream_keep call; its counts are what a select over the kept queries would report (the one host read)
+        *arrays, counts = ops.stream_keep(idx.to(self.tq.device, torch.int32), self.tq, self.xy, self.cur, self.status, self.feat,
+                                          self.trajs, self.vis)
+        self.tq, self.xy, self.cur, self.status, self.feat, self.trajs, self.vis = arrays
+        self._lists()
+        low = counts.tolist()[2]
+        self.low = None if low == _NO_LOW else low
+
     def pending(self):
         return self.low
 
@@ -510,6 +535,22 @@ class _LibraryRounds(_Rounds):
         return ops.stream_emit(self.trajs, self.vis, f0, f1)
 
 
+def _kept(cols, n, what):
+    """``cols``: a tensor or a sequence of columns to remove out of ``n`` -> (cols as host int64, the columns that remain, ascending);
+    ValueError for a column outside [0, n), one that is no integer and a duplicate"""
+    c = torch.as_tensor(cols).detach().to("cpu").reshape(-1)
+    if c.numel() > 0 and (c.is_floating_point() or c.is_complex() or c.dtype == torch.bool):
+        raise ValueError(f"{what} must be integers, not {c.dtype}")
+    c = c.to(torch.int64)
+    if bool(((c < 0) | (c >= n)).any()):
+        raise ValueError(f"{what} must lie in [0, {n}): {c.tolist()}")
+    mask = torch.ones(n, dtype=torch.bool)
+    mask[c] = False
+    if int(mask.sum()) != n - c.numel():
+        raise ValueError(f"{what} holds a column twice: {c.tolist()}")
+    return c, torch.nonzero(mask).squeeze(1)
+
+
 _ROUNDS = {"torch": _TorchRounds, "library": _LibraryRounds}
 ROUNDS = tuple(_ROUNDS)
 
@@ -530,7 +571,9 @@ class StreamTracker:
     ready particle, new ones joining with their first-window features (the same point sample as ``feat_init=None``).  A
     frame is final when it lies below every unfinished particle's window start.  ``push`` splits
     a chunk so that no slot is overwritten while a pending window can still read it: ``slots >= 9`` keeps the 8 frames of
-    a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query.
+    a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query being
+    tracked: ``remove_queries(cols)`` takes queries away while the video runs and gives their rows and their share of every
+    round back, so the state follows the queries there are, not the ones there ever were.
 
     The tracker keeps what every ``rounds`` / ``engine`` value shares; the device state and the rounds are ``self.state``:
     ``_TorchRounds`` (``rounds="torch"``, the default: a ``model.track`` call per round or, with ``engine="native"``, one
@@ -581,6 +624,31 @@ class StreamTracker:
         if self.cache is not None and m > 0:
             self.state.grow(t, xy, m)
         return torch.arange(N, N + m)
+
+    @torch.no_grad()
+    def remove_queries(self, cols):
+        """Stop tracking the queries in the output columns ``cols`` (a tensor or a sequence of current columns) -> ``keep``, a host
+        int64 tensor with the former column of each column that remains, ascending.  From this call on the removed queries are
+        not hopped, do not hold back the frames of the others or the room for new frames, and have no column in what ``push`` /
+        ``finish`` return: the remaining columns keep their order, ``add_queries`` puts new ones behind them, and ``tq_host``,
+        ``xy_in``, ``N``, ``hops`` and the device state shrink (the state's ``keep``).  ``finish()`` no longer looks at a removed
+        query: this is how one on a frame that will never come is cancelled.  Frames of a removed query that were not returned
+        yet are DISCARDED; frames of the remaining queries that the removed ones held back become final and are returned by the
+        next ``push`` / ``finish``.  Each remaining column stays what a stream given only the remaining queries up front returns
+        (the clause of ``add_queries``).  Works before the first ``push``, with no column and with every column.
+        ValueError, with the tracker left as it was, for a column outside ``[0, N)``, a duplicate and after ``finish()``."""
+        if self.finished:
+            raise ValueError("remove_queries() after finish()")
+        cols, keep = _kept(cols, self.N, "the columns to remove")
+        if cols.numel() == 0:
+            return keep
+        self.tq_host, self.xy_in = self.tq_host[keep], self.xy_in[keep.to(self.xy_in.device)]
+        self.N = keep.numel()
+        if self.hops is not None:
+            self.hops = [self.hops[k] for k in keep.tolist()]
+        if self.cache is not None:
+            self.state.keep(keep)
+        return keep
 
     @torch.no_grad()
     def push(self, frames):
@@ -683,6 +751,11 @@ class _MultiTorchRounds(_Rounds):
         feat = self.eng.feat
         self._engine(_longer(self.eng.cur, t), None if feat is None else _longer(feat, torch.zeros(m, feat.shape[1])))
 
+    def keep(self, idx):
+        cur, feat = self.eng.cur, self.eng.feat
+        i = self._keep_torch(idx, ("tq", "xy", "joined", "done", "clip"))
+        self._engine(cur[i], None if feat is None else feat[i])
+
     def end(self, v):
         self.final[v] = True
 
@@ -753,6 +826,13 @@ class _MultiLibraryRounds(_Rounds):
         self.feat = _longer(self.feat, torch.zeros(m, self.feat.shape[1]))
         self._lists()
         self.low[v] = int(t.min()) if self.low[v] is None else min(self.low[v], int(t.min()))
+
+    def keep(self, idx):
+        *arrays, counts = ops.stream_keep(idx.to(self.tq.device, torch.int32), self.tq, self.xy, self.cur, self.status, self.feat,
+                                          self.trajs, self.vis, clip=self.clip, V=self.t.V)
+        self.tq, self.xy, self.cur, self.status, self.feat, self.trajs, self.vis, self.clip = arrays
+        self._lists()
+        self.low = [None if x == _NO_LOW else x for x in counts.tolist()[4:]]
 
     def end(self, v):
         self.final[v:v + 1].fill_(1)
@@ -865,6 +945,29 @@ class MultiStreamTracker:
         if self.cache is not None and m > 0:
             self.state.grow(t, xy, m, v)
         return torch.arange(n_v, n_v + m)
+
+    @torch.no_grad()
+    def remove_queries(self, v, cols):
+        """``StreamTracker.remove_queries`` for stream ``v``: ``cols`` are positions among stream ``v``'s output columns (the numbering
+        ``add_queries(v, ...)`` reports) -> the former positions of that stream's columns that remain, ascending.  The other streams'
+        outputs and hop lists are untouched; the shared state and ``clip_host`` shrink.  ValueError, with the tracker left as it
+        was, for a bad stream, a position outside the stream's columns, a duplicate and a finished stream."""
+        v = self._stream(v)
+        if self.finished[v]:
+            raise ValueError(f"remove_queries() after stream {v} was finished")
+        mine = self.columns(v)
+        cols, keep_v = _kept(cols, mine.numel(), f"the positions to remove from stream {v}")
+        if cols.numel() == 0:
+            return keep_v
+        _, keep = _kept(mine[cols], self.N, "the columns to remove")
+        self.tq_host, self.xy_in = self.tq_host[keep], self.xy_in[keep.to(self.xy_in.device)]
+        self.clip_host = self.clip_host[keep]
+        self.N = keep.numel()
+        if self.hops is not None:
+            self.hops = [self.hops[k] for k in keep.tolist()]
+        if self.cache is not None:
+            self.state.keep(keep)
+        return keep_v
 
     @torch.no_grad()
     def push(self, chunks):

@@ -446,6 +446,25 @@ def stream_emit_cols(trajs, vis, f0, f1, cols):
     return out_t, out_v
 
 
+def stream_keep(keep, tq, xy, cur, status, feat, trajs, vis, clip=None, V=0):
+    """pips_stream_keep: the columns ``keep`` (m) int32, ascending, of the stream state tq / cur / status (n) int32, xy (n,2), feat
+    (n,128), trajs (L,n,2), vis (L,n) -- and ``clip`` (n) int32 of a state over ``V`` streams -- in new arrays for m queries; the
+    inputs are left as they were.  -> (tq, xy, cur, status, feat, trajs, vis[, clip], counts): ``counts`` (4, or 4 + V with
+    ``clip``) int32 on the device holds {0, 0, low, 0[, low_0 .. low_{V-1}]} of the kept set (the caller reads it back)."""
+    L, n = trajs.shape[0], trajs.shape[1]
+    m, dev, i32, f32 = keep.numel(), trajs.device, torch.int32, torch.float32
+    o_tq, o_cur, o_status = (torch.empty(m, dtype=i32, device=dev) for _ in range(3))
+    o_clip = None if clip is None else torch.empty(m, dtype=i32, device=dev)
+    o_xy, o_feat = torch.empty(m, 2, dtype=f32, device=dev), torch.empty(m, LATENT, dtype=f32, device=dev)
+    o_trajs, o_vis = torch.empty(L, m, 2, dtype=f32, device=dev), torch.empty(L, m, dtype=f32, device=dev)
+    counts = torch.empty(4 if clip is None else 4 + int(V), dtype=i32, device=dev)
+    with torch.cuda.device(dev):
+        _call("pips_stream_keep", n, _i32(keep), m, _i32(tq), _chain_f32(xy), _i32(cur), _i32(status), _i32(clip), _chain_f32(feat),
+              _chain_f32(trajs), _chain_f32(vis), L, _lib.ptr(o_tq), _lib.ptr(o_xy), _lib.ptr(o_cur), _lib.ptr(o_status),
+              _lib.ptr(o_clip), _lib.ptr(o_feat), _lib.ptr(o_trajs), _lib.ptr(o_vis), int(V), _lib.ptr(counts), _stream())
+    return (o_tq, o_xy, o_cur, o_status, o_feat, o_trajs, o_vis) + (() if clip is None else (o_clip,)) + (counts,)
+
+
 def gemm(A, W, bias=None, epi=0, R=None):
     """C = epi(A @ W.T + bias).  epi: 0 none, 1 GELU, 2 + R."""
     A, W = _f32(A), _f32(W)

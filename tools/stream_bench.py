@@ -10,7 +10,13 @@ on the host, chunks of 16 frames, a ring of 24 slots.  Prints one JSON line:
 The append kernel's time comes from a separate ``rocprofv3 --kernel-trace --stats`` run of ``--only stream``.
 ``--rounds``: instead, the stream under ``rounds="torch"`` and ``rounds="library"`` (one pips_stream_round call per round) at T,
 alternating on one GPU after a warm-up of each, medians of --reps calls; the rounds of one call are counted and the two outputs
-compared bit for bit."""
+compared bit for bit.
+``--churn``: instead, a ``StreamTracker(rounds="library")`` over T = 400 frames that starts from 256 queries on frame 0 and, from the
+second push on, gets 64 new queries before every push (on the oldest frame not returned yet) -- with the 64 oldest columns taken
+away by ``remove_queries`` at the same moment, against the same run without the removals.  Per run: the state's column count after
+the last push, the median time of the last five pushes and ``torch.cuda.max_memory_allocated``.  Times: one warm-up of each run, then
+--reps of each, alternating on one model, and the medians over those.  Memory: one run of each on a model of its own (a model keeps
+the round workspace of the widest state it has served)."""
 import argparse
 import json
 import os
@@ -100,6 +106,67 @@ def compare_rounds(m, q, host, reps):
             "stream_rounds_library_s": round(statistics.median(ts["library"]), 4), "rounds": count[0], "bit_equal": same}
 
 
+CHURN_T, CHURN_ADD = 400, 64
+
+
+def churn_run(m, q0, host, remove):
+    """one stream with 64 queries added (and, with ``remove``, the 64 oldest removed) ahead of every push from the second on
+    -> (columns of the state after the last push, median seconds of the last five pushes)"""
+    dev = q0.device
+    st = drivers.StreamTracker(m, q0, iters=6, slots=SLOTS, rounds="library")
+    xy = q0[0, :CHURN_ADD, 1:]
+    ts = []
+    for i, c in enumerate(chunks(host)):
+        if i >= 1:
+            t = torch.full((CHURN_ADD, 1), float(st.emitted), device=dev)
+            st.add_queries(torch.cat([t, xy + float(i % 7)], dim=1).unsqueeze(0))
+            if remove:
+                st.remove_queries(range(CHURN_ADD))
+        ts.append(timed(lambda: st.push(c)))
+    cols = st.trajs.shape[1]
+    assert cols == st.N
+    st.finish()
+    torch.cuda.synchronize()
+    return cols, statistics.median(ts[-5:])
+
+
+def compare_churn(dev, q, reps):
+    q0 = q.clone()
+    q0[0, :, 0] = 0
+    host = frames(0, CHURN_T)
+    pushes = (CHURN_T + CHUNK - 1) // CHUNK
+    runs = {"churn": True, "grow": False}
+    res = {"config": "360x640 stride 4, 256 queries on frame 0, chunks of 16, slots 24, library rounds", "T": CHURN_T, "pushes": pushes,
+           "added_per_push": CHURN_ADD}
+    # memory first, each run on a model of its own: a model keeps the round workspace of the widest state it has served
+    for k, remove in runs.items():
+        m = model(dev)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        churn_run(m, q0, host, remove)
+        res[f"{k}_peak_MiB"] = round(torch.cuda.max_memory_allocated() / 2**20, 1)
+        del m
+    m = model(dev)
+    got = {k: [] for k in runs}
+    for k, remove in runs.items():                                      # warm-up: weights, workspaces, the allocator's pools
+        churn_run(m, q0, host, remove)
+    for _ in range(reps):
+        for k, remove in runs.items():
+            got[k].append(churn_run(m, q0, host, remove))
+    for k, rows in got.items():
+        res[f"{k}_columns"] = rows[0][0]
+        res[f"{k}_push_ms_last5"] = round(statistics.median(r[1] for r in rows) * 1e3, 2)
+    assert res["churn_columns"] == N and res["grow_columns"] == N + CHURN_ADD * (pushes - 1), res
+    return res
+
+
+def model(dev):
+    m = Pips(S=8, stride=STRIDE)
+    m.load_state_dict(init_state_dict(0, tamed=True))
+    return m.to(dev).eval()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=100)
@@ -107,12 +174,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default="all", choices=["all", "stream"], help="stream: time the stream alone (kernel trace)")
     ap.add_argument("--rounds", action="store_true", help='time rounds="torch" against rounds="library" and nothing else')
+    ap.add_argument("--churn", action="store_true", help="queries added and removed at every push against added only, and nothing else")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    m = Pips(S=8, stride=STRIDE)
-    m.load_state_dict(init_state_dict(0, tamed=True))
-    m = m.to(dev).eval()
     q = queries(dev)
+    if a.churn:
+        print(json.dumps(compare_churn(dev, q, a.reps)))
+        return
+    m = model(dev)
     names = ["stream"] if a.only == "stream" else ["stream", "queries", "chained"]
     res = {"config": "360x640 stride 4, N=256 over frames 0/33/66/99, chunks of 16, slots 24", "T": a.T}
     host = frames(0, a.T)                                               # host uint8 video: the stream is fed host chunks
