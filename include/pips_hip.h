@@ -105,7 +105,8 @@ const char* pips_last_error(void);
  * pips_mixer_input_build_rings, pips_pyramid_append_at, pips_stream_select_clips, pips_stream_round_clips,
  * pips_stream_workspace_bytes_clips and pips_stream_emit_cols (several streamed videos on one flat cache of rings: one state and
  * one round for all of them); pips_stream_keep (queries leave a running stream: the kept columns of the state in narrower
- * arrays). */
+ * arrays); pips_cover_step and pips_cover_workspace_bytes (which queries of a stream are retired and where new ones are seeded, so
+ * that a bounded set of tracks stays spread over the frame). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -450,6 +451,34 @@ int    pips_stream_keep(int n, const int* keep, int m,
                         int* tq_out, float* xy_out, int* cur_out, int* status_out, int* clip_out, float* feat_out,
                         float* trajs_out, float* vis_out,
                         int V, int* counts, void* stream);
+/* Keeping the frame covered: pips_cover_step judges the n queries of a stream on the frames [f1 - m, f1) that were just moved out
+ * of its row ring (pips_stream_emit's dense trajs (m,n,2) / vis (m,n)), and lists the cells of a grid over the H x W frame that
+ * need a new query.  The grid has gh = ceil(H / cell) rows and gw = ceil(W / cell) columns, row-major; with f = f1 - 1:
+ *  - a query with tq > f is PENDING: kept, its run 0, standing on its query position xy (every query of a step with m = 0 is);
+ *  - a started query updates its run over the returned frames g >= tq in order, run = (vis[g] < vis_logit) ? run + 1 : 0,
+ *    starting from lost[c] (a NaN compares false and resets the run; vis_logit is logit(threshold), computed by the host), and
+ *    stands on (x, y) = trajs[f].  It is retired as OUTSIDE unless x >= 0 && x <= W-1 && y >= 0 && y <= H-1 (NaN and +-inf
+ *    retire), otherwise as LOST if run >= lost_after (INT_MAX: never), otherwise kept;
+ *  - a kept query whose position passes the same test occupies the cell (min(int(floor(y / cell)), gh-1), min(int(floor(x /
+ *    cell)), gw-1)), `/` being the correctly rounded fp32 quotient by float(cell); a pending query outside the frame occupies none.
+ * keep[0..n_keep) receives the kept columns, strictly ascending, and lost_out[0..n_keep) their runs in that order -- keep is the
+ * list pips_stream_keep takes, lost_out the `lost` of the narrower state.  seeds receives one (t, x, y) = (f1, min((j + 0.5) *
+ * cell, W-1), min((i + 0.5) * cell, H-1)) per cell (i, j) that nobody occupies, in row-major order, cut after max(0,
+ * max_queries - n_keep) entries: the (1,n_seed,3) queries to add.  counts = {n_keep, n_seed, n_outside, n_lost}, outside taking
+ * precedence over lost.  keep and lost_out need room for n ints, seeds for min(gh*gw, max_queries) triples; the elements behind
+ * the counts are not written.  Every input stays bit-identical, `lost` included.  The first step of a stream runs before anything
+ * is encoded, with m = 0 and f1 = 0: the seeds land on frame 0.  n = 0 is a valid call (tq, xy, lost, keep and lost_out are then
+ * not looked at; trajs and vis are not looked at when m = 0 or n = 0).
+ * PIPS_E_ARG ahead of any launch: n < 0, m < 0, cell < 8, H or W < 1, lost_after < 1, max_queries < 0, m == 0 with f1 != 0,
+ * f1 < m, more than PIPS_COVER_CELLS_MAX cells, a NULL array that would be read or written.  PIPS_E_WORKSPACE: workspace_bytes <
+ * pips_cover_workspace_bytes(n, gh, gw) (0 for n < 0, gh or gw < 1, too many cells).  A rejected call writes nothing.  One memset
+ * node and two launches; the lists are scanned by one block (their order is the contract); no allocation, no synchronisation. */
+#define PIPS_COVER_CELLS_MAX (1 << 24)
+size_t pips_cover_workspace_bytes(int n, int gh, int gw);
+int    pips_cover_step(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy,
+                       const int* lost, int H, int W, int cell, float vis_logit, int lost_after, int max_queries,
+                       int* keep, int* lost_out, float* seeds, int* counts,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 

@@ -1696,6 +1696,36 @@ int pips_stream_keep(int n, const int* keep, int m, const int* tq, const float* 
     return launch_stream_keep(n, keep, m, in, out, L, clip != nullptr ? V : 0, counts, (hipStream_t)stream);
 }
 
+// ---- the cover step
+size_t pips_cover_workspace_bytes(int n, int gh, int gw) {
+    if (n < 0 || gh < 1 || gw < 1 || (long long)gh * gw > PIPS_COVER_CELLS_MAX) return 0;
+    return cover_workspace_ints(n, gh, gw) * sizeof(int);
+}
+int pips_cover_step(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy, const int* lost,
+                    int H, int W, int cell, float vis_logit, int lost_after, int max_queries, int* keep, int* lost_out,
+                    float* seeds, int* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    PIPS_CHECK_ARG(n >= 0 && m >= 0, "cover_step: need n >= 0 and m >= 0 (n=%d, m=%d)", n, m);
+    PIPS_CHECK_ARG(cell >= 8 && H >= 1 && W >= 1, "cover_step: need cell >= 8 and a frame of at least 1x1 (cell=%d, H=%d, W=%d)", cell, H, W);
+    PIPS_CHECK_ARG(lost_after >= 1 && max_queries >= 0, "cover_step: need lost_after >= 1 and max_queries >= 0 (%d, %d)", lost_after,
+                   max_queries);
+    PIPS_CHECK_ARG(m == 0 ? f1 == 0 : f1 >= m, "cover_step: rows of frames [f1 - m, f1) need f1 >= m, and a step without rows is the first (m=%d, f1=%d)", m, f1);
+    const int gh = (H - 1) / cell + 1, gw = (W - 1) / cell + 1;
+    PIPS_CHECK_ARG((long long)gh * gw <= PIPS_COVER_CELLS_MAX, "cover_step: a grid of %d x %d cells has more than %d", gh, gw,
+                   PIPS_COVER_CELLS_MAX);
+    PIPS_CHECK_ARG(seeds && counts && workspace, "cover_step: null pointer");
+    if (n > 0) {
+        PIPS_CHECK_ARG(tq && xy && lost && keep && lost_out, "cover_step: null pointer");
+        if (m > 0) PIPS_CHECK_ARG(trajs && vis, "cover_step: null pointer");
+    }
+    const size_t need = cover_workspace_ints(n, gh, gw) * sizeof(int);
+    if (workspace_bytes < need) {
+        set_error("cover_step: workspace %zu < %zu bytes", workspace_bytes, need);
+        return PIPS_E_WORKSPACE;
+    }
+    return launch_cover_step(n, m, f1, trajs, vis, tq, xy, lost, H, W, cell, gh, gw, vis_logit, lost_after, max_queries, keep, lost_out,
+                             seeds, counts, (int*)workspace, (hipStream_t)stream);
+}
+
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;

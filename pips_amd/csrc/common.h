@@ -501,4 +501,11 @@ struct StreamStateOut { int* tq; float* xy; int* cur; int* status; int* clip; fl
 int launch_stream_keep(int n, const int* keep, int m, const StreamState& in, const StreamStateOut& out, int L, int V, int* counts,
                        hipStream_t st);
 
+// ---- cover.hip: the cover step of a streamed tracker (pips_cover_step).  workspace: cover_workspace_ints(n, gh, gw) ints -- the
+// flag and the run of each query and the occupancy of each cell; arguments checked by the caller.
+size_t cover_workspace_ints(int n, int gh, int gw);
+int launch_cover_step(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy, const int* lost,
+                      int H, int W, int cell, int gh, int gw, float vis_logit, int lost_after, int max_queries, int* keep,
+                      int* lost_out, float* seeds, int* counts, int* workspace, hipStream_t st);
+
 }  // namespace pips

@@ -18,6 +18,9 @@
 * ``MultiStreamTracker`` / ``track_streams`` -- ``StreamTracker`` for a LIST of streams (equal frame size; own lengths, chunking,
   queries and ends) on one cache of rings (``Pips.ring_cache_videos``) and one state: a round hops the ready queries of every
   stream together, and each stream gets what its own ``StreamTracker`` returns, bit for bit.
+* ``CoverTracker`` / ``track_cover`` (and ``MultiStreamTracker(cover=)``) -- a ``StreamTracker`` that decides which queries it tracks:
+  a ``Cover`` policy retires the queries that left the frame or stayed invisible and seeds the empty cells of a grid over the
+  frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``).
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -720,6 +723,231 @@ def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, e
     return trajs, vis, st.hops
 
 
+# ---------------------------------------------------------------------------------------------- keeping the frame covered
+_INT_MAX = 2 ** 31 - 1
+COVER_SCANS = ("torch", "library")
+
+
+def _whole(x, what, low):
+    """x as an int; ValueError unless it is a whole number >= low (a bool is not a number here)"""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x or x in (float("inf"), float("-inf")) or int(x) != x \
+            or int(x) < low:
+        raise ValueError(f"{what} must be an integer >= {low}, not {x!r}")
+    if int(x) > _INT_MAX:
+        raise ValueError(f"{what} must fit an int32, not {x!r}")
+    return int(x)
+
+
+class Cover:
+    """The policy of a tracker that decides itself which queries it tracks (``CoverTracker``, ``MultiStreamTracker(cover=)``): a grid
+    of ``cell`` x ``cell`` pixel cells lies over the frame, and after every push that returned frames a COVER STEP
+      * retires a started query as "outside" unless its position on the last returned frame has 0 <= x <= W-1 and 0 <= y <= H-1
+        (NaN and infinities retire), and otherwise as "lost" when its visibility logit stayed below ``logit(vis_thr)`` for
+        ``lost_after`` returned frames in a row (``None``: never) -- the run is carried from push to push;
+      * keeps every other query, and every query whose frame was not returned yet (pending) on its query position;
+      * seeds one new query on the next frame at the centre of every cell that holds no kept or pending query, in row-major
+        order, as long as the stream has fewer than ``max_queries`` (``None``: no cap).
+    The full rule is pips_cover_step's in include/pips_hip.h.  ``scan="torch"`` performs the step as torch ops (``cover_scan``; it
+    also runs on CPU tensors); ``scan="library"`` makes one ``pips_cover_step`` call and reads its four counts -- the kept list and
+    the seeds come to the host only when the counts say that something changed.  Both give the same queries and the same bits."""
+
+    def __init__(self, cell=32, vis_thr=0.5, lost_after=4, max_queries=None, scan="torch"):
+        self.cell = _whole(cell, "cell", 8)
+        if isinstance(vis_thr, bool) or not isinstance(vis_thr, (int, float)) or not 0.0 < vis_thr < 1.0:
+            raise ValueError(f"vis_thr must lie in (0, 1), not {vis_thr!r}")
+        self.vis_thr = float(vis_thr)
+        # computed once, on the host, as fp32: no exp on the device, and both scans compare against the same bits
+        self.vis_logit = float(torch.logit(torch.tensor(self.vis_thr, dtype=torch.float32)))
+        self.lost_after = None if lost_after is None else _whole(lost_after, "lost_after", 1)
+        self.max_queries = None if max_queries is None else _whole(max_queries, "max_queries", 0)
+        if scan not in COVER_SCANS:
+            raise ValueError(f"scan must be one of {COVER_SCANS}, not {scan!r}")
+        self.scan = scan
+
+    def grid(self, H, W):
+        """(rows, columns) of the cells over an H x W frame"""
+        return (H - 1) // self.cell + 1, (W - 1) // self.cell + 1
+
+    def step(self, trajs, vis, f1, tq, xy, lost, H, W):
+        """one cover step by the chosen scan -> (keep (n_keep) ints, lost_out (n_keep) int32, seeds (n_seed,3), the four counts
+        on the host); trajs (m,n,2) / vis (m,n) are the rows of frames [f1 - m, f1), tq / lost (n) int32, xy (n,2)"""
+        args = (trajs, vis, f1, tq, xy, lost, H, W, self.cell, self.vis_logit, _INT_MAX if self.lost_after is None else self.lost_after,
+                _INT_MAX if self.max_queries is None else self.max_queries)
+        if self.scan == "library":
+            keep, lost_out, seeds, counts = ops.cover_step(*args)
+            counts = counts.tolist()                                              # the one host read
+        else:
+            keep, lost_out, seeds, counts = cover_scan(*args)
+        return keep[:counts[0]], lost_out[:counts[0]], seeds[:counts[1]], counts
+
+
+def cover_scan(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, max_queries):
+    """The cover step (pips_cover_step, include/pips_hip.h) as torch ops, on any device -> (keep (n_keep) int32 ascending, lost_out
+    (n_keep) int32, seeds (n_seed,3) = (t, x, y), [n_keep, n_seed, n_outside, n_lost]).  trajs (m,n,2) / vis (m,n): the rows of
+    frames [f1 - m, f1); tq / lost (n) int32; xy (n,2); the inputs are left as they were."""
+    n, m, dev = tq.numel(), vis.shape[0], xy.device
+    gh, gw = (H - 1) // cell + 1, (W - 1) // cell + 1
+    pending = (tq > f1 - 1) if m > 0 else torch.ones(n, dtype=torch.bool, device=dev)
+    run, zero = lost.to(torch.int32), torch.zeros(n, dtype=torch.int32, device=dev)
+    for g in range(m):                                                            # the run over the frames from t_q on, in order
+        on = ~pending & (tq <= f1 - m + g)
+        run = torch.where(on, torch.where(vis[g] < vis_logit, run + 1, zero), run)      # (a NaN compares false: the run restarts)
+    run = torch.where(pending, zero, run)
+    pos = torch.where(pending.unsqueeze(1), xy, trajs[m - 1]) if m > 0 else xy
+    x, y = pos[:, 0], pos[:, 1]
+    inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)                    # written so that NaN and +-inf fail it
+    outside = ~pending & ~inside
+    gone = ~pending & inside & (run >= lost_after)
+    kept = ~(outside | gone)
+    keep = torch.nonzero(kept).squeeze(1)
+    stand = kept & inside                                                         # (a pending query outside the frame: no cell)
+    i = torch.div(torch.where(stand, y, torch.zeros_like(y)), float(cell)).floor().to(torch.int64).clamp(max=gh - 1)
+    j = torch.div(torch.where(stand, x, torch.zeros_like(x)), float(cell)).floor().to(torch.int64).clamp(max=gw - 1)
+    occ = torch.zeros(gh * gw, dtype=torch.bool, device=dev)
+    occ[(i * gw + j)[stand]] = True
+    empty = torch.nonzero(~occ).squeeze(1)[:max(max_queries - keep.numel(), 0)]
+    sx = ((empty % gw).to(torch.float32) + 0.5) * cell
+    sy = (torch.div(empty, gw, rounding_mode="floor").to(torch.float32) + 0.5) * cell
+    seeds = torch.stack([torch.full_like(sx, float(f1)), sx.clamp(max=float(W - 1)), sy.clamp(max=float(H - 1))], dim=1)
+    return keep.to(torch.int32), run[keep], seeds, [keep.numel(), empty.numel(), int(outside.sum()), int(gone.sum())]
+
+
+class _CoverBook:
+    """What a covered stream keeps per query beside the tracker's own state: the identity of each column (``ids``), the frame of
+    each identity (``born``), identity -> (frame, reason) of the retired ones (``retired``), their hop lists (``hops``, when recorded)
+    and, on the device, the arrays a cover step reads -- ``tq`` / ``lost`` (n) int32 and ``xy`` (n,2).  ``start`` runs the first step
+    (no rows: every query is pending and the seeds land on frame 0), ``step`` the one after a push; both act on the tracker
+    through ``add(queries (1,k,3))`` and ``remove(columns)``."""
+
+    def __init__(self, cover, tq_host, record_hops):
+        self.cover, self.size = cover, None
+        self.ids, self.born, self.retired = list(range(tq_host.numel())), tq_host.tolist(), {}
+        self.hops = {} if record_hops else None
+
+    def start(self, H, W, dev, tq_host, xy, add, remove):
+        self.size = (int(H), int(W))
+        self.tq, self.xy = tq_host.to(dev, torch.int32), xy.to(dev, torch.float32).contiguous()
+        self.lost = torch.zeros_like(self.tq)
+        n = self.tq.numel()
+        self.step(0, self.xy.new_empty(0, n, 2), self.xy.new_empty(0, n), add, remove, None)
+
+    def step(self, f0, trajs, vis, add, remove, hops):
+        """the cover step on the rows trajs (m,n,2) / vis (m,n) of frames [f0, f0 + m); ``hops``: the hop list of each column"""
+        n, m = len(self.ids), vis.shape[0]
+        f1, (H, W) = f0 + m, self.size
+        keep, lost_out, seeds, counts = self.cover.step(trajs, vis, f1, self.tq, self.xy, self.lost, H, W)
+        if counts[0] < n:                                                         # somebody is retired: the kept list comes over
+            kept = keep.tolist()
+            gone = sorted(set(range(n)) - set(kept))
+            x, y = trajs[m - 1][torch.tensor(gone, device=trajs.device)].to("cpu").unbind(1)
+            inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)
+            for c, ok in zip(gone, inside.tolist()):
+                self.retired[self.ids[c]] = (f1 - 1, "lost" if ok else "outside")
+                if self.hops is not None:
+                    self.hops[self.ids[c]] = hops[c]
+            assert counts[2] == len(gone) - int(inside.sum()) and counts[3] == int(inside.sum())
+            remove(gone)
+            self.ids = [self.ids[c] for c in kept]
+            k = keep.to(torch.int64)
+            self.tq, self.xy = self.tq[k], self.xy[k]
+        self.lost = lost_out
+        if counts[1] > 0:                                                         # and so do the seeds
+            k = counts[1]
+            add(seeds.unsqueeze(0))
+            self.ids += list(range(len(self.born), len(self.born) + k))
+            self.born += [f1] * k
+            self.tq = torch.cat([self.tq, torch.full((k,), f1, dtype=torch.int32, device=self.tq.device)])
+            self.xy = torch.cat([self.xy, seeds[:, 1:]])
+            self.lost = torch.cat([self.lost, torch.zeros(k, dtype=torch.int32, device=self.tq.device)])
+
+    def all_hops(self, live):
+        """hop lists by identity: the saved ones of the retired queries and ``live``, those of the present columns"""
+        out = dict(self.hops)
+        out.update(zip(self.ids, live))
+        return [out[i] for i in range(len(self.born))]
+
+
+def _by_identity(parts, book):
+    """the ``(f0, trajs, vis, ids)`` parts of a covered stream -> trajs (1,T,K,2), vis (1,T,K) by identity, NaN outside each life,
+    and born (K,), retired (K,) (-1: alive at the end) as host int64"""
+    T, K, dev = sum(p[1].shape[1] for p in parts), len(book.born), parts[0][1].device
+    trajs = torch.full((1, T, K, 2), float("nan"), dtype=torch.float32, device=dev)
+    vis = torch.full((1, T, K), float("nan"), dtype=torch.float32, device=dev)
+    for f0, t, v, ids in parts:
+        m = t.shape[1]
+        if m > 0 and ids.numel() > 0:
+            i = ids.to(dev)
+            trajs[0][f0:f0 + m][:, i] = t[0]
+            vis[0][f0:f0 + m][:, i] = v[0]
+    retired = torch.tensor([book.retired.get(i, (-1,))[0] for i in range(K)], dtype=torch.int64)
+    return trajs, vis, torch.tensor(book.born, dtype=torch.int64), retired
+
+
+def _check_frames(frames):
+    if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[2] != 3:
+        raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(frames.shape)}")
+
+
+class CoverTracker:
+    """A stream that decides which queries it tracks: a ``StreamTracker`` (driven only through ``add_queries``, ``remove_queries``,
+    ``push`` and ``finish``) plus the policy ``cover`` (a ``Cover``).  ``queries`` (1,N,3) or None are the caller's own; they are
+    tracked, retired and counted like the seeds.  ``push(frames)`` / ``finish()`` return ``(f0, trajs (1,m,n,2), vis (1,m,n), ids
+    (n,))``: ``ids`` is the identity of each returned column (host int64) -- the caller's queries first, then the seeds in order
+    of creation; an identity never changes and is never reused.  The first cover step runs inside the first ``push``, before
+    anything is encoded (the frame size is known then): it seeds frame 0.  A cover step then runs at the end of every ``push``
+    that returned at least one frame, on those frames, and retires and seeds for the pushes that follow; ``finish()`` runs none.
+    ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost")`` the last frame returned for it and why,
+    ``hops`` (``record_hops=True``) the hop list of each identity.  Over its life an identity is what ``track_stream`` given that
+    query alone returns; frames of a retired query that were not returned before its retirement are discarded."""
+
+    def __init__(self, model, cover, queries=None, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
+        if not isinstance(cover, Cover):
+            raise ValueError(f"cover must be a drivers.Cover, not {cover!r}")
+        if queries is None:
+            queries = torch.zeros(1, 0, 3)
+        self.cover = cover
+        self.st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=record_hops, engine=engine, rounds=rounds)
+        self.book = _CoverBook(cover, self.st.tq_host, record_hops)
+
+    ids = property(lambda self: torch.tensor(self.book.ids, dtype=torch.int64))
+    born, retired = (property(lambda self, k=k: getattr(self.book, k)) for k in ("born", "retired"))
+    hops = property(lambda self: None if self.book.hops is None else self.book.all_hops(self.st.hops))
+    emitted, finished = (property(lambda self, k=k: getattr(self.st, k)) for k in ("emitted", "finished"))
+
+    @torch.no_grad()
+    def push(self, frames):
+        st = self.st
+        if st.finished:
+            raise ValueError("push() after finish()")
+        _check_frames(frames)
+        if st.cache is None:
+            st.push(frames[:, :0])                 # no frame: the ring and the state are made, the device is known
+            self.book.start(frames.shape[3], frames.shape[4], st.cache.device, st.tq_host, st.xy_in, st.add_queries,
+                            st.remove_queries)
+        ids = self.ids
+        f0, trajs, vis = st.push(frames)
+        if trajs.shape[1] > 0:
+            self.book.step(f0, trajs[0], vis[0], st.add_queries, st.remove_queries, st.hops)
+        return f0, trajs, vis, ids
+
+    @torch.no_grad()
+    def finish(self):
+        ids = self.ids
+        return self.st.finish() + (ids,)
+
+
+@torch.no_grad()
+def track_cover(model, chunks, cover, queries=None, iters=6, slots=24, return_hops=False, engine="torch", rounds="torch"):
+    """``CoverTracker`` over an iterable of ``(1,k,3,H,W)`` chunks -> trajs (1,T,K,2) px and vis (1,T,K) logits by identity, NaN
+    outside each identity's life, born (K,) and retired (K,) frames (host int64; retired = -1 for those alive at the end).
+    ``return_hops=True``: also the hop list of each identity."""
+    ct = CoverTracker(model, cover, queries, iters=iters, slots=slots, record_hops=return_hops, engine=engine, rounds=rounds)
+    parts = [ct.push(c) for c in chunks]
+    parts.append(ct.finish())
+    out = _by_identity(parts, ct.book)
+    return out + (ct.hops,) if return_hops else out
+
+
 # ---------------------------------------------------------------------------------------------- several streams at once
 _NO_LOW = 2 ** 31 - 1                                         # the library's "no pending query" (INT_MAX)
 
@@ -882,11 +1110,18 @@ class MultiStreamTracker:
     ``rounds="torch"`` hops with ``_hop(..., clip=)``; ``rounds="library"`` makes one ``pips_stream_round_clips`` call per round.
     ``joint_encode=True`` sends the frames one wave appends across all streams through shared encoder passes
     (``Pips.encode_streams(joint=True)``): fuller passes, and maps that differ from the per-stream ones by the encoder's
-    tile-order noise instead of matching bit for bit."""
+    tile-order noise instead of matching bit for bit.
+    ``cover`` (a ``Cover``; None: the tracker described so far): every stream is covered as its own ``CoverTracker`` would be -- its
+    first cover step runs inside the first ``push``, and a step runs on the part of a stream that a ``push`` returned and acts
+    through ``remove_queries(v, .)`` / ``add_queries(v, .)``, which are then the cover's alone (ValueError for a caller).  ``push`` and
+    ``finish`` return ``(f0, trajs, vis, ids)`` per stream, ``ids`` being the identity of each column as ``CoverTracker`` numbers
+    them; ``books[v]`` holds ``born`` / ``retired`` of stream v and ``cover_hops(v)`` its hop lists by identity."""
 
     S = 8
 
-    def __init__(self, model, queries_list, iters=6, slots=24, record_hops=False, rounds="torch", joint_encode=False):
+    def __init__(self, model, queries_list, iters=6, slots=24, record_hops=False, rounds="torch", joint_encode=False, cover=None):
+        if cover is not None and not isinstance(cover, Cover):
+            raise ValueError(f"cover must be a drivers.Cover or None, not {cover!r}")
         if rounds not in ROUNDS:
             raise ValueError(f"rounds must be one of {ROUNDS}, not {rounds!r}")
         assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
@@ -906,8 +1141,22 @@ class MultiStreamTracker:
         self.finished, self.emitted = [False] * self.V, [0] * self.V                # per stream; frames [0, emitted[v]) returned
         self.hops = [[] for _ in range(self.N)] if record_hops else None          # per column of the shared state
         self.state = _MULTI_ROUNDS[rounds](self, "torch")
+        self.cover = cover
+        self.books = None if cover is None else [_CoverBook(cover, t, record_hops) for t in tqs]
 
     trajs, vis, cur = (property(lambda self, k=k: getattr(self.state, k)) for k in ("trajs", "vis", "cur"))
+
+    def stream_ids(self, v):
+        """the identity of each output column of stream ``v`` of a covered tracker (host int64)"""
+        return torch.tensor(self.books[v].ids, dtype=torch.int64)
+
+    def cover_hops(self, v):
+        """the hop list of each identity of stream ``v`` of a covered tracker (``record_hops=True``)"""
+        return self.books[v].all_hops(self.stream_hops(v))
+
+    def _uncovered(self, what):
+        if self.cover is not None:
+            raise ValueError(f"{what}() on a covered tracker: its cover adds and removes the queries")
 
     def columns(self, v):
         """the columns of the shared state that hold stream ``v``'s queries, in the order of its outputs (host int64)"""
@@ -928,6 +1177,10 @@ class MultiStreamTracker:
     def add_queries(self, v, queries):
         """Further queries (1,m,3) for stream ``v`` while it runs -> the positions (m,) they take among stream ``v``'s output
         columns.  ValueError, with the tracker left as it was, for a frame of that stream returned already and after its end."""
+        self._uncovered("add_queries")
+        return self._add_queries(v, queries)
+
+    def _add_queries(self, v, queries):
         v = self._stream(v)
         if self.finished[v]:
             raise ValueError(f"add_queries() after stream {v} was finished")
@@ -952,6 +1205,10 @@ class MultiStreamTracker:
         ``add_queries(v, ...)`` reports) -> the former positions of that stream's columns that remain, ascending.  The other streams'
         outputs and hop lists are untouched; the shared state and ``clip_host`` shrink.  ValueError, with the tracker left as it
         was, for a bad stream, a position outside the stream's columns, a duplicate and a finished stream."""
+        self._uncovered("remove_queries")
+        return self._remove_queries(v, cols)
+
+    def _remove_queries(self, v, cols):
         v = self._stream(v)
         if self.finished[v]:
             raise ValueError(f"remove_queries() after stream {v} was finished")
@@ -989,6 +1246,11 @@ class MultiStreamTracker:
             self.size = size
             self.cache = self.model.ring_cache_videos(*size, self.slots, self.V)
             self.state.start(self.cache.device)
+            for v in range(self.V if self.cover is not None else 0):            # the first cover step of every stream
+                cols = self.columns(v)
+                self.books[v].start(*size, self.cache.device, self.tq_host[cols], self.xy_in[cols.to(self.xy_in.device)],
+                                    *self._cover_acts(v))
+        ids = None if self.cover is None else [self.stream_ids(v) for v in range(self.V)]
         f0, outs = list(self.emitted), [[] for _ in range(self.V)]
         left = [0 if c is None else c.shape[1] for c in chunks]
         while any(left):
@@ -1007,7 +1269,16 @@ class MultiStreamTracker:
                 for v, c in wave:
                     self.model.encode(c, into=self.cache, clip=v)
             self._rounds(outs)
-        return [self._cat(v, f0[v], outs[v]) for v in range(self.V)]
+        res = [self._cat(v, f0[v], outs[v]) for v in range(self.V)]
+        if self.cover is None:
+            return res
+        for v, (f, t, vi) in enumerate(res):                                       # a cover step on what each stream returned
+            if t.shape[1] > 0:
+                self.books[v].step(f, t[0], vi[0], *self._cover_acts(v), None if self.hops is None else self.stream_hops(v))
+        return [r + (i,) for r, i in zip(res, ids)]
+
+    def _cover_acts(self, v):
+        return (lambda q: self._add_queries(v, q)), (lambda cols: self._remove_queries(v, cols))
 
     @torch.no_grad()
     def finish(self, v=None):
@@ -1026,6 +1297,8 @@ class MultiStreamTracker:
         if self.cache is not None and which:
             self._rounds(outs)
         res = [self._cat(u, f0[u], outs[u]) if u in which else None for u in range(self.V)]
+        if self.cover is not None:                                                  # (no cover step at the end of a stream)
+            res = [None if r is None else r + (self.stream_ids(u),) for u, r in enumerate(res)]
         return res if v is None else res[v]
 
     def _rounds(self, outs):
@@ -1052,13 +1325,15 @@ class MultiStreamTracker:
 
 
 @torch.no_grad()
-def track_streams(model, chunk_lists, queries_list, iters=6, slots=24, return_hops=False, rounds="torch", joint_encode=False):
+def track_streams(model, chunk_lists, queries_list, iters=6, slots=24, return_hops=False, rounds="torch", joint_encode=False,
+                  cover=None):
     """``MultiStreamTracker`` over V lists of ``(1,k,3,H,W)`` chunks (the lists may differ in length: a stream whose list has run
     out is finished while the others go on) -> per stream what ``track_stream`` returns: ``(trajs_e (1,T_v,N_v,2), vis_e
-    (1,T_v,N_v))``, with its hop lists behind them under ``return_hops=True``."""
+    (1,T_v,N_v))``, with its hop lists behind them under ``return_hops=True``.  With a ``cover``: per stream what ``track_cover``
+    returns."""
     chunk_lists = [list(c) for c in chunk_lists]
     mt = MultiStreamTracker(model, queries_list, iters=iters, slots=slots, record_hops=return_hops, rounds=rounds,
-                            joint_encode=joint_encode)
+                            joint_encode=joint_encode, cover=cover)
     if len(chunk_lists) != mt.V:
         raise ValueError(f"{len(chunk_lists)} chunk lists for {mt.V} streams")
     parts = [[] for _ in range(mt.V)]
@@ -1071,6 +1346,11 @@ def track_streams(model, chunk_lists, queries_list, iters=6, slots=24, return_ho
             for v, p in enumerate(mt.push(wave)):
                 parts[v].append(p)
     out = []
+    for v in range(mt.V if cover is not None else 0):
+        res = _by_identity(parts[v], mt.books[v])
+        out.append(res + (mt.cover_hops(v),) if return_hops else res)
+    if cover is not None:
+        return out
     for v in range(mt.V):
         res = (torch.cat([p[1] for p in parts[v]], dim=1), torch.cat([p[2] for p in parts[v]], dim=1))
         out.append(res + (mt.stream_hops(v),) if return_hops else res)

@@ -465,6 +465,24 @@ def stream_keep(keep, tq, xy, cur, status, feat, trajs, vis, clip=None, V=0):
     return (o_tq, o_xy, o_cur, o_status, o_feat, o_trajs, o_vis) + (() if clip is None else (o_clip,)) + (counts,)
 
 
+def cover_step(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, max_queries):
+    """pips_cover_step on the rows trajs (m,n,2) / vis (m,n) of frames [f1 - m, f1) and the per-query tq / lost (n) int32 and xy
+    (n,2): which queries are kept and where new ones are seeded (include/pips_hip.h).  -> (keep (n) int32, lost_out (n) int32,
+    seeds (min(cells, max_queries),3), counts (4) int32) on ``xy``'s device: counts = {n_keep, n_seed, n_outside, n_lost} says how
+    much of each list was written (the caller reads it back); the inputs are left as they were."""
+    m, n, dev = vis.shape[0], tq.numel(), xy.device
+    gh, gw = (int(H) - 1) // int(cell) + 1, (int(W) - 1) // int(cell) + 1
+    keep, lost_out = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    seeds = torch.empty(max(min(gh * gw, int(max_queries)), 1), 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(_lib.load().pips_cover_workspace_bytes(n, gh, gw) // 4, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _call("pips_cover_step", n, m, int(f1), _chain_f32(trajs), _chain_f32(vis), _i32(tq), _chain_f32(xy), _i32(lost), int(H), int(W),
+              int(cell), float(vis_logit), int(lost_after), int(max_queries), _lib.ptr(keep), _lib.ptr(lost_out), _lib.ptr(seeds),
+              _lib.ptr(counts), _lib.ptr(ws), ws.numel() * 4, _stream())
+    return keep, lost_out, seeds, counts
+
+
 def gemm(A, W, bias=None, epi=0, R=None):
     """C = epi(A @ W.T + bias).  epi: 0 none, 1 GELU, 2 + R."""
     A, W = _f32(A), _f32(W)

@@ -16,7 +16,11 @@ second push on, gets 64 new queries before every push (on the oldest frame not r
 away by ``remove_queries`` at the same moment, against the same run without the removals.  Per run: the state's column count after
 the last push, the median time of the last five pushes and ``torch.cuda.max_memory_allocated``.  Times: one warm-up of each run, then
 --reps of each, alternating on one model, and the medians over those.  Memory: one run of each on a model of its own (a model keeps
-the round workspace of the widest state it has served)."""
+the round workspace of the widest state it has served).
+``--cover``: instead, a ``CoverTracker(rounds="library")`` over T = 400 frames of the same config that starts from no query of the
+caller's: cells of 32 px (a 12 x 20 grid), default policy, ``scan="torch"`` against ``scan="library"``.  Prints the live count per
+push (the same under both scans: checked), and per scan the median push time and the median time of the cover step alone (the
+tracker's ``book.step`` timed with a device synchronisation on either side).  One warm-up of each, then --reps of each, alternating."""
 import argparse
 import json
 import os
@@ -161,6 +165,45 @@ def compare_churn(dev, q, reps):
     return res
 
 
+def cover_run(m, host, scan):
+    """one covered stream -> (live count per push, seconds per push, seconds of the cover step of each push that ran one)"""
+    ct = drivers.CoverTracker(m, drivers.Cover(cell=32, scan=scan), None, iters=6, slots=SLOTS, rounds="library")
+    steps = []
+    real = ct.book.step
+
+    def timed_step(*a):
+        steps.append(timed(lambda: real(*a)))
+
+    ct.book.step = timed_step
+    live, ts = [], []
+    for c in chunks(host):
+        ts.append(timed(lambda: ct.push(c)))
+        live.append(len(ct.book.ids))
+    ct.finish()
+    torch.cuda.synchronize()
+    return live, ts, steps[1:]                                         # (steps[0]: the first step, inside the first push)
+
+
+def compare_cover(dev, reps):
+    host = frames(0, CHURN_T)
+    m = model(dev)
+    scans = ("torch", "library")
+    got = {k: [] for k in scans}
+    for k in scans:                                                     # warm-up: weights, workspaces, the allocator's pools
+        cover_run(m, host, k)
+    for _ in range(reps):
+        for k in scans:
+            got[k].append(cover_run(m, host, k))
+    live = got["torch"][0][0]
+    assert all(r[0] == live for rows in got.values() for r in rows), "the two scans kept different queries"
+    res = {"config": "360x640 stride 4, no caller queries, cell 32 (12 x 20), chunks of 16, slots 24, library rounds", "T": CHURN_T,
+           "pushes": len(live), "live_per_push": live}
+    for k, rows in got.items():
+        res[f"{k}_push_ms"] = round(statistics.median(t for r in rows for t in r[1][2:]) * 1e3, 2)
+        res[f"{k}_step_ms"] = round(statistics.median(t for r in rows for t in r[2]) * 1e3, 3)
+    return res
+
+
 def model(dev):
     m = Pips(S=8, stride=STRIDE)
     m.load_state_dict(init_state_dict(0, tamed=True))
@@ -175,8 +218,12 @@ def main():
     ap.add_argument("--only", default="all", choices=["all", "stream"], help="stream: time the stream alone (kernel trace)")
     ap.add_argument("--rounds", action="store_true", help='time rounds="torch" against rounds="library" and nothing else')
     ap.add_argument("--churn", action="store_true", help="queries added and removed at every push against added only, and nothing else")
+    ap.add_argument("--cover", action="store_true", help='a covered stream under scan="torch" against scan="library", and nothing else')
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.cover:
+        print(json.dumps(compare_cover(dev, a.reps)))
+        return
     q = queries(dev)
     if a.churn:
         print(json.dumps(compare_churn(dev, q, a.reps)))
