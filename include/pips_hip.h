@@ -106,7 +106,8 @@ const char* pips_last_error(void);
  * pips_stream_workspace_bytes_clips and pips_stream_emit_cols (several streamed videos on one flat cache of rings: one state and
  * one round for all of them); pips_stream_keep (queries leave a running stream: the kept columns of the state in narrower
  * arrays); pips_cover_step and pips_cover_workspace_bytes (which queries of a stream are retired and where new ones are seeded, so
- * that a bounded set of tracks stays spread over the frame). */
+ * that a bounded set of tracks stays spread over the frame); pips_corner_table and pips_cover_place (the best corner of each
+ * cover cell of each frame, and the seeds of a cover step moved from the cell centres onto them). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -479,6 +480,30 @@ int    pips_cover_step(int n, int m, int f1, const float* trajs, const float* vi
                        const int* lost, int H, int W, int cell, float vis_logit, int lost_after, int max_queries,
                        int* keep, int* lost_out, float* seeds, int* counts,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* Seeding on corners: pips_corner_table looks at the pixels of F frames (F,3,h,w), planar, uint8 (src_is_u8 != 0) or float32 with
+ * values 0..255 (finite), and writes table (F,gh,gw,3) = (x, y, S) -- the most trackable pixel of each cell of pips_cover_step's
+ * grid (gh = (h-1)/cell + 1 rows, gw likewise) and its score.  Everything up to the argmax is integer arithmetic:
+ *  - a float channel is quantised as u = floor(min(max(v, 0), 255) + 0.5); luma Y = (77 R + 150 G + 29 B + 128) >> 8;
+ *  - gx = Y[y][x+1] - Y[y][x-1], gy = Y[y+1][x] - Y[y-1][x]; over the 7x7 window centred on the pixel a = sum gx^2, b = sum gx gy,
+ *    c = sum gy^2 (int32); S = a + c - ceil(sqrt((a-c)^2 + 4 b^2)), the root exact (int64): twice the smaller eigenvalue of the
+ *    structure tensor rounded down, 0 <= S <= 6 372 450, exact as a float;
+ *  - the candidates are the pixels with 4 <= x <= w-5 and 4 <= y <= h-5 (every read lies inside the frame); cell (i, j) covers
+ *    rows [i cell, (i+1) cell) and columns [j cell, (j+1) cell) clipped to the frame, and its entry is the candidate with the
+ *    largest S -- among equals the lowest y, then the lowest x;
+ *  - a cell without a candidate holds pips_cover_step's centre (min((j + 0.5) cell, w-1), min((i + 0.5) cell, h-1)) and S = -1.
+ * With an unweighted window the best pixel of a sharp corner lies about 2 px inside it, not on it.
+ * pips_cover_place moves the k seeds (t, x, y) that pips_cover_step wrote for frame t onto table_of_frame (gh,gw,3), the part of
+ * the table that belongs to frame t: a seed belongs to cell (min(int(floor(y / cell)), gh-1), min(int(floor(x / cell)), gw-1)),
+ * the fp32 quotient of pips_cover_step (it finds the cell of a clamped centre too), and takes that entry's (x, y) if its S >
+ * min_corner; otherwise it stays where it is.  t is not looked at; the number and the order of the seeds do not change.
+ * PIPS_E_ARG ahead of any launch: F < 0, k < 0, h or w < 1, cell < 8, min_corner < 0, a NULL pointer, a frame of more than
+ * INT_MAX pixels, more than PIPS_CORNER_BLOCKS_MAX cells in all frames of a call (a launch takes at most 2^32 threads, a cell
+ * is a block of 256: split the chunk).  A rejected call writes nothing; F = 0 and k = 0 launch nothing and return
+ * PIPS_OK.  One launch each -- a 256-thread block per (frame, cell) / a thread per seed; no atomics, no workspace, no
+ * allocation, no synchronisation. */
+#define PIPS_CORNER_BLOCKS_MAX ((1 << 24) - 1)
+int    pips_corner_table(const void* frames, int src_is_u8, int F, int h, int w, int cell, float* table, void* stream);
+int    pips_cover_place(float* seeds, int k, const float* table_of_frame, int h, int w, int cell, int min_corner, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 

@@ -1726,6 +1726,27 @@ int pips_cover_step(int n, int m, int f1, const float* trajs, const float* vis, 
                              seeds, counts, (int*)workspace, (hipStream_t)stream);
 }
 
+// ---- seeding on corners
+int pips_corner_table(const void* frames, int src_is_u8, int F, int h, int w, int cell, float* table, void* stream) {
+    PIPS_CHECK_ARG(F >= 0, "corner_table: need F >= 0 (F=%d)", F);
+    PIPS_CHECK_ARG(cell >= 8 && h >= 1 && w >= 1, "corner_table: need cell >= 8 and a frame of at least 1x1 (cell=%d, h=%d, w=%d)", cell, h, w);
+    PIPS_CHECK_ARG((long long)h * w <= INT_MAX, "corner_table: a frame of %d x %d has more than %d pixels", h, w, INT_MAX);
+    const int gh = (h - 1) / cell + 1, gw = (w - 1) / cell + 1;
+    PIPS_CHECK_ARG((long long)F * gh * gw <= PIPS_CORNER_BLOCKS_MAX, "corner_table: %d frames of %d x %d cells are more than %d blocks", F, gh, gw,
+                   PIPS_CORNER_BLOCKS_MAX);
+    PIPS_CHECK_ARG(frames && table, "corner_table: null pointer");
+    if (F == 0) return PIPS_OK;
+    return launch_corner_table(frames, src_is_u8 != 0, F, h, w, cell, gh, gw, table, (hipStream_t)stream);
+}
+int pips_cover_place(float* seeds, int k, const float* table_of_frame, int h, int w, int cell, int min_corner, void* stream) {
+    PIPS_CHECK_ARG(k >= 0, "cover_place: need k >= 0 (k=%d)", k);
+    PIPS_CHECK_ARG(cell >= 8 && h >= 1 && w >= 1, "cover_place: need cell >= 8 and a frame of at least 1x1 (cell=%d, h=%d, w=%d)", cell, h, w);
+    PIPS_CHECK_ARG(min_corner >= 0, "cover_place: need min_corner >= 0 (min_corner=%d)", min_corner);
+    PIPS_CHECK_ARG(seeds && table_of_frame, "cover_place: null pointer");
+    if (k == 0) return PIPS_OK;
+    return launch_cover_place(seeds, k, table_of_frame, (h - 1) / cell + 1, (w - 1) / cell + 1, cell, min_corner, (hipStream_t)stream);
+}
+
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;

@@ -508,4 +508,9 @@ int launch_cover_step(int n, int m, int f1, const float* trajs, const float* vis
                       int H, int W, int cell, int gh, int gw, float vis_logit, int lost_after, int max_queries, int* keep,
                       int* lost_out, float* seeds, int* counts, int* workspace, hipStream_t st);
 
+// ---- corners.hip: the best corner of each cover cell of each frame (pips_corner_table) and the seeds of a cover step moved onto
+// them (pips_cover_place).  table: (F,gh,gw,3) = (x, y, score) / (gh,gw,3) of one frame; arguments checked by the caller.
+int launch_corner_table(const void* frames, int src_u8, int F, int h, int w, int cell, int gh, int gw, float* table, hipStream_t st);
+int launch_cover_place(float* seeds, int k, const float* table, int gh, int gw, int cell, int min_corner, hipStream_t st);
+
 }  // namespace pips

@@ -20,7 +20,8 @@
   stream together, and each stream gets what its own ``StreamTracker`` returns, bit for bit.
 * ``CoverTracker`` / ``track_cover`` (and ``MultiStreamTracker(cover=)``) -- a ``StreamTracker`` that decides which queries it tracks:
   a ``Cover`` policy retires the queries that left the frame or stayed invisible and seeds the empty cells of a grid over the
-  frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``).
+  frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``).  ``Cover(seed="corners")`` puts each seed on
+  the most trackable pixel of its cell (``corner_table_torch`` / ``pips_corner_table``); ``corner_queries`` is the offline form.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -726,6 +727,7 @@ def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, e
 # ---------------------------------------------------------------------------------------------- keeping the frame covered
 _INT_MAX = 2 ** 31 - 1
 COVER_SCANS = ("torch", "library")
+COVER_SEEDS = ("centre", "corners")
 
 
 def _whole(x, what, low):
@@ -749,9 +751,16 @@ class Cover:
         order, as long as the stream has fewer than ``max_queries`` (``None``: no cap).
     The full rule is pips_cover_step's in include/pips_hip.h.  ``scan="torch"`` performs the step as torch ops (``cover_scan``; it
     also runs on CPU tensors); ``scan="library"`` makes one ``pips_cover_step`` call and reads its four counts -- the kept list and
-    the seeds come to the host only when the counts say that something changed.  Both give the same queries and the same bits."""
+    the seeds come to the host only when the counts say that something changed.  Both give the same queries and the same bits.
+    ``seed="corners"`` moves each seed from the centre of its cell to the most trackable pixel of that cell on the seed's own frame
+    -- the largest smaller eigenvalue of the 7x7 structure tensor of the 8-bit luma, the integer rule of pips_corner_table in
+    include/pips_hip.h -- where that score is above ``min_corner`` (a whole number >= 0); a cell that is flat by that measure keeps
+    the centre, so which cells are seeded, how many and in which order stay what ``seed="centre"`` (the default) gives.  The table
+    of best corners comes from ``corner_table_torch`` / ``cover_place_torch`` under ``scan="torch"`` and from one ``pips_corner_table``
+    call per pushed chunk and one ``pips_cover_place`` call per step under ``scan="library"``: the same bits again.  With an
+    unweighted window the chosen pixel of a sharp corner lies about 2 px inside it."""
 
-    def __init__(self, cell=32, vis_thr=0.5, lost_after=4, max_queries=None, scan="torch"):
+    def __init__(self, cell=32, vis_thr=0.5, lost_after=4, max_queries=None, scan="torch", seed="centre", min_corner=0):
         self.cell = _whole(cell, "cell", 8)
         if isinstance(vis_thr, bool) or not isinstance(vis_thr, (int, float)) or not 0.0 < vis_thr < 1.0:
             raise ValueError(f"vis_thr must lie in (0, 1), not {vis_thr!r}")
@@ -763,10 +772,28 @@ class Cover:
         if scan not in COVER_SCANS:
             raise ValueError(f"scan must be one of {COVER_SCANS}, not {scan!r}")
         self.scan = scan
+        if not isinstance(seed, str) or seed not in COVER_SEEDS:
+            raise ValueError(f"seed must be one of {COVER_SEEDS}, not {seed!r}")
+        self.seed = seed
+        self.min_corner = _whole(min_corner, "min_corner", 0)
 
     def grid(self, H, W):
         """(rows, columns) of the cells over an H x W frame"""
         return (H - 1) // self.cell + 1, (W - 1) // self.cell + 1
+
+    def table(self, frames, dev=None):
+        """the best corner of each cell of each of the frames (F,3,H,W), uint8 or float 0..255, by the chosen scan -> (F,gh,gw,3) =
+        (x, y, score) on ``dev`` (None: where the frames lie; the GPU under ``scan="library"``).  Host frames are copied to ``dev`` once"""
+        if self.scan == "library":
+            return ops.corner_table(frames if frames.is_cuda else frames.to("cuda" if dev is None else dev), self.cell)
+        return corner_table_torch(frames if dev is None else frames.to(dev), self.cell)
+
+    def place(self, seeds, table, H, W):
+        """the seeds (k,3) of a cover step on the frame whose table (gh,gw,3) this is, by the chosen scan -> the seeds on their
+        corners (``scan="library"`` moves them in place)"""
+        if self.scan == "library":
+            return ops.cover_place(seeds.contiguous(), table, H, W, self.cell, self.min_corner)
+        return cover_place_torch(seeds, table, H, W, self.cell, self.min_corner)
 
     def step(self, trajs, vis, f1, tq, xy, lost, H, W):
         """one cover step by the chosen scan -> (keep (n_keep) ints, lost_out (n_keep) int32, seeds (n_seed,3), the four counts
@@ -812,15 +839,77 @@ def cover_scan(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, 
     return keep.to(torch.int32), run[keep], seeds, [keep.numel(), empty.numel(), int(outside.sum()), int(gone.sum())]
 
 
+def corner_table_torch(frames, cell):
+    """pips_corner_table (include/pips_hip.h) as int64 torch ops, on any device: frames (F,3,h,w), uint8 or float 0..255 -> table
+    (F,gh,gw,3) float32 = (x, y, S), the candidate with the largest S of each cell -- the lowest y, then the lowest x among equals --
+    or the cell's centre and -1 where a cell has no candidate.  Integer arithmetic up to the argmax: the same bits as the kernel."""
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"frames must be (F,3,h,w), not {tuple(frames.shape)}")
+    cell = int(cell)
+    F, _, h, w = frames.shape
+    gh, gw, dev = (h - 1) // cell + 1, (w - 1) // cell + 1, frames.device
+    key = torch.full((F, gh * cell, gw * cell), -1, dtype=torch.int64, device=dev)      # -1: no candidate
+    if F > 0 and h >= 9 and w >= 9:
+        if frames.dtype == torch.uint8:
+            u = frames.to(torch.int64)
+        else:                                           # (as ops.corner_table: anything but uint8 goes through float32)
+            u = (frames.to(torch.float32).clamp(0.0, 255.0) + 0.5).floor().to(torch.int64)
+        Y = (77 * u[:, 0] + 150 * u[:, 1] + 29 * u[:, 2] + 128) >> 8
+        gx = Y[:, 1:-1, 2:] - Y[:, 1:-1, :-2]                                          # pixel (y, x) at [y - 1, x - 1]
+        gy = Y[:, 2:, 1:-1] - Y[:, :-2, 1:-1]
+
+        def window(p):                                                                # 7x7 sums: pixel (y, x) at [y - 4, x - 4]
+            p = sum(p[:, :, k:k + w - 8] for k in range(7))
+            return sum(p[:, k:k + h - 8] for k in range(7))
+
+        a, b, c = window(gx * gx), window(gx * gy), window(gy * gy)
+        d = (a - c) ** 2 + 4 * b * b                                                   # < 2^53: exact as a double
+        r = d.to(torch.float64).sqrt().to(torch.int64)
+        r = torch.where(r * r > d, r - 1, r)
+        r = torch.where((r + 1) * (r + 1) <= d, r + 1, r)                             # floor(sqrt(d)), exactly
+        S = a + c - (r + (r * r < d).to(torch.int64))
+        ys = torch.arange(4, h - 4, device=dev).unsqueeze(1)
+        xs = torch.arange(4, w - 4, device=dev).unsqueeze(0)
+        # S above the complement of the pixel's index: one max per cell picks the largest S, then the lowest y, then the lowest x
+        key[:, 4:h - 4, 4:w - 4] = (S << 32) | (0xFFFFFFFF - (ys * w + xs))
+    best = key.view(F, gh, cell, gw, cell).permute(0, 1, 3, 2, 4).reshape(F, gh, gw, cell * cell).amax(dim=3)
+    at = 0xFFFFFFFF - (best & 0xFFFFFFFF)
+    i = torch.arange(gh, device=dev, dtype=torch.float32).view(1, gh, 1).expand(F, gh, gw)
+    j = torch.arange(gw, device=dev, dtype=torch.float32).view(1, 1, gw).expand(F, gh, gw)
+    none = best < 0
+    x = torch.where(none, ((j + 0.5) * cell).clamp(max=float(w - 1)), (at % w).to(torch.float32))
+    y = torch.where(none, ((i + 0.5) * cell).clamp(max=float(h - 1)), torch.div(at, w, rounding_mode="floor").to(torch.float32))
+    return torch.stack([x, y, torch.where(none, torch.full_like(x, -1.0), (best >> 32).to(torch.float32))], dim=3)
+
+
+def cover_place_torch(seeds, table, H, W, cell, min_corner):
+    """pips_cover_place as torch ops, on any device: seeds (k,3) = (t, x, y) of a cover step and the table (gh,gw,3) of their frame
+    -> new seeds, each on the corner of its cell where that scores above ``min_corner`` and where it was otherwise"""
+    gh, gw = (int(H) - 1) // int(cell) + 1, (int(W) - 1) // int(cell) + 1
+
+    def cell_of(v, g):                                                                # cover_scan's quotient; no position: cell 0
+        q = torch.div(v, float(cell)).floor()
+        return torch.where(q >= 0, q, torch.zeros_like(q)).clamp(max=float(g - 1)).to(torch.int64)
+
+    e = table[cell_of(seeds[:, 2], gh), cell_of(seeds[:, 1], gw)]
+    use = (e[:, 2] > float(min_corner)).unsqueeze(1)
+    return torch.cat([seeds[:, :1], torch.where(use, e[:, :2], seeds[:, 1:])], dim=1)
+
+
 class _CoverBook:
     """What a covered stream keeps per query beside the tracker's own state: the identity of each column (``ids``), the frame of
     each identity (``born``), identity -> (frame, reason) of the retired ones (``retired``), their hop lists (``hops``, when recorded)
     and, on the device, the arrays a cover step reads -- ``tq`` / ``lost`` (n) int32 and ``xy`` (n,2).  ``start`` runs the first step
     (no rows: every query is pending and the seeds land on frame 0), ``step`` the one after a push; both act on the tracker
-    through ``add(queries (1,k,3))`` and ``remove(columns)``."""
+    through ``add(queries (1,k,3))`` and ``remove(columns)``.
+    Under ``seed="corners"`` the book also keeps ``table`` (T - table0, gh, gw, 3), the best corners of the frames ``[table0, T)``
+    that were pushed and not yet returned when the last push began -- ``see`` takes the frames of a push before they are encoded
+    -- and ``held``: the ``(frame, seeds)`` of a step whose frame was not pushed yet.  Held seeds have no column and no identity;
+    the ``see`` that brings their frame places and adds them before anything of that push is encoded."""
 
     def __init__(self, cover, tq_host, record_hops):
         self.cover, self.size = cover, None
+        self.corners, self.table, self.table0, self.T, self.held = cover.seed == "corners", None, 0, 0, None
         self.ids, self.born, self.retired = list(range(tq_host.numel())), tq_host.tolist(), {}
         self.hops = {} if record_hops else None
 
@@ -828,6 +917,8 @@ class _CoverBook:
         self.size = (int(H), int(W))
         self.tq, self.xy = tq_host.to(dev, torch.int32), xy.to(dev, torch.float32).contiguous()
         self.lost = torch.zeros_like(self.tq)
+        if self.corners:
+            self.table = self.xy.new_empty((0,) + self.cover.grid(int(H), int(W)) + (3,))
         n = self.tq.numel()
         self.step(0, self.xy.new_empty(0, n, 2), self.xy.new_empty(0, n), add, remove, None)
 
@@ -852,13 +943,37 @@ class _CoverBook:
             self.tq, self.xy = self.tq[k], self.xy[k]
         self.lost = lost_out
         if counts[1] > 0:                                                         # and so do the seeds
-            k = counts[1]
-            add(seeds.unsqueeze(0))
-            self.ids += list(range(len(self.born), len(self.born) + k))
-            self.born += [f1] * k
-            self.tq = torch.cat([self.tq, torch.full((k,), f1, dtype=torch.int32, device=self.tq.device)])
-            self.xy = torch.cat([self.xy, seeds[:, 1:]])
-            self.lost = torch.cat([self.lost, torch.zeros(k, dtype=torch.int32, device=self.tq.device)])
+            if not self.corners:
+                self._seed(f1, seeds, add)
+            elif f1 < self.T:
+                self._seed(f1, self.cover.place(seeds, self.table[f1 - self.table0], H, W), add)
+            else:                                                                     # their frame comes with a later push
+                assert self.held is None and f1 == self.T
+                self.held = (f1, seeds)
+
+    def _seed(self, f1, seeds, add):
+        """the seeds (k,3) on frame f1 become queries: the columns and identities behind the present ones"""
+        k = seeds.shape[0]
+        add(seeds.unsqueeze(0))
+        self.ids += list(range(len(self.born), len(self.born) + k))
+        self.born += [f1] * k
+        self.tq = torch.cat([self.tq, torch.full((k,), f1, dtype=torch.int32, device=self.tq.device)])
+        self.xy = torch.cat([self.xy, seeds[:, 1:]])
+        self.lost = torch.cat([self.lost, torch.zeros(k, dtype=torch.int32, device=self.tq.device)])
+
+    def see(self, frames, emitted, add):
+        """``seed="corners"``: the frames (k,3,H,W) that a push is about to encode, ``[0, emitted)`` having been returned.  One table
+        call for the chunk; the tables of the returned frames go; seeds held for the first of these frames are placed and added"""
+        k = frames.shape[0]
+        if k == 0:
+            return
+        new = self.cover.table(frames, self.tq.device)
+        self.table = torch.cat([self.table[emitted - self.table0:], new])
+        first, self.table0, self.T = self.T, emitted, self.T + k
+        if self.held is not None:
+            (f1, seeds), self.held = self.held, None
+            assert f1 == first
+            self._seed(f1, self.cover.place(seeds, self.table[f1 - self.table0], *self.size), add)
 
     def all_hops(self, live):
         """hop lists by identity: the saved ones of the retired queries and ``live``, those of the present columns"""
@@ -894,7 +1009,10 @@ class CoverTracker:
     tracked, retired and counted like the seeds.  ``push(frames)`` / ``finish()`` return ``(f0, trajs (1,m,n,2), vis (1,m,n), ids
     (n,))``: ``ids`` is the identity of each returned column (host int64) -- the caller's queries first, then the seeds in order
     of creation; an identity never changes and is never reused.  The first cover step runs inside the first ``push``, before
-    anything is encoded (the frame size is known then): it seeds frame 0.  A cover step then runs at the end of every ``push``
+    anything is encoded (the frame size is known then): it seeds frame 0.  (Under ``Cover(seed="corners")`` seeds whose frame was
+    not pushed yet -- these, and those of a stream that lost every query at once -- wait for the ``push`` that brings that frame, are
+    placed on its corners and join at its start, with the columns and identities they would have had; ``finish()`` drops them.)
+    A cover step then runs at the end of every ``push``
     that returned at least one frame, on those frames, and retires and seeds for the pushes that follow; ``finish()`` runs none.
     ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost")`` the last frame returned for it and why,
     ``hops`` (``record_hops=True``) the hop list of each identity.  Over its life an identity is what ``track_stream`` given that
@@ -924,6 +1042,10 @@ class CoverTracker:
             st.push(frames[:, :0])                 # no frame: the ring and the state are made, the device is known
             self.book.start(frames.shape[3], frames.shape[4], st.cache.device, st.tq_host, st.xy_in, st.add_queries,
                             st.remove_queries)
+        if tuple(frames.shape[3:]) != self.book.size:
+            raise ValueError(f"frames of {tuple(frames.shape[3:])} pushed to a stream of {self.book.size}")
+        if self.book.corners:
+            self.book.see(frames[0], st.emitted, st.add_queries)
         ids = self.ids
         f0, trajs, vis = st.push(frames)
         if trajs.shape[1] > 0:
@@ -932,6 +1054,7 @@ class CoverTracker:
 
     @torch.no_grad()
     def finish(self):
+        self.book.held = None                      # (seeds held for a frame that never comes)
         ids = self.ids
         return self.st.finish() + (ids,)
 
@@ -946,6 +1069,21 @@ def track_cover(model, chunks, cover, queries=None, iters=6, slots=24, return_ho
     parts.append(ct.finish())
     out = _by_identity(parts, ct.book)
     return out + (ct.hops,) if return_hops else out
+
+
+def corner_queries(rgbs, t=0, cell=32, min_corner=0, scan="torch"):
+    """Queries for ``track_queries`` on the corners of frame ``t`` of rgbs (1,T,3,H,W): one per cell of the ``cell`` x ``cell`` grid
+    whose best corner scores above ``min_corner`` (``Cover(seed="corners")``'s table and rule), in row-major order -> (1,K,3) =
+    (t, x, y).  A flat cell gets none.  ``scan="torch"`` works where ``rgbs`` lies, ``scan="library"`` on the GPU."""
+    cover = Cover(cell=cell, scan=scan, seed="corners", min_corner=min_corner)
+    if rgbs.dim() != 5 or rgbs.shape[0] != 1 or rgbs.shape[2] != 3:
+        raise ValueError(f"rgbs must be (1,T,3,H,W), not {tuple(rgbs.shape)}")
+    t = _whole(t, "t", 0)
+    if t >= rgbs.shape[1]:
+        raise ValueError(f"frame {t} of a video of {rgbs.shape[1]} frames")
+    e = cover.table(rgbs[0, t:t + 1])[0].reshape(-1, 3)
+    e = e[e[:, 2] > float(cover.min_corner)]
+    return torch.cat([torch.full_like(e[:, :1], float(t)), e[:, :2]], dim=1).unsqueeze(0)
 
 
 # ---------------------------------------------------------------------------------------------- several streams at once
@@ -1115,7 +1253,9 @@ class MultiStreamTracker:
     first cover step runs inside the first ``push``, and a step runs on the part of a stream that a ``push`` returned and acts
     through ``remove_queries(v, .)`` / ``add_queries(v, .)``, which are then the cover's alone (ValueError for a caller).  ``push`` and
     ``finish`` return ``(f0, trajs, vis, ids)`` per stream, ``ids`` being the identity of each column as ``CoverTracker`` numbers
-    them; ``books[v]`` holds ``born`` / ``retired`` of stream v and ``cover_hops(v)`` its hop lists by identity."""
+    them; ``books[v]`` holds ``born`` / ``retired`` of stream v and ``cover_hops(v)`` its hop lists by identity.  Under
+    ``Cover(seed="corners")`` a push makes one corner table per stream that got a chunk, and the first seeds of a stream whose first
+    chunk is ``None`` wait for its first frames, as in ``CoverTracker``."""
 
     S = 8
 
@@ -1250,6 +1390,9 @@ class MultiStreamTracker:
                 cols = self.columns(v)
                 self.books[v].start(*size, self.cache.device, self.tq_host[cols], self.xy_in[cols.to(self.xy_in.device)],
                                     *self._cover_acts(v))
+        for v, c in enumerate(chunks if self.cover is not None and self.cover.seed == "corners" else []):
+            if c is not None:                                                     # the tables of what this push brings
+                self.books[v].see(c[0], self.emitted[v], self._cover_acts(v)[0])
         ids = None if self.cover is None else [self.stream_ids(v) for v in range(self.V)]
         f0, outs = list(self.emitted), [[] for _ in range(self.V)]
         left = [0 if c is None else c.shape[1] for c in chunks]
@@ -1292,6 +1435,8 @@ class MultiStreamTracker:
         f0, outs = list(self.emitted), [[] for _ in range(self.V)]
         for u in which:
             self.finished[u] = True
+            if self.cover is not None:
+                self.books[u].held = None          # (seeds held for a frame that never comes)
             if self.cache is not None:
                 self.state.end(u)
         if self.cache is not None and which:

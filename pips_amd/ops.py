@@ -483,6 +483,39 @@ def cover_step(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, 
     return keep, lost_out, seeds, counts
 
 
+def corner_table(frames, cell):
+    """pips_corner_table on device frames (F,3,h,w), uint8 or float 0..255 -> table (F,gh,gw,3) float32 = (x, y, S): the best
+    corner of each cover cell of each frame and its score; a cell without a candidate holds its centre and -1 (include/pips_hip.h)."""
+    assert frames.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"frames must be (F,3,h,w), not {tuple(frames.shape)}")
+    src = frames.contiguous() if frames.dtype == torch.uint8 else _f32(frames)
+    F, _, h, w = src.shape
+    gh, gw = (h - 1) // int(cell) + 1, (w - 1) // int(cell) + 1
+    table = torch.empty(F, gh, gw, 3, dtype=torch.float32, device=src.device)
+    if F == 0:                                                                    # (an empty tensor has no pointer to pass)
+        return table
+    with torch.cuda.device(src.device):
+        _call("pips_corner_table", _lib.ptr(src), 1 if src.dtype == torch.uint8 else 0, F, h, w, int(cell), _lib.ptr(table), _stream())
+    return table
+
+
+def cover_place(seeds, table, h, w, cell, min_corner):
+    """pips_cover_place: the seeds (k,3) = (t, x, y) of a cover step, float32 and contiguous, are moved IN PLACE onto the corners
+    of ``table`` (gh,gw,3), the table of the seeds' frame, where the cell's score is above ``min_corner`` -> seeds"""
+    assert seeds.is_cuda and table.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    gh, gw = (int(h) - 1) // int(cell) + 1, (int(w) - 1) // int(cell) + 1
+    if seeds.dtype != torch.float32 or not seeds.is_contiguous() or seeds.dim() != 2 or seeds.shape[1] != 3:
+        raise ValueError("seeds must be a contiguous float32 (k,3) tensor")
+    if table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape) != (gh, gw, 3):
+        raise ValueError(f"table must be a contiguous float32 ({gh},{gw},3) tensor, not {tuple(table.shape)}")
+    if seeds.shape[0] == 0:
+        return seeds
+    with torch.cuda.device(seeds.device):
+        _call("pips_cover_place", _lib.ptr(seeds), seeds.shape[0], _lib.ptr(table), int(h), int(w), int(cell), int(min_corner), _stream())
+    return seeds
+
+
 def gemm(A, W, bias=None, epi=0, R=None):
     """C = epi(A @ W.T + bias).  epi: 0 none, 1 GELU, 2 + R."""
     A, W = _f32(A), _f32(W)

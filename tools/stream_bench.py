@@ -20,7 +20,9 @@ the round workspace of the widest state it has served).
 ``--cover``: instead, a ``CoverTracker(rounds="library")`` over T = 400 frames of the same config that starts from no query of the
 caller's: cells of 32 px (a 12 x 20 grid), default policy, ``scan="torch"`` against ``scan="library"``.  Prints the live count per
 push (the same under both scans: checked), and per scan the median push time and the median time of the cover step alone (the
-tracker's ``book.step`` timed with a device synchronisation on either side).  One warm-up of each, then --reps of each, alternating."""
+tracker's ``book.step`` timed with a device synchronisation on either side).  One warm-up of each, then --reps of each, alternating.
+``--seed corners`` seeds on corners (``Cover(seed="corners")``: one corner table per pushed chunk, the seeds of a step placed on it)
+instead of on the cell centres (``--min-corner``: the score a corner needs); frames per second (T over the summed push times, the median over the runs) is printed per scan."""
 import argparse
 import json
 import os
@@ -165,9 +167,9 @@ def compare_churn(dev, q, reps):
     return res
 
 
-def cover_run(m, host, scan):
+def cover_run(m, host, scan, seed="centre", min_corner=0):
     """one covered stream -> (live count per push, seconds per push, seconds of the cover step of each push that ran one)"""
-    ct = drivers.CoverTracker(m, drivers.Cover(cell=32, scan=scan), None, iters=6, slots=SLOTS, rounds="library")
+    ct = drivers.CoverTracker(m, drivers.Cover(cell=32, scan=scan, seed=seed, min_corner=min_corner), None, iters=6, slots=SLOTS, rounds="library")
     steps = []
     real = ct.book.step
 
@@ -184,23 +186,24 @@ def cover_run(m, host, scan):
     return live, ts, steps[1:]                                         # (steps[0]: the first step, inside the first push)
 
 
-def compare_cover(dev, reps):
+def compare_cover(dev, reps, seed="centre", min_corner=0):
     host = frames(0, CHURN_T)
     m = model(dev)
     scans = ("torch", "library")
     got = {k: [] for k in scans}
     for k in scans:                                                     # warm-up: weights, workspaces, the allocator's pools
-        cover_run(m, host, k)
+        cover_run(m, host, k, seed, min_corner)
     for _ in range(reps):
         for k in scans:
-            got[k].append(cover_run(m, host, k))
+            got[k].append(cover_run(m, host, k, seed, min_corner))
     live = got["torch"][0][0]
     assert all(r[0] == live for rows in got.values() for r in rows), "the two scans kept different queries"
     res = {"config": "360x640 stride 4, no caller queries, cell 32 (12 x 20), chunks of 16, slots 24, library rounds", "T": CHURN_T,
-           "pushes": len(live), "live_per_push": live}
+           "seed": seed, "min_corner": min_corner, "pushes": len(live), "live_per_push": live}
     for k, rows in got.items():
         res[f"{k}_push_ms"] = round(statistics.median(t for r in rows for t in r[1][2:]) * 1e3, 2)
         res[f"{k}_step_ms"] = round(statistics.median(t for r in rows for t in r[2]) * 1e3, 3)
+        res[f"{k}_frames_per_s"] = round(statistics.median(CHURN_T / sum(r[1]) for r in rows), 1)
     return res
 
 
@@ -219,10 +222,13 @@ def main():
     ap.add_argument("--rounds", action="store_true", help='time rounds="torch" against rounds="library" and nothing else')
     ap.add_argument("--churn", action="store_true", help="queries added and removed at every push against added only, and nothing else")
     ap.add_argument("--cover", action="store_true", help='a covered stream under scan="torch" against scan="library", and nothing else')
+    ap.add_argument("--seed", default="centre", choices=list(drivers.COVER_SEEDS), help="with --cover: where in a cell a seed lands")
+    ap.add_argument("--min-corner", type=int, default=0, help="with --seed corners: the score a corner needs (above 6372450: the tables "
+                    "are made and every seed stays on its centre, which prices the tables alone)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.cover:
-        print(json.dumps(compare_cover(dev, a.reps)))
+        print(json.dumps(compare_cover(dev, a.reps, a.seed, a.min_corner)))
         return
     q = queries(dev)
     if a.churn:
