@@ -107,7 +107,8 @@ const char* pips_last_error(void);
  * one round for all of them); pips_stream_keep (queries leave a running stream: the kept columns of the state in narrower
  * arrays); pips_cover_step and pips_cover_workspace_bytes (which queries of a stream are retired and where new ones are seeded, so
  * that a bounded set of tracks stays spread over the frame); pips_corner_table and pips_cover_place (the best corner of each
- * cover cell of each frame, and the seeds of a cover step moved from the cell centres onto them). */
+ * cover cell of each frame, and the seeds of a cover step moved from the cell centres onto them); pips_cover_step_thin and
+ * pips_cover_thin_workspace_bytes (the cover step with at most per_cell tracks in a cell: the youngest surplus are retired). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -480,6 +481,42 @@ int    pips_cover_step(int n, int m, int f1, const float* trajs, const float* vi
                        const int* lost, int H, int W, int cell, float vis_logit, int lost_after, int max_queries,
                        int* keep, int* lost_out, float* seeds, int* counts,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The thin cover step: pips_cover_step with a cap of per_cell tracks in a cell.  Tracks that lose their surface slide onto a
+ * neighbour and ride along with it; pips_cover_step re-seeds the cell they left and never removes the duplicates where they
+ * arrive.  pips_cover_step_thin extends that rule and replaces none of it.  In its notation (rows of frames [f1 - m, f1), f =
+ * f1 - 1, the gh x gw grid, the fp32 quotient, the inside test 0 <= x <= W-1 && 0 <= y <= H-1 that NaN and +-inf fail):
+ *  1. pending, the flags OUTSIDE and LOST and the run `lost` are exactly pips_cover_step's;
+ *  2. a query COUNTS on a returned frame g when it is not pending, tq <= g, it is not flagged outside or lost in this step and
+ *     its position trajs[g] passes the inside test; its cell on g is (min(int(floor(y / cell)), gh-1), min(int(floor(x / cell)), gw-1));
+ *  3. a counting query j is SURPLUS on g when at least per_cell counting queries i < j stand in j's cell on g -- columns are in
+ *     order of creation, so the lower column is the older identity; a query that does not count on g is not surplus on g;
+ *  4. a second run is carried from push to push beside `lost`: over the returned frames g >= tq in order, run = surplus ? run + 1
+ *     : 0, starting from crowd[c]; it is 0 for a pending query;
+ *  5. a started query that is neither outside nor lost is retired as CROWDED when that run >= crowd_after;
+ *  6. occupancy, the seeds, their row-major order and the cap are pips_cover_step's with "kept" also excluding the crowded: a
+ *     crowded query that stood alone in its cell on f frees that cell for a seed of this very step, and the cap is max(0,
+ *     max_queries - n_keep) with the new n_keep.
+ * The rule is NOT greedy: an elder counts on a row even when it is itself retired as crowded in this step (only outside and lost
+ * take it out of the count), so the rank by age is well defined without a sequential pass over the queries.  The rule is per cell,
+ * not per distance: seeds go only into empty cells, so a seed is never surplus where it is born.  Its known limit: two tracks 1 px
+ * apart on either side of a cell border are not merged.  With per_cell = INT_MAX nobody is surplus and keep, lost_out, seeds and
+ * the first four counts are pips_cover_step's bit for bit.
+ * crowd (n) is the second run of each query (0 for a new one), crowd_out[0..n_keep) that of the kept, aligned with keep and
+ * lost_out.  gone[0..n - n_keep) receives the retired columns, ascending, and reason[.] why: 1 outside, 2 lost, 3 crowded (the
+ * precedence in that order).  counts = {n_keep, n_seed, n_outside, n_lost, n_crowded}.  keep, lost_out, crowd_out, gone and reason
+ * need room for n ints each; the elements behind the counts are not written; every input stays bit-identical.
+ * PIPS_E_ARG ahead of any launch: pips_cover_step's cases, per_cell < 1, crowd_after < 1, a NULL crowd, crowd_out, gone or reason
+ * (n > 0).  PIPS_E_WORKSPACE: workspace_bytes < pips_cover_thin_workspace_bytes(n, m, gh, gw) (0 for n < 0, m < 0, gh or gw < 1,
+ * too many cells) -- pips_cover_workspace_bytes plus a run per query and a surplus bit per (row, query).  A rejected call writes
+ * nothing.  One memset node and at most four launches (m = 0 skips the ranking, n = 0 everything but the lists); a block of 256 queries
+ * ranks itself against the older ones of one row through LDS; the lists are scanned by one block; no atomics, no allocation, no
+ * synchronisation. */
+size_t pips_cover_thin_workspace_bytes(int n, int m, int gh, int gw);
+int    pips_cover_step_thin(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy,
+                            const int* lost, const int* crowd, int H, int W, int cell, float vis_logit, int lost_after,
+                            int max_queries, int per_cell, int crowd_after,
+                            int* keep, int* lost_out, int* crowd_out, float* seeds, int* gone, int* reason, int* counts,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* Seeding on corners: pips_corner_table looks at the pixels of F frames (F,3,h,w), planar, uint8 (src_is_u8 != 0) or float32 with
  * values 0..255 (finite), and writes table (F,gh,gw,3) = (x, y, S) -- the most trackable pixel of each cell of pips_cover_step's
  * grid (gh = (h-1)/cell + 1 rows, gw likewise) and its score.  Everything up to the argmax is integer arithmetic:

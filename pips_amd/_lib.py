@@ -87,6 +87,10 @@ SIGNATURES = {
     "pips_cover_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pips_cover_step": (c_int, [c_int, c_int, c_int, fp, fp, c_void_p, fp, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int,
                                 c_void_p, c_void_p, fp, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pips_cover_thin_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pips_cover_step_thin": (c_int, [c_int, c_int, c_int, fp, fp, c_void_p, fp, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                     c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, fp, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
     "pips_corner_table": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, c_void_p]),
     "pips_cover_place": (c_int, [fp, c_int, fp, c_int, c_int, c_int, c_int, c_void_p]),
     "pips_encoder_workspace_bytes": (c_size_t, [c_int] * 4),

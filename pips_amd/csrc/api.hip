@@ -1725,6 +1725,38 @@ int pips_cover_step(int n, int m, int f1, const float* trajs, const float* vis, 
     return launch_cover_step(n, m, f1, trajs, vis, tq, xy, lost, H, W, cell, gh, gw, vis_logit, lost_after, max_queries, keep, lost_out,
                              seeds, counts, (int*)workspace, (hipStream_t)stream);
 }
+size_t pips_cover_thin_workspace_bytes(int n, int m, int gh, int gw) {
+    if (n < 0 || m < 0 || gh < 1 || gw < 1 || (long long)gh * gw > PIPS_COVER_CELLS_MAX) return 0;
+    return cover_thin_workspace_ints(n, m, gh, gw) * sizeof(int);
+}
+int pips_cover_step_thin(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy, const int* lost,
+                         const int* crowd, int H, int W, int cell, float vis_logit, int lost_after, int max_queries, int per_cell,
+                         int crowd_after, int* keep, int* lost_out, int* crowd_out, float* seeds, int* gone, int* reason, int* counts,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    PIPS_CHECK_ARG(n >= 0 && m >= 0, "cover_step_thin: need n >= 0 and m >= 0 (n=%d, m=%d)", n, m);
+    PIPS_CHECK_ARG(cell >= 8 && H >= 1 && W >= 1, "cover_step_thin: need cell >= 8 and a frame of at least 1x1 (cell=%d, H=%d, W=%d)", cell, H, W);
+    PIPS_CHECK_ARG(lost_after >= 1 && max_queries >= 0, "cover_step_thin: need lost_after >= 1 and max_queries >= 0 (%d, %d)", lost_after,
+                   max_queries);
+    PIPS_CHECK_ARG(per_cell >= 1 && crowd_after >= 1, "cover_step_thin: need per_cell >= 1 and crowd_after >= 1 (%d, %d)", per_cell,
+                   crowd_after);
+    PIPS_CHECK_ARG(m == 0 ? f1 == 0 : f1 >= m, "cover_step_thin: rows of frames [f1 - m, f1) need f1 >= m, and a step without rows is the first (m=%d, f1=%d)", m, f1);
+    const int gh = (H - 1) / cell + 1, gw = (W - 1) / cell + 1;
+    PIPS_CHECK_ARG((long long)gh * gw <= PIPS_COVER_CELLS_MAX, "cover_step_thin: a grid of %d x %d cells has more than %d", gh, gw,
+                   PIPS_COVER_CELLS_MAX);
+    PIPS_CHECK_ARG(seeds && counts && workspace, "cover_step_thin: null pointer");
+    if (n > 0) {
+        PIPS_CHECK_ARG(tq && xy && lost && crowd && keep && lost_out && crowd_out && gone && reason, "cover_step_thin: null pointer");
+        if (m > 0) PIPS_CHECK_ARG(trajs && vis, "cover_step_thin: null pointer");
+    }
+    const size_t need = cover_thin_workspace_ints(n, m, gh, gw) * sizeof(int);
+    if (workspace_bytes < need) {
+        set_error("cover_step_thin: workspace %zu < %zu bytes", workspace_bytes, need);
+        return PIPS_E_WORKSPACE;
+    }
+    return launch_cover_step_thin(n, m, f1, trajs, vis, tq, xy, lost, crowd, H, W, cell, gh, gw, vis_logit, lost_after, max_queries,
+                                  per_cell, crowd_after, keep, lost_out, crowd_out, seeds, gone, reason, counts, (int*)workspace,
+                                  (hipStream_t)stream);
+}
 
 // ---- seeding on corners
 int pips_corner_table(const void* frames, int src_is_u8, int F, int h, int w, int cell, float* table, void* stream) {

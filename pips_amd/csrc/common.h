@@ -507,6 +507,13 @@ size_t cover_workspace_ints(int n, int gh, int gw);
 int launch_cover_step(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy, const int* lost,
                       int H, int W, int cell, int gh, int gw, float vis_logit, int lost_after, int max_queries, int* keep,
                       int* lost_out, float* seeds, int* counts, int* workspace, hipStream_t st);
+// the thin step (pips_cover_step_thin).  workspace: cover_thin_workspace_ints(n, m, gh, gw) ints -- cover_workspace_ints, then the
+// second run of each query and the surplus bit of each (row, query).
+size_t cover_thin_workspace_ints(int n, int m, int gh, int gw);
+int launch_cover_step_thin(int n, int m, int f1, const float* trajs, const float* vis, const int* tq, const float* xy, const int* lost,
+                           const int* crowd, int H, int W, int cell, int gh, int gw, float vis_logit, int lost_after, int max_queries,
+                           int per_cell, int crowd_after, int* keep, int* lost_out, int* crowd_out, float* seeds, int* gone,
+                           int* reason, int* counts, int* workspace, hipStream_t st);
 
 // ---- corners.hip: the best corner of each cover cell of each frame (pips_corner_table) and the seeds of a cover step moved onto
 // them (pips_cover_place).  table: (F,gh,gw,3) = (x, y, score) / (gh,gw,3) of one frame; arguments checked by the caller.

@@ -20,7 +20,8 @@
   stream together, and each stream gets what its own ``StreamTracker`` returns, bit for bit.
 * ``CoverTracker`` / ``track_cover`` (and ``MultiStreamTracker(cover=)``) -- a ``StreamTracker`` that decides which queries it tracks:
   a ``Cover`` policy retires the queries that left the frame or stayed invisible and seeds the empty cells of a grid over the
-  frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``).  ``Cover(seed="corners")`` puts each seed on
+  frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``); ``Cover(per_cell=k)`` also retires the youngest
+  of more than k tracks that share a cell (``cover_scan_thin`` / ``pips_cover_step_thin``).  ``Cover(seed="corners")`` puts each seed on
   the most trackable pixel of its cell (``corner_table_torch`` / ``pips_corner_table``); ``corner_queries`` is the offline form.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
@@ -758,9 +759,15 @@ class Cover:
     the centre, so which cells are seeded, how many and in which order stay what ``seed="centre"`` (the default) gives.  The table
     of best corners comes from ``corner_table_torch`` / ``cover_place_torch`` under ``scan="torch"`` and from one ``pips_corner_table``
     call per pushed chunk and one ``pips_cover_place`` call per step under ``scan="library"``: the same bits again.  With an
-    unweighted window the chosen pixel of a sharp corner lies about 2 px inside it."""
+    unweighted window the chosen pixel of a sharp corner lies about 2 px inside it.
+    ``per_cell=k`` (``None``, the default: no cap, the step described so far and its calls) caps the tracks of a cell: tracks that
+    lose their surface slide onto a neighbour and ride along with it, and a query that, on ``crowd_after`` returned frames in a
+    row, stood in a cell with at least ``k`` older started queries is retired as "crowded" -- the youngest go, the run is carried
+    from push to push, and the step is ``cover_scan_thin`` / one ``pips_cover_step_thin`` call (the THIN step; its full rule is in
+    include/pips_hip.h).  The cap is per cell, not per distance: two tracks 1 px apart on either side of a cell border both stay."""
 
-    def __init__(self, cell=32, vis_thr=0.5, lost_after=4, max_queries=None, scan="torch", seed="centre", min_corner=0):
+    def __init__(self, cell=32, vis_thr=0.5, lost_after=4, max_queries=None, scan="torch", seed="centre", min_corner=0, per_cell=None,
+                 crowd_after=4):
         self.cell = _whole(cell, "cell", 8)
         if isinstance(vis_thr, bool) or not isinstance(vis_thr, (int, float)) or not 0.0 < vis_thr < 1.0:
             raise ValueError(f"vis_thr must lie in (0, 1), not {vis_thr!r}")
@@ -776,6 +783,8 @@ class Cover:
             raise ValueError(f"seed must be one of {COVER_SEEDS}, not {seed!r}")
         self.seed = seed
         self.min_corner = _whole(min_corner, "min_corner", 0)
+        self.per_cell = None if per_cell is None else _whole(per_cell, "per_cell", 1)
+        self.crowd_after = _whole(crowd_after, "crowd_after", 1)
 
     def grid(self, H, W):
         """(rows, columns) of the cells over an H x W frame"""
@@ -807,6 +816,20 @@ class Cover:
             keep, lost_out, seeds, counts = cover_scan(*args)
         return keep[:counts[0]], lost_out[:counts[0]], seeds[:counts[1]], counts
 
+    def step_thin(self, trajs, vis, f1, tq, xy, lost, crowd, H, W):
+        """one thin cover step (``per_cell`` is set) by the chosen scan -> (keep, lost_out, crowd_out (n_keep), seeds (n_seed,3), gone,
+        reason (n - n_keep) int32 -- the retired columns and 1 outside / 2 lost / 3 crowded --, the five counts on the host);
+        ``crowd`` (n) int32 is the second run, the other arguments are ``step``'s"""
+        args = (trajs, vis, f1, tq, xy, lost, crowd, H, W, self.cell, self.vis_logit, _INT_MAX if self.lost_after is None else self.lost_after,
+                _INT_MAX if self.max_queries is None else self.max_queries, self.per_cell, self.crowd_after)
+        if self.scan == "library":
+            keep, lost_out, crowd_out, seeds, gone, reason, counts = ops.cover_step_thin(*args)
+            counts = counts.tolist()                                              # the one host read
+        else:
+            keep, lost_out, crowd_out, seeds, gone, reason, counts = cover_scan_thin(*args)
+        k, r = counts[0], tq.numel() - counts[0]
+        return keep[:k], lost_out[:k], crowd_out[:k], seeds[:counts[1]], gone[:r], reason[:r], counts
+
 
 def cover_scan(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, max_queries):
     """The cover step (pips_cover_step, include/pips_hip.h) as torch ops, on any device -> (keep (n_keep) int32 ascending, lost_out
@@ -837,6 +860,62 @@ def cover_scan(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, 
     sy = (torch.div(empty, gw, rounding_mode="floor").to(torch.float32) + 0.5) * cell
     seeds = torch.stack([torch.full_like(sx, float(f1)), sx.clamp(max=float(W - 1)), sy.clamp(max=float(H - 1))], dim=1)
     return keep.to(torch.int32), run[keep], seeds, [keep.numel(), empty.numel(), int(outside.sum()), int(gone.sum())]
+
+
+COVER_REASONS = ("kept", "outside", "lost", "crowded")                           # pips_cover_step_thin's `reason` values
+
+
+def cover_scan_thin(trajs, vis, f1, tq, xy, lost, crowd, H, W, cell, vis_logit, lost_after, max_queries, per_cell, crowd_after):
+    """The thin cover step (pips_cover_step_thin, include/pips_hip.h) as torch ops, on any device -> (keep (n_keep) int32 ascending,
+    lost_out, crowd_out (n_keep) int32, seeds (n_seed,3) = (t, x, y), gone (n - n_keep) int32 ascending, reason (n - n_keep) int32 =
+    1 outside / 2 lost / 3 crowded, [n_keep, n_seed, n_outside, n_lost, n_crowded]).  ``crowd`` (n) int32 is the second run; the
+    other arguments are ``cover_scan``'s; the inputs are left as they were.  Not greedy: an elder counts in its cell even when it
+    is itself retired as crowded in this step.  (A row is ranked through an n x n comparison.)"""
+    n, m, dev = tq.numel(), vis.shape[0], xy.device
+    gh, gw = (H - 1) // cell + 1, (W - 1) // cell + 1
+    pending = (tq > f1 - 1) if m > 0 else torch.ones(n, dtype=torch.bool, device=dev)
+    run, zero = lost.to(torch.int32), torch.zeros(n, dtype=torch.int32, device=dev)
+    for g in range(m):                                                            # the run `lost`: cover_scan's
+        on = ~pending & (tq <= f1 - m + g)
+        run = torch.where(on, torch.where(vis[g] < vis_logit, run + 1, zero), run)
+    run = torch.where(pending, zero, run)
+    pos = torch.where(pending.unsqueeze(1), xy, trajs[m - 1]) if m > 0 else xy
+
+    def judge(p):                                                                 # the inside test and the cell where it passes
+        x, y = p[:, 0], p[:, 1]
+        ok = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)                    # written so that NaN and +-inf fail it
+        i = torch.div(torch.where(ok, y, torch.zeros_like(y)), float(cell)).floor().to(torch.int64).clamp(max=gh - 1)
+        j = torch.div(torch.where(ok, x, torch.zeros_like(x)), float(cell)).floor().to(torch.int64).clamp(max=gw - 1)
+        return ok, i * gw + j
+
+    inside, at = judge(pos)
+    outside = ~pending & ~inside
+    lostq = ~pending & inside & (run >= lost_after)
+    col = torch.arange(n, device=dev)
+    elder = col.unsqueeze(0) < col.unsqueeze(1)                                   # [j, i]: i is older than j
+    crun = crowd.to(torch.int32)
+    for g in range(m):                                                            # the second run: surplus on each returned frame
+        on = ~pending & (tq <= f1 - m + g)
+        ok, cid = judge(trajs[g])
+        counts_here = on & ~outside & ~lostq & ok
+        cid = torch.where(counts_here, cid, torch.full_like(cid, -1))
+        older = ((cid.unsqueeze(1) == cid.unsqueeze(0)) & elder & counts_here.unsqueeze(0)).sum(dim=1)
+        surplus = counts_here & (older >= per_cell)
+        crun = torch.where(on, torch.where(surplus, crun + 1, zero), crun)
+    crun = torch.where(pending, zero, crun)
+    crowded = ~pending & ~outside & ~lostq & (crun >= crowd_after)
+    kept = ~(outside | lostq | crowded)
+    keep, gone = torch.nonzero(kept).squeeze(1), torch.nonzero(~kept).squeeze(1)
+    stand = kept & inside                                                         # (a pending query outside the frame: no cell)
+    occ = torch.zeros(gh * gw, dtype=torch.bool, device=dev)
+    occ[at[stand]] = True
+    empty = torch.nonzero(~occ).squeeze(1)[:max(max_queries - keep.numel(), 0)]
+    sx = ((empty % gw).to(torch.float32) + 0.5) * cell
+    sy = (torch.div(empty, gw, rounding_mode="floor").to(torch.float32) + 0.5) * cell
+    seeds = torch.stack([torch.full_like(sx, float(f1)), sx.clamp(max=float(W - 1)), sy.clamp(max=float(H - 1))], dim=1)
+    reason = (outside.to(torch.int32) + 2 * lostq.to(torch.int32) + 3 * crowded.to(torch.int32))[gone]
+    return (keep.to(torch.int32), run[keep], crun[keep], seeds, gone.to(torch.int32), reason,
+            [keep.numel(), empty.numel(), int(outside.sum()), int(lostq.sum()), int(crowded.sum())])
 
 
 def corner_table_torch(frames, cell):
@@ -899,7 +978,7 @@ def cover_place_torch(seeds, table, H, W, cell, min_corner):
 class _CoverBook:
     """What a covered stream keeps per query beside the tracker's own state: the identity of each column (``ids``), the frame of
     each identity (``born``), identity -> (frame, reason) of the retired ones (``retired``), their hop lists (``hops``, when recorded)
-    and, on the device, the arrays a cover step reads -- ``tq`` / ``lost`` (n) int32 and ``xy`` (n,2).  ``start`` runs the first step
+    and, on the device, the arrays a cover step reads -- ``tq`` / ``lost`` (n) int32, ``xy`` (n,2) and, under ``Cover(per_cell=)``, ``crowd`` (n) int32.  ``start`` runs the first step
     (no rows: every query is pending and the seeds land on frame 0), ``step`` the one after a push; both act on the tracker
     through ``add(queries (1,k,3))`` and ``remove(columns)``.
     Under ``seed="corners"`` the book also keeps ``table`` (T - table0, gh, gw, 3), the best corners of the frames ``[table0, T)``
@@ -917,6 +996,7 @@ class _CoverBook:
         self.size = (int(H), int(W))
         self.tq, self.xy = tq_host.to(dev, torch.int32), xy.to(dev, torch.float32).contiguous()
         self.lost = torch.zeros_like(self.tq)
+        self.crowd = None if self.cover.per_cell is None else torch.zeros_like(self.tq)      # (the thin step's second run)
         if self.corners:
             self.table = self.xy.new_empty((0,) + self.cover.grid(int(H), int(W)) + (3,))
         n = self.tq.numel()
@@ -926,22 +1006,34 @@ class _CoverBook:
         """the cover step on the rows trajs (m,n,2) / vis (m,n) of frames [f0, f0 + m); ``hops``: the hop list of each column"""
         n, m = len(self.ids), vis.shape[0]
         f1, (H, W) = f0 + m, self.size
-        keep, lost_out, seeds, counts = self.cover.step(trajs, vis, f1, self.tq, self.xy, self.lost, H, W)
+        thin = self.cover.per_cell is not None
+        if thin:
+            keep, lost_out, crowd_out, seeds, gone, reason, counts = self.cover.step_thin(trajs, vis, f1, self.tq, self.xy, self.lost,
+                                                                                          self.crowd, H, W)
+        else:
+            keep, lost_out, seeds, counts = self.cover.step(trajs, vis, f1, self.tq, self.xy, self.lost, H, W)
         if counts[0] < n:                                                         # somebody is retired: the kept list comes over
             kept = keep.tolist()
-            gone = sorted(set(range(n)) - set(kept))
-            x, y = trajs[m - 1][torch.tensor(gone, device=trajs.device)].to("cpu").unbind(1)
-            inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)
-            for c, ok in zip(gone, inside.tolist()):
-                self.retired[self.ids[c]] = (f1 - 1, "lost" if ok else "outside")
+            if thin:                                                              # ... and the step's own list of who and why
+                gone, why = gone.tolist(), [COVER_REASONS[r] for r in reason.tolist()]
+                assert len(gone) == n - counts[0] and [why.count(r) for r in COVER_REASONS[1:]] == counts[2:]
+            else:
+                gone = sorted(set(range(n)) - set(kept))
+                x, y = trajs[m - 1][torch.tensor(gone, device=trajs.device)].to("cpu").unbind(1)
+                inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)
+                why = ["lost" if ok else "outside" for ok in inside.tolist()]
+                assert counts[2] == len(gone) - int(inside.sum()) and counts[3] == int(inside.sum())
+            for c, r in zip(gone, why):
+                self.retired[self.ids[c]] = (f1 - 1, r)
                 if self.hops is not None:
                     self.hops[self.ids[c]] = hops[c]
-            assert counts[2] == len(gone) - int(inside.sum()) and counts[3] == int(inside.sum())
             remove(gone)
             self.ids = [self.ids[c] for c in kept]
             k = keep.to(torch.int64)
             self.tq, self.xy = self.tq[k], self.xy[k]
         self.lost = lost_out
+        if thin:
+            self.crowd = crowd_out
         if counts[1] > 0:                                                         # and so do the seeds
             if not self.corners:
                 self._seed(f1, seeds, add)
@@ -960,6 +1052,8 @@ class _CoverBook:
         self.tq = torch.cat([self.tq, torch.full((k,), f1, dtype=torch.int32, device=self.tq.device)])
         self.xy = torch.cat([self.xy, seeds[:, 1:]])
         self.lost = torch.cat([self.lost, torch.zeros(k, dtype=torch.int32, device=self.tq.device)])
+        if self.crowd is not None:
+            self.crowd = torch.cat([self.crowd, torch.zeros(k, dtype=torch.int32, device=self.tq.device)])
 
     def see(self, frames, emitted, add):
         """``seed="corners"``: the frames (k,3,H,W) that a push is about to encode, ``[0, emitted)`` having been returned.  One table
@@ -1014,7 +1108,7 @@ class CoverTracker:
     placed on its corners and join at its start, with the columns and identities they would have had; ``finish()`` drops them.)
     A cover step then runs at the end of every ``push``
     that returned at least one frame, on those frames, and retires and seeds for the pushes that follow; ``finish()`` runs none.
-    ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost")`` the last frame returned for it and why,
+    ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost" | "crowded")`` the last frame returned for it and why,
     ``hops`` (``record_hops=True``) the hop list of each identity.  Over its life an identity is what ``track_stream`` given that
     query alone returns; frames of a retired query that were not returned before its retirement are discarded."""
 

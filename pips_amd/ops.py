@@ -483,6 +483,26 @@ def cover_step(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, 
     return keep, lost_out, seeds, counts
 
 
+def cover_step_thin(trajs, vis, f1, tq, xy, lost, crowd, H, W, cell, vis_logit, lost_after, max_queries, per_cell, crowd_after):
+    """pips_cover_step_thin: ``cover_step`` with at most ``per_cell`` tracks in a cell -- ``crowd`` (n) int32 is the second run of each
+    query, and a query that was surplus in its cell for ``crowd_after`` returned frames in a row is retired (include/pips_hip.h).
+    -> (keep (n), lost_out (n), crowd_out (n) int32, seeds (min(cells, max_queries),3), gone (n), reason (n) int32, counts (5)
+    int32) on ``xy``'s device: counts = {n_keep, n_seed, n_outside, n_lost, n_crowded}; keep / lost_out / crowd_out are written up to
+    n_keep, gone / reason (1 outside, 2 lost, 3 crowded) up to n - n_keep; the inputs are left as they were."""
+    m, n, dev = vis.shape[0], tq.numel(), xy.device
+    gh, gw = (int(H) - 1) // int(cell) + 1, (int(W) - 1) // int(cell) + 1
+    keep, lost_out, crowd_out, gone, reason = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(5))
+    seeds = torch.empty(max(min(gh * gw, int(max_queries)), 1), 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(5, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(_lib.load().pips_cover_thin_workspace_bytes(n, m, gh, gw) // 4, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _call("pips_cover_step_thin", n, m, int(f1), _chain_f32(trajs), _chain_f32(vis), _i32(tq), _chain_f32(xy), _i32(lost), _i32(crowd),
+              int(H), int(W), int(cell), float(vis_logit), int(lost_after), int(max_queries), int(per_cell), int(crowd_after),
+              _lib.ptr(keep), _lib.ptr(lost_out), _lib.ptr(crowd_out), _lib.ptr(seeds), _lib.ptr(gone), _lib.ptr(reason), _lib.ptr(counts),
+              _lib.ptr(ws), ws.numel() * 4, _stream())
+    return keep, lost_out, crowd_out, seeds, gone, reason, counts
+
+
 def corner_table(frames, cell):
     """pips_corner_table on device frames (F,3,h,w), uint8 or float 0..255 -> table (F,gh,gw,3) float32 = (x, y, S): the best
     corner of each cover cell of each frame and its score; a cell without a candidate holds its centre and -1 (include/pips_hip.h)."""

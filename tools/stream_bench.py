@@ -22,7 +22,9 @@ caller's: cells of 32 px (a 12 x 20 grid), default policy, ``scan="torch"`` agai
 push (the same under both scans: checked), and per scan the median push time and the median time of the cover step alone (the
 tracker's ``book.step`` timed with a device synchronisation on either side).  One warm-up of each, then --reps of each, alternating.
 ``--seed corners`` seeds on corners (``Cover(seed="corners")``: one corner table per pushed chunk, the seeds of a step placed on it)
-instead of on the cell centres (``--min-corner``: the score a corner needs); frames per second (T over the summed push times, the median over the runs) is printed per scan."""
+instead of on the cell centres (``--min-corner``: the score a corner needs); frames per second (T over the summed push times, the median over the runs) is printed per scan.
+``--per-cell K [--crowd-after A]`` thins the cover (``Cover(per_cell=K, crowd_after=A)``: the thin step); the retirements of the
+run are counted by reason in every case."""
 import argparse
 import json
 import os
@@ -167,9 +169,11 @@ def compare_churn(dev, q, reps):
     return res
 
 
-def cover_run(m, host, scan, seed="centre", min_corner=0):
-    """one covered stream -> (live count per push, seconds per push, seconds of the cover step of each push that ran one)"""
-    ct = drivers.CoverTracker(m, drivers.Cover(cell=32, scan=scan, seed=seed, min_corner=min_corner), None, iters=6, slots=SLOTS, rounds="library")
+def cover_run(m, host, scan, seed="centre", min_corner=0, per_cell=None, crowd_after=4):
+    """one covered stream -> (live count per push, seconds per push, seconds of the cover step of each push that ran one, the
+    number of retirements by reason)"""
+    cover = drivers.Cover(cell=32, scan=scan, seed=seed, min_corner=min_corner, per_cell=per_cell, crowd_after=crowd_after)
+    ct = drivers.CoverTracker(m, cover, None, iters=6, slots=SLOTS, rounds="library")
     steps = []
     real = ct.book.step
 
@@ -183,23 +187,25 @@ def cover_run(m, host, scan, seed="centre", min_corner=0):
         live.append(len(ct.book.ids))
     ct.finish()
     torch.cuda.synchronize()
-    return live, ts, steps[1:]                                         # (steps[0]: the first step, inside the first push)
+    why = [r for _, r in ct.retired.values()]
+    return live, ts, steps[1:], {r: why.count(r) for r in ("outside", "lost", "crowded")}      # (steps[0]: the first step, inside the first push)
 
 
-def compare_cover(dev, reps, seed="centre", min_corner=0):
+def compare_cover(dev, reps, seed="centre", min_corner=0, per_cell=None, crowd_after=4):
     host = frames(0, CHURN_T)
     m = model(dev)
     scans = ("torch", "library")
     got = {k: [] for k in scans}
     for k in scans:                                                     # warm-up: weights, workspaces, the allocator's pools
-        cover_run(m, host, k, seed, min_corner)
+        cover_run(m, host, k, seed, min_corner, per_cell, crowd_after)
     for _ in range(reps):
         for k in scans:
-            got[k].append(cover_run(m, host, k, seed, min_corner))
-    live = got["torch"][0][0]
-    assert all(r[0] == live for rows in got.values() for r in rows), "the two scans kept different queries"
+            got[k].append(cover_run(m, host, k, seed, min_corner, per_cell, crowd_after))
+    live, retired = got["torch"][0][0], got["torch"][0][3]
+    assert all(r[0] == live and r[3] == retired for rows in got.values() for r in rows), "the two scans kept different queries"
     res = {"config": "360x640 stride 4, no caller queries, cell 32 (12 x 20), chunks of 16, slots 24, library rounds", "T": CHURN_T,
-           "seed": seed, "min_corner": min_corner, "pushes": len(live), "live_per_push": live}
+           "seed": seed, "min_corner": min_corner, "per_cell": per_cell, "crowd_after": crowd_after if per_cell is not None else None,
+           "pushes": len(live), "live_per_push": live, "retired": retired}
     for k, rows in got.items():
         res[f"{k}_push_ms"] = round(statistics.median(t for r in rows for t in r[1][2:]) * 1e3, 2)
         res[f"{k}_step_ms"] = round(statistics.median(t for r in rows for t in r[2]) * 1e3, 3)
@@ -225,10 +231,12 @@ def main():
     ap.add_argument("--seed", default="centre", choices=list(drivers.COVER_SEEDS), help="with --cover: where in a cell a seed lands")
     ap.add_argument("--min-corner", type=int, default=0, help="with --seed corners: the score a corner needs (above 6372450: the tables "
                     "are made and every seed stays on its centre, which prices the tables alone)")
+    ap.add_argument("--per-cell", type=int, default=None, help="with --cover: at most this many tracks to a cell (the thin step)")
+    ap.add_argument("--crowd-after", type=int, default=4, help="with --per-cell: surplus frames in a row before a track is retired")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.cover:
-        print(json.dumps(compare_cover(dev, a.reps, a.seed, a.min_corner)))
+        print(json.dumps(compare_cover(dev, a.reps, a.seed, a.min_corner, a.per_cell, a.crowd_after)))
         return
     q = queries(dev)
     if a.churn:
