@@ -108,7 +108,9 @@ const char* pips_last_error(void);
  * arrays); pips_cover_step and pips_cover_workspace_bytes (which queries of a stream are retired and where new ones are seeded, so
  * that a bounded set of tracks stays spread over the frame); pips_corner_table and pips_cover_place (the best corner of each
  * cover cell of each frame, and the seeds of a cover step moved from the cell centres onto them); pips_cover_step_thin and
- * pips_cover_thin_workspace_bytes (the cover step with at most per_cell tracks in a cell: the youngest surplus are retired). */
+ * pips_cover_thin_workspace_bytes (the cover step with at most per_cell tracks in a cell: the youngest surplus are retired);
+ * pips_cut_table and pips_cut_workspace_bytes (the regional luma histogram of each raw frame and its distance to the frame before:
+ * where a video has its scene cuts). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -541,6 +543,32 @@ int    pips_cover_step_thin(int n, int m, int f1, const float* trajs, const floa
 #define PIPS_CORNER_BLOCKS_MAX ((1 << 24) - 1)
 int    pips_corner_table(const void* frames, int src_is_u8, int F, int h, int w, int cell, float* table, void* stream);
 int    pips_cover_place(float* seeds, int k, const float* table_of_frame, int h, int w, int cell, int min_corner, void* stream);
+/* Scene cuts: pips_cut_table looks at the pixels of F frames (F,3,h,w) -- pips_corner_table's input: planar, uint8 (src_is_u8 != 0)
+ * or float32 with values 0..255 -- and writes hist (F,16,32) int32, the regional luma histogram of each frame, and dist (F) int32,
+ * its distance to the frame before.  Integers only:
+ *  - pips_corner_table's luma: a float channel is quantised as u = floor(min(max(v, 0), 255) + 0.5), Y = (77 R + 150 G + 29 B +
+ *    128) >> 8;
+ *  - pixel (y, x) counts in region r = 4 ((4 y) / h) + (4 x) / w (integer division: a 4 x 4 grid over the frame, with empty
+ *    regions when h or w < 4) and bin b = Y >> 3: hist[f][r][b] is the number of such pixels, and a frame's counts sum to h w;
+ *  - dist[f] = sum over (r, b) of |hist[f][r][b] - hist[f-1][r][b]| for f >= 1; dist[0] is taken against prev_hist (16,32), the
+ *    last histogram of the call before, or is 0 when prev_hist is NULL.  0 <= dist <= 2 h w (stored as its low 32 bits: 2^31 is
+ *    reached only by a frame of exactly 2^30 pixels that shares no bin with its neighbour in any region).
+ * A caller puts a cut before frame f iff dist[f] > limit with limit = floor(cut_thr * 2 h w) computed once on the host in double
+ * (drivers.Cover(cut_thr=), drivers.find_cuts); the library knows no threshold.
+ * Two launches: 4 * S blocks of 256 threads per frame count S strips of pixel rows of each of the 4 region rows (S = min(16,
+ * max(1, (ceil(h / 4) + 7) / 8))) in LDS and store their partial histograms -- 128 int32 each -- to the workspace with plain
+ * stores; then a block per frame sums the partials of frames f and f-1 in a fixed order, writes hist[f] and reduces dist[f].
+ * Rows are read with 16-byte loads where a frame's three planes share their alignment (plane bytes a multiple of 16), from the
+ * first 16-byte address of each row on; every other pixel, row width and base address takes element loads.  No global atomics, no
+ * allocation, no synchronisation; nothing but hist, dist and the first pips_cut_workspace_bytes(F, h, w) bytes of the workspace
+ * (= F * 4 * S * 512; 0 for arguments that pips_cut_table rejects) is written, and prev_hist may not overlap them.
+ * PIPS_E_ARG ahead of any launch: F < 0 or > PIPS_CUT_FRAMES_MAX, h or w < 1, h w > 2^30, and with F > 0 a NULL frames, hist,
+ * dist or workspace.  PIPS_E_WORKSPACE: workspace_bytes < pips_cut_workspace_bytes(F, h, w).  A rejected call writes nothing; F =
+ * 0 launches nothing and returns PIPS_OK. */
+#define PIPS_CUT_FRAMES_MAX ((1 << 25) - 1)
+size_t pips_cut_workspace_bytes(int F, int h, int w);
+int    pips_cut_table(const void* frames, int src_is_u8, int F, int h, int w, const int32_t* prev_hist, int32_t* hist, int32_t* dist,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- stages (same kernels, exposed for parity tests and for callers that cache maps) --*/
 

@@ -93,6 +93,8 @@ SIGNATURES = {
                                      c_void_p, c_size_t, c_void_p]),
     "pips_corner_table": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, fp, c_void_p]),
     "pips_cover_place": (c_int, [fp, c_int, fp, c_int, c_int, c_int, c_int, c_void_p]),
+    "pips_cut_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pips_cut_table": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pips_encoder_workspace_bytes": (c_size_t, [c_int] * 4),
     "pips_pyramid_floats": (c_size_t, [c_int] * 4),
     "pips_pyramid_offset": (c_size_t, [c_int] * 5),

@@ -1779,6 +1779,26 @@ int pips_cover_place(float* seeds, int k, const float* table_of_frame, int h, in
     return launch_cover_place(seeds, k, table_of_frame, (h - 1) / cell + 1, (w - 1) / cell + 1, cell, min_corner, (hipStream_t)stream);
 }
 
+// ---- scene cuts
+size_t pips_cut_workspace_bytes(int F, int h, int w) {
+    if (F < 0 || F > PIPS_CUT_FRAMES_MAX || h < 1 || w < 1 || (long long)h * w > (1ll << 30)) return 0;
+    return (size_t)F * 4 * cut_strips(h) * 128 * sizeof(int);
+}
+int pips_cut_table(const void* frames, int src_is_u8, int F, int h, int w, const int32_t* prev_hist, int32_t* hist, int32_t* dist,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    PIPS_CHECK_ARG(F >= 0 && F <= PIPS_CUT_FRAMES_MAX, "cut_table: need 0 <= F <= %d (F=%d)", PIPS_CUT_FRAMES_MAX, F);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1, "cut_table: need a frame of at least 1x1 (h=%d, w=%d)", h, w);
+    PIPS_CHECK_ARG((long long)h * w <= (1ll << 30), "cut_table: a frame of %d x %d has more than 2^30 pixels", h, w);
+    if (F == 0) return PIPS_OK;
+    PIPS_CHECK_ARG(frames && hist && dist && workspace, "cut_table: null pointer");
+    const size_t need = pips_cut_workspace_bytes(F, h, w);
+    if (workspace_bytes < need) {
+        set_error("cut_table: workspace %zu < %zu bytes", workspace_bytes, need);
+        return PIPS_E_WORKSPACE;
+    }
+    return launch_cut_table(frames, src_is_u8 != 0, F, h, w, prev_hist, hist, dist, (int*)workspace, (hipStream_t)stream);
+}
+
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;

@@ -1,7 +1,9 @@
 // Internal declarations shared by the HIP translation units of libpips_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
+#include <limits.h>
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/pips_hip.h"
@@ -519,5 +521,17 @@ int launch_cover_step_thin(int n, int m, int f1, const float* trajs, const float
 // them (pips_cover_place).  table: (F,gh,gw,3) = (x, y, score) / (gh,gw,3) of one frame; arguments checked by the caller.
 int launch_corner_table(const void* frames, int src_u8, int F, int h, int w, int cell, int gh, int gw, float* table, hipStream_t st);
 int launch_cover_place(float* seeds, int k, const float* table, int gh, int gw, int cell, int min_corner, hipStream_t st);
+
+// ---- cuts.hip: the regional luma histogram of each frame and its distance to the frame before (pips_cut_table).  A frame is read
+// by 4 * cut_strips(h) blocks -- the region rows cut into strips of about 8 pixel rows, 16 strips at the most -- whose partial
+// histograms (128 ints each) are the workspace; arguments checked by the caller.
+constexpr int PIPS_CUT_STRIPS_MAX = 16;
+static_assert(PIPS_CUT_FRAMES_MAX <= INT_MAX / (4 * PIPS_CUT_STRIPS_MAX), "the first launch's grid fits an int");
+inline int cut_strips(int h) {
+    const int rows = (h + 3) / 4;                                                  // the tallest region row
+    return std::min(PIPS_CUT_STRIPS_MAX, std::max(1, (rows + 7) / 8));
+}
+int launch_cut_table(const void* frames, int src_u8, int F, int h, int w, const int* prev_hist, int* hist, int* dist, int* partial,
+                     hipStream_t st);
 
 }  // namespace pips

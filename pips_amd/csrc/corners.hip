@@ -5,6 +5,7 @@
 // is bit for bit drivers.corner_table_torch's.  Plain HIP, the default floating-point flags (cover.hip's): `/` in the placing is
 // the correctly rounded fp32 quotient, as in cover_flag_kernel.  No atomics and no global scratch: one block owns one cell.
 #include "common.h"
+#include "luma.h"
 
 namespace pips {
 
@@ -17,21 +18,7 @@ constexpr int CRN_HALO = 4;                    // 3 for the window and 1 for the
 constexpr int CRN_LW = CRN_TILE + 2 * CRN_HALO;            // 40: the luma tile's side, and the row stride of luma and gradients
 constexpr int CRN_GW = CRN_TILE + 6;                       // 38: the side of the gradient tile
 
-// Luma of pixel (y, x) of a planar frame: the channels quantised to 0..255 (a float by one fp32 add, no product: nothing for the
-// compiler to contract), then the fixed-point BT.601 weights.
-template <typename T>
-__device__ __forceinline__ int luma_at(const T* __restrict__ frame, size_t plane, size_t at) {
-    int ch[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if constexpr (sizeof(T) == 1) {
-            ch[k] = (int)frame[k * plane + at];
-        } else {
-            ch[k] = (int)floorf(fminf(fmaxf(frame[k * plane + at], 0.f), 255.f) + 0.5f);
-        }
-    }
-    return (77 * ch[0] + 150 * ch[1] + 29 * ch[2] + 128) >> 8;
-}
+// (luma_at, the luma of pixel (y, x) of a planar frame, is luma.h's: pips_cut_table quantises the same way)
 
 // One block per (frame, cell).  The candidates of the cell -- its pixels with 4 <= x <= w-5 and 4 <= y <= h-5 -- are walked in
 // tiles; every pass below maps consecutive lanes to consecutive dwords of one LDS row (luma and gradients share the stride 40 and

@@ -40,6 +40,8 @@ away again (``remove_queries``: the state's ``keep`` copies the remaining column
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import ops
@@ -603,6 +605,7 @@ class StreamTracker:
         self.finished = False
         self.emitted = 0                                                          # frames [0, emitted) returned
         self.hops = [[] for _ in range(self.N)] if record_hops else None       # frame steps per query (grows with T)
+        self.cut_hops = None                                                      # the hop lists of the columns at the last cut()
         self.state = _ROUNDS[rounds](self, engine)                                # the device state, made at the first push
 
     # the state's output rows (slots + 8, N, 2) / (slots + 8, N) and window starts (N,)
@@ -689,6 +692,24 @@ class StreamTracker:
         self.finished = True
         return self._cat(self.emitted, [self._rounds(final=True)])
 
+    @torch.no_grad()
+    def cut(self):
+        """End every query that has started, at the ``T`` frames pushed so far, and keep the stream open -> ``(f0, trajs (1,m,N,2),
+        vis (1,m,N), keep)``: the rounds run as ``finish()`` runs them (windows that reach past frame ``T - 1`` repeat it), ALL the
+        frames ``[f0, T)`` not returned yet come back in the columns as they were at the call, and the queries with ``t < T`` are
+        removed (``remove_queries``: state, rows and hop lists shrink).  ``keep`` holds the former column of each column that
+        remains -- the queries with ``t >= T``, which stay waiting, untouched: on later pushes such a query is what a stream that
+        starts at frame ``T`` returns for it, since a forward window never reads below its start.  ``cut_hops`` is, with
+        ``record_hops``, the hop list of every column as it was at the last cut (None otherwise).  Before the first push no frame
+        is returned and nothing is removed.  ValueError, with the tracker left as it was, after ``finish()``."""
+        if self.finished:
+            raise ValueError("cut() after finish()")
+        self.cut_hops = None if self.hops is None else list(self.hops)
+        if self.cache is None:
+            return self._cat(self.emitted, []) + (torch.arange(self.N),)
+        f0, trajs, vis = self._cat(self.emitted, [self._rounds(final=True)])
+        return f0, trajs, vis, self.remove_queries(torch.nonzero(self.tq_host < self.cache.T).squeeze(1))
+
     def _rounds(self, final):
         """the state's hop rounds, their steps recorded per query -> the rows of the frames that became final (None: none did)"""
         for active, steps in self.state.run(final):
@@ -764,10 +785,16 @@ class Cover:
     lose their surface slide onto a neighbour and ride along with it, and a query that, on ``crowd_after`` returned frames in a
     row, stood in a cell with at least ``k`` older started queries is retired as "crowded" -- the youngest go, the run is carried
     from push to push, and the step is ``cover_scan_thin`` / one ``pips_cover_step_thin`` call (the THIN step; its full rule is in
-    include/pips_hip.h).  The cap is per cell, not per distance: two tracks 1 px apart on either side of a cell border both stay."""
+    include/pips_hip.h).  The cap is per cell, not per distance: two tracks 1 px apart on either side of a cell border both stay.
+    ``cut_thr=x`` (``None``, the default: no frame is looked at and every path is the one described so far) ends the tracks at scene
+    cuts: a cut lies before a pushed frame whose regional luma histogram differs from that of the frame before by more than
+    ``cut_limit(x, H, W)`` (``cut_table_torch`` / one ``pips_cut_table`` call per pushed chunk, by ``scan``: the same integers).  A
+    ``CoverTracker`` splits a push there, ends every started query as "cut" on the last frame of the old scene (``StreamTracker.cut``)
+    and seeds every cell of the new scene's first frame.  0.5 is a reasonable value, not a tuned one: on one 640 x 360 video with fast
+    motion consecutive frames stayed below 0.15 and frames 64 apart below 0.45, a frame against its negative reached 0.6."""
 
     def __init__(self, cell=32, vis_thr=0.5, lost_after=4, max_queries=None, scan="torch", seed="centre", min_corner=0, per_cell=None,
-                 crowd_after=4):
+                 crowd_after=4, cut_thr=None):
         self.cell = _whole(cell, "cell", 8)
         if isinstance(vis_thr, bool) or not isinstance(vis_thr, (int, float)) or not 0.0 < vis_thr < 1.0:
             raise ValueError(f"vis_thr must lie in (0, 1), not {vis_thr!r}")
@@ -785,6 +812,16 @@ class Cover:
         self.min_corner = _whole(min_corner, "min_corner", 0)
         self.per_cell = None if per_cell is None else _whole(per_cell, "per_cell", 1)
         self.crowd_after = _whole(crowd_after, "crowd_after", 1)
+        if cut_thr is not None and (isinstance(cut_thr, bool) or not isinstance(cut_thr, (int, float)) or not 0.0 < cut_thr < 1.0):
+            raise ValueError(f"cut_thr must be None or lie in (0, 1), not {cut_thr!r}")
+        self.cut_thr = None if cut_thr is None else float(cut_thr)
+
+    def cut_table(self, frames, prev_hist=None, dev=None):
+        """the regional luma histograms of the frames (F,3,H,W) and their distances (``cut_table_torch``'s rule) by the chosen scan
+        -> (hist (F,16,32), dist (F,)) on ``dev`` (None: where the frames lie; the GPU under ``scan="library"``)"""
+        if self.scan == "library":
+            return ops.cut_table(frames if frames.is_cuda else frames.to("cuda" if dev is None else dev), prev_hist)
+        return cut_table_torch(frames if dev is None else frames.to(dev), prev_hist)
 
     def grid(self, H, W):
         """(rows, columns) of the cells over an H x W frame"""
@@ -961,6 +998,60 @@ def corner_table_torch(frames, cell):
     return torch.stack([x, y, torch.where(none, torch.full_like(x, -1.0), (best >> 32).to(torch.float32))], dim=3)
 
 
+def cut_limit(cut_thr, h, w):
+    """the largest distance that is no cut: floor(cut_thr * 2 h w), computed once on the host in double"""
+    return int(math.floor(float(cut_thr) * (2 * int(h) * int(w))))
+
+
+def cut_table_torch(frames, prev_hist=None):
+    """pips_cut_table (include/pips_hip.h) as int64 torch ops, on any device: frames (F,3,h,w), uint8 or float 0..255 -> (hist
+    (F,16,32), dist (F,)) int64.  hist[f][r][b] counts the pixels of frame f in region r = 4 ((4y)/h) + (4x)/w whose 8-bit luma Y
+    (``corner_table_torch``'s) has Y >> 3 == b; dist[f] is the sum of |hist[f] - hist[f-1]|, frame 0 against ``prev_hist`` (16,32)
+    or 0 without it.  Integers throughout: equal to the kernel's."""
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"frames must be (F,3,h,w), not {tuple(frames.shape)}")
+    F, _, h, w = frames.shape
+    dev = frames.device
+    if h < 1 or w < 1 or h * w > 2 ** 30:
+        raise ValueError(f"frames of {h} x {w}: need at least 1 x 1 and at most 2^30 pixels")
+    if prev_hist is not None and (tuple(prev_hist.shape) != (16, 32) or prev_hist.is_floating_point()):
+        raise ValueError(f"prev_hist must be a (16,32) integer tensor, not {tuple(prev_hist.shape)} {prev_hist.dtype}")
+    if frames.dtype == torch.uint8:
+        u = frames.to(torch.int64)
+    else:                                               # (as ops.cut_table: anything but uint8 goes through float32)
+        u = (frames.to(torch.float32).clamp(0.0, 255.0) + 0.5).floor().to(torch.int64)
+    Y = (77 * u[:, 0] + 150 * u[:, 1] + 29 * u[:, 2] + 128) >> 8
+    ry = torch.div(4 * torch.arange(h, device=dev), h, rounding_mode="floor")
+    rx = torch.div(4 * torch.arange(w, device=dev), w, rounding_mode="floor")
+    key = 512 * torch.arange(F, device=dev).view(F, 1, 1) + 32 * (4 * ry.view(1, h, 1) + rx.view(1, 1, w)) + (Y >> 3)
+    hist = torch.bincount(key.reshape(-1), minlength=512 * F).view(F, 16, 32)
+    if F == 0:
+        return hist, hist.new_zeros(0)
+    first = hist[:1] if prev_hist is None else prev_hist.to(dev, torch.int64).view(1, 16, 32)
+    return hist, (hist - torch.cat([first, hist[:-1]])).abs().sum(dim=(1, 2))
+
+
+def find_cuts(rgbs, cut_thr=0.5, scan="torch", slice_frames=64):
+    """The scene cuts of a video rgbs (1,T,3,H,W), uint8 or float 0..255 -> the ascending host list of the frames a cut lies
+    before: frame f >= 1 whose distance to frame f - 1 (``cut_table_torch``'s) is above ``cut_limit(cut_thr, H, W)``.  The video is
+    looked at in slices of ``slice_frames`` frames, the last histogram carried from slice to slice, where it lies (``scan="torch"``)
+    or on the GPU (``scan="library"``: a ``pips_cut_table`` call per slice).  A caller of ``track_queries_batch`` splits a video
+    there: ``rgbs[:, a:b]`` for consecutive entries a, b of ``[0] + cuts + [T]``."""
+    cover = Cover(scan=scan, cut_thr=cut_thr)
+    if cover.cut_thr is None:
+        raise ValueError("cut_thr must lie in (0, 1), not None")
+    if rgbs.dim() != 5 or rgbs.shape[0] != 1 or rgbs.shape[2] != 3:
+        raise ValueError(f"rgbs must be (1,T,3,H,W), not {tuple(rgbs.shape)}")
+    step = _whole(slice_frames, "slice_frames", 1)
+    limit = cut_limit(cover.cut_thr, rgbs.shape[3], rgbs.shape[4])
+    cuts, prev = [], None
+    for f0 in range(0, rgbs.shape[1], step):
+        hist, dist = cover.cut_table(rgbs[0, f0:f0 + step], prev)
+        prev = hist[-1]
+        cuts += [f0 + f for f in torch.nonzero(dist > limit).squeeze(1).tolist()]
+    return cuts
+
+
 def cover_place_torch(seeds, table, H, W, cell, min_corner):
     """pips_cover_place as torch ops, on any device: seeds (k,3) = (t, x, y) of a cover step and the table (gh,gw,3) of their frame
     -> new seeds, each on the corner of its cell where that scores above ``min_corner`` and where it was otherwise"""
@@ -991,6 +1082,7 @@ class _CoverBook:
         self.corners, self.table, self.table0, self.T, self.held = cover.seed == "corners", None, 0, 0, None
         self.ids, self.born, self.retired = list(range(tq_host.numel())), tq_host.tolist(), {}
         self.hops = {} if record_hops else None
+        self.prev_hist, self.cuts = None, []           # Cover(cut_thr=): the last pushed frame's histogram; the cut frames so far
 
     def start(self, H, W, dev, tq_host, xy, add, remove):
         self.size = (int(H), int(W))
@@ -1002,8 +1094,9 @@ class _CoverBook:
         n = self.tq.numel()
         self.step(0, self.xy.new_empty(0, n, 2), self.xy.new_empty(0, n), add, remove, None)
 
-    def step(self, f0, trajs, vis, add, remove, hops):
-        """the cover step on the rows trajs (m,n,2) / vis (m,n) of frames [f0, f0 + m); ``hops``: the hop list of each column"""
+    def step(self, f0, trajs, vis, add, remove, hops, at=None):
+        """the cover step on the rows trajs (m,n,2) / vis (m,n) of frames [f0, f0 + m); ``hops``: the hop list of each column.
+        ``at``: the step without rows after a cut -- the first step's form (f0 = 0, m = 0) whose seeds land on frame ``at``"""
         n, m = len(self.ids), vis.shape[0]
         f1, (H, W) = f0 + m, self.size
         thin = self.cover.per_cell is not None
@@ -1034,6 +1127,9 @@ class _CoverBook:
         self.lost = lost_out
         if thin:
             self.crowd = crowd_out
+        if at is not None:
+            assert f1 == 0 and counts[0] == n
+            f1, seeds = at, torch.cat([torch.full_like(seeds[:, :1], float(at)), seeds[:, 1:]], dim=1)
         if counts[1] > 0:                                                         # and so do the seeds
             if not self.corners:
                 self._seed(f1, seeds, add)
@@ -1068,6 +1164,34 @@ class _CoverBook:
             (f1, seeds), self.held = self.held, None
             assert f1 == first
             self._seed(f1, self.cover.place(seeds, self.table[f1 - self.table0], *self.size), add)
+
+    def look(self, frames):
+        """``Cover(cut_thr=)``: the frames (k,3,H,W) that a push brings -> the ascending list of the chunk positions a cut lies
+        before.  One table call for the chunk; the last frame's histogram is carried to the next push"""
+        if frames.shape[0] == 0:
+            return []
+        hist, dist = self.cover.cut_table(frames, self.prev_hist, self.tq.device)
+        self.prev_hist = hist[-1].clone()
+        return torch.nonzero(dist > cut_limit(self.cover.cut_thr, *self.size)).squeeze(1).tolist()      # the one host read
+
+    def cut(self, c, keep, hops, add):
+        """a cut before frame ``c``: the tracker ended every started query and kept the columns ``keep`` (``StreamTracker.cut``).
+        The ended identities are retired as "cut" on frame c - 1, their runs go; then the step without rows seeds frame ``c`` in
+        every cell that holds no pending query (seeds held for frame ``c`` by an earlier step are among them again)"""
+        kept = keep.tolist()
+        for col in sorted(set(range(len(self.ids))) - set(kept)):
+            self.retired[self.ids[col]] = (c - 1, "cut")
+            if self.hops is not None:
+                self.hops[self.ids[col]] = hops[col]
+        self.ids = [self.ids[col] for col in kept]
+        k = keep.to(self.tq.device)
+        self.tq, self.xy, self.lost = self.tq[k], self.xy[k], self.lost[k]
+        if self.crowd is not None:
+            self.crowd = self.crowd[k]
+        self.held = None
+        self.cuts.append(c)
+        n = len(self.ids)
+        self.step(0, self.xy.new_empty(0, n, 2), self.xy.new_empty(0, n), add, None, None, at=c)
 
     def all_hops(self, live):
         """hop lists by identity: the saved ones of the retired queries and ``live``, those of the present columns"""
@@ -1110,7 +1234,13 @@ class CoverTracker:
     that returned at least one frame, on those frames, and retires and seeds for the pushes that follow; ``finish()`` runs none.
     ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost" | "crowded")`` the last frame returned for it and why,
     ``hops`` (``record_hops=True``) the hop list of each identity.  Over its life an identity is what ``track_stream`` given that
-    query alone returns; frames of a retired query that were not returned before its retirement are discarded."""
+    query alone returns; frames of a retired query that were not returned before its retirement are discarded.
+    Under ``Cover(cut_thr=)`` a push that holds a scene cut before frame ``c`` is split there: the pieces are pushed one by one, and
+    between them every started query is ended on frame ``c - 1`` as the end of a video ends it (``StreamTracker.cut``: ALL its
+    frames are returned) and retired as ``(c - 1, "cut")``, and every cell without a pending query is seeded on frame ``c``.  Such a
+    push returns the identities alive at its start followed by those created during it (before its last piece's closing step),
+    NaN where an identity had not started or was retired; ``cuts`` lists the cut frames so far.  Over its life an identity of the
+    new scene is what a ``CoverTracker`` started on frame ``c`` gives it."""
 
     def __init__(self, model, cover, queries=None, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
         if not isinstance(cover, Cover):
@@ -1125,6 +1255,7 @@ class CoverTracker:
     born, retired = (property(lambda self, k=k: getattr(self.book, k)) for k in ("born", "retired"))
     hops = property(lambda self: None if self.book.hops is None else self.book.all_hops(self.st.hops))
     emitted, finished = (property(lambda self, k=k: getattr(self.st, k)) for k in ("emitted", "finished"))
+    cuts = property(lambda self: list(self.book.cuts))
 
     @torch.no_grad()
     def push(self, frames):
@@ -1138,9 +1269,43 @@ class CoverTracker:
                             st.remove_queries)
         if tuple(frames.shape[3:]) != self.book.size:
             raise ValueError(f"frames of {tuple(frames.shape[3:])} pushed to a stream of {self.book.size}")
+        at = [] if self.cover.cut_thr is None else self.book.look(frames[0])
+        if not at:
+            return self._piece(frames)
+        # cuts in this chunk: its pieces are pushed one by one, with the tracker's cut and the step without rows between two
+        parts, first, T0 = [], None, st.cache.T
+        for j, (a, b) in enumerate(zip([0] + at, at + [frames.shape[1]])):
+            if j > 0:
+                ids, self._born = self.ids, len(self.book.born)
+                f0, trajs, vis, keep = st.cut()
+                parts.append((f0, trajs, vis, ids))
+                self.book.cut(T0 + a, keep, st.cut_hops, st.add_queries)
+            elif b > a:
+                parts.append(self._piece(frames[:, a:b]))
+            first = self._born if first is None and parts else first
+            if j > 0:
+                parts.append(self._piece(frames[:, a:b]))
+        # the columns: the identities alive at the start of the push, then those created before the last piece's closing step
+        out = parts[0][3].tolist() + list(range(first, self._born))
+        col = {i: j for j, i in enumerate(out)}
+        f0, dev = parts[0][0], parts[0][1].device
+        m = sum(p[1].shape[1] for p in parts)
+        trajs = torch.full((1, m, len(out), 2), float("nan"), dtype=torch.float32, device=dev)
+        vis = torch.full((1, m, len(out)), float("nan"), dtype=torch.float32, device=dev)
+        for g0, t, v, ids in parts:
+            if t.shape[1] > 0 and ids.numel() > 0:
+                j = torch.tensor([col[i] for i in ids.tolist()], device=dev)
+                trajs[0, g0 - f0:g0 - f0 + t.shape[1]] = trajs[0, g0 - f0:g0 - f0 + t.shape[1]].index_copy(1, j, t[0])
+                vis[0, g0 - f0:g0 - f0 + t.shape[1]] = vis[0, g0 - f0:g0 - f0 + t.shape[1]].index_copy(1, j, v[0])
+        return f0, trajs, vis, torch.tensor(out, dtype=torch.int64)
+
+    def _piece(self, frames):
+        """a run of frames without a cut in it: the corners' tables, the tracker's push, the cover step on the rows it returned"""
+        st = self.st
         if self.book.corners:
             self.book.see(frames[0], st.emitted, st.add_queries)
         ids = self.ids
+        self._born = len(self.book.born)           # (the identities there are when ``ids`` is taken: none is made before the step)
         f0, trajs, vis = st.push(frames)
         if trajs.shape[1] > 0:
             self.book.step(f0, trajs[0], vis[0], st.add_queries, st.remove_queries, st.hops)
@@ -1356,6 +1521,8 @@ class MultiStreamTracker:
     def __init__(self, model, queries_list, iters=6, slots=24, record_hops=False, rounds="torch", joint_encode=False, cover=None):
         if cover is not None and not isinstance(cover, Cover):
             raise ValueError(f"cover must be a drivers.Cover or None, not {cover!r}")
+        if cover is not None and cover.cut_thr is not None:
+            raise ValueError("MultiStreamTracker takes no Cover(cut_thr=): a cut of one stream on the shared rings is not supported")
         if rounds not in ROUNDS:
             raise ValueError(f"rounds must be one of {ROUNDS}, not {rounds!r}")
         assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"

@@ -520,6 +520,34 @@ def corner_table(frames, cell):
     return table
 
 
+def cut_table(frames, prev_hist=None):
+    """pips_cut_table on device frames (F,3,h,w), uint8 or float 0..255 -> (hist (F,16,32) int32, dist (F,) int32): the regional
+    luma histogram of each frame and its distance to the frame before -- frame 0 against ``prev_hist`` (16,32) int32, the last
+    histogram of the call before, or 0 without it (include/pips_hip.h).  Outputs and workspace are allocated here: one call."""
+    assert frames.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"frames must be (F,3,h,w), not {tuple(frames.shape)}")
+    src = frames.contiguous() if frames.dtype == torch.uint8 else _f32(frames)
+    F, _, h, w = src.shape
+    if h < 1 or w < 1 or h * w > 2 ** 30:
+        raise ValueError(f"frames of {h} x {w}: need at least 1 x 1 and at most 2^30 pixels")
+    if prev_hist is not None:
+        if tuple(prev_hist.shape) != (16, 32) or prev_hist.is_floating_point():
+            raise ValueError(f"prev_hist must be a (16,32) integer tensor, not {tuple(prev_hist.shape)} {prev_hist.dtype}")
+        prev_hist = prev_hist.to(src.device, torch.int32).contiguous()
+    hist = torch.empty(F, 16, 32, dtype=torch.int32, device=src.device)
+    dist = torch.empty(F, dtype=torch.int32, device=src.device)
+    if F == 0:                                                                    # (an empty tensor has no pointer to pass)
+        return hist, dist
+    lib = _lib.load()
+    nbytes = lib.pips_cut_workspace_bytes(F, h, w)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        _call("pips_cut_table", _lib.ptr(src), 1 if src.dtype == torch.uint8 else 0, F, h, w, _lib.ptr(prev_hist), _lib.ptr(hist),
+              _lib.ptr(dist), _lib.ptr(ws), nbytes, _stream())
+    return hist, dist
+
+
 def cover_place(seeds, table, h, w, cell, min_corner):
     """pips_cover_place: the seeds (k,3) = (t, x, y) of a cover step, float32 and contiguous, are moved IN PLACE onto the corners
     of ``table`` (gh,gw,3), the table of the seeds' frame, where the cell's score is above ``min_corner`` -> seeds"""

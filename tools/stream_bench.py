@@ -24,7 +24,10 @@ tracker's ``book.step`` timed with a device synchronisation on either side).  On
 ``--seed corners`` seeds on corners (``Cover(seed="corners")``: one corner table per pushed chunk, the seeds of a step placed on it)
 instead of on the cell centres (``--min-corner``: the score a corner needs); frames per second (T over the summed push times, the median over the runs) is printed per scan.
 ``--per-cell K [--crowd-after A]`` thins the cover (``Cover(per_cell=K, crowd_after=A)``: the thin step); the retirements of the
-run are counted by reason in every case."""
+run are counted by reason in every case.
+``--cuts K`` makes the synthetic image change K times, at equal distances (another texture in another brightness range: a scene
+cut); ``--cut-thr X`` ends the tracks there (``Cover(cut_thr=X)``).  Run both with and without ``--cut-thr`` on the same video: without
+it the old scene's tracks stay in their cells and the new scene is seeded only where they happen to fall out."""
 import argparse
 import json
 import os
@@ -42,14 +45,20 @@ from pips_amd.weights import init_state_dict  # noqa: E402
 H, W, STRIDE, N, CHUNK, SLOTS = 360, 640, 4, 256, 16, 24
 
 
-def frames(t0, k, seed=5):
-    """frames t0 .. t0+k-1 of a seeded synthetic video (a textured image drifting by one pixel per frame + noise), uint8"""
-    g = torch.Generator().manual_seed(seed)
-    base = torch.randint(0, 256, (3, H // 8, W // 8), generator=g).float()
-    base = torch.nn.functional.interpolate(base[None], size=(H, W), mode="bilinear", align_corners=False)[0]
+def frames(t0, k, seed=5, cuts=0):
+    """frames t0 .. t0+k-1 of a seeded synthetic video (a textured image drifting by one pixel per frame + noise), uint8; with
+    ``cuts`` the image changes that many times over the k frames: a new texture, dark (0..102) and bright (150..252) in turn"""
+    def image(scene):
+        g = torch.Generator().manual_seed(seed + 7919 * scene)
+        base = torch.randint(0, 256, (3, H // 8, W // 8), generator=g).float()
+        base = torch.nn.functional.interpolate(base[None], size=(H, W), mode="bilinear", align_corners=False)[0]
+        return base if cuts == 0 else base * 0.4 + 150.0 * (scene % 2)
+
+    bases = [image(s) for s in range(cuts + 1)]
     out = []
     for t in range(t0, t0 + k):
         gt = torch.Generator().manual_seed(seed * 100003 + t)
+        base = bases[(t - t0) * (cuts + 1) // k]
         f = torch.roll(base, shifts=(t // 3, t), dims=(1, 2)) + torch.randint(0, 12, (3, H, W), generator=gt).float()
         out.append(f.clamp(0, 255).to(torch.uint8))
     return torch.stack(out).unsqueeze(0)
@@ -169,16 +178,17 @@ def compare_churn(dev, q, reps):
     return res
 
 
-def cover_run(m, host, scan, seed="centre", min_corner=0, per_cell=None, crowd_after=4):
+def cover_run(m, host, scan, seed="centre", min_corner=0, per_cell=None, crowd_after=4, cut_thr=None):
     """one covered stream -> (live count per push, seconds per push, seconds of the cover step of each push that ran one, the
     number of retirements by reason)"""
-    cover = drivers.Cover(cell=32, scan=scan, seed=seed, min_corner=min_corner, per_cell=per_cell, crowd_after=crowd_after)
+    cover = drivers.Cover(cell=32, scan=scan, seed=seed, min_corner=min_corner, per_cell=per_cell, crowd_after=crowd_after,
+                          cut_thr=cut_thr)
     ct = drivers.CoverTracker(m, cover, None, iters=6, slots=SLOTS, rounds="library")
     steps = []
     real = ct.book.step
 
-    def timed_step(*a):
-        steps.append(timed(lambda: real(*a)))
+    def timed_step(*a, **kw):
+        steps.append(timed(lambda: real(*a, **kw)))
 
     ct.book.step = timed_step
     live, ts = [], []
@@ -188,23 +198,25 @@ def cover_run(m, host, scan, seed="centre", min_corner=0, per_cell=None, crowd_a
     ct.finish()
     torch.cuda.synchronize()
     why = [r for _, r in ct.retired.values()]
-    return live, ts, steps[1:], {r: why.count(r) for r in ("outside", "lost", "crowded")}      # (steps[0]: the first step, inside the first push)
+    # (steps[0]: the first step, inside the first push)
+    return live, ts, steps[1:], dict({r: why.count(r) for r in ("outside", "lost", "crowded", "cut")}, cuts=ct.cuts)
 
 
-def compare_cover(dev, reps, seed="centre", min_corner=0, per_cell=None, crowd_after=4):
-    host = frames(0, CHURN_T)
+def compare_cover(dev, reps, seed="centre", min_corner=0, per_cell=None, crowd_after=4, cuts=0, cut_thr=None):
+    host = frames(0, CHURN_T, cuts=cuts)
     m = model(dev)
     scans = ("torch", "library")
     got = {k: [] for k in scans}
     for k in scans:                                                     # warm-up: weights, workspaces, the allocator's pools
-        cover_run(m, host, k, seed, min_corner, per_cell, crowd_after)
+        cover_run(m, host, k, seed, min_corner, per_cell, crowd_after, cut_thr)
     for _ in range(reps):
         for k in scans:
-            got[k].append(cover_run(m, host, k, seed, min_corner, per_cell, crowd_after))
+            got[k].append(cover_run(m, host, k, seed, min_corner, per_cell, crowd_after, cut_thr))
     live, retired = got["torch"][0][0], got["torch"][0][3]
     assert all(r[0] == live and r[3] == retired for rows in got.values() for r in rows), "the two scans kept different queries"
     res = {"config": "360x640 stride 4, no caller queries, cell 32 (12 x 20), chunks of 16, slots 24, library rounds", "T": CHURN_T,
            "seed": seed, "min_corner": min_corner, "per_cell": per_cell, "crowd_after": crowd_after if per_cell is not None else None,
+           "image_changes_before": [(j * CHURN_T + cuts) // (cuts + 1) for j in range(1, cuts + 1)], "cut_thr": cut_thr,
            "pushes": len(live), "live_per_push": live, "retired": retired}
     for k, rows in got.items():
         res[f"{k}_push_ms"] = round(statistics.median(t for r in rows for t in r[1][2:]) * 1e3, 2)
@@ -233,10 +245,12 @@ def main():
                     "are made and every seed stays on its centre, which prices the tables alone)")
     ap.add_argument("--per-cell", type=int, default=None, help="with --cover: at most this many tracks to a cell (the thin step)")
     ap.add_argument("--crowd-after", type=int, default=4, help="with --per-cell: surplus frames in a row before a track is retired")
+    ap.add_argument("--cuts", type=int, default=0, help="with --cover: the synthetic image changes this many times")
+    ap.add_argument("--cut-thr", type=float, default=None, help="with --cover: end the tracks at scene cuts (Cover(cut_thr=))")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.cover:
-        print(json.dumps(compare_cover(dev, a.reps, a.seed, a.min_corner, a.per_cell, a.crowd_after)))
+        print(json.dumps(compare_cover(dev, a.reps, a.seed, a.min_corner, a.per_cell, a.crowd_after, a.cuts, a.cut_thr)))
         return
     q = queries(dev)
     if a.churn:
