@@ -31,16 +31,22 @@ The chaining drivers take ``engine="torch" | "native"``: one hop loop (``_chain`
 state.  ``_TorchEngine`` (the default) keeps the hop's bookkeeping -- the indexed read of the start positions, the scatters into
 the trajectory, the sigmoid, ``skip_scan``, the index update -- as the torch ops of ``_hop``; ``_NativeEngine`` runs the whole hop as
 ONE library call (``Pips.chain_hop``: the same bookkeeping as HIP kernels around the same tracker launches, state held as int32)
-and reads the live count back, one host sync per hop either way.  Both give the same hops and the same bits.  ``StreamTracker``
-also takes ``rounds="torch" | "library"`` and keeps its device state in one object per value: ``_TorchRounds`` decides who is ready,
-who joins and which frames are final in torch ops and hops on the chosen engine; for ``_LibraryRounds`` the round itself is one
-``pips_stream_round`` call on int32 state.  Queries can be added while the video runs (``add_queries``, either value) and taken
-away again (``remove_queries``: the state's ``keep`` copies the remaining columns into narrower arrays -- ``pips_stream_keep`` under
-``rounds="library"``), so the device state follows the number of queries being tracked, not the number ever given.
+and reads the live count back, one host sync per hop either way.  Both give the same hops and the same bits.
+
+The streamed trackers are ONE core, ``_StreamCore``, whose docstring states their rules -- when a query is ready, how it joins, when
+a frame is final, how much room a push has: ``StreamTracker`` is its one-stream form on one ring, ``MultiStreamTracker`` its form on V
+rings behind a clip table.  Both take ``rounds="torch" | "library"`` and keep the device state in one object per value, for one
+stream or V: ``_TorchRounds`` decides who is ready, who joins and which frames are final in torch ops and hops on the chosen engine;
+for ``_LibraryRounds`` the round itself is one ``pips_stream_round`` / ``pips_stream_round_clips`` call on int32 state.  The clip table
+is optional in both, as it is in the library (a NULL table is the one-video form): it decides which entry points are called,
+nothing else.  Queries can be added while a video runs (``add_queries``, either value) and taken away again (``remove_queries``: the
+state's ``keep`` copies the remaining columns into narrower arrays -- ``pips_stream_keep`` under ``rounds="library"``), so the device
+state follows the number of queries being tracked, not the number ever given.
 """
 from __future__ import annotations
 
 import math
+import weakref
 
 import torch
 
@@ -387,29 +393,44 @@ def _longer(old, new):                                    # the per-query array 
     return torch.cat([old, new.to(old.device, old.dtype).reshape((-1,) + tuple(old.shape[1:]))])
 
 
+_INT_MAX = 2 ** 31 - 1                                       # the int32 "nothing pending" / "no limit" of the library's counts and rules
+
+
 class _Rounds:
-    """The device state of a ``StreamTracker``, in the form its ``rounds`` value takes.  Both forms hold the output rows -- trajs
-    (L,N,2) and vis (L,N), frame f in row f % L, NaN where nothing was written -- and the queries ``tq`` / ``xy``, and offer
-      start(dev) / grow(t, xy, m)   the state of the tracker's N queries, none joined / m more columns, the old ones copied
+    """The device state of a stream tracker (``_StreamCore``), in the form its ``rounds`` value takes, for the queries of V >= 1
+    streams.  Both forms hold the output rows -- trajs (L,N,2) and vis (L,N), frame f in row f % L, NaN where nothing was written
+    -- the queries ``tq`` / ``xy``, the stream ``clip`` (N) of each query, and the host list ``final`` (V) of the streams that ended.
+      start(dev) / grow(t, xy, m, v)   the state of the tracker's N queries, none joined / m more columns for stream v
       keep(idx)      only the columns idx (host int64, ascending) remain, in narrower arrays; the others are forgotten
-      pending()      lowest window start of the unfinished queries (None when all are finished)
-      run(final)     hop rounds until no query is ready -- one whose 8 window frames have all arrived (final: every unfinished
-                     one); yields (active indices, steps) per round ((None, None) when a library round keeps no steps)
-      emit(f0, f1)   the rows of frames [f0, f1) moved out of the ring (their rows are reset to NaN for reuse)"""
+      end(v, final=True)   stream v has ended: its unfinished queries are ready, their windows repeat its last frame (False: a
+                     cut takes the mark back)
+      lows()         per stream, the lowest window start of its unfinished queries (None: it has none)
+      run()          hop rounds until no query of any stream is ready (the core's readiness rule); yields (active indices,
+                     steps) per round ((None, None) when a library round keeps no steps)
+      emit(f0, f1, cols)   the rows of frames [f0, f1) of one stream's columns ``cols`` (host int64) moved out of the ring (NaN
+                     is left behind for reuse)
+    ``table`` says whether the cache has a clip table (``Pips.ring_cache_videos``: V rings) or is the one ring of one video
+    (``Pips.ring_cache``: then V = 1 and ``clip`` is all zero).  It decides only what the model and the library are handed --
+    ``_handed`` and the entry points next to it: the clip-table forms, or the NULL-table forms the one-video tracker always used."""
 
     def __init__(self, tracker, engine):
-        self.t, self.engine = tracker, engine
+        # (a weak reference: no cycle, so a dropped tracker gives its ring and its rows back at once, not at some later collection)
+        self.t, self.engine = weakref.proxy(tracker), engine
 
     def start(self, dev):
         t = self.t
         L = t.slots + t.S                                                         # output rows: frames f live in row f % L
+        self.table = t.table
         self.trajs = torch.full((L, t.N, 2), float("nan"), dtype=torch.float32, device=dev)
         self.vis = torch.full((L, t.N), float("nan"), dtype=torch.float32, device=dev)
-        self.tq, self.xy = t.tq_host.to(dev), t.xy_in.to(dev, torch.float32)
+        self.tq, self.xy, self.clip = t.tq_host.to(dev), t.xy_in.to(dev, torch.float32), t.clip_host.to(dev)
+        self.final = [False] * t.V
+        self.final_d = torch.zeros(t.V, dtype=torch.bool, device=dev) if self.table else None      # ``final`` as the table form reads it
 
-    def grow(self, t, xy, m):
+    def grow(self, t, xy, m, v):
         self.trajs, self.vis = _wider(self.trajs, m), _wider(self.vis, m)
         self.tq, self.xy = _longer(self.tq, t), _longer(self.xy, xy)
+        self.clip = _longer(self.clip, torch.full((m,), v)) if self.t.V > 1 else self.clip.new_zeros(self.clip.shape[0] + m)
 
     def _keep_torch(self, idx, names):
         """the torch form of ``keep``: the arrays ``names`` indexed on their query axis -> idx on the device"""
@@ -417,17 +438,27 @@ class _Rounds:
         self.trajs, self.vis = self.trajs.index_select(1, i), self.vis.index_select(1, i)       # (new, contiguous tensors)
         for k in names:
             setattr(self, k, getattr(self, k)[i])
+        self.clip = self.clip[i] if self.t.V > 1 else self.clip[:i.numel()]
         return i
+
+    def end(self, v, final=True):
+        self.final[v] = final
+        if self.table:
+            self.final_d[v:v + 1].fill_(int(final))
+
+    def _handed(self):
+        """(final, clip) as the model and the library take them: the tables, or the one stream's bool and no clip"""
+        return (self.final_d, self.clip) if self.table else (self.final[0], None)
 
 
 class _TorchRounds(_Rounds):
     """``rounds="torch"``: which queries are ready, which join (``joined``) and which are finished (``done``) is decided here in
-    torch ops; the hop is a window of the chosen hop engine on the row ring (base 0), which holds the window starts ``cur``
-    (= t_q until a query joins) and the first-window features."""
+    torch ops; the hop is a window of the chosen hop engine on the row ring (base 0) -- ``_hop(..., clip=)`` on a cache of rings --
+    which holds the window starts ``cur`` (= t_q until a query joins) and the first-window features."""
 
     def _engine(self, cur0, feat=None):
         t = self.t
-        self.eng = _ENGINES[self.engine](t.model, t.cache, self.trajs, self.vis, 0, cur0, None, None, None, t.iters, False)
+        self.eng = _ENGINES[self.engine](t.model, t.cache, self.trajs, self.vis, 0, cur0, None, self._handed()[1], None, t.iters, False)
         self.eng.feat = feat
 
     cur = property(lambda self: self.eng.cur)
@@ -437,8 +468,8 @@ class _TorchRounds(_Rounds):
         self.joined, self.done = (torch.zeros(self.t.N, dtype=torch.bool, device=dev) for _ in range(2))
         self._engine(self.tq)
 
-    def grow(self, t, xy, m):
-        super().grow(t, xy, m)
+    def grow(self, t, xy, m, v):
+        super().grow(t, xy, m, v)
         self.joined, self.done = _longer(self.joined, torch.zeros(m)), _longer(self.done, torch.zeros(m))
         feat = self.eng.feat
         self._engine(_longer(self.eng.cur, t), None if feat is None else _longer(feat, torch.zeros(m, feat.shape[1])))
@@ -448,14 +479,29 @@ class _TorchRounds(_Rounds):
         i = self._keep_torch(idx, ("tq", "xy", "joined", "done"))
         self._engine(cur[i], None if feat is None else feat[i])                    # (the engine is rebuilt as ``grow`` rebuilds it)
 
-    def pending(self):
-        live = self.eng.cur[~self.done]
-        return None if live.numel() == 0 else int(live.min())
+    def lows(self):
+        live, cur = ~self.done, self.eng.cur                                      # (int64, or the native engine's int32)
+        if self.t.V == 1:                                                         # one stream: a plain minimum, no scatter
+            live = cur[live]
+            return [None if live.numel() == 0 else int(live.min())]
+        low = torch.full((self.t.V,), _INT_MAX, dtype=cur.dtype, device=cur.device)      # (one host read)
+        low = low.scatter_reduce(0, self.clip[live], cur[live], "amin")
+        return [None if x == _INT_MAX else x for x in low.tolist()]
 
-    def run(self, final):
-        t, eng, T, L = self.t, self.eng, self.t.cache.T, self.trajs.shape[0]
+    def _ends(self):
+        """-> (the queries whose window can run now, ``ended(active, c)``: which of the hopped ones are finished, or None: none is),
+        by the frames T and the end ``fin`` of each query's OWN stream -- (n) tensors through the table, two scalars without one"""
+        cur, S = self.eng.cur, self.t.S
+        if self.table:
+            T, fin = self.t.cache.clip_frames.to(torch.int64)[self.clip], self.final_d[self.clip]
+            return ~self.done & torch.where(fin, cur < T, cur + S <= T), lambda active, c: fin[active] & (c >= T[active])
+        T, fin = self.t.cache.T, self.final[0]
+        return ~self.done & ((cur < T) if fin else (cur + S <= T)), (lambda active, c: c >= T) if fin else None
+
+    def run(self):
+        t, eng, L, clip = self.t, self.eng, self.trajs.shape[0], self._handed()[1]
         while True:
-            ready = ~self.done & ((eng.cur < T) if final else (eng.cur + t.S <= T))
+            ready, ended = self._ends()
             active = torch.nonzero(ready).squeeze(1)
             if active.numel() == 0:
                 return
@@ -463,28 +509,32 @@ class _TorchRounds(_Rounds):
             if new.numel() > 0:
                 # first window: the start is the query and the features are its point sample at t_q (feat_init=None)
                 self.trajs[self.tq[new] % L, new] = self.xy[new]
+                ring = {} if clip is None else {"win_clip": clip[new].to(torch.int32).unsqueeze(0)}
                 ff = t.model.track(t.cache, self.xy[new].unsqueeze(0), iters=0, return_feat=True,
-                                   win_start=self.tq[new].to(torch.int32).unsqueeze(0))[3]
+                                   win_start=self.tq[new].to(torch.int32).unsqueeze(0), **ring)[3]
                 if eng.feat is None:
                     eng.feat = ff.new_zeros(self.tq.shape[0], ff.shape[-1])
                 eng.feat[new] = ff[0]
                 self.joined[new] = True
             c, si = eng.window(active)
-            if final:
-                self.done[active] = c >= T
+            if ended is not None:
+                self.done[active] = ended(active, c)
             yield active, si
 
-    def emit(self, f0, f1):
+    def emit(self, f0, f1, cols):
         rows = torch.arange(f0, f1, device=self.trajs.device) % self.trajs.shape[0]
-        out = (self.trajs[rows], self.vis[rows])
-        self.trajs[rows] = self.vis[rows] = float("nan")
+        at = (rows.unsqueeze(1), cols.to(rows.device).unsqueeze(0)) if self.table else rows      # one stream: its columns are the rows
+        out = (self.trajs[at], self.vis[at])
+        self.trajs[at] = float("nan")
+        self.vis[at] = float("nan")
         return out
 
 
 class _LibraryRounds(_Rounds):
-    """``rounds="library"``: the int32 / float arrays of ``pips_stream_round`` (include/pips_hip.h) -- ``status`` (0 waiting, 1
-    joined, 2 done), ``cur``, ``feat``, the lists ``active`` / ``new_list`` / ``steps`` a round writes and its four ``counts`` -- and
-    ``low``, the host copy of counts[2].  The hop is the library's, so the engine is not looked at."""
+    """``rounds="library"``: the int32 / float arrays of ``pips_stream_round`` / ``pips_stream_round_clips`` (include/pips_hip.h) --
+    ``status`` (0 waiting, 1 joined, 2 done), ``cur``, ``feat``, ``clip``, the lists ``active`` / ``new_list`` / ``steps`` a round writes
+    and its ``counts``: four, the low in counts[2], or with a table 4 + V, the streams' lows behind the four -- and ``low`` (V), the
+    host copy of those lows.  The hop is the library's, so the engine is not looked at."""
 
     def _lists(self):
         """the lists a round writes, for the queries there are now (their contents do not outlive a push)"""
@@ -492,51 +542,74 @@ class _LibraryRounds(_Rounds):
         self.active, self.new_list = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
         self.steps = torch.empty(n, dtype=torch.int32, device=dev) if self.t.hops is not None else None
 
+    def _lows(self, counts):
+        self.low = [None if x == _INT_MAX else x for x in (counts[4:] if self.table else counts[2:3])]
+
     def start(self, dev):
         super().start(dev)
-        n, i32 = self.t.N, torch.int32
-        self.tq, self.xy = self.tq.to(i32), self.xy.contiguous()
+        t, i32 = self.t, torch.int32
+        self.tq, self.xy, self.clip = self.tq.to(i32), self.xy.contiguous(), self.clip.to(i32)
         self.cur = self.tq.clone()                                                # window start (= t_q until it joins)
-        self.status, self.counts = torch.zeros(n, dtype=i32, device=dev), torch.zeros(4, dtype=i32, device=dev)
-        self.feat = torch.zeros(n, 128, dtype=torch.float32, device=dev)
+        self.status = torch.zeros(t.N, dtype=i32, device=dev)
+        self.feat = torch.zeros(t.N, 128, dtype=torch.float32, device=dev)
+        if self.table:
+            self.counts, self.final_d = torch.zeros(4 + t.V, dtype=i32, device=dev), self.final_d.to(i32)
+        else:
+            self.counts = torch.zeros(4, dtype=i32, device=dev)
         self._lists()
-        self.low = None if n == 0 else int(self.t.tq_host.min())
+        self.low = [None] * t.V
+        for v, tq in zip(t.clip_host.tolist(), t.tq_host.tolist()):
+            self.low[v] = tq if self.low[v] is None else min(self.low[v], tq)
 
-    def grow(self, t, xy, m):
-        super().grow(t, xy, m)
+    def grow(self, t, xy, m, v):
+        super().grow(t, xy, m, v)
         self.cur, self.status = _longer(self.cur, t), _longer(self.status, torch.zeros(m))
         self.feat = _longer(self.feat, torch.zeros(m, self.feat.shape[1]))
         self._lists()
-        self.low = int(t.min()) if self.low is None else min(self.low, int(t.min()))
+        self.low[v] = int(t.min()) if self.low[v] is None else min(self.low[v], int(t.min()))
 
     def keep(self, idx):
         # one pips_stream_keep call; its counts are what a select over the kept queries would report (the one host read)
+        table = dict(clip=self.clip, V=self.t.V) if self.table else {}
         *arrays, counts = ops.stream_keep(idx.to(self.tq.device, torch.int32), self.tq, self.xy, self.cur, self.status, self.feat,
-                                          self.trajs, self.vis)
-        self.tq, self.xy, self.cur, self.status, self.feat, self.trajs, self.vis = arrays
+                                          self.trajs, self.vis, **table)
+        self.tq, self.xy, self.cur, self.status, self.feat, self.trajs, self.vis = arrays[:7]
+        self.clip = arrays[7] if self.table else self.clip[:idx.numel()]          # (one stream: all zero)
         self._lists()
-        low = counts.tolist()[2]
-        self.low = None if low == _NO_LOW else low
+        self._lows(counts.tolist())
 
-    def pending(self):
-        return self.low
+    def lows(self):
+        return list(self.low)
 
-    def run(self, final):
-        # select, then one pips_stream_round call per round while any query is ready (one host sync per round: the four counts)
+    def _select(self):
+        c = self.t.cache
+        if self.table:
+            ops.stream_select_clips(self.tq, self.xy, self.cur, self.status, self.clip, c.clip_frames, self.final_d, self.trajs,
+                                    self.active, self.new_list, self.counts)
+        else:
+            ops.stream_select(c.T, self.final[0], self.tq, self.xy, self.cur, self.status, self.trajs, self.active, self.new_list,
+                              self.counts)
+
+    def run(self):
+        # select, then one round call per round while any query of any stream is ready (one host read per round: the counts)
         t = self.t
         if self.tq.shape[0] == 0:
             return
-        ops.stream_select(t.cache.T, final, self.tq, self.xy, self.cur, self.status, self.trajs, self.active, self.new_list, self.counts)
-        n_act, n_new, low, _ = self.counts.tolist()
-        while n_act > 0:
+        final, clip = self._handed()
+        self._select()
+        counts = self.counts.tolist()
+        while counts[0] > 0:
+            n_act, n_new = counts[:2]
             act = self.active[:n_act].clone() if self.steps is not None else None      # the round rewrites the list
             t.model.stream_round(t.cache, final, n_act, n_new, self.tq, self.xy, self.cur, self.status, self.feat, self.trajs,
-                                 self.vis, self.active, self.new_list, self.counts, self.steps, iters=t.iters)
+                                 self.vis, self.active, self.new_list, self.counts, self.steps, iters=t.iters, clip=clip)
             yield act, None if act is None else self.steps[:n_act]
-            n_act, n_new, low, _ = self.counts.tolist()
-        self.low = None if low == 2 ** 31 - 1 else low
+            counts = self.counts.tolist()
+        self._lows(counts)
 
-    def emit(self, f0, f1):
+    def emit(self, f0, f1, cols):
+        if self.table:
+            return ops.stream_emit_cols(self.trajs, self.vis, f0, f1, cols.to(self.trajs.device, torch.int32))
         if self.tq.shape[0] == 0:                                                 # (the library takes no empty state)
             return self.trajs.new_empty(f1 - f0, 0, 2), self.vis.new_empty(f1 - f0, 0)
         return ops.stream_emit(self.trajs, self.vis, f0, f1)
@@ -562,173 +635,333 @@ _ROUNDS = {"torch": _TorchRounds, "library": _LibraryRounds}
 ROUNDS = tuple(_ROUNDS)
 
 
-class StreamTracker:
-    """``track_queries``' forward chains on a video that arrives in chunks, in bounded device memory.
+def _check_frames(frames):
+    if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[2] != 3:
+        raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(frames.shape)}")
 
-    queries (1,N,3) = (t, x, y) as for ``track_queries``; ``t`` may lie beyond the frames pushed so far.  ``push(frames)`` takes
-    the next ``(1,k,3,H,W)`` frames (host or device, uint8 or float, 0..255) and returns ``(f0, trajs (1,m,N,2), vis (1,m,N))``
-    for the frames ``[f0, f0+m)`` that became final (``m`` may be 0); ``finish()`` ends the video and returns the rest.
-    Frame ``t >= t_q`` of a query is the reference's chaining loop (chain_demo.py:40-83) on ``rgbs[:, t_q:]`` -- the forward
-    frames of ``track_queries`` -- and frames before ``t_q`` are NaN (no backward tracking).
-    ``add_queries(queries)`` takes further queries while the video runs, on any frame not yet returned; the outputs of the
-    calls after it have their columns behind the earlier ones, each what a stream given that query up front returns.
 
-    Frames are encoded once into a ring of ``slots`` frames (``Pips.ring_cache``).  A window runs once its 8 frames have
-    arrived (at ``finish()``, past the last frame it repeats it, chain_demo.py:50-52); each round is one hop over every
-    ready particle, new ones joining with their first-window features (the same point sample as ``feat_init=None``).  A
-    frame is final when it lies below every unfinished particle's window start.  ``push`` splits
-    a chunk so that no slot is overwritten while a pending window can still read it: ``slots >= 9`` keeps the 8 frames of
-    a window plus at least one new frame per split.  Device state: the ring, and (slots + 8) output rows per query being
-    tracked: ``remove_queries(cols)`` takes queries away while the video runs and gives their rows and their share of every
-    round back, so the state follows the queries there are, not the ones there ever were.
+class _StreamCore:
+    """``track_queries``' forward chains on V >= 1 videos of one frame size that arrive in chunks, in bounded device memory: what
+    ``StreamTracker`` (one video, ``table=False``) and ``MultiStreamTracker`` (``table=True``) are facades of.  Every stream has its own
+    length, chunking, queries and end.  The rules, stated here once:
 
-    The tracker keeps what every ``rounds`` / ``engine`` value shares; the device state and the rounds are ``self.state``:
-    ``_TorchRounds`` (``rounds="torch"``, the default: a ``model.track`` call per round or, with ``engine="native"``, one
-    ``pips_chain_hop`` call) or ``_LibraryRounds`` (``rounds="library"``: a round is ONE ``pips_stream_round`` call, ``engine`` is not
-    looked at).  Same hops and the same bits either way."""
+    Frames.  Each stream's frames are encoded once into its ring of ``slots`` frames -- the one ring of ``Pips.ring_cache`` without a
+      clip table, V rings on one flat cache (``Pips.ring_cache_videos``) with one.  ``T_v`` is the number of frames stream v has got.
+    Readiness.  A query is READY once the 8 frames of its window have arrived, ``cur + 8 <= T_v``; after the end of its stream
+      (``finish``) every unfinished query is ready, and a window past the last frame repeats it (chain_demo.py:50-52).
+    Rounds and joining.  A round is ONE hop over the ready queries of every stream (V cameras fill the mixer's rows together).  A
+      query JOINS in its first round: its start is the query position and its features are the point sample at ``t_q`` (the
+      sample of ``feat_init=None``), carried from then on.  After each wave of appended frames the rounds run until no query is ready.
+    Final frames.  A frame of stream v is FINAL, and handed out, when it lies below ``low_v``, the lowest window start of the
+      stream's unfinished queries: ``push`` / ``finish`` return the frames ``[emitted_v, min(low_v, T_v))``.  Frame ``t >= t_q`` of a
+      query is the reference's chaining loop (chain_demo.py:40-83) on ``rgbs[:, t_q:]``; frames before ``t_q`` are NaN.
+    Room.  ``push`` splits a stream's chunk so that no slot is overwritten while a pending window can still read it: a wave appends
+      at most ``min(slots, low_v + slots - T_v)`` frames to stream v; ``slots >= 9`` keeps a window plus one new frame per split.
+
+    The state has one column per query -- those of stream 0, then of stream 1, ..., then the ones ``add_queries`` brought, in
+    ``tq_host`` / ``xy_in`` / ``clip_host`` / ``hops`` on the host and in ``self.state`` on the device (``_TorchRounds`` or ``_LibraryRounds`` by
+    ``rounds``: (slots + 8) output rows per query being tracked); ``columns(v)`` are the columns of stream v, in the order of its
+    outputs.  ``engine="native"`` (``rounds="torch"``) needs the one-ring cache.  Same hops and the same bits under every value."""
 
     S = 8
 
-    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
+    def __init__(self, model, queries_list, iters, slots, record_hops, engine, rounds, table, joint_encode=False, cover=None):
         _check_engine(engine)
+        if table and engine != "torch":
+            raise ValueError('engine="native" hops on one ring: pips_chain_hop_clips takes no ring size beside its clip table')
         if rounds not in ROUNDS:
             raise ValueError(f"rounds must be one of {ROUNDS}, not {rounds!r}")
-        self.engine, self.rounds = engine, rounds
         assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
         if int(slots) < self.S + 1:
             raise ValueError(f"slots must be at least {self.S + 1} (one window and a new frame), not {slots}")
-        self.model, self.iters, self.slots = model, iters, int(slots)
-        self.tq_host = _query_frames(queries)
-        self.xy_in = queries[0, :, 1:3]
+        queries_list = list(queries_list)
+        if not queries_list or not (table or len(queries_list) == 1):
+            raise ValueError("a stream tracker needs at least one stream, and a clip table for more than one")
+        self.model, self.iters, self.slots, self.engine, self.rounds = model, iters, int(slots), engine, rounds
+        self.table, self.joint_encode, self.V = table, bool(joint_encode), len(queries_list)
+        self._of = (lambda v: f" of stream {v}") if table else (lambda v: "")      # (for the messages)
+        tqs = [_query_frames(q) for q in queries_list]
+        self.tq_host = torch.cat(tqs)
+        self.xy_in = torch.cat([q[0, :, 1:3] for q in queries_list])
+        self.clip_host = torch.cat([torch.full((t.numel(),), v, dtype=torch.int64) for v, t in enumerate(tqs)])
         self.N = self.tq_host.numel()
-        self.cache = None
-        self.finished = False
-        self.emitted = 0                                                          # frames [0, emitted) returned
-        self.hops = [[] for _ in range(self.N)] if record_hops else None       # frame steps per query (grows with T)
-        self.cut_hops = None                                                      # the hop lists of the columns at the last cut()
-        self.state = _ROUNDS[rounds](self, engine)                                # the device state, made at the first push
+        self.cache = self.size = None                                             # made by the first push: it brings the frame size
+        self.finished, self.emitted = [False] * self.V, [0] * self.V                # per stream; frames [0, emitted[v]) returned
+        self.hops = [[] for _ in range(self.N)] if record_hops else None          # frame steps per column (grows with T)
+        self.cut_hops = None                                                      # the hop lists of a stream's columns at its last cut
+        self.state = _ROUNDS[rounds](self, engine)                                # the device state, started by the first push
+        self.cover = cover
+        self.books = None if cover is None else [_CoverBook(cover, t, record_hops) for t in tqs]
 
     # the state's output rows (slots + 8, N, 2) / (slots + 8, N) and window starts (N,)
     trajs, vis, cur = (property(lambda self, k=k: getattr(self.state, k)) for k in ("trajs", "vis", "cur"))
 
-    def add_queries(self, queries):
-        """Further queries (1,m,3) = (t, x, y) while the video runs -> the columns (m,) they take in the outputs of the ``push``
-        / ``finish`` calls from now on, behind the queries already there.  ``t`` is an integer frame that was not returned yet
-        (``t >= self.emitted``; it may lie beyond the frames pushed so far): such a frame is still in the ring, so the new
-        column is what a stream given the query up front returns -- NaN before ``t``, the forward chain from ``t`` on.
-        ValueError, with the tracker left as it was, for any other ``t`` and after ``finish()``."""
-        if self.finished:
-            raise ValueError("add_queries() after finish()")
+    def stream_ids(self, v):
+        """the identity of each output column of stream ``v`` of a covered tracker (host int64)"""
+        return torch.tensor(self.books[v].ids, dtype=torch.int64)
+
+    def cover_hops(self, v):
+        """the hop list of each identity of stream ``v`` of a covered tracker (``record_hops=True``)"""
+        return self.books[v].all_hops(self.stream_hops(v))
+
+    def _uncovered(self, what):
+        if self.cover is not None:
+            raise ValueError(f"{what}() on a covered tracker: its cover adds and removes the queries")
+
+    def columns(self, v):
+        """the columns of the state that hold stream ``v``'s queries, in the order of its outputs (host int64)"""
+        return torch.arange(self.N) if self.V == 1 else torch.nonzero(self.clip_host == v).squeeze(1)
+
+    def count(self, v):
+        """the number of stream ``v``'s queries"""
+        return self.N if self.V == 1 else int((self.clip_host == v).sum())
+
+    def stream_hops(self, v):
+        """the frame steps of each query of stream ``v`` (``record_hops=True``)"""
+        return [self.hops[c] for c in self.columns(v).tolist()]
+
+    def frames(self, v):
+        """T_v: the frames stream ``v`` has got"""
+        if self.cache is None:
+            return 0
+        return self.cache.clip_lengths[v] if self.table else self.cache.T
+
+    def _stream(self, v):
+        if not (isinstance(v, int) and 0 <= v < self.V):
+            raise ValueError(f"stream must be an int in [0, {self.V - 1}], not {v!r}")
+        return v
+
+    def add_queries(self, v, queries):
+        """Further queries (1,m,3) = (t, x, y) for stream ``v`` while it runs -> the positions (m,) they take among stream ``v``'s
+        output columns in the ``push`` / ``finish`` calls from now on, behind the queries already there.  ``t`` is an integer frame of
+        that stream that was not returned yet (``t >= emitted[v]``; it may lie beyond the frames pushed so far): such a frame is
+        still in the ring, so the new column is what a stream given the query up front returns -- NaN before ``t``, the forward
+        chain from ``t`` on.  ValueError, with the tracker left as it was, for any other ``t`` and after the stream's ``finish``."""
+        self._uncovered("add_queries")
+        return self._add_queries(v, queries)
+
+    def _add_queries(self, v, queries):
+        v = self._stream(v)
+        if self.finished[v]:
+            raise ValueError(f"add_queries() after finish(){self._of(v)}")
         t = _query_frames(queries)
-        if bool((t < self.emitted).any()):
-            raise ValueError(f"a query frame lies before frame {self.emitted}: frames [0, {self.emitted}) were returned already")
-        m, N = t.numel(), self.N
+        if bool((t < self.emitted[v]).any()):
+            raise ValueError(f"a query frame lies before frame {self.emitted[v]}{self._of(v)}: those frames were returned already")
+        m, n_v = t.numel(), self.count(v)
         xy = queries[0, :, 1:3]
         self.tq_host = torch.cat([self.tq_host, t])
         self.xy_in = torch.cat([self.xy_in, xy.to(self.xy_in.device, self.xy_in.dtype)])
-        self.N = N + m
+        self.clip_host = torch.cat([self.clip_host, torch.full((m,), v, dtype=torch.int64)])
+        self.N += m
         if self.hops is not None:
             self.hops += [[] for _ in range(m)]
         if self.cache is not None and m > 0:
-            self.state.grow(t, xy, m)
-        return torch.arange(N, N + m)
+            self.state.grow(t, xy, m, v)
+        return torch.arange(n_v, n_v + m)
 
     @torch.no_grad()
-    def remove_queries(self, cols):
-        """Stop tracking the queries in the output columns ``cols`` (a tensor or a sequence of current columns) -> ``keep``, a host
-        int64 tensor with the former column of each column that remains, ascending.  From this call on the removed queries are
-        not hopped, do not hold back the frames of the others or the room for new frames, and have no column in what ``push`` /
-        ``finish`` return: the remaining columns keep their order, ``add_queries`` puts new ones behind them, and ``tq_host``,
-        ``xy_in``, ``N``, ``hops`` and the device state shrink (the state's ``keep``).  ``finish()`` no longer looks at a removed
-        query: this is how one on a frame that will never come is cancelled.  Frames of a removed query that were not returned
-        yet are DISCARDED; frames of the remaining queries that the removed ones held back become final and are returned by the
-        next ``push`` / ``finish``.  Each remaining column stays what a stream given only the remaining queries up front returns
-        (the clause of ``add_queries``).  Works before the first ``push``, with no column and with every column.
-        ValueError, with the tracker left as it was, for a column outside ``[0, N)``, a duplicate and after ``finish()``."""
-        if self.finished:
-            raise ValueError("remove_queries() after finish()")
-        cols, keep = _kept(cols, self.N, "the columns to remove")
+    def remove_queries(self, v, cols):
+        """Stop tracking the queries at the positions ``cols`` (a tensor or a sequence) among stream ``v``'s output columns -> ``keep``,
+        a host int64 tensor with the former position of each of that stream's columns that remains, ascending.  From this call on
+        the removed queries are not hopped, do not hold back the frames of the others or the room for new frames, and have no
+        column in what ``push`` / ``finish`` return: the remaining columns keep their order, ``add_queries`` puts new ones behind them,
+        and ``tq_host``, ``xy_in``, ``clip_host``, ``N``, ``hops`` and the device state shrink (the state's ``keep``); the other streams are
+        untouched.  ``finish`` no longer looks at a removed query: this is how one on a frame that will never come is cancelled.
+        Frames of a removed query that were not returned yet are DISCARDED; frames of the remaining queries that the removed ones
+        held back become final and are returned by the stream's next ``push`` / ``finish``.  Each remaining column stays what a stream
+        given only the remaining queries up front returns (the clause of ``add_queries``).  Works before the first ``push``, with no
+        column and with every column.  ValueError, with the tracker left as it was, for a bad stream, a position outside the
+        stream's columns, a duplicate and after the stream's ``finish``."""
+        self._uncovered("remove_queries")
+        return self._remove_queries(v, cols)
+
+    def _remove_queries(self, v, cols):
+        v = self._stream(v)
+        if self.finished[v]:
+            raise ValueError(f"remove_queries() after finish(){self._of(v)}")
+        mine = self.columns(v)
+        cols, keep_v = _kept(cols, mine.numel(), f"the columns to remove{self._of(v)}")
         if cols.numel() == 0:
-            return keep
+            return keep_v
+        keep = keep_v if self.V == 1 else _kept(mine[cols], self.N, "the columns to remove")[1]
         self.tq_host, self.xy_in = self.tq_host[keep], self.xy_in[keep.to(self.xy_in.device)]
+        self.clip_host = self.clip_host[keep]
         self.N = keep.numel()
         if self.hops is not None:
             self.hops = [self.hops[k] for k in keep.tolist()]
         if self.cache is not None:
             self.state.keep(keep)
-        return keep
+        return keep_v
 
     @torch.no_grad()
-    def push(self, frames):
-        if self.finished:
-            raise ValueError("push() after finish()")
-        if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[2] != 3:
-            raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(frames.shape)}")
-        if self.cache is None:
-            self.size = tuple(frames.shape[3:])
-            self.cache = self.model.ring_cache(*self.size, self.slots)
+    def push(self, chunks):
+        """``chunks``: one ``(1,k_v,3,H,W)`` tensor (host or device, uint8 or float, 0..255; ``k_v`` may be 0) or ``None`` per stream
+        -> per stream ``(f0, trajs (1,m,N_v,2), vis (1,m,N_v))``, its frames ``[f0, f0 + m)`` that became final (``m`` may be 0),
+        with ``ids (N_v,)`` behind them on a covered tracker.  ValueError, ahead of the first append, for a chunk that is not
+        such a tensor, another frame size and a finished stream."""
+        chunks = list(chunks)
+        if len(chunks) != self.V:
+            raise ValueError(f"push() takes one chunk (or None) per stream: {self.V}, not {len(chunks)}")
+        size = self.size
+        for v, c in enumerate(chunks):                                             # every check ahead of the first append
+            if c is None:
+                continue
+            if self.finished[v]:
+                raise ValueError(f"push() after finish(){self._of(v)}")
+            _check_frames(c)
+            size = tuple(c.shape[3:]) if size is None else size
+            if tuple(c.shape[3:]) != size:
+                raise ValueError(f"frames of {tuple(c.shape[3:])} pushed to a stream of {size}")
+        if self.cache is None and size is not None:
+            self.size = size
+            self.cache = self.model.ring_cache_videos(*size, self.slots, self.V) if self.table else self.model.ring_cache(*size, self.slots)
             self.state.start(self.cache.device)
-        elif tuple(frames.shape[3:]) != self.size:
-            raise ValueError(f"frames of {tuple(frames.shape[3:])} pushed to a stream of {self.size}")
-        f0, outs = self.emitted, []
-        k, i = frames.shape[1], 0
-        while i < k:
-            low = self.state.pending()
-            # the slot of frame T + j holds frame T + j - slots until then: no pending window may still read that one
-            room = self.slots if low is None else min(self.slots, low + self.slots - self.cache.T)
-            n = min(k - i, room)
-            self.model.encode(frames[:, i:i + n], into=self.cache)
-            i += n
-            outs.append(self._rounds(final=False))
-        return self._cat(f0, outs)
+            for v in range(self.V if self.cover is not None else 0):            # the first cover step of every stream
+                cols = self.columns(v)
+                self.books[v].start(*size, self.cache.device, self.tq_host[cols], self.xy_in[cols.to(self.xy_in.device)],
+                                    *self._cover_acts(v))
+        for v, c in enumerate(chunks if self.cover is not None and self.cover.seed == "corners" else []):
+            if c is not None:                                                     # the tables of what this push brings
+                self.books[v].see(c[0], self.emitted[v], self._cover_acts(v)[0])
+        ids = None if self.cover is None else [self.stream_ids(v) for v in range(self.V)]
+        f0, outs = list(self.emitted), [[] for _ in range(self.V)]
+        left = [0 if c is None else c.shape[1] for c in chunks]
+        while any(left):
+            lows, wave = self.state.lows(), []
+            for v, c in enumerate(chunks):
+                if left[v] == 0:
+                    continue
+                # the room rule: the slot of frame T + j holds frame T + j - slots until then
+                room = self.slots if lows[v] is None else min(self.slots, lows[v] + self.slots - self.frames(v))
+                n, i = min(left[v], room), c.shape[1] - left[v]
+                wave.append((v, c[:, i:i + n]))
+                left[v] -= n
+            if self.joint_encode:
+                self.model.encode_streams(self.cache, wave, joint=True)
+            else:
+                for v, c in wave:
+                    self.model.encode(c, into=self.cache, **({"clip": v} if self.table else {}))
+            for v, rows in self._rounds(range(self.V)).items():
+                outs[v].append(rows)
+        res = [self._cat(v, f0[v], outs[v]) for v in range(self.V)]
+        if self.cover is None:
+            return res
+        for v, (f, t, vi) in enumerate(res):                                       # a cover step on what each stream returned
+            if t.shape[1] > 0:
+                self.books[v].step(f, t[0], vi[0], *self._cover_acts(v), None if self.hops is None else self.stream_hops(v))
+        return [r + (i,) for r, i in zip(res, ids)]
+
+    def _cover_acts(self, v):
+        return (lambda q: self._add_queries(v, q)), (lambda cols: self._remove_queries(v, cols))
 
     @torch.no_grad()
-    def finish(self):
-        if self.finished:
-            raise ValueError("finish() called twice")
-        T = 0 if self.cache is None else self.cache.T
-        if bool((self.tq_host > T - 1).any()):
-            raise ValueError(f"a query frame lies beyond the last frame of the video ({T - 1})")
-        self.finished = True
-        return self._cat(self.emitted, [self._rounds(final=True)])
+    def finish(self, v=None):
+        """End stream ``v`` (-> its tuple, as ``push`` returns it: the rest of its frames) or every stream still running (-> the
+        list; None for one ended before).  ValueError, ahead of any change, for a stream ended before and for a query on a frame
+        beyond the stream's last."""
+        which = [u for u in range(self.V) if not self.finished[u]] if v is None else [self._stream(v)]
+        for u in which:                                                             # every check ahead of the first change
+            if self.finished[u]:
+                raise ValueError(f"finish(){self._of(u)} called twice")
+            T = self.frames(u)
+            if bool((self.tq_host[self.clip_host == u] > T - 1).any()):
+                raise ValueError(f"a query frame lies beyond the last frame{self._of(u)} ({T - 1})")
+        f0, outs = list(self.emitted), {}
+        for u in which:
+            self.finished[u] = True
+            if self.cover is not None:
+                self.books[u].held = None          # (seeds held for a frame that never comes)
+            if self.cache is not None:
+                self.state.end(u)
+        if self.cache is not None and which:
+            outs = self._rounds(which)
+        res = [self._cat(u, f0[u], [outs[u]] if u in outs else []) if u in which else None for u in range(self.V)]
+        if self.cover is not None:                                                  # (no cover step at the end of a stream)
+            res = [None if r is None else r + (self.stream_ids(u),) for u, r in enumerate(res)]
+        return res if v is None else res[v]
 
     @torch.no_grad()
-    def cut(self):
-        """End every query that has started, at the ``T`` frames pushed so far, and keep the stream open -> ``(f0, trajs (1,m,N,2),
-        vis (1,m,N), keep)``: the rounds run as ``finish()`` runs them (windows that reach past frame ``T - 1`` repeat it), ALL the
-        frames ``[f0, T)`` not returned yet come back in the columns as they were at the call, and the queries with ``t < T`` are
-        removed (``remove_queries``: state, rows and hop lists shrink).  ``keep`` holds the former column of each column that
-        remains -- the queries with ``t >= T``, which stay waiting, untouched: on later pushes such a query is what a stream that
-        starts at frame ``T`` returns for it, since a forward window never reads below its start.  ``cut_hops`` is, with
-        ``record_hops``, the hop list of every column as it was at the last cut (None otherwise).  Before the first push no frame
-        is returned and nothing is removed.  ValueError, with the tracker left as it was, after ``finish()``."""
-        if self.finished:
-            raise ValueError("cut() after finish()")
-        self.cut_hops = None if self.hops is None else list(self.hops)
+    def _cut(self, v):
+        """End every query of stream ``v`` that has started, at the ``T_v`` frames pushed so far, and keep the stream open -> ``(f0,
+        trajs (1,m,N_v,2), vis (1,m,N_v), keep)``: the rounds run with the stream marked as ended (windows that reach past frame
+        ``T_v - 1`` repeat it), ALL its frames ``[f0, T_v)`` not returned yet come back in the columns as they were at the call, the
+        queries with ``t < T_v`` are removed (``remove_queries``: state, rows and hop lists shrink) and the mark is taken back.
+        ``keep`` holds the former position of each column that remains -- the queries with ``t >= T_v``, which stay waiting,
+        untouched: on later pushes such a query is what a stream that starts at frame ``T_v`` returns for it, since a forward
+        window never reads below its start.  ``cut_hops`` is, with ``record_hops``, the hop list of each of the stream's columns as
+        it was at the last cut (None otherwise).  Before the first push no frame is returned and nothing is removed.  ValueError,
+        with the tracker left as it was, after the stream's ``finish``."""
+        if self.finished[v]:
+            raise ValueError(f"cut() after finish(){self._of(v)}")
+        self.cut_hops = None if self.hops is None else self.stream_hops(v)
+        mine, f0 = self.columns(v), self.emitted[v]
         if self.cache is None:
-            return self._cat(self.emitted, []) + (torch.arange(self.N),)
-        f0, trajs, vis = self._cat(self.emitted, [self._rounds(final=True)])
-        return f0, trajs, vis, self.remove_queries(torch.nonzero(self.tq_host < self.cache.T).squeeze(1))
+            return self._cat(v, f0, []) + (torch.arange(mine.numel()),)
+        self.state.end(v)
+        outs = self._rounds([v])
+        self.state.end(v, False)
+        started = torch.nonzero(self.tq_host[mine] < self.frames(v)).squeeze(1)
+        return self._cat(v, f0, list(outs.values())) + (self._remove_queries(v, started),)
 
-    def _rounds(self, final):
-        """the state's hop rounds, their steps recorded per query -> the rows of the frames that became final (None: none did)"""
-        for active, steps in self.state.run(final):
+    def _rounds(self, which):
+        """the state's hop rounds over every stream, their steps recorded per column -> {v: the rows of the frames of stream v that
+        became final} for the streams ``which`` that had any (another stream's stay in the ring until it is asked)"""
+        for active, steps in self.state.run():
             if self.hops is not None:
                 for q, h in zip(active.tolist(), steps.tolist()):
                     self.hops[q].append(h)
-        low = self.state.pending()
-        f0, f1 = self.emitted, self.cache.T if low is None else min(low, self.cache.T)
-        if f1 <= f0:
-            return None
-        self.emitted = f1
-        return self.state.emit(f0, f1)
+        lows, outs = self.state.lows(), {}
+        for v in which:
+            T = self.frames(v)
+            f1 = T if lows[v] is None else min(lows[v], T)
+            if f1 > self.emitted[v]:
+                outs[v] = self.state.emit(self.emitted[v], f1, self.columns(v))
+                self.emitted[v] = f1
+        return outs
 
-    def _cat(self, f0, outs):
-        outs = [o for o in outs if o is not None]
+    def _cat(self, v, f0, outs):
         if not outs:
             dev = self.cache.device if self.cache is not None else self.xy_in.device
-            return f0, torch.empty(1, 0, self.N, 2, device=dev), torch.empty(1, 0, self.N, device=dev)
+            return f0, torch.empty(1, 0, self.count(v), 2, device=dev), torch.empty(1, 0, self.count(v), device=dev)
         return f0, torch.cat([o[0] for o in outs]).unsqueeze(0), torch.cat([o[1] for o in outs]).unsqueeze(0)
+
+
+class StreamTracker:
+    """One video that arrives in chunks: the one-stream form of ``_StreamCore`` on the one ring of ``Pips.ring_cache`` (no clip table),
+    whose docstring states the rules -- readiness, joining, when a frame is final, the room of a push.
+
+    queries (1,N,3) = (t, x, y) as for ``track_queries``; ``t`` may lie beyond the frames pushed so far.  ``push(frames)`` takes the
+    next ``(1,k,3,H,W)`` frames and returns ``(f0, trajs (1,m,N,2), vis (1,m,N))`` for the frames ``[f0, f0+m)`` that became final;
+    ``finish()`` ends the video and returns the rest; ``add_queries(queries)`` / ``remove_queries(cols)`` / ``cut()`` are the core's
+    ``add_queries`` / ``remove_queries`` / ``_cut`` for stream 0, in columns of the outputs.  ``rounds="torch"`` (the default) makes a
+    ``model.track`` call per round or, with ``engine="native"``, one ``pips_chain_hop`` call; under ``rounds="library"`` a round is ONE
+    ``pips_stream_round`` call and ``engine`` is not looked at."""
+
+    S = 8
+
+    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
+        self.core = _StreamCore(model, [queries], iters, slots, record_hops, engine, rounds, table=False)
+
+    model, iters, slots, engine, rounds, tq_host, xy_in, N, hops, cut_hops, cache, size, state, trajs, vis, cur = (
+        property(lambda self, k=k: getattr(self.core, k)) for k in (
+            "model", "iters", "slots", "engine", "rounds", "tq_host", "xy_in", "N", "hops", "cut_hops", "cache", "size", "state", "trajs",
+            "vis", "cur"))
+    emitted, finished = (property(lambda self, k=k: getattr(self.core, k)[0]) for k in ("emitted", "finished"))
+
+    def add_queries(self, queries):
+        return self.core.add_queries(0, queries)
+
+    def remove_queries(self, cols):
+        return self.core.remove_queries(0, cols)
+
+    def push(self, frames):
+        return self.core.push([frames])[0]
+
+    def finish(self):
+        return self.core.finish(0)
+
+    def cut(self):
+        return self.core._cut(0)
 
 
 @torch.no_grad()
@@ -747,7 +980,6 @@ def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, e
 
 
 # ---------------------------------------------------------------------------------------------- keeping the frame covered
-_INT_MAX = 2 ** 31 - 1
 COVER_SCANS = ("torch", "library")
 COVER_SEEDS = ("centre", "corners")
 
@@ -1216,11 +1448,6 @@ def _by_identity(parts, book):
     return trajs, vis, torch.tensor(book.born, dtype=torch.int64), retired
 
 
-def _check_frames(frames):
-    if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[2] != 3:
-        raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(frames.shape)}")
-
-
 class CoverTracker:
     """A stream that decides which queries it tracks: a ``StreamTracker`` (driven only through ``add_queries``, ``remove_queries``,
     ``push`` and ``finish``) plus the policy ``cover`` (a ``Cover``).  ``queries`` (1,N,3) or None are the caller's own; they are
@@ -1346,164 +1573,15 @@ def corner_queries(rgbs, t=0, cell=32, min_corner=0, scan="torch"):
 
 
 # ---------------------------------------------------------------------------------------------- several streams at once
-_NO_LOW = 2 ** 31 - 1                                         # the library's "no pending query" (INT_MAX)
-
-
-class _MultiTorchRounds(_Rounds):
-    """``MultiStreamTracker(rounds="torch")``: ``_TorchRounds`` over the queries of V streams in one state.  ``clip`` (n) is the
-    stream of each query; a query is ready, or finished, by the frames and the end of its OWN stream (``cache.clip_frames`` /
-    ``final``), and the hop is ``_hop(..., clip=)`` on the cache of rings."""
-
-    def _engine(self, cur0, feat=None):
-        t = self.t
-        self.eng = _TorchEngine(t.model, t.cache, self.trajs, self.vis, 0, cur0, None, self.clip, None, t.iters, False)
-        self.eng.feat = feat
-
-    cur = property(lambda self: self.eng.cur)
-
-    def start(self, dev):
-        super().start(dev)
-        t = self.t
-        self.clip = t.clip_host.to(dev)
-        self.joined, self.done = (torch.zeros(t.N, dtype=torch.bool, device=dev) for _ in range(2))
-        self.final = torch.zeros(t.V, dtype=torch.bool, device=dev)
-        self._engine(self.tq)
-
-    def grow(self, t, xy, m, v):
-        super().grow(t, xy, m)
-        self.clip = _longer(self.clip, torch.full((m,), v))
-        self.joined, self.done = _longer(self.joined, torch.zeros(m)), _longer(self.done, torch.zeros(m))
-        feat = self.eng.feat
-        self._engine(_longer(self.eng.cur, t), None if feat is None else _longer(feat, torch.zeros(m, feat.shape[1])))
-
-    def keep(self, idx):
-        cur, feat = self.eng.cur, self.eng.feat
-        i = self._keep_torch(idx, ("tq", "xy", "joined", "done", "clip"))
-        self._engine(cur[i], None if feat is None else feat[i])
-
-    def end(self, v):
-        self.final[v] = True
-
-    def lows(self):
-        """per stream, the lowest window start of its unfinished queries (None: it has none); one host read"""
-        live = ~self.done
-        low = torch.full((self.t.V,), _NO_LOW, dtype=torch.int64, device=self.done.device)
-        low = low.scatter_reduce(0, self.clip[live], self.eng.cur[live], "amin")
-        return [None if x == _NO_LOW else x for x in low.tolist()]
-
-    def run(self):
-        t, eng, L = self.t, self.eng, self.trajs.shape[0]
-        while True:
-            T, fin = t.cache.clip_frames.to(torch.int64)[self.clip], self.final[self.clip]      # of each query's own stream
-            ready = ~self.done & torch.where(fin, eng.cur < T, eng.cur + t.S <= T)
-            active = torch.nonzero(ready).squeeze(1)
-            if active.numel() == 0:
-                return
-            new = active[~self.joined[active]]
-            if new.numel() > 0:
-                self.trajs[self.tq[new] % L, new] = self.xy[new]
-                ff = t.model.track(t.cache, self.xy[new].unsqueeze(0), iters=0, return_feat=True,
-                                   win_start=self.tq[new].to(torch.int32).unsqueeze(0),
-                                   win_clip=self.clip[new].to(torch.int32).unsqueeze(0))[3]
-                if eng.feat is None:
-                    eng.feat = ff.new_zeros(self.tq.shape[0], ff.shape[-1])
-                eng.feat[new] = ff[0]
-                self.joined[new] = True
-            c, si = eng.window(active)
-            self.done[active] = fin[active] & (c >= T[active])
-            yield active, si
-
-    def emit(self, f0, f1, cols):
-        rows = (torch.arange(f0, f1, device=self.trajs.device) % self.trajs.shape[0]).unsqueeze(1)
-        cols = cols.to(torch.int64).unsqueeze(0)
-        out = (self.trajs[rows, cols], self.vis[rows, cols])
-        self.trajs[rows, cols] = float("nan")
-        self.vis[rows, cols] = float("nan")
-        return out
-
-
-class _MultiLibraryRounds(_Rounds):
-    """``MultiStreamTracker(rounds="library")``: the arrays of ``pips_stream_round_clips`` (include/pips_hip.h) -- those of
-    ``_LibraryRounds`` plus ``clip`` (n), ``final`` (V) int32 and ``counts`` (4 + V), whose tail is kept on the host as ``low``."""
-
-    def _lists(self):
-        n, dev = self.tq.shape[0], self.tq.device
-        self.active, self.new_list = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
-        self.steps = torch.empty(n, dtype=torch.int32, device=dev) if self.t.hops is not None else None
-
-    def start(self, dev):
-        super().start(dev)
-        t, i32 = self.t, torch.int32
-        self.tq, self.xy = self.tq.to(i32), self.xy.contiguous()
-        self.cur, self.clip = self.tq.clone(), t.clip_host.to(dev, i32)
-        self.status = torch.zeros(t.N, dtype=i32, device=dev)
-        self.counts, self.final = torch.zeros(4 + t.V, dtype=i32, device=dev), torch.zeros(t.V, dtype=i32, device=dev)
-        self.feat = torch.zeros(t.N, 128, dtype=torch.float32, device=dev)
-        self._lists()
-        self.low = [None] * t.V
-        for v, tq in zip(t.clip_host.tolist(), t.tq_host.tolist()):
-            self.low[v] = tq if self.low[v] is None else min(self.low[v], tq)
-
-    def grow(self, t, xy, m, v):
-        super().grow(t, xy, m)
-        self.cur, self.status = _longer(self.cur, t), _longer(self.status, torch.zeros(m))
-        self.clip = _longer(self.clip, torch.full((m,), v))
-        self.feat = _longer(self.feat, torch.zeros(m, self.feat.shape[1]))
-        self._lists()
-        self.low[v] = int(t.min()) if self.low[v] is None else min(self.low[v], int(t.min()))
-
-    def keep(self, idx):
-        *arrays, counts = ops.stream_keep(idx.to(self.tq.device, torch.int32), self.tq, self.xy, self.cur, self.status, self.feat,
-                                          self.trajs, self.vis, clip=self.clip, V=self.t.V)
-        self.tq, self.xy, self.cur, self.status, self.feat, self.trajs, self.vis, self.clip = arrays
-        self._lists()
-        self.low = [None if x == _NO_LOW else x for x in counts.tolist()[4:]]
-
-    def end(self, v):
-        self.final[v:v + 1].fill_(1)
-
-    def lows(self):
-        return list(self.low)
-
-    def run(self):
-        # select, then one pips_stream_round_clips call per round while any query of any stream is ready (one host read per round)
-        t = self.t
-        if self.tq.shape[0] == 0:
-            return
-        cache = t.cache
-        ops.stream_select_clips(self.tq, self.xy, self.cur, self.status, self.clip, cache.clip_frames, self.final, self.trajs,
-                                self.active, self.new_list, self.counts)
-        counts = self.counts.tolist()
-        while counts[0] > 0:
-            n_act, n_new = counts[:2]
-            act = self.active[:n_act].clone() if self.steps is not None else None      # the round rewrites the list
-            t.model.stream_round(cache, self.final, n_act, n_new, self.tq, self.xy, self.cur, self.status, self.feat, self.trajs,
-                                 self.vis, self.active, self.new_list, self.counts, self.steps, iters=t.iters, clip=self.clip)
-            yield act, None if act is None else self.steps[:n_act]
-            counts = self.counts.tolist()
-        self.low = [None if x == _NO_LOW else x for x in counts[4:]]
-
-    def emit(self, f0, f1, cols):
-        return ops.stream_emit_cols(self.trajs, self.vis, f0, f1, cols)
-
-
-_MULTI_ROUNDS = {"torch": _MultiTorchRounds, "library": _MultiLibraryRounds}
-
-
-class MultiStreamTracker:
-    """``StreamTracker`` for V videos of one frame size at once: each stream has its own length, its own chunking, its own queries
-    and its own end, and gets what a ``StreamTracker`` given that stream alone (same chunks, same ``slots``) returns -- bit for bit,
+class MultiStreamTracker(_StreamCore):
+    """``StreamTracker`` for V videos of one frame size at once -- ``_StreamCore`` (whose docstring states the rules) on one cache of V
+    rings of ``slots`` slots (``Pips.ring_cache_videos``) and ONE state, V = 1 included: each stream has its own length, chunking,
+    queries and end, and gets what a ``StreamTracker`` given that stream alone (same chunks, same ``slots``) returns -- bit for bit,
     hop lists included, while the mixer's GEMMs take the same route at both row counts (the contract of ``track_*_batch``).
-
-    The streams share ONE cache of V rings of ``slots`` slots (``Pips.ring_cache_videos``) and ONE state, whose columns are the
-    queries of stream 0, then of stream 1, ... (and, behind them, the ones ``add_queries`` brought), so a round is one hop over
-    the ready queries of EVERY stream: V cameras fill the mixer's rows together instead of running V rounds of a few rows each.
       push(chunks)          a list with one ``(1,k_v,3,H,W)`` tensor or ``None`` per stream (the ``k_v`` may differ) -> per stream
                             ``(f0, trajs (1,m,N_v,2), vis (1,m,N_v))``, the frames of that stream that became final
       finish(v=None)        ends stream ``v`` (-> its tuple) or every stream still running (-> the list; None for one ended before)
-      add_queries(v, q)     ``StreamTracker.add_queries`` for stream ``v``, against that stream's ``emitted[v]``
-    Each stream's chunk is split by its own room, ``min(slots, low_v + slots - T_v)``; after each wave of appends the rounds run
-    until no query of any stream is ready, and frames ``[emitted_v, min(low_v, T_v))`` are handed out per stream.
+      add_queries(v, q) / remove_queries(v, cols)   in positions among stream ``v``'s output columns
     ``rounds="torch"`` hops with ``_hop(..., clip=)``; ``rounds="library"`` makes one ``pips_stream_round_clips`` call per round.
     ``joint_encode=True`` sends the frames one wave appends across all streams through shared encoder passes
     (``Pips.encode_streams(joint=True)``): fuller passes, and maps that differ from the per-stream ones by the encoder's
@@ -1516,218 +1594,13 @@ class MultiStreamTracker:
     ``Cover(seed="corners")`` a push makes one corner table per stream that got a chunk, and the first seeds of a stream whose first
     chunk is ``None`` wait for its first frames, as in ``CoverTracker``."""
 
-    S = 8
-
     def __init__(self, model, queries_list, iters=6, slots=24, record_hops=False, rounds="torch", joint_encode=False, cover=None):
         if cover is not None and not isinstance(cover, Cover):
             raise ValueError(f"cover must be a drivers.Cover or None, not {cover!r}")
         if cover is not None and cover.cut_thr is not None:
             raise ValueError("MultiStreamTracker takes no Cover(cut_thr=): a cut of one stream on the shared rings is not supported")
-        if rounds not in ROUNDS:
-            raise ValueError(f"rounds must be one of {ROUNDS}, not {rounds!r}")
-        assert model.S == 8, "chain_demo.py's visibility scan (frames 7..2 of an 8-frame window) is written for S = 8"
-        if int(slots) < self.S + 1:
-            raise ValueError(f"slots must be at least {self.S + 1} (one window and a new frame), not {slots}")
-        queries_list = list(queries_list)
-        if not queries_list:
-            raise ValueError("MultiStreamTracker needs at least one stream")
-        self.model, self.iters, self.slots, self.rounds, self.joint_encode = model, iters, int(slots), rounds, bool(joint_encode)
-        self.V = len(queries_list)
-        tqs = [_query_frames(q) for q in queries_list]
-        self.tq_host = torch.cat(tqs)
-        self.xy_in = torch.cat([q[0, :, 1:3] for q in queries_list])
-        self.clip_host = torch.cat([torch.full((t.numel(),), v, dtype=torch.int64) for v, t in enumerate(tqs)])
-        self.N = self.tq_host.numel()
-        self.cache = None
-        self.finished, self.emitted = [False] * self.V, [0] * self.V                # per stream; frames [0, emitted[v]) returned
-        self.hops = [[] for _ in range(self.N)] if record_hops else None          # per column of the shared state
-        self.state = _MULTI_ROUNDS[rounds](self, "torch")
-        self.cover = cover
-        self.books = None if cover is None else [_CoverBook(cover, t, record_hops) for t in tqs]
-
-    trajs, vis, cur = (property(lambda self, k=k: getattr(self.state, k)) for k in ("trajs", "vis", "cur"))
-
-    def stream_ids(self, v):
-        """the identity of each output column of stream ``v`` of a covered tracker (host int64)"""
-        return torch.tensor(self.books[v].ids, dtype=torch.int64)
-
-    def cover_hops(self, v):
-        """the hop list of each identity of stream ``v`` of a covered tracker (``record_hops=True``)"""
-        return self.books[v].all_hops(self.stream_hops(v))
-
-    def _uncovered(self, what):
-        if self.cover is not None:
-            raise ValueError(f"{what}() on a covered tracker: its cover adds and removes the queries")
-
-    def columns(self, v):
-        """the columns of the shared state that hold stream ``v``'s queries, in the order of its outputs (host int64)"""
-        return torch.nonzero(self.clip_host == v).squeeze(1)
-
-    def stream_hops(self, v):
-        """the frame steps of each query of stream ``v`` (``record_hops=True``), as ``StreamTracker.hops``"""
-        return [self.hops[c] for c in self.columns(v).tolist()]
-
-    def frames(self, v):
-        return 0 if self.cache is None else self.cache.clip_lengths[v]
-
-    def _stream(self, v):
-        if not (isinstance(v, int) and 0 <= v < self.V):
-            raise ValueError(f"stream must be an int in [0, {self.V - 1}], not {v!r}")
-        return v
-
-    def add_queries(self, v, queries):
-        """Further queries (1,m,3) for stream ``v`` while it runs -> the positions (m,) they take among stream ``v``'s output
-        columns.  ValueError, with the tracker left as it was, for a frame of that stream returned already and after its end."""
-        self._uncovered("add_queries")
-        return self._add_queries(v, queries)
-
-    def _add_queries(self, v, queries):
-        v = self._stream(v)
-        if self.finished[v]:
-            raise ValueError(f"add_queries() after stream {v} was finished")
-        t = _query_frames(queries)
-        if bool((t < self.emitted[v]).any()):
-            raise ValueError(f"a query frame lies before frame {self.emitted[v]} of stream {v}: those frames were returned already")
-        m, n_v = t.numel(), int((self.clip_host == v).sum())
-        xy = queries[0, :, 1:3]
-        self.tq_host = torch.cat([self.tq_host, t])
-        self.xy_in = torch.cat([self.xy_in, xy.to(self.xy_in.device, self.xy_in.dtype)])
-        self.clip_host = torch.cat([self.clip_host, torch.full((m,), v, dtype=torch.int64)])
-        self.N += m
-        if self.hops is not None:
-            self.hops += [[] for _ in range(m)]
-        if self.cache is not None and m > 0:
-            self.state.grow(t, xy, m, v)
-        return torch.arange(n_v, n_v + m)
-
-    @torch.no_grad()
-    def remove_queries(self, v, cols):
-        """``StreamTracker.remove_queries`` for stream ``v``: ``cols`` are positions among stream ``v``'s output columns (the numbering
-        ``add_queries(v, ...)`` reports) -> the former positions of that stream's columns that remain, ascending.  The other streams'
-        outputs and hop lists are untouched; the shared state and ``clip_host`` shrink.  ValueError, with the tracker left as it
-        was, for a bad stream, a position outside the stream's columns, a duplicate and a finished stream."""
-        self._uncovered("remove_queries")
-        return self._remove_queries(v, cols)
-
-    def _remove_queries(self, v, cols):
-        v = self._stream(v)
-        if self.finished[v]:
-            raise ValueError(f"remove_queries() after stream {v} was finished")
-        mine = self.columns(v)
-        cols, keep_v = _kept(cols, mine.numel(), f"the positions to remove from stream {v}")
-        if cols.numel() == 0:
-            return keep_v
-        _, keep = _kept(mine[cols], self.N, "the columns to remove")
-        self.tq_host, self.xy_in = self.tq_host[keep], self.xy_in[keep.to(self.xy_in.device)]
-        self.clip_host = self.clip_host[keep]
-        self.N = keep.numel()
-        if self.hops is not None:
-            self.hops = [self.hops[k] for k in keep.tolist()]
-        if self.cache is not None:
-            self.state.keep(keep)
-        return keep_v
-
-    @torch.no_grad()
-    def push(self, chunks):
-        chunks = list(chunks)
-        if len(chunks) != self.V:
-            raise ValueError(f"push() takes one chunk (or None) per stream: {self.V}, not {len(chunks)}")
-        size = getattr(self, "size", None)
-        for v, c in enumerate(chunks):                                             # every check ahead of the first append
-            if c is None:
-                continue
-            if self.finished[v]:
-                raise ValueError(f"push() to stream {v} after it was finished")
-            if c.dim() != 5 or c.shape[0] != 1 or c.shape[2] != 3:
-                raise ValueError(f"frames must be (1,k,3,H,W), not {tuple(c.shape)}")
-            size = tuple(c.shape[3:]) if size is None else size
-            if tuple(c.shape[3:]) != size:
-                raise ValueError(f"frames of {tuple(c.shape[3:])} pushed to streams of {size}")
-        if self.cache is None and size is not None:
-            self.size = size
-            self.cache = self.model.ring_cache_videos(*size, self.slots, self.V)
-            self.state.start(self.cache.device)
-            for v in range(self.V if self.cover is not None else 0):            # the first cover step of every stream
-                cols = self.columns(v)
-                self.books[v].start(*size, self.cache.device, self.tq_host[cols], self.xy_in[cols.to(self.xy_in.device)],
-                                    *self._cover_acts(v))
-        for v, c in enumerate(chunks if self.cover is not None and self.cover.seed == "corners" else []):
-            if c is not None:                                                     # the tables of what this push brings
-                self.books[v].see(c[0], self.emitted[v], self._cover_acts(v)[0])
-        ids = None if self.cover is None else [self.stream_ids(v) for v in range(self.V)]
-        f0, outs = list(self.emitted), [[] for _ in range(self.V)]
-        left = [0 if c is None else c.shape[1] for c in chunks]
-        while any(left):
-            lows, wave = self.state.lows(), []
-            for v, c in enumerate(chunks):
-                if left[v] == 0:
-                    continue
-                # the slot of frame T + j holds frame T + j - slots until then: no pending window of this stream may still read it
-                room = self.slots if lows[v] is None else min(self.slots, lows[v] + self.slots - self.frames(v))
-                n, i = min(left[v], room), c.shape[1] - left[v]
-                wave.append((v, c[:, i:i + n]))
-                left[v] -= n
-            if self.joint_encode:
-                self.model.encode_streams(self.cache, wave, joint=True)
-            else:
-                for v, c in wave:
-                    self.model.encode(c, into=self.cache, clip=v)
-            self._rounds(outs)
-        res = [self._cat(v, f0[v], outs[v]) for v in range(self.V)]
-        if self.cover is None:
-            return res
-        for v, (f, t, vi) in enumerate(res):                                       # a cover step on what each stream returned
-            if t.shape[1] > 0:
-                self.books[v].step(f, t[0], vi[0], *self._cover_acts(v), None if self.hops is None else self.stream_hops(v))
-        return [r + (i,) for r, i in zip(res, ids)]
-
-    def _cover_acts(self, v):
-        return (lambda q: self._add_queries(v, q)), (lambda cols: self._remove_queries(v, cols))
-
-    @torch.no_grad()
-    def finish(self, v=None):
-        which = [u for u in range(self.V) if not self.finished[u]] if v is None else [self._stream(v)]
-        for u in which:                                                             # every check ahead of the first change
-            if self.finished[u]:
-                raise ValueError(f"finish() of stream {u} called twice")
-            T = self.frames(u)
-            if bool((self.tq_host[self.clip_host == u] > T - 1).any()):
-                raise ValueError(f"a query frame lies beyond the last frame of stream {u} ({T - 1})")
-        f0, outs = list(self.emitted), [[] for _ in range(self.V)]
-        for u in which:
-            self.finished[u] = True
-            if self.cover is not None:
-                self.books[u].held = None          # (seeds held for a frame that never comes)
-            if self.cache is not None:
-                self.state.end(u)
-        if self.cache is not None and which:
-            self._rounds(outs)
-        res = [self._cat(u, f0[u], outs[u]) if u in which else None for u in range(self.V)]
-        if self.cover is not None:                                                  # (no cover step at the end of a stream)
-            res = [None if r is None else r + (self.stream_ids(u),) for u, r in enumerate(res)]
-        return res if v is None else res[v]
-
-    def _rounds(self, outs):
-        """the state's hop rounds over every stream, their steps recorded -> the rows that became final, appended per stream"""
-        for active, steps in self.state.run():
-            if self.hops is not None:
-                for q, h in zip(active.tolist(), steps.tolist()):
-                    self.hops[q].append(h)
-        lows = self.state.lows()
-        for v in range(self.V):
-            T = self.frames(v)
-            f1 = T if lows[v] is None else min(lows[v], T)
-            if f1 > self.emitted[v]:
-                cols = self.columns(v).to(self.cache.device, torch.int32)
-                outs[v].append(self.state.emit(self.emitted[v], f1, cols))
-                self.emitted[v] = f1
-
-    def _cat(self, v, f0, outs):
-        if not outs:
-            dev = self.cache.device if self.cache is not None else self.xy_in.device
-            n = int((self.clip_host == v).sum())
-            return f0, torch.empty(1, 0, n, 2, device=dev), torch.empty(1, 0, n, device=dev)
-        return f0, torch.cat([o[0] for o in outs]).unsqueeze(0), torch.cat([o[1] for o in outs]).unsqueeze(0)
+        super().__init__(model, queries_list, iters, slots, record_hops, "torch", rounds, table=True, joint_encode=joint_encode,
+                         cover=cover)
 
 
 @torch.no_grad()

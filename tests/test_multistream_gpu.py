@@ -314,7 +314,7 @@ def _select_state(n, seed, final, all_done=False):
 
 
 def _expected_select(s):
-    """the lines of drivers._MultiTorchRounds.run / lows that pips_stream_select_clips stands for, on the CPU"""
+    """the lines of drivers._TorchRounds.run / lows (the clip-table form) that pips_stream_select_clips stands for, on the CPU"""
     L = SEL_L
     status, cur, tq, clip = s["status"].clone().long(), s["cur"].long(), s["tq"].long(), s["clip"].long()
     T, fin = s["frames"].long()[clip], s["final"][clip] != 0
@@ -482,6 +482,45 @@ def test_add_queries_to_one_stream_under_library_rounds(weights_tamed):
         ref_t, ref_v, ref_h = drivers.track_stream(m, lists[v], qs[v], iters=6, slots=9, return_hops=True)
         assert torch.equal(_bits(torch.cat([p[1] for p in parts[v]], dim=1)), _bits(ref_t)) and mt.stream_hops(v) == ref_h
         assert torch.equal(_bits(torch.cat([p[2] for p in parts[v]], dim=1)), _bits(ref_v))
+
+
+def test_multi_stream_tracker_makes_the_clip_table_library_calls(weights_tamed, monkeypatch):
+    """A MultiStreamTracker of V = 2 under rounds="library" -- 21 frames each in chunks of 5 through rings of 9 slots, one query of
+    stream 0 removed on the way -- calls the clip-table entry points it always called, and none of the one-video forms (the set
+    is read off the drivers before the two trackers shared a core); the outputs are those of rounds="torch", bit for bit with
+    the hop lists."""
+    from pips_amd import drivers, ops
+    _assert_route_0(8, "exact")
+    m = _model(weights_tamed)
+    videos = _videos((21, 21), seed=101)
+    qs = [_queries([0, 3, 11, 11], 103 + v).to(DEV) for v in range(2)]
+
+    def run(rounds):
+        mt = drivers.MultiStreamTracker(m, qs, iters=6, slots=9, record_hops=True, rounds=rounds)
+        parts = []
+        for i in range(0, 21, 5):
+            parts.append(mt.push([v[:, i:i + 5] for v in videos]))
+            if i == 10:
+                assert mt.remove_queries(0, [1]).tolist() == [0, 2, 3]
+        return parts + [mt.finish()], [mt.stream_hops(v) for v in range(2)]
+
+    names, real = [], ops._call
+
+    def recorded(name, *args):
+        names.append(name)
+        return real(name, *args)
+
+    monkeypatch.setattr(ops, "_call", recorded)
+    parts, hops = run("library")
+    seen = {n for n in names if n.startswith(("pips_stream_", "pips_pyramid_append"))}
+    assert seen == {"pips_pyramid_append_at", "pips_stream_select_clips", "pips_stream_round_clips", "pips_stream_emit_cols",
+                    "pips_stream_keep"}
+    ref, ref_hops = run("torch")
+    assert hops == ref_hops and any(len(h) > 1 for h in hops[0] + hops[1])
+    for part, ref_part in zip(parts, ref):
+        for (f0, tr, vi), (g0, ref_t, ref_v) in zip(part, ref_part):
+            assert f0 == g0 and torch.equal(_bits(tr), _bits(ref_t)) and torch.equal(_bits(vi), _bits(ref_v))
+    assert all(sum(p[v][1].shape[1] for p in parts) == 21 for v in range(2))
 
 
 # ------------------------------------------------------------------ (f) against the reference's loop; the joint encoder option

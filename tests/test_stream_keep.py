@@ -268,5 +268,5 @@ def test_stream_keep_is_declared_bound_and_exported():
     assert len(_lib.SIGNATURES["pips_stream_keep"][1]) == 23 and _lib.SIGNATURES["pips_stream_keep"][0] is ctypes.c_int
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "pips_stream_keep") and callable(ops.stream_keep)
     assert _lib.load().pips_abi_version() == 3
-    for cls in (drivers._TorchRounds, drivers._LibraryRounds, drivers._MultiTorchRounds, drivers._MultiLibraryRounds):
+    for cls in (drivers._TorchRounds, drivers._LibraryRounds):
         assert callable(cls.keep)

@@ -284,7 +284,7 @@ def test_removing_every_query_under_library_rounds(weights_tamed):
     video = _video(E2E_T, H_, W_, seed=50)
     st = drivers.StreamTracker(m, _queries([0, 3, 0], 57).to(DEV), iters=6, slots=24, record_hops=True, rounds="library")
     parts = [st.push(video[:, :8])]
-    assert st.remove_queries([0, 1, 2]).numel() == 0 and st.N == 0 and tuple(st.trajs.shape) == (32, 0, 2) and st.state.low is None
+    assert st.remove_queries([0, 1, 2]).numel() == 0 and st.N == 0 and tuple(st.trajs.shape) == (32, 0, 2) and st.state.lows() == [None]
     parts.append(st.push(video[:, 8:12]))
     assert st.emitted == 12 and tuple(parts[-1][1].shape) == (1, 12 - parts[-1][0], 0, 2)
     one = _queries([13], 58)

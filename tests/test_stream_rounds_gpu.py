@@ -59,7 +59,7 @@ def _select_state(n, seed, all_done=False):
 
 
 def _expected_select(s, final):
-    """the lines of drivers._TorchRounds.run / pending that pips_stream_select stands for, on the CPU"""
+    """the lines of drivers._TorchRounds.run / lows (the form without a clip table) that pips_stream_select stands for, on the CPU"""
     T, L = SEL_T, SEL_L
     status, cur, tq = s["status"].clone().long(), s["cur"].long(), s["tq"].long()
     trajs = s["trajs"].clone()
@@ -213,6 +213,48 @@ def test_library_rounds_equal_torch_rounds(weights_tamed, T, chunk, slots, mode)
         assert torch.equal(_bits(got), _bits(ref)) and torch.equal(_bits(vis), _bits(ref_vis)), engine
     plain = drivers.track_stream(m, chunks, q, iters=6, slots=slots, rounds="library")          # without the hop log
     assert torch.equal(_bits(plain[0]), _bits(got)) and torch.equal(_bits(plain[1]), _bits(vis))
+
+
+def _recorded_entries(monkeypatch):
+    """-> the list that receives the name of every entry point called through ops._call from now on"""
+    from pips_amd import ops
+    names, real = [], ops._call
+
+    def recorded(name, *args):
+        names.append(name)
+        return real(name, *args)
+
+    monkeypatch.setattr(ops, "_call", recorded)
+    return names
+
+
+def test_stream_tracker_makes_the_one_video_library_calls(weights_tamed, monkeypatch):
+    """A StreamTracker under rounds="library" -- 21 frames in chunks of 5 through 9 slots, one query removed on the way -- calls the
+    NULL-table entry points it always called, and no _clips / _cols / _at form (the set is read off the drivers before the two
+    trackers shared a core); the outputs are those of rounds="torch", bit for bit with the hop lists."""
+    from pips_amd import drivers
+    _assert_route_0(4, "exact")
+    m = _model(weights_tamed)
+    video = _video(21, H_, W_, seed=43)
+    q = _queries([0, 3, 11, 11], seed=44).to(DEV)
+
+    def run(rounds):
+        st = drivers.StreamTracker(m, q, iters=6, slots=9, record_hops=True, rounds=rounds)
+        parts = []
+        for i in range(0, 21, 5):
+            parts.append(st.push(video[:, i:i + 5]))
+            if i == 10:
+                assert st.remove_queries([1]).tolist() == [0, 2, 3]
+        return parts + [st.finish()], st.hops
+
+    names = _recorded_entries(monkeypatch)
+    parts, hops = run("library")
+    seen = {n for n in names if n.startswith(("pips_stream_", "pips_pyramid_append"))}
+    assert seen == {"pips_pyramid_append", "pips_stream_select", "pips_stream_round", "pips_stream_emit", "pips_stream_keep"}
+    ref, ref_hops = run("torch")
+    assert hops == ref_hops and any(len(h) > 1 for h in hops) and sum(p[1].shape[1] for p in parts) == 21
+    for (f0, tr, vi), (g0, ref_t, ref_v) in zip(parts, ref):
+        assert f0 == g0 and torch.equal(_bits(tr), _bits(ref_t)) and torch.equal(_bits(vi), _bits(ref_v))
 
 
 # ------------------------------------------------------------------ queries added while the video runs
