@@ -167,7 +167,14 @@ int    pips_track_s(const void* arena, const float* pyramid, int B, int T, int H
  *               (coord_predictions2[0]), entries 1.. = coord_predictions
  *   out_vis     (B,S,N) logits             (nets/pips.py:559)
  *   out_ffeat0  (B,N,128) initial feature  (nets/pips.py:463, returned when return_feat)
- * stride is 4 or 8 in the reference's callers; any value >=1 with non-empty level-3 map.
+ * stride is 4 or 8 in the reference's callers; any value >= 1 whose map H/stride x W/stride is at least 16 x 16.
+ * THE MAP SIZE RULE, shared by every entry point that samples correlation windows (pips_forward*, pips_track* in all its forms,
+ * pips_mixer_input_build* in all its forms, pips_chain_hop*, pips_stream_round*): the sampler normalises the coordinates of a
+ * level with 2 x / (W - 1) - 1 (nets/pips.py:318-319), so a pyramid level one pixel wide or high divides by zero and makes
+ * every position behind the query frame NaN.  All four levels must be at least 2 x 2: H8 >= 16 and W8 >= 16 (frames of at least
+ * 128 px a side at stride 8, 64 px at stride 4).  A smaller map is PIPS_E_ARG ahead of any launch -- no output or workspace byte
+ * is written, the encoder is not run -- and pips_last_error() names the map.  The encoder, the pyramid copies, the sizing
+ * queries and pips_score_map_prepare divide by no size - 1 and keep taking maps down to 8 x 8.
  * flags: PIPS_FLAG_REUSE_MAPS = skip the encoder and reuse the pyramid already in the workspace
  *        (same B,S,H,W,stride as the call that produced it); PIPS_FLAG_BF16_MIXER. */
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride);
@@ -191,7 +198,8 @@ int    pips_forward(const void* arena, const float* rgbs, const float* xys,
  *              clamp(win_start - s, 0, T-1): frames before 0 repeat frame 0, which is chain_demo.py's loop run on the
  *              time-reversed video.  The time embedding is still s and row 0 (the query frame) still locks the start.
  *              Needs win_start; windowed particles always take the direct gather.
- * All other arguments as pips_forward.  T = 8 and win_start = NULL is exactly the forward. */
+ * All other arguments as pips_forward.  T = 8 and win_start = NULL is exactly the forward.  H8, W8 >= 16 (the map size rule at
+ * pips_forward); a smaller map is PIPS_E_ARG ahead of any launch. */
 size_t pips_track_workspace_bytes(int B, int N);
 int    pips_track(const void* arena, const float* pyramid, int B, int T, int H8, int W8,
                   const float* xys, const float* coords_init, const float* feat_init,
@@ -285,8 +293,8 @@ int    pips_track_rings(const void* arena, const float* pyramid, int B, int F, i
  *   next_count        device int32: their number.  The library does not synchronise: the caller copies it back
  *   steps             int32 (n_act) or NULL: the step si in 2..7 of each active particle (7 for NaN logits, as the reference's
  *                     comparison admits no frame)
- * n_act == 0: PIPS_OK, *next_count = 0, nothing else.  PIPS_E_ARG: n_act < 0 or > n, L < 8, R < 1, T < 1, a NULL active / trajs /
- * cur / feat / next_active / next_count; PIPS_E_WORKSPACE: workspace_bytes < pips_chain_workspace_bytes(n_act, iters)
+ * n_act == 0: PIPS_OK, *next_count = 0, nothing else.  PIPS_E_ARG: n_act < 0 or > n, L < 8, R < 1, T < 1, a map below 16 x 16
+ * (pips_chain_hop: the map size rule at pips_forward), a NULL active / trajs / cur / feat / next_active / next_count; PIPS_E_WORKSPACE: workspace_bytes < pips_chain_workspace_bytes(n_act, iters)
  * (= pips_track_workspace_bytes_s(1, n_act, 8) + the staging arrays and the windows).  A rejected call writes nothing.
  * pips_chain_threshold(k), k in 0..63: the k-th threshold (host function; the subtraction in double, rounded to fp32).
  * The two stages on their own (parity tests):
@@ -380,7 +388,8 @@ int    pips_chain_hop_clips(const void* arena, const float* pyramid, int T, int 
  *   - tq >= 0 and tq >= the first frame not yet emitted when a query is added; |cur| + 8 below 2^31.
  * A member of active / new_list outside [0, n) is never dereferenced (pips_chain_hop's rule).
  * n_act == 0 (round) or f0 == f1 (emit): PIPS_OK and nothing is done.  PIPS_E_ARG ahead of any launch: n < 1; n_act or n_new
- * outside [0, n]; n_new > n_act; L < 16; R < 9; T < 1; f1 < f0 or f1 - f0 > L; a NULL array (steps may be NULL).
+ * outside [0, n]; n_new > n_act; L < 16; R < 9; T < 1; a map below 16 x 16 (round: the map size rule at pips_forward); f1 < f0 or
+ * f1 - f0 > L; a NULL array (steps may be NULL).
  * PIPS_E_WORKSPACE: workspace_bytes < pips_stream_workspace_bytes(n, iters) (= pips_chain_workspace_bytes(n, iters) + the staging
  * of the join + the hop's unused compacted list).  A rejected call writes nothing.  No allocation, no synchronisation. */
 size_t pips_stream_workspace_bytes(int n, int iters);
@@ -616,7 +625,9 @@ int    pips_point_sample(const float* level0, int B, int S, int H8, int W8,
 /* CorrBlock.corr + CorrBlock.sample + get_3d_embedding + the concat of
  * DeltaBlock.forward (nets/pips.py:384-398, 355-382, 517-522, 304-308; utils/misc.py:44-69):
  * builds the mixer input X (B*N*S, 544) = [ffeat 128 | corr 196 | sincos 192 | dx dy t | 0..].
- * ffeats (B*N*S,128), coords (B*N*S,2) in map pixels, both particle-major. */
+ * ffeats (B*N*S,128), coords (B*N*S,2) in map pixels, both particle-major.  H8, W8 >= 16 in every form below (the map size rule
+ * at pips_forward: PIPS_E_ARG ahead of any launch otherwise).  Finite coordinates of any size are defined: a window wholly outside
+ * the map gives 196 zeros. */
 int    pips_mixer_input_build(const float* pyramid, int B, int S, int H8, int W8,
                               const float* ffeats, const float* coords, const float* times,
                               int N, float* X, void* stream);

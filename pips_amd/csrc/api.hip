@@ -377,6 +377,20 @@ PyramidView pyramid_view(int frames, int H8, int W8) {
     return v;
 }
 
+// THE size rule of every entry point that samples correlation windows (the gathers, the tracker, the hop, the stream round).  The
+// sampler normalises a level's coordinates with 2 x / (W - 1) - 1 (nets/pips.py:318-319; level_sample_geometry, corr_window): a
+// level one pixel wide or high divides by zero and all 49 of its taps are NaN, which the model turns into NaN positions.  So every
+// one of the PIPS_LEVELS levels must be at least 2 x 2 pixels: H8, W8 >= 16.  Encoding, the pyramid copies and the score maps divide
+// by no size - 1 and keep the weaker limit of PyramidView::empty().
+int check_sampled_map(int H8, int W8, const char* who) {
+    const int least = 2 << (PIPS_LEVELS - 1);
+    PIPS_CHECK_ARG(H8 >= least && W8 >= least,
+                   "%s: map %dx%d too small, need at least %dx%d: its coarsest pyramid level would be %dx%d, and a level one pixel "
+                   "wide or high cannot be sampled (the reference normalises with 2x/(W-1)-1, a division by zero: NaN)",
+                   who, H8, W8, least, least, H8 > 0 ? H8 >> (PIPS_LEVELS - 1) : 0, W8 > 0 ? W8 >> (PIPS_LEVELS - 1) : 0);
+    return PIPS_OK;
+}
+
 // ------------------------------------------------------------------ encoder
 struct EncPlan {
     int F, H, W, stride;
@@ -636,8 +650,8 @@ int mixer_input(const GatherCall& g) {
     PIPS_CHECK_ARG(g.pyramid && g.ffeats && g.coords && g.times && g.X, "mixer_input: null pointer");
     PIPS_CHECK_ARG(g.T >= 1 && g.R >= 1 && g.B > 0 && g.N > 0, "mixer_input: need T, R, B, N >= 1");
     PIPS_CHECK_ARG(g.S >= 1 && g.S <= PIPS_S_MAX, "mixer_input: window length S=%d outside 1..%d", g.S, PIPS_S_MAX);
+    RUN(check_sampled_map(g.H8, g.W8, "mixer_input"));
     const PyramidView v = pyramid_view(g.B * g.R, g.H8, g.W8);
-    PIPS_CHECK_ARG(!v.empty(), "mixer_input: map too small");
     ClipTable ct;
     RUN(clip_table(g.win_clip, g.clip_first, g.clip_frames, g.V, g.win_start, g.B, g.T, g.R, g.ring, "mixer_input", ct));
     const ClipTable* clips = g.win_clip != nullptr ? &ct : nullptr;
@@ -884,7 +898,7 @@ int track_impl(const TrackCall& c) {
     PIPS_CHECK_ARG(c.B > 0 && c.N > 0 && c.T >= 1 && c.R >= 1 && c.iters >= 0 && c.stride >= 1,
                    "track: need B,N,T,R,stride >= 1 and iters >= 0");
     PIPS_CHECK_ARG(c.S >= 1 && c.S <= PIPS_S_MAX, "track: window length S=%d outside 1..%d", c.S, PIPS_S_MAX);
-    PIPS_CHECK_ARG(c.H8 >= 8 && c.W8 >= 8, "track: map %dx%d too small for a 4-level pyramid", c.H8, c.W8);
+    RUN(check_sampled_map(c.H8, c.W8, "track"));
     PIPS_CHECK_ARG(c.win_dir == nullptr || c.win_start != nullptr, "track: win_dir needs win_start");
     ClipTable ct;
     RUN(clip_table(c.win_clip, c.clip_first, c.clip_frames, c.V, c.win_start, c.B, c.T, c.R, c.ring, "track", ct));
@@ -1061,7 +1075,8 @@ int chain_hop(const ChainState& s, const void* arena, const float* pyramid, int 
     PIPS_CHECK_ARG(s.clip == nullptr || R == T, "chain_hop: a clip table needs a linear cache, R = T (R=%d, T=%d)", R, T);
     PIPS_CHECK_ARG(next_active && next_count, "chain_hop: null pointer");
     PIPS_CHECK_ARG(next_active != s.active, "chain_hop: next_active may not alias active");
-    PIPS_CHECK_ARG(iters >= 0 && stride >= 1 && H8 >= 8 && W8 >= 8, "chain_hop: need iters >= 0, stride >= 1 and a map of at least 8x8");
+    PIPS_CHECK_ARG(iters >= 0 && stride >= 1, "chain_hop: need iters >= 0 and stride >= 1");
+    RUN(check_sampled_map(H8, W8, "chain_hop"));
     if (n_act == 0) return clear_chain_count(next_count, "chain_hop", st);
     PIPS_CHECK_ARG(arena && pyramid && times && workspace, "chain_hop: null pointer");
     const ChainPlan P = plan_chain(n_act, iters);
@@ -1132,8 +1147,8 @@ int stream_round(const StreamRound& r, hipStream_t st) {
     PIPS_CHECK_ARG(slots >= PIPS_S + 1, "stream_round: a frame ring needs R >= %d slots, a window and a new frame (R=%d)", PIPS_S + 1,
                    slots);
     PIPS_CHECK_ARG(r.T >= 1, "stream_round: need T >= 1 (T=%d)", r.T);
-    PIPS_CHECK_ARG(iters >= 0 && r.stride >= 1 && r.H8 >= 8 && r.W8 >= 8,
-                   "stream_round: need iters >= 0, stride >= 1 and a map of at least 8x8");
+    PIPS_CHECK_ARG(iters >= 0 && r.stride >= 1, "stream_round: need iters >= 0 and stride >= 1");
+    RUN(check_sampled_map(r.H8, r.W8, "stream_round"));
     PIPS_CHECK_ARG(r.arena && r.pyramid && r.times && r.tq && r.xy && r.cur && r.status && r.feat && r.trajs && r.vis && r.active &&
                    r.new_list && r.counts && r.workspace, "stream_round: null pointer");
     if (clips) {
@@ -1815,6 +1830,7 @@ int pips_forward_ce(const void* arena, const float* rgbs, const float* xys, cons
     PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "forward: S=%d outside 1..%d (the arena must be packed for the same S, nets/pips.py:295-301)", S, PIPS_S_MAX);
     PIPS_CHECK_ARG(B > 0 && N > 0 && iters >= 0, "forward: need B,N >= 1 and iters >= 0");
     RUN(check_geometry(B * S, H, W, stride));
+    RUN(check_sampled_map(H / stride, W / stride, "forward"));      // (ahead of the encoder pass: nothing is launched)
     const FwdPlan P = plan_forward(B, S, H, W, N, stride);
     if (workspace_bytes < P.total * sizeof(float)) {
         set_error("forward: workspace %zu < %zu bytes", workspace_bytes, P.total * sizeof(float));

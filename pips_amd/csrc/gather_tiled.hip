@@ -84,6 +84,12 @@ __device__ __forceinline__ void corr_window(float cxm, float cym, int lvl, int H
     const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), (float)(H - 1) / 2.0f);
     const float fx0 = floorf(ix), fy0 = floorf(iy);
     wx = ix - fx0; wy = iy - fy0;
+    // An anchor beyond +-1e6 has an empty window whatever its weights, but the weights must stay finite numbers: hipcc may contract
+    // ix - floorf(ix) with the product that made ix into one fma, and the difference is then the rounding residue of ix -- up to
+    // ulp(ix) / 2, 1.4e22 at ix = 5e29 -- instead of 0.  The blend multiplies the two weights: (1 - wx)(1 - wy) overflowed to inf at
+    // (1e30, 1e30) and inf * 0 made the 49 taps NaN (tests/test_small_maps_gpu.py).  Below 1e6 the residue is at most 0.03.
+    if (fabsf(fx0) > 1.0e6f) wx = 0.f;
+    if (fabsf(fy0) > 1.0e6f) wy = 0.f;
     // clamp before the int conversion: far-out coordinates must not overflow (their windows are empty anyway)
     bx = (int)fminf(fmaxf(fx0, -1.0e6f), 1.0e6f) - PIPS_RADIUS;
     by = (int)fminf(fmaxf(fy0, -1.0e6f), 1.0e6f) - PIPS_RADIUS;

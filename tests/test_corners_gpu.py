@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from test_stream_rounds_gpu import _bits, _model, _video
-from test_cover_gpu import EH, ET, EW, _same_parts, _user
+from test_cover_gpu import ECELL, EH, ET, EW, _assert_live, _same_parts, _user
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -159,18 +159,18 @@ def test_bad_arguments_are_rejected_and_nothing_is_written():
 # ------------------------------------------------------------------ end to end on the device
 def _cover(scan):
     from pips_amd import drivers
-    return drivers.Cover(cell=32, vis_thr=0.9, lost_after=2, scan=scan, seed="corners", min_corner=1000)
+    return drivers.Cover(cell=ECELL, vis_thr=0.9, lost_after=2, scan=scan, seed="corners", min_corner=1000)
 
 
 def _off_centre(xy):
     """how many of the positions (n,2) are no cell centre of the 2 x 3 grid"""
-    centres = {(16.0 + 32 * j, 16.0 + 32 * i) for i in range(2) for j in range(3)}
+    centres = {(ECELL / 2.0 + ECELL * j, ECELL / 2.0 + ECELL * i) for i in range(2) for j in range(3)}
     return sum(tuple(p) not in centres for p in xy.tolist())
 
 
 @pytest.mark.parametrize("rounds", ["torch", "library"])
 def test_library_scan_equals_torch_scan_end_to_end(weights_tamed, rounds):
-    """tests/test_cover_gpu.py's end-to-end run (64 x 96, T = 24 in chunks of 4, cells of 32 px) on its textured video with seeds
+    """tests/test_cover_gpu.py's end-to-end run (128 x 192, T = 24 in chunks of 4, cells of 64 px) on its textured video with seeds
     on corners: scan="library" hands out, push by push, the ids and the bits of scan="torch", with the same births, retirements,
     hop lists and query positions -- which are corners, not centres"""
     from pips_amd import drivers
@@ -189,12 +189,13 @@ def test_library_scan_equals_torch_scan_end_to_end(weights_tamed, rounds):
     _same_parts(pa, pb)
     assert a.born == b.born and a.retired == b.retired and a.hops == b.hops
     assert all(torch.equal(_bits(p), _bits(q)) for p, q in zip(xa, xb))
-    tables = drivers.corner_table_torch(video[0], 32)
+    tables = drivers.corner_table_torch(video[0], ECELL)
     assert _off_centre(xa[0][3:]) >= 3 and all(tuple(p) in {tuple(e) for e in tables[0, :, :, :2].reshape(-1, 2).tolist()}
                                                for p in xa[0][3:].tolist())
     assert a.born[3:].count(0) in (4, 5) and a.retired[2][1] == "outside"
     assert sum(p[1].shape[1] for p in pa) == ET and pa[-1][3].numel() >= 6
     assert a.book.table.is_cuda and b.book.table.is_cuda and torch.equal(_bits(a.book.table), _bits(b.book.table))
+    _assert_live(pa, a.book, [0, 1], f"corner cover e2e {rounds}")
 
 
 def test_multi_stream_library_scan_equals_torch_scan(weights_tamed):
@@ -225,3 +226,5 @@ def test_multi_stream_library_scan_equals_torch_scan(weights_tamed):
         assert a.cover_hops(v) == b.cover_hops(v)
     assert a.books[0].retired[2][1] == "outside" and len(a.books[1].born) >= 6
     assert a.books[1].held is None and sum(p[1].shape[1] for p in pa[1]) == 13
+    for v, user in enumerate(([0, 1], [0])):
+        _assert_live(pa[v], a.books[v], user, f"corner cover streams, stream {v}")

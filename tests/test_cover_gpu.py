@@ -182,7 +182,8 @@ def test_cover_step_rejects_bad_arguments_and_writes_nothing():
 
 
 # ------------------------------------------------------------------ end to end on the device
-EH, EW, ET = 64, 96, 24                                                          # an 8 x 12 map: the smallest the hop accepts
+EH, EW, ET = 128, 192, 24              # a 16 x 24 map: the hop takes no map below 16 x 16 (tests/test_small_maps.py), tracks are live
+ECELL = 64                             # 2 x 3 cells
 
 
 def _user(seed):
@@ -195,7 +196,7 @@ def _user(seed):
 
 def _cover(scan):
     from pips_amd import drivers
-    return drivers.Cover(cell=32, vis_thr=0.9, lost_after=2, scan=scan)
+    return drivers.Cover(cell=ECELL, vis_thr=0.9, lost_after=2, scan=scan)
 
 
 def _same_parts(a, b):
@@ -204,11 +205,29 @@ def _same_parts(a, b):
         assert f0 == g0 and torch.equal(ids, gids) and torch.equal(_bits(t), _bits(gt)) and torch.equal(_bits(v), _bits(gv))
 
 
+def _assert_live(parts, book, user, what):
+    """the run is on live tracks: at least one of the caller's in-frame queries ``user`` (identities) has finite positions and
+    visibilities on every frame from its query frame to its end -- its retirement or the last frame of the video -- and that is more
+    than the query frame alone.  The retirement reasons seen are printed."""
+    from pips_amd import drivers
+    trajs, vis, born, retired = drivers._by_identity(parts, book)
+    live = []
+    for q in user:
+        first, last = int(born[q]), int(retired[q]) if int(retired[q]) >= 0 else trajs.shape[1] - 1
+        if last > first and bool(torch.isfinite(trajs[0, first:last + 1, q]).all()) and bool(torch.isfinite(vis[0, first:last + 1, q]).all()):
+            live.append((q, first, last))
+    reasons = [r for _, r in book.retired.values()]
+    print(f"{what}: live caller queries (id, first frame, last frame) {live}; {len(book.born)} identities, retired "
+          f"{ {r: reasons.count(r) for r in sorted(set(reasons))} }")
+    assert live, what
+
+
 @pytest.mark.parametrize("kw", [dict(rounds="torch", engine="torch"), dict(rounds="torch", engine="native"), dict(rounds="library")],
                          ids=["torch", "native", "library"])
 def test_library_scan_equals_torch_scan_end_to_end(weights_tamed, kw):
-    """64 x 96 frames, T = 24 in chunks of 4, cells of 32 px (2 x 3), lost_after = 2: a CoverTracker under scan="library" hands
-    out, push by push, the ids and the bits of the one under scan="torch", with the same births, retirements and hop lists"""
+    """128 x 192 frames, T = 24 in chunks of 4, cells of 64 px (2 x 3), lost_after = 2: a CoverTracker under scan="library" hands
+    out, push by push, the ids and the bits of the one under scan="torch", with the same births, retirements and hop lists, on
+    tracks with finite positions and visibilities"""
     from pips_amd import drivers
     m = _model(weights_tamed)
     video = _video(ET, EH, EW, seed=70)
@@ -223,6 +242,7 @@ def test_library_scan_equals_torch_scan_end_to_end(weights_tamed, kw):
     print(f"cover e2e {kw}: {len(a.born)} identities, retired {sorted(r for _, r in a.retired.values())}")
     assert a.born[3:].count(0) in (4, 5) and a.retired[2][1] == "outside"      # the first step's seeds; the query outside the frame
     assert sum(p[1].shape[1] for p in pa) == ET and pa[-1][3].numel() >= 6      # the frame is still covered at the end
+    _assert_live(pa, a.book, [0, 1], f"cover e2e {kw}")
 
 
 def test_multi_stream_library_scan_equals_torch_scan(weights_tamed):
@@ -250,3 +270,5 @@ def test_multi_stream_library_scan_equals_torch_scan(weights_tamed):
             assert a.books[v].born == b.books[v].born and a.books[v].retired == b.books[v].retired
             assert a.cover_hops(v) == b.cover_hops(v)
         assert a.books[0].retired[2][1] == "outside" and len(a.books[1].born) >= 6
+        for v, user in enumerate(([0, 1], [0])):
+            _assert_live(pa[v], a.books[v], user, f"cover streams {rounds}, stream {v}")

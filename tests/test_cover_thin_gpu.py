@@ -3,13 +3,14 @@ synthetic rows whose positions come from a few values, so that many queries shar
 five counts, gone / reason, the inputs left as they were, the output tails and the ints behind the workspace left untouched -- at the
 sizes where its tiles and block scans can break, with its return codes; with per_cell = INT_MAX it is pips_cover_step; and
 ``scan="library"`` of a thinned CoverTracker / MultiStreamTracker on the real model equals ``scan="torch"`` in ids, reasons and bits
-under both ``rounds`` values and both engines (64 x 96, where every track of this model ends outside) and on a 128 x 160 video on
-which tracks stay and the crowded ones are retired."""
+under both ``rounds`` values and both engines (128 x 192, a 16 x 24 map: live tracks that the model's visibilities retire) and on a
+128 x 160 video on which no track is ever lost and the crowded ones are retired."""
 import ctypes as C
 
 import pytest
 import torch
 
+from test_cover_gpu import _assert_live
 from test_stream_rounds_gpu import _bits, _model, _video
 
 pytestmark = pytest.mark.gpu
@@ -210,7 +211,8 @@ def test_cover_step_thin_rejects_bad_arguments_and_writes_nothing():
 
 
 # ------------------------------------------------------------------ end to end on the device
-EH, EW, ET = 64, 96, 24                                                          # an 8 x 12 map: the smallest the hop accepts
+EH, EW, ET = 128, 192, 24              # a 16 x 24 map: the hop takes no map below 16 x 16 (tests/test_small_maps.py), tracks are live
+ECELL = 64                             # 2 x 3 cells
 
 
 def _user(seed):
@@ -219,13 +221,13 @@ def _user(seed):
     g = torch.Generator().manual_seed(seed)
     xy = torch.rand(5, 2, generator=g) * torch.tensor([EW - 17.0, EH - 17.0]) + 8.0
     xy[2, 0] = EW + 20.0
-    xy[3], xy[4] = torch.tensor([47.0, 15.0]), torch.tensor([48.0, 16.0])
+    xy[3], xy[4] = torch.tensor([95.0, 31.0]), torch.tensor([96.0, 32.0])
     return torch.cat([torch.tensor([0.0, 9.0, 2.0, 0.0, 0.0]).view(5, 1), xy], dim=1).unsqueeze(0)
 
 
 def _cover(scan, crowd_after):
     from pips_amd import drivers
-    return drivers.Cover(cell=32, vis_thr=0.9, lost_after=2, scan=scan, per_cell=1, crowd_after=crowd_after)
+    return drivers.Cover(cell=ECELL, vis_thr=0.9, lost_after=2, scan=scan, per_cell=1, crowd_after=crowd_after)
 
 
 def _same_parts(a, b):
@@ -237,11 +239,11 @@ def _same_parts(a, b):
 @pytest.mark.parametrize("kw", [dict(rounds="torch", engine="torch"), dict(rounds="torch", engine="native"), dict(rounds="library")],
                          ids=["torch", "native", "library"])
 def test_library_scan_equals_torch_scan_end_to_end(weights_tamed, kw):
-    """64 x 96 frames, T = 24 in chunks of 4, cells of 32 px (2 x 3), one track to a cell after 1 and after 2 surplus frames: a
+    """128 x 192 frames, T = 24 in chunks of 4, cells of 64 px (2 x 3), one track to a cell after 1 and after 2 surplus frames: a
     thinned CoverTracker under scan="library" hands out, push by push, the ids and the bits of the one under scan="torch", with
-    the same births, retirements (frame and reason) and hop lists.  (On a map this small the model's positions are NaN behind the
-    first frame of a hop, so every started query is retired as outside, which takes precedence: the reasons of the thin step must
-    say so under both scans.  Crowding on tracks that stay: test_crowded_tracks_end_to_end.)"""
+    the same births, retirements (frame and reason) and hop lists, on tracks with finite positions and visibilities: the reasons
+    of the thin step come from what the model returns, and the counts seen are printed.  (Crowding on tracks that are never lost:
+    test_crowded_tracks_end_to_end.)"""
     from pips_amd import drivers
     m = _model(weights_tamed)
     video = _video(ET, EH, EW, seed=70)
@@ -259,6 +261,7 @@ def test_library_scan_equals_torch_scan_end_to_end(weights_tamed, kw):
               f"{ {r: reasons.count(r) for r in ('outside', 'lost', 'crowded')} }")
         assert a.retired[2][1] == "outside"
         assert sum(p[1].shape[1] for p in pa) == ET and pa[-1][3].numel() >= 6      # the frame is still covered at the end
+        _assert_live(pa, a.book, [0, 1, 3, 4], f"thin cover e2e {kw} crowd_after {crowd_after}")
 
 
 def test_crowded_tracks_end_to_end(weights_tamed):
@@ -312,3 +315,5 @@ def test_multi_stream_library_scan_equals_torch_scan(weights_tamed):
             assert a.cover_hops(v) == b.cover_hops(v)
         assert a.books[0].retired[2][1] == "outside" and len(a.books[1].born) >= 6
         print(f"thin cover streams {rounds}: retired {[sorted(r for _, r in a.books[v].retired.values()) for v in range(2)]}")
+        for v, user in enumerate(([0, 1, 3, 4], [0, 1])):
+            _assert_live(pa[v], a.books[v], user, f"thin cover streams {rounds}, stream {v}")

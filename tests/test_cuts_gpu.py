@@ -1,14 +1,14 @@
 """GPU: scene cuts in the library.  pips_cut_table is held, as integers, to drivers.cut_table_torch run on the CPU -- uint8 and float32
 frames with the float edge values and a flat frame, sizes with empty regions, ragged rows and regions, rows that start off the
 16-byte grid, several strips per frame -- with poisoned outputs and workspace tails and its return codes.  End to end on the real
-model at 64 x 96 with two scenes of 21 + 19 frames: ``scan="library"`` equals ``scan="torch"``, a covered stream with a cut is its
+model at 128 x 192 with two scenes of 21 + 19 frames: ``scan="library"`` equals ``scan="torch"``, a covered stream with a cut is its
 two scenes tracked apart, and StreamTracker.cut() under library rounds equals torch rounds."""
 import ctypes as C
 
 import pytest
 import torch
 
-from test_cover_gpu import EH, EW, _same_parts, _user
+from test_cover_gpu import ECELL, EH, EW, _assert_live, _same_parts, _user
 from test_cuts import EDGE, TA, TB, _frames, _pieces, _scenes
 from test_stream_rounds_gpu import H_, W_, _assert_route_0, _bits, _model, _queries, _video
 
@@ -62,7 +62,7 @@ def _check(lib, frames, prev, src=None):
 
 
 # 1x1; 3x5: empty regions; 37x53: ragged rows and regions, element loads; 16x53: 16-byte loads on rows that start at every
-# alignment; 64x96: the end-to-end size
+# alignment; 64x96: 16-byte loads on aligned rows, six regions a side
 @pytest.mark.parametrize("dtype", [torch.uint8, torch.float32], ids=["u8", "f32"])
 @pytest.mark.parametrize("h,w", [(1, 1), (3, 5), (37, 53), (16, 53), (64, 96)])
 def test_cut_table_is_the_torch_form(h, w, dtype):
@@ -151,11 +151,11 @@ def test_bad_arguments_are_rejected_and_nothing_is_written():
 # ------------------------------------------------------------------ end to end on the device
 def _cover(scan, **kw):
     from pips_amd import drivers
-    return drivers.Cover(cell=32, vis_thr=0.9, lost_after=2, scan=scan, **kw)
+    return drivers.Cover(cell=ECELL, vis_thr=0.9, lost_after=2, scan=scan, **kw)
 
 
 def _scene_video():
-    """64 x 96, 21 + 19 frames of noise in [0, 100) / [150, 255]; the condition every test below rests on is asserted first, with the
+    """128 x 192, 21 + 19 frames of noise in [0, 100) / [150, 255]; the condition every test below rests on is asserted first, with the
     torch form alone: within a scene dist / 2hw <= 0.3, across the cut >= 0.7"""
     from pips_amd import drivers
     video = _scenes(EH, EW, 13)
@@ -192,6 +192,7 @@ def test_library_scan_equals_torch_scan_across_a_cut(weights_tamed, kw, mode):
     f0, t, v, ids = pa[2]                                                  # the push that holds the cut
     assert f0 < TA < f0 + t.shape[1] or f0 + t.shape[1] == TA
     assert sum(a.born[i] == TA for i in ids.tolist()) == 6
+    _assert_live(pa, a.book, [0, 1], f"cover across a cut {kw} {mode}")
 
 
 @pytest.mark.parametrize("kw", [dict(rounds="torch", engine="torch"), dict(rounds="library")], ids=["torch", "library"])
@@ -219,6 +220,7 @@ def test_a_covered_stream_with_a_cut_is_its_two_scenes_tracked_apart(weights_tam
     assert alive_a and {i: r for i, r in ct.retired.items() if i < KA} == {**a.retired, **{i: (c - 1, "cut") for i in alive_a}}
     assert {i - KA: (f - c, r) for i, (f, r) in ct.retired.items() if i >= KA} == b.retired
     assert ct.hops[:KA] == a.hops and ct.hops[KA:] == b.hops
+    _assert_live(parts, ct.book, [0, 1], f"covered stream with a cut {kw}")
 
 
 @pytest.mark.parametrize("mode", ["exact", "bf16"])
