@@ -754,6 +754,31 @@ int    pips_conv_nhwc_f32_route(const float* in, int F, int H, int W, int Cin,
  * 1 / sqrt(var + 1e-5)}, combined in fp64; C % 16 == 0. */
 int    pips_inorm_finalize_pivot(const float* partial, int F, int parts, int C, float* mean_rstd, void* stream);
 
+/* The encoder's kernels that are not convolutions of a map, one launch each (exposed for unit tests; additive, the ABI version
+ * stays).  Every one answers PIPS_E_ARG ahead of any launch for a NULL pointer it would use, a size below 1 and the cases named.
+ *
+ * pips_encoder_stem: conv1 of BasicEncoder (7x7, stride 2, pad 3, 3 -> 64; nets/pips.py:251) with the 2*(x/255)-1 of :436 on the
+ * caller's (F,3,H,W) frames, on the weights of a packed arena.  flags = 0 | PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_RGB_U8 (anything else:
+ * PIPS_E_ARG): rgbs float or uint8; out = the RAW map [F][Ho][Wo][64], Ho = (H - 1) / 2 + 1, fp32 or (bf16 mode) bf16; stats =
+ * pivoted InstanceNorm partials float4 {sum(x-p), sum((x-p)^2), p, n} [F][parts][64] taken from the fp32 accumulators, parts =
+ * pips_encoder_stem_parts(H, W) (0 for a size below 1), also returned through *parts_host (may be NULL). */
+int    pips_encoder_stem_parts(int H, int W);
+int    pips_encoder_stem(const void* arena, const void* rgbs, int F, int H, int W, int flags, void* out, float* stats,
+                         int* parts_host, void* stream);
+/* InstanceNorm apply + ReLU + shortcut on NHWC maps [F][HW][C], fp32 (maps_bf16 = 0, C % 4 == 0) or bf16 (C % 8 == 0, C <= 2048),
+ * with n(x) = (x - mean) * rstd from stats (F, C, 2):  mode 0: y = relu(n(x));  1: relu(res + relu(n(x)));  2: relu(n2(res) +
+ * relu(n(x))), n2 from res_stats;  3 (bf16 maps only): relu(relu(n2(res)) + relu(n(x))).  PIPS_E_ARG: a mode outside 0..2 (0..3
+ * with bf16 maps), a mode >= 1 without res, a mode >= 2 without res_stats, a C off its alignment. */
+int    pips_inorm_apply(const void* x, const float* stats, const void* res, const float* res_stats, int mode, void* y,
+                        int F, int HW, int C, int maps_bf16, void* stream);
+/* F.interpolate(mode='bilinear', align_corners=True) (nets/pips.py:269-272) of an NHWC map [F][Hs][Ws][C] into channels
+ * [coff, coff + C) of the NHWC map dst [F][Hd][Wd][Cdst] (the torch.cat of :273); the other channels of dst are not written.
+ * fp32 maps (C, Cdst, coff multiples of 4) or bf16 maps (multiples of 8).  PIPS_E_ARG: coff < 0, coff + C > Cdst, alignment. */
+int    pips_resize_into(const void* src, int F, int Hs, int Ws, int C, void* dst, int Hd, int Wd, int Cdst, int coff,
+                        int maps_bf16, void* stream);
+/* F.avg_pool2d(x, 2, stride=2) (nets/pips.py:349) of an fp32 NHWC map [F][H][W][C] -> [F][H/2][W/2][C]; C % 4 == 0, H, W >= 2. */
+int    pips_avgpool2(const float* src, int F, int H, int W, int C, float* dst, void* stream);
+
 /* epi values of the GEMM building blocks; PIPS_EPI_RES_BF16 is OR-ed to PIPS_EPI_RESIDUAL for pips_gemm_bf16 with out_bf16 = 1:
  * the residual R is a bf16 tensor too (the mixer's bf16 residual stream, PIPS_FLAG_BF16_STREAM).  Any other combination with it is
  * rejected (PIPS_E_ARG) -- without out_bf16 a bf16 R would be read as fp32. */

@@ -1268,6 +1268,53 @@ int pips_inorm_finalize_pivot(const float* partial, int F, int parts, int C, flo
     PIPS_CHECK_ARG(partial && mean_rstd && F > 0 && parts > 0 && C > 0 && C % 16 == 0, "inorm_finalize_pivot: bad arguments");
     return launch_inorm_finalize_pivot(partial, F, parts, C, mean_rstd, (hipStream_t)stream);
 }
+int pips_encoder_stem_parts(int H, int W) {
+    if (H < 1 || W < 1) return 0;
+    return stem_tiles_m(conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3));
+}
+int pips_encoder_stem(const void* arena, const void* rgbs, int F, int H, int W, int flags, void* out, float* stats, int* parts_host,
+                      void* stream) {
+    PIPS_CHECK_ARG(arena && rgbs && out && stats, "encoder_stem: null pointer");
+    PIPS_CHECK_ARG(F > 0 && H > 0 && W > 0 && (long)3 * H * W < (1L << 31), "encoder_stem: bad geometry F=%d H=%d W=%d", F, H, W);
+    PIPS_CHECK_ARG((flags & ~(PIPS_FLAG_BF16_ENCODER | PIPS_FLAG_RGB_U8)) == 0, "encoder_stem: unknown flags %d", flags);
+    const ArenaLayout& A = arena_layout();
+    const float* a = (const float*)arena;
+    const int Ho = conv_out(H, 7, 2, 3), Wo = conv_out(W, 7, 2, 3), u8 = (flags & PIPS_FLAG_RGB_U8) ? 1 : 0;
+    if (flags & PIPS_FLAG_BF16_ENCODER)
+        return launch_stem_bf16(rgbs, u8, a + A.conv[0].w, a + A.conv[0].b, out, stats, F, H, W, Ho, Wo, parts_host, (hipStream_t)stream);
+    return launch_stem(rgbs, u8, a + A.conv[0].w, a + A.conv[0].b, (float*)out, stats, F, H, W, Ho, Wo, parts_host, (hipStream_t)stream);
+}
+int pips_inorm_apply(const void* x, const float* stats, const void* res, const float* res_stats, int mode, void* y, int F, int HW,
+                     int C, int maps_bf16, void* stream) {
+    PIPS_CHECK_ARG(x && stats && y, "inorm_apply: null pointer");
+    PIPS_CHECK_ARG(F > 0 && HW > 0 && C > 0, "inorm_apply: bad geometry F=%d HW=%d C=%d", F, HW, C);
+    PIPS_CHECK_ARG(mode >= 0 && mode <= (maps_bf16 ? 3 : 2), "inorm_apply: mode %d on %s maps", mode, maps_bf16 ? "bf16" : "fp32");
+    PIPS_CHECK_ARG(mode == 0 || res != nullptr, "inorm_apply: mode %d needs a shortcut map", mode);
+    PIPS_CHECK_ARG(mode < 2 || res_stats != nullptr, "inorm_apply: mode %d needs the shortcut's statistics", mode);
+    PIPS_CHECK_ARG(C % (maps_bf16 ? 8 : 4) == 0 && C <= 2048, "inorm_apply: C=%d must be a multiple of %d, at most 2048", C,
+                   maps_bf16 ? 8 : 4);
+    if (maps_bf16) return launch_inorm_apply_bf16(x, stats, res, res_stats, mode, y, F, HW, C, (hipStream_t)stream);
+    // the fp32 launcher reads the mode from the pointers: hand it only those of the mode asked for
+    return launch_inorm_apply((const float*)x, stats, mode >= 1 ? (const float*)res : nullptr, mode == 2 ? res_stats : nullptr,
+                              (float*)y, F, HW, C, (hipStream_t)stream);
+}
+int pips_resize_into(const void* src, int F, int Hs, int Ws, int C, void* dst, int Hd, int Wd, int Cdst, int coff, int maps_bf16,
+                     void* stream) {
+    PIPS_CHECK_ARG(src && dst, "resize_into: null pointer");
+    PIPS_CHECK_ARG(F > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && C > 0, "resize_into: bad geometry");
+    const int al = maps_bf16 ? 8 : 4;
+    PIPS_CHECK_ARG(C % al == 0 && Cdst % al == 0 && coff % al == 0, "resize_into: C=%d, Cdst=%d, coff=%d must be multiples of %d", C,
+                   Cdst, coff, al);
+    PIPS_CHECK_ARG(coff >= 0 && (long)coff + C <= Cdst, "resize_into: channels [%d, %d) outside a map of %d", coff, coff + C, Cdst);
+    if (maps_bf16) return launch_resize_into_bf16(src, F, Hs, Ws, C, dst, Hd, Wd, Cdst, coff, (hipStream_t)stream);
+    return launch_resize_into((const float*)src, F, Hs, Ws, C, (float*)dst, Hd, Wd, Cdst, coff, (hipStream_t)stream);
+}
+int pips_avgpool2(const float* src, int F, int H, int W, int C, float* dst, void* stream) {
+    PIPS_CHECK_ARG(src && dst, "avgpool2: null pointer");
+    PIPS_CHECK_ARG(F > 0 && C > 0 && C % 4 == 0, "avgpool2: F=%d, C=%d (a multiple of 4)", F, C);
+    PIPS_CHECK_ARG(H >= 2 && W >= 2, "avgpool2: map %dx%d too small", H, W);
+    return launch_avgpool2(src, F, H, W, C, dst, (hipStream_t)stream);
+}
 int pips_conv_nhwc_bf16(const float* in, int F, int H, int W, int Cin, const void* wgt_bf16, const float* bias,
                         int Cout, int ksize, int cstride, int pad, float* out, float* stats, int* tiles_m_host,
                         void* stream) {

@@ -633,6 +633,69 @@ def inorm_finalize(stats):
     return out
 
 
+def _map(t):
+    """an NHWC activation map as the stage entry points take it: contiguous fp32 or bfloat16 on the device"""
+    assert t.is_cuda and t.dtype in (torch.float32, torch.bfloat16), "a map is a float32 or bfloat16 device tensor"
+    return t.contiguous()
+
+
+def encoder_stem(arena, rgbs, bf16=False):
+    """pips_encoder_stem: rgbs (F,3,H,W) 0..255, float or uint8 -> the raw conv1 map (F,Ho,Wo,64), fp32 or (bf16) bfloat16, and
+    its pivoted partial statistics (F, parts, 64, 4) -- feed those to inorm_finalize()."""
+    lib = _lib.load()
+    u8 = rgbs.dtype == torch.uint8
+    rgbs = rgbs.contiguous() if u8 else _f32(rgbs)
+    F, _, H, W = rgbs.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    parts = lib.pips_encoder_stem_parts(H, W)
+    out = torch.empty(F, Ho, Wo, 64, dtype=torch.bfloat16 if bf16 else torch.float32, device=rgbs.device)
+    stats = torch.zeros(F, parts, 64, 4, dtype=torch.float32, device=rgbs.device)
+    told = C.c_int(0)
+    with torch.cuda.device(rgbs.device):
+        _call("pips_encoder_stem", _lib.ptr(arena), _lib.ptr(rgbs), F, H, W, (FLAG_BF16_ENCODER if bf16 else 0) | (FLAG_RGB_U8 if u8 else 0),
+              _lib.ptr(out), _lib.ptr(stats), C.byref(told), _stream())
+    assert told.value == parts
+    return out, stats
+
+
+def inorm_apply(x, stats, res=None, res_stats=None, mode=0):
+    """pips_inorm_apply on NHWC maps x (F,...,C), fp32 or bfloat16, with stats (F,C,2) = {mean, rstd}: mode 0 relu(n(x)), 1
+    relu(res + relu(n(x))), 2 relu(n2(res) + relu(n(x))), 3 (bfloat16 maps) relu(relu(n2(res)) + relu(n(x)))."""
+    x, stats = _map(x), _f32(stats)
+    res = None if res is None else _map(res)
+    res_stats = None if res_stats is None else _f32(res_stats)
+    assert res is None or (res.dtype == x.dtype and res.shape == x.shape)
+    F, Cc = x.shape[0], x.shape[-1]
+    y = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _call("pips_inorm_apply", _lib.ptr(x), _lib.ptr(stats), _lib.ptr(res), _lib.ptr(res_stats), int(mode), _lib.ptr(y), F,
+              x.numel() // (F * Cc), Cc, int(x.dtype == torch.bfloat16), _stream())
+    return y
+
+
+def resize_into(src, dst, coff):
+    """pips_resize_into: the align_corners bilinear resize of src (F,Hs,Ws,C) written IN PLACE into channels [coff, coff + C) of
+    dst (F,Hd,Wd,Cdst), a contiguous map of the same type (fp32 or bfloat16) -> dst"""
+    src = _map(src)
+    assert dst.is_cuda and dst.is_contiguous() and dst.dtype == src.dtype and dst.shape[0] == src.shape[0]
+    F, Hs, Ws, Cc = src.shape
+    _, Hd, Wd, Cdst = dst.shape
+    with torch.cuda.device(src.device):
+        _call("pips_resize_into", _lib.ptr(src), F, Hs, Ws, Cc, _lib.ptr(dst), Hd, Wd, Cdst, int(coff),
+              int(src.dtype == torch.bfloat16), _stream())
+    return dst
+
+
+def avgpool2(src):
+    """pips_avgpool2: fp32 NHWC map (F,H,W,C) -> its 2x2 means (F,H//2,W//2,C)"""
+    src = _f32(src)
+    F, H, W, Cc = src.shape
+    dst = torch.empty(F, H // 2, W // 2, Cc, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _call("pips_avgpool2", _lib.ptr(src), F, H, W, Cc, _lib.ptr(dst), _stream())
+    return dst
+
+
 def _conv(name, x, w, bias, ksize, stride, pad, want_stats, in_norm=None, out_dtype=torch.float32, route=None, out=None):
     """One NHWC convolution entry point: x (F,H,W,Cin), w with Cout = ``w.shape[-4]`` -> (F,Ho,Wo,Cout) [+ its pivoted partial
     statistics (F, parts, Cout, 4), cut to the parts the kernel reports].  ``pips_conv_nhwc_bf16_maps`` also takes in_norm,
