@@ -110,7 +110,8 @@ const char* pips_last_error(void);
  * cover cell of each frame, and the seeds of a cover step moved from the cell centres onto them); pips_cover_step_thin and
  * pips_cover_thin_workspace_bytes (the cover step with at most per_cell tracks in a cell: the youngest surplus are retired);
  * pips_cut_table and pips_cut_workspace_bytes (the regional luma histogram of each raw frame and its distance to the frame before:
- * where a video has its scene cuts). */
+ * where a video has its scene cuts); pips_frames_import (a decoder's NV12, I420 or packed RGB frames, pitched, to the planar frames
+ * every entry point reads, resized in the same pass). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -616,6 +617,66 @@ int    pips_encoder_fwd_ex(const void* arena, const void* rgbs, int F, int H, in
  * i.e. exactly what pips_forward / pips_encoder_fwd take as rgbs. */
 int    pips_resize_frames(const void* src, int src_is_u8, int planes, int h, int w,
                           float* dst, int H, int W, void* stream);
+
+/* Decoder frames in: pips_frames_import takes F frames of h x w in the layout a decoder, a camera or an image library hands over
+ * and writes dst (F,3,H,W), planar and contiguous, uint8 (dst_is_u8 != 0) or float32 with values 0..255 -- the frames that
+ * pips_encoder_fwd_ex (PIPS_FLAG_RGB_U8 for uint8), pips_forward, pips_corner_table and pips_cut_table read.  Integers only up to
+ * the resize:
+ *  - addressing: frame f, row y of source plane k starts at p_k + f step_k + y pitch_k (bytes).  Any base address, any pitch >= the
+ *    bytes of a row and any step >= pitch_k x rows_k: no alignment is asked for.  Planes a format does not have are not read and
+ *    may be NULL with zero pitch and step;
+ *  - PIPS_FMT_RGB24, BGR24, RGBA32, BGRA32 (packed, bpp = 3 or 4): pixel (y, x) is the bpp bytes at x bpp of row y of plane 0; R, G,
+ *    B are bytes 0, 1, 2 for RGB / RGBA and bytes 2, 1, 0 for BGR / BGRA; the alpha byte is never read.  matrix and range are not
+ *    looked at;
+ *  - PIPS_FMT_NV12: Y = plane0[y][x]; Cb = plane1[y >> 1][2 (x >> 1)] and Cr the byte behind it: plane 1 has ceil(h / 2) rows of
+ *    2 ceil(w / 2) bytes.  PIPS_FMT_I420: Y likewise, Cb = plane1[y >> 1][x >> 1], Cr = plane2[y >> 1][x >> 1]: planes of ceil(h / 2)
+ *    rows of ceil(w / 2) bytes.  Odd h and w are legal;
+ *  - YCbCr -> RGB: c = Y - y0 (y0 = 16 for PIPS_RANGE_LIMITED, 0 for PIPS_RANGE_FULL), d = Cb - 128, e = Cr - 128,
+ *      R = clamp((ky c + rv e + 32768) >> 16), G = clamp((ky c + gu d + gv e + 32768) >> 16), B = clamp((ky c + bu d + 32768) >> 16)
+ *    with >> the arithmetic shift (floor), clamp to [0, 255], and the constants floor(65536 k + 0.5) of the standard coefficients
+ *    (luma scaled by 255/219 and chroma by 255/224 in limited range):
+ *                                 ky      rv      gu      gv      bu
+ *      PIPS_MATRIX_BT601 limited  76309  104597  -25675  -53279  132201
+ *      PIPS_MATRIX_BT601 full     65536   91881  -22553  -46802  116130
+ *      PIPS_MATRIX_BT709 limited  76309  117489  -13975  -34925  138438
+ *      PIPS_MATRIX_BT709 full     65536  103206  -12276  -30679  121609
+ *    Over all 2^24 triples every accumulator stays inside int32 (-1.9e7 .. 3.6e7), and the result is at most one level away from
+ *    clamp(floor(exact + 0.5)) of the real-valued formula;
+ *  - H == h and W == w: dst holds the 8-bit value, as a uint8 or as the same value in a float.  Otherwise the float dst is
+ *    pips_resize_frames' arithmetic on the converted 8-bit planes -- sh = (float)h / (float)H, fy = max(sh (y + 0.5) - 0.5, 0)
+ *    with the product and the difference one fused multiply-add, y0 = min((int)fy, h - 1), y1 = y0 + (y0 < h - 1), the same for x,
+ *    weights ly1 = fy - y0 and ly0 = 1 - ly1, and v = ly0 (lx0 p00 + lx1 p01) + ly1 (lx0 p10 + lx1 p11): four single-rounded fp32
+ *    products and three sums in that order, none fused -- bit for bit what
+ *    importing at (h, w) as uint8 and pips_resize_frames on that gives; the uint8 dst is floor(v + 0.5) of that float (v lies in
+ *    [0, 255]), the quantisation pips_corner_table and pips_cut_table apply to a float frame: they give the same integers on the
+ *    uint8 and on the float output of one import.
+ * Known limits: chroma is replicated to its 2 x 2 pixels (nearest; chroma siting is not modelled, no bilinear chroma); the resize
+ * does not antialias when it scales down; 8-bit formats only; dst may not overlap a source plane.
+ * One launch per call: without a resize a thread owns 16 (uint8 dst) or 4 (float dst) pixels of a row, reads their source bytes
+ * with 16- or 4-byte loads where the addresses allow (byte loads otherwise: the same bits for every base, pitch, step and w) and
+ * stores 16 bytes per plane from the first 16-byte address of each row of dst on; with a resize a thread owns an output pixel,
+ * converts its four neighbours once and fetches a chroma sample once for the neighbours that share it -- no full-size RGB
+ * intermediate exists.  No atomics, no workspace, no allocation, no synchronisation; nothing outside dst is written.
+ * PIPS_E_ARG ahead of any launch, with nothing written: an unknown format; an unknown matrix or range with NV12 or I420; F < 0; h,
+ * w, H or W < 1; F H W > PIPS_IMPORT_PIXELS_MAX (a launch's index: split the chunk); a pitch below the bytes of a row of its
+ * plane; with F > 1 a step below pitch x rows of its plane; with F > 0 a NULL dst or a NULL plane that the format has.  F = 0
+ * launches nothing and returns PIPS_OK. */
+#define PIPS_FMT_RGB24   0
+#define PIPS_FMT_BGR24   1
+#define PIPS_FMT_RGBA32  2
+#define PIPS_FMT_BGRA32  3
+#define PIPS_FMT_NV12    4
+#define PIPS_FMT_I420    5
+#define PIPS_MATRIX_BT601  0
+#define PIPS_MATRIX_BT709  1
+#define PIPS_RANGE_LIMITED 0
+#define PIPS_RANGE_FULL    1
+#define PIPS_IMPORT_PIXELS_MAX (1 << 30)
+int    pips_frames_import(int format, int matrix, int range, int F, int h, int w,
+                          const void* p0, size_t pitch0, size_t step0,
+                          const void* p1, size_t pitch1, size_t step1,
+                          const void* p2, size_t pitch2, size_t step2,
+                          void* dst, int dst_is_u8, int H, int W, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128). */

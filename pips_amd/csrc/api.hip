@@ -1861,6 +1861,39 @@ int pips_cut_table(const void* frames, int src_is_u8, int F, int h, int w, const
     return launch_cut_table(frames, src_is_u8 != 0, F, h, w, prev_hist, hist, dist, (int*)workspace, (hipStream_t)stream);
 }
 
+// ---- decoder frames in
+int pips_frames_import(int format, int matrix, int range, int F, int h, int w, const void* p0, size_t pitch0, size_t step0,
+                       const void* p1, size_t pitch1, size_t step1, const void* p2, size_t pitch2, size_t step2, void* dst,
+                       int dst_is_u8, int H, int W, void* stream) {
+    PIPS_CHECK_ARG(format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I420, "frames_import: unknown format %d", format);
+    const bool yuv = format == PIPS_FMT_NV12 || format == PIPS_FMT_I420;
+    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
+                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
+                   "frames_import: unknown matrix %d or range %d", matrix, range);
+    PIPS_CHECK_ARG(F >= 0, "frames_import: need F >= 0 (F=%d)", F);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1 && H >= 1 && W >= 1, "frames_import: need frames of at least 1x1 (h=%d, w=%d, H=%d, W=%d)", h, w, H, W);
+    PIPS_CHECK_ARG((long long)F * H * W <= PIPS_IMPORT_PIXELS_MAX, "frames_import: %d frames of %d x %d are more than 2^30 output pixels",
+                   F, H, W);
+    // plane k of the format: its rows and the bytes of a row
+    const void* p[3] = {p0, p1, p2};
+    const size_t pitch[3] = {pitch0, pitch1, pitch2}, step[3] = {step0, step1, step2};
+    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2;
+    const int planes = format == PIPS_FMT_NV12 ? 2 : format == PIPS_FMT_I420 ? 3 : 1;
+    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : yuv ? 1 : 3;
+    const size_t rows[3] = {(size_t)h, ch, ch};
+    const size_t row_bytes[3] = {(size_t)w * bpp, format == PIPS_FMT_NV12 ? 2 * cw : cw, cw};
+    for (int k = 0; k < planes; ++k) {
+        PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "frames_import: pitch %zu of plane %d is below the %zu bytes of a row", pitch[k], k,
+                       row_bytes[k]);
+        PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
+                       "frames_import: step %zu of plane %d is below pitch %zu x %zu rows", step[k], k, pitch[k], rows[k]);
+    }
+    if (F == 0) return PIPS_OK;
+    PIPS_CHECK_ARG(dst != nullptr, "frames_import: null dst");
+    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(p[k] != nullptr, "frames_import: null plane %d", k);
+    return launch_frames_import(format, matrix, range, F, h, w, p, pitch, step, dst, dst_is_u8 != 0, H, W, (hipStream_t)stream);
+}
+
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;

@@ -1,0 +1,31 @@
+// The fixed-point YCbCr -> RGB rule of pips_frames_import (include/pips_hip.h): the constants and the one conversion that the
+// kernels of frames_import.hip and their launcher share, so that the table exists once.
+#pragma once
+#include "common.h"
+
+namespace pips {
+
+// R = clamp((ky c + rv e + 32768) >> 16), G = clamp((ky c + gu d + gv e + 32768) >> 16), B = clamp((ky c + bu d + 32768) >> 16)
+// with c = Y - y0, d = Cb - 128, e = Cr - 128; every constant is floor(65536 k + 0.5) of the standard coefficient (luma scaled by
+// 255/219 and chroma by 255/224 in limited range).  Over all 2^24 triples every accumulator stays inside int32 (-1.9e7 .. 3.6e7).
+struct YuvRule {
+    int y0, ky, rv, gu, gv, bu;
+};
+
+// [matrix: PIPS_MATRIX_BT601, PIPS_MATRIX_BT709][range: PIPS_RANGE_LIMITED, PIPS_RANGE_FULL]
+constexpr YuvRule YUV_RULES[2][2] = {
+    {{16, 76309, 104597, -25675, -53279, 132201}, {0, 65536, 91881, -22553, -46802, 116130}},
+    {{16, 76309, 117489, -13975, -34925, 138438}, {0, 65536, 103206, -12276, -30679, 121609}},
+};
+
+__host__ __device__ __forceinline__ int yuv_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// One pixel; >> on a negative int is the arithmetic shift (floor) on every target this compiles for.
+__host__ __device__ __forceinline__ void yuv_to_rgb(const YuvRule& k, int Y, int Cb, int Cr, int& r, int& g, int& b) {
+    const int c = k.ky * (Y - k.y0) + 32768, d = Cb - 128, e = Cr - 128;
+    r = yuv_clamp8((c + k.rv * e) >> 16);
+    g = yuv_clamp8((c + k.gu * d + k.gv * e) >> 16);
+    b = yuv_clamp8((c + k.bu * d) >> 16);
+}
+
+}  // namespace pips

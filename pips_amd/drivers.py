@@ -23,6 +23,9 @@
   frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``); ``Cover(per_cell=k)`` also retires the youngest
   of more than k tracks that share a cell (``cover_scan_thin`` / ``pips_cover_step_thin``).  ``Cover(seed="corners")`` puts each seed on
   the most trackable pixel of its cell (``corner_table_torch`` / ``pips_corner_table``); ``corner_queries`` is the offline form.
+* ``import_frames`` / ``import_frames_torch`` -- a decoder's frames (pitched NV12, I420, packed RGB / BGR with or without alpha) as the
+  planar ``(1,F,3,H,W)`` frames every driver above takes, resized to the model's size in the same ``pips_frames_import`` launch when
+  asked; the second is the same rule in torch ops, bit for bit.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -1261,6 +1264,84 @@ def cut_table_torch(frames, prev_hist=None):
         return hist, hist.new_zeros(0)
     first = hist[:1] if prev_hist is None else prev_hist.to(dev, torch.int64).view(1, 16, 32)
     return hist, (hist - torch.cat([first, hist[:-1]])).abs().sum(dim=(1, 2))
+
+
+# pips_frames_import's constants (include/pips_hip.h; pips_amd/csrc/yuv.h): (y0, ky, rv, gu, gv, bu) by (matrix, range)
+YUV_RULES = {
+    ("bt601", "limited"): (16, 76309, 104597, -25675, -53279, 132201),
+    ("bt601", "full"): (0, 65536, 91881, -22553, -46802, 116130),
+    ("bt709", "limited"): (16, 76309, 117489, -13975, -34925, 138438),
+    ("bt709", "full"): (0, 65536, 103206, -12276, -30679, 121609),
+}
+
+
+def import_frames_torch(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8):
+    """pips_frames_import (include/pips_hip.h) as torch ops, on any device: ``ops.import_frames``' arguments -> planar frames
+    (F,3,H,W), uint8 or float32.  The conversion is int64 arithmetic -- packed formats pick their bytes, NV12 and I420 replicate a
+    chroma sample to its 2 x 2 pixels and apply the fixed-point matrix of ``YUV_RULES`` -- and the resize to ``size`` is the kernel's
+    fp32 arithmetic as elementwise ops in its order (the source index one fused multiply-add, every product and sum of the blend a
+    separate, single-rounded op): equal to the kernel bit for bit."""
+    planes, F, h, w = ops.import_planes(planes, fmt)
+    if matrix not in ops.IMPORT_MATRICES or range not in ops.IMPORT_RANGES:
+        raise ValueError(f"matrix must be one of {sorted(ops.IMPORT_MATRICES)} and range one of {sorted(ops.IMPORT_RANGES)}, "
+                         f"not {matrix!r}, {range!r}")
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"dtype must be torch.uint8 or torch.float32, not {dtype}")
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if H < 1 or W < 1:
+        raise ValueError(f"size must be at least 1 x 1, not {H} x {W}")
+    dev = planes[0].device
+    if fmt in ("nv12", "i420"):
+        Y = planes[0].to(torch.int64)
+        if fmt == "nv12":
+            cb, cr = planes[1][..., 0], planes[1][..., 1]
+        else:
+            cb, cr = planes[1], planes[2]
+        iy, ix = torch.arange(h, device=dev) >> 1, torch.arange(w, device=dev) >> 1
+        cb, cr = (c.to(torch.int64)[:, iy][:, :, ix] for c in (cb, cr))
+        y0, ky, rv, gu, gv, bu = YUV_RULES[(matrix, range)]
+        c, d, e = ky * (Y - y0) + 32768, cb - 128, cr - 128
+        rgb = torch.stack([(c + rv * e) >> 16, (c + gu * d + gv * e) >> 16, (c + bu * d) >> 16], dim=1).clamp(0, 255)
+    else:
+        order = [2, 1, 0] if fmt in ("bgr24", "bgra32") else [0, 1, 2]
+        rgb = planes[0][..., order].permute(0, 3, 1, 2).to(torch.int64)
+    if (H, W) == (h, w):
+        return rgb.to(dtype)
+
+    def taps(n, N):                                     # resize_frames_kernel's source index, second tap and weights along one axis
+        s = torch.tensor(float(n), dtype=torch.float32, device=dev) / torch.tensor(float(N), dtype=torch.float32, device=dev)
+        # the kernel's one fused multiply-add: in float64 the product of a float32 and of i + 0.5 (i < 2^24) and its difference to
+        # 0.5 are exact, so the one rounding to float32 is the fused one
+        f = (s.double() * (torch.arange(N, device=dev).double() + 0.5) - 0.5).to(torch.float32).clamp(min=0.0)
+        i0 = f.to(torch.int64).clamp(max=n - 1)
+        i1 = i0 + (i0 < n - 1).to(torch.int64)
+        l1 = f - i0.to(torch.float32)
+        return i0, i1, 1.0 - l1, l1
+
+    y0, y1, ly0, ly1 = taps(h, H)
+    x0, x1, lx0, lx1 = taps(w, W)
+    p = rgb.to(torch.float32)
+    ly0, ly1 = ly0.view(H, 1), ly1.view(H, 1)
+    r0, r1 = p[:, :, y0], p[:, :, y1]
+    top = lx0 * r0[..., x0] + lx1 * r0[..., x1]
+    bot = lx0 * r1[..., x0] + lx1 * r1[..., x1]
+    v = ly0 * top + ly1 * bot
+    return v if dtype == torch.float32 else (v + 0.5).floor().to(torch.uint8)
+
+
+def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8, device=None):
+    """A decoder's frames -> rgbs (1,F,3,H,W), ready for ``Pips.encode``, ``StreamTracker.push``, ``CoverTracker.push`` and
+    ``MultiStreamTracker.push``: ``ops.import_frames`` (one ``pips_frames_import`` launch; its docstring has the formats) on planes
+    that may still lie on the host.  Host planes are copied to ``device`` (default "cuda") in their SOURCE format and converted
+    there: an NV12 chunk crosses the bus at 1.5 bytes per pixel, where frames converted on the CPU cost 3.  ``size`` = (H, W)
+    resizes to the model's size in the same launch."""
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    if not all(torch.is_tensor(p) for p in planes):
+        raise ValueError("planes must be a tensor or a sequence of tensors")
+    if device is None:
+        device = next((p.device for p in planes if p.is_cuda), "cuda")
+    planes = [p.to(device) for p in planes]
+    return ops.import_frames(planes, fmt, size, matrix, range, dtype).unsqueeze(0)
 
 
 def find_cuts(rgbs, cut_thr=0.5, scan="torch", slice_frames=64):

@@ -122,6 +122,102 @@ def resize_frames(rgbs, size):
     return out
 
 
+# include/pips_hip.h: PIPS_FMT_*, PIPS_MATRIX_*, PIPS_RANGE_*
+IMPORT_FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4, "i420": 5}
+IMPORT_MATRICES = {"bt601": 0, "bt709": 1}
+IMPORT_RANGES = {"limited": 0, "full": 1}
+
+
+def import_planes(planes, fmt):
+    """The checks on the source planes that ``import_frames`` and ``drivers.import_frames_torch`` share: ``planes`` -- a tensor or a
+    sequence of them -- as uint8 tensors of the format's shapes -> (list of planes, F, h, w).  ValueError otherwise."""
+    if fmt not in IMPORT_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(IMPORT_FORMATS)}, not {fmt!r}")
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    want = {"nv12": 2, "i420": 3}.get(fmt, 1)
+    if len(planes) != want or not all(torch.is_tensor(p) for p in planes):
+        raise ValueError(f"{fmt} takes {want} plane tensor(s), not {len(planes)}")
+    for p in planes:
+        if p.dtype != torch.uint8:
+            raise ValueError(f"{fmt} planes must be uint8, not {p.dtype}")
+        if p.device != planes[0].device:
+            raise ValueError("the planes must live on one device")
+    first = planes[0]
+    if want == 1:
+        bpp = 4 if fmt in ("rgba32", "bgra32") else 3
+        if first.dim() != 4 or first.shape[3] != bpp:
+            raise ValueError(f"{fmt} frames must be (F,h,w,{bpp}), not {tuple(first.shape)}")
+        F, h, w = first.shape[:3]
+    else:
+        if first.dim() != 3:
+            raise ValueError(f"the Y plane must be (F,h,w), not {tuple(first.shape)}")
+        F, h, w = first.shape
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        shapes = [(F, ch, cw, 2)] if fmt == "nv12" else [(F, ch, cw)] * 2
+        for p, s in zip(planes[1:], shapes):
+            if tuple(p.shape) != s:
+                raise ValueError(f"a {fmt} chroma plane of (F,h,w) = {(F, h, w)} must be {s}, not {tuple(p.shape)}")
+    if h < 1 or w < 1:
+        raise ValueError(f"frames of {h} x {w}: need at least 1 x 1")
+    return planes, int(F), int(h), int(w)
+
+
+def _pitched(p, inner):
+    """plane (F, rows, ...) whose trailing dimensions must have the element strides ``inner`` -> (plane, pitch, step) in bytes, the
+    plane itself where its strides describe rows ``pitch`` >= a row's bytes apart and frames ``step`` >= pitch * rows apart (a view
+    of a pitched surface imports as it is), one contiguous copy otherwise"""
+    F, rows = p.shape[0], p.shape[1]
+    row_bytes = p[0, 0].numel() if F else 0
+    ok = all(p.stride(-1 - i) == s or p.shape[-1 - i] == 1 for i, s in enumerate(reversed(inner)))
+    pitch, step = p.stride(1), p.stride(0)
+    if rows == 1:
+        pitch = max(pitch, row_bytes)                  # (the stride of a dimension of one element carries no meaning)
+    if F == 1:
+        step = pitch * rows
+    if not ok or pitch < row_bytes or step < pitch * rows:
+        p = p.contiguous()
+        pitch, step = row_bytes, row_bytes * rows
+    return p, pitch, step
+
+
+def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8):
+    """pips_frames_import on device planes in a decoder's layout -> planar frames (F,3,H,W), ``dtype`` uint8 or float32 (0..255):
+    what ``encoder_fwd``, ``corner_table``, ``cut_table`` and ``Pips.encode`` read.  ``fmt``: "rgb24" / "bgr24" (planes (F,h,w,3)),
+    "rgba32" / "bgra32" ((F,h,w,4), alpha not read), "nv12" ((y (F,h,w), uv (F,ceil(h/2),ceil(w/2),2))) or "i420" ((y, u, v)), all
+    uint8.  ``size`` = (H, W) resizes in the same launch (pips_resize_frames' bilinear arithmetic on the converted frames); ``matrix``
+    "bt601" / "bt709" and ``range`` "limited" / "full" are read for nv12 and i420 only.  Row and frame strides go through as pitch
+    and step: a ``surface[:, :h, :w]`` view of a pitched allocation is imported without a copy; a plane whose inner strides are not
+    the format's is copied once (include/pips_hip.h has the whole rule)."""
+    planes, F, h, w = import_planes(planes, fmt)
+    if matrix not in IMPORT_MATRICES or range not in IMPORT_RANGES:
+        raise ValueError(f"matrix must be one of {sorted(IMPORT_MATRICES)} and range one of {sorted(IMPORT_RANGES)}, "
+                         f"not {matrix!r}, {range!r}")
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"dtype must be torch.uint8 or torch.float32, not {dtype}")
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if H < 1 or W < 1:
+        raise ValueError(f"size must be at least 1 x 1, not {H} x {W}")
+    if F * H * W > 2 ** 30:
+        raise ValueError(f"{F} frames of {H} x {W} are more than 2^30 output pixels: split the chunk")
+    assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = planes[0].device
+    out = torch.empty(F, 3, H, W, dtype=dtype, device=dev)
+    if F == 0:                                                                    # (an empty tensor has no pointer to pass)
+        return out
+    # the element strides the format asks of each plane's trailing dimensions
+    inner = {"nv12": [(1,), (2, 1)], "i420": [(1,)] * 3}.get(fmt) or [(planes[0].shape[3], 1)]
+    args, keep = [], []
+    for p, tail in zip(planes, inner):
+        p, pitch, step = _pitched(p, tail)
+        keep.append(p)
+        args += [_lib.ptr(p), pitch, step]
+    args += [None, 0, 0] * (3 - len(planes))
+    with torch.cuda.device(dev):
+        _call("pips_frames_import", IMPORT_FORMATS[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], F, h, w, *args,
+              _lib.ptr(out), 1 if dtype == torch.uint8 else 0, H, W, _stream())
+    return out
+
+
 def point_sample(level0, B, xy):
     """level0 (B*S,H8,W8,128), xy (B,N,2) map pixels -> (B,N,128)."""
     xy = _f32(xy)
