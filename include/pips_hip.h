@@ -786,6 +786,29 @@ int    pips_mixer_gemm_train(const void* arena, int M, int flags, void* workspac
 int    pips_state_update(const void* arena, const float* delta, float* ffeats, float* coords,
                          const float* coords0, int B, int N, float stride,
                          float* out_traj, float* out_vis, void* stream);
+/* The same for an arena packed at any window length S in 1 .. PIPS_S_MAX (PIPS_E_ARG otherwise): delta rows are
+ * pips_delta_stride(S) floats apart, ffeats (B*N,S,128), coords / coords0 (B*N,S,2), out_traj (B,S,N,2), out_vis (B,S,N) or NULL.
+ * pips_state_update is its S = 8 form (same kernel, same bits). */
+int    pips_state_update_s(const void* arena, const float* delta, float* ffeats, float* coords,
+                           const float* coords0, int B, int N, int S, float stride,
+                           float* out_traj, float* out_vis, void* stream);
+
+/* The mixer's and the update's stage kernels, one launch each (exposed for unit tests; additive, the ABI version stays).  Every
+ * one answers PIPS_E_ARG ahead of any launch for a NULL pointer it would use, a size below 1, S outside 1 .. PIPS_S_MAX and the
+ * cases named; none does arithmetic of its own -- each is the launch pips_mixer_fwd_s / pips_track_s make, on the offsets of an
+ * arena packed for S.
+ *
+ * flags (pips_token_mix, pips_ln_mean): 0, PIPS_FLAG_BF16_MIXER, or PIPS_FLAG_BF16_MIXER | PIPS_FLAG_BF16_STREAM (S = 8 only);
+ * anything else is PIPS_E_ARG.
+ *
+ * pips_token_mix: the token-mixing half of mixer layer `layer` (0 .. 11; nets/pips.py:93-109) and the LayerNorm in front of the
+ * channel mixing: x [particles][S][512] += TokenMLP(LN1(x)) in place (fp32, or bf16 with BF16_STREAM), xn = LN2(new x), fp32 or
+ * (both bf16 modes) bf16.
+ * pips_ln_mean: the final LayerNorm and the mean over the S tokens (:120-121): out [particles][512] fp32; x as above.
+ * pips_vis_head: vis_predictor (:421-426) on ffeats (B*N,S,128): out_vis (B,S,N). */
+int    pips_token_mix(const void* arena, int layer, void* x, void* xn, int particles, int S, int flags, void* stream);
+int    pips_ln_mean(const void* arena, const void* x, float* out, int particles, int S, int flags, void* stream);
+int    pips_vis_head(const void* arena, const float* ffeats, int B, int N, int S, float* out_vis, void* stream);
 
 /* Generic fp32-MFMA building blocks (exposed for unit tests).
  * C[M,N] = epi(A[M,K] * W[N,K]^T + bias[N]); K % 32 == 0; epi: 0 none, 1 GELU(erf),

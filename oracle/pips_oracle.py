@@ -168,18 +168,23 @@ def mixer_input(ffeats, fcorrs, coords):
 
 def mixer(sd, x, taps=None):
     """MLPMixer, nets/pips.py:111-123 (PreNormResidual :93-100, FeedForward :102-109).
-    x (M,S,519) -> (M, S*130)."""
+    x (M,S,519) -> (M, S*130).  taps["ln_in"]: the residual stream in front of each of the 25 LayerNorms, in order."""
     md = "delta_block.to_delta"
     x = F.linear(x, sd[f"{md}.0.weight"], sd[f"{md}.0.bias"])
     if taps is not None:
         taps["mix_in_proj"] = x
+        taps["ln_in"] = []
     D = x.shape[-1]
     for d in range(1, MIX_DEPTH + 1):
+        if taps is not None:
+            taps["ln_in"].append(x)
         h = F.layer_norm(x, (D,), sd[f"{md}.{d}.0.norm.weight"], sd[f"{md}.{d}.0.norm.bias"])
         h = F.conv1d(h, sd[f"{md}.{d}.0.fn.0.weight"], sd[f"{md}.{d}.0.fn.0.bias"])     # tokens = conv channels
         h = F.gelu(h)
         h = F.conv1d(h, sd[f"{md}.{d}.0.fn.3.weight"], sd[f"{md}.{d}.0.fn.3.bias"])
         x = h + x
+        if taps is not None:
+            taps["ln_in"].append(x)
         h = F.layer_norm(x, (D,), sd[f"{md}.{d}.1.norm.weight"], sd[f"{md}.{d}.1.norm.bias"])
         h = F.linear(h, sd[f"{md}.{d}.1.fn.0.weight"], sd[f"{md}.{d}.1.fn.0.bias"])
         h = F.gelu(h)
@@ -187,6 +192,8 @@ def mixer(sd, x, taps=None):
         x = h + x
         if taps is not None and d == 1:
             taps["mix_block1"] = x
+    if taps is not None:
+        taps["ln_in"].append(x)
     x = F.layer_norm(x, (D,), sd[f"{md}.{MIX_DEPTH + 1}.weight"], sd[f"{md}.{MIX_DEPTH + 1}.bias"])
     x = x.mean(dim=1)                                                           # Reduce('b n c -> b c','mean')
     return F.linear(x, sd[f"{md}.{MIX_DEPTH + 3}.weight"], sd[f"{md}.{MIX_DEPTH + 3}.bias"])

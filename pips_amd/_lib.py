@@ -136,6 +136,10 @@ SIGNATURES = {
                                         C.POINTER(c_float)]),
     "pips_mixer_gemm_train": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, C.POINTER(c_float)]),
     "pips_state_update": (c_int, [c_void_p, fp, fp, fp, fp, c_int, c_int, c_float, fp, fp, c_void_p]),
+    "pips_state_update_s": (c_int, [c_void_p, fp, fp, fp, fp, c_int, c_int, c_int, c_float, fp, fp, c_void_p]),
+    "pips_token_mix": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "pips_ln_mean": (c_int, [c_void_p, c_void_p, fp, c_int, c_int, c_int, c_void_p]),
+    "pips_vis_head": (c_int, [c_void_p, fp, c_int, c_int, c_int, fp, c_void_p]),
     "pips_gemm_f32": (c_int, [fp, c_int, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, fp, c_int, c_void_p]),
     "pips_conv_nhwc_f32": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_int, c_int, fp, fp,
                                    C.POINTER(c_int), c_void_p]),

@@ -1530,12 +1530,52 @@ int pips_mixer_gemm_train(const void* arena, int M, int flags, void* workspace, 
     return mixer_gemm_train(arena, M, flags, workspace, workspace_bytes, (hipStream_t)stream, reps, ms2_host);
 }
 
-int pips_state_update(const void* arena, const float* delta, float* ffeats, float* coords, const float* coords0,
-                      int B, int N, float stride, float* out_traj, float* out_vis, void* stream) {
+int pips_state_update_s(const void* arena, const float* delta, float* ffeats, float* coords, const float* coords0,
+                        int B, int N, int S, float stride, float* out_traj, float* out_vis, void* stream) {
     PIPS_CHECK_ARG(arena && delta && ffeats && coords && coords0 && out_traj, "state_update: null pointer");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "state_update: S=%d outside 1..%d", S, PIPS_S_MAX);
     PIPS_CHECK_ARG(B > 0 && N > 0, "state_update: empty");
     return launch_state_update((const float*)arena, delta, ffeats, coords, coords0, B, N, stride, out_traj, out_vis,
-                               (hipStream_t)stream);
+                               (hipStream_t)stream, S);
+}
+int pips_state_update(const void* arena, const float* delta, float* ffeats, float* coords, const float* coords0,
+                      int B, int N, float stride, float* out_traj, float* out_vis, void* stream) {
+    return pips_state_update_s(arena, delta, ffeats, coords, coords0, B, N, PIPS_S, stride, out_traj, out_vis, stream);
+}
+
+// ---- the mixer's stage kernels alone (unit tests): the launches of mixer_impl / track_impl, nothing else
+// flags -> {bf16 operands, bf16 stream}; false for anything but the three combinations the mixer itself runs these kernels in
+static bool stage_mode(int flags, int S, bool* bf16, bool* xb) {
+    *bf16 = (flags & PIPS_FLAG_BF16_MIXER) != 0;
+    *xb = (flags & PIPS_FLAG_BF16_STREAM) != 0;
+    if (flags & ~(PIPS_FLAG_BF16_MIXER | PIPS_FLAG_BF16_STREAM)) return false;
+    return !*xb || (*bf16 && S == PIPS_S);
+}
+int pips_token_mix(const void* arena, int layer, void* x, void* xn, int particles, int S, int flags, void* stream) {
+    PIPS_CHECK_ARG(arena && x && xn, "token_mix: null pointer");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "token_mix: S=%d outside 1..%d", S, PIPS_S_MAX);
+    PIPS_CHECK_ARG(particles > 0, "token_mix: particles=%d", particles);
+    PIPS_CHECK_ARG(layer >= 0 && layer < PIPS_DEPTH, "token_mix: layer %d outside 0..%d", layer, PIPS_DEPTH - 1);
+    bool bf16, xb;
+    PIPS_CHECK_ARG(stage_mode(flags, S, &bf16, &xb), "token_mix: flags %d at S=%d", flags, S);
+    return launch_token_mix((const float*)arena, arena_layout(S).mix[layer], (float*)x, (float*)xn, particles, (hipStream_t)stream, bf16,
+                            S, xb);
+}
+int pips_ln_mean(const void* arena, const void* x, float* out, int particles, int S, int flags, void* stream) {
+    PIPS_CHECK_ARG(arena && x && out, "ln_mean: null pointer");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "ln_mean: S=%d outside 1..%d", S, PIPS_S_MAX);
+    PIPS_CHECK_ARG(particles > 0, "ln_mean: particles=%d", particles);
+    bool bf16, xb;
+    PIPS_CHECK_ARG(stage_mode(flags, S, &bf16, &xb), "ln_mean: flags %d at S=%d", flags, S);
+    const ArenaLayout& A = arena_layout(S);
+    const float* a = (const float*)arena;
+    return launch_ln_mean((const float*)x, a + A.lnf_g, a + A.lnf_b, out, particles, (hipStream_t)stream, S, xb);
+}
+int pips_vis_head(const void* arena, const float* ffeats, int B, int N, int S, float* out_vis, void* stream) {
+    PIPS_CHECK_ARG(arena && ffeats && out_vis, "vis_head: null pointer");
+    PIPS_CHECK_ARG(S >= 1 && S <= PIPS_S_MAX, "vis_head: S=%d outside 1..%d", S, PIPS_S_MAX);
+    PIPS_CHECK_ARG(B > 0 && N > 0, "vis_head: empty");
+    return launch_vis_head((const float*)arena, ffeats, B, N, out_vis, (hipStream_t)stream, S);
 }
 
 size_t pips_score_map_workspace_bytes(int B, int S, int H8, int W8) { return score_map_workspace_bytes(B, S, H8, W8); }

@@ -388,14 +388,61 @@ def mixer_gemm_train(arena, X, flags=0, reps=4):
     return {"up_proj": ms[0], "down_proj": ms[1]}
 
 
-def state_update(arena, delta, ffeats, coords, coords0, B, N, stride, want_vis=False):
-    """In-place update of ffeats/coords (particle-major); returns (traj (B,S,N,2) px, vis or None)."""
+def state_update(arena, delta, ffeats, coords, coords0, B, N, stride, want_vis=False, S=8):
+    """In-place update of ffeats/coords (particle-major); returns (traj (B,S,N,2) px, vis or None).  S != 8 (arena packed
+    for that S): delta rows are pips_delta_stride(S) floats apart (pips_state_update_s)."""
     traj = torch.empty(B, S, N, 2, dtype=torch.float32, device=delta.device)
     vis = torch.empty(B, S, N, dtype=torch.float32, device=delta.device) if want_vis else None
     with torch.cuda.device(delta.device):
-        _call("pips_state_update", _lib.ptr(arena), _lib.ptr(delta), _lib.ptr(ffeats), _lib.ptr(coords), _lib.ptr(coords0), B, N,
-              float(stride), _lib.ptr(traj), _lib.ptr(vis), _stream())
+        if S == 8:
+            _call("pips_state_update", _lib.ptr(arena), _lib.ptr(delta), _lib.ptr(ffeats), _lib.ptr(coords), _lib.ptr(coords0), B, N,
+                  float(stride), _lib.ptr(traj), _lib.ptr(vis), _stream())
+        else:
+            _call("pips_state_update_s", _lib.ptr(arena), _lib.ptr(delta), _lib.ptr(ffeats), _lib.ptr(coords), _lib.ptr(coords0), B,
+                  N, int(S), float(stride), _lib.ptr(traj), _lib.ptr(vis), _stream())
     return traj, vis
+
+
+def _stage_flags(bf16, stream_bf16, S):
+    if stream_bf16:
+        assert bf16 and S == 8
+    return (FLAG_BF16_MIXER if bf16 else 0) | (FLAG_BF16_STREAM if stream_bf16 else 0)
+
+
+def token_mix(arena, layer, x, bf16=False, stream_bf16=False):
+    """One launch of the token-mixing kernel of mixer layer ``layer`` (pips_token_mix; exposed for unit tests): x
+    (particles, S, 512), fp32 or (stream_bf16) bfloat16, is updated IN PLACE; returns xn = LayerNorm-2 of the new x, fp32 or
+    (bf16) bfloat16.  The arena must have been packed for S = x.shape[1]."""
+    assert x.is_cuda and x.is_contiguous() and x.dtype == (torch.bfloat16 if stream_bf16 else torch.float32)
+    P, Sw, D = x.shape
+    assert D == 512
+    xn = torch.empty(P, Sw, D, dtype=torch.bfloat16 if bf16 else torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _call("pips_token_mix", _lib.ptr(arena), int(layer), _lib.ptr(x), _lib.ptr(xn), P, Sw, _stage_flags(bf16, stream_bf16, Sw),
+              _stream())
+    return xn
+
+
+def ln_mean(arena, x, bf16=False, stream_bf16=False):
+    """The final LayerNorm and the mean over tokens (pips_ln_mean; exposed for unit tests): x (particles, S, 512) fp32 or
+    (stream_bf16) bfloat16 -> (particles, 512) fp32."""
+    assert x.is_cuda and x.is_contiguous() and x.dtype == (torch.bfloat16 if stream_bf16 else torch.float32)
+    P, Sw, D = x.shape
+    assert D == 512
+    out = torch.empty(P, D, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _call("pips_ln_mean", _lib.ptr(arena), _lib.ptr(x), _lib.ptr(out), P, Sw, _stage_flags(bf16, stream_bf16, Sw), _stream())
+    return out
+
+
+def vis_head(arena, ffeats, B, N):
+    """vis_predictor alone (pips_vis_head; exposed for unit tests): ffeats (B*N, S, 128) fp32 -> (B, S, N) logits."""
+    assert ffeats.is_cuda and ffeats.is_contiguous() and ffeats.dtype == torch.float32 and ffeats.shape[0] == B * N
+    Sw = ffeats.shape[1]
+    vis = torch.empty(B, Sw, N, dtype=torch.float32, device=ffeats.device)
+    with torch.cuda.device(ffeats.device):
+        _call("pips_vis_head", _lib.ptr(arena), _lib.ptr(ffeats), B, N, Sw, _lib.ptr(vis), _stream())
+    return vis
 
 
 def chain_thresholds() -> torch.Tensor:

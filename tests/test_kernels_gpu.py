@@ -821,7 +821,7 @@ def test_fixed_window_entry_points_equal_the_general_ones(weights_raw):
     pips_encoder_fwd / _bf16 = pips_encoder_fwd_ex(flags), pips_track_ce = pips_track_s(S = 8) -- bit-identical results.  So are the forms the Python package reaches only through their
     general ones: pips_track (= _win without win_dir = _ring with R = T), pips_mixer_input_build (= _ex = _win = _ring),
     pips_mixer_input_build_tiled / _tiled_timed (= _tiled_ex), pips_mixer_fwd / _bf16 / _x3 (= pips_mixer_fwd_s(8, flags)) and
-    pips_mixer_fwd_timed (= _timed_ex(0))."""
+    pips_mixer_fwd_timed (= _timed_ex(0)), and pips_state_update (= pips_state_update_s(S = 8))."""
     import ctypes as C
     from pips_amd import _lib, ops
     from pips_amd.weights import param_table
@@ -935,6 +935,21 @@ def test_fixed_window_entry_points_equal_the_general_ones(weights_raw):
     d0 = mixer("pips_mixer_fwd")
     assert torch.equal(mixer("pips_mixer_fwd_timed", after=(ms5,)), mixer("pips_mixer_fwd_timed_ex", before=(0,), after=(ms5,)))
     assert torch.equal(mixer("pips_mixer_fwd_timed", after=(ms5,)), d0)
+    # state update on that mixer output: pips_state_update = pips_state_update_s(S = 8), with and without the visibility head
+    Bu, Nu = 1, Mg // 8
+    for want_vis in (True, False):
+        outs = []
+        for name, s_arg in (("pips_state_update", ()), ("pips_state_update_s", (8,))):
+            ffu, cou = ffe.clone(), co.clone()
+            traj = torch.zeros(Bu, 8, Nu, 2, device=dev)
+            visu = torch.zeros(Bu, 8, Nu, device=dev)
+            _lib.check(getattr(lib, name)(_lib.ptr(a0), _lib.ptr(d0), _lib.ptr(ffu), _lib.ptr(cou), _lib.ptr(co), Bu, Nu, *s_arg, 8.0,
+                                          _lib.ptr(traj), _lib.ptr(visu) if want_vis else None, st()), name)
+            torch.cuda.synchronize()
+            outs.append((ffu, cou, traj, visu))
+        for x, y in zip(*outs):
+            assert torch.equal(x, y) and bool(torch.isfinite(x).all())
+        assert float((outs[0][0] - ffe).abs().max()) > 0 and (float(outs[0][3].abs().max()) > 0) == want_vis
 
 
 def test_gather_mfma_batches():

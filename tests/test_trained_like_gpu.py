@@ -289,8 +289,9 @@ def test_forward_bf16_mode_tamed(name, stream, sd_tamed, forward_oracles):
 @pytest.mark.parametrize("matmul", MATMUL)
 @pytest.mark.parametrize("S", [5, 12, 24])
 def test_forward_window_lengths(S, matmul):
-    """Pips(S != 8) end to end on a tamed trained-like dict: state_update_any_kernel and ln_mean_any_kernel have no stage
-    entry point and read `norm.*` / the final LayerNorm pair only here.  Gates of test_golden_reference_outputs_window_lengths."""
+    """Pips(S != 8) end to end on a tamed trained-like dict: state_update_any_kernel and ln_mean_any_kernel read `norm.*` / the
+    final LayerNorm pair here inside a whole forward (alone: tests/test_mixer_stages_gpu.py).  Gates of
+    test_golden_reference_outputs_window_lengths."""
     O = _oracle()
     case = dict(S=S, B=1, N=6, H=128, W=160, stride=8, iters=3, tamed=True, border=True)
     sd = G.trained_like_state_dict(0, S=S, tamed=True)
