@@ -111,7 +111,8 @@ const char* pips_last_error(void);
  * pips_cover_thin_workspace_bytes (the cover step with at most per_cell tracks in a cell: the youngest surplus are retired);
  * pips_cut_table and pips_cut_workspace_bytes (the regional luma histogram of each raw frame and its distance to the frame before:
  * where a video has its scene cuts); pips_frames_import (a decoder's NV12, I420 or packed RGB frames, pitched, to the planar frames
- * every entry point reads, resized in the same pass). */
+ * every entry point reads, resized in the same pass); pips_frames_import_ex (the same with a filter argument -- the antialiasing
+ * triangle filter beside the two-tap bilinear -- and the 10-bit formats P010 and I010). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -650,8 +651,44 @@ int    pips_resize_frames(const void* src, int src_is_u8, int planes, int h, int
  *    importing at (h, w) as uint8 and pips_resize_frames on that gives; the uint8 dst is floor(v + 0.5) of that float (v lies in
  *    [0, 255]), the quantisation pips_corner_table and pips_cut_table apply to a float frame: they give the same integers on the
  *    uint8 and on the float output of one import.
+ * pips_frames_import_ex is the same entry with a filter argument and two more formats (pips_frames_import is
+ * pips_frames_import_ex with PIPS_FILTER_BILINEAR and keeps rejecting formats above PIPS_FMT_I420):
+ *  - PIPS_FMT_P010 (semi-planar as NV12) and PIPS_FMT_I010 (planar as I420, yuv420p10le): samples are 16-bit little-endian words,
+ *    the 10-bit value is word >> 6 for P010 and word & 1023 for I010 (the other six bits are not looked at).  Geometry and chroma
+ *    replication are NV12's and I420's; pitches and steps stay in bytes: a row of Y is 2 w bytes, a row of P010's chroma
+ *    2 x 2 ceil(w / 2) and of I010's 2 ceil(w / 2).  Every plane pointer, pitch and step of these two formats must be even;
+ *  - 10-bit YCbCr -> the same 8-bit RGB: c = Y - y0 (y0 = 64 limited, 0 full), d = Cb - 512, e = Cr - 512,
+ *      R = clamp((ky c + rv e + 2^17) >> 18), G = clamp((ky c + gu d + gv e + 2^17) >> 18), B = clamp((ky c + bu d + 2^17) >> 18)
+ *    with the constants floor(2^18 k + 0.5) of the standard coefficients, luma scaled by 255/876 and chroma by 255/896 in limited
+ *    range and both by 255/1023 in full range:
+ *                                         ky      rv      gu      gv      bu
+ *      10-bit PIPS_MATRIX_BT601 limited   76309  104597  -25675  -53279  132201
+ *      10-bit PIPS_MATRIX_BT601 full      65344   91612  -22487  -46664  115789
+ *      10-bit PIPS_MATRIX_BT709 limited   76309  117489  -13975  -34925  138438
+ *      10-bit PIPS_MATRIX_BT709 full      65344  102903  -12240  -30589  121252
+ *    The limited rows are the 8-bit constants: a limited-range surface whose samples are 4 x the bytes of an 8-bit one imports to
+ *    the same frames (in full range 4 x 255 is not 1023: the two differ by design).  Every accumulator stays inside int32
+ *    (-7.7e7 .. 1.5e8); without a resize and with PIPS_FILTER_BILINEAR everything behind the conversion is the 8-bit formats';
+ *  - PIPS_FILTER_TRIANGLE with (H, W) != (h, w): the separable triangle (antialiasing) filter on the converted 8-bit planes p,
+ *    PIL's and torch's antialiased bilinear in integers.  Along an axis of n source and N output samples, with m = max(n, N), the
+ *    raw weight of source j for output i is r(i, j) = max(0, 2 m - |(2 j + 1) N - (2 i + 1) n|), 0 <= j < n: the triangle of
+ *    half-width max(n / N, 1) around (i + 0.5) n / N, clipped to the source.  num = sum_y ry sum_x rx p and
+ *    den = (sum ry)(sum rx) are exact integers, q = floor((512 num + den) / (2 den)) is the value in 8.8 fixed point rounded half
+ *    up (0 <= q <= 65280); the float dst is q / 256 (exact), the uint8 dst (q + 128) >> 8 = floor(v + 0.5) of that float, so the
+ *    tables agree on both outputs as above.  N == n on an axis is one tap (identity on that axis), N > n the two-tap bilinear with
+ *    the clamped edge.  Within 1/512 (the rounding of q) of F.interpolate(p.double(), (H, W), mode='bilinear', antialias=True).
+ *    Limits: h, w, H, W <= PIPS_FILTER_DIM_MAX and h <= 16 H, w <= 16 W -- a weight sum along an axis stays below 2^19, a row sum
+ *    sum_x rx p below 2^27 (int32) and 512 num below 2^55 (int64).  With (H, W) == (h, w) no filter runs: the plain conversion.
+ *    One launch: a block owns a tile of 32 x up to 8 output pixels; it stages the rows of the tile's footprint eight at a time in
+ *    LDS, each source pixel converted once and read by neighbouring lanes, writes the row sums sum_x rx p (int32, one LDS plane per
+ *    channel, x on the lanes) and then sums them over y in int64 and divides.  The tile's height is chosen from the ratio so that
+ *    a block's LDS stays at or below 64 KiB at the 16 x limit; no workspace, no atomics, nothing outside dst written.
+ *  PIPS_E_ARG from pips_frames_import_ex, ahead of any launch and with nothing written: everything pips_frames_import rejects (a
+ *  format above PIPS_FMT_I010 here); an unknown filter; the filter limits; an odd plane pointer, pitch or step of a 16-bit format.
  * Known limits: chroma is replicated to its 2 x 2 pixels (nearest; chroma siting is not modelled, no bilinear chroma); the resize
- * does not antialias when it scales down; 8-bit formats only; dst may not overlap a source plane.
+ * does not antialias when it scales down unless PIPS_FILTER_TRIANGLE is asked for (the two-tap rule stays the default); the output
+ * of the 10-bit formats is the 8-bit RGB of every other format (the two extra bits are not kept in the float output), BT.2020 and
+ * transfer functions are not handled; dst may not overlap a source plane.
  * One launch per call: without a resize a thread owns 16 (uint8 dst) or 4 (float dst) pixels of a row, reads their source bytes
  * with 16- or 4-byte loads where the addresses allow (byte loads otherwise: the same bits for every base, pitch, step and w) and
  * stores 16 bytes per plane from the first 16-byte address of each row of dst on; with a resize a thread owns an output pixel,
@@ -677,6 +714,16 @@ int    pips_frames_import(int format, int matrix, int range, int F, int h, int w
                           const void* p1, size_t pitch1, size_t step1,
                           const void* p2, size_t pitch2, size_t step2,
                           void* dst, int dst_is_u8, int H, int W, void* stream);
+#define PIPS_FMT_P010    6
+#define PIPS_FMT_I010    7
+#define PIPS_FILTER_BILINEAR 0
+#define PIPS_FILTER_TRIANGLE 1
+#define PIPS_FILTER_DIM_MAX  8192
+int    pips_frames_import_ex(int format, int matrix, int range, int filter, int F, int h, int w,
+                             const void* p0, size_t pitch0, size_t step0,
+                             const void* p1, size_t pitch1, size_t step1,
+                             const void* p2, size_t pitch2, size_t step2,
+                             void* dst, int dst_is_u8, int H, int W, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128). */

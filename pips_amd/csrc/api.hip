@@ -1902,11 +1902,14 @@ int pips_cut_table(const void* frames, int src_is_u8, int F, int h, int w, const
 }
 
 // ---- decoder frames in
-int pips_frames_import(int format, int matrix, int range, int F, int h, int w, const void* p0, size_t pitch0, size_t step0,
-                       const void* p1, size_t pitch1, size_t step1, const void* p2, size_t pitch2, size_t step2, void* dst,
-                       int dst_is_u8, int H, int W, void* stream) {
-    PIPS_CHECK_ARG(format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I420, "frames_import: unknown format %d", format);
-    const bool yuv = format == PIPS_FMT_NV12 || format == PIPS_FMT_I420;
+int pips_frames_import_ex(int format, int matrix, int range, int filter, int F, int h, int w, const void* p0, size_t pitch0,
+                          size_t step0, const void* p1, size_t pitch1, size_t step1, const void* p2, size_t pitch2, size_t step2,
+                          void* dst, int dst_is_u8, int H, int W, void* stream) {
+    PIPS_CHECK_ARG(format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I010, "frames_import: unknown format %d", format);
+    PIPS_CHECK_ARG(filter == PIPS_FILTER_BILINEAR || filter == PIPS_FILTER_TRIANGLE, "frames_import: unknown filter %d", filter);
+    const bool wide = format == PIPS_FMT_P010 || format == PIPS_FMT_I010;                   // 16-bit samples
+    const bool semi = format == PIPS_FMT_NV12 || format == PIPS_FMT_P010;
+    const bool yuv = semi || format == PIPS_FMT_I420 || format == PIPS_FMT_I010;
     PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
                             (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
                    "frames_import: unknown matrix %d or range %d", matrix, range);
@@ -1914,24 +1917,42 @@ int pips_frames_import(int format, int matrix, int range, int F, int h, int w, c
     PIPS_CHECK_ARG(h >= 1 && w >= 1 && H >= 1 && W >= 1, "frames_import: need frames of at least 1x1 (h=%d, w=%d, H=%d, W=%d)", h, w, H, W);
     PIPS_CHECK_ARG((long long)F * H * W <= PIPS_IMPORT_PIXELS_MAX, "frames_import: %d frames of %d x %d are more than 2^30 output pixels",
                    F, H, W);
+    if (filter == PIPS_FILTER_TRIANGLE && (H != h || W != w)) {
+        // the triangle filter's accumulators: a weight sum below 2^19, a row sum in int32, 512 num in int64
+        PIPS_CHECK_ARG(h <= PIPS_FILTER_DIM_MAX && w <= PIPS_FILTER_DIM_MAX && H <= PIPS_FILTER_DIM_MAX && W <= PIPS_FILTER_DIM_MAX,
+                       "frames_import: the triangle filter takes sizes up to %d (h=%d, w=%d, H=%d, W=%d)", PIPS_FILTER_DIM_MAX, h, w, H, W);
+        PIPS_CHECK_ARG((long long)h <= 16ll * H && (long long)w <= 16ll * W,
+                       "frames_import: the triangle filter scales down by at most 16 (%d x %d to %d x %d)", h, w, H, W);
+    }
     // plane k of the format: its rows and the bytes of a row
     const void* p[3] = {p0, p1, p2};
     const size_t pitch[3] = {pitch0, pitch1, pitch2}, step[3] = {step0, step1, step2};
-    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2;
-    const int planes = format == PIPS_FMT_NV12 ? 2 : format == PIPS_FMT_I420 ? 3 : 1;
-    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : yuv ? 1 : 3;
+    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2, sb = wide ? 2 : 1;
+    const int planes = semi ? 2 : yuv ? 3 : 1;
+    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : yuv ? sb : 3;
     const size_t rows[3] = {(size_t)h, ch, ch};
-    const size_t row_bytes[3] = {(size_t)w * bpp, format == PIPS_FMT_NV12 ? 2 * cw : cw, cw};
+    const size_t row_bytes[3] = {(size_t)w * bpp, (semi ? 2 * cw : cw) * sb, cw * sb};
     for (int k = 0; k < planes; ++k) {
         PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "frames_import: pitch %zu of plane %d is below the %zu bytes of a row", pitch[k], k,
                        row_bytes[k]);
         PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
                        "frames_import: step %zu of plane %d is below pitch %zu x %zu rows", step[k], k, pitch[k], rows[k]);
+        PIPS_CHECK_ARG(!wide || (((uintptr_t)p[k] | pitch[k] | step[k]) & 1) == 0,
+                       "frames_import: plane %d of a 16-bit format needs an even pointer, pitch and step (pitch %zu, step %zu)", k,
+                       pitch[k], step[k]);
     }
     if (F == 0) return PIPS_OK;
     PIPS_CHECK_ARG(dst != nullptr, "frames_import: null dst");
     for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(p[k] != nullptr, "frames_import: null plane %d", k);
-    return launch_frames_import(format, matrix, range, F, h, w, p, pitch, step, dst, dst_is_u8 != 0, H, W, (hipStream_t)stream);
+    return launch_frames_import(format, matrix, range, filter, F, h, w, p, pitch, step, dst, dst_is_u8 != 0, H, W, (hipStream_t)stream);
+}
+
+int pips_frames_import(int format, int matrix, int range, int F, int h, int w, const void* p0, size_t pitch0, size_t step0,
+                       const void* p1, size_t pitch1, size_t step1, const void* p2, size_t pitch2, size_t step2, void* dst,
+                       int dst_is_u8, int H, int W, void* stream) {
+    PIPS_CHECK_ARG(format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I420, "frames_import: unknown format %d", format);
+    return pips_frames_import_ex(format, matrix, range, PIPS_FILTER_BILINEAR, F, h, w, p0, pitch0, step0, p1, pitch1, step1, p2, pitch2,
+                                 step2, dst, dst_is_u8, H, W, stream);
 }
 
 // ---- whole forward

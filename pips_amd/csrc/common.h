@@ -534,10 +534,11 @@ inline int cut_strips(int h) {
 int launch_cut_table(const void* frames, int src_u8, int F, int h, int w, const int* prev_hist, int* hist, int* dist, int* partial,
                      hipStream_t st);
 
-// ---- frames_import.hip: decoder frames (packed RGB, NV12, I420; any base, pitch and step) to planar (F,3,H,W) uint8 or float32,
-// resized in the same pass when (H, W) != (h, w) (pips_frames_import).  p, pitch, step: three entries each, those of planes the
-// format does not have unused; arguments checked by the caller (F h w and F H W <= PIPS_IMPORT_PIXELS_MAX: a launch's index).
-int launch_frames_import(int format, int matrix, int range, int F, int h, int w, const void* const* p, const size_t* pitch,
+// ---- frames_import.hip: decoder frames (packed RGB, NV12, I420, P010, I010; any base, pitch and step) to planar (F,3,H,W) uint8 or
+// float32, resized in the same pass when (H, W) != (h, w) by `filter` (pips_frames_import_ex).  p, pitch, step: three entries each,
+// those of planes the format does not have unused; arguments checked by the caller (F h w and F H W <= PIPS_IMPORT_PIXELS_MAX: a
+// launch's index; PIPS_FILTER_TRIANGLE's limits).
+int launch_frames_import(int format, int matrix, int range, int filter, int F, int h, int w, const void* const* p, const size_t* pitch,
                          const size_t* step, void* dst, int dst_u8, int H, int W, hipStream_t st);
 
 }  // namespace pips

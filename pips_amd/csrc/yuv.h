@@ -28,4 +28,20 @@ __host__ __device__ __forceinline__ void yuv_to_rgb(const YuvRule& k, int Y, int
     b = yuv_clamp8((c + k.bu * d) >> 16);
 }
 
+// The 10-bit rule (PIPS_FMT_P010, PIPS_FMT_I010): samples 0..1023, c = Y - y0, d = Cb - 512, e = Cr - 512 and
+// R = clamp((ky c + rv e + 2^17) >> 18), G and B likewise, to the same 8-bit levels; every constant is floor(2^18 k + 0.5) with luma
+// scaled by 255/876 and chroma by 255/896 in limited range (the 8-bit constants: a sample of 4 v converts as the 8-bit v does) and
+// both by 255/1023 in full range.  Over all 2^30 triples every accumulator stays inside int32 (-7.7e7 .. 1.5e8).
+constexpr YuvRule YUV10_RULES[2][2] = {
+    {{64, 76309, 104597, -25675, -53279, 132201}, {0, 65344, 91612, -22487, -46664, 115789}},
+    {{64, 76309, 117489, -13975, -34925, 138438}, {0, 65344, 102903, -12240, -30589, 121252}},
+};
+
+__host__ __device__ __forceinline__ void yuv10_to_rgb(const YuvRule& k, int Y, int Cb, int Cr, int& r, int& g, int& b) {
+    const int c = k.ky * (Y - k.y0) + 131072, d = Cb - 512, e = Cr - 512;
+    r = yuv_clamp8((c + k.rv * e) >> 18);
+    g = yuv_clamp8((c + k.gu * d + k.gv * e) >> 18);
+    b = yuv_clamp8((c + k.bu * d) >> 18);
+}
+
 }  // namespace pips

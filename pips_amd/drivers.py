@@ -23,9 +23,10 @@
   frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``); ``Cover(per_cell=k)`` also retires the youngest
   of more than k tracks that share a cell (``cover_scan_thin`` / ``pips_cover_step_thin``).  ``Cover(seed="corners")`` puts each seed on
   the most trackable pixel of its cell (``corner_table_torch`` / ``pips_corner_table``); ``corner_queries`` is the offline form.
-* ``import_frames`` / ``import_frames_torch`` -- a decoder's frames (pitched NV12, I420, packed RGB / BGR with or without alpha) as the
-  planar ``(1,F,3,H,W)`` frames every driver above takes, resized to the model's size in the same ``pips_frames_import`` launch when
-  asked; the second is the same rule in torch ops, bit for bit.
+* ``import_frames`` / ``import_frames_torch`` -- a decoder's frames (pitched NV12, I420, 10-bit P010 and I010, packed RGB / BGR with
+  or without alpha) as the planar ``(1,F,3,H,W)`` frames every driver above takes, resized to the model's size in the same
+  ``pips_frames_import_ex`` launch when asked -- two-tap bilinear, or antialiased with ``antialias=True``; the second is the same
+  rule in torch ops, bit for bit.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -1275,38 +1276,76 @@ YUV_RULES = {
 }
 
 
-def import_frames_torch(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8):
-    """pips_frames_import (include/pips_hip.h) as torch ops, on any device: ``ops.import_frames``' arguments -> planar frames
-    (F,3,H,W), uint8 or float32.  The conversion is int64 arithmetic -- packed formats pick their bytes, NV12 and I420 replicate a
-    chroma sample to its 2 x 2 pixels and apply the fixed-point matrix of ``YUV_RULES`` -- and the resize to ``size`` is the kernel's
-    fp32 arithmetic as elementwise ops in its order (the source index one fused multiply-add, every product and sum of the blend a
-    separate, single-rounded op): equal to the kernel bit for bit."""
+# the 10-bit formats' (P010, I010: samples 0..1023, y0 = 64, chroma centred on 512, constants scaled by 2^18)
+YUV10_RULES = {
+    ("bt601", "limited"): (64, 76309, 104597, -25675, -53279, 132201),
+    ("bt601", "full"): (0, 65344, 91612, -22487, -46664, 115789),
+    ("bt709", "limited"): (64, 76309, 117489, -13975, -34925, 138438),
+    ("bt709", "full"): (0, 65344, 102903, -12240, -30589, 121252),
+}
+
+
+def triangle_taps(n, N, device=None):
+    """PIPS_FILTER_TRIANGLE along one axis of ``n`` source and ``N`` output samples -> (idx, wgt) int64 (N, T): output i sums
+    ``wgt[i, t] * p[idx[i, t]]`` and divides by ``wgt[i].sum()``.  The raw weight of source j is
+    max(0, 2 m - |(2 j + 1) N - (2 i + 1) n|), m = max(n, N), 0 <= j < n; T is the most positive weights of any output, and the
+    entries behind an output's last tap have weight 0 (and a clamped index)."""
+    m2 = 2 * max(n, N)
+    i = torch.arange(N, dtype=torch.int64, device=device)
+    lo = (torch.div((2 * i + 1) * n - m2 - N, 2 * N, rounding_mode="floor") + 1).clamp(min=0)
+    T = 2 * (max(n, N) // N) + 2
+    idx = lo.view(N, 1) + torch.arange(T, dtype=torch.int64, device=device).view(1, T)
+    wgt = (m2 - ((2 * idx + 1) * N - (2 * i.view(N, 1) + 1) * n).abs()).clamp(min=0)
+    wgt = torch.where(idx < n, wgt, torch.zeros_like(wgt))
+    keep = int((wgt > 0).any(dim=0).sum())                                       # (the positive weights of a row are its first ones)
+    return idx.clamp(max=n - 1)[:, :keep], wgt[:, :keep]
+
+
+def import_frames_torch(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8, antialias=False):
+    """pips_frames_import_ex (include/pips_hip.h) as torch ops, on any device: ``ops.import_frames``' arguments -> planar frames
+    (F,3,H,W), uint8 or float32.  The conversion is int64 arithmetic -- packed formats pick their bytes, the YCbCr formats replicate
+    a chroma sample to its 2 x 2 pixels and apply the fixed-point matrix of ``YUV_RULES`` (``YUV10_RULES`` for p010 and i010) -- and
+    the resize to ``size`` is the kernel's fp32 arithmetic as elementwise ops in its order (the source index one fused multiply-add,
+    every product and sum of the blend a separate, single-rounded op), or with ``antialias=True`` the triangle filter in integers:
+    two contractions with ``triangle_taps``' weights and one division.  Equal to the kernels bit for bit."""
     planes, F, h, w = ops.import_planes(planes, fmt)
     if matrix not in ops.IMPORT_MATRICES or range not in ops.IMPORT_RANGES:
         raise ValueError(f"matrix must be one of {sorted(ops.IMPORT_MATRICES)} and range one of {sorted(ops.IMPORT_RANGES)}, "
                          f"not {matrix!r}, {range!r}")
     if dtype not in (torch.uint8, torch.float32):
         raise ValueError(f"dtype must be torch.uint8 or torch.float32, not {dtype}")
-    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
-    if H < 1 or W < 1:
-        raise ValueError(f"size must be at least 1 x 1, not {H} x {W}")
+    H, W = ops.import_size(size, h, w, antialias)
     dev = planes[0].device
-    if fmt in ("nv12", "i420"):
-        Y = planes[0].to(torch.int64)
-        if fmt == "nv12":
+    if fmt in ("nv12", "i420", "p010", "i010"):
+        if fmt in ("nv12", "p010"):
             cb, cr = planes[1][..., 0], planes[1][..., 1]
         else:
             cb, cr = planes[1], planes[2]
+        Y, cb, cr = (c.to(torch.int64) for c in (planes[0], cb, cr))
+        if fmt == "p010":                               # the high ten bits of the word (planes: int16 views of the bits)
+            Y, cb, cr = ((c & 0xFFFF) >> 6 for c in (Y, cb, cr))
+        elif fmt == "i010":                             # the low ten
+            Y, cb, cr = (c & 1023 for c in (Y, cb, cr))
         iy, ix = torch.arange(h, device=dev) >> 1, torch.arange(w, device=dev) >> 1
-        cb, cr = (c.to(torch.int64)[:, iy][:, :, ix] for c in (cb, cr))
-        y0, ky, rv, gu, gv, bu = YUV_RULES[(matrix, range)]
-        c, d, e = ky * (Y - y0) + 32768, cb - 128, cr - 128
-        rgb = torch.stack([(c + rv * e) >> 16, (c + gu * d + gv * e) >> 16, (c + bu * d) >> 16], dim=1).clamp(0, 255)
+        cb, cr = (c[:, iy][:, :, ix] for c in (cb, cr))
+        if fmt in ops.IMPORT_16BIT:
+            (y0, ky, rv, gu, gv, bu), mid, shift = YUV10_RULES[(matrix, range)], 512, 18
+        else:
+            (y0, ky, rv, gu, gv, bu), mid, shift = YUV_RULES[(matrix, range)], 128, 16
+        c, d, e = ky * (Y - y0) + (1 << (shift - 1)), cb - mid, cr - mid
+        rgb = torch.stack([(c + rv * e) >> shift, (c + gu * d + gv * e) >> shift, (c + bu * d) >> shift], dim=1).clamp(0, 255)
     else:
         order = [2, 1, 0] if fmt in ("bgr24", "bgra32") else [0, 1, 2]
         rgb = planes[0][..., order].permute(0, 3, 1, 2).to(torch.int64)
     if (H, W) == (h, w):
         return rgb.to(dtype)
+    if antialias:
+        (jx, wx), (jy, wy) = triangle_taps(w, W, dev), triangle_taps(h, H, dev)
+        rows = sum(rgb[..., j] * r for j, r in zip(jx.unbind(1), wx.unbind(1)))                        # (F,3,h,W): sum_x rx p < 2^27
+        num = sum(rows[:, :, j] * r.view(H, 1) for j, r in zip(jy.unbind(1), wy.unbind(1)))            # (F,3,H,W): < 2^46
+        den = wy.sum(dim=1).view(H, 1) * wx.sum(dim=1).view(1, W)
+        q = torch.div(512 * num + den, 2 * den, rounding_mode="floor")                                 # 8.8 fixed point, half up
+        return q.to(torch.float32) / 256.0 if dtype == torch.float32 else ((q + 128) >> 8).to(torch.uint8)
 
     def taps(n, N):                                     # resize_frames_kernel's source index, second tap and weights along one axis
         s = torch.tensor(float(n), dtype=torch.float32, device=dev) / torch.tensor(float(N), dtype=torch.float32, device=dev)
@@ -1329,19 +1368,20 @@ def import_frames_torch(planes, fmt, size=None, matrix="bt709", range="limited",
     return v if dtype == torch.float32 else (v + 0.5).floor().to(torch.uint8)
 
 
-def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8, device=None):
+def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8, device=None, antialias=False):
     """A decoder's frames -> rgbs (1,F,3,H,W), ready for ``Pips.encode``, ``StreamTracker.push``, ``CoverTracker.push`` and
-    ``MultiStreamTracker.push``: ``ops.import_frames`` (one ``pips_frames_import`` launch; its docstring has the formats) on planes
+    ``MultiStreamTracker.push``: ``ops.import_frames`` (one ``pips_frames_import_ex`` launch; its docstring has the formats) on planes
     that may still lie on the host.  Host planes are copied to ``device`` (default "cuda") in their SOURCE format and converted
     there: an NV12 chunk crosses the bus at 1.5 bytes per pixel, where frames converted on the CPU cost 3.  ``size`` = (H, W)
-    resizes to the model's size in the same launch."""
+    resizes to the model's size in the same launch, with ``antialias=True`` through the triangle filter instead of the two-tap
+    bilinear rule."""
     planes = [planes] if torch.is_tensor(planes) else list(planes)
     if not all(torch.is_tensor(p) for p in planes):
         raise ValueError("planes must be a tensor or a sequence of tensors")
     if device is None:
         device = next((p.device for p in planes if p.is_cuda), "cuda")
     planes = [p.to(device) for p in planes]
-    return ops.import_frames(planes, fmt, size, matrix, range, dtype).unsqueeze(0)
+    return ops.import_frames(planes, fmt, size, matrix, range, dtype, antialias).unsqueeze(0)
 
 
 def find_cuts(rgbs, cut_thr=0.5, scan="torch", slice_frames=64):

@@ -122,26 +122,35 @@ def resize_frames(rgbs, size):
     return out
 
 
-# include/pips_hip.h: PIPS_FMT_*, PIPS_MATRIX_*, PIPS_RANGE_*
-IMPORT_FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4, "i420": 5}
+# include/pips_hip.h: PIPS_FMT_*, PIPS_MATRIX_*, PIPS_RANGE_*, PIPS_FILTER_*
+IMPORT_FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4, "i420": 5, "p010": 6, "i010": 7}
+IMPORT_16BIT = ("p010", "i010")
+FILTER_BILINEAR, FILTER_TRIANGLE = 0, 1
+FILTER_DIM_MAX = 8192
 IMPORT_MATRICES = {"bt601": 0, "bt709": 1}
 IMPORT_RANGES = {"limited": 0, "full": 1}
 
 
 def import_planes(planes, fmt):
     """The checks on the source planes that ``import_frames`` and ``drivers.import_frames_torch`` share: ``planes`` -- a tensor or a
-    sequence of them -- as uint8 tensors of the format's shapes -> (list of planes, F, h, w).  ValueError otherwise."""
+    sequence of them -- as uint8 tensors of the format's shapes -> (list of planes, F, h, w).  The 16-bit formats "p010" and "i010"
+    take uint16 planes, or int16 planes holding the same bits, and come back as int16 views.  ValueError otherwise."""
     if fmt not in IMPORT_FORMATS:
         raise ValueError(f"fmt must be one of {sorted(IMPORT_FORMATS)}, not {fmt!r}")
     planes = [planes] if torch.is_tensor(planes) else list(planes)
-    want = {"nv12": 2, "i420": 3}.get(fmt, 1)
+    want = {"nv12": 2, "i420": 3, "p010": 2, "i010": 3}.get(fmt, 1)
     if len(planes) != want or not all(torch.is_tensor(p) for p in planes):
         raise ValueError(f"{fmt} takes {want} plane tensor(s), not {len(planes)}")
     for p in planes:
-        if p.dtype != torch.uint8:
+        if fmt in IMPORT_16BIT:
+            if p.dtype not in (torch.uint16, torch.int16):
+                raise ValueError(f"{fmt} planes must be uint16 (or int16 holding the same bits), not {p.dtype}")
+        elif p.dtype != torch.uint8:
             raise ValueError(f"{fmt} planes must be uint8, not {p.dtype}")
         if p.device != planes[0].device:
             raise ValueError("the planes must live on one device")
+    if fmt in IMPORT_16BIT:
+        planes = [p.view(torch.int16) for p in planes]
     first = planes[0]
     if want == 1:
         bpp = 4 if fmt in ("rgba32", "bgra32") else 3
@@ -153,13 +162,27 @@ def import_planes(planes, fmt):
             raise ValueError(f"the Y plane must be (F,h,w), not {tuple(first.shape)}")
         F, h, w = first.shape
         ch, cw = (h + 1) // 2, (w + 1) // 2
-        shapes = [(F, ch, cw, 2)] if fmt == "nv12" else [(F, ch, cw)] * 2
+        shapes = [(F, ch, cw, 2)] if fmt in ("nv12", "p010") else [(F, ch, cw)] * 2
         for p, s in zip(planes[1:], shapes):
             if tuple(p.shape) != s:
                 raise ValueError(f"a {fmt} chroma plane of (F,h,w) = {(F, h, w)} must be {s}, not {tuple(p.shape)}")
     if h < 1 or w < 1:
         raise ValueError(f"frames of {h} x {w}: need at least 1 x 1")
     return planes, int(F), int(h), int(w)
+
+
+def import_size(size, h, w, antialias):
+    """``size`` of ``import_frames`` / ``drivers.import_frames_torch`` -> (H, W), held to PIPS_FILTER_TRIANGLE's limits when
+    ``antialias`` asks for it and the size changes.  ValueError otherwise."""
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if H < 1 or W < 1:
+        raise ValueError(f"size must be at least 1 x 1, not {H} x {W}")
+    if antialias and (H, W) != (h, w):
+        if max(h, w, H, W) > FILTER_DIM_MAX:
+            raise ValueError(f"antialias=True takes sizes up to {FILTER_DIM_MAX}, not {h} x {w} -> {H} x {W}")
+        if h > 16 * H or w > 16 * W:
+            raise ValueError(f"antialias=True scales down by at most 16 per axis, not {h} x {w} -> {H} x {W}")
+    return H, W
 
 
 def _pitched(p, inner):
@@ -180,12 +203,15 @@ def _pitched(p, inner):
     return p, pitch, step
 
 
-def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8):
-    """pips_frames_import on device planes in a decoder's layout -> planar frames (F,3,H,W), ``dtype`` uint8 or float32 (0..255):
+def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype=torch.uint8, antialias=False):
+    """pips_frames_import_ex on device planes in a decoder's layout -> planar frames (F,3,H,W), ``dtype`` uint8 or float32 (0..255):
     what ``encoder_fwd``, ``corner_table``, ``cut_table`` and ``Pips.encode`` read.  ``fmt``: "rgb24" / "bgr24" (planes (F,h,w,3)),
     "rgba32" / "bgra32" ((F,h,w,4), alpha not read), "nv12" ((y (F,h,w), uv (F,ceil(h/2),ceil(w/2),2))) or "i420" ((y, u, v)), all
-    uint8.  ``size`` = (H, W) resizes in the same launch (pips_resize_frames' bilinear arithmetic on the converted frames); ``matrix``
-    "bt601" / "bt709" and ``range`` "limited" / "full" are read for nv12 and i420 only.  Row and frame strides go through as pitch
+    uint8; "p010" and "i010" are the 10-bit forms of nv12 and i420 in uint16 (or int16) planes of the same shapes, the value in the
+    high ten bits of a p010 word and the low ten of an i010 word.  ``size`` = (H, W) resizes in the same launch: pips_resize_frames'
+    two-tap bilinear arithmetic on the converted frames, or with ``antialias=True`` the triangle filter (torch's
+    ``antialias=True``; sizes up to 8192, at most 16 x down per axis).  ``matrix`` "bt601" / "bt709" and ``range`` "limited" /
+    "full" are read for the YCbCr formats only.  Row and frame strides go through as pitch
     and step: a ``surface[:, :h, :w]`` view of a pitched allocation is imported without a copy; a plane whose inner strides are not
     the format's is copied once (include/pips_hip.h has the whole rule)."""
     planes, F, h, w = import_planes(planes, fmt)
@@ -194,9 +220,7 @@ def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype
                          f"not {matrix!r}, {range!r}")
     if dtype not in (torch.uint8, torch.float32):
         raise ValueError(f"dtype must be torch.uint8 or torch.float32, not {dtype}")
-    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
-    if H < 1 or W < 1:
-        raise ValueError(f"size must be at least 1 x 1, not {H} x {W}")
+    H, W = import_size(size, h, w, antialias)
     if F * H * W > 2 ** 30:
         raise ValueError(f"{F} frames of {H} x {W} are more than 2^30 output pixels: split the chunk")
     assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
@@ -205,16 +229,17 @@ def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype
     if F == 0:                                                                    # (an empty tensor has no pointer to pass)
         return out
     # the element strides the format asks of each plane's trailing dimensions
-    inner = {"nv12": [(1,), (2, 1)], "i420": [(1,)] * 3}.get(fmt) or [(planes[0].shape[3], 1)]
+    inner = {"nv12": [(1,), (2, 1)], "i420": [(1,)] * 3, "p010": [(1,), (2, 1)], "i010": [(1,)] * 3}.get(fmt) or [(planes[0].shape[3], 1)]
     args, keep = [], []
     for p, tail in zip(planes, inner):
         p, pitch, step = _pitched(p, tail)
         keep.append(p)
-        args += [_lib.ptr(p), pitch, step]
+        args += [_lib.ptr(p), pitch * p.element_size(), step * p.element_size()]
     args += [None, 0, 0] * (3 - len(planes))
     with torch.cuda.device(dev):
-        _call("pips_frames_import", IMPORT_FORMATS[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], F, h, w, *args,
-              _lib.ptr(out), 1 if dtype == torch.uint8 else 0, H, W, _stream())
+        _call("pips_frames_import_ex", IMPORT_FORMATS[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range],
+              FILTER_TRIANGLE if antialias else FILTER_BILINEAR, F, h, w, *args, _lib.ptr(out), 1 if dtype == torch.uint8 else 0, H, W,
+              _stream())
     return out
 
 
