@@ -112,7 +112,8 @@ const char* pips_last_error(void);
  * pips_cut_table and pips_cut_workspace_bytes (the regional luma histogram of each raw frame and its distance to the frame before:
  * where a video has its scene cuts); pips_frames_import (a decoder's NV12, I420 or packed RGB frames, pitched, to the planar frames
  * every entry point reads, resized in the same pass); pips_frames_import_ex (the same with a filter argument -- the antialiasing
- * triangle filter beside the two-tap bilinear -- and the 10-bit formats P010 and I010). */
+ * triangle filter beside the two-tap bilinear -- and the 10-bit formats P010 and I010); pips_tracks_draw and
+ * pips_draw_workspace_bytes (the trails of the tracks drawn onto the decoder's 8-bit surfaces, in place). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -724,6 +725,79 @@ int    pips_frames_import_ex(int format, int matrix, int range, int filter, int 
                              const void* p1, size_t pitch1, size_t step1,
                              const void* p2, size_t pitch2, size_t step2,
                              void* dst, int dst_is_u8, int H, int W, void* stream);
+
+/* Tracks out: pips_tracks_draw draws the trails of n tracks into F caller-owned surfaces of h x w IN PLACE -- the decoder's surface
+ * that pips_frames_import read, on its way to an encoder or a display (chain_demo.py:92-108, utils/improc.py:655-925 draw lines
+ * with a dot at the head on the CPU).  Integers only behind the quantisation of the positions:
+ *  - addressing and formats: planes, pitches and steps in bytes as pips_frames_import's.  PIPS_FMT_RGB24, BGR24, RGBA32, BGRA32,
+ *    NV12 and I420 are taken, and PIPS_FMT_PLANAR8: three planes R, G, B of h rows of w bytes (the (F,3,H,W) uint8 frames
+ *    pips_frames_import writes: p_k = base + k H W, pitch W, step 3 H W).  Bytes outside the w x h image of a plane -- pitch
+ *    padding, the alpha byte, the gap between frames -- are never written; a sample that no track covers keeps its byte and need
+ *    not be written;
+ *  - positions: trajs (G,n,2) float32 are pixel-index coordinates of a src_h x src_w image (the model's frames; an integer is a
+ *    pixel centre), vis (G,n) logits or NULL.  Frame k of the call uses row r = first + k.  With src_w == w the x coordinate is
+ *    used as it is, otherwise u = ((x + 0.5) s) - 0.5 with s = (float)w / (float)src_w, the sum, the product and the difference
+ *    each rounded once to fp32 (the inverse of the import's align_corners=False resize); y likewise with h and src_h.
+ *    Q = (int)floor(8 u + 0.5) (product and sum rounded once each) is the coordinate in eighths of a pixel for finite u with
+ *    |u| <= 32768; for any other u (NaN, infinities, out of range), in x or in y, the point is ABSENT.  Pixel (x, y) has its
+ *    centre at (8 x, 8 y) and four subsamples at (8 x +- 2, 8 y +- 2);
+ *  - the primitives of track i in frame k: none when the point of row r is absent (the trail of a retired or not yet started
+ *    track disappears).  Otherwise the head, a disc of radius dot8 (eighths) around the point of row r, and for every g with
+ *    max(r - trail, 0) < g <= r the capsule of radius line8 around the segment from the point of row g - 1 to that of row g when
+ *    both are present and |dQx| <= PIPS_DRAW_JUMP8_MAX and |dQy| <= PIPS_DRAW_JUMP8_MAX (a longer segment is a tracking failure,
+ *    not a motion).  A negative radius draws nothing of its kind; trail = 0 draws heads only;
+ *  - inside, in exact integers: c the subsample, P0 and P1 the ends (P0 = P1 for the disc), R the radius, a = P1 - P0,
+ *    b = c - P0, L = a . a, t = a . b.  L = 0 or t <= 0: inside when b . b <= R^2; else t >= L: inside when |c - P1|^2 <= R^2;
+ *    else inside when (ax by - ay bx)^2 <= R^2 L.  A subsample outside the ends' bounding box grown by R is never inside and may
+ *    be skipped; within it, with |a| <= 2047 a component and R <= PIPS_DRAW_RADIUS8_MAX (16 px), a . b, b . b and the cross
+ *    product stay below 2^24 (int32), the cross product's square below 2^47 and R^2 L below 2^38 (int64);
+ *  - coverage: k_i in 0..4 = the subsamples of the pixel inside the UNION of track i's primitives (a joint is not drawn twice);
+ *  - opacity: A_i = alpha_vis when vis == NULL or vis[r][i] > vis_logit, else alpha_occ (a NaN logit compares false); both 0..256;
+ *  - blend: the tracks are applied in increasing column order i, each changing the current 8-bit value p of a sample towards
+ *    its colour's component c: a full-resolution sample (R, G, B or Y) to p' = (p (1024 - k A) + c k A + 512) >> 10; a 4:2:0
+ *    chroma sample, with K = the sum of k over those of its 2 x 2 pixels that lie inside the image (0..16; the edge samples of an
+ *    odd h or w have fewer pixels and keep the denominator), to p' = (p (4096 - K A) + c K A + 2048) >> 12.  A weight of 0 leaves
+ *    p.  The order is part of the rule: two overlapping tracks swapped give other bytes;
+ *  - colours: colors (n,3) uint8 R, G, B on the device.  For NV12 and I420 each is converted once,
+ *      Y = y0 + ((yr R + yg G + yb B + 32768) >> 16), Cb = clamp(128 + ((ur R + ug G + ub B + 32768) >> 16)),
+ *      Cr = clamp(128 + ((vr R + vg G + vb B + 32768) >> 16)), >> the arithmetic shift, clamp to [0, 255]:
+ *                                 y0  yr     yg     yb    ur      ug      ub     vr     vg      vb
+ *      PIPS_MATRIX_BT601 limited  16  16829  33039  6416  -9714   -19070  28784  28784  -24103  -4681
+ *      PIPS_MATRIX_BT601 full     0   19595  38470  7471  -11058  -21710  32768  32768  -27439  -5329
+ *      PIPS_MATRIX_BT709 limited  16  11966  40254  4064  -6596   -22188  28784  28784  -26145  -2639
+ *      PIPS_MATRIX_BT709 full     0   13933  46871  4732  -7509   -25259  32768  32768  -29763  -3005
+ *    A grey gives exactly (Y, 128, 128), white 235 / 255; over all 2^24 triples every component is at most one level from
+ *    floor(exact + 0.5) of the real-valued formula, limited range stays in 16..235 / 16..240, and full-range chroma reaches 256
+ *    ahead of the clamp.  matrix and range are looked at for NV12 and I420 only.
+ * Two launches on `stream`: one thread per (frame, track) writes a record into the workspace -- the trail + 1 quantised points, the
+ * drawn segments, the box of pixels the track can touch (the boxes lie together, 16 bytes each), its opacity and converted colour; then one 256-thread block per 16 x 16
+ * pixel tile and frame (it owns the tile's 8 x 8 chroma samples too) walks the tracks 256 at a time, compacts those whose box meets
+ * the tile in column order (a wave ballot and a prefix over the four waves in LDS) and every thread applies them to its pixel in
+ * registers; the four pixels of a chroma sample are neighbouring lanes.  A tile no track meets loads and stores nothing.  No
+ * atomics, no allocation, no synchronisation; the workspace is read and written by this call only and may be reused by the next.
+ * PIPS_E_ARG ahead of any launch, with nothing written: a format that is not one of the seven (PIPS_FMT_P010 and PIPS_FMT_I010
+ * among them); an unknown matrix or range with NV12 or I420; F < 0; n < 0; h, w, src_h or src_w < 1; h or w > PIPS_DRAW_DIM_MAX;
+ * trail outside 0..PIPS_DRAW_TRAIL_MAX; line8 or dot8 > PIPS_DRAW_RADIUS8_MAX; alpha_vis or alpha_occ outside 0..256; first < 0 or
+ * first + F > G; a pitch below the bytes of a row of its plane; with F > 1 a step below pitch x rows of its plane; and with F > 0
+ * and n > 0: a NULL plane that the format has, a NULL trajs, colors or workspace, a workspace off a 16-byte address, workspace_bytes <
+ * pips_draw_workspace_bytes(F, n, trail) (= 4 F n (2 trail + 10) bytes; 0 for F < 0, n < 0 or a trail outside its range).  F = 0 or
+ * n = 0 launches nothing and returns PIPS_OK.
+ * Known limits: the 10-bit surfaces (P010, I010) are not drawn on; chroma is treated as import treats it (one sample for its 2 x 2
+ * pixels, siting not modelled); no text, no colour map along time, no antialiasing beyond the four subsamples; trajs, vis, colors
+ * and the workspace may not overlap a plane. */
+#define PIPS_FMT_PLANAR8 8
+#define PIPS_DRAW_DIM_MAX     8192
+#define PIPS_DRAW_TRAIL_MAX   32
+#define PIPS_DRAW_RADIUS8_MAX 128
+#define PIPS_DRAW_JUMP8_MAX   2047
+size_t pips_draw_workspace_bytes(int F, int n, int trail);
+int    pips_tracks_draw(int format, int matrix, int range, int F, int h, int w,
+                        void* p0, size_t pitch0, size_t step0,
+                        void* p1, size_t pitch1, size_t step1,
+                        void* p2, size_t pitch2, size_t step2,
+                        const float* trajs, const float* vis, int G, int n, int first, int src_h, int src_w,
+                        const uint8_t* colors, int trail, int line8, int dot8, int alpha_vis, int alpha_occ, float vis_logit,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128). */

@@ -28,6 +28,27 @@ __host__ __device__ __forceinline__ void yuv_to_rgb(const YuvRule& k, int Y, int
     b = yuv_clamp8((c + k.bu * d) >> 16);
 }
 
+// The way back, for pips_tracks_draw's colours (include/pips_hip.h): Y = y0 + ((yr R + yg G + yb B + 32768) >> 16),
+// Cb = clamp(128 + ((ur R + ug G + ub B + 32768) >> 16)), Cr = clamp(128 + ((vr R + vg G + vb B + 32768) >> 16)).  The constants are
+// the standard coefficients scaled by 65536 (and by 219/255 for luma, 224/255 for chroma in limited range) and rounded so that each
+// luma row sums to 65536 (56284 in limited range) and each chroma row to 0: a grey gives exactly (Y, 128, 128), white 235 / 255.
+// Full-range chroma reaches 256 ahead of the clamp.  Every accumulator stays inside int32 (|sum| < 2^24).
+struct RgbRule {
+    int y0, yr, yg, yb, ur, ug, ub, vr, vg, vb;
+};
+
+// [matrix][range], as YUV_RULES
+constexpr RgbRule RGB_RULES[2][2] = {
+    {{16, 16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681}, {0, 19595, 38470, 7471, -11058, -21710, 32768, 32768, -27439, -5329}},
+    {{16, 11966, 40254, 4064, -6596, -22188, 28784, 28784, -26145, -2639}, {0, 13933, 46871, 4732, -7509, -25259, 32768, 32768, -29763, -3005}},
+};
+
+__host__ __device__ __forceinline__ void rgb_to_yuv(const RgbRule& k, int r, int g, int b, int& Y, int& Cb, int& Cr) {
+    Y = k.y0 + ((k.yr * r + k.yg * g + k.yb * b + 32768) >> 16);
+    Cb = yuv_clamp8(128 + ((k.ur * r + k.ug * g + k.ub * b + 32768) >> 16));
+    Cr = yuv_clamp8(128 + ((k.vr * r + k.vg * g + k.vb * b + 32768) >> 16));
+}
+
 // The 10-bit rule (PIPS_FMT_P010, PIPS_FMT_I010): samples 0..1023, c = Y - y0, d = Cb - 512, e = Cr - 512 and
 // R = clamp((ky c + rv e + 2^17) >> 18), G and B likewise, to the same 8-bit levels; every constant is floor(2^18 k + 0.5) with luma
 // scaled by 255/876 and chroma by 255/896 in limited range (the 8-bit constants: a sample of 4 v converts as the 8-bit v does) and

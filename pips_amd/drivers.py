@@ -27,6 +27,10 @@
   or without alpha) as the planar ``(1,F,3,H,W)`` frames every driver above takes, resized to the model's size in the same
   ``pips_frames_import_ex`` launch when asked -- two-tap bilinear, or antialiased with ``antialias=True``; the second is the same
   rule in torch ops, bit for bit.
+* ``draw_tracks`` / ``draw_tracks_torch`` / ``TrackPainter`` -- the way out: the trails of a tracker's output drawn onto the decoder's
+  8-bit surfaces on the device, in place (one ``pips_tracks_draw`` call; the second is the same integer rule in torch ops, byte for
+  byte); ``TrackPainter`` paints the pushes of a streamed tracker one by one, keeping the last rows by identity; ``track_colors``
+  gives each identity its colour.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -1382,6 +1386,252 @@ def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype
         device = next((p.device for p in planes if p.is_cuda), "cuda")
     planes = [p.to(device) for p in planes]
     return ops.import_frames(planes, fmt, size, matrix, range, dtype, antialias).unsqueeze(0)
+
+
+_range = range                                     # (several functions below name an argument ``range``, as import does)
+
+
+# pips_tracks_draw's constants (include/pips_hip.h; pips_amd/csrc/yuv.h): (y0, yr, yg, yb, ur, ug, ub, vr, vg, vb) by (matrix, range)
+RGB_RULES = {
+    ("bt601", "limited"): (16, 16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681),
+    ("bt601", "full"): (0, 19595, 38470, 7471, -11058, -21710, 32768, 32768, -27439, -5329),
+    ("bt709", "limited"): (16, 11966, 40254, 4064, -6596, -22188, 28784, 28784, -26145, -2639),
+    ("bt709", "full"): (0, 13933, 46871, 4732, -7509, -25259, 32768, 32768, -29763, -3005),
+}
+
+
+def rgb_to_yuv_torch(rgb, matrix="bt709", range="limited"):
+    """the colour conversion of pips_tracks_draw: rgb (...,3) integers 0..255 -> (...,3) int64 Y, Cb, Cr"""
+    y0, yr, yg, yb, ur, ug, ub, vr, vg, vb = RGB_RULES[(matrix, range)]
+    R, G, B = rgb.to(torch.int64).unbind(-1)
+    Y = y0 + ((yr * R + yg * G + yb * B + 32768) >> 16)
+    Cb = (128 + ((ur * R + ug * G + ub * B + 32768) >> 16)).clamp(0, 255)
+    Cr = (128 + ((vr * R + vg * G + vb * B + 32768) >> 16)).clamp(0, 255)
+    return torch.stack([Y, Cb, Cr], dim=-1)
+
+
+def track_colors(ids):
+    """The colour of each identity, ids (n,) integers -> (n,3) uint8 RGB: the hue h = ((id * 2654435769) mod 2^32) >> 24 on a
+    six-segment wheel -- seg = (6 h) >> 8, up = (6 h) & 255, down = 255 - up, and (255,up,0), (down,255,0), (0,255,up), (0,down,255),
+    (up,0,255), (255,0,down) for seg 0..5.  Integers only, on the device of ``ids``: an identity keeps its colour for life."""
+    ids = torch.as_tensor(ids).to(torch.int64).reshape(-1)
+    h = (((ids & 0xFFFFFFFF) * 2654435769) & 0xFFFFFFFF) >> 24               # (int64 products wrap: the low 32 bits are exact)
+    seg, up = (6 * h) >> 8, (6 * h) & 255
+    down, full, none = 255 - up, torch.full_like(up, 255), torch.zeros_like(up)
+    wheel = torch.stack([torch.stack(c, dim=1) for c in ((full, up, none), (down, full, none), (none, full, up), (none, down, full),
+                                                         (up, none, full), (full, none, down))])               # (6,n,3)
+    return wheel[seg, torch.arange(ids.numel(), device=ids.device)].to(torch.uint8)
+
+
+def _round_half_up(v, scale):
+    return int(math.floor(scale * float(v) + 0.5))
+
+
+def _draw_setup(planes, trajs, vis, colors, ids, width, dot, alpha, alpha_occ, vis_thr):
+    """what ``draw_tracks`` and ``draw_tracks_torch`` make of their arguments: trajs (1,G,n,2) / vis (1,G,n) without the batch
+    dimension, the colours, and the rule's integers -> (trajs, vis, colors, line8, dot8, alpha_vis, alpha_occ, vis_logit)"""
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    if not planes or not all(torch.is_tensor(p) for p in planes):
+        raise ValueError("planes must be a tensor or a sequence of tensors")
+    dev = planes[0].device
+    if trajs.dim() != 4 or trajs.shape[0] != 1 or trajs.shape[3] != 2:
+        raise ValueError(f"trajs must be (1,G,n,2), not {tuple(trajs.shape)}")
+    trajs = trajs[0].to(dev, torch.float32)
+    G, n = trajs.shape[:2]
+    if vis is not None:
+        if tuple(vis.shape) != (1, G, n):
+            raise ValueError(f"vis must be (1,G,n) = {(1, G, n)}, not {tuple(vis.shape)}")
+        vis = vis[0].to(dev, torch.float32)
+    if colors is None:
+        if ids is not None and torch.as_tensor(ids).numel() != n:
+            raise ValueError(f"{torch.as_tensor(ids).numel()} ids for {n} columns")
+        colors = track_colors(torch.arange(n) if ids is None else ids)
+    colors = colors.to(dev)
+    if isinstance(vis_thr, bool) or not isinstance(vis_thr, (int, float)) or not 0.0 < vis_thr < 1.0:
+        raise ValueError(f"vis_thr must lie in (0, 1), not {vis_thr!r}")
+    vis_logit = float(torch.logit(torch.tensor(float(vis_thr), dtype=torch.float32)))              # (as Cover: fp32, on the host)
+    return (planes, trajs, vis, colors, _round_half_up(width, 4.0), _round_half_up(dot, 8.0), _round_half_up(alpha, 256.0),
+            _round_half_up(alpha_occ, 256.0), vis_logit)
+
+
+def _draw_quantise(v, n_src, n_dst):
+    """a coordinate column (…) float32 of an ``n_src`` wide axis -> (Q int64 eighths of a pixel of the ``n_dst`` wide axis, present)"""
+    if n_src != n_dst:
+        s = torch.tensor(float(n_dst), dtype=torch.float32, device=v.device) / torch.tensor(float(n_src), dtype=torch.float32, device=v.device)
+        v = ((v + 0.5) * s) - 0.5                                  # three elementwise ops: each rounded once, none fused
+    ok = v.abs() <= 32768.0                                        # (false for NaN and the infinities)
+    q = torch.floor(torch.where(ok, v, torch.zeros_like(v)) * 8.0 + 0.5).to(torch.int64)
+    return q, ok
+
+
+def _draw_inside(cx, cy, p0, p1, R):
+    """the inside test of the rule in int64: subsample coordinates cx (1,1,X), cy (1,Y,1), the ends p0, p1 (n,2) and the radius ->
+    bool (n,Y,X)"""
+    x0, y0, x1, y1 = (t.view(-1, 1, 1) for t in (p0[:, 0], p0[:, 1], p1[:, 0], p1[:, 1]))
+    ax, ay = x1 - x0, y1 - y0
+    bx, by = cx - x0, cy - y0
+    L, t = ax * ax + ay * ay, ax * bx + ay * by
+    R2 = R * R
+    at_p0 = bx * bx + by * by <= R2
+    at_p1 = (cx - x1) ** 2 + (cy - y1) ** 2 <= R2
+    along = (ax * by - ay * bx) ** 2 <= R2 * L
+    return torch.where((L == 0) | (t <= 0), at_p0, torch.where(t >= L, at_p1, along))
+
+
+def draw_coverage_torch(trajs, r, h, w, src_size, trail, line8, dot8):
+    """The coverage of the rule for the frame that takes row ``r`` of trajs (G,n,2): k (n,h,w) int64 in 0..4, the subsamples of
+    each pixel inside the union of each track's primitives.  Subsample (j, i) of the 2h x 2w grid lies at (4 i - 2, 4 j - 2)
+    eighths: pixel x owns columns 2 x and 2 x + 1."""
+    dev, n = trajs.device, trajs.shape[1]
+    src_h, src_w = src_size
+    cx = (4 * torch.arange(2 * w, device=dev) - 2).view(1, 1, -1)
+    cy = (4 * torch.arange(2 * h, device=dev) - 2).view(1, -1, 1)
+    rows = trajs[max(r - trail, 0):r + 1]
+    qx, okx = _draw_quantise(rows[..., 0], src_w, w)
+    qy, oky = _draw_quantise(rows[..., 1], src_h, h)
+    pts, ok = torch.stack([qx, qy], dim=-1), okx & oky             # (m,n,2), (m,n): the head is the last row
+    live = torch.nonzero(ok[-1]).squeeze(1)                        # an absent head hides the whole trail: only these tracks draw
+    pts, ok = pts[:, live], ok[:, live]
+    inside = torch.zeros(live.numel(), 2 * h, 2 * w, dtype=torch.bool, device=dev)
+    if dot8 >= 0:
+        inside |= _draw_inside(cx, cy, pts[-1], pts[-1], dot8)
+    if line8 >= 0:
+        for g in range(1, pts.shape[0]):
+            d = (pts[g] - pts[g - 1]).abs()
+            drawn = ok[g] & ok[g - 1] & (d[:, 0] <= ops.DRAW_JUMP8_MAX) & (d[:, 1] <= ops.DRAW_JUMP8_MAX)
+            if bool(drawn.any()):
+                inside |= _draw_inside(cx, cy, pts[g - 1], pts[g], line8) & drawn.view(-1, 1, 1)
+    k = torch.zeros(n, h, w, dtype=torch.int64, device=dev)
+    k[live] = inside.view(live.numel(), h, 2, w, 2).sum(dim=(2, 4))
+    return k
+
+
+def draw_tracks_torch(planes, fmt, trajs, vis=None, colors=None, ids=None, size=None, first=0, trail=16, width=2.0, dot=3.0, alpha=1.0,
+                      alpha_occ=0.35, vis_thr=0.5, matrix="bt709", range="limited", inplace=False):
+    """pips_tracks_draw (include/pips_hip.h) as int64 torch ops, on any device: ``draw_tracks``' arguments and result.  Per frame the
+    coverage of every track (``draw_coverage_torch``), then the tracks one after the other in column order: the blend of the
+    full-resolution samples with 1024 - k A, and for nv12 / i420 of the chroma samples with K summed over each 2 x 2 block of the
+    zero-padded coverage.  Equal to the kernels bit for bit; written to be read, not to be fast."""
+    planes, trajs, vis, colors, line8, dot8, a_vis, a_occ, vis_logit = _draw_setup(planes, trajs, vis, colors, ids, width, dot, alpha,
+                                                                                  alpha_occ, vis_thr)
+    trail, first = _whole(trail, "trail", 0), _whole(first, "first", 0)
+    planes, F, h, w, G, n, src_h, src_w = ops.draw_check(planes, fmt, trajs, vis, colors, first, size, trail, line8, dot8, a_vis, a_occ,
+                                                         matrix, range)
+    if not inplace:
+        planes = [p.clone() for p in planes]
+    yuv = fmt in ("nv12", "i420")
+    comp = rgb_to_yuv_torch(colors, matrix, range) if yuv else colors.to(torch.int64)               # (n,3) in the surface's components
+    if fmt == "planar8":
+        full = [planes[0][:, c] for c in (0, 1, 2)]                                                # views (F,h,w) the blend writes into
+    elif yuv:
+        full = [planes[0]]
+        chroma = [planes[1][..., 0], planes[1][..., 1]] if fmt == "nv12" else [planes[1], planes[2]]
+    else:
+        full = [planes[0][..., c] for c in ((2, 1, 0) if fmt in ("bgr24", "bgra32") else (0, 1, 2))]
+    for f in _range(F):
+        r = first + f
+        k = draw_coverage_torch(trajs, r, h, w, (src_h, src_w), trail, line8, dot8)                # (n,h,w)
+        seen = torch.ones(n, dtype=torch.bool, device=k.device) if vis is None else vis[r] > vis_logit      # (NaN compares false)
+        A = torch.where(seen, a_vis, a_occ).to(torch.int64)
+        wgt = k * A.view(n, 1, 1)
+        cur = [p[f].to(torch.int64) for p in full]
+        if yuv:
+            K = torch.nn.functional.pad(wgt, (0, w % 2, 0, h % 2)).view(n, (h + 1) // 2, 2, (w + 1) // 2, 2).sum(dim=(2, 4))
+            cur_c = [p[f].to(torch.int64) for p in chroma]
+        for i in _range(n):                                                                # column order is part of the rule
+            cur = [(p * (1024 - wgt[i]) + comp[i, c] * wgt[i] + 512) >> 10 for c, p in enumerate(cur)]
+            if yuv:
+                cur_c = [(p * (4096 - K[i]) + comp[i, 1 + c] * K[i] + 2048) >> 12 for c, p in enumerate(cur_c)]
+        for p, v in zip(full, cur):
+            p[f] = v.to(torch.uint8)
+        if yuv:
+            for p, v in zip(chroma, cur_c):
+                p[f] = v.to(torch.uint8)
+    return planes[0] if len(planes) == 1 else planes
+
+
+def draw_tracks(planes, fmt, trajs, vis=None, colors=None, ids=None, size=None, first=0, trail=16, width=2.0, dot=3.0, alpha=1.0,
+                alpha_occ=0.35, vis_thr=0.5, matrix="bt709", range="limited", inplace=False):
+    """Tracks drawn onto frames on the device, one ``pips_tracks_draw`` call (``ops.draw_tracks``; include/pips_hip.h has the rule):
+    lines along the last ``trail`` rows with a dot at the head, as the reference's demos end (chain_demo.py:92-108).  ``planes`` /
+    ``fmt`` are F surfaces in one of ``ops.import_frames``' six 8-bit layouts, or ``fmt="planar8"`` with one (F,3,h,w) uint8 tensor
+    (``import_frames``' own output, without the batch dimension).  trajs (1,G,n,2) and vis (1,G,n) logits (or None) are a tracker's
+    output; frame k of the surfaces takes row ``first + k``.  ``size`` = the model's (H, W) when the surfaces are larger (positions
+    are mapped back through the import's resize).  ``width`` is the full line width and ``dot`` the head's radius in surface pixels
+    (a negative value draws none), ``alpha`` / ``alpha_occ`` the opacity of a track whose visibility is above / not above
+    ``vis_thr`` (a probability; ``vis=None``: all visible).  ``colors`` (n,3) uint8 RGB, default ``track_colors(ids)``
+    (``track_colors(arange(n))`` without ``ids``); ``matrix`` / ``range`` as for import.  ``inplace=False`` draws on clones and
+    returns them (a tensor for one plane, a list otherwise); ``inplace=True`` draws on the given tensors -- pitched views included
+    -- and returns them.  Later columns are drawn over earlier ones."""
+    planes, trajs, vis, colors, line8, dot8, a_vis, a_occ, vis_logit = _draw_setup(planes, trajs, vis, colors, ids, width, dot, alpha,
+                                                                                  alpha_occ, vis_thr)
+    trail, first = _whole(trail, "trail", 0), _whole(first, "first", 0)
+    if not inplace:
+        planes = [p.clone() for p in planes]
+    ops.draw_tracks(planes, fmt, trajs, vis, colors, first, size, trail, line8, dot8, a_vis, a_occ, vis_logit, matrix, range)
+    return planes[0] if len(planes) == 1 else planes
+
+
+PAINT_ENGINES = ("library", "torch")
+
+
+class TrackPainter:
+    """Draws what a streamed tracker returns, push by push: ``paint(planes, fmt, f0, trajs, vis, ids)`` takes the ``(f0, trajs
+    (1,m,n,2), vis (1,m,n)[, ids (n,)])`` of ``StreamTracker.push``, ``CoverTracker.push`` or one stream of
+    ``MultiStreamTracker.push`` (one painter per stream) and the m surfaces of the frames ``[f0, f0 + m)``, and draws them as
+    ``draw_tracks`` does.  It keeps the last ``trail`` rows BY IDENTITY on the device between calls, so a trail runs across pushes:
+    painting push by push gives the bytes of one ``draw_tracks`` call over the whole video (trajs by identity, NaN outside each
+    life, ``colors=track_colors(arange(K))``).  An identity it has not seen gets NaN history, one that is no longer among ``ids`` is
+    dropped; ``ids=None`` means the columns are stable (their number may not change).  ``size`` is the model's (H, W); ``style`` are
+    ``draw_tracks``' width, dot, alpha, alpha_occ, vis_thr, matrix and range.
+    The painter does not hold frames.  A push returns rows of frames it was given EARLIER (a frame is returned once every query is
+    past it), so the caller keeps its surfaces -- a decoder's pool, a ring of NV12 buffers -- until their rows come back, paints
+    them then and hands them on.  ``engine="torch"`` paints with ``draw_tracks_torch`` (any device) instead of the library."""
+
+    def __init__(self, size, trail=16, engine="library", **style):
+        self.size = (int(size[0]), int(size[1]))
+        self.trail = _whole(trail, "trail", 0)
+        if self.trail > ops.DRAW_TRAIL_MAX:
+            raise ValueError(f"trail must lie in 0..{ops.DRAW_TRAIL_MAX}, not {trail}")
+        if engine not in PAINT_ENGINES:
+            raise ValueError(f"engine must be one of {PAINT_ENGINES}, not {engine!r}")
+        unknown = set(style) - {"width", "dot", "alpha", "alpha_occ", "vis_thr", "matrix", "range"}
+        if unknown:
+            raise ValueError(f"unknown style arguments {sorted(unknown)}")
+        self.engine, self.style = engine, style
+        self.ids, self.rows, self.T = None, None, None              # the columns of ``rows`` (trail,n,2), the next frame
+
+    @torch.no_grad()
+    def paint(self, planes, fmt, f0, trajs, vis=None, ids=None, inplace=True):
+        if trajs.dim() != 4 or trajs.shape[0] != 1 or trajs.shape[3] != 2:
+            raise ValueError(f"trajs must be (1,m,n,2), not {tuple(trajs.shape)}")
+        if self.T is not None and int(f0) != self.T:
+            raise ValueError(f"rows of frame {int(f0)} painted after frame {self.T - 1}")
+        m, n = trajs.shape[1:3]
+        now = trajs[0].to(torch.float32)
+        if ids is not None:
+            ids = [int(i) for i in torch.as_tensor(ids).reshape(-1).tolist()]
+            if len(ids) != n or len(set(ids)) != n:
+                raise ValueError(f"ids must name the {n} columns, each once")
+        elif self.rows is not None and self.rows.shape[1] != n:
+            raise ValueError(f"{n} columns after {self.rows.shape[1]}: pass ids when the columns change")
+        hist = torch.full((self.trail, n, 2), float("nan"), dtype=torch.float32, device=now.device)
+        if self.rows is not None and self.rows.numel() > 0 and n > 0:
+            if ids is None or self.ids is None:
+                hist = self.rows.to(now.device)
+            else:
+                col = {i: j for j, i in enumerate(self.ids)}
+                new = [j for j, i in enumerate(ids) if i in col]
+                if new:
+                    old = torch.tensor([col[ids[j]] for j in new], device=now.device)
+                    hist[:, torch.tensor(new, device=now.device)] = self.rows.to(now.device)[:, old]
+        rows = torch.cat([hist, now])                                 # (trail + m, n, 2): frame k of the push takes row trail + k
+        all_vis = None if vis is None else torch.cat([vis.new_zeros(1, self.trail, n).to(torch.float32), vis.to(torch.float32)], dim=1)
+        draw = draw_tracks if self.engine == "library" else draw_tracks_torch
+        out = draw(planes, fmt, rows.unsqueeze(0), all_vis, ids=ids, size=self.size, first=self.trail, trail=self.trail,
+                   inplace=inplace, **self.style)
+        self.rows, self.ids, self.T = rows[rows.shape[0] - self.trail:], ids, int(f0) + m
+        return out
 
 
 def find_cuts(rgbs, cut_thr=0.5, scan="torch", slice_frames=64):

@@ -243,6 +243,127 @@ def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype
     return out
 
 
+# include/pips_hip.h: the formats pips_tracks_draw takes, PIPS_DRAW_*
+DRAW_FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4, "i420": 5, "planar8": 8}
+DRAW_DIM_MAX, DRAW_TRAIL_MAX, DRAW_RADIUS8_MAX, DRAW_JUMP8_MAX = 8192, 32, 128, 2047
+
+
+def draw_planes(planes, fmt):
+    """The checks on the surfaces that ``draw_tracks`` and ``drivers.draw_tracks_torch`` share: ``import_planes``' for the six 8-bit
+    decoder formats, and for "planar8" one uint8 tensor (F,3,h,w) -- the frames ``import_frames`` returns -> (list of planes, F, h,
+    w).  ValueError otherwise (the 10-bit formats are not drawn on)."""
+    if fmt not in DRAW_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(DRAW_FORMATS)}, not {fmt!r}")
+    if fmt != "planar8":
+        return import_planes(planes, fmt)
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    if len(planes) != 1 or not torch.is_tensor(planes[0]):
+        raise ValueError(f"planar8 takes 1 plane tensor, not {len(planes)}")
+    p = planes[0]
+    if p.dtype != torch.uint8 or p.dim() != 4 or p.shape[1] != 3:
+        raise ValueError(f"planar8 frames must be uint8 (F,3,h,w), not {p.dtype} {tuple(p.shape)}")
+    F, _, h, w = p.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"frames of {h} x {w}: need at least 1 x 1")
+    return planes, int(F), int(h), int(w)
+
+
+def draw_check(planes, fmt, trajs, vis, colors, first, src_size, trail, line8, dot8, alpha_vis, alpha_occ, matrix, range):
+    """pips_tracks_draw's limits on the values, shared by ``draw_tracks`` and the twin -> (planes, F, h, w, G, n, src_h, src_w)"""
+    planes, F, h, w = draw_planes(planes, fmt)
+    if matrix not in IMPORT_MATRICES or range not in IMPORT_RANGES:
+        raise ValueError(f"matrix must be one of {sorted(IMPORT_MATRICES)} and range one of {sorted(IMPORT_RANGES)}, "
+                         f"not {matrix!r}, {range!r}")
+    if trajs.dim() != 3 or trajs.shape[2] != 2 or trajs.dtype != torch.float32:
+        raise ValueError(f"trajs must be float32 (G,n,2), not {trajs.dtype} {tuple(trajs.shape)}")
+    G, n = int(trajs.shape[0]), int(trajs.shape[1])
+    if vis is not None and (tuple(vis.shape) != (G, n) or vis.dtype != torch.float32):
+        raise ValueError(f"vis must be float32 (G,n) = {(G, n)} or None, not {vis.dtype} {tuple(vis.shape)}")
+    if tuple(colors.shape) != (n, 3) or colors.dtype != torch.uint8:
+        raise ValueError(f"colors must be uint8 (n,3) = {(n, 3)}, not {colors.dtype} {tuple(colors.shape)}")
+    src_h, src_w = (h, w) if src_size is None else (int(src_size[0]), int(src_size[1]))
+    if src_h < 1 or src_w < 1:
+        raise ValueError(f"size must be at least 1 x 1, not {src_h} x {src_w}")
+    if max(h, w) > DRAW_DIM_MAX:
+        raise ValueError(f"surfaces up to {DRAW_DIM_MAX} a side, not {h} x {w}")
+    if not 0 <= trail <= DRAW_TRAIL_MAX:
+        raise ValueError(f"trail must lie in 0..{DRAW_TRAIL_MAX}, not {trail}")
+    if max(line8, dot8) > DRAW_RADIUS8_MAX:
+        raise ValueError(f"a radius of at most {DRAW_RADIUS8_MAX} eighths of a pixel, not line8 = {line8}, dot8 = {dot8}")
+    if not (0 <= alpha_vis <= 256 and 0 <= alpha_occ <= 256):
+        raise ValueError(f"alphas must lie in 0..256, not {alpha_vis}, {alpha_occ}")
+    if first < 0 or first + F > G:
+        raise ValueError(f"rows [{first}, {first} + {F}) of trajs with {G} rows")
+    return planes, F, h, w, G, n, src_h, src_w
+
+
+def _surface(p, inner):
+    """plane (F, rows, ...) that is drawn on in place -> (pitch, step) in elements; ValueError where its strides do not describe
+    rows ``pitch`` >= a row apart and frames ``step`` >= pitch * rows apart with the format's element strides ``inner`` inside a row
+    (``_pitched`` copies such a plane; a copy cannot be drawn on)"""
+    F, rows = p.shape[0], p.shape[1]
+    row_bytes = p[0, 0].numel() if F else 0
+    ok = all(p.stride(-1 - i) == s or p.shape[-1 - i] == 1 for i, s in enumerate(reversed(inner)))
+    pitch, step = p.stride(1), p.stride(0)
+    if rows == 1:
+        pitch = max(pitch, row_bytes)
+    if F == 1:
+        step = pitch * rows
+    if not ok or pitch < row_bytes or step < pitch * rows:
+        raise ValueError(f"a surface of shape {tuple(p.shape)} and strides {tuple(p.stride())} cannot be drawn on in place")
+    return pitch, step
+
+
+def draw_workspace_bytes(F, n, trail):
+    return int(_lib.load().pips_draw_workspace_bytes(int(F), int(n), int(trail)))
+
+
+def draw_tracks(planes, fmt, trajs, vis, colors, first=0, src_size=None, trail=16, line8=8, dot8=24, alpha_vis=256, alpha_occ=90,
+                vis_logit=0.0, matrix="bt709", range="limited", workspace=None):
+    """pips_tracks_draw: the trails of trajs (G,n,2) float32 (pixels of a ``src_size`` = (src_h, src_w) image, default the
+    surfaces' own size) drawn IN PLACE into the device surfaces ``planes`` of format ``fmt`` -- ``import_frames``' six 8-bit formats
+    and shapes, or "planar8": one (F,3,h,w) uint8 tensor.  Frame k takes row ``first + k``; ``vis`` (G,n) logits or None, ``colors``
+    (n,3) uint8 RGB; radii in eighths of a pixel, alphas 0..256 (include/pips_hip.h has the whole rule).  Row and frame strides go
+    through as pitch and step: a ``surface[:, :h, :w]`` view of a pitched allocation is drawn on as it is; a plane whose strides
+    cannot be expressed so is a ValueError.  ``workspace``: a device tensor of at least ``draw_workspace_bytes(F, n, trail)`` bytes
+    to use instead of a fresh one."""
+    trail, line8, dot8, alpha_vis, alpha_occ, first = (int(v) for v in (trail, line8, dot8, alpha_vis, alpha_occ, first))
+    planes, F, h, w, G, n, src_h, src_w = draw_check(planes, fmt, trajs, vis, colors, first, src_size, trail, line8, dot8, alpha_vis,
+                                                     alpha_occ, matrix, range)
+    assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = planes[0].device
+    for t in (trajs, vis, colors, workspace):
+        if t is not None and t.device != dev:
+            raise ValueError("trajs, vis, colors and the workspace must live on the surfaces' device")
+    if F == 0 or n == 0:
+        return
+    if fmt == "planar8":
+        p = planes[0]
+        pitch, step = _surface(p[:, 0], (1,))                                     # the three planes share pitch and step
+        if p.stride(1) < pitch * h:
+            raise ValueError(f"a surface of shape {tuple(p.shape)} and strides {tuple(p.stride())} cannot be drawn on in place")
+        args = []
+        for k in (0, 1, 2):
+            args += [C.c_void_p(p.data_ptr() + k * p.stride(1)), pitch, step]
+    else:
+        inner = {"nv12": [(1,), (2, 1)], "i420": [(1,)] * 3}.get(fmt) or [(planes[0].shape[3], 1)]
+        args = []
+        for p, tail in zip(planes, inner):
+            pitch, step = _surface(p, tail)
+            args += [_lib.ptr(p), pitch, step]
+        args += [None, 0, 0] * (3 - len(planes))
+    trajs, colors = trajs.contiguous(), colors.contiguous()
+    vis = None if vis is None else vis.contiguous()
+    need = draw_workspace_bytes(F, n, trail)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    nbytes = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(dev):
+        _call("pips_tracks_draw", DRAW_FORMATS[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], F, h, w, *args, _lib.ptr(trajs),
+              _lib.ptr(vis), G, n, first, src_h, src_w, _lib.ptr(colors), trail, line8, dot8, alpha_vis, alpha_occ, float(vis_logit),
+              _lib.ptr(workspace), nbytes, _stream())
+
+
 def point_sample(level0, B, xy):
     """level0 (B*S,H8,W8,128), xy (B,N,2) map pixels -> (B,N,128)."""
     xy = _f32(xy)
