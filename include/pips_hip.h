@@ -800,7 +800,8 @@ int    pips_tracks_draw(int format, int matrix, int range, int F, int h, int w,
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
- * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128). */
+ * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128).  PIPS_E_ARG ahead of the launch for a
+ * NULL pointer or B, S, N, H8 or W8 below 1. */
 int    pips_point_sample(const float* level0, int B, int S, int H8, int W8,
                          const float* xy, int N, float* out, void* stream);
 
@@ -1056,7 +1057,8 @@ int    pips_conv_nhwc_f32x3(const float* in, int F, int H, int W, int Cin,
  * the two totals by (#used rows * iters) and (#used rows * iters * (H8*W8 - 1)) (+1e-6, utils.basic.reduce_masked_mean)
  * and adds them;  ce_ws: pips_score_map_workspace_bytes(B,S,H8,W8) of scratch (the four pyramid levels upsampled and
  * summed once: the (B,S,N,H8,W8) volume itself is never formed).  ce_tgt == NULL: exactly pips_forward / pips_track.
- * pips_score_map_prepare / _terms are the two stages on their own. */
+ * pips_score_map_prepare / _terms are the two stages on their own (_terms on any U of B*S frames of H8 x W8 pixels; PIPS_E_ARG
+ * ahead of the launch for a NULL pointer or B, S, N, H8 or W8 below 1). */
 size_t pips_score_map_workspace_bytes(int B, int S, int H8, int W8);
 int    pips_score_map_prepare(const float* pyramid, int B, int S, int H8, int W8, float* U, void* stream);
 int    pips_score_map_terms(const float* U, int B, int S, int H8, int W8, const float* ffeats, int N,

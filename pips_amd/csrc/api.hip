@@ -1410,7 +1410,7 @@ int pips_resize_frames(const void* src, int src_is_u8, int planes, int h, int w,
 // ---- tracker stages
 int pips_point_sample(const float* level0, int B, int S, int H8, int W8, const float* xy, int N, float* out,
                       void* stream) {
-    PIPS_CHECK_ARG(level0 && xy && out && B > 0 && N > 0 && S > 0, "point_sample: bad argument");
+    PIPS_CHECK_ARG(level0 && xy && out && B > 0 && N > 0 && S > 0 && H8 > 0 && W8 > 0, "point_sample: bad argument");
     return launch_point_sample(level0, B, S, H8, W8, xy, N, out, (hipStream_t)stream);
 }
 
@@ -1584,7 +1584,7 @@ int pips_score_map_prepare(const float* pyramid, int B, int S, int H8, int W8, f
 }
 int pips_score_map_terms(const float* U, int B, int S, int H8, int W8, const float* ffeats, int N, const float* tgt,
                          float* out, void* stream) {
-    PIPS_CHECK_ARG(U && ffeats && tgt && out && B > 0 && S > 0 && N > 0, "score_map_terms: bad argument");
+    PIPS_CHECK_ARG(U && ffeats && tgt && out && B > 0 && S > 0 && N > 0 && H8 > 0 && W8 > 0, "score_map_terms: bad argument");
     return launch_score_terms(U, B, S, H8, W8, ffeats, N, tgt, out, (hipStream_t)stream);
 }
 

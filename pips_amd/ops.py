@@ -468,16 +468,54 @@ def mixer_input_build_tiled_timed(pyr, B, H8, W8, ffeats, coords, bf16_maps=Fals
 def score_map_terms(pyr, B, H8, W8, ffeats, tgt):
     """Per mixer row {loss at the target pixel, sum of the losses of the other pixels} of the dense score map
     (nets/pips.py:501-511 + score_map_loss :58-92).  ffeats (B*N*S,128), tgt (B*N*S,3) = {x, y, use}."""
-    lib = _lib.load()
+    return score_map_terms_u(score_map_prepare(pyr, B, S, H8, W8), B, S, H8, W8, ffeats, tgt)
+
+
+def score_map_prepare(pyr, B, S, H8, W8):
+    """pips_score_map_prepare alone: the four levels of a packed pyramid of B*S frames upsampled (align_corners=True) to the
+    level-0 size and summed -> U (B*S, H8, W8, 128)."""
+    U = torch.empty(B * S, H8, W8, LATENT, dtype=torch.float32, device=pyr.device)
+    with torch.cuda.device(pyr.device):
+        _call("pips_score_map_prepare", _lib.ptr(pyr), int(B), int(S), int(H8), int(W8), _lib.ptr(U), _stream())
+    return U
+
+
+def score_map_terms_u(U, B, S, H8, W8, ffeats, tgt):
+    """pips_score_map_terms alone on a given U (B*S, H8, W8, 128), any window length S: ffeats (B*N*S,128), tgt (B*N*S,3) =
+    {x, y, use} -> (B*N*S, 2) {loss at the target pixel, sum of the losses of the other pixels}."""
     ffeats, tgt = _f32(ffeats), _f32(tgt)
+    assert U.is_cuda and U.is_contiguous() and U.dtype == torch.float32 and U.numel() == B * S * H8 * W8 * LATENT
     M = ffeats.shape[0]
-    N = M // (B * S)
-    U = torch.empty(lib.pips_score_map_workspace_bytes(B, S, H8, W8) // 4, dtype=torch.float32, device=ffeats.device)
     out = torch.empty(M, 2, dtype=torch.float32, device=ffeats.device)
     with torch.cuda.device(ffeats.device):
-        _call("pips_score_map_prepare", _lib.ptr(pyr), B, S, H8, W8, _lib.ptr(U), _stream())
-        _call("pips_score_map_terms", _lib.ptr(U), B, S, H8, W8, _lib.ptr(ffeats), N, _lib.ptr(tgt), _lib.ptr(out), _stream())
+        _call("pips_score_map_terms", _lib.ptr(U), int(B), int(S), int(H8), int(W8), _lib.ptr(ffeats), M // (B * S), _lib.ptr(tgt),
+              _lib.ptr(out), _stream())
     return out
+
+
+def track_ce(arena, pyr, B, H8, W8, xys, stride, iters, flags=0, ce_tgt=None):
+    """pips_track_ce on a cached pyramid of B clips of 8 frames: xys (B,N,2) px -> (trajs (iters+1,B,8,N,2), vis (B,8,N),
+    ffeat0 (B,N,128), ce_terms (iters,B*N*8,2) or None).  ce_tgt (B*N*8,3): the score-map targets; None = pips_track."""
+    lib = _lib.load()
+    xys = _f32(xys)
+    N = xys.shape[1]
+    dev = xys.device
+    trajs = torch.empty(iters + 1, B, S, N, 2, dtype=torch.float32, device=dev)
+    vis = torch.empty(B, S, N, dtype=torch.float32, device=dev)
+    ffeat0 = torch.empty(B, N, LATENT, dtype=torch.float32, device=dev)
+    nb = lib.pips_track_workspace_bytes(B, N)
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+    tt = times_table(dev)
+    ce_terms = ce_ws = None
+    if ce_tgt is not None:
+        ce_tgt = _f32(ce_tgt)
+        ce_terms = torch.empty(iters, B * N * S, 2, dtype=torch.float32, device=dev)
+        ce_ws = torch.empty(lib.pips_score_map_workspace_bytes(B, S, H8, W8) // 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _call("pips_track_ce", _lib.ptr(arena), _lib.ptr(pyr), int(B), S, int(H8), int(W8), _lib.ptr(xys), None, None, None, _lib.ptr(tt),
+              N, int(stride), int(iters), int(flags), _lib.ptr(ws), nb, _lib.ptr(trajs), _lib.ptr(vis), _lib.ptr(ffeat0), _lib.ptr(ce_tgt),
+              _lib.ptr(ce_terms), _lib.ptr(ce_ws), 0 if ce_ws is None else ce_ws.numel() * 4, _stream())
+    return trajs, vis, ffeat0, ce_terms
 
 
 def _mixer_buffers(X, S):
