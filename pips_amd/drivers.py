@@ -18,7 +18,7 @@
 * ``MultiStreamTracker`` / ``track_streams`` -- ``StreamTracker`` for a LIST of streams (equal frame size; own lengths, chunking,
   queries and ends) on one cache of rings (``Pips.ring_cache_videos``) and one state: a round hops the ready queries of every
   stream together, and each stream gets what its own ``StreamTracker`` returns, bit for bit.
-* ``CoverTracker`` / ``track_cover`` (and ``MultiStreamTracker(cover=)``) -- a ``StreamTracker`` that decides which queries it tracks:
+* ``CoverTracker`` / ``track_cover`` (and ``MultiStreamTracker(cover=)``) -- a stream that decides which queries it tracks:
   a ``Cover`` policy retires the queries that left the frame or stayed invisible and seeds the empty cells of a grid over the
   frame after every push, in torch ops or as one ``pips_cover_step`` call (``scan``); ``Cover(per_cell=k)`` also retires the youngest
   of more than k tracks that share a cell (``cover_scan_thin`` / ``pips_cover_step_thin``).  ``Cover(seed="corners")`` puts each seed on
@@ -42,9 +42,10 @@ ONE library call (``Pips.chain_hop``: the same bookkeeping as HIP kernels around
 and reads the live count back, one host sync per hop either way.  Both give the same hops and the same bits.
 
 The streamed trackers are ONE core, ``_StreamCore``, whose docstring states their rules -- when a query is ready, how it joins, when
-a frame is final, how much room a push has: ``StreamTracker`` is its one-stream form on one ring, ``MultiStreamTracker`` its form on V
-rings behind a clip table.  Both take ``rounds="torch" | "library"`` and keep the device state in one object per value, for one
-stream or V: ``_TorchRounds`` decides who is ready, who joins and which frames are final in torch ops and hops on the chosen engine;
+a frame is final, how much room a push has, and what a covered stream does when: ``StreamTracker`` is its one-stream form on one
+ring, ``CoverTracker`` that form with a cover, ``MultiStreamTracker`` its form on V rings behind a clip table, covered or not.
+All take ``rounds="torch" | "library"`` and keep the device state in one object per value, for one stream or V:
+``_TorchRounds`` decides who is ready, who joins and which frames are final in torch ops and hops on the chosen engine;
 for ``_LibraryRounds`` the round itself is one ``pips_stream_round`` / ``pips_stream_round_clips`` call on int32 state.  The clip table
 is optional in both, as it is in the library (a NULL table is the one-video form): it decides which entry points are called,
 nothing else.  Queries can be added while a video runs (``add_queries``, either value) and taken away again (``remove_queries``: the
@@ -669,7 +670,25 @@ class _StreamCore:
     The state has one column per query -- those of stream 0, then of stream 1, ..., then the ones ``add_queries`` brought, in
     ``tq_host`` / ``xy_in`` / ``clip_host`` / ``hops`` on the host and in ``self.state`` on the device (``_TorchRounds`` or ``_LibraryRounds`` by
     ``rounds``: (slots + 8) output rows per query being tracked); ``columns(v)`` are the columns of stream v, in the order of its
-    outputs.  ``engine="native"`` (``rounds="torch"``) needs the one-ring cache.  Same hops and the same bits under every value."""
+    outputs.  ``engine="native"`` (``rounds="torch"``) needs the one-ring cache.  Same hops and the same bits under every value.
+
+    Cover.  With ``cover`` (a ``Cover``) the queries are the cover's: every stream has a book (``books[v]``, a ``_CoverBook``) that acts
+      through ``_add_queries`` / ``_remove_queries``, a caller's ``add_queries`` / ``remove_queries`` raise, and ``push`` / ``finish`` put
+      ``ids``, the identity of each returned column, behind each stream's tuple.  The FIRST STEP of every stream runs inside the
+      first ``push``, after every check and once the ring is made (the frame size is known then), before anything is encoded: it
+      seeds frame 0.  A ``push`` then, in this order: hands each book the frames it brings (``see``, under ``seed="corners"``: their
+      corner tables, one call per chunk and stream); takes ``ids``; encodes and hops; and runs a cover step (``step``) on the
+      frames each stream returned, if any -- it retires and seeds for the pushes that follow.  ``finish`` runs no step.
+      HELD SEEDS (``seed="corners"``): seeds whose frame was not pushed yet -- the first step's, and those of a stream that lost
+      every query at once -- have no column and no identity; the ``see`` that brings their frame places them on its corners and
+      adds them, with the columns and identities they would have had; ``finish`` drops them.
+      CUTS (``Cover(cut_thr=)``, ONE stream: ``MultiStreamTracker`` refuses it).  After the checks and the first step the book
+      looks at the pushed frames (``look``: one table call per chunk); a refused push leaves its ``prev_hist`` alone.  A push that
+      holds a cut before frame ``c`` is split there: between two pieces every started query is ended on frame ``c - 1`` as the end
+      of a video ends it (``_cut``: ALL its frames are returned) and retired as ``(c - 1, "cut")``, and every cell without a pending
+      query is seeded on frame ``c`` (the book's ``cut``); each piece is a push of its own, tables and closing step included.  Such
+      a push returns the identities alive at its start followed by those created during it (before its last piece's closing
+      step), NaN where an identity had not started or was retired."""
 
     S = 8
 
@@ -828,10 +847,40 @@ class _StreamCore:
                 cols = self.columns(v)
                 self.books[v].start(*size, self.cache.device, self.tq_host[cols], self.xy_in[cols.to(self.xy_in.device)],
                                     *self._cover_acts(v))
+        if self.cover is None or self.cover.cut_thr is None:
+            return self._piece(chunks)
+        # scene cuts.  ONE stream from here on (MultiStreamTracker takes no Cover(cut_thr=)): the frames are looked at after every
+        # check and after the first step, the push is split at the cuts, and between two pieces every started query is ended
+        # (``_cut``) and the book retires them and seeds the new scene (``cut``)
+        assert self.V == 1
+        (frames,), book = chunks, self.books[0]
+        at = [] if frames is None else book.look(frames[0])
+        if not at:
+            return self._piece(chunks)
+        parts, T0 = [], self.frames(0)
+        for j, (a, b) in enumerate(zip([0] + at, at + [frames.shape[1]])):
+            if j > 0:
+                ids = self.stream_ids(0)
+                f0, trajs, vis, keep = self._cut(0)
+                parts.append((f0, trajs, vis, ids))
+                book.cut(T0 + a, keep, self.cut_hops, self._cover_acts(0)[0])
+            if b > a:
+                parts.append(self._piece([frames[:, a:b]])[0])
+        # the columns: the identities alive at the start of the push, then those created before the last piece's closing step --
+        # every identity is in the part that follows its creation, and the new ones are numbered upwards
+        first = parts[0][3].tolist()
+        out = first + sorted({i for p in parts[1:] for i in p[3].tolist()} - set(first))
+        col = torch.zeros(max(out) + 1 if out else 0, dtype=torch.int64)
+        col[torch.tensor(out, dtype=torch.int64)] = torch.arange(len(out))
+        return [(parts[0][0],) + _scatter(parts, col, len(out), parts[0][0]) + (torch.tensor(out, dtype=torch.int64),)]
+
+    def _piece(self, chunks):
+        """``push`` for a run of frames with no cut inside: under ``seed="corners"`` the books' tables of what it brings, the waves
+        and their rounds and, on a covered tracker, the cover step on what each stream returned"""
         for v, c in enumerate(chunks if self.cover is not None and self.cover.seed == "corners" else []):
-            if c is not None:                                                     # the tables of what this push brings
+            if c is not None:
                 self.books[v].see(c[0], self.emitted[v], self._cover_acts(v)[0])
-        ids = None if self.cover is None else [self.stream_ids(v) for v in range(self.V)]
+        ids = None if self.cover is None else [self.stream_ids(v) for v in range(self.V)]      # (none is made before the step)
         f0, outs = list(self.emitted), [[] for _ in range(self.V)]
         left = [0 if c is None else c.shape[1] for c in chunks]
         while any(left):
@@ -947,8 +996,8 @@ class StreamTracker:
 
     S = 8
 
-    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
-        self.core = _StreamCore(model, [queries], iters, slots, record_hops, engine, rounds, table=False)
+    def __init__(self, model, queries, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch", _cover=None):
+        self.core = _StreamCore(model, [queries], iters, slots, record_hops, engine, rounds, table=False, cover=_cover)
 
     model, iters, slots, engine, rounds, tq_host, xy_in, N, hops, cut_hops, cache, size, state, trajs, vis, cur = (
         property(lambda self, k=k: getattr(self.core, k)) for k in (
@@ -969,6 +1018,7 @@ class StreamTracker:
         return self.core.finish(0)
 
     def cut(self):
+        self.core._uncovered("cut")
         return self.core._cut(0)
 
 
@@ -978,13 +1028,14 @@ def track_stream(model, chunks, queries, iters=6, slots=24, return_hops=False, e
     before each query's frame.  ``return_hops=True``: also, per query, the frame steps of its windows.  ``engine`` / ``rounds``:
     see ``StreamTracker``."""
     st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=return_hops, engine=engine, rounds=rounds)
-    parts = [st.push(c) for c in chunks]
-    parts.append(st.finish())
-    trajs = torch.cat([p[1] for p in parts], dim=1)
-    vis = torch.cat([p[2] for p in parts], dim=1)
-    if not return_hops:
-        return trajs, vis
-    return trajs, vis, st.hops
+    return _joined([st.push(c) for c in chunks] + [st.finish()], None, st.hops, return_hops)
+
+
+def _joined(parts, book, hops, return_hops):
+    """the parts one stream's pushes and its ``finish`` returned as ONE result: their rows behind one another -> (trajs, vis), or
+    with the ``book`` of a covered stream by identity (``_by_identity``) -> (trajs, vis, born, retired); ``hops`` behind them when asked"""
+    out = (torch.cat([p[1] for p in parts], dim=1), torch.cat([p[2] for p in parts], dim=1)) if book is None else _by_identity(parts, book)
+    return out + (hops,) if return_hops else out
 
 
 # ---------------------------------------------------------------------------------------------- keeping the frame covered
@@ -1029,7 +1080,7 @@ class Cover:
     ``cut_thr=x`` (``None``, the default: no frame is looked at and every path is the one described so far) ends the tracks at scene
     cuts: a cut lies before a pushed frame whose regional luma histogram differs from that of the frame before by more than
     ``cut_limit(x, H, W)`` (``cut_table_torch`` / one ``pips_cut_table`` call per pushed chunk, by ``scan``: the same integers).  A
-    ``CoverTracker`` splits a push there, ends every started query as "cut" on the last frame of the old scene (``StreamTracker.cut``)
+    ``CoverTracker`` splits a push there, ends every started query as "cut" on the last frame of the old scene (the core's ``_cut``)
     and seeds every cell of the new scene's first frame.  0.5 is a reasonable value, not a tuned one: on one 640 x 360 video with fast
     motion consecutive frames stayed below 0.15 and frames 64 apart below 0.45, a frame against its negative reached 0.6."""
 
@@ -1081,31 +1132,34 @@ class Cover:
             return ops.cover_place(seeds.contiguous(), table, H, W, self.cell, self.min_corner)
         return cover_place_torch(seeds, table, H, W, self.cell, self.min_corner)
 
-    def step(self, trajs, vis, f1, tq, xy, lost, H, W):
-        """one cover step by the chosen scan -> (keep (n_keep) ints, lost_out (n_keep) int32, seeds (n_seed,3), the four counts
-        on the host); trajs (m,n,2) / vis (m,n) are the rows of frames [f1 - m, f1), tq / lost (n) int32, xy (n,2)"""
-        args = (trajs, vis, f1, tq, xy, lost, H, W, self.cell, self.vis_logit, _INT_MAX if self.lost_after is None else self.lost_after,
-                _INT_MAX if self.max_queries is None else self.max_queries)
-        if self.scan == "library":
-            keep, lost_out, seeds, counts = ops.cover_step(*args)
-            counts = counts.tolist()                                              # the one host read
+    def step(self, trajs, vis, f1, tq, xy, lost, crowd, H, W):
+        """one cover step by the chosen scan and policy -> (keep (n_keep) ints, lost_out (n_keep) int32, crowd_out (n_keep) int32 or
+        None, seeds (n_seed,3), gone, why, counts): ``gone`` are the retired columns, ascending, and ``why`` their reasons ("outside" /
+        "lost" / "crowded"), both host lists; ``counts`` [n_keep, n_seed, n_outside, n_lost(, n_crowded)] on the host.  trajs (m,n,2) /
+        vis (m,n) are the rows of frames [f1 - m, f1), tq / lost (n) int32, xy (n,2).  Without ``per_cell`` it is ``cover_scan`` or one
+        ``pips_cover_step`` call and ``crowd`` is not looked at; with it, ``crowd`` (n) int32 is the second run and the step is
+        ``cover_scan_thin`` or one ``pips_cover_step_thin`` call.  The counts are the one host read; who went and why comes over only
+        when they say that somebody did -- the thin step's own lists, or the kept list and the goners' last row, which tell
+        "outside" from "lost" by the step's inside test"""
+        n, thin, library = tq.numel(), self.per_cell is not None, self.scan == "library"
+        caps = (_INT_MAX if self.lost_after is None else self.lost_after, _INT_MAX if self.max_queries is None else self.max_queries)
+        if thin:
+            keep, lost_out, crowd_out, seeds, gone, reason, counts = (ops.cover_step_thin if library else cover_scan_thin)(
+                trajs, vis, f1, tq, xy, lost, crowd, H, W, self.cell, self.vis_logit, *caps, self.per_cell, self.crowd_after)
         else:
-            keep, lost_out, seeds, counts = cover_scan(*args)
-        return keep[:counts[0]], lost_out[:counts[0]], seeds[:counts[1]], counts
-
-    def step_thin(self, trajs, vis, f1, tq, xy, lost, crowd, H, W):
-        """one thin cover step (``per_cell`` is set) by the chosen scan -> (keep, lost_out, crowd_out (n_keep), seeds (n_seed,3), gone,
-        reason (n - n_keep) int32 -- the retired columns and 1 outside / 2 lost / 3 crowded --, the five counts on the host);
-        ``crowd`` (n) int32 is the second run, the other arguments are ``step``'s"""
-        args = (trajs, vis, f1, tq, xy, lost, crowd, H, W, self.cell, self.vis_logit, _INT_MAX if self.lost_after is None else self.lost_after,
-                _INT_MAX if self.max_queries is None else self.max_queries, self.per_cell, self.crowd_after)
-        if self.scan == "library":
-            keep, lost_out, crowd_out, seeds, gone, reason, counts = ops.cover_step_thin(*args)
+            keep, lost_out, seeds, counts = (ops.cover_step if library else cover_scan)(
+                trajs, vis, f1, tq, xy, lost, H, W, self.cell, self.vis_logit, *caps)
+        if library:
             counts = counts.tolist()                                              # the one host read
-        else:
-            keep, lost_out, crowd_out, seeds, gone, reason, counts = cover_scan_thin(*args)
-        k, r = counts[0], tq.numel() - counts[0]
-        return keep[:k], lost_out[:k], crowd_out[:k], seeds[:counts[1]], gone[:r], reason[:r], counts
+        k, went, why = counts[0], [], []
+        if k < n and thin:
+            went, why = gone[:n - k].tolist(), [COVER_REASONS[r] for r in reason[:n - k].tolist()]
+        elif k < n:
+            went = sorted(set(range(n)) - set(keep[:k].tolist()))
+            x, y = trajs[-1][torch.tensor(went, device=trajs.device)].to("cpu").unbind(1)
+            why = ["lost" if ok else "outside" for ok in ((x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)).tolist()]
+        assert len(went) == n - k and [why.count(r) for r in COVER_REASONS[1:len(counts) - 1]] == counts[2:]
+        return keep[:k], lost_out[:k], crowd_out[:k] if thin else None, seeds[:counts[1]], went, why, counts
 
 
 def cover_scan(trajs, vis, f1, tq, xy, lost, H, W, cell, vis_logit, lost_after, max_queries):
@@ -1672,9 +1726,10 @@ def cover_place_torch(seeds, table, H, W, cell, min_corner):
 class _CoverBook:
     """What a covered stream keeps per query beside the tracker's own state: the identity of each column (``ids``), the frame of
     each identity (``born``), identity -> (frame, reason) of the retired ones (``retired``), their hop lists (``hops``, when recorded)
-    and, on the device, the arrays a cover step reads -- ``tq`` / ``lost`` (n) int32, ``xy`` (n,2) and, under ``Cover(per_cell=)``, ``crowd`` (n) int32.  ``start`` runs the first step
-    (no rows: every query is pending and the seeds land on frame 0), ``step`` the one after a push; both act on the tracker
-    through ``add(queries (1,k,3))`` and ``remove(columns)``.
+    and, on the device, the arrays a cover step reads -- ``tq`` / ``lost`` (n) int32, ``xy`` (n,2) and ``crowd``, (n) int32 under
+    ``Cover(per_cell=)`` and None without.  ``start`` runs the first step (no rows: every query is pending and the seeds land on
+    frame 0), ``step`` the one after a push; both act on the tracker through ``add(queries (1,k,3))`` and ``remove(columns)``.
+    ``_StreamCore`` is the only caller of ``start`` / ``see`` / ``step`` / ``look`` / ``cut``; its docstring says when each runs.
     Under ``seed="corners"`` the book also keeps ``table`` (T - table0, gh, gw, 3), the best corners of the frames ``[table0, T)``
     that were pushed and not yet returned when the last push began -- ``see`` takes the frames of a push before they are encoded
     -- and ``held``: the ``(frame, seeds)`` of a step whose frame was not pushed yet.  Held seeds have no column and no identity;
@@ -1702,34 +1757,18 @@ class _CoverBook:
         ``at``: the step without rows after a cut -- the first step's form (f0 = 0, m = 0) whose seeds land on frame ``at``"""
         n, m = len(self.ids), vis.shape[0]
         f1, (H, W) = f0 + m, self.size
-        thin = self.cover.per_cell is not None
-        if thin:
-            keep, lost_out, crowd_out, seeds, gone, reason, counts = self.cover.step_thin(trajs, vis, f1, self.tq, self.xy, self.lost,
-                                                                                          self.crowd, H, W)
-        else:
-            keep, lost_out, seeds, counts = self.cover.step(trajs, vis, f1, self.tq, self.xy, self.lost, H, W)
-        if counts[0] < n:                                                         # somebody is retired: the kept list comes over
-            kept = keep.tolist()
-            if thin:                                                              # ... and the step's own list of who and why
-                gone, why = gone.tolist(), [COVER_REASONS[r] for r in reason.tolist()]
-                assert len(gone) == n - counts[0] and [why.count(r) for r in COVER_REASONS[1:]] == counts[2:]
-            else:
-                gone = sorted(set(range(n)) - set(kept))
-                x, y = trajs[m - 1][torch.tensor(gone, device=trajs.device)].to("cpu").unbind(1)
-                inside = (x >= 0) & (x <= W - 1) & (y >= 0) & (y <= H - 1)
-                why = ["lost" if ok else "outside" for ok in inside.tolist()]
-                assert counts[2] == len(gone) - int(inside.sum()) and counts[3] == int(inside.sum())
+        keep, self.lost, self.crowd, seeds, gone, why, counts = self.cover.step(trajs, vis, f1, self.tq, self.xy, self.lost, self.crowd,
+                                                                                H, W)
+        if gone:                                                                  # somebody is retired
             for c, r in zip(gone, why):
                 self.retired[self.ids[c]] = (f1 - 1, r)
                 if self.hops is not None:
                     self.hops[self.ids[c]] = hops[c]
             remove(gone)
-            self.ids = [self.ids[c] for c in kept]
+            went = set(gone)
+            self.ids = [i for c, i in enumerate(self.ids) if c not in went]
             k = keep.to(torch.int64)
             self.tq, self.xy = self.tq[k], self.xy[k]
-        self.lost = lost_out
-        if thin:
-            self.crowd = crowd_out
         if at is not None:
             assert f1 == 0 and counts[0] == n
             f1, seeds = at, torch.cat([torch.full_like(seeds[:, :1], float(at)), seeds[:, 1:]], dim=1)
@@ -1778,7 +1817,7 @@ class _CoverBook:
         return torch.nonzero(dist > cut_limit(self.cover.cut_thr, *self.size)).squeeze(1).tolist()      # the one host read
 
     def cut(self, c, keep, hops, add):
-        """a cut before frame ``c``: the tracker ended every started query and kept the columns ``keep`` (``StreamTracker.cut``).
+        """a cut before frame ``c``: the tracker ended every started query and kept the columns ``keep`` (``_StreamCore._cut``).
         The ended identities are retired as "cut" on frame c - 1, their runs go; then the step without rows seeds frame ``c`` in
         every cell that holds no pending query (seeds held for frame ``c`` by an earlier step are among them again)"""
         kept = keep.tolist()
@@ -1803,42 +1842,40 @@ class _CoverBook:
         return [out[i] for i in range(len(self.born))]
 
 
-def _by_identity(parts, book):
-    """the ``(f0, trajs, vis, ids)`` parts of a covered stream -> trajs (1,T,K,2), vis (1,T,K) by identity, NaN outside each life,
-    and born (K,), retired (K,) (-1: alive at the end) as host int64"""
-    T, K, dev = sum(p[1].shape[1] for p in parts), len(book.born), parts[0][1].device
+def _scatter(parts, col, K, first=0):
+    """the ``(f0, trajs, vis, ids)`` parts of a covered stream, frames ``first`` and up -> trajs (1,T,K,2), vis (1,T,K) over the T
+    frames the parts hold: identity i in column ``col[i]`` (host int64), NaN where no part has it"""
+    T, dev = sum(p[1].shape[1] for p in parts), parts[0][1].device
     trajs = torch.full((1, T, K, 2), float("nan"), dtype=torch.float32, device=dev)
     vis = torch.full((1, T, K), float("nan"), dtype=torch.float32, device=dev)
     for f0, t, v, ids in parts:
         m = t.shape[1]
         if m > 0 and ids.numel() > 0:
-            i = ids.to(dev)
-            trajs[0][f0:f0 + m][:, i] = t[0]
-            vis[0][f0:f0 + m][:, i] = v[0]
+            j = col[ids].to(dev)
+            trajs[0][f0 - first:f0 - first + m][:, j] = t[0]
+            vis[0][f0 - first:f0 - first + m][:, j] = v[0]
+    return trajs, vis
+
+
+def _by_identity(parts, book):
+    """the ``(f0, trajs, vis, ids)`` parts of a covered stream -> trajs (1,T,K,2), vis (1,T,K) by identity, NaN outside each life,
+    and born (K,), retired (K,) (-1: alive at the end) as host int64"""
+    K = len(book.born)
     retired = torch.tensor([book.retired.get(i, (-1,))[0] for i in range(K)], dtype=torch.int64)
-    return trajs, vis, torch.tensor(book.born, dtype=torch.int64), retired
+    return _scatter(parts, torch.arange(K), K) + (torch.tensor(book.born, dtype=torch.int64), retired)
 
 
 class CoverTracker:
-    """A stream that decides which queries it tracks: a ``StreamTracker`` (driven only through ``add_queries``, ``remove_queries``,
-    ``push`` and ``finish``) plus the policy ``cover`` (a ``Cover``).  ``queries`` (1,N,3) or None are the caller's own; they are
-    tracked, retired and counted like the seeds.  ``push(frames)`` / ``finish()`` return ``(f0, trajs (1,m,n,2), vis (1,m,n), ids
-    (n,))``: ``ids`` is the identity of each returned column (host int64) -- the caller's queries first, then the seeds in order
-    of creation; an identity never changes and is never reused.  The first cover step runs inside the first ``push``, before
-    anything is encoded (the frame size is known then): it seeds frame 0.  (Under ``Cover(seed="corners")`` seeds whose frame was
-    not pushed yet -- these, and those of a stream that lost every query at once -- wait for the ``push`` that brings that frame, are
-    placed on its corners and join at its start, with the columns and identities they would have had; ``finish()`` drops them.)
-    A cover step then runs at the end of every ``push``
-    that returned at least one frame, on those frames, and retires and seeds for the pushes that follow; ``finish()`` runs none.
-    ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost" | "crowded")`` the last frame returned for it and why,
-    ``hops`` (``record_hops=True``) the hop list of each identity.  Over its life an identity is what ``track_stream`` given that
-    query alone returns; frames of a retired query that were not returned before its retirement are discarded.
-    Under ``Cover(cut_thr=)`` a push that holds a scene cut before frame ``c`` is split there: the pieces are pushed one by one, and
-    between them every started query is ended on frame ``c - 1`` as the end of a video ends it (``StreamTracker.cut``: ALL its
-    frames are returned) and retired as ``(c - 1, "cut")``, and every cell without a pending query is seeded on frame ``c``.  Such a
-    push returns the identities alive at its start followed by those created during it (before its last piece's closing step),
-    NaN where an identity had not started or was retired; ``cuts`` lists the cut frames so far.  Over its life an identity of the
-    new scene is what a ``CoverTracker`` started on frame ``c`` gives it."""
+    """A stream that decides which queries it tracks: the one-stream form of a covered ``_StreamCore`` -- a ``StreamTracker`` (``st``)
+    whose core has the policy ``cover`` (a ``Cover``) and the book of stream 0 (``book``); the core's docstring states the rules of a
+    covered stream.  ``queries`` (1,N,3) or None are the caller's own; they are tracked, retired and counted like the seeds.
+    ``push(frames)`` / ``finish()`` return ``(f0, trajs (1,m,n,2), vis (1,m,n), ids (n,))``: ``ids`` is the identity of each returned
+    column (host int64) -- the caller's queries first, then the seeds in order of creation; an identity never changes and is never
+    reused.  ``born[i]`` is the frame of identity i, ``retired[i] = (frame, "outside" | "lost" | "crowded" | "cut")`` the last frame
+    returned for it and why, ``hops`` (``record_hops=True``) the hop list of each identity, ``cuts`` the cut frames so far.  Over its
+    life an identity is what ``track_stream`` given that query alone returns -- an identity of a scene behind a cut, what a
+    ``CoverTracker`` started on the cut frame gives it; frames of a retired query that were not returned before its retirement are
+    discarded.  The queries are the cover's: ``st.add_queries`` / ``st.remove_queries`` / ``st.cut`` raise ValueError."""
 
     def __init__(self, model, cover, queries=None, iters=6, slots=24, record_hops=False, engine="torch", rounds="torch"):
         if not isinstance(cover, Cover):
@@ -1846,8 +1883,9 @@ class CoverTracker:
         if queries is None:
             queries = torch.zeros(1, 0, 3)
         self.cover = cover
-        self.st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=record_hops, engine=engine, rounds=rounds)
-        self.book = _CoverBook(cover, self.st.tq_host, record_hops)
+        self.st = StreamTracker(model, queries, iters=iters, slots=slots, record_hops=record_hops, engine=engine, rounds=rounds,
+                                _cover=cover)
+        self.book = self.st.core.books[0]
 
     ids = property(lambda self: torch.tensor(self.book.ids, dtype=torch.int64))
     born, retired = (property(lambda self, k=k: getattr(self.book, k)) for k in ("born", "retired"))
@@ -1855,65 +1893,11 @@ class CoverTracker:
     emitted, finished = (property(lambda self, k=k: getattr(self.st, k)) for k in ("emitted", "finished"))
     cuts = property(lambda self: list(self.book.cuts))
 
-    @torch.no_grad()
     def push(self, frames):
-        st = self.st
-        if st.finished:
-            raise ValueError("push() after finish()")
-        _check_frames(frames)
-        if st.cache is None:
-            st.push(frames[:, :0])                 # no frame: the ring and the state are made, the device is known
-            self.book.start(frames.shape[3], frames.shape[4], st.cache.device, st.tq_host, st.xy_in, st.add_queries,
-                            st.remove_queries)
-        if tuple(frames.shape[3:]) != self.book.size:
-            raise ValueError(f"frames of {tuple(frames.shape[3:])} pushed to a stream of {self.book.size}")
-        at = [] if self.cover.cut_thr is None else self.book.look(frames[0])
-        if not at:
-            return self._piece(frames)
-        # cuts in this chunk: its pieces are pushed one by one, with the tracker's cut and the step without rows between two
-        parts, first, T0 = [], None, st.cache.T
-        for j, (a, b) in enumerate(zip([0] + at, at + [frames.shape[1]])):
-            if j > 0:
-                ids, self._born = self.ids, len(self.book.born)
-                f0, trajs, vis, keep = st.cut()
-                parts.append((f0, trajs, vis, ids))
-                self.book.cut(T0 + a, keep, st.cut_hops, st.add_queries)
-            elif b > a:
-                parts.append(self._piece(frames[:, a:b]))
-            first = self._born if first is None and parts else first
-            if j > 0:
-                parts.append(self._piece(frames[:, a:b]))
-        # the columns: the identities alive at the start of the push, then those created before the last piece's closing step
-        out = parts[0][3].tolist() + list(range(first, self._born))
-        col = {i: j for j, i in enumerate(out)}
-        f0, dev = parts[0][0], parts[0][1].device
-        m = sum(p[1].shape[1] for p in parts)
-        trajs = torch.full((1, m, len(out), 2), float("nan"), dtype=torch.float32, device=dev)
-        vis = torch.full((1, m, len(out)), float("nan"), dtype=torch.float32, device=dev)
-        for g0, t, v, ids in parts:
-            if t.shape[1] > 0 and ids.numel() > 0:
-                j = torch.tensor([col[i] for i in ids.tolist()], device=dev)
-                trajs[0, g0 - f0:g0 - f0 + t.shape[1]] = trajs[0, g0 - f0:g0 - f0 + t.shape[1]].index_copy(1, j, t[0])
-                vis[0, g0 - f0:g0 - f0 + t.shape[1]] = vis[0, g0 - f0:g0 - f0 + t.shape[1]].index_copy(1, j, v[0])
-        return f0, trajs, vis, torch.tensor(out, dtype=torch.int64)
+        return self.st.push(frames)
 
-    def _piece(self, frames):
-        """a run of frames without a cut in it: the corners' tables, the tracker's push, the cover step on the rows it returned"""
-        st = self.st
-        if self.book.corners:
-            self.book.see(frames[0], st.emitted, st.add_queries)
-        ids = self.ids
-        self._born = len(self.book.born)           # (the identities there are when ``ids`` is taken: none is made before the step)
-        f0, trajs, vis = st.push(frames)
-        if trajs.shape[1] > 0:
-            self.book.step(f0, trajs[0], vis[0], st.add_queries, st.remove_queries, st.hops)
-        return f0, trajs, vis, ids
-
-    @torch.no_grad()
     def finish(self):
-        self.book.held = None                      # (seeds held for a frame that never comes)
-        ids = self.ids
-        return self.st.finish() + (ids,)
+        return self.st.finish()
 
 
 @torch.no_grad()
@@ -1922,10 +1906,7 @@ def track_cover(model, chunks, cover, queries=None, iters=6, slots=24, return_ho
     outside each identity's life, born (K,) and retired (K,) frames (host int64; retired = -1 for those alive at the end).
     ``return_hops=True``: also the hop list of each identity."""
     ct = CoverTracker(model, cover, queries, iters=iters, slots=slots, record_hops=return_hops, engine=engine, rounds=rounds)
-    parts = [ct.push(c) for c in chunks]
-    parts.append(ct.finish())
-    out = _by_identity(parts, ct.book)
-    return out + (ct.hops,) if return_hops else out
+    return _joined([ct.push(c) for c in chunks] + [ct.finish()], ct.book, ct.hops, return_hops)
 
 
 def corner_queries(rgbs, t=0, cell=32, min_corner=0, scan="torch"):
@@ -1957,13 +1938,12 @@ class MultiStreamTracker(_StreamCore):
     ``joint_encode=True`` sends the frames one wave appends across all streams through shared encoder passes
     (``Pips.encode_streams(joint=True)``): fuller passes, and maps that differ from the per-stream ones by the encoder's
     tile-order noise instead of matching bit for bit.
-    ``cover`` (a ``Cover``; None: the tracker described so far): every stream is covered as its own ``CoverTracker`` would be -- its
-    first cover step runs inside the first ``push``, and a step runs on the part of a stream that a ``push`` returned and acts
-    through ``remove_queries(v, .)`` / ``add_queries(v, .)``, which are then the cover's alone (ValueError for a caller).  ``push`` and
-    ``finish`` return ``(f0, trajs, vis, ids)`` per stream, ``ids`` being the identity of each column as ``CoverTracker`` numbers
-    them; ``books[v]`` holds ``born`` / ``retired`` of stream v and ``cover_hops(v)`` its hop lists by identity.  Under
+    ``cover`` (a ``Cover`` without ``cut_thr``; None: the tracker described so far): every stream is covered by the core's rules, the
+    ones its own ``CoverTracker`` follows, so ``add_queries`` / ``remove_queries`` are the cover's alone (ValueError for a caller).
+    ``push`` and ``finish`` return ``(f0, trajs, vis, ids)`` per stream, ``ids`` being the identity of each column as ``CoverTracker``
+    numbers them; ``books[v]`` holds ``born`` / ``retired`` of stream v and ``cover_hops(v)`` its hop lists by identity.  Under
     ``Cover(seed="corners")`` a push makes one corner table per stream that got a chunk, and the first seeds of a stream whose first
-    chunk is ``None`` wait for its first frames, as in ``CoverTracker``."""
+    chunk is ``None`` wait for its first frames."""
 
     def __init__(self, model, queries_list, iters=6, slots=24, record_hops=False, rounds="torch", joint_encode=False, cover=None):
         if cover is not None and not isinstance(cover, Cover):
@@ -1995,13 +1975,5 @@ def track_streams(model, chunk_lists, queries_list, iters=6, slots=24, return_ho
         if any(w is not None for w in wave):
             for v, p in enumerate(mt.push(wave)):
                 parts[v].append(p)
-    out = []
-    for v in range(mt.V if cover is not None else 0):
-        res = _by_identity(parts[v], mt.books[v])
-        out.append(res + (mt.cover_hops(v),) if return_hops else res)
-    if cover is not None:
-        return out
-    for v in range(mt.V):
-        res = (torch.cat([p[1] for p in parts[v]], dim=1), torch.cat([p[2] for p in parts[v]], dim=1))
-        out.append(res + (mt.stream_hops(v),) if return_hops else res)
-    return out
+    hops = (mt.stream_hops if cover is None else mt.cover_hops) if return_hops else (lambda v: None)
+    return [_joined(parts[v], None if cover is None else mt.books[v], hops(v), return_hops) for v in range(mt.V)]
