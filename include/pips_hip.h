@@ -113,7 +113,9 @@ const char* pips_last_error(void);
  * where a video has its scene cuts); pips_frames_import (a decoder's NV12, I420 or packed RGB frames, pitched, to the planar frames
  * every entry point reads, resized in the same pass); pips_frames_import_ex (the same with a filter argument -- the antialiasing
  * triangle filter beside the two-tap bilinear -- and the 10-bit formats P010 and I010); pips_tracks_draw and
- * pips_draw_workspace_bytes (the trails of the tracks drawn onto the decoder's 8-bit surfaces, in place). */
+ * pips_draw_workspace_bytes (the trails of the tracks drawn onto the decoder's 8-bit surfaces, in place);
+ * pips_conv_nhwc_f32_r and pips_encoder_l1_fused (the LDS-resident 64 -> 64 convolution of the fp32 encoder's layer 1 and whether
+ * the encoder takes it); pips_inorm_apply_f32 (pips_inorm_apply on fp32 maps with mode 3 beside modes 0..2). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -952,9 +954,25 @@ int    pips_conv_nhwc_f32(const float* in, int F, int H, int W, int Cin,
 #define PIPS_CONV_ROUTE_AUTO   0
 #define PIPS_CONV_ROUTE_IGEMM  1
 #define PIPS_CONV_ROUTE_E      2
+#define PIPS_CONV_ROUTE_R      3      /* the LDS-resident 64 -> 64 kernel: through pips_conv_nhwc_f32_r only */
 int    pips_conv_nhwc_f32_route(const float* in, int F, int H, int W, int Cin,
                                 const float* wgt, const float* bias, int Cout, int ksize, int cstride, int pad,
                                 float* out, float* stats, int* tiles_m_host, int route, void* stream);
+/* The LDS-resident 3x3 convolution of the fp32 encoder's layer 1 (conv3x3_c64_f32_r_kernel; exposed for unit tests) at ANY map
+ * size, whatever pips_encoder_l1_fused says: weights of all nine taps and the input patch of a 4 x 32 pixel tile in LDS, exact fp32
+ * products in the K order of PIPS_CONV_ROUTE_IGEMM -- the output map is bitwise that route's.  in_norm (optional): {mean, rstd} per
+ * (frame, input channel) of the layer that produced `in`; fmaxf((x - mean) * rstd, 0) -- bitwise pips_inorm_apply's mode 0 -- is
+ * applied to the map while it is staged, taps outside the image stay zero.  stats (required) receives 4*ceil(H/4)*ceil(W/32) parts
+ * per frame (returned through *parts_host): one per image row of every tile, n = 0 for the rows below the image;
+ * stats_parts_cap = room in stats in parts per frame (0 = the 2*ceil(H*W/64)+4 of pips_conv_nhwc_f32).  PIPS_E_ARG: anything but
+ * ksize 3, cstride 1, pad 1, Cin = Cout = 64, a bias, stats, parts within the cap and a map of (H+2)*(W+2)*256 < 2^31 bytes. */
+int    pips_conv_nhwc_f32_r(const float* in, const float* in_norm, int F, int H, int W, int Cin,
+                            const float* wgt, const float* bias, int Cout, int ksize, int cstride, int pad,
+                            float* out, float* stats, int stats_parts_cap, int* parts_host, void* stream);
+/* 1 if pips_encoder_fwd (exact fp32) runs layer 1 of F frames of H x W pixels on that kernel -- its four convolutions normalise
+ * their input while staging it, so three normalised half-resolution maps are never stored -- 0 if it runs the staged sequence
+ * (fewer than a threshold of tiles per compute unit).  Host function; needs a current device. */
+int    pips_encoder_l1_fused(int F, int H, int W);
 
 /* The finalize of those partials (exposed for unit tests): partial (F, parts, C) float4 -> mean_rstd (F, C, 2) = {mean,
  * 1 / sqrt(var + 1e-5)}, combined in fp64; C % 16 == 0. */
@@ -977,6 +995,13 @@ int    pips_encoder_stem(const void* arena, const void* rgbs, int F, int H, int 
  * with bf16 maps), a mode >= 1 without res, a mode >= 2 without res_stats, a C off its alignment. */
 int    pips_inorm_apply(const void* x, const float* stats, const void* res, const float* res_stats, int mode, void* y,
                         int F, int HW, int C, int maps_bf16, void* stream);
+/* pips_inorm_apply on fp32 maps with every mode of the bf16 form: modes 0..2 as above (the same kernels), and mode 3,
+ * relu(relu(n2(res)) + relu(n(x))) -- a residual block's closing pass when the block's input exists only as the RAW map of the layer
+ * that produced it (the fused layer 1 of the fp32 encoder, pips_encoder_l1_fused): the same fp32 operations in the same order as mode 0
+ * on each operand followed by relu(a + b).  PIPS_E_ARG: a mode outside 0..3, a mode >= 1 without res, a mode >= 2 without res_stats,
+ * C % 4 != 0 or C > 2048. */
+int    pips_inorm_apply_f32(const float* x, const float* stats, const float* res, const float* res_stats, int mode, float* y,
+                            int F, int HW, int C, void* stream);
 /* F.interpolate(mode='bilinear', align_corners=True) (nets/pips.py:269-272) of an NHWC map [F][Hs][Ws][C] into channels
  * [coff, coff + C) of the NHWC map dst [F][Hd][Wd][Cdst] (the torch.cat of :273); the other channels of dst are not written.
  * fp32 maps (C, Cdst, coff multiples of 4) or bf16 maps (multiples of 8).  PIPS_E_ARG: coff < 0, coff + C > Cdst, alignment. */

@@ -149,10 +149,14 @@ SIGNATURES = {
                                    C.POINTER(c_int), c_void_p]),
     "pips_conv_nhwc_f32_route": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_int, c_int, fp, fp,
                                          C.POINTER(c_int), c_int, c_void_p]),
+    "pips_conv_nhwc_f32_r": (c_int, [fp, fp, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_int, c_int, fp, fp, c_int,
+                                     C.POINTER(c_int), c_void_p]),
+    "pips_encoder_l1_fused": (c_int, [c_int] * 3),
     "pips_inorm_finalize_pivot": (c_int, [fp, c_int, c_int, c_int, fp, c_void_p]),
     "pips_encoder_stem_parts": (c_int, [c_int, c_int]),
     "pips_encoder_stem": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, fp, C.POINTER(c_int), c_void_p]),
     "pips_inorm_apply": (c_int, [c_void_p, fp, c_void_p, fp, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "pips_inorm_apply_f32": (c_int, [fp, fp, fp, fp, c_int, fp, c_int, c_int, c_int, c_void_p]),
     "pips_resize_into": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "pips_avgpool2": (c_int, [fp, c_int, c_int, c_int, c_int, fp, c_void_p]),
     "pips_gemm_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, fp, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, fp, c_int,

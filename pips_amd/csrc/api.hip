@@ -346,7 +346,8 @@ int conv_nhwc(const ConvCall& c, hipStream_t st) {
     g.M = g.Ho * g.Wo; g.N = c.Cout; g.K = c.k * c.k * c.Cin; g.ldc = c.Cout; g.epi = EPI_BIAS;
     PIPS_CHECK_ARG(g.Ho > 0 && g.Wo > 0, "conv: empty output");
     if (c.mode == SPLIT) return launch_conv_x3(g, c.F, c.tiles, st);
-    PIPS_CHECK_ARG(c.mode == BF16 || (!c.in_bf16 && !c.out_bf16 && !c.in_norm), "conv: bf16 maps need the bf16-operand kernels");
+    PIPS_CHECK_ARG(c.mode == BF16 || (!c.in_bf16 && !c.out_bf16), "conv: bf16 maps need the bf16-operand kernels");
+    PIPS_CHECK_ARG(c.mode == BF16 || !c.in_norm || c.route == PIPS_CONV_ROUTE_R, "conv: an fp32 map is normalised while staged by the LDS-resident 64 -> 64 kernel only");
     return c.mode == BF16 ? launch_conv_bf16(g, c.F, c.tiles, st, c.in_bf16, c.out_bf16) : launch_conv(g, c.F, c.tiles, st);
 }
 
@@ -480,14 +481,16 @@ ConvCall enc_conv(const Enc& e, int ci, const void* in, int H, int W, void* out,
     return cc;
 }
 
-// conv (BF16: optional normalise-on-load of the input map by in_norm) -> raw map + partial stats -> {mean, rstd}
+// conv (optional normalise-on-load of the input map by in_norm: BF16, or EXACT on `route` PIPS_CONV_ROUTE_R) -> raw map + partial
+// stats -> {mean, rstd}
 int conv_stats(const Enc& e, int ci, const void* in, const float* in_norm, int H, int W, void* out, float* partial,
-               float* mean_rstd) {
+               float* mean_rstd, int route = PIPS_CONV_ROUTE_AUTO) {
     const ConvW& c = e.A.conv[ci];
     int tiles = 0;
     ConvCall cc = enc_conv(e, ci, in, H, W, out, e.mode == BF16);
-    cc.stats = partial; cc.tiles = &tiles; cc.in_norm = in_norm;
-    if (e.mode == BF16) cc.parts_cap = enc_parts_cap(conv_out(H, c.k, c.stride, c.pad), conv_out(W, c.k, c.stride, c.pad));
+    cc.stats = partial; cc.tiles = &tiles; cc.in_norm = in_norm; cc.route = route;
+    if (e.mode == BF16 || route == PIPS_CONV_ROUTE_R)
+        cc.parts_cap = enc_parts_cap(conv_out(H, c.k, c.stride, c.pad), conv_out(W, c.k, c.stride, c.pad));
     RUN(conv_nhwc(cc, e.st));
     return launch_inorm_finalize_pivot(partial, e.F, tiles, c.cout, mean_rstd, e.st);
 }
@@ -518,6 +521,18 @@ int res_block(const Enc& e, int& ci, bool down, const void* x, int H, int W, voi
     return inorm_apply(e, raw, ws + P.st_a, x, nullptr, out, Ho * Wo, c2.cout);
 }
 
+// Does the exact-fp32 encoder run layer 1 of F maps of H0 x W0 pixels on the LDS-resident kernel (conv_f32_r.hip)?  The geometry
+// of the layer's four convolutions, with the room plan_encoder() gives their partials.
+bool enc_l1_fused(int F, int H0, int W0) {
+    static const float dummy = 0.f;
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.bias = &dummy; g.stats = const_cast<float*>(&dummy);      // only their null-ness is inspected
+    g.H = g.Ho = H0; g.Win = g.Wo = W0; g.Cin = g.N = g.ldc = 64; g.KH = g.KW = 3; g.cstride = 1; g.pad = 1;
+    g.M = H0 * W0; g.K = 9 * 64; g.stats_parts_cap = enc_parts_cap(H0, W0);
+    return conv_f32_r_takes(g, F);
+}
+
 // stem + layer1 with fp32 maps (nets/pips.py:251-253, 265) -> ws + P.outs[0]
 int enc_front_f32(const Enc& e, const void* rgbs, int rgb_u8, int H, int W, int& ci) {
     float* ws = e.ws; const EncPlan& P = e.P;
@@ -526,6 +541,20 @@ int enc_front_f32(const Enc& e, const void* rgbs, int rgb_u8, int H, int W, int&
     RUN(launch_stem(rgbs, rgb_u8, e.arena + e.A.conv[0].w, e.arena + e.A.conv[0].b, ws + P.raw, ws + P.partial, e.F, H, W, H0, W0,
                     &tiles, e.st));
     RUN(launch_inorm_finalize_pivot(ws + P.partial, e.F, tiles, 64, ws + P.st_a, e.st));
+    if (e.mode == EXACT && enc_l1_fused(e.F, H0, W0)) {
+        // layer 1 on the LDS-resident 64 -> 64 kernel, the sequence of enc_front_bf16: a convolution normalises its input while
+        // staging it, so relu(norm(.)) of the stem and of each block's first convolution never goes to memory
+        const int R = PIPS_CONV_ROUTE_R;
+        float* raw = ws + P.raw; float* mid = ws + P.mid; float* xa = ws + P.xa; float* xb = ws + P.xb;
+        float* st_a = ws + P.st_a; float* st_b = ws + P.st_b;
+        RUN(conv_stats(e, ci++, raw, st_a, H0, W0, mid, ws + P.partial, st_b, R));       // block 1 conv1 on the raw stem map
+        RUN(conv_stats(e, ci++, mid, st_b, H0, W0, xa, ws + P.partial, st_b, R));        // block 1 conv2
+        // relu(x + y), x = relu(norm1(stem)) recomputed from the raw stem map, y = relu(norm2(conv2)) (:176-181)
+        RUN(launch_inorm_apply(xa, st_b, raw, st_a, xb, e.F, H0 * W0, 64, e.st, true));
+        RUN(conv_stats(e, ci++, xb, nullptr, H0, W0, raw, ws + P.partial, st_a, R));     // block 2 conv1
+        RUN(conv_stats(e, ci++, raw, st_a, H0, W0, mid, ws + P.partial, st_b, R));       // block 2 conv2
+        return launch_inorm_apply(mid, st_b, xb, nullptr, ws + P.outs[0], e.F, H0 * W0, 64, e.st);
+    }
     RUN(launch_inorm_apply(ws + P.raw, ws + P.st_a, nullptr, nullptr, ws + P.xa, e.F, H0 * W0, 64, e.st));
     RUN(res_block(e, ci, false, ws + P.xa, H0, W0, ws + P.xb));
     return res_block(e, ci, false, ws + P.xb, H0, W0, ws + P.outs[0]);
@@ -1264,6 +1293,22 @@ int pips_conv_nhwc_f32_route(const float* in, int F, int H, int W, int Cin, cons
     c.route = route;
     return conv_nhwc(c, (hipStream_t)stream);
 }
+int pips_conv_nhwc_f32_r(const float* in, const float* in_norm, int F, int H, int W, int Cin, const float* wgt, const float* bias,
+                         int Cout, int ksize, int cstride, int pad, float* out, float* stats, int stats_parts_cap, int* parts_host,
+                         void* stream) {
+    PIPS_CHECK_ARG(in && wgt && out, "conv_f32_r: null pointer");
+    PIPS_CHECK_ARG(F > 0 && H > 0 && W > 0 && stats_parts_cap >= 0, "conv_f32_r: bad geometry F=%d H=%d W=%d cap=%d", F, H, W, stats_parts_cap);
+    PIPS_CHECK_ARG(Cin == 64, "conv_f32_r: Cin=%d, the kernel takes 64 -> 64 layers", Cin);      // ahead of launch_conv's own checks
+    ConvCall c = conv_call(in, F, H, W, Cin, wgt, bias, Cout, ksize, cstride, pad, out, stats, parts_host);
+    c.route = PIPS_CONV_ROUTE_R;
+    c.in_norm = in_norm;
+    c.parts_cap = stats_parts_cap;
+    return conv_nhwc(c, (hipStream_t)stream);
+}
+int pips_encoder_l1_fused(int F, int H, int W) {
+    if (F <= 0 || H <= 0 || W <= 0) return 0;
+    return enc_l1_fused(F, conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3)) ? 1 : 0;
+}
 int pips_inorm_finalize_pivot(const float* partial, int F, int parts, int C, float* mean_rstd, void* stream) {
     PIPS_CHECK_ARG(partial && mean_rstd && F > 0 && parts > 0 && C > 0 && C % 16 == 0, "inorm_finalize_pivot: bad arguments");
     return launch_inorm_finalize_pivot(partial, F, parts, C, mean_rstd, (hipStream_t)stream);
@@ -1297,6 +1342,18 @@ int pips_inorm_apply(const void* x, const float* stats, const void* res, const f
     // the fp32 launcher reads the mode from the pointers: hand it only those of the mode asked for
     return launch_inorm_apply((const float*)x, stats, mode >= 1 ? (const float*)res : nullptr, mode == 2 ? res_stats : nullptr,
                               (float*)y, F, HW, C, (hipStream_t)stream);
+}
+int pips_inorm_apply_f32(const float* x, const float* stats, const float* res, const float* res_stats, int mode, float* y, int F,
+                         int HW, int C, void* stream) {
+    PIPS_CHECK_ARG(x && stats && y, "inorm_apply_f32: null pointer");
+    PIPS_CHECK_ARG(F > 0 && HW > 0 && C > 0, "inorm_apply_f32: bad geometry F=%d HW=%d C=%d", F, HW, C);
+    PIPS_CHECK_ARG(mode >= 0 && mode <= 3, "inorm_apply_f32: mode %d", mode);
+    PIPS_CHECK_ARG(mode == 0 || res != nullptr, "inorm_apply_f32: mode %d needs a shortcut map", mode);
+    PIPS_CHECK_ARG(mode < 2 || res_stats != nullptr, "inorm_apply_f32: mode %d needs the shortcut's statistics", mode);
+    PIPS_CHECK_ARG(C % 4 == 0 && C <= 2048, "inorm_apply_f32: C=%d must be a multiple of 4, at most 2048", C);
+    // the launcher reads the mode from the pointers: hand it only those of the mode asked for
+    return launch_inorm_apply(x, stats, mode >= 1 ? res : nullptr, mode >= 2 ? res_stats : nullptr, y, F, HW, C, (hipStream_t)stream,
+                              mode == 3);
 }
 int pips_resize_into(const void* src, int F, int Hs, int Ws, int C, void* dst, int Hd, int Wd, int Cdst, int coff, int maps_bf16,
                      void* stream) {

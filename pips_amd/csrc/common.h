@@ -251,11 +251,11 @@ struct GemmArgs {
     int swz;             // XCD-aware tile order (set by the launcher)
     // implicit-GEMM geometry (conv only); M = Ho*Wo rows per frame, gridDim.z = frames
     int H, Win, Cin, Ho, Wo, KH, KW, cstride, pad;
-    // bf16-activation convolutions: {mean, rstd} [frame][Cin] of the PRODUCING layer -- relu((x - mean) * rstd) is applied
-    // to the bf16 input map while it is staged (conv_bf16_c64.hip only); null = the map is read as it is
+    // {mean, rstd} [frame][Cin] of the PRODUCING layer -- relu((x - mean) * rstd) is applied to the input map while it is
+    // staged (bf16 maps: conv_bf16_c64.hip; fp32 maps: conv_f32_r.hip, no other kernel); null = the map is read as it is
     const float* in_norm;
     int stats_parts_cap;     // room in stats in partials per frame; 0 = the documented 2*ceil(Ho*Wo/64)+4
-    int conv_route;          // fp32 convolutions: 0 = the kernel launch_conv picks for the shape, PIPS_CONV_ROUTE_IGEMM / _E = that kernel
+    int conv_route;          // fp32 convolutions: 0 = the kernel launch_conv picks for the shape, PIPS_CONV_ROUTE_IGEMM / _E / _R = that kernel
 #ifdef PIPS_GEMM_TRACE
     unsigned long long* trace;   // tools/gemm_trace.py: per-block phase timestamps
 #endif
@@ -334,6 +334,11 @@ int launch_conv_f32_t4(const GemmArgs& a, int cfg, int frames, int* parts_out, h
 // 1x1 / 3x3, stride 1 / 2 convolutions on 64 x 64 tiles staged by LDS-DMA (conv_f32_e.hip): can the body run the layer, and its launcher
 bool conv_f32_e_admits(const GemmArgs& a);
 int launch_conv_f32_e(const GemmArgs& a, int frames, int* parts_out, hipStream_t st);
+// the 64 -> 64 3x3 / stride 1 layers with weights and input patch resident in LDS, optional normalise-on-stage by GemmArgs::in_norm
+// (conv_f32_r.hip): can the kernel run the layer, does launch_conv send it there (tiles per compute unit), and its launcher
+bool conv_f32_r_admits(const GemmArgs& a);
+bool conv_f32_r_takes(const GemmArgs& a, int frames);
+int launch_conv_f32_r(const GemmArgs& a, int frames, int* parts_out, hipStream_t st);
 // bf16-operand GEMM (gemm_bf16.hip): A fp32 or bf16, W bf16, C fp32 or bf16; pointers passed as float*
 int launch_gemm_bf16(const GemmArgs& a, int a_bf16, int out_bf16, hipStream_t st);
 // in_bf16 / out_bf16: the NHWC maps are bf16 instead of fp32 (the bf16 encoder keeps every activation in bf16)
@@ -392,7 +397,7 @@ int launch_inorm_finalize_pivot(const float* partial, int F, int parts, int C, f
 // y = relu(res + relu((x-m)*r))                   (res != null, res_stats == null)
 // y = relu((res-m2)*r2 + relu((x-m)*r))           (res_stats != null)
 int launch_inorm_apply(const float* x, const float* stats, const float* res, const float* res_stats,
-                       float* y, int F, int HW, int C, hipStream_t st);
+                       float* y, int F, int HW, int C, hipStream_t st, bool res_relu = false);
 int launch_resize_into(const float* src, int F, int Hs, int Ws, int C, float* dst, int Hd, int Wd,
                        int Cdst, int coff, hipStream_t st);
 int launch_avgpool2(const float* src, int F, int H, int W, int C, float* dst, hipStream_t st);

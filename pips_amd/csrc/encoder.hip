@@ -298,6 +298,8 @@ int launch_inorm_finalize_pivot(const float* partial, int F, int parts, int C, f
 // MODE 0: y = relu((x-m)*r)                              nets/pips.py:175/176/252-253/274-275
 // MODE 1: y = relu(res + relu((x-m)*r))                  :176,181 (identity shortcut)
 // MODE 2: y = relu((res-m2)*r2 + relu((x-m)*r))          :169-170,179,181 (1x1 s2 shortcut + norm3)
+// MODE 3: y = relu(relu((res-m2)*r2) + relu((x-m)*r))    :176,181 with the block's input given as the RAW map of the layer that
+//         produced it (the fused layer 1 never stores relu(norm1(stem)): enc_front_f32); inorm_apply_bf16_kernel's mode 3
 template <int MODE>
 __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restrict__ x,
                                                           const float2* __restrict__ stats,
@@ -325,13 +327,20 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const float4* __restri
             const float rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = fmaxf((rr[k] - rs[k].x) * rs[k].y + o[k], 0.f);
+        } else if (MODE == 3) {
+            const float4 r = res[i];
+            const float2* rs = res_stats + ((size_t)f * C4 + c4) * 4;
+            const float rr[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = fmaxf(fmaxf((rr[k] - rs[k].x) * rs[k].y, 0.f) + o[k], 0.f);
         }
         y[i] = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
+// the mode follows from the pointers: res == null: 0; res_stats == null: 1; else 2, or 3 with res_relu
 int launch_inorm_apply(const float* x, const float* stats, const float* res, const float* res_stats,
-                       float* y, int F, int HW, int C, hipStream_t st) {
+                       float* y, int F, int HW, int C, hipStream_t st, bool res_relu) {
     PIPS_CHECK_ARG(C % 4 == 0, "inorm_apply: C %% 4");
     const size_t total4 = (size_t)F * HW * (C / 4);
     const int blocks = (int)((total4 + 255) / 256 < 4096 ? (total4 + 255) / 256 : 4096);
@@ -344,8 +353,10 @@ int launch_inorm_apply(const float* x, const float* stats, const float* res, con
         hipLaunchKernelGGL(inorm_apply_kernel<0>, dim3(blocks), dim3(256), 0, st, x4, s2, r4, rs2, y4, HW, C / 4, total4);
     else if (res_stats == nullptr)
         hipLaunchKernelGGL(inorm_apply_kernel<1>, dim3(blocks), dim3(256), 0, st, x4, s2, r4, rs2, y4, HW, C / 4, total4);
-    else
+    else if (!res_relu)
         hipLaunchKernelGGL(inorm_apply_kernel<2>, dim3(blocks), dim3(256), 0, st, x4, s2, r4, rs2, y4, HW, C / 4, total4);
+    else
+        hipLaunchKernelGGL(inorm_apply_kernel<3>, dim3(blocks), dim3(256), 0, st, x4, s2, r4, rs2, y4, HW, C / 4, total4);
     PIPS_CHECK_LAUNCH("inorm_apply_kernel");
     return PIPS_OK;
 }

@@ -498,6 +498,14 @@ int launch_conv(const GemmArgs& a, int frames, int* tiles_m, hipStream_t st) {
                        a.cstride, a.pad, a.Cin);
         return launch_conv_f32_e(a, frames, tiles_m, st);
     }
+    if (a.conv_route == PIPS_CONV_ROUTE_R) {
+        PIPS_CHECK_ARG(conv_f32_r_admits(a), "conv: the LDS-resident 64 -> 64 kernel does not take this layer (k=%d stride=%d pad=%d Cin=%d "
+                       "Cout=%d, bias, statistics and room for 4*ceil(H/4)*ceil(W/32) parts per frame)", a.KH, a.cstride, a.pad, a.Cin, a.N);
+        return launch_conv_f32_r(a, frames, tiles_m, st);
+    }
+    // (never picked by shape here: its partition of the statistics needs more room than the documented bound, so the encoder,
+    // which owns the buffers, names it where conv_f32_r_takes() -- enc_front_f32)
+    PIPS_CHECK_ARG(a.in_norm == nullptr, "conv: only the LDS-resident 64 -> 64 kernel normalises an fp32 map while staging it");
     if (a.conv_route != PIPS_CONV_ROUTE_IGEMM) {
         // the four-wave assembly kernels: conv_f32_t4.hip (the big 3x3 layers), conv_f32_e.hip (64 x 64 tiles on shape E's pipeline)
         const int cfg = conv_f32_t4_config(a, frames);

@@ -986,8 +986,8 @@ def encoder_stem(arena, rgbs, bf16=False):
 
 
 def inorm_apply(x, stats, res=None, res_stats=None, mode=0):
-    """pips_inorm_apply on NHWC maps x (F,...,C), fp32 or bfloat16, with stats (F,C,2) = {mean, rstd}: mode 0 relu(n(x)), 1
-    relu(res + relu(n(x))), 2 relu(n2(res) + relu(n(x))), 3 (bfloat16 maps) relu(relu(n2(res)) + relu(n(x)))."""
+    """pips_inorm_apply (fp32 maps in mode 3: pips_inorm_apply_f32) on NHWC maps x (F,...,C), fp32 or bfloat16, with stats (F,C,2) = {mean, rstd}: mode 0 relu(n(x)), 1
+    relu(res + relu(n(x))), 2 relu(n2(res) + relu(n(x))), 3 relu(relu(n2(res)) + relu(n(x)))."""
     x, stats = _map(x), _f32(stats)
     res = None if res is None else _map(res)
     res_stats = None if res_stats is None else _f32(res_stats)
@@ -995,8 +995,12 @@ def inorm_apply(x, stats, res=None, res_stats=None, mode=0):
     F, Cc = x.shape[0], x.shape[-1]
     y = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _call("pips_inorm_apply", _lib.ptr(x), _lib.ptr(stats), _lib.ptr(res), _lib.ptr(res_stats), int(mode), _lib.ptr(y), F,
-              x.numel() // (F * Cc), Cc, int(x.dtype == torch.bfloat16), _stream())
+        if int(mode) == 3 and x.dtype == torch.float32:       # fp32 maps: mode 3 lives on the fp32 entry point
+            _call("pips_inorm_apply_f32", _lib.ptr(x), _lib.ptr(stats), _lib.ptr(res), _lib.ptr(res_stats), 3, _lib.ptr(y), F,
+                  x.numel() // (F * Cc), Cc, _stream())
+        else:
+            _call("pips_inorm_apply", _lib.ptr(x), _lib.ptr(stats), _lib.ptr(res), _lib.ptr(res_stats), int(mode), _lib.ptr(y), F,
+                  x.numel() // (F * Cc), Cc, int(x.dtype == torch.bfloat16), _stream())
     return y
 
 
@@ -1063,6 +1067,33 @@ def conv_nhwc(x, w_packed, bias, ksize, stride, pad, want_stats=False, route=Non
         return _conv("pips_conv_nhwc_f32", _f32(x), _f32(w_packed), bias, ksize, stride, pad, want_stats, out=out)
     return _conv("pips_conv_nhwc_f32_route", _f32(x), _f32(w_packed), bias, ksize, stride, pad, want_stats,
                  route={"igemm": 1, "e": 2}[route], out=out)
+
+
+def conv_nhwc_f32_r(x, w_packed, bias, in_norm=None, ksize=3, stride=1, pad=1, out=None, stats=None):
+    """pips_conv_nhwc_f32_r: the LDS-resident 64 -> 64 3x3 convolution of the fp32 encoder's layer 1 at any map size.  x (F,H,W,64)
+    fp32, ``in_norm`` (F,64,2) = {mean, rstd} of the producing layer (relu((x - mean) * rstd) while the map is staged) -> the raw
+    map (F,H,W,64) and its partials (F, parts, 64, 4), parts = 4 * ceil(H/4) * ceil(W/32).  out / stats: contiguous fp32 tensors to
+    write into (views of larger buffers in the containment tests); stats holds (F, cap, 64, 4), its cap is handed to the library."""
+    x, w = _f32(x), _f32(w_packed)
+    F, H, W, Cin = x.shape
+    Cout = w.shape[-4]
+    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    if out is None:
+        out = torch.empty(F, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+    if stats is None:
+        stats = torch.zeros(F, 4 * ((Ho + 3) // 4) * ((Wo + 31) // 32), Cout, 4, dtype=torch.float32, device=x.device)
+    assert out.shape == (F, Ho, Wo, Cout) and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
+    assert stats.dim() == 4 and stats.shape[0] == F and stats.shape[2:] == (Cout, 4) and stats.is_contiguous()
+    parts = C.c_int(0)
+    with torch.cuda.device(x.device):
+        _call("pips_conv_nhwc_f32_r", _lib.ptr(x), _lib.ptr(None if in_norm is None else _f32(in_norm)), F, H, W, Cin, _lib.ptr(w),
+              _lib.ptr(bias), Cout, ksize, stride, pad, _lib.ptr(out), _lib.ptr(stats), stats.shape[1], C.byref(parts), _stream())
+    return out, stats.view(-1)[: F * parts.value * Cout * 4].view(F, parts.value, Cout, 4)
+
+
+def encoder_l1_fused(F, H, W):
+    """pips_encoder_l1_fused: does the exact-fp32 encoder run layer 1 of F frames of H x W pixels on that kernel (current device)?"""
+    return bool(_lib.load().pips_encoder_l1_fused(int(F), int(H), int(W)))
 
 
 def conv_nhwc_bf16(x, w_bf16, bias, ksize, stride, pad, want_stats=False):
