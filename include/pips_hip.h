@@ -115,7 +115,9 @@ const char* pips_last_error(void);
  * triangle filter beside the two-tap bilinear -- and the 10-bit formats P010 and I010); pips_tracks_draw and
  * pips_draw_workspace_bytes (the trails of the tracks drawn onto the decoder's 8-bit surfaces, in place);
  * pips_conv_nhwc_f32_r and pips_encoder_l1_fused (the LDS-resident 64 -> 64 convolution of the fp32 encoder's layer 1 and whether
- * the encoder takes it); pips_inorm_apply_f32 (pips_inorm_apply on fp32 maps with mode 3 beside modes 0..2). */
+ * the encoder takes it); pips_inorm_apply_f32 (pips_inorm_apply on fp32 maps with mode 3 beside modes 0..2);
+ * pips_tracks_draw_ex (pips_tracks_draw with the 10-bit surfaces P010 and I010 and a fade table: trails whose opacity falls with
+ * age; pips_draw_workspace_bytes sizes both at the same figure). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -784,9 +786,53 @@ int    pips_frames_import_ex(int format, int matrix, int range, int filter, int 
  * and n > 0: a NULL plane that the format has, a NULL trajs, colors or workspace, a workspace off a 16-byte address, workspace_bytes <
  * pips_draw_workspace_bytes(F, n, trail) (= 4 F n (2 trail + 10) bytes; 0 for F < 0, n < 0 or a trail outside its range).  F = 0 or
  * n = 0 launches nothing and returns PIPS_OK.
- * Known limits: the 10-bit surfaces (P010, I010) are not drawn on; chroma is treated as import treats it (one sample for its 2 x 2
- * pixels, siting not modelled); no text, no colour map along time, no antialiasing beyond the four subsamples; trajs, vis, colors
- * and the workspace may not overlap a plane. */
+ * Known limits: the 10-bit surfaces (P010, I010) are drawn on by pips_tracks_draw_ex only, and so are trails that fade with age;
+ * chroma is treated as import treats it (one sample for its 2 x 2 pixels, siting not modelled); no text, one colour per track
+ * (none that changes along the trail), no antialiasing beyond the four subsamples; trajs, vis, colors and the workspace may not
+ * overlap a plane.
+ *
+ * pips_tracks_draw_ex is pips_tracks_draw with two additions; everything not named here -- positions, the quantisation to eighths,
+ * the primitives, the integer inside test, opacity by visibility, column order, what is never written -- is pips_tracks_draw's
+ * rule word for word (pips_tracks_draw itself is not changed and keeps rejecting formats 6 and 7):
+ *  1. PIPS_FMT_P010 and PIPS_FMT_I010 beside the seven formats above.  Geometry and addressing are pips_frames_import_ex's:
+ *     samples are 16-bit little-endian words, pitches and steps are in bytes, a row of Y is 2 w bytes, a row of P010's chroma
+ *     2 x 2 ceil(w / 2) and of I010's 2 ceil(w / 2); every plane pointer, pitch and step must be even.  The 10-bit value v is
+ *     word >> 6 for P010 and word & 1023 for I010.  A sample that gets a non-zero weight from at least one track is rewritten as
+ *     v' << 6 (P010) or v' (I010): its other six bits become zero.  EVERY OTHER WORD KEEPS ALL 16 BITS -- a sample no track covers
+ *     (the junk a decoder left in its unused bits included), pitch padding, the gap between frames: they are not written.  The
+ *     blend is the one above on 0..1023: a full-resolution sample to (p (1024 - wgt) + c wgt + 512) >> 10, a 4:2:0 chroma sample to
+ *     (p (4096 - W) + c W + 2048) >> 12; no accumulator passes 2^22.  Colours stay (n,3) uint8 R, G, B and are converted once per
+ *     track, with h = 1 << (sh - 1):
+ *       Y = y0 + ((yr R + yg G + yb B + h) >> sh), Cb = clamp(512 + ((ur R + ug G + ub B + h) >> sh)),
+ *       Cr = clamp(512 + ((vr R + vg G + vb B + h) >> sh)), >> the arithmetic shift, clamp to [0, 1023]:
+ *                                         y0  sh  yr     yg      yb     ur      ug       ub      vr      vg       vb
+ *       10-bit PIPS_MATRIX_BT601 limited  64  14  16829  33039   6416   -9714   -19070   28784   28784   -24103   -4681
+ *       10-bit PIPS_MATRIX_BT601 full     0   16  78612  154331  29972  -44363  -87095   131458  131458  -110079  -21379
+ *       10-bit PIPS_MATRIX_BT709 limited  64  14  11966  40254   4064   -6596   -22188   28784   28784   -26145   -2639
+ *       10-bit PIPS_MATRIX_BT709 full     0   16  55896  188037  18982  -30123  -101335  131458  131458  -119404  -12054
+ *     The limited rows are the 8-bit constants with two more result bits: white 940, chroma within 64..960.  The full rows are the
+ *     standard coefficients scaled by 65536 x 1023 / 255, rounded so that each luma row sums to 262915 and each chroma row to 0:
+ *     black 0, white 1023, pure blue and red reach 1024 ahead of the clamp.  A grey gives exactly (Y, 512, 512); every component
+ *     is at most one level from floor(exact + 0.5) of the real-valued formula; every accumulator stays inside int32 (< 2^27);
+ *  2. fade: a HOST pointer to `trail` ints in 0..256, or NULL.  The library reads it before the launch and passes it by value; the
+ *     kernels read no host memory and the array may be freed on return.  fade[a] scales the opacity of the capsule of age a: the
+ *     segment that ends on the head (g = r) has age 0, the oldest age trail - 1; the head's disc always has factor 256.  Per
+ *     subsample phi = the LARGEST factor among the track's primitives that contain it, 0 when none does (no order among the
+ *     primitives; with a table that does not grow with age the youngest wins; a joint is still not drawn twice).  Per pixel
+ *     Wp = the sum of phi over its four subsamples (0..1024) and wgt = (Wp A + 128) >> 8; for a 4:2:0 chroma sample K = the sum
+ *     of Wp over its pixels inside the image (0..4096) and W = (K A + 128) >> 8.  A weight of 0 leaves the sample unwritten.  A
+ *     capsule with factor 0 draws nothing.  trail = 0 reads no entry.  With fade == NULL, or with every entry 256, Wp = 256 k, so
+ *     wgt = k A and W = K A exactly: THE RULE COLLAPSES TO pips_tracks_draw's, byte for byte, on the seven 8-bit formats.
+ * The launches are pips_tracks_draw's: the record of a 10-bit surface holds its colour as three 10-bit fields of the same word, so
+ * pips_draw_workspace_bytes serves both entries at the same size; a 2 x 2 quad is still four neighbouring lanes with 16-bit loads
+ * and stores; with a table the raster blocks stage it once in LDS and keep four factors per pixel in place of the coverage mask,
+ * walking the segments youngest first so that four factors of 256 end the walk.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "tracks_draw_ex:": everything pips_tracks_draw
+ * rejects, except that formats 6 and 7 are legal here (an unknown matrix or range is rejected with any of the four YCbCr
+ * formats); a fade entry outside 0..256; an odd plane pointer, pitch or step of a 16-bit format.  The pitch and step minimums
+ * are counted in bytes of the 16-bit rows.
+ * Known limits: as pips_tracks_draw's, but for the two it lifts; one colour per track (none that changes along the trail), no
+ * text; BT.2020 and transfer functions are not handled, 12- and 16-bit surfaces are not taken. */
 #define PIPS_FMT_PLANAR8 8
 #define PIPS_DRAW_DIM_MAX     8192
 #define PIPS_DRAW_TRAIL_MAX   32
@@ -800,6 +846,13 @@ int    pips_tracks_draw(int format, int matrix, int range, int F, int h, int w,
                         const float* trajs, const float* vis, int G, int n, int first, int src_h, int src_w,
                         const uint8_t* colors, int trail, int line8, int dot8, int alpha_vis, int alpha_occ, float vis_logit,
                         void* workspace, size_t workspace_bytes, void* stream);
+int    pips_tracks_draw_ex(int format, int matrix, int range, int F, int h, int w,
+                           void* p0, size_t pitch0, size_t step0,
+                           void* p1, size_t pitch1, size_t step1,
+                           void* p2, size_t pitch2, size_t step2,
+                           const float* trajs, const float* vis, int G, int n, int first, int src_h, int src_w,
+                           const uint8_t* colors, int trail, int line8, int dot8, int alpha_vis, int alpha_occ, float vis_logit,
+                           const int* fade, void* workspace, size_t workspace_bytes, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128).  PIPS_E_ARG ahead of the launch for a

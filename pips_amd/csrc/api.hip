@@ -2017,51 +2017,80 @@ size_t pips_draw_workspace_bytes(int F, int n, int trail) {
     if (F < 0 || n < 0 || trail < 0 || trail > PIPS_DRAW_TRAIL_MAX) return 0;
     return (size_t)F * (size_t)n * draw_track_ints(trail) * sizeof(int);
 }
+// pips_tracks_draw (ex = false, fade = NULL) and pips_tracks_draw_ex: one list of checks, `who` in front of every message
+static int tracks_draw_any(const char* who, bool ex, int format, int matrix, int range, int F, int h, int w, void* p0, size_t pitch0,
+                           size_t step0, void* p1, size_t pitch1, size_t step1, void* p2, size_t pitch2, size_t step2,
+                           const float* trajs, const float* vis, int G, int n, int first, int src_h, int src_w, const uint8_t* colors,
+                           int trail, int line8, int dot8, int alpha_vis, int alpha_occ, float vis_logit, const int* fade,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    const bool wide = format == PIPS_FMT_P010 || format == PIPS_FMT_I010;                   // 16-bit samples
+    if (ex)
+        PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I010) || format == PIPS_FMT_PLANAR8, "%s: unknown format %d", who,
+                       format);
+    else
+        PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I420) || format == PIPS_FMT_PLANAR8,
+                       "%s: format %d is not an 8-bit surface (pips_tracks_draw_ex draws on the 10-bit formats)", who, format);
+    const bool semi = format == PIPS_FMT_NV12 || format == PIPS_FMT_P010;
+    const bool yuv = semi || format == PIPS_FMT_I420 || format == PIPS_FMT_I010;
+    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
+                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
+                   "%s: unknown matrix %d or range %d", who, matrix, range);
+    PIPS_CHECK_ARG(F >= 0 && n >= 0, "%s: need F >= 0 and n >= 0 (F=%d, n=%d)", who, F, n);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1 && src_h >= 1 && src_w >= 1, "%s: need sizes of at least 1x1 (h=%d, w=%d, src_h=%d, src_w=%d)", who,
+                   h, w, src_h, src_w);
+    PIPS_CHECK_ARG(h <= PIPS_DRAW_DIM_MAX && w <= PIPS_DRAW_DIM_MAX, "%s: surfaces up to %d a side (h=%d, w=%d)", who,
+                   PIPS_DRAW_DIM_MAX, h, w);
+    PIPS_CHECK_ARG(trail >= 0 && trail <= PIPS_DRAW_TRAIL_MAX, "%s: trail=%d outside 0..%d", who, trail, PIPS_DRAW_TRAIL_MAX);
+    PIPS_CHECK_ARG(line8 <= PIPS_DRAW_RADIUS8_MAX && dot8 <= PIPS_DRAW_RADIUS8_MAX, "%s: a radius above %d eighths (line8=%d, dot8=%d)",
+                   who, PIPS_DRAW_RADIUS8_MAX, line8, dot8);
+    PIPS_CHECK_ARG(alpha_vis >= 0 && alpha_vis <= 256 && alpha_occ >= 0 && alpha_occ <= 256,
+                   "%s: alphas outside 0..256 (alpha_vis=%d, alpha_occ=%d)", who, alpha_vis, alpha_occ);
+    PIPS_CHECK_ARG(first >= 0 && (long long)first + F <= (long long)G, "%s: rows [%d, %d + %d) of %d", who, first, first, F, G);
+    if (fade != nullptr)                                                                    // (a host array: read here, passed by value)
+        for (int a = 0; a < trail; ++a) PIPS_CHECK_ARG(fade[a] >= 0 && fade[a] <= 256, "%s: fade[%d]=%d outside 0..256", who, a, fade[a]);
+    // plane k of the format: its rows and the bytes of a row
+    void* p[3] = {p0, p1, p2};
+    const size_t pitch[3] = {pitch0, pitch1, pitch2}, step[3] = {step0, step1, step2};
+    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2, sb = wide ? 2 : 1;
+    const bool planar = format == PIPS_FMT_PLANAR8;
+    const int planes = semi ? 2 : (yuv || planar) ? 3 : 1;
+    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : (yuv || planar) ? sb : 3;
+    const size_t rows[3] = {(size_t)h, planar ? (size_t)h : ch, planar ? (size_t)h : ch};
+    const size_t row_bytes[3] = {(size_t)w * bpp, planar ? (size_t)w : (semi ? 2 * cw : cw) * sb, planar ? (size_t)w : cw * sb};
+    for (int k = 0; k < planes; ++k) {
+        PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "%s: pitch %zu of plane %d is below the %zu bytes of a row", who, pitch[k], k,
+                       row_bytes[k]);
+        PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
+                       "%s: step %zu of plane %d is below pitch %zu x %zu rows", who, step[k], k, pitch[k], rows[k]);
+        PIPS_CHECK_ARG(!wide || (((uintptr_t)p[k] | pitch[k] | step[k]) & 1) == 0,
+                       "%s: plane %d of a 16-bit format needs an even pointer, pitch and step (pitch %zu, step %zu)", who, k, pitch[k],
+                       step[k]);
+    }
+    if (F == 0 || n == 0) return PIPS_OK;
+    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(p[k] != nullptr, "%s: null plane %d", who, k);
+    PIPS_CHECK_ARG(trajs && colors && workspace, "%s: null trajs, colors or workspace", who);
+    const size_t need = pips_draw_workspace_bytes(F, n, trail);
+    PIPS_CHECK_ARG(workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    PIPS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: the workspace must lie on a 16-byte address", who);
+    const DrawStyle style{trail, line8, dot8, alpha_vis, alpha_occ, vis_logit};
+    return launch_tracks_draw(format, matrix, range, F, h, w, p, pitch, step, trajs, vis, n, first, src_h, src_w, colors, style, fade,
+                              (int*)workspace, (hipStream_t)stream);
+}
 int pips_tracks_draw(int format, int matrix, int range, int F, int h, int w, void* p0, size_t pitch0, size_t step0, void* p1,
                      size_t pitch1, size_t step1, void* p2, size_t pitch2, size_t step2, const float* trajs, const float* vis, int G,
                      int n, int first, int src_h, int src_w, const uint8_t* colors, int trail, int line8, int dot8, int alpha_vis,
                      int alpha_occ, float vis_logit, void* workspace, size_t workspace_bytes, void* stream) {
-    PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I420) || format == PIPS_FMT_PLANAR8,
-                   "tracks_draw: format %d is not an 8-bit surface (the 10-bit formats are not drawn on)", format);
-    const bool semi = format == PIPS_FMT_NV12, yuv = semi || format == PIPS_FMT_I420;
-    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
-                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
-                   "tracks_draw: unknown matrix %d or range %d", matrix, range);
-    PIPS_CHECK_ARG(F >= 0 && n >= 0, "tracks_draw: need F >= 0 and n >= 0 (F=%d, n=%d)", F, n);
-    PIPS_CHECK_ARG(h >= 1 && w >= 1 && src_h >= 1 && src_w >= 1, "tracks_draw: need sizes of at least 1x1 (h=%d, w=%d, src_h=%d, src_w=%d)",
-                   h, w, src_h, src_w);
-    PIPS_CHECK_ARG(h <= PIPS_DRAW_DIM_MAX && w <= PIPS_DRAW_DIM_MAX, "tracks_draw: surfaces up to %d a side (h=%d, w=%d)",
-                   PIPS_DRAW_DIM_MAX, h, w);
-    PIPS_CHECK_ARG(trail >= 0 && trail <= PIPS_DRAW_TRAIL_MAX, "tracks_draw: trail=%d outside 0..%d", trail, PIPS_DRAW_TRAIL_MAX);
-    PIPS_CHECK_ARG(line8 <= PIPS_DRAW_RADIUS8_MAX && dot8 <= PIPS_DRAW_RADIUS8_MAX, "tracks_draw: a radius above %d eighths (line8=%d, dot8=%d)",
-                   PIPS_DRAW_RADIUS8_MAX, line8, dot8);
-    PIPS_CHECK_ARG(alpha_vis >= 0 && alpha_vis <= 256 && alpha_occ >= 0 && alpha_occ <= 256,
-                   "tracks_draw: alphas outside 0..256 (alpha_vis=%d, alpha_occ=%d)", alpha_vis, alpha_occ);
-    PIPS_CHECK_ARG(first >= 0 && (long long)first + F <= (long long)G, "tracks_draw: rows [%d, %d + %d) of %d", first, first, F, G);
-    // plane k of the format: its rows and the bytes of a row
-    void* p[3] = {p0, p1, p2};
-    const size_t pitch[3] = {pitch0, pitch1, pitch2}, step[3] = {step0, step1, step2};
-    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2;
-    const bool planar = format == PIPS_FMT_PLANAR8;
-    const int planes = semi ? 2 : (yuv || planar) ? 3 : 1;
-    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : (yuv || planar) ? 1 : 3;
-    const size_t rows[3] = {(size_t)h, planar ? (size_t)h : ch, planar ? (size_t)h : ch};
-    const size_t row_bytes[3] = {(size_t)w * bpp, planar ? (size_t)w : semi ? 2 * cw : cw, planar ? (size_t)w : cw};
-    for (int k = 0; k < planes; ++k) {
-        PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "tracks_draw: pitch %zu of plane %d is below the %zu bytes of a row", pitch[k], k,
-                       row_bytes[k]);
-        PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
-                       "tracks_draw: step %zu of plane %d is below pitch %zu x %zu rows", step[k], k, pitch[k], rows[k]);
-    }
-    if (F == 0 || n == 0) return PIPS_OK;
-    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(p[k] != nullptr, "tracks_draw: null plane %d", k);
-    PIPS_CHECK_ARG(trajs && colors && workspace, "tracks_draw: null trajs, colors or workspace");
-    const size_t need = pips_draw_workspace_bytes(F, n, trail);
-    PIPS_CHECK_ARG(workspace_bytes >= need, "tracks_draw: workspace %zu < %zu bytes", workspace_bytes, need);
-    PIPS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "tracks_draw: the workspace must lie on a 16-byte address");
-    const DrawStyle style{trail, line8, dot8, alpha_vis, alpha_occ, vis_logit};
-    return launch_tracks_draw(format, matrix, range, F, h, w, p, pitch, step, trajs, vis, n, first, src_h, src_w, colors, style,
-                              (int*)workspace, (hipStream_t)stream);
+    return tracks_draw_any("tracks_draw", false, format, matrix, range, F, h, w, p0, pitch0, step0, p1, pitch1, step1, p2, pitch2, step2,
+                           trajs, vis, G, n, first, src_h, src_w, colors, trail, line8, dot8, alpha_vis, alpha_occ, vis_logit, nullptr,
+                           workspace, workspace_bytes, stream);
+}
+int pips_tracks_draw_ex(int format, int matrix, int range, int F, int h, int w, void* p0, size_t pitch0, size_t step0, void* p1,
+                        size_t pitch1, size_t step1, void* p2, size_t pitch2, size_t step2, const float* trajs, const float* vis, int G,
+                        int n, int first, int src_h, int src_w, const uint8_t* colors, int trail, int line8, int dot8, int alpha_vis,
+                        int alpha_occ, float vis_logit, const int* fade, void* workspace, size_t workspace_bytes, void* stream) {
+    return tracks_draw_any("tracks_draw_ex", true, format, matrix, range, F, h, w, p0, pitch0, step0, p1, pitch1, step1, p2, pitch2, step2,
+                           trajs, vis, G, n, first, src_h, src_w, colors, trail, line8, dot8, alpha_vis, alpha_occ, vis_logit, fade,
+                           workspace, workspace_bytes, stream);
 }
 
 // ---- whole forward

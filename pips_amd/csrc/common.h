@@ -546,10 +546,11 @@ int launch_cut_table(const void* frames, int src_u8, int F, int h, int w, const 
 int launch_frames_import(int format, int matrix, int range, int filter, int F, int h, int w, const void* const* p, const size_t* pitch,
                          const size_t* step, void* dst, int dst_u8, int H, int W, hipStream_t st);
 
-// ---- draw.hip: track trails drawn into F caller-owned surfaces in place (pips_tracks_draw).  The workspace holds, per (frame,
+// ---- draw.hip: track trails drawn into F caller-owned surfaces in place (pips_tracks_draw, pips_tracks_draw_ex).  The workspace holds, per (frame,
 // track), DRAW_HEAD_INTS ints -- the box of pixels the track can touch (the boxes lie together at its start), its opacity, its
 // colour in the surface's components, the mask of its drawn segments -- and the trail + 1 quantised points; arguments checked
-// by the caller (the workspace on a 16-byte address).
+// by the caller (the workspace on a 16-byte address).  fade: NULL, or the `trail` factors 0..256 of pips_tracks_draw_ex on the HOST
+// (they travel to the kernels by value).
 constexpr int DRAW_HEAD_INTS = 8;
 __host__ __device__ inline size_t draw_track_ints(int trail) { return (size_t)DRAW_HEAD_INTS + 2 * ((size_t)trail + 1); }
 struct DrawStyle {
@@ -558,6 +559,6 @@ struct DrawStyle {
 };
 int launch_tracks_draw(int format, int matrix, int range, int F, int h, int w, void* const* p, const size_t* pitch, const size_t* step,
                        const float* trajs, const float* vis, int n, int first, int src_h, int src_w, const unsigned char* colors,
-                       const DrawStyle& style, int* workspace, hipStream_t st);
+                       const DrawStyle& style, const int* fade, int* workspace, hipStream_t st);
 
 }  // namespace pips

@@ -1,9 +1,11 @@
-// Tracks out (pips_tracks_draw; drivers.draw_tracks, drivers.TrackPainter): the trails of n tracks drawn into F caller-owned
-// surfaces in place -- packed RGB / BGR / RGBA / BGRA, NV12, I420 or planar RGB with any base address, row pitch and frame step.
+// Tracks out (pips_tracks_draw, pips_tracks_draw_ex; drivers.draw_tracks, drivers.TrackPainter): the trails of n tracks drawn into F
+// caller-owned surfaces in place -- packed RGB / BGR / RGBA / BGRA, NV12, I420 or planar RGB, and through the _ex entry the 16-bit
+// P010 and I010, with any base address, row pitch and frame step.
 // The rule (include/pips_hip.h; yuv.h for the RGB -> YCbCr constants) is integer arithmetic behind the quantisation of the
 // positions, so the bytes are drivers.draw_tracks_torch's.  Plain HIP, two launches: draw_prepare_kernel writes one record per
-// (frame, track) into the workspace, draw_raster_kernel blends the records into the tiles they touch.  No atomics: a pixel is owned
-// by one thread, which applies the tracks in column order.  Nothing outside the w x h image of a plane is written.
+// (frame, track) into the workspace, draw_raster_kernel blends the records into the tiles they touch (its DrawFade form when the
+// _ex entry has a fade table: the same body with a factor per subsample in place of the coverage mask).  No atomics: a pixel is
+// owned by one thread, which applies the tracks in column order.  Nothing outside the w x h image of a plane is written.
 #include "common.h"
 #include "fp_rn.h"
 #include "yuv.h"
@@ -15,12 +17,12 @@ namespace {
 constexpr int DRAW_THREADS = 256;
 constexpr int DRAW_TILE = 16;                                   // pixels a side: 256 pixels, 8 x 8 chroma samples
 constexpr int DRAW_ABSENT = INT_MIN;                            // x of a point that is not there
-enum { DRAW_PACKED3 = 0, DRAW_PACKED4 = 1, DRAW_NV12 = 2, DRAW_I420 = 3, DRAW_PLANAR8 = 4 };
+enum { DRAW_PACKED3 = 0, DRAW_PACKED4 = 1, DRAW_NV12 = 2, DRAW_I420 = 3, DRAW_PLANAR8 = 4, DRAW_P010 = 5, DRAW_I010 = 6 };
 // The workspace: first the boxes, one int4 per (frame, track) = x0, y0, x1, y1 of the pixels it can touch (inclusive; x0 > x1:
 // none) -- every tile of a frame reads all of them, 16 bytes a lane -- then the records of DRAW_REC_INTS + 2 (trail + 1) ints:
-// [0] the opacity A, [1] the colour c0 | c1 << 8 | c2 << 16 (R G B, or Y Cb Cr for the YCbCr surfaces), [2] bit j - 1 set when the
-// segment from point j - 1 to point j is drawn, [3] 1 when the head's disc is drawn; then the points (x, y) in eighths, point
-// `trail` the head
+// [0] the opacity A, [1] the colour c0 | c1 << 8 | c2 << 16 (R G B, or Y Cb Cr for the YCbCr surfaces; three 10-bit fields
+// c0 | c1 << 10 | c2 << 20 for P010 and I010), [2] bit j - 1 set when the segment from point j - 1 to point j is drawn, [3] 1 when
+// the head's disc is drawn; then the points (x, y) in eighths, point `trail` the head
 constexpr int DRAW_REC_INTS = DRAW_HEAD_INTS - 4;
 enum { DH_ALPHA = 0, DH_COLOR = 1, DH_SEGS = 2, DH_HEAD = 3 };
 __host__ __device__ __forceinline__ size_t draw_rec_ints(int trail) { return draw_track_ints(trail) - 4; }
@@ -31,8 +33,18 @@ struct DrawDst {
     size_t pitch[3], step[3];
 };
 
+// pips_tracks_draw_ex's table by value: f[a] the factor 0..256 of the capsule of age a
+struct DrawFade {
+    unsigned short f[PIPS_DRAW_TRAIL_MAX];
+};
+
 __device__ __forceinline__ unsigned char* dst_row(const DrawDst& d, int k, int f, int y) {
     return d.p[k] + (size_t)f * d.step[k] + (size_t)y * d.pitch[k];
+}
+
+// the same row of a 16-bit plane (pointer, pitch and step are even)
+__device__ __forceinline__ unsigned short* dst_row16(const DrawDst& d, int k, int f, int y) {
+    return (unsigned short*)dst_row(d, k, f, y);
 }
 
 // a coordinate of the model's frame -> eighths of a surface pixel, DRAW_ABSENT for NaN, infinities and |u| > 32768
@@ -45,11 +57,13 @@ __device__ __forceinline__ int quantise(float x, bool scaled, float s) {
 // ------------------------------------------------------------------------------------------------------------------ prepare
 // One thread per (frame, track): the trail + 1 points of rows r - trail .. r quantised, the segments that are drawn, the box of
 // pixels with a subsample within the larger radius of a drawn end (clipped to the image), the opacity and the converted colour.
+// yuv: 0 the colour stays R G B, 1 the 8-bit rule, 2 rule10.  dead: bit a set when the fade factor of age a is 0 -- such a capsule
+// draws nothing, so it is not among the record's segments and not in the box.
 __global__ __launch_bounds__(DRAW_THREADS) void draw_prepare_kernel(const float* __restrict__ trajs, const float* __restrict__ vis, int n,
                                                                     int first, int f_base, int h, int w, int scale_x, int scale_y,
                                                                     float sx, float sy, const unsigned char* __restrict__ colors,
-                                                                    int yuv, RgbRule rule, DrawStyle st, int4* __restrict__ boxes,
-                                                                    int* __restrict__ recs) {
+                                                                    int yuv, RgbRule rule, Rgb10Rule rule10, unsigned dead, DrawStyle st,
+                                                                    int4* __restrict__ boxes, int* __restrict__ recs) {
     const int i = (int)(blockIdx.x * (unsigned)DRAW_THREADS + threadIdx.x);
     if (i >= n) return;
     const int f = f_base + (int)blockIdx.y, r = first + f;
@@ -69,8 +83,9 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_prepare_kernel(const float*
             if (qx == DRAW_ABSENT) qy = 0;
         }
         pts[2 * j] = qx, pts[2 * j + 1] = qy;
+        // (the segment that ends on point j has age trail - j)
         if (j > 0 && st.line8 >= 0 && qx != DRAW_ABSENT && px != DRAW_ABSENT && abs(qx - px) <= PIPS_DRAW_JUMP8_MAX &&
-            abs(qy - py) <= PIPS_DRAW_JUMP8_MAX) {
+            abs(qy - py) <= PIPS_DRAW_JUMP8_MAX && !((dead >> (st.trail - j)) & 1u)) {
             segs |= 1u << (j - 1);
             lox = min(lox, min(px, qx)), hix = max(hix, max(px, qx));
             loy = min(loy, min(py, qy)), hiy = max(hiy, max(py, qy));
@@ -91,9 +106,11 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_prepare_kernel(const float*
     }
     const int R = colors[3 * (size_t)i], G = colors[3 * (size_t)i + 1], B = colors[3 * (size_t)i + 2];
     int c0 = R, c1 = G, c2 = B;
-    if (yuv) rgb_to_yuv(rule, R, G, B, c0, c1, c2);
+    if (yuv == 1) rgb_to_yuv(rule, R, G, B, c0, c1, c2);
+    if (yuv == 2) rgb_to_yuv10(rule10, R, G, B, c0, c1, c2);
     boxes[(size_t)f * n + i] = make_int4(x0, y0, x1, y1);
-    rec[DH_ALPHA] = alpha, rec[DH_COLOR] = c0 | c1 << 8 | c2 << 16, rec[DH_SEGS] = (int)segs, rec[DH_HEAD] = disc ? 1 : 0;
+    rec[DH_ALPHA] = alpha, rec[DH_COLOR] = yuv == 2 ? (c0 | c1 << 10 | c2 << 20) : (c0 | c1 << 8 | c2 << 16), rec[DH_SEGS] = (int)segs,
+    rec[DH_HEAD] = disc ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------- raster
@@ -131,14 +148,34 @@ __device__ __forceinline__ unsigned capsule_mask(int p0x, int p0y, int p1x, int 
 // the four waves compact the hits, in column order, into an LDS list, and every thread walks that list for its pixel -- the union
 // of the track's primitives on four subsamples, the sum over the quad by two lane exchanges, the blend in registers.  The pixel is
 // loaded when the first list is not empty and stored when a track changed it.
-template <int LAYOUT>
+// FADE: the pixel keeps a factor 0..256 per subsample, the largest among the primitives that hold it (the head's disc: 256), in
+// place of the mask; the segments are walked youngest first, so that a table that does not grow with age ends the walk as soon as
+// all four stand at 256.  The table is the one trailing argument `fade` (a DrawFade; the form without it is the plain kernel, with
+// pips_tracks_draw's arguments and instructions); the block stages it in LDS ahead of its first barrier.
+// The 16-bit layouts: a sample is a word whose 10-bit value lies in the high (P010) or low (I010) bits; a touched word is written
+// back with the other six bits zero, every other word is not written.
+template <int LAYOUT, typename... Fade>
 __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, int bgr, int h, int w, int n, int trail, int line8, int dot8,
                                                                    const int4* __restrict__ boxes, const int* __restrict__ recs,
-                                                                   int tiles_x, int f_base) {
-    constexpr bool YUV = LAYOUT == DRAW_NV12 || LAYOUT == DRAW_I420;
+                                                                   int tiles_x, int f_base, Fade... fade) {
+    constexpr bool FADE = sizeof...(Fade) != 0;
+    constexpr bool WIDE = LAYOUT == DRAW_P010 || LAYOUT == DRAW_I010;
+    constexpr bool YUV = LAYOUT == DRAW_NV12 || LAYOUT == DRAW_I420 || WIDE;
     constexpr int BPP = LAYOUT == DRAW_PACKED3 ? 3 : 4;
+    constexpr int CBITS = WIDE ? 10 : 8, CMASK = (1 << CBITS) - 1;  // a field of the record's colour word
+    constexpr int VSHIFT = LAYOUT == DRAW_P010 ? 6 : 0;            // where the value lies in a 16-bit word
     __shared__ int list[DRAW_THREADS];
     __shared__ int wave_hits[DRAW_THREADS / 64];
+    __shared__ int fade_s[FADE ? PIPS_DRAW_TRAIL_MAX : 1];
+    if constexpr (FADE) {                                       // (static indices only: the argument stays in scalar registers)
+        const DrawFade& table = (fade, ...);
+        if (threadIdx.x < PIPS_DRAW_TRAIL_MAX) {
+            int v = 0;
+#pragma unroll
+            for (int a = 0; a < PIPS_DRAW_TRAIL_MAX; ++a) v = (int)threadIdx.x == a ? (int)table.f[a] : v;
+            fade_s[threadIdx.x] = v;
+        }
+    }
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f = f_base + (int)blockIdx.y;
     const int X0 = (int)(blockIdx.x % (unsigned)tiles_x) * DRAW_TILE, Y0 = (int)(blockIdx.x / (unsigned)tiles_x) * DRAW_TILE;
@@ -182,6 +219,8 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, in
                 } else if constexpr (LAYOUT == DRAW_PLANAR8) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) c[k] = dst_row(d, k, f, y)[x];
+                } else if constexpr (WIDE) {
+                    c[0] = (dst_row16(d, 0, f, y)[x] >> VSHIFT) & 1023;
                 } else {
                     c[0] = dst_row(d, 0, f, y)[x];
                 }
@@ -192,6 +231,11 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, in
                     cb = q[0], cr = q[1];
                 } else if constexpr (LAYOUT == DRAW_I420) {
                     cb = dst_row(d, 1, f, y >> 1)[x >> 1], cr = dst_row(d, 2, f, y >> 1)[x >> 1];
+                } else if constexpr (LAYOUT == DRAW_P010) {
+                    const unsigned short* q = dst_row16(d, 1, f, y >> 1) + 2 * (size_t)(x >> 1);
+                    cb = q[0] >> 6, cr = q[1] >> 6;
+                } else if constexpr (LAYOUT == DRAW_I010) {
+                    cb = dst_row16(d, 1, f, y >> 1)[x >> 1] & 1023, cr = dst_row16(d, 2, f, y >> 1)[x >> 1] & 1023;
                 }
             }
         }
@@ -199,37 +243,57 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, in
             const int ti = __builtin_amdgcn_readfirstlane(list[e]);
             const int* rec = rec_f + (size_t)ti * RI;
             const int4 b = box_f[ti];
-            int k = 0;
+            int k = 0;                                          // the pixel's coverage: 0..4 subsamples, 0..1024 with FADE
             if (inimg && x >= b.x && x <= b.z && y >= b.y && y <= b.w) {
                 const int* pts = rec + DRAW_REC_INTS;
                 unsigned mask = 0;
                 if (rec[DH_HEAD]) mask = capsule_mask(pts[2 * trail], pts[2 * trail + 1], pts[2 * trail], pts[2 * trail + 1], dot8, 8 * x, 8 * y);
-                for (unsigned m = (unsigned)rec[DH_SEGS]; m != 0 && mask != 15u; m &= m - 1) {
-                    const int j = __builtin_ctz(m);             // the segment from point j to point j + 1
-                    const int p0x = pts[2 * j], p0y = pts[2 * j + 1], p1x = pts[2 * j + 2], p1y = pts[2 * j + 3];
-                    // a segment that reaches no subsample of the tile (the same for every thread: decided once for the block)
-                    if (max(p0x, p1x) + line8 < TX0 || min(p0x, p1x) - line8 > TX0 + TSPAN || max(p0y, p1y) + line8 < TY0 ||
-                        min(p0y, p1y) - line8 > TY0 + TSPAN)
-                        continue;
-                    mask |= capsule_mask(p0x, p0y, p1x, p1y, line8, 8 * x, 8 * y);
+                if constexpr (!FADE) {
+                    for (unsigned m = (unsigned)rec[DH_SEGS]; m != 0 && mask != 15u; m &= m - 1) {
+                        const int j = __builtin_ctz(m);         // the segment from point j to point j + 1
+                        const int p0x = pts[2 * j], p0y = pts[2 * j + 1], p1x = pts[2 * j + 2], p1y = pts[2 * j + 3];
+                        // a segment that reaches no subsample of the tile (the same for every thread: decided once for the block)
+                        if (max(p0x, p1x) + line8 < TX0 || min(p0x, p1x) - line8 > TX0 + TSPAN || max(p0y, p1y) + line8 < TY0 ||
+                            min(p0y, p1y) - line8 > TY0 + TSPAN)
+                            continue;
+                        mask |= capsule_mask(p0x, p0y, p1x, p1y, line8, 8 * x, 8 * y);
+                    }
+                    k = __popc(mask);
+                } else {
+                    int phi[4];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) phi[s] = ((mask >> s) & 1u) ? 256 : 0;
+                    // (a factor is at most 256: the four together have bit 8 set when all stand there)
+                    for (unsigned m = (unsigned)rec[DH_SEGS]; m != 0 && ((phi[0] & phi[1] & phi[2] & phi[3]) & 256) == 0;) {
+                        const int j = 31 - __builtin_clz(m);    // the youngest left: from point j to point j + 1, age trail - 1 - j
+                        m &= ~(1u << j);
+                        const int p0x = pts[2 * j], p0y = pts[2 * j + 1], p1x = pts[2 * j + 2], p1y = pts[2 * j + 3];
+                        if (max(p0x, p1x) + line8 < TX0 || min(p0x, p1x) - line8 > TX0 + TSPAN || max(p0y, p1y) + line8 < TY0 ||
+                            min(p0y, p1y) - line8 > TY0 + TSPAN)
+                            continue;
+                        const int fa = fade_s[trail - 1 - j];
+                        const unsigned in = capsule_mask(p0x, p0y, p1x, p1y, line8, 8 * x, 8 * y);
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) phi[s] = max(phi[s], ((in >> s) & 1u) ? fa : 0);
+                    }
+                    k = phi[0] + phi[1] + phi[2] + phi[3];
                 }
-                k = __popc(mask);
             }
             const int A = rec[DH_ALPHA], col = rec[DH_COLOR];
             if constexpr (YUV) {
                 int K = k + __shfl_xor(k, 1);
                 K += __shfl_xor(K, 2);
-                const int W = K * A;
+                const int W = FADE ? (K * A + 128) >> 8 : K * A;
                 if (chroma && W != 0) {
-                    cb = (cb * (4096 - W) + ((col >> 8) & 255) * W + 2048) >> 12;
-                    cr = (cr * (4096 - W) + ((col >> 16) & 255) * W + 2048) >> 12;
+                    cb = (cb * (4096 - W) + ((col >> CBITS) & CMASK) * W + 2048) >> 12;
+                    cr = (cr * (4096 - W) + ((col >> (2 * CBITS)) & CMASK) * W + 2048) >> 12;
                     ctouched = true;
                 }
             }
-            const int wgt = k * A;
+            const int wgt = FADE ? (k * A + 128) >> 8 : k * A;
             if (wgt != 0) {
 #pragma unroll
-                for (int q = 0; q < (YUV ? 1 : 3); ++q) c[q] = (c[q] * (1024 - wgt) + ((col >> (8 * q)) & 255) * wgt + 512) >> 10;
+                for (int q = 0; q < (YUV ? 1 : 3); ++q) c[q] = (c[q] * (1024 - wgt) + ((col >> (CBITS * q)) & CMASK) * wgt + 512) >> 10;
                 touched = true;
             }
         }
@@ -241,6 +305,8 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, in
         } else if constexpr (LAYOUT == DRAW_PLANAR8) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) dst_row(d, k, f, y)[x] = (unsigned char)c[k];
+        } else if constexpr (WIDE) {
+            dst_row16(d, 0, f, y)[x] = (unsigned short)(c[0] << VSHIFT);
         } else {
             dst_row(d, 0, f, y)[x] = (unsigned char)c[0];
         }
@@ -251,6 +317,11 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, in
             q[0] = (unsigned char)cb, q[1] = (unsigned char)cr;
         } else if constexpr (LAYOUT == DRAW_I420) {
             dst_row(d, 1, f, y >> 1)[x >> 1] = (unsigned char)cb, dst_row(d, 2, f, y >> 1)[x >> 1] = (unsigned char)cr;
+        } else if constexpr (LAYOUT == DRAW_P010) {
+            unsigned short* q = dst_row16(d, 1, f, y >> 1) + 2 * (size_t)(x >> 1);
+            q[0] = (unsigned short)(cb << 6), q[1] = (unsigned short)(cr << 6);
+        } else if constexpr (LAYOUT == DRAW_I010) {
+            dst_row16(d, 1, f, y >> 1)[x >> 1] = (unsigned short)cb, dst_row16(d, 2, f, y >> 1)[x >> 1] = (unsigned short)cr;
         }
     }
 }
@@ -259,25 +330,39 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_raster_kernel(DrawDst d, in
 
 int launch_tracks_draw(int format, int matrix, int range, int F, int h, int w, void* const* p, const size_t* pitch, const size_t* step,
                        const float* trajs, const float* vis, int n, int first, int src_h, int src_w, const unsigned char* colors,
-                       const DrawStyle& style, int* workspace, hipStream_t st) {
+                       const DrawStyle& style, const int* fade, int* workspace, hipStream_t st) {
     DrawDst d;
     for (int k = 0; k < 3; ++k) d.p[k] = (unsigned char*)p[k], d.pitch[k] = pitch[k], d.step[k] = step[k];
-    const bool yuv = format == PIPS_FMT_NV12 || format == PIPS_FMT_I420;
-    const RgbRule rule = yuv ? RGB_RULES[matrix][range] : RgbRule{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool yuv8 = format == PIPS_FMT_NV12 || format == PIPS_FMT_I420, yuv10 = format == PIPS_FMT_P010 || format == PIPS_FMT_I010;
+    const RgbRule rule = yuv8 ? RGB_RULES[matrix][range] : RgbRule{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const Rgb10Rule rule10 = yuv10 ? RGB10_RULES[matrix][range] : Rgb10Rule{0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int bgr = format == PIPS_FMT_BGR24 || format == PIPS_FMT_BGRA32;
     const float sx = (float)w / (float)src_w, sy = (float)h / (float)src_h;
     const int tiles_x = (w + DRAW_TILE - 1) / DRAW_TILE, tiles_y = (h + DRAW_TILE - 1) / DRAW_TILE;     // <= 512 each
     int4* boxes = (int4*)workspace;
     int* recs = workspace + 4 * (size_t)F * n;
+    DrawFade table;
+    unsigned dead = 0;
+    for (int a = 0; a < PIPS_DRAW_TRAIL_MAX; ++a) {
+        table.f[a] = (unsigned short)((fade != nullptr && a < style.trail) ? fade[a] : 256);
+        if (table.f[a] == 0) dead |= 1u << a;
+    }
     constexpr int FRAMES_A_LAUNCH = 65535;                     // the grid's y
     for (int f0 = 0; f0 < F; f0 += FRAMES_A_LAUNCH) {
         const unsigned fc = (unsigned)std::min(F - f0, FRAMES_A_LAUNCH);
         hipLaunchKernelGGL(draw_prepare_kernel, dim3((unsigned)((n + DRAW_THREADS - 1) / DRAW_THREADS), fc), dim3(DRAW_THREADS), 0, st,
-                           trajs, vis, n, first, f0, h, w, src_w != w, src_h != h, sx, sy, colors, yuv ? 1 : 0, rule, style, boxes, recs);
+                           trajs, vis, n, first, f0, h, w, src_w != w, src_h != h, sx, sy, colors, yuv8 ? 1 : yuv10 ? 2 : 0, rule, rule10,
+                           dead, style, boxes, recs);
         const dim3 grid((unsigned)(tiles_x * tiles_y), fc);
-#define PIPS_DRAW_CASE(L)                                                                                                           \
-    hipLaunchKernelGGL(draw_raster_kernel<L>, grid, dim3(DRAW_THREADS), 0, st, d, bgr, h, w, n, style.trail, style.line8, style.dot8, \
-                       (const int4*)boxes, (const int*)recs, tiles_x, f0)
+#define PIPS_DRAW_CASE(L)                                                                                                                \
+    do {                                                                                                                                 \
+        if (fade == nullptr)                                                                                                             \
+            hipLaunchKernelGGL(draw_raster_kernel<L>, grid, dim3(DRAW_THREADS), 0, st, d, bgr, h, w, n, style.trail, style.line8,        \
+                               style.dot8, (const int4*)boxes, (const int*)recs, tiles_x, f0);                                           \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((draw_raster_kernel<L, DrawFade>), grid, dim3(DRAW_THREADS), 0, st, d, bgr, h, w, n, style.trail, style.line8,   \
+                               style.dot8, (const int4*)boxes, (const int*)recs, tiles_x, f0, table);                                    \
+    } while (0)
         switch (format) {
             case PIPS_FMT_RGB24:
             case PIPS_FMT_BGR24: PIPS_DRAW_CASE(DRAW_PACKED3); break;
@@ -285,6 +370,8 @@ int launch_tracks_draw(int format, int matrix, int range, int F, int h, int w, v
             case PIPS_FMT_BGRA32: PIPS_DRAW_CASE(DRAW_PACKED4); break;
             case PIPS_FMT_NV12: PIPS_DRAW_CASE(DRAW_NV12); break;
             case PIPS_FMT_I420: PIPS_DRAW_CASE(DRAW_I420); break;
+            case PIPS_FMT_P010: PIPS_DRAW_CASE(DRAW_P010); break;
+            case PIPS_FMT_I010: PIPS_DRAW_CASE(DRAW_I010); break;
             default: PIPS_DRAW_CASE(DRAW_PLANAR8); break;
         }
 #undef PIPS_DRAW_CASE

@@ -65,4 +65,29 @@ __host__ __device__ __forceinline__ void yuv10_to_rgb(const YuvRule& k, int Y, i
     b = yuv_clamp8((c + k.bu * d) >> 18);
 }
 
+// The way back to 10 bits, for pips_tracks_draw_ex's colours on P010 and I010 (include/pips_hip.h): with h = 1 << (sh - 1),
+// Y = y0 + ((yr R + yg G + yb B + h) >> sh), Cb = clamp(512 + ((ur R + ug G + ub B + h) >> sh)), Cr likewise, clamp to [0, 1023].
+// Limited range is the 8-bit row with two more result bits (sh = 14): white 940, chroma 64..960.  Full range (sh = 16) has the
+// standard coefficients scaled by 65536 x 1023 / 255 and rounded so that each luma row sums to 262915 and each chroma row to 0:
+// black 0, white 1023, chroma reaches 1024 ahead of the clamp.  A grey gives exactly (Y, 512, 512) in both.  Every accumulator
+// stays inside int32 (|sum| < 2^27).
+struct Rgb10Rule {
+    int y0, sh, yr, yg, yb, ur, ug, ub, vr, vg, vb;
+};
+
+// [matrix][range], as YUV_RULES
+constexpr Rgb10Rule RGB10_RULES[2][2] = {
+    {{64, 14, 16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681}, {0, 16, 78612, 154331, 29972, -44363, -87095, 131458, 131458, -110079, -21379}},
+    {{64, 14, 11966, 40254, 4064, -6596, -22188, 28784, 28784, -26145, -2639}, {0, 16, 55896, 188037, 18982, -30123, -101335, 131458, 131458, -119404, -12054}},
+};
+
+__host__ __device__ __forceinline__ int yuv_clamp10(int v) { return v < 0 ? 0 : (v > 1023 ? 1023 : v); }
+
+__host__ __device__ __forceinline__ void rgb_to_yuv10(const Rgb10Rule& k, int r, int g, int b, int& Y, int& Cb, int& Cr) {
+    const int half = 1 << (k.sh - 1);
+    Y = k.y0 + ((k.yr * r + k.yg * g + k.yb * b + half) >> k.sh);
+    Cb = yuv_clamp10(512 + ((k.ur * r + k.ug * g + k.ub * b + half) >> k.sh));
+    Cr = yuv_clamp10(512 + ((k.vr * r + k.vg * g + k.vb * b + half) >> k.sh));
+}
+
 }  // namespace pips

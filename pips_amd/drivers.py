@@ -28,8 +28,9 @@
   ``pips_frames_import_ex`` launch when asked -- two-tap bilinear, or antialiased with ``antialias=True``; the second is the same
   rule in torch ops, bit for bit.
 * ``draw_tracks`` / ``draw_tracks_torch`` / ``TrackPainter`` -- the way out: the trails of a tracker's output drawn onto the decoder's
-  8-bit surfaces on the device, in place (one ``pips_tracks_draw`` call; the second is the same integer rule in torch ops, byte for
-  byte); ``TrackPainter`` paints the pushes of a streamed tracker one by one, keeping the last rows by identity; ``track_colors``
+  surfaces on the device, in place -- the 8-bit ones by one ``pips_tracks_draw`` call, the 10-bit P010 / I010 and trails that fade
+  with age (``fade=``) by ``pips_tracks_draw_ex``; the second is the same integer rule in torch ops, byte for byte; ``TrackPainter``
+  paints the pushes of a streamed tracker one by one, keeping the last rows by identity; ``track_colors``
   gives each identity its colour.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
@@ -1454,10 +1455,29 @@ RGB_RULES = {
 }
 
 
-def rgb_to_yuv_torch(rgb, matrix="bt709", range="limited"):
-    """the colour conversion of pips_tracks_draw: rgb (...,3) integers 0..255 -> (...,3) int64 Y, Cb, Cr"""
-    y0, yr, yg, yb, ur, ug, ub, vr, vg, vb = RGB_RULES[(matrix, range)]
+# pips_tracks_draw_ex's constants for P010 and I010: (y0, sh, yr, yg, yb, ur, ug, ub, vr, vg, vb) by (matrix, range)
+RGB10_RULES = {
+    ("bt601", "limited"): (64, 14, 16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681),
+    ("bt601", "full"): (0, 16, 78612, 154331, 29972, -44363, -87095, 131458, 131458, -110079, -21379),
+    ("bt709", "limited"): (64, 14, 11966, 40254, 4064, -6596, -22188, 28784, 28784, -26145, -2639),
+    ("bt709", "full"): (0, 16, 55896, 188037, 18982, -30123, -101335, 131458, 131458, -119404, -12054),
+}
+
+
+def rgb_to_yuv_torch(rgb, matrix="bt709", range="limited", bits=8):
+    """the colour conversion of pips_tracks_draw (``bits=8``) and of pips_tracks_draw_ex on the 10-bit surfaces (``bits=10``): rgb
+    (...,3) integers 0..255 -> (...,3) int64 Y, Cb, Cr"""
+    if bits not in (8, 10):
+        raise ValueError(f"bits must be 8 or 10, not {bits!r}")
     R, G, B = rgb.to(torch.int64).unbind(-1)
+    if bits == 10:
+        y0, sh, yr, yg, yb, ur, ug, ub, vr, vg, vb = RGB10_RULES[(matrix, range)]
+        half = 1 << (sh - 1)
+        Y = y0 + ((yr * R + yg * G + yb * B + half) >> sh)
+        Cb = (512 + ((ur * R + ug * G + ub * B + half) >> sh)).clamp(0, 1023)
+        Cr = (512 + ((vr * R + vg * G + vb * B + half) >> sh)).clamp(0, 1023)
+        return torch.stack([Y, Cb, Cr], dim=-1)
+    y0, yr, yg, yb, ur, ug, ub, vr, vg, vb = RGB_RULES[(matrix, range)]
     Y = y0 + ((yr * R + yg * G + yb * B + 32768) >> 16)
     Cb = (128 + ((ur * R + ug * G + ub * B + 32768) >> 16)).clamp(0, 255)
     Cr = (128 + ((vr * R + vg * G + vb * B + 32768) >> 16)).clamp(0, 255)
@@ -1508,6 +1528,23 @@ def _draw_setup(planes, trajs, vis, colors, ids, width, dot, alpha, alpha_occ, v
             _round_half_up(alpha_occ, 256.0), vis_logit)
 
 
+def _draw_fade(fade, trail):
+    """``fade`` of ``draw_tracks``: None, "linear" or ``trail`` floats in 0..1 -> None or the rule's ``trail`` ints 0..256 by age"""
+    if fade is None:
+        return None
+    if isinstance(fade, str):
+        if fade != "linear":
+            raise ValueError(f"fade must be None, 'linear' or a sequence of {trail} floats in 0..1, not {fade!r}")
+        return [(512 * (trail - a) + trail) // (2 * trail) for a in _range(trail)]       # round_half_up(256 (trail - a) / trail)
+    fade = fade.tolist() if torch.is_tensor(fade) else list(fade)
+    if len(fade) != trail:
+        raise ValueError(f"fade must have trail = {trail} entries, not {len(fade)}")
+    for v in fade:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError(f"a fade entry must lie in 0..1, not {v!r}")
+    return [_round_half_up(v, 256.0) for v in fade]
+
+
 def _draw_quantise(v, n_src, n_dst):
     """a coordinate column (…) float32 of an ``n_src`` wide axis -> (Q int64 eighths of a pixel of the ``n_dst`` wide axis, present)"""
     if n_src != n_dst:
@@ -1532,10 +1569,12 @@ def _draw_inside(cx, cy, p0, p1, R):
     return torch.where((L == 0) | (t <= 0), at_p0, torch.where(t >= L, at_p1, along))
 
 
-def draw_coverage_torch(trajs, r, h, w, src_size, trail, line8, dot8):
+def draw_coverage_torch(trajs, r, h, w, src_size, trail, line8, dot8, fade=None):
     """The coverage of the rule for the frame that takes row ``r`` of trajs (G,n,2): k (n,h,w) int64 in 0..4, the subsamples of
     each pixel inside the union of each track's primitives.  Subsample (j, i) of the 2h x 2w grid lies at (4 i - 2, 4 j - 2)
-    eighths: pixel x owns columns 2 x and 2 x + 1."""
+    eighths: pixel x owns columns 2 x and 2 x + 1.  With ``fade`` (``trail`` ints 0..256 by age) the result is Wp (n,h,w) in
+    0..1024 instead: per subsample the largest factor among the primitives that hold it -- 256 for the head's disc, fade[a] for the
+    segment of age a -- summed over the pixel's four."""
     dev, n = trajs.device, trajs.shape[1]
     src_h, src_w = src_size
     cx = (4 * torch.arange(2 * w, device=dev) - 2).view(1, 1, -1)
@@ -1546,66 +1585,93 @@ def draw_coverage_torch(trajs, r, h, w, src_size, trail, line8, dot8):
     pts, ok = torch.stack([qx, qy], dim=-1), okx & oky             # (m,n,2), (m,n): the head is the last row
     live = torch.nonzero(ok[-1]).squeeze(1)                        # an absent head hides the whole trail: only these tracks draw
     pts, ok = pts[:, live], ok[:, live]
-    inside = torch.zeros(live.numel(), 2 * h, 2 * w, dtype=torch.bool, device=dev)
+    faded = fade is not None
+    inside = torch.zeros(live.numel(), 2 * h, 2 * w, dtype=torch.int64 if faded else torch.bool, device=dev)     # phi when faded
     if dot8 >= 0:
-        inside |= _draw_inside(cx, cy, pts[-1], pts[-1], dot8)
+        head = _draw_inside(cx, cy, pts[-1], pts[-1], dot8)
+        inside = torch.where(head, 256, inside) if faded else inside | head
     if line8 >= 0:
         for g in range(1, pts.shape[0]):
             d = (pts[g] - pts[g - 1]).abs()
             drawn = ok[g] & ok[g - 1] & (d[:, 0] <= ops.DRAW_JUMP8_MAX) & (d[:, 1] <= ops.DRAW_JUMP8_MAX)
             if bool(drawn.any()):
-                inside |= _draw_inside(cx, cy, pts[g - 1], pts[g], line8) & drawn.view(-1, 1, 1)
+                seg = _draw_inside(cx, cy, pts[g - 1], pts[g], line8) & drawn.view(-1, 1, 1)
+                if faded:                                              # the segment that ends on row g has age (rows - 1) - g
+                    inside = torch.maximum(inside, seg.to(torch.int64) * int(fade[pts.shape[0] - 1 - g]))
+                else:
+                    inside |= seg
     k = torch.zeros(n, h, w, dtype=torch.int64, device=dev)
     k[live] = inside.view(live.numel(), h, 2, w, 2).sum(dim=(2, 4))
     return k
 
 
 def draw_tracks_torch(planes, fmt, trajs, vis=None, colors=None, ids=None, size=None, first=0, trail=16, width=2.0, dot=3.0, alpha=1.0,
-                      alpha_occ=0.35, vis_thr=0.5, matrix="bt709", range="limited", inplace=False):
-    """pips_tracks_draw (include/pips_hip.h) as int64 torch ops, on any device: ``draw_tracks``' arguments and result.  Per frame the
-    coverage of every track (``draw_coverage_torch``), then the tracks one after the other in column order: the blend of the
-    full-resolution samples with 1024 - k A, and for nv12 / i420 of the chroma samples with K summed over each 2 x 2 block of the
-    zero-padded coverage.  Equal to the kernels bit for bit; written to be read, not to be fast."""
+                      alpha_occ=0.35, vis_thr=0.5, matrix="bt709", range="limited", inplace=False, fade=None):
+    """pips_tracks_draw and pips_tracks_draw_ex (include/pips_hip.h) as int64 torch ops, on any device: ``draw_tracks``' arguments and
+    result.  Per frame the coverage of every track (``draw_coverage_torch``), then the tracks one after the other in column order:
+    the blend of the full-resolution samples with 1024 - k A, and for the 4:2:0 formats of the chroma samples with K summed over
+    each 2 x 2 block of the zero-padded coverage; with ``fade`` the weights are (Wp A + 128) >> 8 and (K A + 128) >> 8 of the faded
+    coverage.  On "p010" / "i010" the blend runs on the 10-bit values and only the words that got a weight are written, their six
+    other bits zero.  Equal to the kernels bit for bit; written to be read, not to be fast."""
     planes, trajs, vis, colors, line8, dot8, a_vis, a_occ, vis_logit = _draw_setup(planes, trajs, vis, colors, ids, width, dot, alpha,
                                                                                   alpha_occ, vis_thr)
     trail, first = _whole(trail, "trail", 0), _whole(first, "first", 0)
+    if not 0 <= trail <= ops.DRAW_TRAIL_MAX:
+        raise ValueError(f"trail must lie in 0..{ops.DRAW_TRAIL_MAX}, not {trail}")
+    fade = _draw_fade(fade, trail)
+    dtypes = [p.dtype for p in planes]                                                             # (uint16 planes are worked on as int16)
     planes, F, h, w, G, n, src_h, src_w = ops.draw_check(planes, fmt, trajs, vis, colors, first, size, trail, line8, dot8, a_vis, a_occ,
                                                          matrix, range)
     if not inplace:
         planes = [p.clone() for p in planes]
-    yuv = fmt in ("nv12", "i420")
-    comp = rgb_to_yuv_torch(colors, matrix, range) if yuv else colors.to(torch.int64)               # (n,3) in the surface's components
+    wide, shift = fmt in ops.IMPORT_16BIT, 6 if fmt == "p010" else 0
+    yuv = fmt in ("nv12", "i420") or wide
+    comp = rgb_to_yuv_torch(colors, matrix, range, 10 if wide else 8) if yuv else colors.to(torch.int64)     # (n,3) in the surface's components
+
+    def value(p):                                                                                  # a plane of one frame -> its samples' values
+        return ((p.to(torch.int64) & 0xFFFF) >> shift) & 1023 if wide else p.to(torch.int64)
+
+    def put(p, f, v, hit):
+        """the blended values ``v`` into frame f of plane p: every byte of an 8-bit plane (an untouched one is its old value), of a
+        16-bit plane the words that got a weight (``hit``) alone, as int16 bit patterns"""
+        if not wide:
+            p[f] = v.to(torch.uint8)
+            return
+        word = v << shift
+        p[f] = torch.where(hit, word - ((word & 0x8000) << 1), p[f].to(torch.int64)).to(torch.int16)
     if fmt == "planar8":
         full = [planes[0][:, c] for c in (0, 1, 2)]                                                # views (F,h,w) the blend writes into
     elif yuv:
         full = [planes[0]]
-        chroma = [planes[1][..., 0], planes[1][..., 1]] if fmt == "nv12" else [planes[1], planes[2]]
+        chroma = [planes[1][..., 0], planes[1][..., 1]] if fmt in ("nv12", "p010") else [planes[1], planes[2]]
     else:
         full = [planes[0][..., c] for c in ((2, 1, 0) if fmt in ("bgr24", "bgra32") else (0, 1, 2))]
     for f in _range(F):
         r = first + f
-        k = draw_coverage_torch(trajs, r, h, w, (src_h, src_w), trail, line8, dot8)                # (n,h,w)
+        k = draw_coverage_torch(trajs, r, h, w, (src_h, src_w), trail, line8, dot8, fade)          # (n,h,w): k, or Wp when faded
         seen = torch.ones(n, dtype=torch.bool, device=k.device) if vis is None else vis[r] > vis_logit      # (NaN compares false)
-        A = torch.where(seen, a_vis, a_occ).to(torch.int64)
-        wgt = k * A.view(n, 1, 1)
-        cur = [p[f].to(torch.int64) for p in full]
+        A = torch.where(seen, a_vis, a_occ).to(torch.int64).view(n, 1, 1)
+        wgt = k * A if fade is None else (k * A + 128) >> 8
+        cur = [value(p[f]) for p in full]
         if yuv:
-            K = torch.nn.functional.pad(wgt, (0, w % 2, 0, h % 2)).view(n, (h + 1) // 2, 2, (w + 1) // 2, 2).sum(dim=(2, 4))
-            cur_c = [p[f].to(torch.int64) for p in chroma]
+            K = torch.nn.functional.pad(k, (0, w % 2, 0, h % 2)).view(n, (h + 1) // 2, 2, (w + 1) // 2, 2).sum(dim=(2, 4))
+            K = K * A if fade is None else (K * A + 128) >> 8
+            cur_c = [value(p[f]) for p in chroma]
         for i in _range(n):                                                                # column order is part of the rule
             cur = [(p * (1024 - wgt[i]) + comp[i, c] * wgt[i] + 512) >> 10 for c, p in enumerate(cur)]
             if yuv:
                 cur_c = [(p * (4096 - K[i]) + comp[i, 1 + c] * K[i] + 2048) >> 12 for c, p in enumerate(cur_c)]
         for p, v in zip(full, cur):
-            p[f] = v.to(torch.uint8)
+            put(p, f, v, (wgt > 0).any(dim=0))
         if yuv:
             for p, v in zip(chroma, cur_c):
-                p[f] = v.to(torch.uint8)
+                put(p, f, v, (K > 0).any(dim=0))
+    planes = [p.view(t) for p, t in zip(planes, dtypes)]
     return planes[0] if len(planes) == 1 else planes
 
 
 def draw_tracks(planes, fmt, trajs, vis=None, colors=None, ids=None, size=None, first=0, trail=16, width=2.0, dot=3.0, alpha=1.0,
-                alpha_occ=0.35, vis_thr=0.5, matrix="bt709", range="limited", inplace=False):
+                alpha_occ=0.35, vis_thr=0.5, matrix="bt709", range="limited", inplace=False, fade=None):
     """Tracks drawn onto frames on the device, one ``pips_tracks_draw`` call (``ops.draw_tracks``; include/pips_hip.h has the rule):
     lines along the last ``trail`` rows with a dot at the head, as the reference's demos end (chain_demo.py:92-108).  ``planes`` /
     ``fmt`` are F surfaces in one of ``ops.import_frames``' six 8-bit layouts, or ``fmt="planar8"`` with one (F,3,h,w) uint8 tensor
@@ -1616,13 +1682,20 @@ def draw_tracks(planes, fmt, trajs, vis=None, colors=None, ids=None, size=None, 
     ``vis_thr`` (a probability; ``vis=None``: all visible).  ``colors`` (n,3) uint8 RGB, default ``track_colors(ids)``
     (``track_colors(arange(n))`` without ``ids``); ``matrix`` / ``range`` as for import.  ``inplace=False`` draws on clones and
     returns them (a tensor for one plane, a list otherwise); ``inplace=True`` draws on the given tensors -- pitched views included
-    -- and returns them.  Later columns are drawn over earlier ones."""
+    -- and returns them.  Later columns are drawn over earlier ones.  ``fmt`` "p010" / "i010" draws on the decoder's 10-bit
+    surfaces (uint16 or int16 planes of ``import_frames``' shapes).  ``fade``: None for one opacity from head to tail, "linear" for
+    a trail that fades towards nothing with age (factor (trail - a) / trail on the segment of age a, the one that ends on the head
+    being age 0), or ``trail`` factors in 0..1 by age; the head's dot is never faded.  A 10-bit format or a fade goes through
+    ``pips_tracks_draw_ex``."""
     planes, trajs, vis, colors, line8, dot8, a_vis, a_occ, vis_logit = _draw_setup(planes, trajs, vis, colors, ids, width, dot, alpha,
                                                                                   alpha_occ, vis_thr)
     trail, first = _whole(trail, "trail", 0), _whole(first, "first", 0)
+    if not 0 <= trail <= ops.DRAW_TRAIL_MAX:
+        raise ValueError(f"trail must lie in 0..{ops.DRAW_TRAIL_MAX}, not {trail}")
+    fade = _draw_fade(fade, trail)
     if not inplace:
         planes = [p.clone() for p in planes]
-    ops.draw_tracks(planes, fmt, trajs, vis, colors, first, size, trail, line8, dot8, a_vis, a_occ, vis_logit, matrix, range)
+    ops.draw_tracks(planes, fmt, trajs, vis, colors, first, size, trail, line8, dot8, a_vis, a_occ, vis_logit, matrix, range, fade=fade)
     return planes[0] if len(planes) == 1 else planes
 
 
@@ -1637,12 +1710,13 @@ class TrackPainter:
     painting push by push gives the bytes of one ``draw_tracks`` call over the whole video (trajs by identity, NaN outside each
     life, ``colors=track_colors(arange(K))``).  An identity it has not seen gets NaN history, one that is no longer among ``ids`` is
     dropped; ``ids=None`` means the columns are stable (their number may not change).  ``size`` is the model's (H, W); ``style`` are
-    ``draw_tracks``' width, dot, alpha, alpha_occ, vis_thr, matrix and range.
+    ``draw_tracks``' width, dot, alpha, alpha_occ, vis_thr, matrix and range; ``fade`` is ``draw_tracks``' (None, "linear" or
+    ``trail`` factors in 0..1).
     The painter does not hold frames.  A push returns rows of frames it was given EARLIER (a frame is returned once every query is
     past it), so the caller keeps its surfaces -- a decoder's pool, a ring of NV12 buffers -- until their rows come back, paints
     them then and hands them on.  ``engine="torch"`` paints with ``draw_tracks_torch`` (any device) instead of the library."""
 
-    def __init__(self, size, trail=16, engine="library", **style):
+    def __init__(self, size, trail=16, engine="library", fade=None, **style):
         self.size = (int(size[0]), int(size[1]))
         self.trail = _whole(trail, "trail", 0)
         if self.trail > ops.DRAW_TRAIL_MAX:
@@ -1652,7 +1726,8 @@ class TrackPainter:
         unknown = set(style) - {"width", "dot", "alpha", "alpha_occ", "vis_thr", "matrix", "range"}
         if unknown:
             raise ValueError(f"unknown style arguments {sorted(unknown)}")
-        self.engine, self.style = engine, style
+        _draw_fade(fade, self.trail)                                  # (a ValueError here, not at the first paint)
+        self.engine, self.style, self.fade = engine, style, fade
         self.ids, self.rows, self.T = None, None, None              # the columns of ``rows`` (trail,n,2), the next frame
 
     @torch.no_grad()
@@ -1683,7 +1758,7 @@ class TrackPainter:
         all_vis = None if vis is None else torch.cat([vis.new_zeros(1, self.trail, n).to(torch.float32), vis.to(torch.float32)], dim=1)
         draw = draw_tracks if self.engine == "library" else draw_tracks_torch
         out = draw(planes, fmt, rows.unsqueeze(0), all_vis, ids=ids, size=self.size, first=self.trail, trail=self.trail,
-                   inplace=inplace, **self.style)
+                   inplace=inplace, fade=self.fade, **self.style)
         self.rows, self.ids, self.T = rows[rows.shape[0] - self.trail:], ids, int(f0) + m
         return out
 

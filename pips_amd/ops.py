@@ -245,15 +245,16 @@ def import_frames(planes, fmt, size=None, matrix="bt709", range="limited", dtype
 
 # include/pips_hip.h: the formats pips_tracks_draw takes, PIPS_DRAW_*
 DRAW_FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4, "i420": 5, "planar8": 8}
+DRAW_FORMATS_EX = dict(DRAW_FORMATS, p010=6, i010=7)                  # pips_tracks_draw_ex takes the two 16-bit formats too
 DRAW_DIM_MAX, DRAW_TRAIL_MAX, DRAW_RADIUS8_MAX, DRAW_JUMP8_MAX = 8192, 32, 128, 2047
 
 
 def draw_planes(planes, fmt):
-    """The checks on the surfaces that ``draw_tracks`` and ``drivers.draw_tracks_torch`` share: ``import_planes``' for the six 8-bit
-    decoder formats, and for "planar8" one uint8 tensor (F,3,h,w) -- the frames ``import_frames`` returns -> (list of planes, F, h,
-    w).  ValueError otherwise (the 10-bit formats are not drawn on)."""
-    if fmt not in DRAW_FORMATS:
-        raise ValueError(f"fmt must be one of {sorted(DRAW_FORMATS)}, not {fmt!r}")
+    """The checks on the surfaces that ``draw_tracks`` and ``drivers.draw_tracks_torch`` share: ``import_planes``' for the eight
+    decoder formats ("p010" and "i010" as uint16 or int16 planes, which come back as int16 views), and for "planar8" one uint8
+    tensor (F,3,h,w) -- the frames ``import_frames`` returns -> (list of planes, F, h, w).  ValueError otherwise."""
+    if fmt not in DRAW_FORMATS_EX:
+        raise ValueError(f"fmt must be one of {sorted(DRAW_FORMATS_EX)}, not {fmt!r}")
     if fmt != "planar8":
         return import_planes(planes, fmt)
     planes = [planes] if torch.is_tensor(planes) else list(planes)
@@ -268,8 +269,23 @@ def draw_planes(planes, fmt):
     return planes, int(F), int(h), int(w)
 
 
+def draw_fade(fade, trail):
+    """``fade`` of ``draw_tracks``: None, or a sequence of ``trail`` whole numbers in 0..256 -> None or the list of ints.  ValueError
+    otherwise."""
+    if fade is None:
+        return None
+    fade = fade.tolist() if torch.is_tensor(fade) else list(fade)
+    if len(fade) != trail:
+        raise ValueError(f"fade must have trail = {trail} entries, not {len(fade)}")
+    for v in fade:
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 256:
+            raise ValueError(f"a fade entry must be a whole number in 0..256, not {v!r}")
+    return [int(v) for v in fade]
+
+
 def draw_check(planes, fmt, trajs, vis, colors, first, src_size, trail, line8, dot8, alpha_vis, alpha_occ, matrix, range):
-    """pips_tracks_draw's limits on the values, shared by ``draw_tracks`` and the twin -> (planes, F, h, w, G, n, src_h, src_w)"""
+    """pips_tracks_draw_ex's limits on the values (but for the fade table: ``draw_fade``), shared by ``draw_tracks`` and the twin ->
+    (planes, F, h, w, G, n, src_h, src_w)"""
     planes, F, h, w = draw_planes(planes, fmt)
     if matrix not in IMPORT_MATRICES or range not in IMPORT_RANGES:
         raise ValueError(f"matrix must be one of {sorted(IMPORT_MATRICES)} and range one of {sorted(IMPORT_RANGES)}, "
@@ -318,18 +334,43 @@ def draw_workspace_bytes(F, n, trail):
     return int(_lib.load().pips_draw_workspace_bytes(int(F), int(n), int(trail)))
 
 
+def draw_surfaces(planes, fmt):
+    """the planes of ``draw_planes`` as the nine surface arguments of pips_tracks_draw: (pointer, pitch, step) per plane, in bytes.
+    ValueError for a plane whose strides cannot be pitch and step (the planes may live on any device: nothing is read)"""
+    size = planes[0].element_size()
+    if fmt == "planar8":
+        p = planes[0]
+        pitch, step = _surface(p[:, 0], (1,))                                     # the three planes share pitch and step
+        if p.stride(1) < pitch * p.shape[2]:
+            raise ValueError(f"a surface of shape {tuple(p.shape)} and strides {tuple(p.stride())} cannot be drawn on in place")
+        args = []
+        for k in (0, 1, 2):
+            args += [C.c_void_p(p.data_ptr() + k * p.stride(1)), pitch, step]
+        return args
+    semi = [(1,), (2, 1)]
+    inner = {"nv12": semi, "p010": semi, "i420": [(1,)] * 3, "i010": [(1,)] * 3}.get(fmt) or [(planes[0].shape[3], 1)]
+    args = []
+    for p, tail in zip(planes, inner):
+        pitch, step = _surface(p, tail)
+        args += [_lib.ptr(p), pitch * size, step * size]
+    return args + [None, 0, 0] * (3 - len(planes))
+
+
 def draw_tracks(planes, fmt, trajs, vis, colors, first=0, src_size=None, trail=16, line8=8, dot8=24, alpha_vis=256, alpha_occ=90,
-                vis_logit=0.0, matrix="bt709", range="limited", workspace=None):
+                vis_logit=0.0, matrix="bt709", range="limited", workspace=None, fade=None):
     """pips_tracks_draw: the trails of trajs (G,n,2) float32 (pixels of a ``src_size`` = (src_h, src_w) image, default the
-    surfaces' own size) drawn IN PLACE into the device surfaces ``planes`` of format ``fmt`` -- ``import_frames``' six 8-bit formats
-    and shapes, or "planar8": one (F,3,h,w) uint8 tensor.  Frame k takes row ``first + k``; ``vis`` (G,n) logits or None, ``colors``
-    (n,3) uint8 RGB; radii in eighths of a pixel, alphas 0..256 (include/pips_hip.h has the whole rule).  Row and frame strides go
-    through as pitch and step: a ``surface[:, :h, :w]`` view of a pitched allocation is drawn on as it is; a plane whose strides
-    cannot be expressed so is a ValueError.  ``workspace``: a device tensor of at least ``draw_workspace_bytes(F, n, trail)`` bytes
-    to use instead of a fresh one."""
+    surfaces' own size) drawn IN PLACE into the device surfaces ``planes`` of format ``fmt`` -- ``import_frames``' formats and
+    shapes ("p010" and "i010" as uint16 or int16 planes), or "planar8": one (F,3,h,w) uint8 tensor.  Frame k takes row
+    ``first + k``; ``vis`` (G,n) logits or None, ``colors`` (n,3) uint8 RGB; radii in eighths of a pixel, alphas 0..256
+    (include/pips_hip.h has the whole rule).  ``fade``: None, or ``trail`` ints 0..256, the factor on the opacity of the segment of
+    each age (0: the one that ends on the head).  A 16-bit format or a fade goes to pips_tracks_draw_ex, every other call to
+    pips_tracks_draw.  Row and frame strides go through as pitch and step: a ``surface[:, :h, :w]`` view of a pitched allocation is
+    drawn on as it is; a plane whose strides cannot be expressed so is a ValueError.  ``workspace``: a device tensor of at least
+    ``draw_workspace_bytes(F, n, trail)`` bytes to use instead of a fresh one."""
     trail, line8, dot8, alpha_vis, alpha_occ, first = (int(v) for v in (trail, line8, dot8, alpha_vis, alpha_occ, first))
     planes, F, h, w, G, n, src_h, src_w = draw_check(planes, fmt, trajs, vis, colors, first, src_size, trail, line8, dot8, alpha_vis,
                                                      alpha_occ, matrix, range)
+    fade = draw_fade(fade, trail)
     assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
     dev = planes[0].device
     for t in (trajs, vis, colors, workspace):
@@ -337,31 +378,21 @@ def draw_tracks(planes, fmt, trajs, vis, colors, first=0, src_size=None, trail=1
             raise ValueError("trajs, vis, colors and the workspace must live on the surfaces' device")
     if F == 0 or n == 0:
         return
-    if fmt == "planar8":
-        p = planes[0]
-        pitch, step = _surface(p[:, 0], (1,))                                     # the three planes share pitch and step
-        if p.stride(1) < pitch * h:
-            raise ValueError(f"a surface of shape {tuple(p.shape)} and strides {tuple(p.stride())} cannot be drawn on in place")
-        args = []
-        for k in (0, 1, 2):
-            args += [C.c_void_p(p.data_ptr() + k * p.stride(1)), pitch, step]
-    else:
-        inner = {"nv12": [(1,), (2, 1)], "i420": [(1,)] * 3}.get(fmt) or [(planes[0].shape[3], 1)]
-        args = []
-        for p, tail in zip(planes, inner):
-            pitch, step = _surface(p, tail)
-            args += [_lib.ptr(p), pitch, step]
-        args += [None, 0, 0] * (3 - len(planes))
+    args = draw_surfaces(planes, fmt)
     trajs, colors = trajs.contiguous(), colors.contiguous()
     vis = None if vis is None else vis.contiguous()
     need = draw_workspace_bytes(F, n, trail)
     if workspace is None:
         workspace = torch.empty(need // 4, dtype=torch.int32, device=dev)
     nbytes = workspace.numel() * workspace.element_size()
+    head = (DRAW_FORMATS_EX[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], F, h, w, *args, _lib.ptr(trajs), _lib.ptr(vis), G, n,
+            first, src_h, src_w, _lib.ptr(colors), trail, line8, dot8, alpha_vis, alpha_occ, float(vis_logit))
     with torch.cuda.device(dev):
-        _call("pips_tracks_draw", DRAW_FORMATS[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], F, h, w, *args, _lib.ptr(trajs),
-              _lib.ptr(vis), G, n, first, src_h, src_w, _lib.ptr(colors), trail, line8, dot8, alpha_vis, alpha_occ, float(vis_logit),
-              _lib.ptr(workspace), nbytes, _stream())
+        if fmt in IMPORT_16BIT or fade is not None:
+            table = None if fade is None else (C.c_int * max(trail, 1))(*fade)      # a host array: read before the launch
+            _call("pips_tracks_draw_ex", *head, table, _lib.ptr(workspace), nbytes, _stream())
+        else:
+            _call("pips_tracks_draw", *head, _lib.ptr(workspace), nbytes, _stream())
 
 
 def point_sample(level0, B, xy):
