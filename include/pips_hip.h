@@ -117,7 +117,8 @@ const char* pips_last_error(void);
  * pips_conv_nhwc_f32_r and pips_encoder_l1_fused (the LDS-resident 64 -> 64 convolution of the fp32 encoder's layer 1 and whether
  * the encoder takes it); pips_inorm_apply_f32 (pips_inorm_apply on fp32 maps with mode 3 beside modes 0..2);
  * pips_tracks_draw_ex (pips_tracks_draw with the 10-bit surfaces P010 and I010 and a fade table: trails whose opacity falls with
- * age; pips_draw_workspace_bytes sizes both at the same figure). */
+ * age; pips_draw_workspace_bytes sizes both at the same figure); pips_motion_fit and pips_motion_workspace_bytes (the camera motion
+ * between consecutive rows of a trajectory tensor: an exact consensus similarity). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -853,6 +854,60 @@ int    pips_tracks_draw_ex(int format, int matrix, int range, int F, int h, int 
                            const float* trajs, const float* vis, int G, int n, int first, int src_h, int src_w,
                            const uint8_t* colors, int trail, int line8, int dot8, int alpha_vis, int alpha_occ, float vis_logit,
                            const int* fade, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Motion: pips_motion_fit fits, for every pair of consecutive rows of trajs (F,n,2) float32 (pixel positions; vis (F,n) logits or
+ * NULL), a robust 2-D similarity q = a p + t (a complex: rotation and uniform scale; t the shift) from the positions p of row f - 1
+ * to the positions q of row f, 1 <= f < F: the frame-to-frame camera motion a stabiliser, an ego-motion estimate or a moving-object
+ * mask starts from.  The consensus is decided in integers, 2-vectors read as complex numbers:
+ *  - quantisation: s = 4 x in fp32 (exact) is the position in quarter pixels.  A row's point is USABLE when both components are
+ *    finite with |s| <= PIPS_MOTION_QUARTER_MAX (8191: |x| <= 2047.75); its quantised value is rint(s), round-half-even;
+ *  - valid columns: column k is VALID for pair f when it is usable in rows f - 1 and f and, with vis, vis > vis_logit holds in both
+ *    rows (a NaN is not above the threshold).  The valid columns in ascending column order are the list 0..m-1;
+ *  - hypotheses: K of them, 1 <= K <= PIPS_MOTION_HYPS_MAX.  Hypothesis h uses the list entries i = (mix(2h) m) >> 32 and
+ *    j = (mix(2h + 1) (m - 1)) >> 32, then j += (j >= i) (64-bit products of 32-bit values).  mix(k), in 32-bit wrap-around
+ *    arithmetic: u = seed + 0x9E3779B9 (g + 1) + 0x85EBCA6B (k + 1); u ^= u >> 16; u *= 0x85EBCA6B; u ^= u >> 13; u *= 0xC2B2AE35;
+ *    u ^= u >> 16, with seed the 32 bits of the `seed` argument and g = frame0 + f the absolute frame index: a stream fed push by
+ *    push draws the hypotheses of the whole video;
+ *  - inlier test: d = p_j - p_i, e = q_j - q_i, r = e (p_k - p_i) - d (q_k - q_i) (complex products).  Column k is an inlier of h
+ *    iff d != 0 and |r|^2 <= thr4^2 |d|^2, thr4 the threshold in quarter pixels, 1..PIPS_MOTION_THR4_MAX.  Every component of r is
+ *    below 2^31 and both sides are below 2^62: the products of differences fit 32 bits, the two squares and the right side need 64;
+ *  - selection: the score of h is its inlier count; the best hypothesis has the highest score, ties go to the lowest h.  With
+ *    m < 2 or a best score below 2 the pair has NO MODEL.
+ * Outputs, one row per pair (row f - 1 for pair f):
+ *  - head int32[4] = (m, n_in, h_best or -1, 0);
+ *  - flags uint8[n]: 0 not valid, 1 valid but outside the consensus, 2 inlier;
+ *  - sums int64[8] over the inliers: n_in, S px, S py, S qx, S qy, S |p|^2, S (px qx + py qy), S (px qy - py qx) in quarter pixels
+ *    (exact for n <= PIPS_MOTION_N_MAX); zeros without a model;
+ *  - model float64[4] = (a_re, a_im, tx, ty), the least-squares similarity on the inliers, in pixels.  In int64, all below 2^61:
+ *      D = n_in S|p|^2 - ((S px)^2 + (S py)^2),  A = n_in Sdot - (S px S qx + S py S qy),  B = n_in Scross - (S px S qy - S py S qx);
+ *    then in fp64, D, A, B, the four sums and 4 n_in converted first (each rounded to nearest), one rounding per operation in this
+ *    order, never fused:
+ *      a_re = A / D,  a_im = B / D,  tx = (S qx - (a_re S px - a_im S py)) / (4 n_in),  ty = (S qy - (a_im S px + a_re S py)) / (4 n_in).
+ *    (1, 0, 0, 0) without a model.  The model is not re-scored: the inliers are those of the winning two-point hypothesis.
+ * drivers.motion_table_torch is the same rule in int64 / float64 torch ops: every output is compared bit for bit.
+ * Three launches on `stream`: a 256-thread block per pair quantises the valid columns and stores them in column order (four int16
+ * each; a wave ballot and a prefix over the waves, no atomics); a block per (pair, 64 hypotheses) scores them -- a lane owns a
+ * hypothesis, the points pass through LDS in tiles of 2048 (n is not limited by LDS) and the block stores its best (score, h) with
+ * a plain store; a block per pair picks the winner, tests every column against it and writes flags, sums, head and model.  No
+ * atomics, no allocation, no synchronisation; the workspace is read and written by this call only.
+ * pips_motion_workspace_bytes(F, n, K) = (F - 1) (8 n + 4 (1 + ceil(K / 64))); 0 for F <= 1, n <= 0 or arguments pips_motion_fit
+ * rejects.  PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "motion_fit:": F < 0 or >
+ * PIPS_MOTION_ROWS_MAX; n < 0 or > PIPS_MOTION_N_MAX; K outside 1..PIPS_MOTION_HYPS_MAX; thr4 outside 1..PIPS_MOTION_THR4_MAX;
+ * frame0 < 0 or frame0 + F > INT_MAX; a NaN vis_logit; with F > 1 a NULL head, sums or model; with F > 1 and n > 0 a NULL trajs,
+ * flags or workspace or a workspace off a 16-byte address.  PIPS_E_WORKSPACE: workspace_bytes < pips_motion_workspace_bytes(F, n, K).
+ * F <= 1 launches nothing, writes nothing and returns PIPS_OK.  n == 0 with F > 1 needs no workspace and runs the last launch alone:
+ * every head row is (0, 0, -1, 0), sums are zeros and the model is the identity.
+ * Known limits: a similarity only (no affine, no homography, no rolling shutter); no re-scoring after the refit; the frames are
+ * not warped and the cover step does not use the result. */
+#define PIPS_MOTION_QUARTER_MAX 8191
+#define PIPS_MOTION_HYPS_MAX    1024
+#define PIPS_MOTION_THR4_MAX    1024
+#define PIPS_MOTION_N_MAX       65536
+#define PIPS_MOTION_ROWS_MAX    (1 << 24)
+size_t pips_motion_workspace_bytes(int F, int n, int K);
+int    pips_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, int seed,
+                       int32_t* head, int64_t* sums, double* model, uint8_t* flags, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128).  PIPS_E_ARG ahead of the launch for a

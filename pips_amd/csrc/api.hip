@@ -2093,6 +2093,39 @@ int pips_tracks_draw_ex(int format, int matrix, int range, int F, int h, int w, 
                            workspace, workspace_bytes, stream);
 }
 
+// ---- motion
+static bool motion_shape_ok(int F, int n, int K) {
+    return F >= 0 && F <= PIPS_MOTION_ROWS_MAX && n >= 0 && n <= PIPS_MOTION_N_MAX && K >= 1 && K <= PIPS_MOTION_HYPS_MAX;
+}
+size_t pips_motion_workspace_bytes(int F, int n, int K) {
+    if (!motion_shape_ok(F, n, K) || F <= 1 || n == 0) return 0;
+    return motion_workspace_bytes(F, n, K);
+}
+int pips_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, int seed,
+                    int32_t* head, int64_t* sums, double* model, uint8_t* flags, void* workspace, size_t workspace_bytes, void* stream) {
+    PIPS_CHECK_ARG(F >= 0 && F <= PIPS_MOTION_ROWS_MAX, "motion_fit: need 0 <= F <= %d (F=%d)", PIPS_MOTION_ROWS_MAX, F);
+    PIPS_CHECK_ARG(n >= 0 && n <= PIPS_MOTION_N_MAX, "motion_fit: need 0 <= n <= %d (n=%d): the sums are exact up to there",
+                   PIPS_MOTION_N_MAX, n);
+    PIPS_CHECK_ARG(K >= 1 && K <= PIPS_MOTION_HYPS_MAX, "motion_fit: K=%d hypotheses outside 1..%d", K, PIPS_MOTION_HYPS_MAX);
+    PIPS_CHECK_ARG(thr4 >= 1 && thr4 <= PIPS_MOTION_THR4_MAX, "motion_fit: thr4=%d quarter pixels outside 1..%d", thr4,
+                   PIPS_MOTION_THR4_MAX);
+    PIPS_CHECK_ARG(frame0 >= 0 && frame0 <= INT_MAX - F, "motion_fit: frames [%d, %d + %d) do not fit an int", frame0, frame0, F);
+    PIPS_CHECK_ARG(vis_logit == vis_logit, "motion_fit: vis_logit is a NaN");
+    if (F <= 1) return PIPS_OK;
+    PIPS_CHECK_ARG(head && sums && model, "motion_fit: null head, sums or model");
+    if (n > 0) {
+        PIPS_CHECK_ARG(trajs && flags && workspace, "motion_fit: null trajs, flags or workspace");
+        PIPS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "motion_fit: the workspace must lie on a 16-byte address");
+        const size_t need = pips_motion_workspace_bytes(F, n, K);
+        if (workspace_bytes < need) {
+            set_error("motion_fit: workspace %zu < %zu bytes", workspace_bytes, need);
+            return PIPS_E_WORKSPACE;
+        }
+    }
+    return launch_motion_fit(trajs, vis, F, n, frame0, vis_logit, K, thr4, (unsigned)seed, (int*)head, (long long*)sums, model,
+                             (unsigned char*)flags, workspace, (hipStream_t)stream);
+}
+
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;

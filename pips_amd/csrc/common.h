@@ -561,4 +561,17 @@ int launch_tracks_draw(int format, int matrix, int range, int F, int h, int w, v
                        const float* trajs, const float* vis, int n, int first, int src_h, int src_w, const unsigned char* colors,
                        const DrawStyle& style, const int* fade, int* workspace, hipStream_t st);
 
+// ---- motion.hip: the consensus similarity between consecutive rows of a trajectory tensor (pips_motion_fit).  The workspace holds,
+// for each of the F - 1 pairs, the quantised valid columns in column order (n slots of four int16), their number, and the best
+// (score, hypothesis) key of each block of MOTION_HYPS hypotheses; arguments checked by the caller (the workspace on a 16-byte
+// address).  n == 0: the workspace is not touched and only the second small launch runs (the rows of a pair without a model).
+constexpr int MOTION_HYPS = 64;                                                    // hypotheses of one scoring block: a lane each
+constexpr int MOTION_TILE = 2048;                                                  // points in LDS at a time (ops.MOTION_TILE)
+__host__ __device__ inline int motion_blocks(int K) { return (K + MOTION_HYPS - 1) / MOTION_HYPS; }
+inline size_t motion_workspace_bytes(int F, int n, int K) {
+    return ((size_t)F - 1) * ((size_t)n * 8 + 4 * ((size_t)1 + motion_blocks(K)));
+}
+int launch_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, unsigned seed,
+                      int* head, long long* sums, double* model, unsigned char* flags, void* workspace, hipStream_t st);
+
 }  // namespace pips

@@ -23,4 +23,20 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
     return a - b;
 }
 
+// the same in fp64 (the least-squares similarity of pips_motion_fit and its torch twin); a quotient is never fused
+__device__ __forceinline__ double mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+__device__ __forceinline__ double add_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+__device__ __forceinline__ double sub_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 }  // namespace pips

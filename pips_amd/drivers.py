@@ -32,6 +32,10 @@
   with age (``fade=``) by ``pips_tracks_draw_ex``; the second is the same integer rule in torch ops, byte for byte; ``TrackPainter``
   paints the pushes of a streamed tracker one by one, keeping the last rows by identity; ``track_colors``
   gives each identity its colour.
+* ``motion_fit`` / ``motion_fit_torch`` / ``MotionEstimator`` / ``motion_path`` -- what the tracks mean together: the frame-to-frame
+  camera motion as a consensus similarity between consecutive rows, by one ``pips_motion_fit`` call; the second is the same exact
+  rule in torch ops, equal in every bit; ``MotionEstimator`` fits the pushes of a streamed tracker one by one, keeping the last row
+  by identity; ``motion_path`` composes the pairs into frame -> frame-0 transforms.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -1761,6 +1765,266 @@ class TrackPainter:
                    inplace=inplace, fade=self.fade, **self.style)
         self.rows, self.ids, self.T = rows[rows.shape[0] - self.trail:], ids, int(f0) + m
         return out
+
+
+# ---------------------------------------------------------------------------------------------- global motion from tracks
+_M32 = 0xFFFFFFFF
+
+
+def _mul32(u, c):
+    """(u c) mod 2^32 for an int64 tensor 0 <= u < 2^32 and a constant 0 <= c < 2^32; no intermediate passes 2^49"""
+    return ((u & 0xFFFF) * c + ((((u >> 16) * c) & 0xFFFF) << 16)) & _M32
+
+
+def motion_mix(seed, g, k):
+    """pips_motion_fit's mix(k) of frame g (include/pips_hip.h), k an int64 tensor (or an int) -> int64 tensor of 32-bit words"""
+    k = torch.as_tensor(k, dtype=torch.int64)
+    c0 = (int(seed) + 0x9E3779B9 * (int(g) + 1)) & _M32
+    u = (c0 + _mul32((k + 1) & _M32, 0x85EBCA6B)) & _M32
+    u = u ^ (u >> 16)
+    u = _mul32(u, 0x85EBCA6B)
+    u = u ^ (u >> 13)
+    u = _mul32(u, 0xC2B2AE35)
+    return u ^ (u >> 16)
+
+
+def _motion_inliers(p, q, pi, qi, d, e, thr4):
+    """the rule's inlier test of the points p, q (m,2) against the hypotheses (c,2) each of pi, qi, d, e -> (c,m) bool; int64"""
+    a, b = p.unsqueeze(0) - pi.unsqueeze(1), q.unsqueeze(0) - qi.unsqueeze(1)                    # (c,m,2)
+    ex, ey, dx, dy = (v.unsqueeze(1) for v in (e[:, 0], e[:, 1], d[:, 0], d[:, 1]))
+    rre = (ex * a[..., 0] - ey * a[..., 1]) - (dx * b[..., 0] - dy * b[..., 1])
+    rim = (ex * a[..., 1] + ey * a[..., 0]) - (dx * b[..., 1] + dy * b[..., 0])
+    return (rre * rre + rim * rim <= (thr4 * thr4) * (dx * dx + dy * dy)) & ((dx != 0) | (dy != 0))
+
+
+def motion_table_torch(trajs, vis, frame0, vis_logit, K, thr4, seed):
+    """pips_motion_fit (include/pips_hip.h) as int64 / float64 torch ops, on any device: rows trajs (F,n,2) and vis (F,n) logits or
+    None -> (head (P,4) int64, sums (P,8) int64, model (P,4) float64, flags (P,n) uint8) for the P = max(F - 1, 0) pairs of
+    consecutive rows.  Integers up to the sums, then one float64 operation per rounding of the rule: equal to the kernels' in
+    every bit."""
+    if trajs.dim() != 3 or trajs.shape[2] != 2:
+        raise ValueError(f"trajs must be (F,n,2), not {tuple(trajs.shape)}")
+    F, n = trajs.shape[:2]
+    if vis is not None and tuple(vis.shape) != (F, n):
+        raise ValueError(f"vis must be (F,n) = {(F, n)}, not {tuple(vis.shape)}")
+    K, thr4, frame0, seed = int(K), int(thr4), int(frame0), int(seed)
+    if n > ops.MOTION_N_MAX:
+        raise ValueError(f"{n} columns: the sums are exact up to {ops.MOTION_N_MAX}")
+    if not 1 <= K <= ops.MOTION_HYPS_MAX or not 1 <= thr4 <= ops.MOTION_THR4_MAX:
+        raise ValueError(f"need 1 <= K <= {ops.MOTION_HYPS_MAX} and 1 <= thr4 <= {ops.MOTION_THR4_MAX} (K={K}, thr4={thr4})")
+    if frame0 < 0 or frame0 + F > _INT_MAX or not 0 <= seed <= _M32:
+        raise ValueError(f"frame0 + F must fit an int32 and seed a uint32 (frame0={frame0}, seed={seed})")
+    dev, I64, P = trajs.device, torch.int64, max(F - 1, 0)
+    s = trajs.to(torch.float32) * 4.0                                                            # exact
+    usable = (s.abs() <= float(ops.MOTION_QUARTER_MAX)).all(dim=2)                               # (a NaN compares false)
+    quarter = torch.where(usable.unsqueeze(2), s, torch.zeros_like(s)).round().to(I64)           # round-half-even
+    if vis is not None:
+        usable = usable & (vis.to(dev, torch.float32) > float(vis_logit))
+    head = torch.zeros(P, 4, dtype=I64, device=dev)
+    sums = torch.zeros(P, 8, dtype=I64, device=dev)
+    flags = torch.zeros(P, n, dtype=torch.uint8, device=dev)
+    hyp = torch.arange(K, device=dev)
+    for f in range(1, F):
+        ok = usable[f - 1] & usable[f]
+        cols = torch.nonzero(ok).squeeze(1)
+        m = int(cols.numel())
+        flags[f - 1] = ok.to(torch.uint8)
+        head[f - 1, 0], head[f - 1, 2] = m, -1
+        if m < 2:
+            continue
+        p, q = quarter[f - 1][cols], quarter[f][cols]
+        i = (motion_mix(seed, frame0 + f, 2 * hyp) * m) >> 32
+        j = (motion_mix(seed, frame0 + f, 2 * hyp + 1) * (m - 1)) >> 32
+        j = j + (j >= i).to(I64)
+        d, e = p[j] - p[i], q[j] - q[i]
+        step = max(1, (1 << 22) // m)                                                            # hypotheses at a time
+        score = torch.cat([_motion_inliers(p, q, p[i[a:a + step]], q[i[a:a + step]], d[a:a + step], e[a:a + step], thr4).sum(dim=1)
+                           for a in range(0, K, step)])
+        best = int(score.max())
+        if best < 2:
+            continue
+        h = int(torch.nonzero(score == best)[0, 0])                                              # ties: the lowest h
+        inl = _motion_inliers(p, q, p[i[h:h + 1]], q[i[h:h + 1]], d[h:h + 1], e[h:h + 1], thr4)[0]
+        p, q = p[inl], q[inl]
+        flags[f - 1, cols[inl]] = 2
+        head[f - 1, 1], head[f - 1, 2] = best, h
+        sums[f - 1] = torch.stack([inl.sum(), p[:, 0].sum(), p[:, 1].sum(), q[:, 0].sum(), q[:, 1].sum(), (p * p).sum(),
+                                   (p * q).sum(), (p[:, 0] * q[:, 1] - p[:, 1] * q[:, 0]).sum()])
+    # the least-squares similarity on the inliers: int64 up to D, A, B, then float64, an operation a line
+    N, spx, spy, sqx, sqy, spp, sdot, scross = sums.unbind(dim=1)
+    have = head[:, 2] >= 0
+    F64 = torch.float64
+    D = torch.where(have, N * spp - (spx * spx + spy * spy), torch.ones_like(N)).to(F64)
+    A = (N * sdot - (spx * sqx + spy * sqy)).to(F64)
+    B = (N * scross - (spx * sqy - spy * sqx)).to(F64)
+    n4 = torch.where(have, 4 * N, torch.ones_like(N)).to(F64)
+    spx, spy, sqx, sqy = spx.to(F64), spy.to(F64), sqx.to(F64), sqy.to(F64)
+    are, aim = A / D, B / D
+    tx = are * spx
+    tx = tx - aim * spy
+    tx = (sqx - tx) / n4
+    ty = aim * spx
+    ty = ty + are * spy
+    ty = (sqy - ty) / n4
+    one, zero = torch.ones_like(are), torch.zeros_like(are)
+    model = torch.stack([torch.where(have, are, one), torch.where(have, aim, zero), torch.where(have, tx, zero),
+                         torch.where(have, ty, zero)], dim=1)
+    return head, sums, model, flags
+
+
+MOTION_ENGINES = ("library", "torch")
+_MOTION_PARAMS = ("thr", "hypotheses", "vis_thr", "seed")
+
+
+def _motion_setup(trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed):
+    """what ``motion_fit`` and ``motion_fit_torch`` make of their arguments -> (rows (F,n,2), vis (F,n) or None, order or None,
+    the rule's integers (frame0, vis_logit, K, thr4, seed)); with ``ids`` the columns are put in ascending id order (``order``)"""
+    if trajs.dim() != 4 or trajs.shape[0] != 1 or trajs.shape[3] != 2:
+        raise ValueError(f"trajs must be (1,F,n,2), not {tuple(trajs.shape)}")
+    rows = trajs[0].to(torch.float32)
+    F, n = rows.shape[:2]
+    if vis is not None:
+        if tuple(vis.shape) != (1, F, n):
+            raise ValueError(f"vis must be (1,F,n) = {(1, F, n)}, not {tuple(vis.shape)}")
+        vis = vis[0].to(rows.device, torch.float32)
+    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.25 <= thr <= ops.MOTION_THR4_MAX / 4 or \
+            float(thr) * 4.0 != int(float(thr) * 4.0):
+        raise ValueError(f"thr must be a multiple of 0.25 px in 0.25..{ops.MOTION_THR4_MAX / 4}, not {thr!r}")
+    K = _whole(hypotheses, "hypotheses", 1)
+    if K > ops.MOTION_HYPS_MAX:
+        raise ValueError(f"hypotheses must lie in 1..{ops.MOTION_HYPS_MAX}, not {hypotheses!r}")
+    if isinstance(vis_thr, bool) or not isinstance(vis_thr, (int, float)) or not 0.0 < vis_thr < 1.0:
+        raise ValueError(f"vis_thr must lie in (0, 1), not {vis_thr!r}")
+    vis_logit = float(torch.logit(torch.tensor(float(vis_thr), dtype=torch.float32)))              # (as Cover: fp32, on the host)
+    order = None
+    if ids is not None:
+        ids = torch.as_tensor(ids).reshape(-1).to(torch.int64).cpu()
+        if ids.numel() != n or torch.unique(ids).numel() != n:
+            raise ValueError(f"ids must name the {n} columns, each once")
+        order = torch.argsort(ids).to(rows.device)
+        rows, vis = rows[:, order], None if vis is None else vis[:, order]
+    return rows, vis, order, (_whole(frame0, "frame0", 0), vis_logit, K, int(float(thr) * 4.0), _whole(seed, "seed", 0))
+
+
+def _motion_result(head, model, flags, order):
+    """the rule's tables -> (models (P,4) float64, inliers (P,n) bool, valid (P,n) bool, counts (P,2) int64 = (m, n_in)), the
+    columns back in the caller's order"""
+    if order is not None:
+        back = torch.empty_like(flags)
+        back[:, order] = flags
+        flags = back
+    return model, flags == 2, flags >= 1, head[:, :2].to(torch.int64)
+
+
+def motion_fit(trajs, vis=None, ids=None, frame0=0, thr=2.0, hypotheses=256, vis_thr=0.5, seed=0):
+    """The camera motion between consecutive frames of a tracker's output, one ``pips_motion_fit`` call (``ops.motion_fit``;
+    include/pips_hip.h has the rule): trajs (1,F,n,2) and vis (1,F,n) logits (or None) on the GPU -> ``models`` (F-1,4) float64 =
+    (a_re, a_im, tx, ty) with q = a p + t taking the positions of frame f - 1 to those of frame f (the identity where a pair has no
+    model), ``inliers`` (F-1,n) bool, ``valid`` (F-1,n) bool and ``counts`` (F-1,2) = (valid columns, inliers).  A column counts
+    in a pair when it has a position within +-2047.75 px in both frames and, with ``vis``, a visibility above ``vis_thr`` (a
+    probability) in both; a track that is valid but no inlier moves on its own.  ``thr`` is the inlier distance in px at the scale
+    of the hypothesis' two points, a multiple of 0.25; ``hypotheses`` two-point samples are scored, drawn from ``seed`` and the
+    absolute frame index ``frame0 + f``.  With ``ids`` (n,) the valid columns are taken in ascending id order, so the result does
+    not depend on where a tracker put its columns."""
+    rows, vis, order, (frame0, vis_logit, K, thr4, seed) = _motion_setup(trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed)
+    head, _, model, flags = ops.motion_fit(rows, vis, frame0, vis_logit, K, thr4, seed)
+    return _motion_result(head, model, flags, order)
+
+
+def motion_fit_torch(trajs, vis=None, ids=None, frame0=0, thr=2.0, hypotheses=256, vis_thr=0.5, seed=0):
+    """``motion_fit`` by ``motion_table_torch``: the same rule as int64 / float64 torch ops on any device, equal in every bit"""
+    rows, vis, order, (frame0, vis_logit, K, thr4, seed) = _motion_setup(trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed)
+    head, _, model, flags = motion_table_torch(rows, vis, frame0, vis_logit, K, thr4, seed)
+    return _motion_result(head, model, flags, order)
+
+
+class MotionEstimator:
+    """The camera motion of a streamed tracker, push by push: ``step(f0, trajs, vis, ids)`` takes the ``(f0, trajs (1,m,n,2), vis
+    (1,m,n)[, ids (n,)])`` of ``StreamTracker.push``, ``CoverTracker.push`` or one stream of ``MultiStreamTracker.push`` and returns
+    the models (float64, four a row) of the pairs that END on the frames ``f0 .. f0 + m - 1`` -- the first push with rows has no pair
+    for its first row.  It keeps the last row BY IDENTITY between calls, so the pair across two pushes is fitted too: stepping push
+    by push gives what one ``motion_fit`` call gives on the whole video laid out by identity (NaN outside each life, ``ids =
+    arange(K)``).  An identity it has not seen has no position in the kept row, one that is no longer among ``ids`` is dropped;
+    ``ids=None`` means the columns are stable (their number may not change).  ``vis`` is given on every step or on none.
+    ``inliers``, ``valid`` and ``counts`` hold ``motion_fit``'s other results for the pairs of the last step, in its column order.
+    ``params`` are ``motion_fit``'s thr, hypotheses, vis_thr and seed; ``engine="torch"`` fits with ``motion_fit_torch`` (any
+    device) instead of the library."""
+
+    def __init__(self, engine="library", **params):
+        if engine not in MOTION_ENGINES:
+            raise ValueError(f"engine must be one of {MOTION_ENGINES}, not {engine!r}")
+        unknown = set(params) - set(_MOTION_PARAMS)
+        if unknown:
+            raise ValueError(f"unknown arguments {sorted(unknown)}")
+        _motion_setup(torch.zeros(1, 0, 0, 2), None, None, 0, **{**dict(thr=2.0, hypotheses=256, vis_thr=0.5, seed=0), **params})
+        self.engine, self.params = engine, params
+        self.ids, self.row, self.vis_row, self.T = None, None, None, None           # the columns of ``row`` (n,2), the next frame
+        self.inliers = self.valid = self.counts = None
+
+    @torch.no_grad()
+    def step(self, f0, trajs, vis=None, ids=None):
+        if trajs.dim() != 4 or trajs.shape[0] != 1 or trajs.shape[3] != 2:
+            raise ValueError(f"trajs must be (1,m,n,2), not {tuple(trajs.shape)}")
+        if self.T is not None and int(f0) != self.T:
+            raise ValueError(f"rows of frame {int(f0)} after frame {self.T - 1}")
+        m, n = trajs.shape[1:3]
+        if vis is not None and tuple(vis.shape) != (1, m, n):
+            raise ValueError(f"vis must be (1,m,n) = {(1, m, n)}, not {tuple(vis.shape)}")
+        if ids is not None:
+            ids = [int(i) for i in torch.as_tensor(ids).reshape(-1).tolist()]
+            if len(ids) != n or len(set(ids)) != n:
+                raise ValueError(f"ids must name the {n} columns, each once")
+        elif self.row is not None and self.row.shape[0] != n:
+            raise ValueError(f"{n} columns after {self.row.shape[0]}: pass ids when the columns change")
+        if self.row is not None and (vis is None) != (self.vis_row is None):
+            raise ValueError("vis must be given on every step or on none")
+        self.T = int(f0) + m
+        if m == 0:
+            return torch.zeros(0, 4, dtype=torch.float64, device=trajs.device)
+        now = trajs[0].to(torch.float32)
+        now_vis = None if vis is None else vis[0].to(now.device, torch.float32)
+        rows, all_vis, frame0 = now, now_vis, int(f0)
+        if self.row is not None:
+            old = torch.full((1, n, 2), float("nan"), dtype=torch.float32, device=now.device)
+            old_vis = None if vis is None else torch.full((1, n), float("nan"), dtype=torch.float32, device=now.device)
+            if n > 0 and self.row.shape[0] > 0:
+                if ids is None or self.ids is None:
+                    old[0] = self.row.to(now.device)
+                    if vis is not None:
+                        old_vis[0] = self.vis_row.to(now.device)
+                else:
+                    col = {i: j for j, i in enumerate(self.ids)}
+                    new = [j for j, i in enumerate(ids) if i in col]
+                    if new:
+                        at, src = torch.tensor(new, device=now.device), torch.tensor([col[ids[j]] for j in new], device=now.device)
+                        old[0, at] = self.row.to(now.device)[src]
+                        if vis is not None:
+                            old_vis[0, at] = self.vis_row.to(now.device)[src]
+            rows, frame0 = torch.cat([old, now]), int(f0) - 1
+            all_vis = None if vis is None else torch.cat([old_vis, now_vis])
+        fit = motion_fit if self.engine == "library" else motion_fit_torch
+        models, self.inliers, self.valid, self.counts = fit(rows.unsqueeze(0), None if all_vis is None else all_vis.unsqueeze(0),
+                                                            ids=ids, frame0=frame0, **self.params)
+        self.row, self.vis_row, self.ids = now[m - 1], None if vis is None else now_vis[m - 1], ids
+        return models
+
+
+def motion_path(models):
+    """Per-pair similarities ``models`` (P,4) = (a_re, a_im, tx, ty), pair f taking frame f - 1 to frame f -> (P+1,4) float64 on
+    the host: row f takes the positions of frame f to those of FRAME 0 (row 0 is the identity) -- the inverses composed,
+    path_f = path_{f-1} o model_f^-1, in complex float64.  Warping frame f by row f holds the camera still."""
+    models = torch.as_tensor(models).to("cpu", torch.float64)
+    if models.dim() != 2 or models.shape[1] != 4:
+        raise ValueError(f"models must be (P,4), not {tuple(models.shape)}")
+    A, T = complex(1.0, 0.0), complex(0.0, 0.0)
+    out = [[1.0, 0.0, 0.0, 0.0]]
+    for a_re, a_im, tx, ty in models.tolist():
+        a, t = complex(a_re, a_im), complex(tx, ty)
+        if a == 0:
+            raise ValueError("a model with a = 0 has no inverse")
+        A, T = A / a, T - (A / a) * t                                              # x_0 = A ((q - t) / a) + T
+        out.append([A.real, A.imag, T.real, T.imag])
+    return torch.tensor(out, dtype=torch.float64)
 
 
 def find_cuts(rgbs, cut_thr=0.5, scan="torch", slice_frames=64):

@@ -906,6 +906,50 @@ def cut_table(frames, prev_hist=None):
     return hist, dist
 
 
+# include/pips_hip.h: PIPS_MOTION_*; MOTION_TILE is csrc/common.h's (the points a scoring block holds in LDS at a time: n may be larger)
+MOTION_QUARTER_MAX, MOTION_HYPS_MAX, MOTION_THR4_MAX, MOTION_N_MAX = 8191, 1024, 1024, 65536
+MOTION_HYPS, MOTION_TILE = 64, 2048
+
+
+def motion_workspace_bytes(F, n, K):
+    return int(_lib.load().pips_motion_workspace_bytes(int(F), int(n), int(K)))
+
+
+def motion_fit(trajs, vis, frame0, vis_logit, K, thr4, seed):
+    """pips_motion_fit on device rows trajs (F,n,2) float32 and vis (F,n) logits or None -> (head (P,4) int32, sums (P,8) int64,
+    model (P,4) float64, flags (P,n) uint8) for the P = max(F - 1, 0) pairs of consecutive rows: the consensus similarity of each
+    pair (include/pips_hip.h has the rule).  Outputs and workspace are allocated here: one call."""
+    assert trajs.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    if trajs.dim() != 3 or trajs.shape[2] != 2:
+        raise ValueError(f"trajs must be (F,n,2), not {tuple(trajs.shape)}")
+    src = _f32(trajs)
+    F, n = src.shape[:2]
+    if vis is not None:
+        if tuple(vis.shape) != (F, n):
+            raise ValueError(f"vis must be (F,n) = {(F, n)}, not {tuple(vis.shape)}")
+        vis = _f32(vis.to(src.device))
+    K, thr4, frame0, seed = int(K), int(thr4), int(frame0), int(seed)
+    if n > MOTION_N_MAX:
+        raise ValueError(f"{n} columns: the sums are exact up to {MOTION_N_MAX}")
+    if not 1 <= K <= MOTION_HYPS_MAX or not 1 <= thr4 <= MOTION_THR4_MAX:
+        raise ValueError(f"need 1 <= K <= {MOTION_HYPS_MAX} and 1 <= thr4 <= {MOTION_THR4_MAX} (K={K}, thr4={thr4})")
+    if frame0 < 0 or frame0 + F > 2 ** 31 - 1 or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"frame0 + F must fit an int32 and seed a uint32 (frame0={frame0}, seed={seed})")
+    P, dev = max(F - 1, 0), src.device
+    head = torch.empty(P, 4, dtype=torch.int32, device=dev)
+    sums = torch.empty(P, 8, dtype=torch.int64, device=dev)
+    model = torch.empty(P, 4, dtype=torch.float64, device=dev)
+    flags = torch.empty(P, n, dtype=torch.uint8, device=dev)
+    if P == 0:                                                                    # (nothing is launched, nothing to write)
+        return head, sums, model, flags
+    nbytes = motion_workspace_bytes(F, n, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _call("pips_motion_fit", _lib.ptr(src) if n else None, _lib.ptr(vis) if n else None, F, n, frame0, float(vis_logit), K, thr4,
+              seed - (1 << 32) if seed >= 1 << 31 else seed, _lib.ptr(head), _lib.ptr(sums), _lib.ptr(model), _lib.ptr(flags) if n else None, _lib.ptr(ws), nbytes, _stream())
+    return head, sums, model, flags
+
+
 def cover_place(seeds, table, h, w, cell, min_corner):
     """pips_cover_place: the seeds (k,3) = (t, x, y) of a cover step, float32 and contiguous, are moved IN PLACE onto the corners
     of ``table`` (gh,gw,3), the table of the seeds' frame, where the cell's score is above ``min_corner`` -> seeds"""
