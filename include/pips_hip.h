@@ -118,7 +118,8 @@ const char* pips_last_error(void);
  * the encoder takes it); pips_inorm_apply_f32 (pips_inorm_apply on fp32 maps with mode 3 beside modes 0..2);
  * pips_tracks_draw_ex (pips_tracks_draw with the 10-bit surfaces P010 and I010 and a fade table: trails whose opacity falls with
  * age; pips_draw_workspace_bytes sizes both at the same figure); pips_motion_fit and pips_motion_workspace_bytes (the camera motion
- * between consecutive rows of a trajectory tensor: an exact consensus similarity). */
+ * between consecutive rows of a trajectory tensor: an exact consensus similarity); pips_frames_warp (the decoder's surfaces
+ * resampled through a per-frame affine map in exact integers: frames out, stabilised). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -908,6 +909,62 @@ size_t pips_motion_workspace_bytes(int F, int n, int K);
 int    pips_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, int seed,
                        int32_t* head, int64_t* sums, double* model, uint8_t* flags, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* Frames out, stabilised: pips_frames_warp resamples F frames from the `src` surfaces into the `dst` surfaces, format and size the
+ * same on both sides, through one affine map per frame -- what a stabiliser does with pips_motion_fit's models
+ * (drivers.motion_path, drivers.motion_smooth, drivers.warp_coefficients make the coefficients on the host).  Integers only:
+ *  - formats and addressing: all nine formats, PIPS_FMT_RGB24, BGR24, RGBA32, BGRA32, NV12, I420, P010, I010 and PLANAR8.  Planes,
+ *    pitches and steps in bytes, the plane geometry (odd h and w legal, chroma planes of ceil(h/2) x ceil(w/2) samples) and the
+ *    even pointers, pitches and steps of the 16-bit formats are pips_tracks_draw_ex's.  src is const.  NO PLANE OF dst MAY OVERLAP A
+ *    PLANE OF src: the byte range of plane k is [p_k, p_k + (F - 1) step_k + (rows_k - 1) pitch_k + the bytes of a row), and an
+ *    intersection of a src range with a dst range is rejected;
+ *  - coefficients: coef (F,6) int32 on the device.  Row f = (m0, m1, m2, m3, m4, m5) maps OUTPUT pixel indices to SOURCE positions;
+ *    m0, m1, m3, m4 are in Q24 (2^24 = 1.0), m2 and m5 in Q16 pixels;
+ *  - position of a full-resolution sample (R, G, B of a pixel, Y) at output pixel (x, y): X = m0 x + m1 y + 256 m2 in int64,
+ *    U = (X + 32768) >> 16 with the arithmetic shift: the source x in 1/256 px, rounded half up.  x0 = U >> 8, fx = U & 255; V, y0
+ *    and fy likewise from m3, m4, m5.  Tap indices are compared with the image bounds as int64 before any narrowing: coefficients
+ *    at INT32_MIN / INT32_MAX are legal and land outside;
+ *  - position of a 4:2:0 chroma sample (cx, cy), which stands at luma position (2 cx + 0.5, 2 cy + 0.5) (siting is not modelled,
+ *    as in import and draw): XL = m0 (4 cx + 1) + m1 (4 cy + 1) + 512 m2, Uc = (XL - 2^24 + 2^17) >> 18 is the position in the
+ *    chroma grid in 1/256 sample, Vc likewise; the identity gives Uc = 256 cx.  Cb and Cr share taps and weights;
+ *  - value: with p00, p01, p10, p11 the taps at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1),
+ *      v = ((256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11) + 32768) >> 16
+ *    (below 2^27 for 10-bit samples: int32).  A 10-bit sample is read as draw reads it (word >> 6 for P010, word & 1023 for I010)
+ *    and written as v << 6 (P010) or v (I010); EVERY word of dst inside the image is written.  The alpha byte of RGBA32 / BGRA32
+ *    dst is written 255 (src's is not read).  Bytes outside the w x h image of a plane are never written;
+ *  - border: PIPS_WARP_BORDER_CONSTANT -- a tap outside the plane takes the fill value; PIPS_WARP_BORDER_REPLICATE -- a tap's index
+ *    is clamped into the plane.  fill_rgb is one int 0xRRGGBB: the RGB formats use its bytes, NV12 / I420 convert it once by
+ *    pips_tracks_draw's table and P010 / I010 by pips_tracks_draw_ex's 10-bit table (matrix and range are looked at for these four
+ *    only).  A tap with weight 0 contributes nothing, so the identity (2^24, 0, 0, 0, 2^24, 0) copies every sample exactly, the last
+ *    row and column included, under either border.
+ * drivers.warp_frames_torch is the same rule in int64 torch ops: every byte is compared.
+ * One launch on `stream`: a 256-thread block owns a 64 x 16 tile of output luma of one frame and that tile's 32 x 8 chroma samples;
+ * a thread produces two or four adjacent samples of a row (whole dwords) and stores dwords where the dst address allows.  The block computes the box of
+ * source samples its tile can tap from the same integers at the tile's four corners, the +1 tap added; when that box, with rows
+ * of round_up(width x bytes of a pixel + 3, 4) bytes, is at most 12288 bytes in every plane, its rows are staged in LDS (aligned
+ * dword loads, byte loads at the ragged ends) and the taps read there, otherwise the taps are read from global memory: the same
+ * bits either way, and the choice depends on the coefficients, the format and the tile alone.  A tile whose box lies inside the
+ * plane takes the same pass without the border rule (no tap can be outside).  No workspace, no atomics, no
+ * allocation, no synchronisation, no floating point.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "frames_warp:": an unknown format or border; an
+ * unknown matrix or range with a YCbCr format; fill_rgb outside 0..0xFFFFFF; F < 0; h or w < 1 or > PIPS_WARP_DIM_MAX; a pitch
+ * below the bytes of a row of its plane; with F > 1 a step below pitch x rows of its plane; an odd plane pointer, pitch or step of
+ * a 16-bit format; and with F > 0: a NULL plane that the format has, a NULL coef, src and dst ranges that overlap.  F = 0 launches
+ * nothing and returns PIPS_OK.
+ * Known limits: bilinear only (no bicubic, no Lanczos, no antialiasing when the map shrinks the image); chroma siting is not
+ * modelled; the single-pixel chroma samples of an odd edge are treated like any other; alpha is not resampled; an affine map only
+ * (no homography, no rolling shutter). */
+#define PIPS_WARP_BORDER_CONSTANT  0
+#define PIPS_WARP_BORDER_REPLICATE 1
+#define PIPS_WARP_DIM_MAX 8192
+int    pips_frames_warp(int format, int matrix, int range, int border, int fill_rgb, int F, int h, int w,
+                        const void* s0, size_t spitch0, size_t sstep0,
+                        const void* s1, size_t spitch1, size_t sstep1,
+                        const void* s2, size_t spitch2, size_t sstep2,
+                        void* d0, size_t dpitch0, size_t dstep0,
+                        void* d1, size_t dpitch1, size_t dstep1,
+                        void* d2, size_t dpitch2, size_t dstep2,
+                        const int32_t* coef, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128).  PIPS_E_ARG ahead of the launch for a

@@ -2126,6 +2126,65 @@ int pips_motion_fit(const float* trajs, const float* vis, int F, int n, int fram
                              (unsigned char*)flags, workspace, (hipStream_t)stream);
 }
 
+// ---- frames out, stabilised
+int pips_frames_warp(int format, int matrix, int range, int border, int fill_rgb, int F, int h, int w, const void* s0, size_t spitch0,
+                     size_t sstep0, const void* s1, size_t spitch1, size_t sstep1, const void* s2, size_t spitch2, size_t sstep2, void* d0,
+                     size_t dpitch0, size_t dstep0, void* d1, size_t dpitch1, size_t dstep1, void* d2, size_t dpitch2, size_t dstep2,
+                     const int32_t* coef, void* stream) {
+    PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I010) || format == PIPS_FMT_PLANAR8, "frames_warp: unknown format %d",
+                   format);
+    PIPS_CHECK_ARG(border == PIPS_WARP_BORDER_CONSTANT || border == PIPS_WARP_BORDER_REPLICATE, "frames_warp: unknown border %d", border);
+    const bool wide = format == PIPS_FMT_P010 || format == PIPS_FMT_I010;                   // 16-bit samples
+    const bool semi = format == PIPS_FMT_NV12 || format == PIPS_FMT_P010;
+    const bool yuv = semi || format == PIPS_FMT_I420 || format == PIPS_FMT_I010;
+    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
+                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
+                   "frames_warp: unknown matrix %d or range %d", matrix, range);
+    PIPS_CHECK_ARG(fill_rgb >= 0 && fill_rgb <= 0xFFFFFF, "frames_warp: fill_rgb %d outside 0..0xFFFFFF", fill_rgb);
+    PIPS_CHECK_ARG(F >= 0, "frames_warp: need F >= 0 (F=%d)", F);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1, "frames_warp: need a size of at least 1x1 (h=%d, w=%d)", h, w);
+    PIPS_CHECK_ARG(h <= PIPS_WARP_DIM_MAX && w <= PIPS_WARP_DIM_MAX, "frames_warp: surfaces up to %d a side (h=%d, w=%d)",
+                   PIPS_WARP_DIM_MAX, h, w);
+    // plane k of the format: its rows and the bytes of a row (pips_tracks_draw_ex's geometry)
+    const void* sp[3] = {s0, s1, s2};
+    void* dp[3] = {d0, d1, d2};
+    const size_t spitch[3] = {spitch0, spitch1, spitch2}, sstep[3] = {sstep0, sstep1, sstep2};
+    const size_t dpitch[3] = {dpitch0, dpitch1, dpitch2}, dstep[3] = {dstep0, dstep1, dstep2};
+    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2, sb = wide ? 2 : 1;
+    const bool planar = format == PIPS_FMT_PLANAR8;
+    const int planes = semi ? 2 : (yuv || planar) ? 3 : 1;
+    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : (yuv || planar) ? sb : 3;
+    const size_t rows[3] = {(size_t)h, planar ? (size_t)h : ch, planar ? (size_t)h : ch};
+    const size_t row_bytes[3] = {(size_t)w * bpp, planar ? (size_t)w : (semi ? 2 * cw : cw) * sb, planar ? (size_t)w : cw * sb};
+    for (int side = 0; side < 2; ++side) {
+        const char* who = side ? "dst" : "src";
+        const size_t* pitch = side ? dpitch : spitch;
+        const size_t* step = side ? dstep : sstep;
+        for (int k = 0; k < planes; ++k) {
+            const uintptr_t p = side ? (uintptr_t)dp[k] : (uintptr_t)sp[k];
+            PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "frames_warp: pitch %zu of %s plane %d is below the %zu bytes of a row", pitch[k], who,
+                           k, row_bytes[k]);
+            PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
+                           "frames_warp: step %zu of %s plane %d is below pitch %zu x %zu rows", step[k], who, k, pitch[k], rows[k]);
+            PIPS_CHECK_ARG(!wide || ((p | pitch[k] | step[k]) & 1) == 0,
+                           "frames_warp: %s plane %d of a 16-bit format needs an even pointer, pitch and step (pitch %zu, step %zu)", who,
+                           k, pitch[k], step[k]);
+        }
+    }
+    if (F == 0) return PIPS_OK;
+    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(sp[k] != nullptr && dp[k] != nullptr, "frames_warp: null plane %d", k);
+    PIPS_CHECK_ARG(coef != nullptr, "frames_warp: null coef");
+    // the bytes of a plane: [p, p + (F - 1) step + (rows - 1) pitch + the bytes of a row)
+    for (int i = 0; i < planes; ++i)
+        for (int k = 0; k < planes; ++k) {
+            const uintptr_t a0 = (uintptr_t)sp[i], a1 = a0 + ((size_t)F - 1) * sstep[i] + (rows[i] - 1) * spitch[i] + row_bytes[i];
+            const uintptr_t b0 = (uintptr_t)dp[k], b1 = b0 + ((size_t)F - 1) * dstep[k] + (rows[k] - 1) * dpitch[k] + row_bytes[k];
+            PIPS_CHECK_ARG(a1 <= b0 || b1 <= a0, "frames_warp: src plane %d and dst plane %d overlap", i, k);
+        }
+    return launch_frames_warp(format, matrix, range, border, fill_rgb, F, h, w, sp, spitch, sstep, dp, dpitch, dstep, (const int*)coef,
+                              (hipStream_t)stream);
+}
+
 // ---- whole forward
 size_t pips_workspace_bytes(int B, int S, int H, int W, int N, int stride) {
     if (B <= 0 || S < 1 || S > PIPS_S_MAX || H <= 0 || W <= 0 || N <= 0 || stride < 1) return 0;

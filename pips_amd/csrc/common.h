@@ -574,4 +574,14 @@ inline size_t motion_workspace_bytes(int F, int n, int K) {
 int launch_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, unsigned seed,
                       int* head, long long* sums, double* model, unsigned char* flags, void* workspace, hipStream_t st);
 
+// ---- warp.hip: F frames resampled from the src surfaces into the dst surfaces through a per-frame affine map (pips_frames_warp).
+// One launch: a block per 64 x 16 tile of output luma and frame; the source box of a tile is staged in LDS when it fits
+// WARP_LDS_BYTES in every plane (the criterion reads the coefficients, the format and the tile alone), taps come straight from
+// global memory otherwise -- the same integers either way.  Arguments checked by the caller (src and dst do not overlap).
+constexpr int WARP_TILE_W = 64, WARP_TILE_H = 16;
+constexpr int WARP_LDS_BYTES = 12288;
+int launch_frames_warp(int format, int matrix, int range, int border, int fill_rgb, int F, int h, int w, const void* const* sp,
+                       const size_t* spitch, const size_t* sstep, void* const* dp, const size_t* dpitch, const size_t* dstep,
+                       const int* coef, hipStream_t st);
+
 }  // namespace pips

@@ -36,6 +36,11 @@
   camera motion as a consensus similarity between consecutive rows, by one ``pips_motion_fit`` call; the second is the same exact
   rule in torch ops, equal in every bit; ``MotionEstimator`` fits the pushes of a streamed tracker one by one, keeping the last row
   by identity; ``motion_path`` composes the pairs into frame -> frame-0 transforms.
+* ``motion_smooth`` / ``warp_coefficients`` / ``warp_frames`` / ``warp_frames_torch`` / ``Stabilizer`` -- frames out, stabilised: the
+  camera path smoothed on the host, the corrections turned into fixed-point affine rows, and the decoder's surfaces resampled
+  through them by one ``pips_frames_warp`` call, in every format import and draw speak; the torch form is the same integer rule,
+  byte for byte; ``Stabilizer`` does it for the pushes of a streamed tracker, handing a frame's correction back once the frames
+  its window needs have been seen.
 
 Host logic only (a few tiny torch ops on (8,N) tensors); all model arithmetic is in
 libpips_hip.so through ``Pips.encode`` / ``Pips.track``.
@@ -59,6 +64,7 @@ state follows the number of queries being tracked, not the number ever given.
 """
 from __future__ import annotations
 
+import cmath
 import math
 import weakref
 
@@ -2025,6 +2031,242 @@ def motion_path(models):
         A, T = A / a, T - (A / a) * t                                              # x_0 = A ((q - t) / a) + T
         out.append([A.real, A.imag, T.real, T.imag])
     return torch.tensor(out, dtype=torch.float64)
+
+
+# ---------------------------------------------------------------------------------------------- frames out, stabilised
+def _smooth_params(A_prev, theta_prev, A, T):
+    """the parameters (log|A|, theta, Re T, Im T) of one path row, theta unwrapped from the row before"""
+    if A == 0:
+        raise ValueError("a path row with A = 0 has no logarithm")
+    theta = cmath.phase(A) if A_prev is None else theta_prev + cmath.phase(A / A_prev)
+    return [math.log(abs(A)), theta, T.real, T.imag]
+
+
+def _smooth_row(g, A, T, f, radius):
+    """the correction of frame f: its window of ``g`` summed on its own in ascending frame order, plain float adds"""
+    lo, hi = max(0, f - radius), min(len(g) - 1, f + radius)
+    mean = []
+    for c in _range(4):
+        acc = 0.0
+        for k in _range(lo, hi + 1):
+            acc = acc + g[k][c]
+        mean.append(acc / (hi - lo + 1))
+    As = math.exp(mean[0]) * complex(math.cos(mean[1]), math.sin(mean[1]))
+    Ts = complex(mean[2], mean[3])
+    Wa, Wt = A / As, (T - Ts) / As
+    return [Wa.real, Wa.imag, Wt.real, Wt.imag]
+
+
+def _smooth_radius(radius):
+    return None if radius is None else _whole(radius, "radius", 0)
+
+
+def motion_smooth(path, radius=15):
+    """The corrections that stabilise a video, on the host in float64: ``path`` (F,4) is ``motion_path``'s output, row f = (A, T)
+    taking frame f to frame 0 -> (F,4) rows W_f taking frame f to the STABILISED frame f.  ``radius=None``: W = path, the camera
+    held still.  Otherwise the path's parameters g_f = (log|A_f|, theta_f, Re T_f, Im T_f), theta unwrapped (theta_0 = arg A_0,
+    theta_f = theta_{f-1} + arg(A_f / A_{f-1})), are replaced by their mean over the frames max(0, f - radius) .. min(F - 1, f +
+    radius) -- each window summed on its own in ascending order, so that ``Stabilizer`` reproduces the bits push by push -- and with
+    A~ = exp(l~) e^{i theta~}, W_f = (A_f / A~_f, (T_f - T~_f) / A~_f): the smoothed camera keeps the slow motion, the frame loses
+    the shake."""
+    radius = _smooth_radius(radius)
+    path = torch.as_tensor(path).to("cpu", torch.float64)
+    if path.dim() != 2 or path.shape[1] != 4:
+        raise ValueError(f"path must be (F,4), not {tuple(path.shape)}")
+    if not bool(torch.isfinite(path).all()):
+        raise ValueError("path has a non-finite entry")
+    if radius is None:
+        return path.clone()
+    rows = [(complex(r[0], r[1]), complex(r[2], r[3])) for r in path.tolist()]
+    g = []
+    for f, (A, T) in enumerate(rows):
+        g.append(_smooth_params(rows[f - 1][0] if f else None, g[f - 1][1] if f else 0.0, A, T))
+    out = [_smooth_row(g, A, T, f, radius) for f, (A, T) in enumerate(rows)]
+    return torch.tensor(out, dtype=torch.float64).reshape(len(out), 4)
+
+
+def warp_coefficients(transforms, size, surface=None, zoom=1.0):
+    """Forward transforms -> the (F,6) int32 rows of ``pips_frames_warp`` on the host, in float64.  ``transforms`` is (F,4)
+    similarity rows (a_re, a_im, tx, ty) -- ``motion_smooth``'s output; the affine row (a_re, -a_im, tx, a_im, a_re, ty) -- or (F,6)
+    affine rows (a, b, c, d, e, f) with x' = a x + b y + c, y' = d x + e y + f: FORWARD maps, taking a position of the frame to
+    where it shall be shown, in pixel-index coordinates of the model's ``size`` = (H, W).  ``surface`` = (h, w) of the surfaces that
+    are warped (default ``size``).  An output pixel u of the surface goes, as 3 x 3 float64 matrices applied in this order, through
+    the zoom about the surface centre ((w-1)/2, (h-1)/2) -- the output pixel shows the stabilised position c + (u - c) / zoom --,
+    from surface index to model index, x = (u + 0.5) / s - 0.5 with s = w / W (y with h / H: the inverse of what draw applies),
+    through the inverse of the forward map, and from model index back to surface index.  Rows 0 and 1 of the product are quantised
+    with floor(v 2^24 + 0.5) for the linear terms and floor(v 2^16 + 0.5) for the offsets.  ValueError for a singular map, zoom <= 0,
+    a non-finite entry and a coefficient outside int32 (a linear term needs |v| < 128, an offset |v| < 32768 px)."""
+    t = torch.as_tensor(transforms).to("cpu", torch.float64)
+    if t.dim() != 2 or t.shape[1] not in (4, 6):
+        raise ValueError(f"transforms must be (F,4) or (F,6), not {tuple(t.shape)}")
+    H, W = int(size[0]), int(size[1])
+    h, w = (H, W) if surface is None else (int(surface[0]), int(surface[1]))
+    if min(H, W, h, w) < 1:
+        raise ValueError(f"sizes must be at least 1 x 1, not {H} x {W} and {h} x {w}")
+    if isinstance(zoom, bool) or not isinstance(zoom, (int, float)) or not math.isfinite(zoom) or zoom <= 0:
+        raise ValueError(f"zoom must be a finite number above 0, not {zoom!r}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("transforms has a non-finite entry")
+    if t.shape[1] == 4:
+        t = torch.stack([t[:, 0], -t[:, 1], t[:, 2], t[:, 1], t[:, 0], t[:, 3]], dim=1)
+    sx, sy, cx, cy, z = w / W, h / H, (w - 1) / 2, (h - 1) / 2, 1.0 / float(zoom)
+    eye = [0.0, 0.0, 1.0]
+    Z = torch.tensor([[z, 0.0, cx - cx * z], [0.0, z, cy - cy * z], eye], dtype=torch.float64)
+    S1 = torch.tensor([[1.0 / sx, 0.0, 0.5 / sx - 0.5], [0.0, 1.0 / sy, 0.5 / sy - 0.5], eye], dtype=torch.float64)
+    S4 = torch.tensor([[sx, 0.0, 0.5 * sx - 0.5], [0.0, sy, 0.5 * sy - 0.5], eye], dtype=torch.float64)
+    out = []
+    for a, b, c, d, e, f in t.tolist():
+        det = a * e - b * d
+        if det == 0.0 or not math.isfinite(det) or not math.isfinite(1.0 / det):
+            raise ValueError(f"the map ({a}, {b}, {c}, {d}, {e}, {f}) is singular")
+        ia, ib, id_, ie = e / det, -b / det, -d / det, a / det
+        inv = torch.tensor([[ia, ib, -(ia * c + ib * f)], [id_, ie, -(id_ * c + ie * f)], eye], dtype=torch.float64)
+        M = (S4 @ (inv @ (S1 @ Z))).tolist()
+        row = []
+        for r in (0, 1):
+            for k, (scale, limit) in enumerate(((2.0 ** 24, 128.0), (2.0 ** 24, 128.0), (2.0 ** 16, 32768.0))):
+                v = M[r][k]
+                q = math.floor(v * scale + 0.5) if math.isfinite(v) and abs(v) < limit else None
+                if q is None or not -2 ** 31 <= q <= 2 ** 31 - 1:
+                    raise ValueError(f"coefficient {v!r} of the map ({a}, {b}, {c}, {d}, {e}, {f}) does not fit its fixed-point int32")
+                row.append(q)
+        out.append(row)
+    return torch.tensor(out, dtype=torch.int32).reshape(len(out), 6)
+
+
+def _warp_plane(src, m, chroma, border, fill):
+    """one plane of one frame: src (h,w,C) int64 values, m the frame's six python ints, fill (C,) int64 -> (h,w,C) int64"""
+    h, w, _ = src.shape
+    dev = src.device
+    x, y = torch.arange(w, dtype=torch.int64, device=dev).view(1, w), torch.arange(h, dtype=torch.int64, device=dev).view(h, 1)
+    if chroma:
+        U = (m[0] * (4 * x + 1) + m[1] * (4 * y + 1) + 512 * m[2] - 2 ** 24 + 2 ** 17) >> 18
+        V = (m[3] * (4 * x + 1) + m[4] * (4 * y + 1) + 512 * m[5] - 2 ** 24 + 2 ** 17) >> 18
+    else:
+        U = (m[0] * x + m[1] * y + 256 * m[2] + 32768) >> 16
+        V = (m[3] * x + m[4] * y + 256 * m[5] + 32768) >> 16
+    x0, fx, y0, fy = U >> 8, (U & 255).unsqueeze(-1), V >> 8, (V & 255).unsqueeze(-1)
+
+    def tap(xi, yi):
+        v = src[yi.clamp(0, h - 1), xi.clamp(0, w - 1)]                                           # (h,w,C)
+        if border == "replicate":
+            return v
+        inside = (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)
+        return torch.where(inside.unsqueeze(-1), v, fill.view(1, 1, -1))
+    p00, p01, p10, p11 = tap(x0, y0), tap(x0 + 1, y0), tap(x0, y0 + 1), tap(x0 + 1, y0 + 1)
+    return ((256 - fy) * ((256 - fx) * p00 + fx * p01) + fy * ((256 - fx) * p10 + fx * p11) + 32768) >> 16
+
+
+def warp_frames_torch(planes, fmt, coef, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited"):
+    """pips_frames_warp (include/pips_hip.h) as int64 torch ops, on any device: ``ops.warp_frames``' arguments (without ``out``) ->
+    new planes of the source's shapes and types, a tensor for one plane and a list otherwise.  Per frame and plane the positions
+    U, V of every output sample from the six integers, the four taps under the border rule, the blend with 256 - f and f.  Equal
+    to the kernel byte for byte; written to be read, not to be fast."""
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    dtypes = [p.dtype for p in planes]
+    planes, F, h, w, coef, fill_rgb = ops.warp_check(planes, fmt, coef, border, fill, matrix, range)
+    dev = planes[0].device
+    rows = coef.to("cpu", torch.int64).tolist()
+    wide, shift = fmt in ops.IMPORT_16BIT, 6 if fmt == "p010" else 0
+    yuv = fmt in ("nv12", "i420") or wide
+    rgb = torch.tensor([fill_rgb >> 16, (fill_rgb >> 8) & 255, fill_rgb & 255], dtype=torch.int64)
+    comp = (rgb_to_yuv_torch(rgb, matrix, range, 10 if wide else 8) if yuv else rgb).to(dev)
+    out = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in planes]
+
+    def value(p):                                                                                  # a plane of one frame -> its samples' values
+        return ((p.to(torch.int64) & 0xFFFF) >> shift) & 1023 if wide else p.to(torch.int64)
+
+    def word(v):                                                                                   # values -> what is stored
+        if not wide:
+            return v.to(torch.uint8)
+        v = v << shift
+        return (v - ((v & 0x8000) << 1)).to(torch.int16)
+    for f in _range(F):
+        m = rows[f]
+        if fmt == "planar8":
+            for c in (0, 1, 2):
+                out[0][f, c] = word(_warp_plane(value(planes[0][f, c]).unsqueeze(-1), m, False, border, comp[c:c + 1])[..., 0])
+        elif yuv:
+            out[0][f] = word(_warp_plane(value(planes[0][f]).unsqueeze(-1), m, False, border, comp[:1])[..., 0])
+            if fmt in ("nv12", "p010"):
+                out[1][f] = word(_warp_plane(value(planes[1][f]), m, True, border, comp[1:]))
+            else:
+                for k in (1, 2):
+                    out[k][f] = word(_warp_plane(value(planes[k][f]).unsqueeze(-1), m, True, border, comp[k:k + 1])[..., 0])
+        else:
+            order = comp.flip(0) if fmt in ("bgr24", "bgra32") else comp                            # the bytes of a pixel in memory order
+            out[0][f, ..., :3] = word(_warp_plane(value(planes[0][f, ..., :3]), m, False, border, order))
+            if fmt in ("rgba32", "bgra32"):
+                out[0][f, ..., 3] = 255
+    out = [p.view(t) for p, t in zip(out, dtypes)]
+    return out[0] if len(out) == 1 else out
+
+
+def warp_frames(planes, fmt, transforms, size=None, zoom=1.0, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited",
+                out=None):
+    """Frames moved by forward transforms on the device: ``warp_coefficients(transforms, size, surface, zoom)`` followed by one
+    ``pips_frames_warp`` call (``ops.warp_frames``).  ``planes`` / ``fmt`` are F surfaces in any of ``draw_tracks``' layouts,
+    ``transforms`` (F,4) similarities -- ``motion_smooth``'s or ``Stabilizer``'s corrections -- or (F,6) affine rows in the pixels of
+    the model's ``size`` = (H, W) (default: the surfaces' own size).  Returns new surfaces (``out`` when given): a tensor for one
+    plane, a list otherwise."""
+    got, _, h, w = ops.draw_planes(planes, fmt)
+    coef = warp_coefficients(transforms, (h, w) if size is None else size, (h, w), zoom)
+    res = ops.warp_frames(planes, fmt, coef, border, fill, matrix, range, out=out)
+    if out is None:                                                                                # (uint16 planes come back as uint16)
+        given = [planes] if torch.is_tensor(planes) else list(planes)
+        res = [r.view(p.dtype) for r, p in zip(res, given)]
+    else:
+        res = [out] if torch.is_tensor(out) else list(out)
+    return res[0] if len(res) == 1 else res
+
+
+class Stabilizer:
+    """The corrections that stabilise a streamed video, push by push: ``step(f0, trajs, vis, ids)`` takes the ``(f0, trajs
+    (1,m,n,2), vis (1,m,n)[, ids (n,)])`` of a tracker's push, fits the camera motion of its pairs with an internal
+    ``MotionEstimator`` (``motion_params``: thr, hypotheses, vis_thr, seed; ``engine`` "library" or "torch"), extends the path with
+    ``motion_path``'s two complex operations per pair and returns ``(g0, corrections (k,4) float64)``: the rows W_g of
+    ``motion_smooth`` for the frames g0 .. g0 + k - 1 that became FINAL -- frame g is final once frame g + radius has been seen.
+    ``finish()`` returns the rest, their windows clamped at the end of the video; ``radius=None`` holds the camera still and makes
+    every frame final at once.  All returns together equal ``motion_smooth(motion_path(all models), radius)`` in every bit.
+    The stabiliser holds no frames: the caller keeps its surfaces until their corrections come back, as with ``TrackPainter``, and
+    warps them then (``warp_frames``)."""
+
+    def __init__(self, radius=15, engine="library", **motion_params):
+        self.radius = _smooth_radius(radius)
+        self.estimator = MotionEstimator(engine=engine, **motion_params)
+        self.A, self.T = complex(1.0, 0.0), complex(0.0, 0.0)
+        self.path, self.g, self.done = [], [], 0                     # (A, T) and parameters of every frame seen; frames handed out
+
+    def _emit(self, upto):
+        rows = []
+        for f in _range(self.done, upto):
+            A, T = self.path[f]
+            rows.append([A.real, A.imag, T.real, T.imag] if self.radius is None else _smooth_row(self.g, A, T, f, self.radius))
+        g0, self.done = self.done, max(upto, self.done)
+        return g0, torch.tensor(rows, dtype=torch.float64).reshape(len(rows), 4)
+
+    def _see(self, A, T):
+        if self.radius is not None:
+            self.g.append(_smooth_params(self.path[-1][0] if self.path else None, self.g[-1][1] if self.g else 0.0, A, T))
+        self.path.append((A, T))
+
+    @torch.no_grad()
+    def step(self, f0, trajs, vis=None, ids=None):
+        first = self.estimator.row is None                           # no row kept: the first row of this push ends no pair
+        models = self.estimator.step(f0, trajs, vis, ids)
+        if first and trajs.shape[1] > 0:
+            self._see(self.A, self.T)
+        for a_re, a_im, tx, ty in models.to("cpu", torch.float64).tolist():
+            a, t = complex(a_re, a_im), complex(tx, ty)
+            if a == 0:
+                raise ValueError("a model with a = 0 has no inverse")
+            self.A, self.T = self.A / a, self.T - (self.A / a) * t
+            self._see(self.A, self.T)
+        n = len(self.path)
+        return self._emit(n if self.radius is None else max(n - self.radius, 0))
+
+    def finish(self):
+        return self._emit(len(self.path))
 
 
 def find_cuts(rgbs, cut_thr=0.5, scan="torch", slice_frames=64):

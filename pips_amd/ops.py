@@ -395,6 +395,91 @@ def draw_tracks(planes, fmt, trajs, vis, colors, first=0, src_size=None, trail=1
             _call("pips_tracks_draw", *head, _lib.ptr(workspace), nbytes, _stream())
 
 
+# include/pips_hip.h: PIPS_WARP_BORDER_*, PIPS_WARP_DIM_MAX; pips_amd/csrc/common.h: the tile and the staging budget of warp.hip
+WARP_BORDERS = {"constant": 0, "replicate": 1}
+WARP_DIM_MAX, WARP_TILE_W, WARP_TILE_H, WARP_LDS_BYTES = 8192, 64, 16, 12288
+_INT32 = (-2 ** 31, 2 ** 31 - 1)
+
+
+def warp_check(planes, fmt, coef, border, fill, matrix, range):
+    """pips_frames_warp's limits on the values, shared by ``warp_frames`` and ``drivers.warp_frames_torch`` -> (planes, F, h, w,
+    coef (F,6) int32 on its own device, fill_rgb)"""
+    planes, F, h, w = draw_planes(planes, fmt)
+    if matrix not in IMPORT_MATRICES or range not in IMPORT_RANGES:
+        raise ValueError(f"matrix must be one of {sorted(IMPORT_MATRICES)} and range one of {sorted(IMPORT_RANGES)}, "
+                         f"not {matrix!r}, {range!r}")
+    if border not in WARP_BORDERS:
+        raise ValueError(f"border must be one of {sorted(WARP_BORDERS)}, not {border!r}")
+    if max(h, w) > WARP_DIM_MAX:
+        raise ValueError(f"surfaces up to {WARP_DIM_MAX} a side, not {h} x {w}")
+    fill = list(fill)
+    if len(fill) != 3 or any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 255 for v in fill):
+        raise ValueError(f"fill must be three whole numbers R, G, B in 0..255, not {fill!r}")
+    coef = torch.as_tensor(coef)
+    if coef.dim() != 2 or tuple(coef.shape) != (F, 6) or coef.dtype.is_floating_point or coef.dtype == torch.bool:
+        raise ValueError(f"coef must be integers (F,6) = {(F, 6)}, not {coef.dtype} {tuple(coef.shape)}")
+    if coef.numel() and (int(coef.min()) < _INT32[0] or int(coef.max()) > _INT32[1]):
+        raise ValueError("a coefficient does not fit int32")
+    return planes, F, h, w, coef.to(torch.int32), int(fill[0]) << 16 | int(fill[1]) << 8 | int(fill[2])
+
+
+def warp_staged(row, fmt, x0=0, y0=0):
+    """Which tap path warp.hip's block takes for the WARP_TILE_W x WARP_TILE_H tile of output luma at (x0, y0) under the six
+    coefficients ``row``: True when the source box of every plane of ``fmt`` fits WARP_LDS_BYTES and is staged in LDS, False when the
+    taps are read from global memory.  The box is the tap range of the tile's four corners, the +1 tap added, not held to the image;
+    a row of it takes round_up(width x bytes of a pixel + 3, 4) bytes.  Python integers: the criterion, restated."""
+    if fmt not in DRAW_FORMATS_EX:
+        raise ValueError(f"fmt must be one of {sorted(DRAW_FORMATS_EX)}, not {fmt!r}")
+    m = [int(v) for v in row]
+    sb = 2 if fmt in IMPORT_16BIT else 1
+    luma = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4}.get(fmt, sb)
+
+    def fits(chroma, tx, ty, tw, th, pxb):
+        us, vs = [], []
+        for x, y in ((tx, ty), (tx + tw - 1, ty), (tx, ty + th - 1), (tx + tw - 1, ty + th - 1)):
+            if chroma:
+                us.append((m[0] * (4 * x + 1) + m[1] * (4 * y + 1) + 512 * m[2] - 2 ** 24 + 2 ** 17) >> 26)
+                vs.append((m[3] * (4 * x + 1) + m[4] * (4 * y + 1) + 512 * m[5] - 2 ** 24 + 2 ** 17) >> 26)
+            else:
+                us.append((m[0] * x + m[1] * y + 256 * m[2] + 32768) >> 24)
+                vs.append((m[3] * x + m[4] * y + 256 * m[5] + 32768) >> 24)
+        bw, bh = max(us) + 1 - min(us) + 1, max(vs) + 1 - min(vs) + 1
+        return bh * ((bw * pxb + 6) & ~3) <= WARP_LDS_BYTES
+    ok = fits(False, x0, y0, WARP_TILE_W, WARP_TILE_H, luma)
+    if fmt in ("nv12", "i420", "p010", "i010"):
+        ok = ok and fits(True, x0 // 2, y0 // 2, WARP_TILE_W // 2, WARP_TILE_H // 2, 2 * sb if fmt in ("nv12", "p010") else sb)
+    return ok
+
+
+def warp_frames(planes, fmt, coef, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited", out=None):
+    """pips_frames_warp: the device surfaces ``planes`` of format ``fmt`` -- ``draw_tracks``' formats and shapes -- resampled into
+    ``out`` (surfaces of the same format and shapes; allocated like the source when None) and returned as a list of planes.  ``coef``
+    (F,6) int32, from the host or the device: row f = (m0, m1, m2, m3, m4, m5) maps the OUTPUT pixel (x, y) of frame f to the source
+    position (m0 x + m1 y) / 2^24 + m2 / 2^16, (m3 x + m4 y) / 2^24 + m5 / 2^16 (include/pips_hip.h has the whole rule;
+    ``drivers.warp_coefficients`` makes the rows).  ``border`` "constant" (a tap outside the image is ``fill`` = (R, G, B)) or
+    "replicate"; ``matrix`` / ``range`` convert the fill for the YCbCr formats.  Row and frame strides go through as pitch and step,
+    on both sides: ``surface[:, :h, :w]`` views of pitched allocations are read and written as they are; a plane whose strides
+    cannot be expressed so is a ValueError, and so is an ``out`` that is not of the source's shapes.  ``out`` may not overlap
+    ``planes``."""
+    planes, F, h, w, coef, fill_rgb = warp_check(planes, fmt, coef, border, fill, matrix, range)
+    assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = planes[0].device
+    if out is None:
+        out = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in planes]
+    else:
+        out, Fo, ho, wo = draw_planes(out, fmt)
+        if (Fo, ho, wo) != (F, h, w) or any(o.device != dev for o in out):
+            raise ValueError(f"out must be {F} surfaces of {h} x {w} on the source's device, not {Fo} of {ho} x {wo}")
+    if F == 0:
+        return out
+    coef = coef.to(dev).contiguous()
+    args = draw_surfaces(planes, fmt) + draw_surfaces(out, fmt)
+    with torch.cuda.device(dev):
+        _call("pips_frames_warp", DRAW_FORMATS_EX[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], WARP_BORDERS[border], fill_rgb,
+              F, h, w, *args, _lib.ptr(coef), _stream())
+    return out
+
+
 def point_sample(level0, B, xy):
     """level0 (B*S,H8,W8,128), xy (B,N,2) map pixels -> (B,N,128)."""
     xy = _f32(xy)
