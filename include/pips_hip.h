@@ -119,7 +119,9 @@ const char* pips_last_error(void);
  * pips_tracks_draw_ex (pips_tracks_draw with the 10-bit surfaces P010 and I010 and a fade table: trails whose opacity falls with
  * age; pips_draw_workspace_bytes sizes both at the same figure); pips_motion_fit and pips_motion_workspace_bytes (the camera motion
  * between consecutive rows of a trajectory tensor: an exact consensus similarity); pips_frames_warp (the decoder's surfaces
- * resampled through a per-frame affine map in exact integers: frames out, stabilised). */
+ * resampled through a per-frame affine map in exact integers: frames out, stabilised); pips_motion_layers and
+ * pips_motion_layers_workspace_bytes (the consensus of pips_motion_fit peeled into up to 8 motion layers a pair, with the overlap
+ * table that links a pair's layers to those of the pair before: what moves, beside the camera). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -909,6 +911,55 @@ size_t pips_motion_workspace_bytes(int F, int n, int K);
 int    pips_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, int seed,
                        int32_t* head, int64_t* sums, double* model, uint8_t* flags, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* Motion layers: pips_motion_layers answers WHAT moves.  For every pair of consecutive rows it finds the camera's similarity as
+ * pips_motion_fit does, then repeats the consensus on the columns left over, for L layers, and counts how the layers of a pair
+ * overlap those of the pair before, so that a host can link them into objects that persist (drivers.link_layers).  Everything not
+ * restated here is pips_motion_fit's rule above, word for word: quantisation, usable and valid columns, mix, the choice of i and j,
+ * the inlier test, the key score * 1024 + (1023 - h), ties to the lowest h, the eight sums and the fp64 model with one rounding per
+ * operation.  Per pair f (1 <= f < F) and layer l = 0..L-1, in this order:
+ *  - the LIST of layer l holds the valid columns of the pair that no layer below l took, in ascending column order; m_l its length;
+ *  - layer l draws its hypotheses with seed_l = seed + l * 0x632BE5AB (32-bit wrap-around) in place of seed: seed_0 = seed, layer 0
+ *    draws pips_motion_fit's hypotheses.  The indices i and j index layer l's own list, with m_l in place of m;
+ *  - layer l HAS A MODEL iff m_l >= 2 and its best score is at least need_l: need_0 = 2 as pips_motion_fit, need_l = min_in for
+ *    l >= 1, 2 <= min_in <= PIPS_MOTION_N_MAX;
+ *  - with a model the inliers of the winning hypothesis leave the list.  Without a model nothing leaves, and the next layer is
+ *    still tried on the same columns with its own hypotheses: there is no early stop, every layer follows one rule.
+ * Outputs, one row per pair (row f - 1 for pair f), 1 <= L <= PIPS_MOTION_LAYERS_MAX:
+ *  - layer uint8[n]: 255 for a column that is not valid, 254 for a valid column in no layer, otherwise the l that took the column;
+ *  - per (pair, layer), row (f - 1) L + l: head int32[4] = (m_l, n_in, h_best or -1, 0); sums int64[8] and model float64[4],
+ *    pips_motion_fit's formulas on that layer's inliers (zeros and (1, 0, 0, 0) without a model); box int32[4] = (min qx, min qy,
+ *    max qx, max qy) of the inliers' positions in row f, in quarter pixels (zeros without a model);
+ *  - overlap int32[L][L] per pair: overlap[a][b] is the number of columns k with layer_f[k] == a and prev[k] == b, for a, b < L
+ *    (254 and 255 on either side count nowhere).  prev is the pair before, layer_{f-1}; for the first pair of a call it is
+ *    prev_layer uint8[n], the labels of the pair before this call in THIS call's column order, or NULL: then the first pair's table
+ *    is all zeros.  prev_layer may NOT lie inside this call's `layer` output (its first launch writes every row of `layer` before
+ *    the last one reads prev_layer): a host that keeps the last row of one call for the next copies it out of the buffer first.
+ * Layer 0 is pips_motion_fit: head, sums and model of layer 0 are its rows, layer == 0 where its flags are 2 and layer == 255 where
+ * they are 0.  drivers.motion_layers_table_torch is the same rule in int64 / float64 torch ops: every output is compared bit for bit.
+ * 1 + 2 L + 1 launches on `stream`, no atomics: a block per pair quantises the valid columns once and stores them in column order
+ * (four int16 and the int32 column index each) and writes 255 / 254 into layer; per layer, pips_motion_fit's scoring launch on the
+ * layer's list with seed_l, then a block per pair that picks the winner, tests the list's entries, writes layer[col] = l and the
+ * (pair, layer) rows and compacts the entries that stay into the other of two ping-pong lists (a wave ballot and a prefix over the
+ * waves: stable); a last block per pair counts the L * L (now, before) codes with one ballot a code.  A pair whose list is shorter
+ * than 2 costs its scoring blocks one load and its select block the copy of at most one entry.
+ * pips_motion_layers_workspace_bytes(F, n, K, L) = (F - 1) (24 n + 4 (1 + ceil(K / 64))), whatever L; 0 for F <= 1, n <= 0 or
+ * arguments pips_motion_layers rejects.  PIPS_E_ARG ahead of any launch, with nothing written and the message prefix
+ * "motion_layers:": pips_motion_fit's rejections of F, n, K, thr4, frame0 and vis_logit; L outside 1..PIPS_MOTION_LAYERS_MAX; min_in
+ * outside 2..PIPS_MOTION_N_MAX; with F > 1 a NULL head, sums, model, box or overlap; with F > 1 and n > 0 a NULL trajs, layer or
+ * workspace, a workspace off a 16-byte address or a prev_layer whose n bytes meet the (F - 1) n bytes of layer.
+ * PIPS_E_WORKSPACE: workspace_bytes below the figure above.  F <= 1 launches
+ * nothing, writes nothing and returns PIPS_OK.  n == 0 with F > 1 needs no workspace: every head row is (0, 0, -1, 0), sums, box and
+ * overlap are zeros and every model is the identity.
+ * Known limits: similarities only (no affine or homography layers); a layer is a motion, not a region -- nothing makes it spatially
+ * compact; no re-scoring after the refit; layers whose motions coincide are not merged; the overlap table links a pair to the pair
+ * before and no further, so an identity linked from it has no memory beyond one pair; labels are per track, there are no per-pixel
+ * masks. */
+#define PIPS_MOTION_LAYERS_MAX  8
+size_t pips_motion_layers_workspace_bytes(int F, int n, int K, int L);
+int    pips_motion_layers(const float* trajs, const float* vis, const uint8_t* prev_layer, int F, int n, int frame0, float vis_logit,
+                          int K, int thr4, int seed, int L, int min_in, int32_t* head, int64_t* sums, double* model, int32_t* box,
+                          uint8_t* layer, int32_t* overlap, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Frames out, stabilised: pips_frames_warp resamples F frames from the `src` surfaces into the `dst` surfaces, format and size the
  * same on both sides, through one affine map per frame -- what a stabiliser does with pips_motion_fit's models

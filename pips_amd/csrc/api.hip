@@ -2125,6 +2125,42 @@ int pips_motion_fit(const float* trajs, const float* vis, int F, int n, int fram
     return launch_motion_fit(trajs, vis, F, n, frame0, vis_logit, K, thr4, (unsigned)seed, (int*)head, (long long*)sums, model,
                              (unsigned char*)flags, workspace, (hipStream_t)stream);
 }
+size_t pips_motion_layers_workspace_bytes(int F, int n, int K, int L) {
+    if (!motion_shape_ok(F, n, K) || L < 1 || L > PIPS_MOTION_LAYERS_MAX || F <= 1 || n == 0) return 0;
+    return motion_layers_workspace_bytes(F, n, K);
+}
+int pips_motion_layers(const float* trajs, const float* vis, const uint8_t* prev_layer, int F, int n, int frame0, float vis_logit, int K,
+                       int thr4, int seed, int L, int min_in, int32_t* head, int64_t* sums, double* model, int32_t* box, uint8_t* layer,
+                       int32_t* overlap, void* workspace, size_t workspace_bytes, void* stream) {
+    PIPS_CHECK_ARG(F >= 0 && F <= PIPS_MOTION_ROWS_MAX, "motion_layers: need 0 <= F <= %d (F=%d)", PIPS_MOTION_ROWS_MAX, F);
+    PIPS_CHECK_ARG(n >= 0 && n <= PIPS_MOTION_N_MAX, "motion_layers: need 0 <= n <= %d (n=%d): the sums are exact up to there",
+                   PIPS_MOTION_N_MAX, n);
+    PIPS_CHECK_ARG(K >= 1 && K <= PIPS_MOTION_HYPS_MAX, "motion_layers: K=%d hypotheses outside 1..%d", K, PIPS_MOTION_HYPS_MAX);
+    PIPS_CHECK_ARG(thr4 >= 1 && thr4 <= PIPS_MOTION_THR4_MAX, "motion_layers: thr4=%d quarter pixels outside 1..%d", thr4,
+                   PIPS_MOTION_THR4_MAX);
+    PIPS_CHECK_ARG(frame0 >= 0 && frame0 <= INT_MAX - F, "motion_layers: frames [%d, %d + %d) do not fit an int", frame0, frame0, F);
+    PIPS_CHECK_ARG(vis_logit == vis_logit, "motion_layers: vis_logit is a NaN");
+    PIPS_CHECK_ARG(L >= 1 && L <= PIPS_MOTION_LAYERS_MAX, "motion_layers: L=%d layers outside 1..%d", L, PIPS_MOTION_LAYERS_MAX);
+    PIPS_CHECK_ARG(min_in >= 2 && min_in <= PIPS_MOTION_N_MAX, "motion_layers: min_in=%d outside 2..%d", min_in, PIPS_MOTION_N_MAX);
+    if (F <= 1) return PIPS_OK;
+    PIPS_CHECK_ARG(head && sums && model && box && overlap, "motion_layers: null head, sums, model, box or overlap");
+    if (n > 0) {
+        PIPS_CHECK_ARG(trajs && layer && workspace, "motion_layers: null trajs, layer or workspace");
+        PIPS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "motion_layers: the workspace must lie on a 16-byte address");
+        // the first launch writes every row of layer before the last one reads prev_layer: they may not share a byte
+        const uintptr_t lo = (uintptr_t)layer, hi = lo + ((size_t)F - 1) * (size_t)n, p0 = (uintptr_t)prev_layer;
+        PIPS_CHECK_ARG(prev_layer == nullptr || p0 + (size_t)n <= lo || p0 >= hi,
+                       "motion_layers: prev_layer lies inside the layer output of this call: copy the row first");
+        const size_t need = pips_motion_layers_workspace_bytes(F, n, K, L);
+        if (workspace_bytes < need) {
+            set_error("motion_layers: workspace %zu < %zu bytes", workspace_bytes, need);
+            return PIPS_E_WORKSPACE;
+        }
+    }
+    return launch_motion_layers(trajs, vis, prev_layer, F, n, frame0, vis_logit, K, thr4, (unsigned)seed, L, min_in, (int*)head,
+                                (long long*)sums, model, (int*)box, (unsigned char*)layer, (int*)overlap, workspace,
+                                (hipStream_t)stream);
+}
 
 // ---- frames out, stabilised
 int pips_frames_warp(int format, int matrix, int range, int border, int fill_rgb, int F, int h, int w, const void* s0, size_t spitch0,

@@ -573,6 +573,16 @@ inline size_t motion_workspace_bytes(int F, int n, int K) {
 }
 int launch_motion_fit(const float* trajs, const float* vis, int F, int n, int frame0, float vis_logit, int K, int thr4, unsigned seed,
                       int* head, long long* sums, double* model, unsigned char* flags, void* workspace, hipStream_t st);
+// Motion layers (pips_motion_layers): the consensus peeled L times and the overlap of a pair's layers with those of the pair before.
+// The workspace holds, for each pair, two lists of n slots (the quantised columns of the layer in turn and of the next one: four
+// int16 and the int32 column index each), the length of the list in turn and the keys of the scoring blocks.  n == 0: only the L
+// select launches and the overlap launch run.
+inline size_t motion_layers_workspace_bytes(int F, int n, int K) {
+    return ((size_t)F - 1) * ((size_t)n * 24 + 4 * ((size_t)1 + motion_blocks(K)));
+}
+int launch_motion_layers(const float* trajs, const float* vis, const unsigned char* prev_layer, int F, int n, int frame0,
+                         float vis_logit, int K, int thr4, unsigned seed, int L, int min_in, int* head, long long* sums, double* model,
+                         int* box, unsigned char* layer, int* overlap, void* workspace, hipStream_t st);
 
 // ---- warp.hip: F frames resampled from the src surfaces into the dst surfaces through a per-frame affine map (pips_frames_warp).
 // One launch: a block per 64 x 16 tile of output luma and frame; the source box of a tile is staged in LDS when it fits

@@ -36,6 +36,10 @@
   camera motion as a consensus similarity between consecutive rows, by one ``pips_motion_fit`` call; the second is the same exact
   rule in torch ops, equal in every bit; ``MotionEstimator`` fits the pushes of a streamed tracker one by one, keeping the last row
   by identity; ``motion_path`` composes the pairs into frame -> frame-0 transforms.
+* ``motion_layers`` / ``motion_layers_torch`` / ``link_layers`` / ``MotionLayers`` -- what moves, beside the camera: the consensus
+  of ``motion_fit`` peeled into motion layers on the columns left over, by one ``pips_motion_layers`` call, and the layers linked
+  from pair to pair into object ids on the host; the torch form is the same exact rule, equal in every bit; ``MotionLayers`` does
+  it for the pushes of a streamed tracker, keeping the last pair's labels, ids and counts by identity.
 * ``motion_smooth`` / ``warp_coefficients`` / ``warp_frames`` / ``warp_frames_torch`` / ``Stabilizer`` -- frames out, stabilised: the
   camera path smoothed on the host, the corrections turned into fixed-point affine rows, and the decoder's surfaces resampled
   through them by one ``pips_frames_warp`` call, in every format import and draw speak; the torch form is the same integer rule,
@@ -1856,9 +1860,13 @@ def motion_table_torch(trajs, vis, frame0, vis_logit, K, thr4, seed):
         head[f - 1, 1], head[f - 1, 2] = best, h
         sums[f - 1] = torch.stack([inl.sum(), p[:, 0].sum(), p[:, 1].sum(), q[:, 0].sum(), q[:, 1].sum(), (p * p).sum(),
                                    (p * q).sum(), (p[:, 0] * q[:, 1] - p[:, 1] * q[:, 0]).sum()])
-    # the least-squares similarity on the inliers: int64 up to D, A, B, then float64, an operation a line
+    return head, sums, _motion_model(sums, head[:, 2] >= 0), flags
+
+
+def _motion_model(sums, have):
+    """the rule's least-squares similarity on the inliers from their sums (R,8) int64 and ``have`` (R,) bool -> (R,4) float64: int64
+    up to D, A, B, then float64, an operation a line"""
     N, spx, spy, sqx, sqy, spp, sdot, scross = sums.unbind(dim=1)
-    have = head[:, 2] >= 0
     F64 = torch.float64
     D = torch.where(have, N * spp - (spx * spx + spy * spy), torch.ones_like(N)).to(F64)
     A = (N * sdot - (spx * sqx + spy * sqy)).to(F64)
@@ -1873,9 +1881,130 @@ def motion_table_torch(trajs, vis, frame0, vis_logit, K, thr4, seed):
     ty = ty + are * spy
     ty = (sqy - ty) / n4
     one, zero = torch.ones_like(are), torch.zeros_like(are)
-    model = torch.stack([torch.where(have, are, one), torch.where(have, aim, zero), torch.where(have, tx, zero),
-                         torch.where(have, ty, zero)], dim=1)
-    return head, sums, model, flags
+    return torch.stack([torch.where(have, are, one), torch.where(have, aim, zero), torch.where(have, tx, zero),
+                        torch.where(have, ty, zero)], dim=1)
+
+
+MOTION_LAYER_SEED = 0x632BE5AB                                                                   # seed_l = seed + l * this, mod 2^32
+MOTION_NO_LAYER, MOTION_NOT_VALID = 254, 255                                                     # pips_motion_layers' labels
+
+
+def motion_layers_table_torch(trajs, vis, frame0, vis_logit, K, thr4, seed, L, min_in, prev_layer=None):
+    """pips_motion_layers (include/pips_hip.h) as int64 / float64 torch ops, on any device: rows trajs (F,n,2), vis (F,n) logits or
+    None and prev_layer (n,) uint8 or None -> (head (P,L,4) int64, sums (P,L,8) int64, model (P,L,4) float64, box (P,L,4) int64,
+    layer (P,n) uint8, overlap (P,L,L) int64) for the P = max(F - 1, 0) pairs of consecutive rows: ``motion_table_torch``'s consensus
+    peeled L times on the columns left over, equal to the kernels' in every bit."""
+    if trajs.dim() != 3 or trajs.shape[2] != 2:
+        raise ValueError(f"trajs must be (F,n,2), not {tuple(trajs.shape)}")
+    F, n = trajs.shape[:2]
+    if vis is not None and tuple(vis.shape) != (F, n):
+        raise ValueError(f"vis must be (F,n) = {(F, n)}, not {tuple(vis.shape)}")
+    if prev_layer is not None and (tuple(prev_layer.shape) != (n,) or prev_layer.dtype != torch.uint8):
+        raise ValueError(f"prev_layer must be uint8 (n,) = {(n,)}, not {prev_layer.dtype} {tuple(prev_layer.shape)}")
+    K, thr4, frame0, seed, L, min_in = int(K), int(thr4), int(frame0), int(seed), int(L), int(min_in)
+    if n > ops.MOTION_N_MAX:
+        raise ValueError(f"{n} columns: the sums are exact up to {ops.MOTION_N_MAX}")
+    if not 1 <= K <= ops.MOTION_HYPS_MAX or not 1 <= thr4 <= ops.MOTION_THR4_MAX:
+        raise ValueError(f"need 1 <= K <= {ops.MOTION_HYPS_MAX} and 1 <= thr4 <= {ops.MOTION_THR4_MAX} (K={K}, thr4={thr4})")
+    if frame0 < 0 or frame0 + F > _INT_MAX or not 0 <= seed <= _M32:
+        raise ValueError(f"frame0 + F must fit an int32 and seed a uint32 (frame0={frame0}, seed={seed})")
+    if not 1 <= L <= ops.MOTION_LAYERS_MAX or not 2 <= min_in <= ops.MOTION_N_MAX:
+        raise ValueError(f"need 1 <= L <= {ops.MOTION_LAYERS_MAX} and 2 <= min_in <= {ops.MOTION_N_MAX} (L={L}, min_in={min_in})")
+    dev, I64, P = trajs.device, torch.int64, max(F - 1, 0)
+    s = trajs.to(torch.float32) * 4.0                                                            # exact
+    usable = (s.abs() <= float(ops.MOTION_QUARTER_MAX)).all(dim=2)                               # (a NaN compares false)
+    quarter = torch.where(usable.unsqueeze(2), s, torch.zeros_like(s)).round().to(I64)           # round-half-even
+    if vis is not None:
+        usable = usable & (vis.to(dev, torch.float32) > float(vis_logit))
+    head = torch.zeros(P, L, 4, dtype=I64, device=dev)
+    head[:, :, 2] = -1
+    sums = torch.zeros(P, L, 8, dtype=I64, device=dev)
+    box = torch.zeros(P, L, 4, dtype=I64, device=dev)
+    layer = torch.full((P, n), MOTION_NOT_VALID, dtype=torch.uint8, device=dev)
+    overlap = torch.zeros(P, L, L, dtype=I64, device=dev)
+    hyp = torch.arange(K, device=dev)
+    for f in range(1, F):
+        ok = usable[f - 1] & usable[f]
+        cols = torch.nonzero(ok).squeeze(1)                                                      # the list of layer 0
+        layer[f - 1, cols] = MOTION_NO_LAYER
+        for l in range(L):
+            m = int(cols.numel())
+            head[f - 1, l, 0] = m
+            if m < 2:
+                continue
+            seed_l = (seed + l * MOTION_LAYER_SEED) & _M32
+            p, q = quarter[f - 1][cols], quarter[f][cols]
+            i = (motion_mix(seed_l, frame0 + f, 2 * hyp) * m) >> 32
+            j = (motion_mix(seed_l, frame0 + f, 2 * hyp + 1) * (m - 1)) >> 32
+            j = j + (j >= i).to(I64)
+            d, e = p[j] - p[i], q[j] - q[i]
+            step = max(1, (1 << 22) // m)                                                        # hypotheses at a time
+            score = torch.cat([_motion_inliers(p, q, p[i[a:a + step]], q[i[a:a + step]], d[a:a + step], e[a:a + step], thr4).sum(dim=1)
+                               for a in range(0, K, step)])
+            best = int(score.max())
+            if best < (2 if l == 0 else min_in):
+                continue
+            h = int(torch.nonzero(score == best)[0, 0])                                          # ties: the lowest h
+            inl = _motion_inliers(p, q, p[i[h:h + 1]], q[i[h:h + 1]], d[h:h + 1], e[h:h + 1], thr4)[0]
+            p, q = p[inl], q[inl]
+            layer[f - 1, cols[inl]] = l
+            head[f - 1, l, 1], head[f - 1, l, 2] = best, h
+            sums[f - 1, l] = torch.stack([inl.sum(), p[:, 0].sum(), p[:, 1].sum(), q[:, 0].sum(), q[:, 1].sum(), (p * p).sum(),
+                                          (p * q).sum(), (p[:, 0] * q[:, 1] - p[:, 1] * q[:, 0]).sum()])
+            box[f - 1, l] = torch.cat([q.min(dim=0).values, q.max(dim=0).values])
+            cols = cols[~inl]                                                                    # the inliers leave, the order stays
+        before = layer[f - 2] if f >= 2 else None if prev_layer is None else prev_layer.to(dev)
+        if before is not None:
+            now, before = layer[f - 1].to(I64), before.to(I64)
+            both = (now < L) & (before < L)
+            overlap[f - 1] = torch.bincount((now * L + before)[both], minlength=L * L).view(L, L)
+    model = _motion_model(sums.view(P * L, 8), head.view(P * L, 4)[:, 2] >= 0).view(P, L, 4)
+    return head, sums, model, box, layer, overlap
+
+
+def link_layers(head, overlap, prev_ids=None, prev_counts=None, next_id=1):
+    """Object identities for ``pips_motion_layers``' layers, on the host, from ``head`` (P,L,4) and ``overlap`` (P,L,L) alone ->
+    (object_ids (P,L) int64, next_id).  Layer 0 with a model is the camera, id 0; a layer without a model has id -1.  For l = 1..L-1
+    in ascending order, with a model: the candidates are the layers b >= 1 of the pair before with an id >= 1 that no lower l of this
+    pair has taken; the b with the largest overlap[f][l][b] is taken, ties to the lowest b; its id is inherited iff overlap >= 1 and
+    2 overlap >= min(n_in[f][l], n_in[f-1][b]); otherwise the id is ``next_id``, which then goes up by one.  The first pair links
+    against ``prev_ids`` (L,) and ``prev_counts`` (L,) = the ids and n_in of the pair before the call when both are given, otherwise
+    against nothing.  Known limit: an identity has no memory beyond the previous pair -- an object that loses its layer for one pair
+    comes back under a new id."""
+    head, overlap = torch.as_tensor(head), torch.as_tensor(overlap)
+    if head.dim() != 3 or head.shape[2] != 4 or tuple(overlap.shape) != (head.shape[0], head.shape[1], head.shape[1]):
+        raise ValueError(f"head must be (P,L,4) and overlap (P,L,L), not {tuple(head.shape)} and {tuple(overlap.shape)}")
+    P, L = head.shape[:2]
+    next_id = _whole(next_id, "next_id", 1)
+    if (prev_ids is None) != (prev_counts is None):
+        raise ValueError("prev_ids and prev_counts are given together or not at all")
+    ids_before = counts_before = None
+    if prev_ids is not None:
+        ids_before = [int(v) for v in torch.as_tensor(prev_ids).reshape(-1).tolist()]
+        counts_before = [int(v) for v in torch.as_tensor(prev_counts).reshape(-1).tolist()]
+        if len(ids_before) != L or len(counts_before) != L:
+            raise ValueError(f"prev_ids and prev_counts must hold {L} entries")
+    n_in, have, over = head[:, :, 1].tolist(), (head[:, :, 2] >= 0).tolist(), overlap.tolist()
+    out = []
+    for f in range(P):
+        ids, taken = [-1] * L, set()
+        if L and have[f][0]:
+            ids[0] = 0
+        for l in range(1, L):
+            if not have[f][l]:
+                continue
+            best, best_b = 0, -1
+            for b in range(1, L if ids_before is not None else 0):
+                if ids_before[b] >= 1 and b not in taken and over[f][l][b] > best:               # (ties: the lowest b stays)
+                    best, best_b = over[f][l][b], b
+            if best_b >= 0 and 2 * best >= min(n_in[f][l], counts_before[best_b]):
+                ids[l] = ids_before[best_b]
+                taken.add(best_b)
+            else:
+                ids[l], next_id = next_id, next_id + 1
+        out.append(ids)
+        ids_before, counts_before = ids, n_in[f]
+    return torch.tensor(out, dtype=torch.int64).view(P, L), next_id
 
 
 MOTION_ENGINES = ("library", "torch")
@@ -2013,6 +2142,138 @@ class MotionEstimator:
                                                             ids=ids, frame0=frame0, **self.params)
         self.row, self.vis_row, self.ids = now[m - 1], None if vis is None else now_vis[m - 1], ids
         return models
+
+
+# ---------------------------------------------------------------------------------------------- moving objects from tracks
+_MOTION_LAYER_PARAMS = _MOTION_PARAMS + ("layers", "min_inliers")
+_MOTION_LAYER_DEFAULTS = dict(thr=2.0, hypotheses=256, vis_thr=0.5, seed=0, layers=4, min_inliers=8)
+
+
+def _motion_layers_run(engine, trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed, layers, min_inliers, prev_layer=None,
+                       prev_ids=None, prev_counts=None, next_id=1):
+    """``motion_layers`` / ``motion_layers_torch`` with the state a stream carries from call to call: ``prev_layer`` (n,) uint8 are
+    the library's labels of the pair before the call in the CALLER's column order, ``prev_ids`` / ``prev_counts`` / ``next_id``
+    are ``link_layers``' -> (the six results, layer (P,n) uint8 in the caller's order, next_id)"""
+    rows, vis, order, (frame0, vis_logit, K, thr4, seed) = _motion_setup(trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed)
+    L, min_in = _whole(layers, "layers", 1), _whole(min_inliers, "min_inliers", 2)
+    if L > ops.MOTION_LAYERS_MAX or min_in > ops.MOTION_N_MAX:
+        raise ValueError(f"layers must lie in 1..{ops.MOTION_LAYERS_MAX} and min_inliers in 2..{ops.MOTION_N_MAX}, not {layers!r} "
+                         f"and {min_inliers!r}")
+    if prev_layer is not None:
+        prev_layer = prev_layer.to(rows.device)
+        prev_layer = prev_layer if order is None else prev_layer[order]
+    table = ops.motion_layers if engine == "library" else motion_layers_table_torch
+    head, _, model, box, layer, overlap = table(rows, vis, frame0, vis_logit, K, thr4, seed, L, min_in, prev_layer)
+    if order is not None:
+        back = torch.empty_like(layer)
+        back[:, order] = layer
+        layer = back
+    head = head.to(torch.int64)
+    object_ids, next_id = link_layers(head.cpu(), overlap.cpu(), prev_ids, prev_counts, next_id)
+    object_ids = object_ids.to(rows.device)
+    at = layer.to(torch.int64)
+    labels = torch.where(at == MOTION_NOT_VALID, -2, torch.where(at == MOTION_NO_LAYER, -1, at))
+    P = head.shape[0]
+    objects = torch.where(labels >= 0, torch.gather(object_ids, 1, labels.clamp(min=0)), labels) if P else labels
+    return (model, head[:, :, :2], labels, object_ids, objects, box.to(torch.float64) / 4.0), layer, next_id
+
+
+def motion_layers(trajs, vis=None, ids=None, frame0=0, thr=2.0, hypotheses=256, vis_thr=0.5, seed=0, layers=4, min_inliers=8):
+    """What moves, beside the camera: one ``pips_motion_layers`` call (``ops.motion_layers``; include/pips_hip.h has the rule) and
+    ``link_layers`` on its small tables.  For every pair of consecutive frames of trajs (1,F,n,2) (vis (1,F,n) logits or None) the
+    consensus similarity of ``motion_fit`` is found -- layer 0, the camera --, then found again on the valid columns left over, up
+    to ``layers`` times; a layer above 0 needs ``min_inliers`` columns to count.  The layers are linked from pair to pair into
+    objects by the columns they share.  Returns ``models`` (P,L,4) float64 (the identity without a model), ``counts`` (P,L,2) =
+    (columns the layer chose from, its inliers), ``labels`` (P,n) int64 with -2 for a column that is not valid, -1 for a valid one
+    in no layer and 0..L-1 otherwise, ``object_ids`` (P,L) int64 (0 the camera, >= 1 objects, -1 no model), ``objects`` (P,n) the
+    id of each column's layer (-2, -1 as in labels) and ``boxes`` (P,L,4) float64 = (min x, min y, max x, max y) px of each layer's
+    columns in the pair's second frame (zeros without a model).  The other arguments are ``motion_fit``'s; with ``ids`` the columns
+    are taken in ascending id order and come back in the caller's.  Known limits: similarities only; a layer is a motion, not a
+    compact region; no re-scoring after the refit; layers with the same motion are not merged; an identity has no memory beyond
+    the previous pair; no per-pixel masks."""
+    return _motion_layers_run("library", trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed, layers, min_inliers)[0]
+
+
+def motion_layers_torch(trajs, vis=None, ids=None, frame0=0, thr=2.0, hypotheses=256, vis_thr=0.5, seed=0, layers=4, min_inliers=8):
+    """``motion_layers`` by ``motion_layers_table_torch``: the same rule as int64 / float64 torch ops on any device, equal in every
+    bit"""
+    return _motion_layers_run("torch", trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed, layers, min_inliers)[0]
+
+
+class MotionLayers:
+    """The moving objects of a streamed tracker, push by push: ``step(f0, trajs, vis, ids)`` takes the ``(f0, trajs (1,m,n,2), vis
+    (1,m,n)[, ids (n,)])`` of ``StreamTracker.push`` or ``CoverTracker.push`` and returns ``motion_layers``' six results for the
+    pairs that END on the frames ``f0 .. f0 + m - 1``, in the push's column order.  Like ``MotionEstimator`` it keeps the last row
+    and vis BY IDENTITY, and beside them the last pair's labels by identity (an identity it has not seen counts in no overlap),
+    the last pair's object ids and inlier counts and the next free id: stepping push by push gives what one ``motion_layers`` call
+    gives on the whole video laid out by identity, object ids included.  ``ids=None`` means the columns are stable; ``ids`` and
+    ``vis`` are each given on every step or on none.  ``params`` are ``motion_layers``' thr, hypotheses, vis_thr, seed, layers
+    and min_inliers; ``engine="torch"`` runs ``motion_layers_torch`` (any device) instead of the library."""
+
+    def __init__(self, engine="library", **params):
+        if engine not in MOTION_ENGINES:
+            raise ValueError(f"engine must be one of {MOTION_ENGINES}, not {engine!r}")
+        unknown = set(params) - set(_MOTION_LAYER_PARAMS)
+        if unknown:
+            raise ValueError(f"unknown arguments {sorted(unknown)}")
+        self.engine, self.params = engine, {**_MOTION_LAYER_DEFAULTS, **params}
+        _motion_layers_run("torch", torch.zeros(1, 0, 0, 2), None, None, 0, **self.params)
+        self.ids, self.row, self.vis_row, self.T = None, None, None, None           # the columns of ``row`` (n,2), the next frame
+        self.layer, self.object_ids, self.counts, self.next_id = None, None, None, 1   # of the last pair: labels (n,) uint8, (L,), (L,)
+
+    def _by_identity(self, kept, ids, fill, like):
+        """the kept per-column tensor in the columns of this push: ``fill`` for an identity that was not there"""
+        n = len(ids) if ids is not None else kept.shape[0]
+        out = torch.full((n,) + tuple(kept.shape[1:]), fill, dtype=kept.dtype, device=like.device)
+        if n == 0 or kept.shape[0] == 0:
+            return out
+        if ids is None:                                                             # (stable columns: step checked their number)
+            return kept.to(like.device).clone()
+        col = {i: j for j, i in enumerate(self.ids)}
+        new = [j for j, i in enumerate(ids) if i in col]
+        if new:
+            at, src = torch.tensor(new, device=like.device), torch.tensor([col[ids[j]] for j in new], device=like.device)
+            out[at] = kept.to(like.device)[src]
+        return out
+
+    @torch.no_grad()
+    def step(self, f0, trajs, vis=None, ids=None):
+        if trajs.dim() != 4 or trajs.shape[0] != 1 or trajs.shape[3] != 2:
+            raise ValueError(f"trajs must be (1,m,n,2), not {tuple(trajs.shape)}")
+        if self.T is not None and int(f0) != self.T:
+            raise ValueError(f"rows of frame {int(f0)} after frame {self.T - 1}")
+        m, n = trajs.shape[1:3]
+        if vis is not None and tuple(vis.shape) != (1, m, n):
+            raise ValueError(f"vis must be (1,m,n) = {(1, m, n)}, not {tuple(vis.shape)}")
+        if ids is not None:
+            ids = [int(i) for i in torch.as_tensor(ids).reshape(-1).tolist()]
+            if len(ids) != n or len(set(ids)) != n:
+                raise ValueError(f"ids must name the {n} columns, each once")
+        elif self.row is not None and self.row.shape[0] != n:
+            raise ValueError(f"{n} columns after {self.row.shape[0]}: pass ids when the columns change")
+        if self.row is not None and (vis is None) != (self.vis_row is None):
+            raise ValueError("vis must be given on every step or on none")
+        if self.row is not None and (ids is None) != (self.ids is None):
+            raise ValueError("ids must be given on every step or on none: the kept row and labels are matched by identity")
+        self.T = int(f0) + m
+        now = trajs[0].to(torch.float32)
+        now_vis = None if vis is None else vis[0].to(now.device, torch.float32)
+        rows, all_vis, frame0, prev_layer = now, now_vis, int(f0), None
+        if m > 0 and self.row is not None:
+            nan = float("nan")
+            rows, frame0 = torch.cat([self._by_identity(self.row, ids, nan, now).unsqueeze(0), now]), int(f0) - 1
+            if vis is not None:
+                all_vis = torch.cat([self._by_identity(self.vis_row, ids, nan, now).unsqueeze(0), now_vis])
+            if self.layer is not None:
+                prev_layer = self._by_identity(self.layer, ids, MOTION_NOT_VALID, now)
+        out, layer, self.next_id = _motion_layers_run(self.engine, rows.unsqueeze(0), None if all_vis is None else all_vis.unsqueeze(0),
+                                                      ids, frame0, **self.params, prev_layer=prev_layer, prev_ids=self.object_ids,
+                                                      prev_counts=self.counts, next_id=self.next_id)
+        if m > 0:
+            self.row, self.vis_row, self.ids = now[m - 1], None if vis is None else now_vis[m - 1], ids
+        if layer.shape[0] > 0:
+            self.layer, self.object_ids, self.counts = layer[-1], out[3][-1].cpu(), out[1][-1, :, 1].cpu()
+        return out
 
 
 def motion_path(models):

@@ -1035,6 +1035,59 @@ def motion_fit(trajs, vis, frame0, vis_logit, K, thr4, seed):
     return head, sums, model, flags
 
 
+MOTION_LAYERS_MAX = 8                                                              # PIPS_MOTION_LAYERS_MAX
+
+
+def motion_layers_workspace_bytes(F, n, K, L):
+    return int(_lib.load().pips_motion_layers_workspace_bytes(int(F), int(n), int(K), int(L)))
+
+
+def motion_layers(trajs, vis, frame0, vis_logit, K, thr4, seed, L, min_in, prev_layer=None):
+    """pips_motion_layers on device rows trajs (F,n,2) float32, vis (F,n) logits or None and prev_layer (n,) uint8 or None -> (head
+    (P,L,4) int32, sums (P,L,8) int64, model (P,L,4) float64, box (P,L,4) int32, layer (P,n) uint8, overlap (P,L,L) int32) for the
+    P = max(F - 1, 0) pairs of consecutive rows: the consensus of ``motion_fit`` peeled into L layers a pair (include/pips_hip.h has
+    the rule).  Outputs and workspace are allocated here: one call."""
+    assert trajs.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    if trajs.dim() != 3 or trajs.shape[2] != 2:
+        raise ValueError(f"trajs must be (F,n,2), not {tuple(trajs.shape)}")
+    src = _f32(trajs)
+    F, n = src.shape[:2]
+    if vis is not None:
+        if tuple(vis.shape) != (F, n):
+            raise ValueError(f"vis must be (F,n) = {(F, n)}, not {tuple(vis.shape)}")
+        vis = _f32(vis.to(src.device))
+    if prev_layer is not None:
+        if tuple(prev_layer.shape) != (n,) or prev_layer.dtype != torch.uint8:
+            raise ValueError(f"prev_layer must be uint8 (n,) = {(n,)}, not {prev_layer.dtype} {tuple(prev_layer.shape)}")
+        prev_layer = prev_layer.to(src.device).contiguous()
+    K, thr4, frame0, seed, L, min_in = int(K), int(thr4), int(frame0), int(seed), int(L), int(min_in)
+    if n > MOTION_N_MAX:
+        raise ValueError(f"{n} columns: the sums are exact up to {MOTION_N_MAX}")
+    if not 1 <= K <= MOTION_HYPS_MAX or not 1 <= thr4 <= MOTION_THR4_MAX:
+        raise ValueError(f"need 1 <= K <= {MOTION_HYPS_MAX} and 1 <= thr4 <= {MOTION_THR4_MAX} (K={K}, thr4={thr4})")
+    if frame0 < 0 or frame0 + F > 2 ** 31 - 1 or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"frame0 + F must fit an int32 and seed a uint32 (frame0={frame0}, seed={seed})")
+    if not 1 <= L <= MOTION_LAYERS_MAX or not 2 <= min_in <= MOTION_N_MAX:
+        raise ValueError(f"need 1 <= L <= {MOTION_LAYERS_MAX} and 2 <= min_in <= {MOTION_N_MAX} (L={L}, min_in={min_in})")
+    P, dev = max(F - 1, 0), src.device
+    head = torch.empty(P, L, 4, dtype=torch.int32, device=dev)
+    sums = torch.empty(P, L, 8, dtype=torch.int64, device=dev)
+    model = torch.empty(P, L, 4, dtype=torch.float64, device=dev)
+    box = torch.empty(P, L, 4, dtype=torch.int32, device=dev)
+    layer = torch.empty(P, n, dtype=torch.uint8, device=dev)
+    overlap = torch.empty(P, L, L, dtype=torch.int32, device=dev)
+    if P == 0:                                                                    # (nothing is launched, nothing to write)
+        return head, sums, model, box, layer, overlap
+    nbytes = motion_layers_workspace_bytes(F, n, K, L)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _call("pips_motion_layers", _lib.ptr(src) if n else None, _lib.ptr(vis) if n else None, _lib.ptr(prev_layer) if n else None, F, n,
+              frame0, float(vis_logit), K, thr4, seed - (1 << 32) if seed >= 1 << 31 else seed, L, min_in, _lib.ptr(head),
+              _lib.ptr(sums), _lib.ptr(model), _lib.ptr(box), _lib.ptr(layer) if n else None, _lib.ptr(overlap), _lib.ptr(ws), nbytes,
+              _stream())
+    return head, sums, model, box, layer, overlap
+
+
 def cover_place(seeds, table, h, w, cell, min_corner):
     """pips_cover_place: the seeds (k,3) = (t, x, y) of a cover step, float32 and contiguous, are moved IN PLACE onto the corners
     of ``table`` (gh,gw,3), the table of the seeds' frame, where the cell's score is above ``min_corner`` -> seeds"""
