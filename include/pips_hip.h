@@ -953,13 +953,86 @@ int    pips_motion_fit(const float* trajs, const float* vis, int F, int n, int f
  * overlap are zeros and every model is the identity.
  * Known limits: similarities only (no affine or homography layers); a layer is a motion, not a region -- nothing makes it spatially
  * compact; no re-scoring after the refit; layers whose motions coincide are not merged; the overlap table links a pair to the pair
- * before and no further, so an identity linked from it has no memory beyond one pair; labels are per track, there are no per-pixel
- * masks. */
+ * before and no further, so an identity linked from it has no memory beyond one pair; labels are per track (pips_object_masks
+ * below makes the per-pixel masks). */
 #define PIPS_MOTION_LAYERS_MAX  8
 size_t pips_motion_layers_workspace_bytes(int F, int n, int K, int L);
 int    pips_motion_layers(const float* trajs, const float* vis, const uint8_t* prev_layer, int F, int n, int frame0, float vis_logit,
                           int K, int thr4, int seed, int L, int min_in, int32_t* head, int64_t* sums, double* model, int32_t* box,
                           uint8_t* layer, int32_t* overlap, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Object masks: pips_object_masks turns a label per TRACK (pips_motion_layers' `layer` rows, or any uint8 labels) into a label per
+ * PIXEL of an h x w image: every pixel takes the label its nearest tracks vote for.  Integers only behind the quantisation:
+ *  - positions: frame k of the call uses row r = first + k of trajs (G,n,2) float32 and of labels (G,n) uint8.  A position becomes
+ *    Q, in eighths of a pixel of the h x w mask, by pips_tracks_draw's rule above, word for word (the same device function): the
+ *    scaling from src_h x src_w when the sizes differ, one rounding per operation, Q = floor(8 u + 0.5), and the point is ABSENT for
+ *    NaN, infinities and |u| > 32768 in x or in y.  Pixel (X, Y) has its centre at (8 X, 8 Y);
+ *  - who takes part: column i takes part in frame k when its point of row r is present and labels[r][i] != PIPS_MASK_NONE (255);
+ *  - candidates of a pixel: the participating columns with dx = 8 X - Qx, dy = 8 Y - Qy, |dx| <= radius8, |dy| <= radius8 and
+ *    d2 = dx^2 + dy^2 <= radius8^2 (a column at exactly the radius is in);
+ *  - order: candidates are ordered by the key (d2, column): of two candidates at the same distance the lower column is nearer;
+ *  - vote: the min(vote, candidates) nearest candidates vote, one each, for their label; the pixel gets the label with the most
+ *    votes, and among labels with equally many the one that holds the smallest key;
+ *  - a pixel with no candidate gets PIPS_MASK_NONE;
+ *  - what is written: every byte of the w x h image of every frame, frame k at mask + k step, row Y at + Y pitch (bytes).  Pitch
+ *    padding and the gap between frames are never written.
+ * Limits: radius8 in 0..PIPS_MASK_RADIUS8_MAX (256 px), vote in 1..PIPS_MASK_VOTE_MAX, n <= PIPS_MASK_N_MAX, h and w <=
+ * PIPS_DRAW_DIM_MAX.  With these d2 <= 2^22 and the key d2 2^24 + column 2^8 + label fits an int64 (below 2^48).
+ * drivers.object_masks_torch is the same rule in int64 torch ops: every byte is compared.
+ * Two launches on `stream`: one thread per (frame, column) writes an 8-byte record into the workspace -- Qx, and Qy 2^8 + label
+ * (|Q| < 2^19), or ABSENT for a column that takes no part; then one 256-thread block per 32 x 32 pixel tile and frame walks the
+ * records 256 at a time, compacts those within radius8 of the tile in column order (a wave ballot and a prefix over the four
+ * waves in LDS) and every thread keeps the `vote` smallest keys of its four neighbouring pixels of a row in registers; it stores
+ * them as one dword where the address allows.  No atomics, no allocation, no synchronisation; the workspace is read and written by
+ * this call only and may be reused by the next.
+ * pips_object_masks_workspace_bytes(F, n) = 8 F n; 0 for F < 0, n < 0 or n > PIPS_MASK_N_MAX.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "object_masks:": F < 0, n < 0 or G < 0; n >
+ * PIPS_MASK_N_MAX; h, w, src_h or src_w < 1; h or w > PIPS_DRAW_DIM_MAX; radius8 or vote outside its range; first < 0 or first + F >
+ * G; pitch < w; with F > 1 a step below pitch x h; with F > 0 a NULL mask; with F > 0 and n > 0 a NULL trajs, labels or workspace,
+ * workspace_bytes below the figure above, a workspace off a 16-byte address.  F = 0 launches nothing and returns PIPS_OK; n = 0
+ * needs no trajs, labels or workspace and fills the images with PIPS_MASK_NONE.
+ *
+ * pips_masks_tint shows such a label plane on F caller-owned surfaces of h x w IN PLACE: a colour and an opacity per (frame,
+ * label).  Formats, planes, pitches and steps are pips_tracks_draw's: the seven 8-bit formats RGB24, BGR24, RGBA32, BGRA32, NV12,
+ * I420 and PLANAR8.  mask: frame k at mask + k mask_step, row Y at + Y mask_pitch, a byte a pixel (the surface's own size).
+ * colors (F,C,3) uint8 R G B on the DEVICE; alpha (F,C) int in 0..256 on the HOST -- the library reads it before the launch and
+ * passes it by value, so it can be checked and may be freed on return; 1 <= C <= PIPS_MASK_LABELS_MAX.
+ *  - a pixel of frame f whose label l < C has the opacity A = alpha[f][l] and the colour colors[f][l], for NV12 and I420 converted
+ *    once to Y Cb Cr by pips_tracks_draw's 8-bit table (matrix and range are looked at for these two only); a label >= C has
+ *    A = 0 (PIPS_MASK_NONE is such a label);
+ *  - a full-resolution sample (R, G, B or Y) goes to p' = (p (256 - A) + c A + 128) >> 8;
+ *  - a 4:2:0 chroma sample, the sums running over those of its 2 x 2 pixels j that lie inside the image, goes to
+ *    p' = (p (1024 - S A_j) + S c_j A_j + 512) >> 10 (the edge samples of an odd h or w keep the denominator, as in draw);
+ *  - a weight of 0 leaves the sample as it is.  The alpha byte of RGBA32 / BGRA32, pitch padding and gaps are never written.
+ * drivers.tint_masks_torch is the same rule in int64 torch ops: every byte is compared.
+ * One launch per floor(1024 / C) frames on `stream` (1024 opacities travel in a launch's arguments: one launch for 128 frames of
+ * 8 labels), no workspace: a 256-thread block per 64 x 32 pixel tile and frame first converts the frame's C (opacity, colour) pairs
+ * into LDS; a thread owns 4 x 2 pixels and their two chroma samples, reads its labels as dwords and, where any has a weight, the
+ * samples as dwords where the address allows; four samples that the blend leaves as they were are not stored, so a tile whose
+ * labels all have weight 0 touches no surface byte.  No atomics, no allocation, no synchronisation.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "masks_tint:": a format that is not one of the seven
+ * (P010 and I010 among them); an unknown matrix or range with NV12 or I420; F < 0; h or w < 1 or > PIPS_DRAW_DIM_MAX; C outside
+ * 1..PIPS_MASK_LABELS_MAX; a pitch below the bytes of a row of its plane or of the mask; with F > 1 a step below pitch x rows; and
+ * with F > 0: a NULL plane that the format has, a NULL mask, colors or alpha, an alpha entry outside 0..256.  F = 0 launches nothing.
+ * Known limits: the nearest tracks decide, not the image -- no edge-aware or photometric refinement; no tint on P010 / I010; no
+ * outlines, no text; a mask is made from one row alone (no temporal smoothing); mask and surface have one size; the mask, colors
+ * and the workspace may not overlap a plane. */
+#define PIPS_MASK_NONE        255
+#define PIPS_MASK_RADIUS8_MAX 2048
+#define PIPS_MASK_VOTE_MAX    5
+#define PIPS_MASK_N_MAX       65536
+#define PIPS_MASK_LABELS_MAX  255
+size_t pips_object_masks_workspace_bytes(int F, int n);
+int    pips_object_masks(const float* trajs, const uint8_t* labels, int G, int n, int first, int F,
+                         int src_h, int src_w, int h, int w, int radius8, int vote,
+                         uint8_t* mask, size_t pitch, size_t step,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int    pips_masks_tint(int format, int matrix, int range, int F, int h, int w,
+                       void* p0, size_t pitch0, size_t step0,
+                       void* p1, size_t pitch1, size_t step1,
+                       void* p2, size_t pitch2, size_t step2,
+                       const uint8_t* mask, size_t mask_pitch, size_t mask_step,
+                       const uint8_t* colors, const int* alpha, int C, void* stream);
 
 /* Frames out, stabilised: pips_frames_warp resamples F frames from the `src` surfaces into the `dst` surfaces, format and size the
  * same on both sides, through one affine map per frame -- what a stabiliser does with pips_motion_fit's models

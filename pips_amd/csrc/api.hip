@@ -2093,6 +2093,79 @@ int pips_tracks_draw_ex(int format, int matrix, int range, int F, int h, int w, 
                            workspace, workspace_bytes, stream);
 }
 
+// ---- object masks
+size_t pips_object_masks_workspace_bytes(int F, int n) {
+    if (F < 0 || n < 0 || n > PIPS_MASK_N_MAX) return 0;
+    return (size_t)F * (size_t)n * MASK_REC_BYTES;
+}
+int pips_object_masks(const float* trajs, const uint8_t* labels, int G, int n, int first, int F, int src_h, int src_w, int h, int w,
+                      int radius8, int vote, uint8_t* mask, size_t pitch, size_t step, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    PIPS_CHECK_ARG(F >= 0 && n >= 0 && G >= 0, "object_masks: need F >= 0, n >= 0 and G >= 0 (F=%d, n=%d, G=%d)", F, n, G);
+    PIPS_CHECK_ARG(n <= PIPS_MASK_N_MAX, "object_masks: at most %d columns (n=%d): a key holds 16 bits of column", PIPS_MASK_N_MAX, n);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1 && src_h >= 1 && src_w >= 1,
+                   "object_masks: need sizes of at least 1x1 (h=%d, w=%d, src_h=%d, src_w=%d)", h, w, src_h, src_w);
+    PIPS_CHECK_ARG(h <= PIPS_DRAW_DIM_MAX && w <= PIPS_DRAW_DIM_MAX, "object_masks: masks up to %d a side (h=%d, w=%d)",
+                   PIPS_DRAW_DIM_MAX, h, w);
+    PIPS_CHECK_ARG(radius8 >= 0 && radius8 <= PIPS_MASK_RADIUS8_MAX, "object_masks: radius8=%d eighths outside 0..%d", radius8,
+                   PIPS_MASK_RADIUS8_MAX);
+    PIPS_CHECK_ARG(vote >= 1 && vote <= PIPS_MASK_VOTE_MAX, "object_masks: vote=%d outside 1..%d", vote, PIPS_MASK_VOTE_MAX);
+    PIPS_CHECK_ARG(first >= 0 && (long long)first + F <= (long long)G, "object_masks: rows [%d, %d + %d) of %d", first, first, F, G);
+    PIPS_CHECK_ARG(pitch >= (size_t)w, "object_masks: pitch %zu is below the %d bytes of a row", pitch, w);
+    PIPS_CHECK_ARG(F <= 1 || (step >= pitch && step / pitch >= (size_t)h), "object_masks: step %zu is below pitch %zu x %d rows", step,
+                   pitch, h);
+    if (F == 0) return PIPS_OK;
+    PIPS_CHECK_ARG(mask != nullptr, "object_masks: null mask");
+    if (n > 0) {
+        PIPS_CHECK_ARG(trajs && labels && workspace, "object_masks: null trajs, labels or workspace");
+        const size_t need = pips_object_masks_workspace_bytes(F, n);
+        PIPS_CHECK_ARG(workspace_bytes >= need, "object_masks: workspace %zu < %zu bytes", workspace_bytes, need);
+        PIPS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "object_masks: the workspace must lie on a 16-byte address");
+    }
+    return launch_object_masks(trajs, labels, n, first, F, src_h, src_w, h, w, radius8, vote, mask, pitch, step, workspace,
+                               (hipStream_t)stream);
+}
+int pips_masks_tint(int format, int matrix, int range, int F, int h, int w, void* p0, size_t pitch0, size_t step0, void* p1,
+                    size_t pitch1, size_t step1, void* p2, size_t pitch2, size_t step2, const uint8_t* mask, size_t mask_pitch,
+                    size_t mask_step, const uint8_t* colors, const int* alpha, int C, void* stream) {
+    PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I420) || format == PIPS_FMT_PLANAR8,
+                   "masks_tint: format %d is not one of the seven 8-bit surfaces", format);
+    const bool semi = format == PIPS_FMT_NV12, yuv = semi || format == PIPS_FMT_I420, planar = format == PIPS_FMT_PLANAR8;
+    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
+                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
+                   "masks_tint: unknown matrix %d or range %d", matrix, range);
+    PIPS_CHECK_ARG(F >= 0, "masks_tint: need F >= 0 (F=%d)", F);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1, "masks_tint: need a size of at least 1x1 (h=%d, w=%d)", h, w);
+    PIPS_CHECK_ARG(h <= PIPS_DRAW_DIM_MAX && w <= PIPS_DRAW_DIM_MAX, "masks_tint: surfaces up to %d a side (h=%d, w=%d)",
+                   PIPS_DRAW_DIM_MAX, h, w);
+    PIPS_CHECK_ARG(C >= 1 && C <= PIPS_MASK_LABELS_MAX, "masks_tint: C=%d labels outside 1..%d", C, PIPS_MASK_LABELS_MAX);
+    // plane k of the format: its rows and the bytes of a row (pips_tracks_draw's geometry)
+    void* p[3] = {p0, p1, p2};
+    const size_t pitch[3] = {pitch0, pitch1, pitch2}, step[3] = {step0, step1, step2};
+    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2;
+    const int planes = semi ? 2 : (yuv || planar) ? 3 : 1;
+    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : (yuv || planar) ? 1 : 3;
+    const size_t rows[3] = {(size_t)h, planar ? (size_t)h : ch, planar ? (size_t)h : ch};
+    const size_t row_bytes[3] = {(size_t)w * bpp, planar ? (size_t)w : (semi ? 2 * cw : cw), planar ? (size_t)w : cw};
+    for (int k = 0; k < planes; ++k) {
+        PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "masks_tint: pitch %zu of plane %d is below the %zu bytes of a row", pitch[k], k,
+                       row_bytes[k]);
+        PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
+                       "masks_tint: step %zu of plane %d is below pitch %zu x %zu rows", step[k], k, pitch[k], rows[k]);
+    }
+    PIPS_CHECK_ARG(mask_pitch >= (size_t)w, "masks_tint: mask pitch %zu is below the %d bytes of a row", mask_pitch, w);
+    PIPS_CHECK_ARG(F <= 1 || (mask_step >= mask_pitch && mask_step / mask_pitch >= (size_t)h),
+                   "masks_tint: mask step %zu is below pitch %zu x %d rows", mask_step, mask_pitch, h);
+    if (F == 0) return PIPS_OK;
+    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(p[k] != nullptr, "masks_tint: null plane %d", k);
+    PIPS_CHECK_ARG(mask && colors && alpha, "masks_tint: null mask, colors or alpha");
+    for (size_t k = 0; k < (size_t)F * (size_t)C; ++k)                                      // (a host array: read here, passed by value)
+        PIPS_CHECK_ARG(alpha[k] >= 0 && alpha[k] <= 256, "masks_tint: alpha[%zu][%zu]=%d outside 0..256", k / (size_t)C, k % (size_t)C,
+                       alpha[k]);
+    return launch_masks_tint(format, matrix, range, F, h, w, p, pitch, step, mask, mask_pitch, mask_step, colors, alpha, C,
+                             (hipStream_t)stream);
+}
+
 // ---- motion
 static bool motion_shape_ok(int F, int n, int K) {
     return F >= 0 && F <= PIPS_MOTION_ROWS_MAX && n >= 0 && n <= PIPS_MOTION_N_MAX && K >= 1 && K <= PIPS_MOTION_HYPS_MAX;

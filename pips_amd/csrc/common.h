@@ -561,6 +561,19 @@ int launch_tracks_draw(int format, int matrix, int range, int F, int h, int w, v
                        const float* trajs, const float* vis, int n, int first, int src_h, int src_w, const unsigned char* colors,
                        const DrawStyle& style, const int* fade, int* workspace, hipStream_t st);
 
+// ---- masks.hip: a label per pixel from a label per track (pips_object_masks) and that plane tinted onto surfaces in place
+// (pips_masks_tint).  The workspace of the masks holds one record of MASK_REC_BYTES per (frame, column): Qx and Qy * 256 + label;
+// n == 0 runs the raster launch alone (every pixel PIPS_MASK_NONE) and reads no workspace.  alpha of the tint is a HOST array: it
+// travels to the kernels by value, TINT_ALPHAS entries a launch, so F frames take ceil(F / (TINT_ALPHAS / C)) launches.  Arguments
+// checked by the caller.
+constexpr int MASK_REC_BYTES = 8;
+constexpr int TINT_ALPHAS = 1024;
+int launch_object_masks(const float* trajs, const unsigned char* labels, int n, int first, int F, int src_h, int src_w, int h, int w,
+                        int radius8, int vote, unsigned char* mask, size_t pitch, size_t step, void* workspace, hipStream_t st);
+int launch_masks_tint(int format, int matrix, int range, int F, int h, int w, void* const* p, const size_t* pitch, const size_t* step,
+                      const unsigned char* mask, size_t mpitch, size_t mstep, const unsigned char* colors, const int* alpha, int C,
+                      hipStream_t st);
+
 // ---- motion.hip: the consensus similarity between consecutive rows of a trajectory tensor (pips_motion_fit).  The workspace holds,
 // for each of the F - 1 pairs, the quantised valid columns in column order (n slots of four int16), their number, and the best
 // (score, hypothesis) key of each block of MOTION_HYPS hypotheses; arguments checked by the caller (the workspace on a 16-byte

@@ -7,6 +7,7 @@
 // _ex entry has a fade table: the same body with a factor per subsample in place of the coverage mask).  No atomics: a pixel is
 // owned by one thread, which applies the tracks in column order.  Nothing outside the w x h image of a plane is written.
 #include "common.h"
+#include "draw_quant.h"
 #include "fp_rn.h"
 #include "yuv.h"
 
@@ -16,7 +17,6 @@ namespace {
 
 constexpr int DRAW_THREADS = 256;
 constexpr int DRAW_TILE = 16;                                   // pixels a side: 256 pixels, 8 x 8 chroma samples
-constexpr int DRAW_ABSENT = INT_MIN;                            // x of a point that is not there
 enum { DRAW_PACKED3 = 0, DRAW_PACKED4 = 1, DRAW_NV12 = 2, DRAW_I420 = 3, DRAW_PLANAR8 = 4, DRAW_P010 = 5, DRAW_I010 = 6 };
 // The workspace: first the boxes, one int4 per (frame, track) = x0, y0, x1, y1 of the pixels it can touch (inclusive; x0 > x1:
 // none) -- every tile of a frame reads all of them, 16 bytes a lane -- then the records of DRAW_REC_INTS + 2 (trail + 1) ints:
@@ -47,13 +47,7 @@ __device__ __forceinline__ unsigned short* dst_row16(const DrawDst& d, int k, in
     return (unsigned short*)dst_row(d, k, f, y);
 }
 
-// a coordinate of the model's frame -> eighths of a surface pixel, DRAW_ABSENT for NaN, infinities and |u| > 32768
-__device__ __forceinline__ int quantise(float x, bool scaled, float s) {
-    const float u = scaled ? sub_rn(mul_rn(add_rn(x, 0.5f), s), 0.5f) : x;
-    if (!(fabsf(u) <= 32768.0f)) return DRAW_ABSENT;
-    return (int)floorf(add_rn(mul_rn(u, 8.0f), 0.5f));
-}
-
+// (quantise and DRAW_ABSENT: draw_quant.h)
 // ------------------------------------------------------------------------------------------------------------------ prepare
 // One thread per (frame, track): the trail + 1 points of rows r - trail .. r quantised, the segments that are drawn, the box of
 // pixels with a subsample within the larger radius of a drawn end (clipped to the image), the opacity and the converted colour.

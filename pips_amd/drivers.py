@@ -2190,7 +2190,7 @@ def motion_layers(trajs, vis=None, ids=None, frame0=0, thr=2.0, hypotheses=256, 
     columns in the pair's second frame (zeros without a model).  The other arguments are ``motion_fit``'s; with ``ids`` the columns
     are taken in ascending id order and come back in the caller's.  Known limits: similarities only; a layer is a motion, not a
     compact region; no re-scoring after the refit; layers with the same motion are not merged; an identity has no memory beyond
-    the previous pair; no per-pixel masks."""
+    the previous pair; the labels are per track (``object_masks`` makes per-pixel masks of them)."""
     return _motion_layers_run("library", trajs, vis, ids, frame0, thr, hypotheses, vis_thr, seed, layers, min_inliers)[0]
 
 
@@ -2274,6 +2274,162 @@ class MotionLayers:
         if layer.shape[0] > 0:
             self.layer, self.object_ids, self.counts = layer[-1], out[3][-1].cpu(), out[1][-1, :, 1].cpu()
         return out
+
+
+# ---------------------------------------------------------------------------------------------- object masks from the layers
+def _masks_setup(trajs, labels, size, out_size, radius, vote, first):
+    """what ``object_masks`` and ``object_masks_torch`` make of their arguments -> (rows (F,n,2) float32, labels (F,n) uint8 with
+    255 for every value outside 0..254, (h, w), (src_h, src_w), radius8, vote, first)"""
+    if trajs.dim() != 4 or trajs.shape[0] != 1 or trajs.shape[3] != 2:
+        raise ValueError(f"trajs must be (1,F,n,2), not {tuple(trajs.shape)}")
+    rows = trajs[0].to(torch.float32)
+    F, n = rows.shape[:2]
+    labels = torch.as_tensor(labels)
+    if tuple(labels.shape) != (F, n) or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f"labels must be integers (F,n) = {(F, n)}, not {labels.dtype} {tuple(labels.shape)}")
+    labels = labels.to(rows.device, torch.int64)
+    labels = torch.where((labels >= 0) & (labels < ops.MASK_NONE), labels, ops.MASK_NONE).to(torch.uint8)
+    src = (int(size[0]), int(size[1]))
+    out = src if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not 0.0 <= radius <= ops.MASK_RADIUS8_MAX / 8:
+        raise ValueError(f"radius must lie in 0..{ops.MASK_RADIUS8_MAX // 8} px, not {radius!r}")
+    return rows, labels, out, src, _round_half_up(radius, 8.0), _whole(vote, "vote", 1), _whole(first, "first", 0)
+
+
+def object_masks(trajs, labels, size, out_size=None, radius=48.0, vote=1, first=0):
+    """A label per pixel from a label per track, one ``pips_object_masks`` call (``ops.object_masks``; include/pips_hip.h has the
+    rule): trajs (1,F,n,2) on the GPU are positions in a ``size`` = (H, W) image (the model's frames), labels (F,n) integers of
+    any dtype; a value outside 0..254 takes no part -- ``motion_layers``' -1 and -2 among them.  Returns (F - first, h, w) uint8,
+    ``out_size`` = (h, w) (default ``size``; a decoder's surface when it is larger: positions are mapped as ``draw_tracks`` maps
+    them): frame k is made from row ``first + k`` alone, every pixel taking the label that its ``vote`` nearest participating
+    tracks within ``radius`` px OF THE MASK vote for -- ties to the nearest -- and 255 where no track is that near.  With
+    ``vote=1`` the mask is the Voronoi diagram of the tracks cut off at ``radius``; a radius of about 1.5 x the track spacing
+    closes the cells of a regular cover.  With ``motion_layers``' result the call is ``object_masks(trajs[:, 1:], res_labels, size)``:
+    a pair's labels sit on its second frame, as its boxes do.  No stateful class is needed for a stream: a mask depends on one row
+    only, so a streaming user calls this per push on the labels ``MotionLayers.step`` returns and the rows the push brought."""
+    rows, labels, out, src, radius8, vote, first = _masks_setup(trajs, labels, size, out_size, radius, vote, first)
+    return ops.object_masks(rows, labels, out, src, radius8, vote, first)
+
+
+def object_masks_torch(trajs, labels, size, out_size=None, radius=48.0, vote=1, first=0):
+    """``object_masks`` as int64 torch ops on any device, equal in every byte: per frame the keys d2 2^24 + column 2^8 + label of
+    the participating columns at every pixel (2^62 outside the radius), the ``vote`` smallest by ``topk``, and the label with the
+    most votes among them, the first such in key order.  Rows of pixels are taken in slabs, each against the columns within the
+    radius of the slab.  Written to be read, not to be fast."""
+    rows, labels, (h, w), (src_h, src_w), radius8, vote, first = _masks_setup(trajs, labels, size, out_size, radius, vote, first)
+    G, n, F = ops.object_masks_check(rows, labels, (h, w), (src_h, src_w), radius8, vote, first)[:3]
+    dev = rows.device
+    out = torch.full((F, h, w), ops.MASK_NONE, dtype=torch.uint8, device=dev)
+    far = 1 << 62
+    X8 = (8 * torch.arange(w, device=dev)).view(1, 1, w)
+    for k in _range(F):
+        qx, okx = _draw_quantise(rows[first + k, :, 0], src_w, w)
+        qy, oky = _draw_quantise(rows[first + k, :, 1], src_h, h)
+        lab = labels[first + k].to(torch.int64)
+        part = okx & oky & (lab != ops.MASK_NONE)
+        slab = max(1, min(h, (1 << 22) // max(1, w * max(int(part.sum()), 1))))
+        for y0 in _range(0, h, slab):
+            y1 = min(h, y0 + slab)
+            col = torch.nonzero(part & (qy >= 8 * y0 - radius8) & (qy <= 8 * (y1 - 1) + radius8)).squeeze(1)
+            if col.numel() == 0:
+                continue
+            dx = X8 - qx[col].view(-1, 1, 1)
+            dy = (8 * torch.arange(y0, y1, device=dev)).view(1, -1, 1) - qy[col].view(-1, 1, 1)
+            d2 = dx * dx + dy * dy
+            near = (dx.abs() <= radius8) & (dy.abs() <= radius8) & (d2 <= radius8 * radius8)
+            key = torch.where(near, (d2 << 24) + (col.view(-1, 1, 1) << 8) + lab[col].view(-1, 1, 1), far)
+            top = torch.topk(key, min(vote, col.numel()), dim=0, largest=False).values          # ascending: the nearest first
+            took, vlab = top != far, top & 255
+            count = ((vlab.unsqueeze(0) == vlab.unsqueeze(1)) & took.unsqueeze(0) & took.unsqueeze(1)).sum(dim=1)   # votes of entry j's label
+            best, most = torch.full_like(vlab[0], ops.MASK_NONE), torch.zeros_like(vlab[0])
+            for j in _range(top.shape[0]):
+                better = took[j] & (count[j] > most)
+                best, most = torch.where(better, vlab[j], best), torch.where(better, count[j], most)
+            out[k, y0:y1] = best.to(torch.uint8)
+    return out
+
+
+def object_colors(object_ids, alpha=0.5, camera_alpha=0.0):
+    """The colours and opacities ``tint_masks`` takes, from ``motion_layers``' ``object_ids`` (P,L): -> (colors (P,L,3) uint8,
+    alpha (P,L) float64).  A mask holds LAYER indices, which an object may change from pair to pair; the colour of layer l of pair
+    f is ``track_colors`` of its OBJECT id, so an object keeps its colour for life.  The opacity is ``alpha`` for an object (id >=
+    1), ``camera_alpha`` for the camera (id 0) and 0 for a layer without a model (id -1)."""
+    object_ids = torch.as_tensor(object_ids)
+    if object_ids.dim() != 2 or object_ids.dtype.is_floating_point or object_ids.dtype == torch.bool:
+        raise ValueError(f"object_ids must be integers (P,L), not {object_ids.dtype} {tuple(object_ids.shape)}")
+    for v in (alpha, camera_alpha):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError(f"an opacity must lie in 0..1, not {v!r}")
+    ids = object_ids.to(torch.int64)
+    colors = track_colors(ids.clamp(min=0)).view(ids.shape[0], ids.shape[1], 3)
+    a = torch.full(ids.shape, float(alpha), dtype=torch.float64, device=ids.device)
+    a[ids == 0], a[ids < 0] = float(camera_alpha), 0.0
+    return colors, a
+
+
+def _tint_setup(planes, masks, colors, alpha):
+    """what ``tint_masks`` and ``tint_masks_torch`` make of their arguments -> (planes, masks, colors on the surfaces' device,
+    alpha (F,C) int64 0..256 on the host)"""
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    if not planes or not all(torch.is_tensor(p) for p in planes):
+        raise ValueError("planes must be a tensor or a sequence of tensors")
+    dev = planes[0].device
+    alpha = torch.as_tensor(alpha).to("cpu", torch.float64)
+    if alpha.numel() and not bool(((alpha >= 0.0) & (alpha <= 1.0)).all()):                      # (false for a NaN)
+        raise ValueError("an alpha must lie in 0..1")
+    return planes, masks.to(dev), colors.to(dev), torch.floor(alpha * 256.0 + 0.5).to(torch.int64)
+
+
+def tint_masks(planes, fmt, masks, colors, alpha, matrix="bt709", range="limited", inplace=False):
+    """Label planes shown on frames on the device, one ``pips_masks_tint`` call (``ops.masks_tint``; include/pips_hip.h has the
+    rule): ``planes`` / ``fmt`` are F surfaces in one of ``draw_tracks``' seven 8-bit layouts, ``masks`` (F,h,w) uint8 of the
+    surfaces' size (``object_masks``' result), ``colors`` (F,C,3) uint8 RGB and ``alpha`` (F,C) opacities in 0..1 per (frame,
+    label) -- ``object_colors`` makes both.  A pixel with label l < C is blended towards its colour with opacity round(256 alpha)
+    / 256; a label >= C, 255 among them, and an opacity of 0 leave the pixel.  ``inplace=False`` tints clones and returns them (a
+    tensor for one plane, a list otherwise); ``inplace=True`` tints the given tensors -- pitched views included."""
+    planes, masks, colors, alpha = _tint_setup(planes, masks, colors, alpha)
+    if not inplace:
+        planes = [p.clone() for p in planes]
+    ops.masks_tint(planes, fmt, masks, colors, alpha, matrix, range)
+    return planes[0] if len(planes) == 1 else planes
+
+
+def tint_masks_torch(planes, fmt, masks, colors, alpha, matrix="bt709", range="limited", inplace=False):
+    """``tint_masks`` as int64 torch ops on any device, equal in every byte: the opacity and the colour of every pixel looked up by
+    its label, the full-resolution samples blended with 256 - A, the 4:2:0 chroma samples with 1024 - the sum of A over each 2 x 2
+    block of the zero-padded opacities.  Written to be read, not to be fast."""
+    planes, masks, colors, alpha = _tint_setup(planes, masks, colors, alpha)
+    planes, F, h, w, C, alpha = ops.tint_check(planes, fmt, masks, colors, alpha, matrix, range)
+    if not inplace:
+        planes = [p.clone() for p in planes]
+    dev = planes[0].device
+    yuv = fmt in ("nv12", "i420")
+    comp = rgb_to_yuv_torch(colors, matrix, range) if yuv else colors.to(torch.int64)             # (F,C,3) in the surface's components
+    alpha = alpha.to(dev)
+    if fmt == "planar8":
+        full = [planes[0][:, c] for c in (0, 1, 2)]
+    elif yuv:
+        full = [planes[0]]
+        chroma = [planes[1][..., 0], planes[1][..., 1]] if fmt == "nv12" else [planes[1], planes[2]]
+    else:
+        full = [planes[0][..., c] for c in ((2, 1, 0) if fmt in ("bgr24", "bgra32") else (0, 1, 2))]
+    for f in _range(F):
+        l = masks[f].to(torch.int64)
+        known = l < C
+        at = l.clamp(max=C - 1)
+        A = torch.where(known, alpha[f][at], 0)                                                    # (h,w)
+        c = comp[f][at]                                                                            # (h,w,3)
+        for k, p in enumerate(full):
+            old = p[f].to(torch.int64)
+            p[f] = torch.where(A > 0, (old * (256 - A) + c[..., k] * A + 128) >> 8, old).to(torch.uint8)
+        if yuv:
+            pad = (0, w % 2, 0, h % 2)
+            SA = torch.nn.functional.pad(A, pad).view((h + 1) // 2, 2, (w + 1) // 2, 2).sum(dim=(1, 3))
+            for k, p in enumerate(chroma):
+                S = torch.nn.functional.pad(c[..., 1 + k] * A, pad).view((h + 1) // 2, 2, (w + 1) // 2, 2).sum(dim=(1, 3))
+                old = p[f].to(torch.int64)
+                p[f] = torch.where(SA > 0, (old * (1024 - SA) + S + 512) >> 10, old).to(torch.uint8)
+    return planes[0] if len(planes) == 1 else planes
 
 
 def motion_path(models):

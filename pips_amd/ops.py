@@ -395,6 +395,124 @@ def draw_tracks(planes, fmt, trajs, vis, colors, first=0, src_size=None, trail=1
             _call("pips_tracks_draw", *head, _lib.ptr(workspace), nbytes, _stream())
 
 
+# include/pips_hip.h: PIPS_MASK_*
+MASK_NONE, MASK_RADIUS8_MAX, MASK_VOTE_MAX, MASK_N_MAX, MASK_LABELS_MAX = 255, 2048, 5, 65536, 255
+MASK_TILE = 32                                                         # pips_amd/csrc/masks.hip: the pixels a side a raster block owns
+
+
+def object_masks_check(trajs, labels, size, src_size, radius8, vote, first):
+    """pips_object_masks' limits on the values, shared by ``object_masks`` and ``drivers.object_masks_torch`` -> (G, n, F, h, w,
+    src_h, src_w); the call makes the F = G - first frames of the rows ``first`` .. G - 1"""
+    if trajs.dim() != 3 or trajs.shape[2] != 2 or trajs.dtype != torch.float32:
+        raise ValueError(f"trajs must be float32 (G,n,2), not {trajs.dtype} {tuple(trajs.shape)}")
+    G, n = int(trajs.shape[0]), int(trajs.shape[1])
+    if tuple(labels.shape) != (G, n) or labels.dtype != torch.uint8:
+        raise ValueError(f"labels must be uint8 (G,n) = {(G, n)}, not {labels.dtype} {tuple(labels.shape)}")
+    if n > MASK_N_MAX:
+        raise ValueError(f"at most {MASK_N_MAX} columns, not {n}")
+    h, w = int(size[0]), int(size[1])
+    src_h, src_w = (h, w) if src_size is None else (int(src_size[0]), int(src_size[1]))
+    if min(h, w, src_h, src_w) < 1:
+        raise ValueError(f"sizes must be at least 1 x 1, not {h} x {w} from {src_h} x {src_w}")
+    if max(h, w) > DRAW_DIM_MAX:
+        raise ValueError(f"masks up to {DRAW_DIM_MAX} a side, not {h} x {w}")
+    if not 0 <= radius8 <= MASK_RADIUS8_MAX:
+        raise ValueError(f"radius8 must lie in 0..{MASK_RADIUS8_MAX} eighths of a pixel, not {radius8}")
+    if not 1 <= vote <= MASK_VOTE_MAX:
+        raise ValueError(f"vote must lie in 1..{MASK_VOTE_MAX}, not {vote}")
+    if not 0 <= first <= G:
+        raise ValueError(f"first = {first} of trajs with {G} rows")
+    return G, n, G - first, h, w, src_h, src_w
+
+
+def object_masks_workspace_bytes(F, n):
+    return int(_lib.load().pips_object_masks_workspace_bytes(int(F), int(n)))
+
+
+def object_masks(trajs, labels, size, src_size=None, radius8=384, vote=1, first=0, out=None, workspace=None):
+    """pips_object_masks: a label per pixel from a label per track.  trajs (G,n,2) float32 are pixels of a ``src_size`` = (src_h,
+    src_w) image (default ``size``), labels (G,n) uint8 with 255 for a column that takes no part; frame k of the result takes row
+    ``first + k`` -> (G - first, h, w) uint8, ``size`` = (h, w): every pixel the label that its ``vote`` nearest participating
+    tracks within ``radius8`` eighths of a pixel vote for, 255 where there is none (include/pips_hip.h has the whole rule).
+    ``out``: a uint8 (F,h,w) device tensor to write instead of a fresh one -- row and frame strides go through as pitch and step, so
+    a ``buffer[:, :h, :w]`` view of a pitched allocation is written as it is.  ``workspace``: a device tensor of at least
+    ``object_masks_workspace_bytes(F, n)`` bytes to use instead of a fresh one."""
+    radius8, vote, first = int(radius8), int(vote), int(first)
+    G, n, F, h, w, src_h, src_w = object_masks_check(trajs, labels, size, src_size, radius8, vote, first)
+    assert trajs.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = trajs.device
+    if out is None:
+        out = torch.empty(F, h, w, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, h, w):
+        raise ValueError(f"out must be uint8 (F,h,w) = {(F, h, w)}, not {out.dtype} {tuple(out.shape)}")
+    for t in (labels, out, workspace):
+        if t is not None and t.device != dev:
+            raise ValueError("trajs, labels, out and the workspace must live on one device")
+    if F == 0:
+        return out
+    pitch, step = _surface(out, (1,))
+    trajs, labels = trajs.contiguous(), labels.contiguous()
+    need = object_masks_workspace_bytes(F, n)
+    if workspace is None:
+        workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=dev)
+    nbytes = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(dev):
+        _call("pips_object_masks", _lib.ptr(trajs), _lib.ptr(labels), G, n, first, F, src_h, src_w, h, w, radius8, vote, _lib.ptr(out),
+              pitch, step, _lib.ptr(workspace), nbytes, _stream())
+    return out
+
+
+def tint_check(planes, fmt, masks, colors, alpha, matrix, range):
+    """pips_masks_tint's limits on the values, shared by ``masks_tint`` and ``drivers.tint_masks_torch`` -> (planes, F, h, w, C,
+    alpha (F,C) int64 on the host)"""
+    if fmt not in DRAW_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(DRAW_FORMATS)}, not {fmt!r}")
+    planes, F, h, w = draw_planes(planes, fmt)
+    if matrix not in IMPORT_MATRICES or range not in IMPORT_RANGES:
+        raise ValueError(f"matrix must be one of {sorted(IMPORT_MATRICES)} and range one of {sorted(IMPORT_RANGES)}, "
+                         f"not {matrix!r}, {range!r}")
+    if max(h, w) > DRAW_DIM_MAX:
+        raise ValueError(f"surfaces up to {DRAW_DIM_MAX} a side, not {h} x {w}")
+    if not torch.is_tensor(masks) or masks.dtype != torch.uint8 or tuple(masks.shape) != (F, h, w):
+        raise ValueError(f"masks must be uint8 (F,h,w) = {(F, h, w)}, not {getattr(masks, 'dtype', None)} {tuple(getattr(masks, 'shape', ()))}")
+    if not torch.is_tensor(colors) or colors.dtype != torch.uint8 or colors.dim() != 3 or colors.shape[0] != F or colors.shape[2] != 3:
+        raise ValueError(f"colors must be uint8 (F,C,3) with F = {F}, not {getattr(colors, 'dtype', None)} "
+                         f"{tuple(getattr(colors, 'shape', ()))}")
+    C = int(colors.shape[1])
+    if not 1 <= C <= MASK_LABELS_MAX:
+        raise ValueError(f"C must lie in 1..{MASK_LABELS_MAX}, not {C}")
+    alpha = torch.as_tensor(alpha)
+    if tuple(alpha.shape) != (F, C) or alpha.dtype.is_floating_point or alpha.dtype == torch.bool:
+        raise ValueError(f"alpha must be integers (F,C) = {(F, C)}, not {alpha.dtype} {tuple(alpha.shape)}")
+    alpha = alpha.to("cpu", torch.int64)
+    if alpha.numel() and (int(alpha.min()) < 0 or int(alpha.max()) > 256):
+        raise ValueError("an alpha must lie in 0..256")
+    return planes, F, h, w, C, alpha
+
+
+def masks_tint(planes, fmt, masks, colors, alpha, matrix="bt709", range="limited"):
+    """pips_masks_tint: the label planes ``masks`` (F,h,w) uint8 shown IN PLACE on the device surfaces ``planes`` of format ``fmt``
+    -- ``draw_tracks``' seven 8-bit formats and shapes.  A pixel of frame f with label l < C is blended towards ``colors[f][l]``
+    ((F,C,3) uint8 R G B on the device) with the opacity ``alpha[f][l]`` ((F,C) whole numbers 0..256; they are read on the host: a
+    device tensor is copied there first); a label >= C, 255 among them, leaves its pixel (include/pips_hip.h has the whole rule).
+    Row and frame strides of the surfaces and of the masks go through as pitch and step; a plane whose strides cannot be expressed
+    so is a ValueError."""
+    planes, F, h, w, nlab, alpha = tint_check(planes, fmt, masks, colors, alpha, matrix, range)
+    assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = planes[0].device
+    if masks.device != dev or colors.device != dev:
+        raise ValueError("masks and colors must live on the surfaces' device")
+    if F == 0:
+        return
+    args = draw_surfaces(planes, fmt)
+    mpitch, mstep = _surface(masks, (1,))
+    colors = colors.contiguous()
+    table = (C.c_int * (F * nlab))(*alpha.reshape(-1).tolist())                     # a host array: read before the launch
+    with torch.cuda.device(dev):
+        _call("pips_masks_tint", DRAW_FORMATS[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], F, h, w, *args, _lib.ptr(masks), mpitch,
+              mstep, _lib.ptr(colors), table, nlab, _stream())
+
+
 # include/pips_hip.h: PIPS_WARP_BORDER_*, PIPS_WARP_DIM_MAX; pips_amd/csrc/common.h: the tile and the staging budget of warp.hip
 WARP_BORDERS = {"constant": 0, "replicate": 1}
 WARP_DIM_MAX, WARP_TILE_W, WARP_TILE_H, WARP_LDS_BYTES = 8192, 64, 16, 12288
