@@ -400,7 +400,8 @@ int    pips_chain_hop_clips(const void* arena, const float* pyramid, int T, int 
  * A member of active / new_list outside [0, n) is never dereferenced (pips_chain_hop's rule).
  * n_act == 0 (round) or f0 == f1 (emit): PIPS_OK and nothing is done.  PIPS_E_ARG ahead of any launch: n < 1; n_act or n_new
  * outside [0, n]; n_new > n_act; L < 16; R < 9; T < 1; a map below 16 x 16 (round: the map size rule at pips_forward); f1 < f0 or
- * f1 - f0 > L; a NULL array (steps may be NULL).
+ * f1 - f0 > L; f1 - f0 > PIPS_STREAM_EMIT_FRAMES_MAX (emit puts a frame on each of the grid's rows of blocks: a longer ring is
+ * emitted in several calls); a NULL array (steps may be NULL).
  * PIPS_E_WORKSPACE: workspace_bytes < pips_stream_workspace_bytes(n, iters) (= pips_chain_workspace_bytes(n, iters) + the staging
  * of the join + the hop's unused compacted list).  A rejected call writes nothing.  No allocation, no synchronisation. */
 size_t pips_stream_workspace_bytes(int n, int iters);
@@ -437,8 +438,10 @@ int    pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, 
  * final at different frames.  Rows f mod L, f in [f0, f1), of those columns go to the dense out_trajs (f1-f0, m, 2) / out_vis
  * (f1-f0, m) as bit patterns, and 0x7fc00000 is stored back into exactly those elements; every other element stays bit-identical.
  * A member of cols outside [0, n) is skipped: nothing is read or reset, and its output elements receive the same NaN.  f0 == f1
- * or m == 0: PIPS_OK and nothing is done.  PIPS_E_ARG: n < 1, L < 16, m < 0, f1 < f0 or f1 - f0 > L, a NULL array. */
+ * or m == 0: PIPS_OK and nothing is done.  PIPS_E_ARG: n < 1, L < 16, m < 0, f1 < f0, f1 - f0 > L or
+ * > PIPS_STREAM_EMIT_FRAMES_MAX, a NULL array. */
 #define PIPS_STREAM_V_MAX 64
+#define PIPS_STREAM_EMIT_FRAMES_MAX 65535
 size_t pips_stream_workspace_bytes_clips(int n, int iters, int V);
 int    pips_stream_select_clips(int n, const int* tq, const float* xy, int* cur, int* status, const int* clip,
                                 const int* clip_frames, const int* clip_final, int V, float* trajs, int L,

@@ -1823,6 +1823,8 @@ int pips_stream_emit(float* trajs, float* vis, int L, int n, int f0, int f1, flo
     PIPS_CHECK_ARG(n >= 1, "stream_emit: need n >= 1 (n=%d)", n);
     PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_emit: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
     PIPS_CHECK_ARG(f1 >= f0 && (long long)f1 - f0 <= L, "stream_emit: need 0 <= f1 - f0 <= L (f0=%d, f1=%d, L=%d)", f0, f1, L);
+    PIPS_CHECK_ARG(f1 - f0 <= PIPS_STREAM_EMIT_FRAMES_MAX, "stream_emit: at most %d frames a call, one on each row of blocks (f0=%d, f1=%d)",
+                   PIPS_STREAM_EMIT_FRAMES_MAX, f0, f1);
     PIPS_CHECK_ARG(trajs && vis, "stream_emit: null pointer");
     if (f0 == f1) return PIPS_OK;                 // (no frame: the outputs are empty and may be NULL)
     PIPS_CHECK_ARG(out_trajs && out_vis, "stream_emit: null pointer");
@@ -1833,6 +1835,8 @@ int pips_stream_emit_cols(float* trajs, float* vis, int L, int n, int f0, int f1
     PIPS_CHECK_ARG(n >= 1 && m >= 0, "stream_emit_cols: need n >= 1 and m >= 0 (n=%d, m=%d)", n, m);
     PIPS_CHECK_ARG(L >= 2 * PIPS_S, "stream_emit_cols: a row ring needs L >= %d rows (L=%d)", 2 * PIPS_S, L);
     PIPS_CHECK_ARG(f1 >= f0 && (long long)f1 - f0 <= L, "stream_emit_cols: need 0 <= f1 - f0 <= L (f0=%d, f1=%d, L=%d)", f0, f1, L);
+    PIPS_CHECK_ARG(f1 - f0 <= PIPS_STREAM_EMIT_FRAMES_MAX, "stream_emit_cols: at most %d frames a call, one on each row of blocks (f0=%d, f1=%d)",
+                   PIPS_STREAM_EMIT_FRAMES_MAX, f0, f1);
     PIPS_CHECK_ARG(trajs && vis, "stream_emit_cols: null pointer");
     if (f0 == f1 || m == 0) return PIPS_OK;                 // (nothing to move: the outputs are empty and may be NULL)
     PIPS_CHECK_ARG(cols && out_trajs && out_vis, "stream_emit_cols: null pointer");
