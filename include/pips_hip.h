@@ -1017,9 +1017,10 @@ int    pips_motion_layers(const float* trajs, const float* vis, const uint8_t* p
  * (P010 and I010 among them); an unknown matrix or range with NV12 or I420; F < 0; h or w < 1 or > PIPS_DRAW_DIM_MAX; C outside
  * 1..PIPS_MASK_LABELS_MAX; a pitch below the bytes of a row of its plane or of the mask; with F > 1 a step below pitch x rows; and
  * with F > 0: a NULL plane that the format has, a NULL mask, colors or alpha, an alpha entry outside 0..256.  F = 0 launches nothing.
- * Known limits: the nearest tracks decide, not the image -- no edge-aware or photometric refinement; no tint on P010 / I010; no
- * outlines, no text; a mask is made from one row alone (no temporal smoothing); mask and surface have one size; the mask, colors
- * and the workspace may not overlap a plane. */
+ * Known limits: in pips_object_masks the nearest tracks decide, not the image (pips_object_masks_guided below lets the image's
+ * luma edges decide; no colour distances, no smoothing of the guide); no tint on P010 / I010; no outlines, no text; a mask is made
+ * from one row alone (no temporal smoothing); mask and surface have one size; the mask, colors and the workspace may not overlap a
+ * plane. */
 #define PIPS_MASK_NONE        255
 #define PIPS_MASK_RADIUS8_MAX 2048
 #define PIPS_MASK_VOTE_MAX    5
@@ -1036,6 +1037,76 @@ int    pips_masks_tint(int format, int matrix, int range, int F, int h, int w,
                        void* p2, size_t pitch2, size_t step2,
                        const uint8_t* mask, size_t mask_pitch, size_t mask_step,
                        const uint8_t* colors, const int* alpha, int C, void* stream);
+
+/* Object masks that follow image edges: pips_object_masks_guided makes the same label plane as pips_object_masks, but a pixel
+ * takes the label of the track that is nearest ALONG A PATH that avoids crossing luma edges -- a geodesic distance on an 8-bit
+ * guide plane of the mask's size (the surface's own luma) -- so the boundary between two labels runs along the object's outline
+ * where the image shows one, not halfway between two tracks.  Integers only behind the quantisation.  Per frame k of the call,
+ * row r = first + k:
+ *  - positions and who takes part: exactly pips_object_masks' rules -- Q in eighths of a pixel of the h x w mask by
+ *    pips_tracks_draw's quantisation (the same device function); column i takes part when its point is present and
+ *    labels[r][i] != PIPS_MASK_NONE;
+ *  - seeds: a participating column seeds the pixel X = (Qx + 4) >> 3, Y = (Qy + 4) >> 3 (arithmetic shift).  A seed pixel outside
+ *    the image seeds nothing;
+ *  - state: one 32-bit key per pixel, cost << 16 | column, or 0xFFFFFFFF for none.  A seed pixel starts with cost 0 and the
+ *    lowest column that seeds it; every other pixel starts as none;
+ *  - step cost: the step between 8-neighbours p and q, both inside the image, costs c(p,q) = L + edge |G(p) - G(q)|, L = 5 for
+ *    the four axial neighbours and L = 7 for the four diagonal ones (the 5-7 chamfer), G the guide plane: frame k at guide + k
+ *    guide_step, row Y at + Y guide_pitch, a byte a pixel;
+ *  - relaxation: key'(p) = min(key(p), min over the neighbours q that have a key and cost(q) + c(p,q) <= reach of
+ *    (cost(q) + c(p,q)) << 16 | column(q));
+ *  - result: the fixed point of that relaxation.  Every step costs at least 5, so a path within `reach` has at most
+ *    floor(reach / 5) steps and that many Jacobi applications from the seeds reach the fixed point; it equals Dijkstra on the
+ *    keys -- cost first, then the lower column;
+ *  - output: mask[Y][X] = labels[r][column] of the pixel's key, PIPS_MASK_NONE where it has none.  Every byte of the w x h image
+ *    of every frame is written; pitch padding and the gap between frames are never written.
+ * Limits: edge in 0..PIPS_MASK_EDGE_MAX, reach in 0..PIPS_MASK_REACH_MAX, n <= PIPS_MASK_N_MAX, h and w <= PIPS_DRAW_DIM_MAX.
+ * With these c <= 16327 and cost + c <= 49094: a key never wraps and never collides with none.  edge = 0 is the chamfer Voronoi
+ * diagram of the seed pixels cut off at reach / 5 px.  drivers.object_masks_guided_torch is the same rule in int64 torch ops: every
+ * byte is compared.
+ * Launches on `stream`: one thread per (frame, column) writes an 8-byte record into the workspace -- the seed pixel Y << 16 | X,
+ * or -1, and the label -- then ceil(floor(reach / 5) / 16) launches, at least one, counted on the host from `reach` alone: no
+ * convergence flag comes back from the device.  In each a 256-thread block owns a 64 x 64 pixel tile of one frame, holds the keys
+ * and the guide of the tile grown by 16 pixels a side in LDS, relaxes them there -- 16 in-place sweeps over the four classes
+ * (X & 1, Y & 1) of pixels, a barrier between two classes, leaving early when a sweep changes nothing -- and stores the tile
+ * alone.  The first launch builds the seeds of its patch from the records (an integer atomicMin in LDS: the lowest column), the
+ * launches hand the keys on through two planes in the workspace in turn, the last gathers the labels and stores them as dwords
+ * where the address allows.  The schedule does at least the Jacobi steps and never below the fixed point; the relaxation is
+ * monotone, so the result is the fixed point and a pure function of the inputs.  No other atomics, no allocation, no
+ * synchronisation; the workspace is read and written by this call only and may be reused by the next.
+ * pips_object_masks_guided_workspace_bytes(F, n, h, w) = (8 F n rounded up to 16) + 2 x 4 F h w: the records and two key planes;
+ * 0 for F = 0 or n = 0 and for F < 0, n < 0, n > PIPS_MASK_N_MAX, h or w < 1 or > PIPS_DRAW_DIM_MAX.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "object_masks_guided:": F < 0, n < 0 or G < 0; n >
+ * PIPS_MASK_N_MAX; h, w, src_h or src_w < 1; h or w > PIPS_DRAW_DIM_MAX; edge or reach outside its range; first < 0 or first + F >
+ * G; pitch < w; with F > 1 a step below pitch x h; with F > 0 a NULL mask; with F > 0 and n > 0 a NULL trajs, labels, guide or
+ * workspace, guide_pitch < w, with F > 1 a guide_step below guide_pitch x h, workspace_bytes below the figure above, a workspace
+ * off a 16-byte address.  F = 0 launches nothing and returns PIPS_OK; n = 0 needs no trajs, labels, guide or workspace and fills
+ * the images with PIPS_MASK_NONE in one launch.
+ *
+ * pips_guide_plane makes such a guide from F surfaces of h x w: G = (77 R + 150 G + 29 B + 128) >> 8, the luma of
+ * pips_corner_table and pips_cut_table, for the formats RGB24, BGR24, RGBA32, BGRA32 (plane 0) and PLANAR8 (planes 0, 1, 2 = R, G,
+ * B); planes, pitches and steps in bytes as in pips_tracks_draw.  One launch on `stream`: a thread per four neighbouring pixels
+ * of a row, a dword store where the address allows; frames past the 65535th are walked by the same blocks.  The Y plane of an
+ * NV12 or I420 surface IS a guide and goes into pips_object_masks_guided by pointer, pitch and step without a copy.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "guide_plane:": any other format (NV12, I420, P010
+ * and I010 among them); F < 0; h or w < 1 or > PIPS_DRAW_DIM_MAX; a pitch below the bytes of a row of its plane or guide_pitch <
+ * w; with F > 1 a step below pitch x h; with F > 0 a NULL plane that the format has or a NULL guide.  F = 0 launches nothing.
+ * Known limits: luma only (no colour distances), 8-bit guides only, no smoothing or denoising of the guide, one geodesic
+ * neighbour decides (no vote), no temporal smoothing; every first-launch block walks all n records (they are not binned by
+ * tile); the guide, the mask and the workspace may not overlap. */
+#define PIPS_MASK_EDGE_MAX    64
+#define PIPS_MASK_REACH_MAX   32767
+size_t pips_object_masks_guided_workspace_bytes(int F, int n, int h, int w);
+int    pips_object_masks_guided(const float* trajs, const uint8_t* labels, int G, int n, int first, int F,
+                                int src_h, int src_w, int h, int w, int edge, int reach,
+                                const uint8_t* guide, size_t guide_pitch, size_t guide_step,
+                                uint8_t* mask, size_t pitch, size_t step,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int    pips_guide_plane(int format, int F, int h, int w,
+                        const void* p0, size_t pitch0, size_t step0,
+                        const void* p1, size_t pitch1, size_t step1,
+                        const void* p2, size_t pitch2, size_t step2,
+                        uint8_t* guide, size_t guide_pitch, size_t guide_step, void* stream);
 
 /* Frames out, stabilised: pips_frames_warp resamples F frames from the `src` surfaces into the `dst` surfaces, format and size the
  * same on both sides, through one affine map per frame -- what a stabiliser does with pips_motion_fit's models

@@ -2170,6 +2170,72 @@ int pips_masks_tint(int format, int matrix, int range, int F, int h, int w, void
                              (hipStream_t)stream);
 }
 
+// ---- object masks along the image's edges
+size_t pips_object_masks_guided_workspace_bytes(int F, int n, int h, int w) {
+    if (F < 0 || n < 0 || n > PIPS_MASK_N_MAX || h < 1 || w < 1 || h > PIPS_DRAW_DIM_MAX || w > PIPS_DRAW_DIM_MAX) return 0;
+    if (F == 0 || n == 0) return 0;
+    return guided_workspace_bytes(F, n, h, w);
+}
+int pips_object_masks_guided(const float* trajs, const uint8_t* labels, int G, int n, int first, int F, int src_h, int src_w, int h,
+                             int w, int edge, int reach, const uint8_t* guide, size_t guide_pitch, size_t guide_step, uint8_t* mask,
+                             size_t pitch, size_t step, void* workspace, size_t workspace_bytes, void* stream) {
+    PIPS_CHECK_ARG(F >= 0 && n >= 0 && G >= 0, "object_masks_guided: need F >= 0, n >= 0 and G >= 0 (F=%d, n=%d, G=%d)", F, n, G);
+    PIPS_CHECK_ARG(n <= PIPS_MASK_N_MAX, "object_masks_guided: at most %d columns (n=%d): a key holds 16 bits of column", PIPS_MASK_N_MAX,
+                   n);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1 && src_h >= 1 && src_w >= 1,
+                   "object_masks_guided: need sizes of at least 1x1 (h=%d, w=%d, src_h=%d, src_w=%d)", h, w, src_h, src_w);
+    PIPS_CHECK_ARG(h <= PIPS_DRAW_DIM_MAX && w <= PIPS_DRAW_DIM_MAX, "object_masks_guided: masks up to %d a side (h=%d, w=%d)",
+                   PIPS_DRAW_DIM_MAX, h, w);
+    PIPS_CHECK_ARG(edge >= 0 && edge <= PIPS_MASK_EDGE_MAX, "object_masks_guided: edge=%d outside 0..%d", edge, PIPS_MASK_EDGE_MAX);
+    PIPS_CHECK_ARG(reach >= 0 && reach <= PIPS_MASK_REACH_MAX, "object_masks_guided: reach=%d outside 0..%d", reach, PIPS_MASK_REACH_MAX);
+    PIPS_CHECK_ARG(first >= 0 && (long long)first + F <= (long long)G, "object_masks_guided: rows [%d, %d + %d) of %d", first, first, F, G);
+    PIPS_CHECK_ARG(pitch >= (size_t)w, "object_masks_guided: pitch %zu is below the %d bytes of a row", pitch, w);
+    PIPS_CHECK_ARG(F <= 1 || (step >= pitch && step / pitch >= (size_t)h), "object_masks_guided: step %zu is below pitch %zu x %d rows",
+                   step, pitch, h);
+    if (F == 0) return PIPS_OK;
+    PIPS_CHECK_ARG(mask != nullptr, "object_masks_guided: null mask");
+    if (n > 0) {
+        PIPS_CHECK_ARG(trajs && labels && workspace, "object_masks_guided: null trajs, labels or workspace");
+        PIPS_CHECK_ARG(guide != nullptr, "object_masks_guided: null guide");
+        PIPS_CHECK_ARG(guide_pitch >= (size_t)w, "object_masks_guided: guide pitch %zu is below the %d bytes of a row", guide_pitch, w);
+        PIPS_CHECK_ARG(F <= 1 || (guide_step >= guide_pitch && guide_step / guide_pitch >= (size_t)h),
+                       "object_masks_guided: guide step %zu is below pitch %zu x %d rows", guide_step, guide_pitch, h);
+        const size_t need = pips_object_masks_guided_workspace_bytes(F, n, h, w);
+        PIPS_CHECK_ARG(workspace_bytes >= need, "object_masks_guided: workspace %zu < %zu bytes", workspace_bytes, need);
+        PIPS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "object_masks_guided: the workspace must lie on a 16-byte address");
+    }
+    return launch_object_masks_guided(trajs, labels, n, first, F, src_h, src_w, h, w, edge, reach, n > 0 ? guide : nullptr, guide_pitch,
+                                      guide_step, mask, pitch, step, workspace, (hipStream_t)stream);
+}
+int pips_guide_plane(int format, int F, int h, int w, const void* p0, size_t pitch0, size_t step0, const void* p1, size_t pitch1,
+                     size_t step1, const void* p2, size_t pitch2, size_t step2, uint8_t* guide, size_t guide_pitch, size_t guide_step,
+                     void* stream) {
+    PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_BGRA32) || format == PIPS_FMT_PLANAR8,
+                   "guide_plane: format %d is not RGB24, BGR24, RGBA32, BGRA32 or PLANAR8 (the Y plane of NV12 and I420 is a guide as it is)",
+                   format);
+    PIPS_CHECK_ARG(F >= 0, "guide_plane: need F >= 0 (F=%d)", F);
+    PIPS_CHECK_ARG(h >= 1 && w >= 1, "guide_plane: need a size of at least 1x1 (h=%d, w=%d)", h, w);
+    PIPS_CHECK_ARG(h <= PIPS_DRAW_DIM_MAX && w <= PIPS_DRAW_DIM_MAX, "guide_plane: surfaces up to %d a side (h=%d, w=%d)",
+                   PIPS_DRAW_DIM_MAX, h, w);
+    const bool planar = format == PIPS_FMT_PLANAR8;
+    const void* p[3] = {p0, p1, p2};
+    const size_t pitch[3] = {pitch0, pitch1, pitch2}, step[3] = {step0, step1, step2};
+    const int planes = planar ? 3 : 1;
+    const size_t row_bytes = (size_t)w * (planar ? 1 : (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : 3);
+    for (int k = 0; k < planes; ++k) {
+        PIPS_CHECK_ARG(pitch[k] >= row_bytes, "guide_plane: pitch %zu of plane %d is below the %zu bytes of a row", pitch[k], k, row_bytes);
+        PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= (size_t)h),
+                       "guide_plane: step %zu of plane %d is below pitch %zu x %d rows", step[k], k, pitch[k], h);
+    }
+    PIPS_CHECK_ARG(guide_pitch >= (size_t)w, "guide_plane: guide pitch %zu is below the %d bytes of a row", guide_pitch, w);
+    PIPS_CHECK_ARG(F <= 1 || (guide_step >= guide_pitch && guide_step / guide_pitch >= (size_t)h),
+                   "guide_plane: guide step %zu is below pitch %zu x %d rows", guide_step, guide_pitch, h);
+    if (F == 0) return PIPS_OK;
+    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(p[k] != nullptr, "guide_plane: null plane %d", k);
+    PIPS_CHECK_ARG(guide != nullptr, "guide_plane: null guide");
+    return launch_guide_plane(format, F, h, w, p, pitch, step, guide, guide_pitch, guide_step, (hipStream_t)stream);
+}
+
 // ---- motion
 static bool motion_shape_ok(int F, int n, int K) {
     return F >= 0 && F <= PIPS_MOTION_ROWS_MAX && n >= 0 && n <= PIPS_MOTION_N_MAX && K >= 1 && K <= PIPS_MOTION_HYPS_MAX;

@@ -574,6 +574,21 @@ int launch_masks_tint(int format, int matrix, int range, int F, int h, int w, vo
                       const unsigned char* mask, size_t mpitch, size_t mstep, const unsigned char* colors, const int* alpha, int C,
                       hipStream_t st);
 
+// ---- masks_guided.hip: a label per pixel from a label per track along geodesic paths on a guide plane (pips_object_masks_guided)
+// and that plane from RGB surfaces (pips_guide_plane).  The workspace holds the records -- MASK_REC_BYTES per (frame, column): the
+// seed pixel and the label -- rounded up to 16 bytes, then two planes of one 32-bit key per (frame, pixel) that the launches write
+// in turn; guided_launches(reach) launches follow the prepare launch.  n == 0 runs one launch (every pixel PIPS_MASK_NONE) and reads
+// neither workspace nor guide.  Arguments checked by the caller.
+inline size_t guided_workspace_bytes(int F, int n, int h, int w) {
+    return align_up((size_t)F * (size_t)n * MASK_REC_BYTES, 16) + 2 * 4 * (size_t)F * (size_t)h * (size_t)w;
+}
+int guided_launches(int reach);
+int launch_object_masks_guided(const float* trajs, const unsigned char* labels, int n, int first, int F, int src_h, int src_w, int h, int w,
+                               int edge, int reach, const unsigned char* guide, size_t gpitch, size_t gstep, unsigned char* mask,
+                               size_t pitch, size_t step, void* workspace, hipStream_t st);
+int launch_guide_plane(int format, int F, int h, int w, const void* const* p, const size_t* pitch, const size_t* step, unsigned char* guide,
+                       size_t gpitch, size_t gstep, hipStream_t st);
+
 // ---- motion.hip: the consensus similarity between consecutive rows of a trajectory tensor (pips_motion_fit).  The workspace holds,
 // for each of the F - 1 pairs, the quantised valid columns in column order (n slots of four int16), their number, and the best
 // (score, hypothesis) key of each block of MOTION_HYPS hypotheses; arguments checked by the caller (the workspace on a 16-byte

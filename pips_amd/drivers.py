@@ -2349,6 +2349,111 @@ def object_masks_torch(trajs, labels, size, out_size=None, radius=48.0, vote=1, 
     return out
 
 
+def _guided_setup(trajs, labels, guide, size, out_size, radius, edge, first):
+    """what ``object_masks_guided`` and ``object_masks_guided_torch`` make of their arguments -> (rows, labels, guide on the rows'
+    device, (h, w), (src_h, src_w), edge, reach, first); reach = floor(5 radius + 0.5), the radius in pixels of the mask"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not 0.0 <= radius <= ops.MASK_REACH_MAX or \
+            _round_half_up(radius, 5.0) > ops.MASK_REACH_MAX:
+        raise ValueError(f"radius must lie in 0..{ops.MASK_REACH_MAX / 5} px (reach = floor(5 radius + 0.5) <= {ops.MASK_REACH_MAX}), "
+                         f"not {radius!r}")
+    rows, labels, out, src, _, _, first = _masks_setup(trajs, labels, size, out_size, 0.0, 1, first)
+    if guide is not None:
+        if not torch.is_tensor(guide) or guide.dtype != torch.uint8 or guide.dim() != 3:
+            raise ValueError(f"guide must be a uint8 tensor (F - first, h, w), not {getattr(guide, 'dtype', None)} "
+                             f"{tuple(getattr(guide, 'shape', ()))}")
+        guide = guide.to(rows.device)
+    return rows, labels, guide, out, src, _whole(edge, "edge", 0), _round_half_up(radius, 5.0), first
+
+
+def object_masks_guided(trajs, labels, guide, size, out_size=None, radius=48.0, edge=4, first=0):
+    """``object_masks`` with the image in the decision, one ``pips_object_masks_guided`` call (``ops.object_masks_guided``;
+    include/pips_hip.h has the rule): trajs, labels, ``size``, ``out_size`` and ``first`` as there; ``guide`` (F - first, h, w) uint8
+    on the GPU is the 8-bit luma of the frames at the mask's size -- ``guide_plane`` of the surfaces; any row and frame strides
+    with a unit last stride.  A pixel takes the label of the track that is nearest along a path over the pixel grid whose steps
+    cost 1 px (1.4 px diagonally; 5 and 7 in fifths of a pixel) plus ``edge`` / 5 px per grey level that the step changes the
+    guide by, within ``radius`` px of cost; 255 where no track is that near.  Crossing a luma edge of 60 levels at ``edge=4``
+    costs as much as 48 px of flat ground, so the boundary between two labels runs along such an edge wherever one lies between
+    their tracks; ``edge=0`` is the (chamfer) Voronoi diagram of ``object_masks``' ``vote=1``.  A streaming user calls this per
+    push on what ``MotionLayers.step`` returns, as ``object_masks``."""
+    rows, labels, guide, out, src, edge, reach, first = _guided_setup(trajs, labels, guide, size, out_size, radius, edge, first)
+    return ops.object_masks_guided(rows, labels, guide, out, src, edge, reach, first)
+
+
+def object_masks_guided_torch(trajs, labels, guide, size, out_size=None, radius=48.0, edge=4, first=0):
+    """``object_masks_guided`` as int64 torch ops on any device, equal in every byte: per frame the keys cost 2^16 + column of the
+    seed pixels, then floor(reach / 5) Jacobi steps -- the keys padded by a ring of none, shifted to each of the eight neighbours,
+    the step's cost added and the minimum taken -- leaving early when a step changes nothing.  Written to be read, not to be
+    fast."""
+    return _guided_keys(trajs, labels, guide, size, out_size, radius, edge, first)[0]
+
+
+def _guided_keys(trajs, labels, guide, size, out_size, radius, edge, first):
+    """the twin's work -> (masks (F,h,w) uint8, keys (F,h,w) int64 with 2^32 - 1 for none, the Jacobi steps each frame took before
+    one changed nothing)"""
+    rows, labels, guide, (h, w), (src_h, src_w), edge, reach, first = _guided_setup(trajs, labels, guide, size, out_size, radius, edge,
+                                                                                    first)
+    G, n, F = ops.object_masks_guided_check(rows, labels, guide, (h, w), (src_h, src_w), edge, reach, first)[:3]
+    dev = rows.device
+    none = (1 << 32) - 1
+    masks = torch.full((F, h, w), ops.MASK_NONE, dtype=torch.uint8, device=dev)
+    keys = torch.full((F, h, w), none, dtype=torch.int64, device=dev)
+    steps = []
+    pad = torch.nn.functional.pad
+    for k in _range(F):
+        qx, okx = _draw_quantise(rows[first + k, :, 0], src_w, w)
+        qy, oky = _draw_quantise(rows[first + k, :, 1], src_h, h)
+        lab = labels[first + k].to(torch.int64)
+        X, Y = (qx + 4) >> 3, (qy + 4) >> 3
+        seeds = torch.nonzero(okx & oky & (lab != ops.MASK_NONE) & (X >= 0) & (X < w) & (Y >= 0) & (Y < h)).squeeze(1)
+        key = keys[k].view(-1)
+        key.scatter_reduce_(0, Y[seeds] * w + X[seeds], seeds, "amin")                      # cost 0: the key is the lowest column
+        key = key.view(h, w)
+        done = 0
+        if seeds.numel() > 0:
+            g = pad(guide[k].to(torch.int64), (1, 1, 1, 1))
+            for _ in _range(reach // 5):
+                kp = pad(key, (1, 1, 1, 1), value=none)
+                new = key
+                for dy in (-1, 0, 1):
+                    for dx in (-1, 0, 1):
+                        if dx == 0 and dy == 0:
+                            continue
+                        kq = kp[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+                        c = (7 if dx != 0 and dy != 0 else 5) + edge * (g[1:1 + h, 1:1 + w] - g[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]).abs()
+                        cand = kq + (c << 16)
+                        new = torch.minimum(new, torch.where((kq != none) & ((cand >> 16) <= reach), cand, none))
+                if torch.equal(new, key):
+                    break
+                key, done = new, done + 1
+        keys[k] = key
+        if n > 0:
+            masks[k] = torch.where(key != none, lab[(key & 0xFFFF).clamp(max=n - 1)], ops.MASK_NONE).to(torch.uint8)
+        steps.append(done)
+    return masks, keys, steps
+
+
+def guide_plane(planes, fmt):
+    """The guide of ``object_masks_guided`` from F surfaces on the GPU: their 8-bit luma (F,h,w) uint8.  ``planes`` / ``fmt`` as in
+    ``draw_tracks``: for "nv12" and "i420" the Y plane itself, as the view it is -- no copy, no launch; for "rgb24", "bgr24",
+    "rgba32", "bgra32" and "planar8" one ``pips_guide_plane`` call (``ops.guide_plane``): (77 R + 150 G + 29 B + 128) >> 8.  The
+    16-bit formats are a ValueError."""
+    if fmt in ("nv12", "i420"):
+        return ops.draw_planes(planes, fmt)[0][0]
+    return ops.guide_plane(planes, fmt)
+
+
+def guide_plane_torch(planes, fmt):
+    """``guide_plane`` as int64 torch ops on any device, equal in every byte"""
+    if fmt in ("nv12", "i420"):
+        return ops.draw_planes(planes, fmt)[0][0]
+    planes = ops.guide_check(planes, fmt)[0]
+    if fmt == "planar8":
+        r, g, b = (planes[0][:, c].to(torch.int64) for c in (0, 1, 2))
+    else:
+        r, g, b = (planes[0][..., c].to(torch.int64) for c in ((2, 1, 0) if fmt in ("bgr24", "bgra32") else (0, 1, 2)))
+    return ((77 * r + 150 * g + 29 * b + 128) >> 8).to(torch.uint8)
+
+
 def object_colors(object_ids, alpha=0.5, camera_alpha=0.0):
     """The colours and opacities ``tint_masks`` takes, from ``motion_layers``' ``object_ids`` (P,L): -> (colors (P,L,3) uint8,
     alpha (P,L) float64).  A mask holds LAYER indices, which an object may change from pair to pair; the colour of layer l of pair

@@ -513,6 +513,103 @@ def masks_tint(planes, fmt, masks, colors, alpha, matrix="bt709", range="limited
               mstep, _lib.ptr(colors), table, nlab, _stream())
 
 
+# include/pips_hip.h: PIPS_MASK_EDGE_MAX, PIPS_MASK_REACH_MAX; pips_amd/csrc/masks_guided.hip: the tile a block stores and the halo
+# around it, the steps one launch is good for
+MASK_EDGE_MAX, MASK_REACH_MAX = 64, 32767
+GUIDED_TILE, GUIDED_HALO = 64, 16
+GUIDE_FORMATS = ("rgb24", "bgr24", "rgba32", "bgra32", "planar8")     # pips_guide_plane's; the Y plane of nv12 / i420 is a guide as it is
+
+
+def guided_launches(reach):
+    """the relaxation launches of one pips_object_masks_guided call with n > 0: ceil(floor(reach / 5) / GUIDED_HALO), at least one"""
+    return max(1, -(-(int(reach) // 5) // GUIDED_HALO))
+
+
+def object_masks_guided_check(trajs, labels, guide, size, src_size, edge, reach, first):
+    """pips_object_masks_guided's limits on the values, shared by ``object_masks_guided`` and
+    ``drivers.object_masks_guided_torch`` -> (G, n, F, h, w, src_h, src_w); ``guide`` may be None when n = 0"""
+    G, n, F, h, w, src_h, src_w = object_masks_check(trajs, labels, size, src_size, 0, 1, first)
+    if not 0 <= edge <= MASK_EDGE_MAX:
+        raise ValueError(f"edge must lie in 0..{MASK_EDGE_MAX}, not {edge}")
+    if not 0 <= reach <= MASK_REACH_MAX:
+        raise ValueError(f"reach must lie in 0..{MASK_REACH_MAX}, not {reach}")
+    if guide is None:
+        if n > 0 and F > 0:
+            raise ValueError("a call with columns needs a guide")
+    elif not torch.is_tensor(guide) or guide.dtype != torch.uint8 or tuple(guide.shape) != (F, h, w):
+        raise ValueError(f"guide must be uint8 (F,h,w) = {(F, h, w)}, not {getattr(guide, 'dtype', None)} {tuple(getattr(guide, 'shape', ()))}")
+    return G, n, F, h, w, src_h, src_w
+
+
+def object_masks_guided_workspace_bytes(F, n, h, w):
+    return int(_lib.load().pips_object_masks_guided_workspace_bytes(int(F), int(n), int(h), int(w)))
+
+
+def object_masks_guided(trajs, labels, guide, size, src_size=None, edge=4, reach=240, first=0, out=None, workspace=None):
+    """pips_object_masks_guided: a label per pixel from a label per track along paths that avoid luma edges.  trajs, labels,
+    ``size``, ``src_size`` and ``first`` as in ``object_masks``; ``guide`` (G - first, h, w) uint8 on the device is the 8-bit plane
+    whose differences make a step expensive (``guide_plane``, or the Y plane of an NV12 / I420 surface) -- its row and frame
+    strides go through as pitch and step, so a view of a pitched surface is read as it is.  Every pixel gets the label of the
+    column whose seed pixel is nearest by the cost 5 / 7 per axial / diagonal step + ``edge`` x the step's guide difference,
+    within ``reach``; 255 where there is none (include/pips_hip.h has the whole rule).  ``out`` and ``workspace`` as in
+    ``object_masks``, the workspace of ``object_masks_guided_workspace_bytes(F, n, h, w)`` bytes."""
+    edge, reach, first = int(edge), int(reach), int(first)
+    G, n, F, h, w, src_h, src_w = object_masks_guided_check(trajs, labels, guide, size, src_size, edge, reach, first)
+    assert trajs.is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = trajs.device
+    if out is None:
+        out = torch.empty(F, h, w, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, h, w):
+        raise ValueError(f"out must be uint8 (F,h,w) = {(F, h, w)}, not {out.dtype} {tuple(out.shape)}")
+    for t in (labels, guide, out, workspace):
+        if t is not None and t.device != dev:
+            raise ValueError("trajs, labels, guide, out and the workspace must live on one device")
+    if F == 0:
+        return out
+    pitch, step = _surface(out, (1,))
+    gpitch, gstep = (0, 0) if guide is None else _surface(guide, (1,))
+    trajs, labels = trajs.contiguous(), labels.contiguous()
+    need = object_masks_guided_workspace_bytes(F, n, h, w)
+    if workspace is None:
+        workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=dev)
+    nbytes = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(dev):
+        _call("pips_object_masks_guided", _lib.ptr(trajs), _lib.ptr(labels), G, n, first, F, src_h, src_w, h, w, edge, reach, _lib.ptr(guide),
+              gpitch, gstep, _lib.ptr(out), pitch, step, _lib.ptr(workspace), nbytes, _stream())
+    return out
+
+
+def guide_check(planes, fmt):
+    """pips_guide_plane's limits on the values, shared by ``guide_plane`` and ``drivers.guide_plane_torch`` -> (planes, F, h, w)"""
+    if fmt not in GUIDE_FORMATS:
+        raise ValueError(f"fmt must be one of {GUIDE_FORMATS}, not {fmt!r}")
+    planes, F, h, w = draw_planes(planes, fmt)
+    if max(h, w) > DRAW_DIM_MAX:
+        raise ValueError(f"surfaces up to {DRAW_DIM_MAX} a side, not {h} x {w}")
+    return planes, F, h, w
+
+
+def guide_plane(planes, fmt, out=None):
+    """pips_guide_plane: the 8-bit luma (77 R + 150 G + 29 B + 128) >> 8 of the device surfaces ``planes`` of format ``fmt`` --
+    "rgb24", "bgr24", "rgba32", "bgra32" or "planar8" in ``draw_tracks``' shapes, pitched views included -> (F,h,w) uint8, the
+    guide of ``object_masks_guided``.  ``out``: a uint8 (F,h,w) device tensor to write instead of a fresh one, row and frame strides
+    as pitch and step."""
+    planes, F, h, w = guide_check(planes, fmt)
+    assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = planes[0].device
+    if out is None:
+        out = torch.empty(F, h, w, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, h, w) or out.device != dev:
+        raise ValueError(f"out must be uint8 (F,h,w) = {(F, h, w)} on the surfaces' device, not {out.dtype} {tuple(out.shape)}")
+    if F == 0:
+        return out
+    args = draw_surfaces(planes, fmt)
+    gpitch, gstep = _surface(out, (1,))
+    with torch.cuda.device(dev):
+        _call("pips_guide_plane", DRAW_FORMATS[fmt], F, h, w, *args, _lib.ptr(out), gpitch, gstep, _stream())
+    return out
+
+
 # include/pips_hip.h: PIPS_WARP_BORDER_*, PIPS_WARP_DIM_MAX; pips_amd/csrc/common.h: the tile and the staging budget of warp.hip
 WARP_BORDERS = {"constant": 0, "replicate": 1}
 WARP_DIM_MAX, WARP_TILE_W, WARP_TILE_H, WARP_LDS_BYTES = 8192, 64, 16, 12288
