@@ -121,7 +121,9 @@ const char* pips_last_error(void);
  * between consecutive rows of a trajectory tensor: an exact consensus similarity); pips_frames_warp (the decoder's surfaces
  * resampled through a per-frame affine map in exact integers: frames out, stabilised); pips_motion_layers and
  * pips_motion_layers_workspace_bytes (the consensus of pips_motion_fit peeled into up to 8 motion layers a pair, with the overlap
- * table that links a pair's layers to those of the pair before: what moves, beside the camera). */
+ * table that links a pair's layers to those of the pair before: what moves, beside the camera); pips_frames_warp_fill
+ * (pips_frames_warp with a list of candidate source frames per output frame: the border of a stabilised frame filled from its
+ * neighbours). */
 int         pips_abi_version(void);
 
 /* ---- weights ------------------------------------------------------------------------
@@ -1163,6 +1165,52 @@ int    pips_frames_warp(int format, int matrix, int range, int border, int fill_
                         void* d1, size_t dpitch1, size_t dstep1,
                         void* d2, size_t dpitch2, size_t dstep2,
                         const int32_t* coef, void* stream);
+
+/* The border of a stabilised frame filled from neighbouring frames: pips_frames_warp_fill writes Fd output frames from Fs source
+ * frames, format and h x w the same on both sides.  Output frame j has K candidates, 1 <= K <= PIPS_WARP_FILL_MAX: cand (Fd,K)
+ * int32 on the device, cand[j][k] an index into the source frames, and coef (Fd,K,6) int32 on the device, coef[j][k] a row of
+ * exactly pips_frames_warp's meaning and fixed point.  The decision is made for every output sample of every plane on its own:
+ *  1. position: U, V of candidate k are pips_frames_warp's, in int64 -- luma U = (X + 32768) >> 16, chroma
+ *     Uc = (XL - 2^24 + 2^17) >> 18 -- and x0 = U >> 8, fx = U & 255, y0 = V >> 8, fy = V & 255;
+ *  2. valid: candidate k is valid when 0 <= cand[j][k] < Fs.  An invalid candidate is skipped; -1 is the conventional "none";
+ *  3. covers: a valid candidate covers the sample when every tap that has weight lies inside the plane, pw x ph the sample grid of
+ *     that plane: x0 >= 0 and (x0 + 1 <= pw - 1, or fx == 0 and x0 <= pw - 1) on the x axis, and the same with y0, fy, ph on the
+ *     y axis.  The identity therefore covers every sample, the last row and column included;
+ *  4. value: the plain two-by-two blend of pips_frames_warp (no border rule needed) from the first candidate in list order that
+ *     covers the sample, read from source frame cand[j][k].  If none covers it: pips_frames_warp's value for candidate 0 under
+ *     border / fill_rgb, partial taps blended with the fill or clamped exactly as there; if candidate 0 is itself invalid, the
+ *     fill value, whatever border is.  K = 1 with cand[j][0] = j is pips_frames_warp, byte for byte;
+ *  5. source map: `source` is NULL or an (Fd,h,w) uint8 surface with its own pitch and step in bytes.  It receives, for plane 0,
+ *     the list position k that supplied the sample, or 255 where none covered.  The three planes of PLANAR8 share positions, so
+ *     plane 0 speaks for them;
+ *  6. unchanged from pips_frames_warp: formats and addressing, the 10-bit read and write, the alpha byte (written 255), every word
+ *     of dst inside the image is written, nothing outside the image is written and nothing outside a src plane is read.  cand and
+ *     coef are not read back to the host.
+ * drivers.warp_frames_fill_torch is the same rule in int64 torch ops: every byte is compared, the source map included.
+ * One launch on `stream` per 65535 output frames: pips_frames_warp's block per 64 x 16 luma tile and OUTPUT frame.  A tile whose
+ * candidate-0 box lies inside every plane, candidate 0 valid, cannot have an uncovered sample: it runs pips_frames_warp's staged
+ * or direct pass on frame cand[j][0] and writes zeros to the source map.  Every other tile walks the list: a thread keeps a
+ * done-mask over its two or four samples in registers, skips (with its whole block) an invalid candidate and one whose box misses
+ * the plane, leaves the list when nothing of it is left to fill, and takes the rule-4 fallback at the end; these tiles read
+ * their taps from global memory.  No workspace, no atomics, no allocation, no synchronisation, no floating point; dword stores
+ * where the address allows, the source map too.
+ * PIPS_E_ARG ahead of any launch, with nothing written and the message prefix "frames_warp_fill:": everything pips_frames_warp
+ * rejects, applied to Fs with src and to Fd with dst separately; K outside 1..PIPS_WARP_FILL_MAX; with Fd > 0 a NULL cand or coef, a
+ * NULL dst plane, and with Fs > 0 a NULL src plane; a source pitch below w, or with Fd > 1 a source step below pitch x h; dst or
+ * source overlapping src or each other.  Fd = 0 launches nothing and returns PIPS_OK.
+ * Known limits beside pips_frames_warp's: a moving object is shown where the neighbour saw it (ghosts in the border); no
+ * feathering and no exposure matching at the seam; luma and chroma choose their candidate independently, so a one-sample fringe
+ * is possible on a seam; nothing comes from frames outside the list. */
+#define PIPS_WARP_FILL_MAX 16
+int    pips_frames_warp_fill(int format, int matrix, int range, int border, int fill_rgb, int Fs, int Fd, int K, int h, int w,
+                             const void* s0, size_t spitch0, size_t sstep0,
+                             const void* s1, size_t spitch1, size_t sstep1,
+                             const void* s2, size_t spitch2, size_t sstep2,
+                             void* d0, size_t dpitch0, size_t dstep0,
+                             void* d1, size_t dpitch1, size_t dstep1,
+                             void* d2, size_t dpitch2, size_t dstep2,
+                             const int32_t* cand, const int32_t* coef,
+                             uint8_t* source, size_t source_pitch, size_t source_step, void* stream);
 
 /* utils.samp.bilinear_sample2d (utils/samp.py:5-78): clamped-index point sample of frame
  * 0 of every clip.  xy (B,N,2) in map pixels -> out (B,N,128).  PIPS_E_ARG ahead of the launch for a

@@ -134,6 +134,8 @@ SIGNATURES = {
     "pips_object_masks_guided": (c_int, [fp, c_void_p] + [c_int] * 10 + [c_void_p, c_size_t, c_size_t] * 2 + [c_void_p, c_size_t, c_void_p]),
     "pips_guide_plane": (c_int, [c_int] * 4 + [c_void_p, c_size_t, c_size_t] * 4 + [c_void_p]),
     "pips_frames_warp": (c_int, [c_int] * 8 + [c_void_p, c_size_t, c_size_t] * 6 + [c_void_p, c_void_p]),
+    "pips_frames_warp_fill": (c_int, [c_int] * 10 + [c_void_p, c_size_t, c_size_t] * 6 + [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t,
+                                                                                          c_void_p]),
     "pips_point_sample": (c_int, [fp, c_int, c_int, c_int, c_int, fp, c_int, fp, c_void_p]),
     "pips_mixer_input_build": (c_int, [fp, c_int, c_int, c_int, c_int, fp, fp, fp, c_int, fp, c_void_p]),
     "pips_gather_scratch_bytes": (c_size_t, [c_int] * 4),

@@ -2306,62 +2306,136 @@ int pips_motion_layers(const float* trajs, const float* vis, const uint8_t* prev
 }
 
 // ---- frames out, stabilised
+namespace {
+
+// plane k of a format of pips_frames_warp: its rows and the bytes of a row (pips_tracks_draw_ex's geometry)
+struct WarpGeom {
+    bool wide;                                                                          // 16-bit samples
+    int planes;
+    size_t rows[3], row_bytes[3];
+};
+
+// what pips_frames_warp and pips_frames_warp_fill check of their values alike; `fn` is the message prefix
+int warp_check_values(const char* fn, int format, int matrix, int range, int border, int fill_rgb) {
+    PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I010) || format == PIPS_FMT_PLANAR8, "%s: unknown format %d", fn,
+                   format);
+    PIPS_CHECK_ARG(border == PIPS_WARP_BORDER_CONSTANT || border == PIPS_WARP_BORDER_REPLICATE, "%s: unknown border %d", fn, border);
+    const bool yuv = format == PIPS_FMT_NV12 || format == PIPS_FMT_P010 || format == PIPS_FMT_I420 || format == PIPS_FMT_I010;
+    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
+                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
+                   "%s: unknown matrix %d or range %d", fn, matrix, range);
+    PIPS_CHECK_ARG(fill_rgb >= 0 && fill_rgb <= 0xFFFFFF, "%s: fill_rgb %d outside 0..0xFFFFFF", fn, fill_rgb);
+    return PIPS_OK;
+}
+
+int warp_check_size(const char* fn, int format, int h, int w, WarpGeom& g) {
+    PIPS_CHECK_ARG(h >= 1 && w >= 1, "%s: need a size of at least 1x1 (h=%d, w=%d)", fn, h, w);
+    PIPS_CHECK_ARG(h <= PIPS_WARP_DIM_MAX && w <= PIPS_WARP_DIM_MAX, "%s: surfaces up to %d a side (h=%d, w=%d)", fn, PIPS_WARP_DIM_MAX, h,
+                   w);
+    g.wide = format == PIPS_FMT_P010 || format == PIPS_FMT_I010;
+    const bool semi = format == PIPS_FMT_NV12 || format == PIPS_FMT_P010;
+    const bool yuv = semi || format == PIPS_FMT_I420 || format == PIPS_FMT_I010;
+    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2, sb = g.wide ? 2 : 1;
+    const bool planar = format == PIPS_FMT_PLANAR8;
+    g.planes = semi ? 2 : (yuv || planar) ? 3 : 1;
+    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : (yuv || planar) ? sb : 3;
+    const size_t rows[3] = {(size_t)h, planar ? (size_t)h : ch, planar ? (size_t)h : ch};
+    const size_t row_bytes[3] = {(size_t)w * bpp, planar ? (size_t)w : (semi ? 2 * cw : cw) * sb, planar ? (size_t)w : cw * sb};
+    for (int k = 0; k < 3; ++k) g.rows[k] = rows[k], g.row_bytes[k] = row_bytes[k];
+    return PIPS_OK;
+}
+
+// the pitches, steps and 16-bit alignment of the F surfaces `who` ("src" / "dst")
+int warp_check_side(const char* fn, const char* who, const WarpGeom& g, int F, const void* const* p, const size_t* pitch,
+                    const size_t* step) {
+    for (int k = 0; k < g.planes; ++k) {
+        PIPS_CHECK_ARG(pitch[k] >= g.row_bytes[k], "%s: pitch %zu of %s plane %d is below the %zu bytes of a row", fn, pitch[k], who, k,
+                       g.row_bytes[k]);
+        PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= g.rows[k]),
+                       "%s: step %zu of %s plane %d is below pitch %zu x %zu rows", fn, step[k], who, k, pitch[k], g.rows[k]);
+        PIPS_CHECK_ARG(!g.wide || (((uintptr_t)p[k] | pitch[k] | step[k]) & 1) == 0,
+                       "%s: %s plane %d of a 16-bit format needs an even pointer, pitch and step (pitch %zu, step %zu)", fn, who, k,
+                       pitch[k], step[k]);
+    }
+    return PIPS_OK;
+}
+
+// the bytes of plane k of F >= 1 surfaces: [p, p + (F - 1) step + (rows - 1) pitch + the bytes of a row)
+void warp_range(const WarpGeom& g, int k, int F, const void* p, size_t pitch, size_t step, uintptr_t& lo, uintptr_t& hi) {
+    lo = (uintptr_t)p, hi = lo + ((size_t)F - 1) * step + (g.rows[k] - 1) * pitch + g.row_bytes[k];
+}
+
+}  // namespace
+
 int pips_frames_warp(int format, int matrix, int range, int border, int fill_rgb, int F, int h, int w, const void* s0, size_t spitch0,
                      size_t sstep0, const void* s1, size_t spitch1, size_t sstep1, const void* s2, size_t spitch2, size_t sstep2, void* d0,
                      size_t dpitch0, size_t dstep0, void* d1, size_t dpitch1, size_t dstep1, void* d2, size_t dpitch2, size_t dstep2,
                      const int32_t* coef, void* stream) {
-    PIPS_CHECK_ARG((format >= PIPS_FMT_RGB24 && format <= PIPS_FMT_I010) || format == PIPS_FMT_PLANAR8, "frames_warp: unknown format %d",
-                   format);
-    PIPS_CHECK_ARG(border == PIPS_WARP_BORDER_CONSTANT || border == PIPS_WARP_BORDER_REPLICATE, "frames_warp: unknown border %d", border);
-    const bool wide = format == PIPS_FMT_P010 || format == PIPS_FMT_I010;                   // 16-bit samples
-    const bool semi = format == PIPS_FMT_NV12 || format == PIPS_FMT_P010;
-    const bool yuv = semi || format == PIPS_FMT_I420 || format == PIPS_FMT_I010;
-    PIPS_CHECK_ARG(!yuv || ((matrix == PIPS_MATRIX_BT601 || matrix == PIPS_MATRIX_BT709) &&
-                            (range == PIPS_RANGE_LIMITED || range == PIPS_RANGE_FULL)),
-                   "frames_warp: unknown matrix %d or range %d", matrix, range);
-    PIPS_CHECK_ARG(fill_rgb >= 0 && fill_rgb <= 0xFFFFFF, "frames_warp: fill_rgb %d outside 0..0xFFFFFF", fill_rgb);
+    const char* fn = "frames_warp";
+    if (int e = warp_check_values(fn, format, matrix, range, border, fill_rgb)) return e;
     PIPS_CHECK_ARG(F >= 0, "frames_warp: need F >= 0 (F=%d)", F);
-    PIPS_CHECK_ARG(h >= 1 && w >= 1, "frames_warp: need a size of at least 1x1 (h=%d, w=%d)", h, w);
-    PIPS_CHECK_ARG(h <= PIPS_WARP_DIM_MAX && w <= PIPS_WARP_DIM_MAX, "frames_warp: surfaces up to %d a side (h=%d, w=%d)",
-                   PIPS_WARP_DIM_MAX, h, w);
-    // plane k of the format: its rows and the bytes of a row (pips_tracks_draw_ex's geometry)
+    WarpGeom g;
+    if (int e = warp_check_size(fn, format, h, w, g)) return e;
     const void* sp[3] = {s0, s1, s2};
     void* dp[3] = {d0, d1, d2};
     const size_t spitch[3] = {spitch0, spitch1, spitch2}, sstep[3] = {sstep0, sstep1, sstep2};
     const size_t dpitch[3] = {dpitch0, dpitch1, dpitch2}, dstep[3] = {dstep0, dstep1, dstep2};
-    const size_t ch = ((size_t)h + 1) / 2, cw = ((size_t)w + 1) / 2, sb = wide ? 2 : 1;
-    const bool planar = format == PIPS_FMT_PLANAR8;
-    const int planes = semi ? 2 : (yuv || planar) ? 3 : 1;
-    const size_t bpp = (format == PIPS_FMT_RGBA32 || format == PIPS_FMT_BGRA32) ? 4 : (yuv || planar) ? sb : 3;
-    const size_t rows[3] = {(size_t)h, planar ? (size_t)h : ch, planar ? (size_t)h : ch};
-    const size_t row_bytes[3] = {(size_t)w * bpp, planar ? (size_t)w : (semi ? 2 * cw : cw) * sb, planar ? (size_t)w : cw * sb};
-    for (int side = 0; side < 2; ++side) {
-        const char* who = side ? "dst" : "src";
-        const size_t* pitch = side ? dpitch : spitch;
-        const size_t* step = side ? dstep : sstep;
-        for (int k = 0; k < planes; ++k) {
-            const uintptr_t p = side ? (uintptr_t)dp[k] : (uintptr_t)sp[k];
-            PIPS_CHECK_ARG(pitch[k] >= row_bytes[k], "frames_warp: pitch %zu of %s plane %d is below the %zu bytes of a row", pitch[k], who,
-                           k, row_bytes[k]);
-            PIPS_CHECK_ARG(F <= 1 || (step[k] >= pitch[k] && step[k] / pitch[k] >= rows[k]),
-                           "frames_warp: step %zu of %s plane %d is below pitch %zu x %zu rows", step[k], who, k, pitch[k], rows[k]);
-            PIPS_CHECK_ARG(!wide || ((p | pitch[k] | step[k]) & 1) == 0,
-                           "frames_warp: %s plane %d of a 16-bit format needs an even pointer, pitch and step (pitch %zu, step %zu)", who,
-                           k, pitch[k], step[k]);
-        }
-    }
+    if (int e = warp_check_side(fn, "src", g, F, sp, spitch, sstep)) return e;
+    if (int e = warp_check_side(fn, "dst", g, F, dp, dpitch, dstep)) return e;
     if (F == 0) return PIPS_OK;
-    for (int k = 0; k < planes; ++k) PIPS_CHECK_ARG(sp[k] != nullptr && dp[k] != nullptr, "frames_warp: null plane %d", k);
+    for (int k = 0; k < g.planes; ++k) PIPS_CHECK_ARG(sp[k] != nullptr && dp[k] != nullptr, "frames_warp: null plane %d", k);
     PIPS_CHECK_ARG(coef != nullptr, "frames_warp: null coef");
-    // the bytes of a plane: [p, p + (F - 1) step + (rows - 1) pitch + the bytes of a row)
-    for (int i = 0; i < planes; ++i)
-        for (int k = 0; k < planes; ++k) {
-            const uintptr_t a0 = (uintptr_t)sp[i], a1 = a0 + ((size_t)F - 1) * sstep[i] + (rows[i] - 1) * spitch[i] + row_bytes[i];
-            const uintptr_t b0 = (uintptr_t)dp[k], b1 = b0 + ((size_t)F - 1) * dstep[k] + (rows[k] - 1) * dpitch[k] + row_bytes[k];
+    for (int i = 0; i < g.planes; ++i)
+        for (int k = 0; k < g.planes; ++k) {
+            uintptr_t a0, a1, b0, b1;
+            warp_range(g, i, F, sp[i], spitch[i], sstep[i], a0, a1);
+            warp_range(g, k, F, dp[k], dpitch[k], dstep[k], b0, b1);
             PIPS_CHECK_ARG(a1 <= b0 || b1 <= a0, "frames_warp: src plane %d and dst plane %d overlap", i, k);
         }
     return launch_frames_warp(format, matrix, range, border, fill_rgb, F, h, w, sp, spitch, sstep, dp, dpitch, dstep, (const int*)coef,
                               (hipStream_t)stream);
+}
+
+int pips_frames_warp_fill(int format, int matrix, int range, int border, int fill_rgb, int Fs, int Fd, int K, int h, int w, const void* s0,
+                          size_t spitch0, size_t sstep0, const void* s1, size_t spitch1, size_t sstep1, const void* s2, size_t spitch2,
+                          size_t sstep2, void* d0, size_t dpitch0, size_t dstep0, void* d1, size_t dpitch1, size_t dstep1, void* d2,
+                          size_t dpitch2, size_t dstep2, const int32_t* cand, const int32_t* coef, uint8_t* source, size_t source_pitch,
+                          size_t source_step, void* stream) {
+    const char* fn = "frames_warp_fill";
+    if (int e = warp_check_values(fn, format, matrix, range, border, fill_rgb)) return e;
+    PIPS_CHECK_ARG(Fs >= 0 && Fd >= 0, "frames_warp_fill: need Fs >= 0 and Fd >= 0 (Fs=%d, Fd=%d)", Fs, Fd);
+    PIPS_CHECK_ARG(K >= 1 && K <= PIPS_WARP_FILL_MAX, "frames_warp_fill: K=%d outside 1..%d", K, PIPS_WARP_FILL_MAX);
+    WarpGeom g;
+    if (int e = warp_check_size(fn, format, h, w, g)) return e;
+    const void* sp[3] = {s0, s1, s2};
+    void* dp[3] = {d0, d1, d2};
+    const size_t spitch[3] = {spitch0, spitch1, spitch2}, sstep[3] = {sstep0, sstep1, sstep2};
+    const size_t dpitch[3] = {dpitch0, dpitch1, dpitch2}, dstep[3] = {dstep0, dstep1, dstep2};
+    if (int e = warp_check_side(fn, "src", g, Fs, sp, spitch, sstep)) return e;
+    if (int e = warp_check_side(fn, "dst", g, Fd, dp, dpitch, dstep)) return e;
+    if (source != nullptr) {
+        PIPS_CHECK_ARG(source_pitch >= (size_t)w, "frames_warp_fill: source pitch %zu is below the %d bytes of a row", source_pitch, w);
+        PIPS_CHECK_ARG(Fd <= 1 || (source_step >= source_pitch && source_step / source_pitch >= (size_t)h),
+                       "frames_warp_fill: source step %zu is below pitch %zu x %d rows", source_step, source_pitch, h);
+    }
+    if (Fd == 0) return PIPS_OK;
+    for (int k = 0; k < g.planes; ++k)
+        PIPS_CHECK_ARG((Fs == 0 || sp[k] != nullptr) && dp[k] != nullptr, "frames_warp_fill: null plane %d", k);
+    PIPS_CHECK_ARG(cand != nullptr && coef != nullptr, "frames_warp_fill: null cand or coef");
+    const uintptr_t m0 = (uintptr_t)source, m1 = m0 + ((size_t)Fd - 1) * source_step + ((size_t)h - 1) * source_pitch + (size_t)w;
+    for (int k = 0; k < g.planes; ++k) {
+        uintptr_t b0, b1;
+        warp_range(g, k, Fd, dp[k], dpitch[k], dstep[k], b0, b1);
+        PIPS_CHECK_ARG(source == nullptr || m1 <= b0 || b1 <= m0, "frames_warp_fill: source and dst plane %d overlap", k);
+        for (int i = 0; i < g.planes && Fs > 0; ++i) {
+            uintptr_t a0, a1;
+            warp_range(g, i, Fs, sp[i], spitch[i], sstep[i], a0, a1);
+            PIPS_CHECK_ARG(a1 <= b0 || b1 <= a0, "frames_warp_fill: src plane %d and dst plane %d overlap", i, k);
+            PIPS_CHECK_ARG(source == nullptr || m1 <= a0 || a1 <= m0, "frames_warp_fill: source and src plane %d overlap", i);
+        }
+    }
+    return launch_frames_warp_fill(format, matrix, range, border, fill_rgb, Fs, Fd, K, h, w, sp, spitch, sstep, dp, dpitch, dstep,
+                                   (const int*)cand, (const int*)coef, source, source_pitch, source_step, (hipStream_t)stream);
 }
 
 // ---- whole forward

@@ -621,5 +621,12 @@ constexpr int WARP_LDS_BYTES = 12288;
 int launch_frames_warp(int format, int matrix, int range, int border, int fill_rgb, int F, int h, int w, const void* const* sp,
                        const size_t* spitch, const size_t* sstep, void* const* dp, const size_t* dpitch, const size_t* dstep,
                        const int* coef, hipStream_t st);
+// pips_frames_warp_fill: Fd output frames from Fs source frames, K candidates (cand (Fd,K), coef (Fd,K,6)) per output frame; the same
+// block per tile and OUTPUT frame.  A tile that candidate 0 covers whole is launch_frames_warp's tile; the others walk the list.
+// source: nullptr or the (Fd,h,w) map of list positions.  Arguments checked by the caller.
+int launch_frames_warp_fill(int format, int matrix, int range, int border, int fill_rgb, int Fs, int Fd, int K, int h, int w,
+                            const void* const* sp, const size_t* spitch, const size_t* sstep, void* const* dp, const size_t* dpitch,
+                            const size_t* dstep, const int* cand, const int* coef, unsigned char* source, size_t source_pitch,
+                            size_t source_step, hipStream_t st);
 
 }  // namespace pips

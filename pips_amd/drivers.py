@@ -40,6 +40,9 @@
   of ``motion_fit`` peeled into motion layers on the columns left over, by one ``pips_motion_layers`` call, and the layers linked
   from pair to pair into object ids on the host; the torch form is the same exact rule, equal in every bit; ``MotionLayers`` does
   it for the pushes of a streamed tracker, keeping the last pair's labels, ids and counts by identity.
+* ``fill_candidates`` / ``warp_frames_fill`` / ``warp_frames_fill_torch`` / ``crop_zoom`` / ``Stabilizer(neighbors=)`` -- the border of
+  a stabilised frame filled from its neighbouring frames by one ``pips_frames_warp_fill`` call, with a byte-exact torch twin, and
+  the crop zoom at which no border shows at all.
 * ``motion_smooth`` / ``warp_coefficients`` / ``warp_frames`` / ``warp_frames_torch`` / ``Stabilizer`` -- frames out, stabilised: the
   camera path smoothed on the host, the corrections turned into fixed-point affine rows, and the decoder's surfaces resampled
   through them by one ``pips_frames_warp`` call, in every format import and draw speak; the torch form is the same integer rule,
@@ -2607,6 +2610,36 @@ def motion_smooth(path, radius=15):
     return torch.tensor(out, dtype=torch.float64).reshape(len(out), 4)
 
 
+def _warp_maps(transforms, size, surface):
+    """the checks of ``warp_coefficients`` on the transforms and the sizes -> (affine rows as a list of six floats each, (h, w) of the
+    surface, S1: surface index -> model index, S4: model index -> surface index, both 3 x 3 float64)"""
+    t = torch.as_tensor(transforms).to("cpu", torch.float64)
+    if t.dim() != 2 or t.shape[1] not in (4, 6):
+        raise ValueError(f"transforms must be (F,4) or (F,6), not {tuple(t.shape)}")
+    H, W = int(size[0]), int(size[1])
+    h, w = (H, W) if surface is None else (int(surface[0]), int(surface[1]))
+    if min(H, W, h, w) < 1:
+        raise ValueError(f"sizes must be at least 1 x 1, not {H} x {W} and {h} x {w}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("transforms has a non-finite entry")
+    if t.shape[1] == 4:
+        t = torch.stack([t[:, 0], -t[:, 1], t[:, 2], t[:, 1], t[:, 0], t[:, 3]], dim=1)
+    sx, sy = w / W, h / H
+    eye = [0.0, 0.0, 1.0]
+    S1 = torch.tensor([[1.0 / sx, 0.0, 0.5 / sx - 0.5], [0.0, 1.0 / sy, 0.5 / sy - 0.5], eye], dtype=torch.float64)
+    S4 = torch.tensor([[sx, 0.0, 0.5 * sx - 0.5], [0.0, sy, 0.5 * sy - 0.5], eye], dtype=torch.float64)
+    return t.tolist(), (h, w), S1, S4
+
+
+def _affine_inverse(a, b, c, d, e, f):
+    """the inverse of x' = a x + b y + c, y' = d x + e y + f as a 3 x 3 float64 matrix; ValueError for a singular map"""
+    det = a * e - b * d
+    if det == 0.0 or not math.isfinite(det) or not math.isfinite(1.0 / det):
+        raise ValueError(f"the map ({a}, {b}, {c}, {d}, {e}, {f}) is singular")
+    ia, ib, id_, ie = e / det, -b / det, -d / det, a / det
+    return torch.tensor([[ia, ib, -(ia * c + ib * f)], [id_, ie, -(id_ * c + ie * f)], [0.0, 0.0, 1.0]], dtype=torch.float64)
+
+
 def warp_coefficients(transforms, size, surface=None, zoom=1.0):
     """Forward transforms -> the (F,6) int32 rows of ``pips_frames_warp`` on the host, in float64.  ``transforms`` is (F,4)
     similarity rows (a_re, a_im, tx, ty) -- ``motion_smooth``'s output; the affine row (a_re, -a_im, tx, a_im, a_re, ty) -- or (F,6)
@@ -2618,31 +2651,14 @@ def warp_coefficients(transforms, size, surface=None, zoom=1.0):
     through the inverse of the forward map, and from model index back to surface index.  Rows 0 and 1 of the product are quantised
     with floor(v 2^24 + 0.5) for the linear terms and floor(v 2^16 + 0.5) for the offsets.  ValueError for a singular map, zoom <= 0,
     a non-finite entry and a coefficient outside int32 (a linear term needs |v| < 128, an offset |v| < 32768 px)."""
-    t = torch.as_tensor(transforms).to("cpu", torch.float64)
-    if t.dim() != 2 or t.shape[1] not in (4, 6):
-        raise ValueError(f"transforms must be (F,4) or (F,6), not {tuple(t.shape)}")
-    H, W = int(size[0]), int(size[1])
-    h, w = (H, W) if surface is None else (int(surface[0]), int(surface[1]))
-    if min(H, W, h, w) < 1:
-        raise ValueError(f"sizes must be at least 1 x 1, not {H} x {W} and {h} x {w}")
     if isinstance(zoom, bool) or not isinstance(zoom, (int, float)) or not math.isfinite(zoom) or zoom <= 0:
         raise ValueError(f"zoom must be a finite number above 0, not {zoom!r}")
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError("transforms has a non-finite entry")
-    if t.shape[1] == 4:
-        t = torch.stack([t[:, 0], -t[:, 1], t[:, 2], t[:, 1], t[:, 0], t[:, 3]], dim=1)
-    sx, sy, cx, cy, z = w / W, h / H, (w - 1) / 2, (h - 1) / 2, 1.0 / float(zoom)
-    eye = [0.0, 0.0, 1.0]
-    Z = torch.tensor([[z, 0.0, cx - cx * z], [0.0, z, cy - cy * z], eye], dtype=torch.float64)
-    S1 = torch.tensor([[1.0 / sx, 0.0, 0.5 / sx - 0.5], [0.0, 1.0 / sy, 0.5 / sy - 0.5], eye], dtype=torch.float64)
-    S4 = torch.tensor([[sx, 0.0, 0.5 * sx - 0.5], [0.0, sy, 0.5 * sy - 0.5], eye], dtype=torch.float64)
+    t, (h, w), S1, S4 = _warp_maps(transforms, size, surface)
+    cx, cy, z = (w - 1) / 2, (h - 1) / 2, 1.0 / float(zoom)
+    Z = torch.tensor([[z, 0.0, cx - cx * z], [0.0, z, cy - cy * z], [0.0, 0.0, 1.0]], dtype=torch.float64)
     out = []
-    for a, b, c, d, e, f in t.tolist():
-        det = a * e - b * d
-        if det == 0.0 or not math.isfinite(det) or not math.isfinite(1.0 / det):
-            raise ValueError(f"the map ({a}, {b}, {c}, {d}, {e}, {f}) is singular")
-        ia, ib, id_, ie = e / det, -b / det, -d / det, a / det
-        inv = torch.tensor([[ia, ib, -(ia * c + ib * f)], [id_, ie, -(id_ * c + ie * f)], eye], dtype=torch.float64)
+    for a, b, c, d, e, f in t:
+        inv = _affine_inverse(a, b, c, d, e, f)
         M = (S4 @ (inv @ (S1 @ Z))).tolist()
         row = []
         for r in (0, 1):
@@ -2656,10 +2672,8 @@ def warp_coefficients(transforms, size, surface=None, zoom=1.0):
     return torch.tensor(out, dtype=torch.int32).reshape(len(out), 6)
 
 
-def _warp_plane(src, m, chroma, border, fill):
-    """one plane of one frame: src (h,w,C) int64 values, m the frame's six python ints, fill (C,) int64 -> (h,w,C) int64"""
-    h, w, _ = src.shape
-    dev = src.device
+def _warp_positions(h, w, m, chroma, dev):
+    """U (h,w) and V (h,w) int64: the source position, in 1/256 sample, of every sample of an h x w plane under the six python ints m"""
     x, y = torch.arange(w, dtype=torch.int64, device=dev).view(1, w), torch.arange(h, dtype=torch.int64, device=dev).view(h, 1)
     if chroma:
         U = (m[0] * (4 * x + 1) + m[1] * (4 * y + 1) + 512 * m[2] - 2 ** 24 + 2 ** 17) >> 18
@@ -2667,6 +2681,13 @@ def _warp_plane(src, m, chroma, border, fill):
     else:
         U = (m[0] * x + m[1] * y + 256 * m[2] + 32768) >> 16
         V = (m[3] * x + m[4] * y + 256 * m[5] + 32768) >> 16
+    return U, V
+
+
+def _warp_plane(src, m, chroma, border, fill):
+    """one plane of one frame: src (h,w,C) int64 values, m the frame's six python ints, fill (C,) int64 -> (h,w,C) int64"""
+    h, w, _ = src.shape
+    U, V = _warp_positions(h, w, m, chroma, src.device)
     x0, fx, y0, fy = U >> 8, (U & 255).unsqueeze(-1), V >> 8, (V & 255).unsqueeze(-1)
 
     def tap(xi, yi):
@@ -2677,6 +2698,38 @@ def _warp_plane(src, m, chroma, border, fill):
         return torch.where(inside.unsqueeze(-1), v, fill.view(1, 1, -1))
     p00, p01, p10, p11 = tap(x0, y0), tap(x0 + 1, y0), tap(x0, y0 + 1), tap(x0 + 1, y0 + 1)
     return ((256 - fy) * ((256 - fx) * p00 + fx * p01) + fy * ((256 - fx) * p10 + fx * p11) + 32768) >> 16
+
+
+def _warp_covers(h, w, m, chroma, dev="cpu"):
+    """(h,w) bool: the samples of an h x w plane that the row m covers -- every tap that has weight lies inside the plane, per axis
+    x0 >= 0 and (x0 + 1 <= w - 1, or fx == 0 and x0 <= w - 1)"""
+    U, V = _warp_positions(h, w, m, chroma, dev)
+
+    def axis(P, n):
+        i, f = P >> 8, P & 255
+        return (i >= 0) & ((i + 1 <= n - 1) | ((f == 0) & (i <= n - 1)))
+    return axis(U, w) & axis(V, h)
+
+
+def _fill_plane(get, shape, Fs, cand, rows, chroma, border, fill):
+    """one plane of one output frame of pips_frames_warp_fill: get(f) -> the (h,w,C) int64 values of source frame f, shape = (h,w,C),
+    cand the K python ints and rows the K rows of the frame -> (values (h,w,C), who (h,w)): candidate 0 under the border rule (the
+    fill when it is invalid), then the candidates from the last to the first, each laid over what it covers, so that the first in
+    list order is the one that stays.  A covering candidate needs no border rule: "replicate" only moves its taps of weight 0"""
+    h, w, C = shape
+    dev = fill.device
+    if 0 <= cand[0] < Fs:
+        value = _warp_plane(get(cand[0]), rows[0], chroma, border, fill)
+    else:
+        value = fill.view(1, 1, C).expand(h, w, C)
+    who = torch.full((h, w), ops.WARP_FILL_NONE, dtype=torch.int64, device=dev)
+    for k in reversed(_range(len(cand))):
+        if not 0 <= cand[k] < Fs:
+            continue
+        cov = _warp_covers(h, w, rows[k], chroma, dev)
+        value = torch.where(cov.unsqueeze(-1), _warp_plane(get(cand[k]), rows[k], chroma, "replicate", fill), value)
+        who = torch.where(cov, k, who)
+    return value, who
 
 
 def warp_frames_torch(planes, fmt, coef, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited"):
@@ -2724,6 +2777,61 @@ def warp_frames_torch(planes, fmt, coef, border="constant", fill=(0, 0, 0), matr
     return out[0] if len(out) == 1 else out
 
 
+def warp_frames_fill_torch(planes, fmt, cand, coef, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited", source=False):
+    """pips_frames_warp_fill (include/pips_hip.h) as int64 torch ops, on any device: ``ops.warp_frames_fill``'s arguments (without
+    ``out``) -> Fd new surfaces of the source's format, a tensor for one plane and a list otherwise, and with ``source=True``
+    ``(planes, map)``, the (Fd,h,w) uint8 map of the list position that supplied each sample of plane 0.  Per output frame and
+    plane ``_fill_plane``: candidate 0 under the border rule, every covering candidate laid over it.  Equal to the kernel byte for
+    byte, the map included; written to be read, not to be fast."""
+    planes = [planes] if torch.is_tensor(planes) else list(planes)
+    dtypes = [p.dtype for p in planes]
+    planes, Fs, Fd, K, h, w, cand, coef, fill_rgb = ops.warp_fill_check(planes, fmt, cand, coef, border, fill, matrix, range)
+    dev = planes[0].device
+    cands, rows = cand.to("cpu", torch.int64).tolist(), coef.to("cpu", torch.int64).tolist()
+    wide, shift = fmt in ops.IMPORT_16BIT, 6 if fmt == "p010" else 0
+    yuv = fmt in ("nv12", "i420") or wide
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    rgb = torch.tensor([fill_rgb >> 16, (fill_rgb >> 8) & 255, fill_rgb & 255], dtype=torch.int64)
+    comp = (rgb_to_yuv_torch(rgb, matrix, range, 10 if wide else 8) if yuv else rgb).to(dev)
+    out = [torch.zeros((Fd,) + tuple(p.shape[1:]), dtype=p.dtype, device=dev) for p in planes]
+    smap = torch.zeros(Fd, h, w, dtype=torch.uint8, device=dev)
+
+    def value(p):                                                                                  # a plane of one frame -> its samples' values
+        return ((p.to(torch.int64) & 0xFFFF) >> shift) & 1023 if wide else p.to(torch.int64)
+
+    def word(v):                                                                                   # values -> what is stored
+        if not wide:
+            return v.to(torch.uint8)
+        v = v << shift
+        return (v - ((v & 0x8000) << 1)).to(torch.int16)
+    for j in _range(Fd):
+        def one(get, shape, chroma, fillc):
+            return _fill_plane(get, shape, Fs, cands[j], rows[j], chroma, border, fillc)
+        if fmt == "planar8":
+            for c in (0, 1, 2):
+                v, who = one(lambda f: value(planes[0][f, c]).unsqueeze(-1), (h, w, 1), False, comp[c:c + 1])
+                out[0][j, c] = word(v[..., 0])
+                if c == 0:
+                    smap[j] = who.to(torch.uint8)
+        elif yuv:
+            v, who = one(lambda f: value(planes[0][f]).unsqueeze(-1), (h, w, 1), False, comp[:1])
+            out[0][j], smap[j] = word(v[..., 0]), who.to(torch.uint8)
+            if fmt in ("nv12", "p010"):
+                out[1][j] = word(one(lambda f: value(planes[1][f]), (ch, cw, 2), True, comp[1:])[0])
+            else:
+                for k in (1, 2):
+                    out[k][j] = word(one(lambda f: value(planes[k][f]).unsqueeze(-1), (ch, cw, 1), True, comp[k:k + 1])[0][..., 0])
+        else:
+            order = comp.flip(0) if fmt in ("bgr24", "bgra32") else comp                            # the bytes of a pixel in memory order
+            v, who = one(lambda f: value(planes[0][f, ..., :3]), (h, w, 3), False, order)
+            out[0][j, ..., :3], smap[j] = word(v), who.to(torch.uint8)
+            if fmt in ("rgba32", "bgra32"):
+                out[0][j, ..., 3] = 255
+    out = [p.view(t) for p, t in zip(out, dtypes)]
+    out = out[0] if len(out) == 1 else out
+    return (out, smap) if source else out
+
+
 def warp_frames(planes, fmt, transforms, size=None, zoom=1.0, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited",
                 out=None):
     """Frames moved by forward transforms on the device: ``warp_coefficients(transforms, size, surface, zoom)`` followed by one
@@ -2742,6 +2850,152 @@ def warp_frames(planes, fmt, transforms, size=None, zoom=1.0, border="constant",
     return res[0] if len(res) == 1 else res
 
 
+def _fill_neighbors(neighbors):
+    if isinstance(neighbors, (str, bytes)) or len(tuple(neighbors)) != 2:
+        raise ValueError(f"neighbors must be (back, ahead), not {neighbors!r}")
+    back, ahead = (_whole(v, "neighbors", 0) for v in neighbors)
+    if 1 + back + ahead > ops.WARP_FILL_MAX:
+        raise ValueError(f"at most {ops.WARP_FILL_MAX} candidates a frame, not 1 + {back} + {ahead}")
+    return back, ahead
+
+
+def _fill_offsets(back, ahead):
+    """the slot order: offset 0, -1, +1, -2, +2, ..., restricted to -back .. +ahead"""
+    out = [0]
+    for d in _range(1, max(back, ahead) + 1):
+        out += ([-d] if d <= back else []) + ([d] if d <= ahead else [])
+    return out
+
+
+def _fill_rows(path, corr, f0, offsets, total):
+    """the candidate rows of the frames f0 .. f0 + len(corr) - 1: ``path(g)`` -> (A_g, T_g) complex for a frame 0 <= g < total, corr
+    their corrections as lists of four floats -> (frames, transforms) as nested lists.  Slot 0 is the correction itself.  The
+    transform of frame g into the stabilised frame f, W_f o P_f^-1 o P_g, is composed in this order of complex operations:
+    I = (1 / A_f, -(1 / A_f) T_f); C = (W_a I_a, W_a I_t + W_t); R = (C_a A_g, C_a T_g + C_t)"""
+    frames, rows = [], []
+    for i, w in enumerate(corr):
+        f = f0 + i
+        Wa, Wt = complex(w[0], w[1]), complex(w[2], w[3])
+        Af, Tf = path(f)
+        Ia = 1.0 / Af
+        It = -(Ia * Tf)
+        Ca, Ct = Wa * Ia, Wa * It + Wt
+        fr, tr = [], []
+        for off in offsets:
+            g = f + off
+            if off == 0:
+                fr.append(f), tr.append([w[0], w[1], w[2], w[3]])
+            elif 0 <= g < total:
+                Ag, Tg = path(g)
+                Ra, Rt = Ca * Ag, Ca * Tg + Ct
+                fr.append(g), tr.append([Ra.real, Ra.imag, Rt.real, Rt.imag])
+            else:
+                fr.append(-1), tr.append([1.0, 0.0, 0.0, 0.0])
+        frames.append(fr), rows.append(tr)
+    return frames, rows
+
+
+def fill_candidates(path, corrections, neighbors=(3, 1), first=0):
+    """The candidate lists that fill a stabilised frame's border from its neighbours (``warp_frames_fill``), on the host in float64:
+    ``path`` (F,4) is ``motion_path``'s output for the whole video and ``corrections`` (n,4) the rows of ``motion_smooth`` /
+    ``Stabilizer`` for the frames ``first .. first + n - 1`` (default: all F) -> ``(frames (n,K) int64, transforms (n,K,4) float64)``
+    with K = 1 + back + ahead for ``neighbors`` = (back, ahead).  Slot order: offset 0, -1, +1, -2, +2, ..., restricted to -back ..
+    +ahead; ``frames[f][k]`` is the absolute index of the frame in slot k and ``transforms[f][k]`` the similarity that takes its
+    positions into the STABILISED frame f: W_f o P_f^-1 o P_g, with P from ``path`` (frame -> frame 0) and W the correction, composed
+    in the fixed order of complex operations of ``_fill_rows`` so that ``Stabilizer.candidates`` reproduces the bits; slot 0 is the
+    correction itself.  A slot whose frame falls outside [0, F) holds -1 and an identity row -- it is NOT replaced by a farther
+    frame, so K is fixed and the streamed form is the one-shot."""
+    back, ahead = _fill_neighbors(neighbors)
+    path = torch.as_tensor(path).to("cpu", torch.float64)
+    corr = torch.as_tensor(corrections).to("cpu", torch.float64)
+    first = _whole(first, "first", 0)
+    if path.dim() != 2 or path.shape[1] != 4 or corr.dim() != 2 or corr.shape[1] != 4:
+        raise ValueError(f"path and corrections must be (F,4) and (n,4), not {tuple(path.shape)} and {tuple(corr.shape)}")
+    if first + corr.shape[0] > path.shape[0]:
+        raise ValueError(f"corrections of frames [{first}, {first + corr.shape[0]}) of a path with {path.shape[0]} rows")
+    if not bool(torch.isfinite(path).all()) or not bool(torch.isfinite(corr).all()):
+        raise ValueError("path or corrections has a non-finite entry")
+    rows = [(complex(r[0], r[1]), complex(r[2], r[3])) for r in path.tolist()]
+    if any(A == 0 for A, _ in rows):
+        raise ValueError("a path row with A = 0 has no inverse")
+    offsets = _fill_offsets(back, ahead)
+    frames, tr = _fill_rows(lambda g: rows[g], corr.tolist(), first, offsets, len(rows))
+    return (torch.tensor(frames, dtype=torch.int64).reshape(len(frames), len(offsets)),
+            torch.tensor(tr, dtype=torch.float64).reshape(len(tr), len(offsets), 4))
+
+
+def _fill_setup(planes, fmt, frames, transforms, first, size, zoom):
+    """``warp_frames_fill``'s candidate lists -> (cand (F,K) int64 indices into the held surfaces, coef (F,K,6) int32)"""
+    _, Fs, h, w = ops.draw_planes(planes, fmt)
+    frames = torch.as_tensor(frames).to("cpu")
+    t = torch.as_tensor(transforms).to("cpu", torch.float64)
+    if frames.dim() != 2 or frames.dtype.is_floating_point or t.dim() != 3 or tuple(t.shape[:2]) != tuple(frames.shape) or t.shape[2] not in (4, 6):
+        raise ValueError(f"frames must be integers (F,K) and transforms (F,K,4) or (F,K,6), not {tuple(frames.shape)} and {tuple(t.shape)}")
+    frames, first = frames.to(torch.int64), _whole(first, "first", 0)
+    held = frames >= 0
+    if bool((held & ((frames < first) | (frames >= first + Fs))).any()):
+        raise ValueError(f"a candidate frame lies outside the held surfaces [{first}, {first + Fs})")
+    F, K = frames.shape
+    coef = warp_coefficients(t.reshape(F * K, t.shape[2]), (h, w) if size is None else size, (h, w), zoom).reshape(F, K, 6)
+    return torch.where(held, frames - first, torch.full_like(frames, -1)), coef
+
+
+def warp_frames_fill(planes, fmt, frames, transforms, first=0, size=None, zoom=1.0, border="constant", fill=(0, 0, 0), matrix="bt709",
+                     range="limited", out=None, source=None):
+    """Stabilised frames whose border is filled from neighbouring frames, on the device: ``warp_coefficients`` on every slot of
+    ``fill_candidates``' / ``Stabilizer.candidates``' ``(frames (F,K), transforms (F,K,4))`` followed by one
+    ``pips_frames_warp_fill`` call (``ops.warp_frames_fill``).  ``planes`` / ``fmt`` hold the source frames ``first .. first + Fs - 1``
+    of the video; ``frames`` are absolute indices, -1 for an empty slot; a non-negative index outside the held range is a
+    ValueError.  ``size``, ``zoom``, ``border``, ``fill``, ``matrix``, ``range`` as in ``warp_frames``; ``out`` / ``source`` as in
+    ``ops.warp_frames_fill``.  Returns F new surfaces (``out`` when given), a tensor for one plane and a list otherwise, and
+    ``(surfaces, map)`` when a source map was asked for.  Known limits: a moving object is shown where the neighbour saw it, no
+    feathering or exposure matching at the seam, luma and chroma choose independently, nothing comes from frames outside the list."""
+    cand, coef = _fill_setup(planes, fmt, frames, transforms, first, size, zoom)
+    res = ops.warp_frames_fill(planes, fmt, cand, coef, border, fill, matrix, range, out=out, source=source)
+    res, smap = res if isinstance(res, tuple) else (res, None)
+    if out is None:                                                                                # (uint16 planes come back as uint16)
+        given = [planes] if torch.is_tensor(planes) else list(planes)
+        res = [r.view(p.dtype) for r, p in zip(res, given)]
+    else:
+        res = [out] if torch.is_tensor(out) else list(out)
+    res = res[0] if len(res) == 1 else res
+    return res if smap is None else (res, smap)
+
+
+def crop_zoom(transforms, size, surface=None, margin=1.0 / 128):
+    """The automatic crop: the smallest ``zoom`` of ``warp_frames`` / ``warp_frames_fill`` at which every output pixel of every frame
+    lands inside its own source frame, so that no border shows.  A closed form on the host, in float64: ``transforms`` (F,4) or
+    (F,6), ``size`` and ``surface`` are ``warp_coefficients``'.  With N_f the product that function forms without the zoom (model
+    index <- surface index, the inverse forward map, surface index <- model index), L_f its linear part and c the surface centre,
+    the corner u of the output lands at N_f c + L_f (u - c) / z.  Per frame, corner and axis, with d the component of L_f (u - c)
+    and the slack that of N_f c to the end of [margin, extent - 1 - margin] that d points to: z >= |d| / slack; the maximum over all
+    of them is returned (corners suffice: the map is affine).  The identity gives exactly 1.0 at ``margin=0``.  The fixed-point rows of
+    ``warp_coefficients`` stand within about 0.003 px of the float map at sides up to 8192 (2^-24 of a linear term times 8192, twice,
+    and 2^-17 of the offset): the default margin of 1/128 px keeps the quantised rows inside too.  ValueError when a frame's centre
+    lies outside that interval (no zoom can help), for a singular map and for a negative or non-finite margin."""
+    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin) or margin < 0:
+        raise ValueError(f"margin must be a finite number of at least 0, not {margin!r}")
+    t, (h, w), S1, S4 = _warp_maps(transforms, size, surface)
+    cx, cy = (w - 1) / 2, (h - 1) / 2
+    zoom = 0.0
+    for a, b, c, d, e, f in t:
+        N = (S4 @ (_affine_inverse(a, b, c, d, e, f) @ S1)).tolist()
+        for r, extent in ((0, w), (1, h)):
+            at = N[r][0] * cx + N[r][1] * cy + N[r][2]
+            lo, hi = float(margin), extent - 1 - float(margin)
+            if not lo <= at <= hi:
+                raise ValueError(f"the centre of a frame under ({a}, {b}, {c}, {d}, {e}, {f}) lands at {at} outside [{lo}, {hi}]")
+            for ux in (-cx, cx):
+                for uy in (-cy, cy):
+                    dist = N[r][0] * ux + N[r][1] * uy
+                    slack = hi - at if dist > 0 else at - lo
+                    if dist != 0.0:
+                        if slack <= 0.0:
+                            raise ValueError(f"the centre of a frame under ({a}, {b}, {c}, {d}, {e}, {f}) lies on the margin")
+                        zoom = max(zoom, abs(dist) / slack)
+    return zoom
+
+
 class Stabilizer:
     """The corrections that stabilise a streamed video, push by push: ``step(f0, trajs, vis, ids)`` takes the ``(f0, trajs
     (1,m,n,2), vis (1,m,n)[, ids (n,)])`` of a tracker's push, fits the camera motion of its pairs with an internal
@@ -2751,10 +3005,17 @@ class Stabilizer:
     ``finish()`` returns the rest, their windows clamped at the end of the video; ``radius=None`` holds the camera still and makes
     every frame final at once.  All returns together equal ``motion_smooth(motion_path(all models), radius)`` in every bit.
     The stabiliser holds no frames: the caller keeps its surfaces until their corrections come back, as with ``TrackPainter``, and
-    warps them then (``warp_frames``)."""
+    warps them then (``warp_frames``).  ``neighbors=(back, ahead)``: after a ``step`` / ``finish`` that returned ``(g0, k rows)``,
+    ``candidates(g0, k)`` returns the ``(frames, transforms)`` rows of those frames for ``warp_frames_fill``, equal in every bit to
+    ``fill_candidates`` on the whole video's path and corrections.  ``ahead`` may not pass ``radius`` (0 with ``radius=None``): a
+    final frame's ``ahead`` neighbours have then been seen; at ``finish`` the slots past the last frame are -1."""
 
-    def __init__(self, radius=15, engine="library", **motion_params):
+    def __init__(self, radius=15, engine="library", neighbors=None, **motion_params):
         self.radius = _smooth_radius(radius)
+        self.neighbors = None if neighbors is None else _fill_neighbors(neighbors)
+        if self.neighbors is not None and self.neighbors[1] > (0 if self.radius is None else self.radius):
+            raise ValueError(f"neighbors ahead = {self.neighbors[1]} passes radius = {self.radius}: a final frame's neighbours must have been seen")
+        self.corr = []                                               # the corrections handed out, for candidates()
         self.estimator = MotionEstimator(engine=engine, **motion_params)
         self.A, self.T = complex(1.0, 0.0), complex(0.0, 0.0)
         self.path, self.g, self.done = [], [], 0                     # (A, T) and parameters of every frame seen; frames handed out
@@ -2765,7 +3026,23 @@ class Stabilizer:
             A, T = self.path[f]
             rows.append([A.real, A.imag, T.real, T.imag] if self.radius is None else _smooth_row(self.g, A, T, f, self.radius))
         g0, self.done = self.done, max(upto, self.done)
+        if self.neighbors is not None:
+            self.corr += rows
         return g0, torch.tensor(rows, dtype=torch.float64).reshape(len(rows), 4)
+
+    def candidates(self, g0, k):
+        """the ``fill_candidates`` rows of the frames g0 .. g0 + k - 1, all of them handed out already -> (frames (k,K) int64,
+        transforms (k,K,4) float64).  Called after the ``step`` / ``finish`` that returned them: a slot ahead that has not been
+        seen is past the end of the video only then"""
+        if self.neighbors is None:
+            raise ValueError("candidates() needs Stabilizer(neighbors=(back, ahead))")
+        g0, k = _whole(g0, "g0", 0), _whole(k, "k", 0)
+        if g0 + k > self.done:
+            raise ValueError(f"frames [{g0}, {g0 + k}) have not all been handed out ({self.done} have)")
+        offsets = _fill_offsets(*self.neighbors)
+        frames, tr = _fill_rows(lambda g: self.path[g], self.corr[g0:g0 + k], g0, offsets, len(self.path))
+        return (torch.tensor(frames, dtype=torch.int64).reshape(k, len(offsets)),
+                torch.tensor(tr, dtype=torch.float64).reshape(k, len(offsets), 4))
 
     def _see(self, A, T):
         if self.radius is not None:

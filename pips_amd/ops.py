@@ -616,10 +616,8 @@ WARP_DIM_MAX, WARP_TILE_W, WARP_TILE_H, WARP_LDS_BYTES = 8192, 64, 16, 12288
 _INT32 = (-2 ** 31, 2 ** 31 - 1)
 
 
-def warp_check(planes, fmt, coef, border, fill, matrix, range):
-    """pips_frames_warp's limits on the values, shared by ``warp_frames`` and ``drivers.warp_frames_torch`` -> (planes, F, h, w,
-    coef (F,6) int32 on its own device, fill_rgb)"""
-    planes, F, h, w = draw_planes(planes, fmt)
+def _warp_values(h, w, border, fill, matrix, range):
+    """the limits on the values that pips_frames_warp and pips_frames_warp_fill share -> fill_rgb"""
     if matrix not in IMPORT_MATRICES or range not in IMPORT_RANGES:
         raise ValueError(f"matrix must be one of {sorted(IMPORT_MATRICES)} and range one of {sorted(IMPORT_RANGES)}, "
                          f"not {matrix!r}, {range!r}")
@@ -630,12 +628,25 @@ def warp_check(planes, fmt, coef, border, fill, matrix, range):
     fill = list(fill)
     if len(fill) != 3 or any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 255 for v in fill):
         raise ValueError(f"fill must be three whole numbers R, G, B in 0..255, not {fill!r}")
+    return int(fill[0]) << 16 | int(fill[1]) << 8 | int(fill[2])
+
+
+def _warp_rows(coef, shape, name):
+    """integer rows of the given shape that fit int32 -> int32, on their own device"""
     coef = torch.as_tensor(coef)
-    if coef.dim() != 2 or tuple(coef.shape) != (F, 6) or coef.dtype.is_floating_point or coef.dtype == torch.bool:
-        raise ValueError(f"coef must be integers (F,6) = {(F, 6)}, not {coef.dtype} {tuple(coef.shape)}")
+    if tuple(coef.shape) != shape or coef.dtype.is_floating_point or coef.dtype == torch.bool:
+        raise ValueError(f"coef must be integers {name} = {shape}, not {coef.dtype} {tuple(coef.shape)}")
     if coef.numel() and (int(coef.min()) < _INT32[0] or int(coef.max()) > _INT32[1]):
         raise ValueError("a coefficient does not fit int32")
-    return planes, F, h, w, coef.to(torch.int32), int(fill[0]) << 16 | int(fill[1]) << 8 | int(fill[2])
+    return coef.to(torch.int32)
+
+
+def warp_check(planes, fmt, coef, border, fill, matrix, range):
+    """pips_frames_warp's limits on the values, shared by ``warp_frames`` and ``drivers.warp_frames_torch`` -> (planes, F, h, w,
+    coef (F,6) int32 on its own device, fill_rgb)"""
+    planes, F, h, w = draw_planes(planes, fmt)
+    fill_rgb = _warp_values(h, w, border, fill, matrix, range)
+    return planes, F, h, w, _warp_rows(coef, (F, 6), "(F,6)"), fill_rgb
 
 
 def warp_staged(row, fmt, x0=0, y0=0):
@@ -693,6 +704,64 @@ def warp_frames(planes, fmt, coef, border="constant", fill=(0, 0, 0), matrix="bt
         _call("pips_frames_warp", DRAW_FORMATS_EX[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], WARP_BORDERS[border], fill_rgb,
               F, h, w, *args, _lib.ptr(coef), _stream())
     return out
+
+
+WARP_FILL_MAX = 16                                                    # include/pips_hip.h: PIPS_WARP_FILL_MAX
+WARP_FILL_NONE = 255                                                  # the source map where no candidate covered
+
+
+def warp_fill_check(planes, fmt, cand, coef, border, fill, matrix, range):
+    """pips_frames_warp_fill's limits on the values, shared by ``warp_frames_fill`` and ``drivers.warp_frames_fill_torch`` -> (planes,
+    Fs, Fd, K, h, w, cand (Fd,K) int32 and coef (Fd,K,6) int32 on their own devices, fill_rgb)"""
+    planes, Fs, h, w = draw_planes(planes, fmt)
+    cand = torch.as_tensor(cand)
+    if cand.dim() != 2 or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+        raise ValueError(f"cand must be integers (Fd,K), not {cand.dtype} {tuple(cand.shape)}")
+    Fd, K = cand.shape
+    if not 1 <= K <= WARP_FILL_MAX:
+        raise ValueError(f"1 to {WARP_FILL_MAX} candidates a frame, not {K}")
+    if cand.numel() and (int(cand.min()) < _INT32[0] or int(cand.max()) > _INT32[1]):
+        raise ValueError("a candidate index does not fit int32")
+    fill_rgb = _warp_values(h, w, border, fill, matrix, range)
+    return planes, Fs, Fd, K, h, w, cand.to(torch.int32), _warp_rows(coef, (Fd, K, 6), "(Fd,K,6)"), fill_rgb
+
+
+def warp_frames_fill(planes, fmt, cand, coef, border="constant", fill=(0, 0, 0), matrix="bt709", range="limited", out=None,
+                     source=None):
+    """pips_frames_warp_fill: ``warp_frames`` with a list of candidates per output frame -- the border of a stabilised frame filled
+    from its neighbours.  ``planes`` are Fs device surfaces of ``fmt``; ``cand`` (Fd,K) integers, ``cand[j][k]`` the source frame of
+    candidate k of output frame j (outside 0..Fs-1, conventionally -1: none), and ``coef`` (Fd,K,6) its row in ``warp_frames``'
+    meaning; both from the host or the device.  Every sample comes from the first candidate in list order whose taps with weight
+    all lie inside the plane, and from candidate 0 under ``border`` / ``fill`` when none does (include/pips_hip.h has the whole
+    rule).  ``out``: Fd surfaces of the source's format and size, allocated when None.  ``source``: True allocates the (Fd,h,w)
+    uint8 map of the list position that supplied each sample of plane 0 (255: none), a tensor is used as given (row and frame
+    strides as pitch and step), None asks for no map.  Returns the list of planes, or ``(planes, source)`` when a map was asked
+    for.  ``out`` and ``source`` may not overlap ``planes`` or each other."""
+    planes, Fs, Fd, K, h, w, cand, coef, fill_rgb = warp_fill_check(planes, fmt, cand, coef, border, fill, matrix, range)
+    assert planes[0].is_cuda, "pips_amd runs on the GPU only (no CPU fallback)"
+    dev = planes[0].device
+    if out is None:
+        out = [torch.empty((Fd,) + tuple(p.shape[1:]), dtype=p.dtype, device=dev) for p in planes]
+    else:
+        out, Fo, ho, wo = draw_planes(out, fmt)
+        if (Fo, ho, wo) != (Fd, h, w) or any(o.device != dev for o in out):
+            raise ValueError(f"out must be {Fd} surfaces of {h} x {w} on the source's device, not {Fo} of {ho} x {wo}")
+    if source is True:
+        source = torch.empty(Fd, h, w, dtype=torch.uint8, device=dev)
+    elif source is False:
+        source = None
+    elif source is not None and (source.dtype != torch.uint8 or tuple(source.shape) != (Fd, h, w) or source.device != dev):
+        raise ValueError(f"source must be uint8 (Fd,h,w) = {(Fd, h, w)} on the surfaces' device, not {source.dtype} {tuple(source.shape)}")
+    if Fd > 0:
+        cand, coef = cand.to(dev).contiguous(), coef.to(dev).contiguous()
+        mpitch, mstep = (0, 0) if source is None else _surface(source, (1,))
+        # (no source frame: every candidate is invalid and no plane of src is read)
+        src_args = draw_surfaces(planes, fmt) if Fs else draw_surfaces(out, fmt)
+        with torch.cuda.device(dev):
+            _call("pips_frames_warp_fill", DRAW_FORMATS_EX[fmt], IMPORT_MATRICES[matrix], IMPORT_RANGES[range], WARP_BORDERS[border],
+                  fill_rgb, Fs, Fd, K, h, w, *src_args, *draw_surfaces(out, fmt), _lib.ptr(cand), _lib.ptr(coef), _lib.ptr(source), mpitch,
+                  mstep, _stream())
+    return out if source is None else (out, source)
 
 
 def point_sample(level0, B, xy):
